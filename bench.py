@@ -13,11 +13,15 @@ neptune.cpp:1512-1529, timed call solver_gurobi_poly.cpp:823-826); the new traje
 Inputs are resident in HBM before the timed region.  `--workload config5`: BASELINE configs[4] instead (256 agents + 100
 obstacles, enable_entangle_check on), 256 / N agents per GPU.
 
-Output: ONE short JSON line on stdout (bench_legs/compact.py: the contract's fields, `roofline`, `cpu_baseline`, a few
-scalar highlights; <= 4 KB — the driver parses the last line of an 8 KB tail).  The full record of every leg — long_run,
-launch_order_off, reference_tolerances, presolve, chain, moving, crossing, single_scene, small_configs, per_agent_api,
-config5 (+ full_rows, chain), per-kernel rooflines, notes — goes to bench_detail.json beside this file (--detail) and, as one
-line, to stderr.  The legs live in bench_legs/ (see its __init__).
+A plain run sets up, warms up, times exactly --steps steps and prints ONE short JSON line on stdout (bench_legs/compact.py):
+the contract's fields (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = wall time of one timed step),
+the configuration and the solver's status counts.  --dump-outputs DIR also writes what the last timed step returned
+(bench_legs/outputs.py).  --full runs everything else as well: the separately reported legs — long_run, launch_order_off,
+reference_tolerances, full_rows, chain, moving, crossing, single_scene, small_configs, per_agent_api, config5 (+ full_rows,
+chain) —, per-kernel times and rooflines, `cpu_baseline` and the one-rank RCCL check; its line (<= 4 KB: the contract's
+fields, `roofline`, `cpu_baseline`, a few scalar highlights) is parsed from the last line of an 8 KB tail, and the full
+record of every leg goes to bench_detail.json beside this file (--detail) and, as one line, to stderr.  The legs live in
+bench_legs/ (see its __init__).
 
 N > 1: the agents of every scene are block-sharded by id across the ranks and the number of scenes grows with N, so every GPU
 does the same number of replans per step at any N: "scaling" is "weak".  The exchange step is one RCCL all-gather per round
@@ -86,8 +90,16 @@ def parse_args(argv=None):
     ap.add_argument("--beam", type=int, default=32)
     ap.add_argument("--safety", action="store_true",
                     help="also run the post-solve safety check + commit (SURVEY §8f rank 1) in every step")
-    ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"), help="where every leg's full record goes ('' = nowhere)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the separately reported legs, the CPU baseline, per-kernel times and rooflines, the one-rank "
+                         "RCCL check, the full record in --detail.  Without it a run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float64; bench_legs/outputs.py)")
+    ap.add_argument("--detail", default=None,
+                    help="where every leg's full record goes ('' = nowhere; default: bench_detail.json beside this file with --full, nowhere without)")
     args = ap.parse_args(argv)
+    if args.detail is None:
+        args.detail = os.path.join(ROOT, "bench_detail.json") if args.full else ""
     c5 = args.workload == "config5"
     if args.agents is None:
         args.agents = 256 if c5 else 64
@@ -115,20 +127,23 @@ def launch_ranks(args):
 
 
 def run_config4(ctx):
-    """the default command: headline + the separately reported legs -> detail record (rank 0) or None"""
+    """the headline; with --full also the separately reported legs -> detail record (rank 0) or None"""
     from bench_legs import chain as chain_legs, config5, cpu, headline, small
     args, world, rank = ctx.args, ctx.world, ctx.rank
-    extra = world == 1 and not args.no_extra_legs and not args.frontend and not args.safety and args.cull_radius is None
+    extra = args.full and world == 1 and not args.no_extra_legs and not args.frontend and not args.safety and args.cull_radius is None
     want_c5 = (extra and not args.no_config5) or args.config5_only
     pool = None
     if want_c5 and rank == 0:
         pool = config5.ScenePool(256, 100, range(args.config5_scenes), ctx.host_cores // 2, cache=os.environ.get("NEP_BENCH_SCENE_CACHE"))
-    ctx.init_process_group(want_one_rank_group=not args.no_process_group and not args.config5_only)
+    ctx.init_process_group(want_one_rank_group=args.full and not args.no_process_group and not args.config5_only)
     if args.config5_only:
         c5 = config5.leg(ctx, pool.wait(), pool.wait_s) if rank == 0 else None
         return {"metric": "backend_replans_per_sec", "config5": c5, "graph_notes": ctx.graph_notes, **{k: c5[k] for k in ("value", "unit")}} if c5 else None
     H = headline.setup(ctx, pool)
     headline.run(ctx, H)
+    ctx.outputs = H.outputs
+    if not args.full:
+        return headline.summary(ctx, H) if rank == 0 else None
     legs = headline.retimed_legs(ctx, H)
     Hc = headline.full_handle_view(ctx, H) if (extra and (H.C == 1 or H.G > 1)) else None
     if Hc is not None and H.G > 1:
@@ -184,15 +199,17 @@ def main():
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args))
-    from bench_legs import compact, config5
+    from bench_legs import compact, config5, outputs
     from bench_legs.context import Ctx
     ctx = Ctx(args)
     if args.workload == "config5":
-        ctx.init_process_group(want_one_rank_group=not args.no_process_group)
+        ctx.init_process_group(want_one_rank_group=args.full and not args.no_process_group)
         detail = config5.workload(ctx)
     else:
         detail = run_config4(ctx)
     ctx.teardown()
+    if ctx.rank == 0 and args.dump_outputs:
+        outputs.write(args.dump_outputs, ctx.outputs)
     if ctx.rank == 0 and detail is not None:
         where = None
         if args.detail:
@@ -202,8 +219,9 @@ def main():
                 where = os.path.relpath(args.detail, ROOT) if args.detail.startswith(ROOT) else args.detail
             except OSError as e:
                 print("[bench] detail file not written: %r" % (e,), file=sys.stderr)
-        print("[bench detail] " + json.dumps(detail), file=sys.stderr)
-        sys.stderr.flush()
+        if args.full:
+            print("[bench detail] " + json.dumps(detail), file=sys.stderr)
+            sys.stderr.flush()
         line = json.dumps(compact.compact_line(detail, where))
         sys.stdout.write(line + "\n")                       # the LAST thing this process prints
         sys.stdout.flush()

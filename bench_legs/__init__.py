@@ -9,5 +9,6 @@ the modules here do the timing.
   small.py     single_scene, BASELINE configs[1] / [2] batched, the per-agent drop-in call
   config5.py   BASELINE configs[4]: the single-GPU legs and the N-GPU workload (`--workload config5`)
   cpu.py       the CPU oracle timed on the host cores (cpu_baseline), the reference's own solvers where a box has them
-  compact.py   the short line (<= 4 KB) the driver parses; everything else goes to bench_detail.json
+  compact.py   the short result line (<= 4 KB); with --full everything else goes to bench_detail.json
+  outputs.py   --dump-outputs: what the last timed step returned, as .npy files
 """

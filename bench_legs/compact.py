@@ -25,7 +25,7 @@ def _short(s, n):
 
 def compact_line(d, detail_path="bench_detail.json"):
     """d: the detail record of rank 0 -> dict for the last stdout line"""
-    out = _pick(d, ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data"), 6)
+    out = _pick(d, ("metric", "value", "unit", "n_gpus", "steps", "timed_steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data"), 6)
     cfg = d.get("config", {})
     out["config"] = {"workload": _short(cfg.get("workload", ""), 240), **_pick(cfg, ("agents", "obstacles", "scenes_per_gpu", "scenes_in_flight", "scene_groups", "replans_per_step", "replans_per_gpu_per_step")),
                      "sharding": _short(cfg.get("sharding", ""), 200)}
@@ -81,7 +81,9 @@ def compact_line(d, detail_path="bench_detail.json"):
     out["launch"] = _short(d.get("launch", ""), 60)
     if d.get("graph_notes"):
         out["graph_notes"] = _short("; ".join(d["graph_notes"]), 200)
-    out["detail"] = detail_path
+    if detail_path:
+        out["detail"] = detail_path
+    out = {k: v for k, v in out.items() if v != {}}          # (a plain run has no kernel_ms, roofline or rccl record)
     # never print a line the driver cannot read: shed the optional parts, largest first
     for drop in ("per_rank", "highlights", "reference_solvers", "scene_digest", "graph_notes"):
         if len(json.dumps(out)) <= LIMIT:

@@ -28,6 +28,24 @@ class _timed:
     def __exit__(self, *a): self.lst.append((self.e0, self.ctx.ev()))
 
 
+def usable_cores():
+    """CPUs this process may use for host work (scene generation pools): its affinity mask, capped by a cgroup CPU quota and by
+    OMP_NUM_THREADS where either is set.  os.cpu_count() counts the whole machine, and a pool sized by it on a share of a large
+    host spends its time on process start-up and contention."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, int(int(quota) / int(period))))
+    except (OSError, ValueError):
+        pass
+    try:
+        n = min(n, int(os.environ.get("OMP_NUM_THREADS", "")))
+    except ValueError:
+        pass
+    return max(1, n)
+
+
 class Ctx:
     """One rank of the bench: device, process group and the timing primitives every leg uses."""
 
@@ -57,10 +75,11 @@ class Ctx:
         self.use_dist = self.world > 1 or "RANK" in os.environ          # launched by torch.distributed.run
         self.own_group = False; self.rccl_torn_down = False              # (plain `python bench.py`: the one-rank group made below)
         self.rccl_note = None
-        self.host_cores = os.cpu_count() or 1
+        self.host_cores = usable_cores()
         self.aux_steps = max(args.aux_steps, args.steps)
         self.ev_on = True
         self.graph_notes = []
+        self.outputs = {}                 # --dump-outputs: the timed path's outputs of its last timed step (bench_legs/outputs.py)
         self.last_wall = 0.0
 
     # ---- process group -------------------------------------------------------------------------------------------------
@@ -205,10 +224,11 @@ class Ctx:
             torch.cuda.synchronize(self.dev)
             return None
 
-    def run_leg(self, step_fn, handles, steps, warm, graph_ok=True, eager_after=40, clear=()):
+    def run_leg(self, step_fn, handles, steps, warm, graph_ok=True, eager_after=40, clear=(), after=None):
         """warm untimed steps, then exactly `steps` steps between barriers (max over ranks), replaying one captured graph
         when possible.  Per-kernel HIP events (handle timing) cannot live inside a graph: with a graph they are taken from
-        `eager_after` host-launched steps after the timed region.  -> (seconds, per-step GPU ms, graph used)"""
+        `eager_after` host-launched steps after the timed region.  after(): called once the timed steps are done, before
+        anything else is launched (the handles still hold the last timed step's results).  -> (seconds, per-step GPU ms, graph used)"""
         for _ in range(warm):
             step_fn()
         self.barrier()
@@ -229,7 +249,9 @@ class Ctx:
         self.barrier()
         self.last_wall = time.perf_counter() - t0
         dt = self.max_over_ranks(self.last_wall)
-        step_ms = np.array([evs[i].elapsed_time(evs[i + 1]) for i in range(steps)])
+        step_ms = np.array([evs[i].elapsed_time(evs[i + 1]) for i in range(len(evs) - 1)])      # one per step run
+        if after is not None:
+            after()
         if g_ is not None and eager_after > 0:
             for b in handles:
                 b.enable_timing(True); b.reset_timing()

@@ -9,7 +9,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from . import account as acc
+from . import account as acc, outputs
 
 
 def setup(ctx, c5=None):
@@ -25,8 +25,9 @@ def setup(ctx, c5=None):
     N, M, S = args.agents, args.obstacles, args.scenes * world
     first_local, n_local = ndist.shard(N, world, rank)
     # each rank generates its share of the seeded scenes (seeds 0..S-1 overall), then they are shared
+    # (every usable core unless the config-5 pool is making its scenes beside this one; the ranks share the host)
     mine = scene.make_scenes(N, M, range(rank * args.scenes, (rank + 1) * args.scenes),
-                             workers=min(args.scenes, max(1, (ctx.host_cores // (4 if c5 is not None and c5.busy() else 2)) // world), 64))
+                             workers=min(args.scenes, max(1, (ctx.host_cores // (4 if c5 is not None and c5.busy() else 1)) // world), 64))
     scene0 = mine[0] if rank == 0 else scene.make_scene(N, M, seed=0)
     if c5 is not None:
         # the config-5 pool has been running beside this one; nothing is timed while host processes are still busy (a first
@@ -275,7 +276,11 @@ def run(ctx, H):
             # ~0.27 ms (found on the config-5 step: 1.55 instead of 1.28 ms with identical kernel times; the presolve's redo
             # counters are now zeroed by a kernel and the step has no memset node): this tears the one-rank group down early
             tdist.destroy_process_group(); ctx.use_dist = False; ctx.rccl_torn_down = True
-    dt, step_ms, graph = ctx.run_leg(H.step, bes, args.steps, 0, graph_ok=H.graph_plain, clear=(H.safety_ev, H.hull_ev, H.gather_ev))
+    H.outputs = {}
+    after = (lambda: H.outputs.update(outputs.snapshot(bes))) if args.dump_outputs else None
+    # per-kernel times from eager steps after the timed region: --full only (the roofline and per-rank figures read them)
+    dt, step_ms, graph = ctx.run_leg(H.step, bes, args.steps, 0, graph_ok=H.graph_plain, eager_after=40 if args.full else 0,
+                                     clear=(H.safety_ev, H.hull_ev, H.gather_ev), after=after)
     H.dt, H.step_ms, H.graph, H.dt_local = dt, step_ms, graph, ctx.last_wall
     H.qp_ms, H.n_launch = be.kernel_time_ms(2)           # per launch of one chunk (chunk 0)
     H.hull_ms, _ = be.kernel_time_ms(0)
@@ -286,7 +291,7 @@ def run(ctx, H):
     for b in bes:
         b.enable_timing(False)
     H.sol = np.concatenate([b.solutions() for b in bes])
-    H.active = acc.active_summary(be) if (H.C == 1 or H.G > 1) else None          # (group 0's handle when the scenes run as groups)
+    H.active = acc.active_summary(be) if args.full and (H.C == 1 or H.G > 1) else None          # (group 0's handle when the scenes run as groups)
     H.solve_us = acc.solve_us_stats(be)
     H.n_states = int(H.sol[0]["n_states"])
     H.value = H.replans_per_step * args.steps / dt
@@ -383,6 +388,48 @@ def per_rank_records(ctx, H):
     return per_rank
 
 
+def summary(ctx, H):
+    """rank 0: the contract fields, the configuration and the solver's status counts of the timed steps — what a plain run reports"""
+    args, world = ctx.args, ctx.world
+    be, sol, N, M, S, C, Sc, n_local = H.be, H.sol, H.N, H.M, H.S, H.C, H.Sc, H.n_local
+    status = sol["stats"]["status"].astype(int)
+    cull_m = be.line_cull()
+    if world == 1:
+        sharding = "one GPU: all %d agents of every scene" % N
+        if H.G > 1:
+            sharding += ("; the %d scenes in flight run as %d groups of %d scenes, pipelined on streams: the groups' geometry halves in turn on one stream, each group's QP half on its own, ordered by events" % (S, H.G, Sc)
+                         if getattr(H, "PIPE", False) else
+                         "; the %d scenes in flight run as %d groups of %d scenes, each group a launch sequence on its own HIP stream, all inside one captured graph per step" % (S, H.G, Sc))
+    elif H.sharded_hulls:
+        sharding = ("agents of every scene block-sharded by id, %d per GPU; per step and scene chunk (%d chunks, pipelined) one all-gather "
+                    "(RCCL, %s) of the interval hulls of the local agents' committed trajectories (%d B per agent and scene)"
+                    % (n_local, C, "native binding on a side stream inside the captured step" if H.native else "torch.distributed", be.hull_block_bytes() // (Sc * n_local)))
+    else:
+        sharding = "agents of every scene block-sharded by id, %d per GPU; per step one all-gather (RCCL) of the committed trajectory records" % n_local
+    return {
+        "metric": "backend_replans_per_sec", "value": H.value, "unit": "replans/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": H.dt / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "%d agents + %d static obstacles, K=8, %d seeded scenes in flight per GPU per step (seeds 0..%d over %d GPU%s); %s"
+                               % (N, M, args.scenes, S - 1, world, "" if world == 1 else "s",
+                                  (("the handle's default solve path: verified line presolve %g m, polish on" % cull_m) if cull_m > 0.0 else
+                                   "line presolve off: every separating-line row through the interior point, polish on")
+                                  + (("; %d scene groups pipelined on streams" % H.G) if getattr(H, "PIPE", False) else ("; %d scene groups on %d HIP streams" % (H.G, H.G) if H.G > 1 else ""))),
+                   "agents": N, "obstacles": M, "scenes_in_flight": S, "scenes_per_gpu": args.scenes,
+                   "replans_per_step": H.replans_per_step, "replans_per_gpu_per_step": S * n_local,
+                   "sharding": sharding, "scene_groups": H.G,
+                   "params": "reference neptune_mtlp_benchmark.yaml (T_span 0.5, num_pol 8, weight 1000, v 2, a 3)"},
+        "solver": {"status_ok": int((status == 0).sum()), "status_relaxed": int((status == 1).sum()),
+                   "status_failed": int((status == 2).sum()), "ipm_iters_mean": float(sol["stats"]["iters"].mean()),
+                   "lines_mean": float(sol["stats"]["n_lines"].mean()), "lp_failed": int(sol["stats"]["n_lp_failed"].sum()),
+                   "rows_solved_mean": float(sol["stats"]["n_rows"].mean())},
+        "step_ms": acc.step_quantiles(H.step_ms), "timed_steps": len(H.step_ms),
+        "launch": ("one captured HIP graph per step, replayed" + (" (per-kernel events from %d eager steps after the timed region)" % min(args.steps, 40) if args.full else "")
+                   if H.graph is not None else ("host launches: two enqueues per scene group and step (nep_batch_replan_lines / _solve) on the groups' streams"
+                                                if getattr(H, "PIPE", False) else ("; ".join(ctx.graph_notes) or "host launches"))),
+    }
+
+
 def record(ctx, H):
     """rank 0: the headline's part of the detail record (contract fields, solver statistics, roofline)"""
     args, world = ctx.args, ctx.world
@@ -437,46 +484,21 @@ def record(ctx, H):
             fp64["executed_achieved"] = None; fp64["executed_frac"] = None
         fp64["executed_mfma_share"] = ex_f["mfma_flops_per_launch"] / ex_f["flops_per_launch"] if ex_f["flops_per_launch"] > 0 else None
         fp64["executed_source"] = ex_f["source"]
-    if world == 1:
-        sharding = "one GPU: all %d agents of every scene" % N
-        if H.G > 1:
-            sharding += ("; the %d scenes in flight run as %d groups of %d scenes, pipelined on streams: the groups' geometry halves in turn on one stream, each group's QP half on its own, ordered by events" % (S, H.G, Sc)
-                         if getattr(H, "PIPE", False) else
-                         "; the %d scenes in flight run as %d groups of %d scenes, each group a launch sequence on its own HIP stream, all inside one captured graph per step" % (S, H.G, Sc))
-    elif H.sharded_hulls:
-        sharding = ("agents of every scene block-sharded by id, %d per GPU; per step and scene chunk (%d chunks, pipelined) one all-gather "
-                    "(RCCL, %s) of the interval hulls of the local agents' committed trajectories (%d B per agent and scene)"
-                    % (n_local, C, "native binding on a side stream inside the captured step" if H.native else "torch.distributed", be.hull_block_bytes() // (Sc * n_local)))
-    else:
-        sharding = "agents of every scene block-sharded by id, %d per GPU; per step one all-gather (RCCL) of the committed trajectory records" % n_local
     from neptune_amd import abi
     fe_res = H.d_fe_res.cpu().numpy().view(abi.FE_RESULT_DTYPE) if args.frontend else None
-    return {
-        "metric": "backend_replans_per_sec", "value": H.value, "unit": "replans/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": H.dt / args.steps * 1e3,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "%d agents + %d static obstacles, K=8, %d seeded scenes in flight per GPU per step (seeds 0..%d over %d GPU%s); %s"
-                               % (N, M, args.scenes, S - 1, world, "" if world == 1 else "s",
-                                  (("the handle's default solve path: verified line presolve %g m, polish on" % cull_m) if cull_m > 0.0 else
-                                   "line presolve off: every separating-line row through the interior point, polish on")
-                                  + (("; %d scene groups pipelined on streams" % H.G) if getattr(H, "PIPE", False) else ("; %d scene groups on %d HIP streams" % (H.G, H.G) if H.G > 1 else ""))),
-                   "agents": N, "obstacles": M, "scenes_in_flight": S, "scenes_per_gpu": args.scenes,
-                   "replans_per_step": H.replans_per_step, "replans_per_gpu_per_step": S * n_local,
-                   "sharding": sharding, "scene_groups": H.G,
-                   "params": "reference neptune_mtlp_benchmark.yaml (T_span 0.5, num_pol 8, weight 1000, v 2, a 3)"},
-        "solver": {"status_ok": int((status == 0).sum()), "status_relaxed": int((status == 1).sum()),
-                   "status_failed": int((status == 2).sum()), "ipm_iters_mean": float(iters.mean()),
-                   "ipm_iters_quantiles": {"p50": float(np.percentile(iters, 50)), "p90": float(np.percentile(iters, 90)),
-                                           "p99": float(np.percentile(iters, 99)), "max": int(iters.max())},
-                   "ipm_iters_mean_by_status": {name: (float(iters[status == k].mean()) if (status == k).any() else None)
-                                                for k, name in ((0, "ok"), (1, "relaxed"), (2, "failed"))},
-                   "lines_mean": L_mean, "lp_failed": int(sol["stats"]["n_lp_failed"].sum()),
-                   "rows_solved_mean": float(sol["stats"]["n_rows"].mean()), "line_cull_radius_m": be.line_cull(), "solved_without_iteration": int((iters == 0).sum()),
-                   "presolve_redo_last_step": be.redo_count(), "polish_listed_certified_last_step": list(be.polish_count()),
-                   "lp_failed_note": "separator LPs without a separating line: the constraint is skipped as in the reference "
-                                     "(solver_gurobi_poly.cpp:483-494).  Round 0 has none (scenes are sampled so that every LP is feasible); "
-                                     "later rounds replan the same guesses against the others' optimised trajectories, which may cross them",
-                   "active_rows": H.active},
+    out = summary(ctx, H)
+    out["solver"].update({
+        "ipm_iters_quantiles": {"p50": float(np.percentile(iters, 50)), "p90": float(np.percentile(iters, 90)),
+                                "p99": float(np.percentile(iters, 99)), "max": int(iters.max())},
+        "ipm_iters_mean_by_status": {name: (float(iters[status == k].mean()) if (status == k).any() else None)
+                                     for k, name in ((0, "ok"), (1, "relaxed"), (2, "failed"))},
+        "line_cull_radius_m": be.line_cull(), "solved_without_iteration": int((iters == 0).sum()),
+        "presolve_redo_last_step": be.redo_count(), "polish_listed_certified_last_step": list(be.polish_count()),
+        "lp_failed_note": "separator LPs without a separating line: the constraint is skipped as in the reference "
+                          "(solver_gurobi_poly.cpp:483-494).  Round 0 has none (scenes are sampled so that every LP is feasible); "
+                          "later rounds replan the same guesses against the others' optimised trajectories, which may cross them",
+        "active_rows": H.active})
+    out.update({
         # Per-replan latency by SURVEY 8(d)'s definition of one replan (setters + separator loop + QP solve + generatePwpOut).  In a batch
         # every replan completes with its launch sequence, so a batched replan's latency IS the sequence's duration (hull + lines + QP
         # + polish of replans_per_launch replans: batch_sequence_ms); bench.py replaces these two by the blocking six-call drop-in
@@ -488,12 +510,8 @@ def record(ctx, H):
         "qp_workgroup_us": dict(H.solve_us, note="device time of each replan's interior-point workgroup alone (setup + interior point + outputs, nep_stats.solve_us); "
                                                  "hulls (%.3f ms per launch) and separating lines (%.3f ms) are shared by the batch" % (hull_ms, sep_ms)),
         "batch_sequence_ms": seq_ms + (hull_ms if H.sharded_hulls else 0.0),
-        "step_ms": acc.step_quantiles(H.step_ms),
         "kernel_ms": {"hull": hull_ms, "separator": sep_ms, "qp": qp_ms, "sequence": seq_ms, "exchange_wait": ctx.mean_ms(H.gather_ev),
                       "launches": H.n_launch, "launches_per_step": C},
-        "launch": ("one captured HIP graph per step, replayed (per-kernel events from %d eager steps after the timed region)" % min(args.steps, 40)
-                   if H.graph is not None else ("host launches: two enqueues per scene group and step (nep_batch_replan_lines / _solve) on the groups' streams"
-                                                if getattr(H, "PIPE", False) else ("; ".join(ctx.graph_notes) or "host launches"))),
         "frontend": ({"ms": ctx.mean_ms(H.fe_ev), "beam_width": args.beam,
                       "status_goal_reached": int((fe_res["status"] == 1).sum()), "status_no_solution": int((fe_res["status"] == 3).sum()),
                       "children_mean": float(fe_res["n_children"].mean())} if args.frontend else None),
@@ -520,7 +538,8 @@ def record(ctx, H):
         "rccl": dict(rccl_record(ctx, H.nranks, H.native, H.rccl_one_rank_ok), **({"note": H.exchange_note} if H.exchange_note else {})),
         "roofline_fp64": fp64,
         "reference_budget": "reference TimeLimit 0.05 s/solve, replan timer 20 Hz/agent => <= %d replans/s for %d agents" % (20 * N, N),
-    }
+    })
+    return out
 
 
 def rccl_record(ctx, nranks, native, one_rank_ok=None):

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -16,9 +17,14 @@ REQUIRED = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
             "p50_solve_ms", "p99_solve_ms", "kernel_ms", "roofline", "rccl")
 
 
-def _run(extra, env_extra, tmp_path=None, merged=False):
+# what the line of a plain run (no --full) holds
+PLAIN = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "dtype", "data", "config", "solver")
+
+
+def _run(extra, env_extra, tmp_path=None, merged=False, full=True):
     """runs bench.py from a plain shell -> (the parsed LAST line, the detail record or None).  merged: stderr into stdout, as a driver
-    that keeps one tail of both streams sees it — the JSON line must still be the last line."""
+    that keeps one tail of both streams sees it — the JSON line must still be the last line.  full: the command has --full (the
+    line carries the per-kernel and roofline records)."""
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     env.update(env_extra)
@@ -33,17 +39,18 @@ def _run(extra, env_extra, tmp_path=None, merged=False):
     # the driver keeps an 8 KB tail and parses its last line (round 4's 27 KB line came back as parsed: null)
     assert len(last) < 6000, len(last)
     out = json.loads(last)
-    for k in REQUIRED:
+    for k in (REQUIRED if full else PLAIN):
         assert k in out, k
-    for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic"):
-        assert k in out["roofline"], k
+    if full:
+        for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic"):
+            assert k in out["roofline"], k
     return out, (json.load(open(detail)) if detail and os.path.exists(detail) else None)
 
 
 @pytest.mark.gpu
 def test_plain_shell_gpus_2_launches_its_own_ranks():
     out, _ = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--scenes", "4", "--agents", "16", "--obstacles", "8",
-                   "--no-extra-legs", "--no-cpu-baseline"], {"NEP_BENCH_ONE_DEVICE": "1"})
+                   "--no-extra-legs", "--no-cpu-baseline", "--full"], {"NEP_BENCH_ONE_DEVICE": "1"})
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["steps"] == 3
     assert out["config"]["replans_per_gpu_per_step"] == 4 * 2 * 8          # scenes per GPU x world x local agents
     assert out["value"] > 0 and out["solver"]["status_failed"] == 0
@@ -54,11 +61,11 @@ def test_plain_shell_gpus_2_launches_its_own_ranks():
 
 @pytest.mark.gpu
 def test_the_drivers_command_prints_one_short_parsable_line(tmp_path):
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` — the driver's command, every leg on but short (fewer scenes in flight, a
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --full` — every leg on but short (fewer scenes in flight, a
     handful of steps per extra leg) — with stderr merged into stdout: the LAST line of everything the process prints must be the JSON
     line, below 6 000 bytes, with the contract's fields, `roofline` and `cpu_baseline`; every leg's full record is in the detail file.
     The timed call this measures: solver_gurobi_poly.cpp:823-826."""
-    out, detail = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--scenes", "16", "--aux-steps", "20", "--config5-scenes", "2"], {},
+    out, detail = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--scenes", "16", "--aux-steps", "20", "--config5-scenes", "2", "--full"], {},
                        tmp_path, merged=True)
     assert out["n_gpus"] == 1 and out["steps"] == 20 and out["warmup"] == 5 and out["dtype"] == "f64" and out["vs_baseline"] is None
     assert out["value"] > 0 and abs(out["value"] - 64 * 16 * 20 / (out["ms_per_step"] * 20e-3)) < 1e-3 * out["value"]
@@ -82,12 +89,42 @@ def test_the_drivers_command_prints_one_short_parsable_line(tmp_path):
 
 
 @pytest.mark.gpu
+def test_plain_run_times_the_headline_only_and_dumps_the_same_outputs_twice(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the headline alone (no extra legs, no CPU baseline, no per-kernel or
+    roofline records, no detail file) over exactly K timed steps (`timed_steps`: the steps the timed loop ran, counted by its per-step
+    events); with --dump-outputs the last timed step's outputs as float64 .npy files well below 64 MB, whose statuses are the
+    line's — and two runs with the same arguments write the same arrays (seeded inputs, deterministic kernels)."""
+    args = ["--gpus", "1", "--steps", "7", "--warmup", "2", "--scenes", "8"]
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("outputs%d" % k)
+        out, detail = _run(args + ["--dump-outputs", str(d)], {}, full=False)
+        assert detail is None and out["steps"] == 7 and out["timed_steps"] == 7 and out["warmup"] == 2 and out["n_gpus"] == 1
+        assert out["metric"] == "backend_replans_per_sec" and out["unit"] == "replans/s" and out["higher_is_better"] is True and out["dtype"] == "f64"
+        assert out["value"] > 0 and abs(out["value"] - 64 * 8 * 7 / (out["ms_per_step"] * 7e-3)) < 1e-3 * out["value"]
+        for k_ in ("cpu_baseline", "highlights", "roofline", "kernel_ms", "rccl", "per_rank"):
+            assert k_ not in out, k_
+        files = sorted(os.listdir(d))
+        assert {"coeff.npy", "times.npy", "objective.npy", "status.npy", "states.npy", "states_slot.npy"} <= set(files), files
+        arrs = {f: np.load(d / f) for f in files}
+        assert all(a.dtype == np.float64 for a in arrs.values())
+        assert sum(os.path.getsize(d / f) for f in files) < 64 << 20
+        assert np.array_equal(arrs["states_slot.npy"], np.arange(64 * 8)) and len(arrs["coeff.npy"]) == 64 * 8
+        st = arrs["status.npy"]
+        assert (st == 0).sum() == out["solver"]["status_ok"] and (st == 2).sum() == out["solver"]["status_failed"]
+        assert np.isfinite(arrs["coeff.npy"]).all() and np.abs(arrs["coeff.npy"]).max() > 0
+        dumps.append(arrs)
+    for f, a in dumps[0].items():
+        assert np.array_equal(a, dumps[1][f]), f
+
+
+@pytest.mark.gpu
 def test_config5_workload_two_ranks_equal_one_rank(tmp_path):
     """`--workload config5` (BASELINE configs[4]: entangle rows on, agents block-sharded by id, hull blocks with the tethers' samples and
     bend points all-gathered per round) launched from a plain shell with two ranks on the one device, against the same command with one
     rank: the replans of the scenes both runs hold are byte-identical after the warm-up rounds (sizes cut so that scene generation takes
     seconds; the exchange being replaced: neptune_ros.cpp:379-480)."""
-    common = ["--workload", "config5", "--agents", "32", "--obstacles", "12", "--scenes", "2", "--steps", "3", "--warmup", "2", "--no-cpu-baseline"]
+    common = ["--workload", "config5", "--agents", "32", "--obstacles", "12", "--scenes", "2", "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--full"]
     one, d1 = _run(["--gpus", "1"] + common, {}, tmp_path)
     two, d2 = _run(["--gpus", "2"] + common, {"NEP_BENCH_ONE_DEVICE": "1"}, tmp_path)
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2 and two["scaling"] == "weak"
@@ -96,6 +133,11 @@ def test_config5_workload_two_ranks_equal_one_rank(tmp_path):
     assert [r["rank"] for r in two["per_rank"]] == [0, 1]
     assert len(d1["scene_digest"]) == 2 and d2["scene_digest"][:2] == d1["scene_digest"]          # scenes 0, 1: in both runs
     assert d1["solver"]["lines_mean"] > 0 and one["value"] > 0 and two["value"] > 0
+    # without --full no per-kernel times are taken: the line carries no kernel_ms / roofline / solve-latency figures (zeros would pass for measurements)
+    plain, _ = _run(["--gpus", "1"] + common[:-1], {}, full=False)
+    assert plain["timed_steps"] == 3 and plain["value"] > 0 and plain["solver"]["status_ok"] > 0
+    for k in ("kernel_ms", "roofline", "p50_solve_ms", "p99_solve_ms", "cpu_baseline", "per_rank"):
+        assert k not in plain, k
 
 
 def test_gpus_n_without_a_gpu_fails_loudly():
