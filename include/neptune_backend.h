@@ -43,6 +43,7 @@ extern "C" {
 #define NEP_OK 0            /* first solve succeeded                      -> optimize()==true  */
 #define NEP_RELAXED 1       /* first failed, relaxed re-solve succeeded   -> optimize()==true  */
 #define NEP_FAILED 2        /* both failed: output == initial guess       -> optimize()==false */
+#define NEP_SKIPPED 3       /* batched handle: slot not in the active set this round — not solved (nep_batch_set_active) */
 
 /* error codes (< 0) */
 #define NEP_E_ARG (-1)
@@ -365,6 +366,29 @@ int64_t nep_batch_ent_bytes(const nep_batch_t* h);
 int nep_batch_safety_commit(nep_batch_t* h, const nep_traj_rec* d_prev, const nep_traj_rec* d_new,
                             const nep_guess* d_guess, nep_traj_rec* d_final, int32_t* d_accept,
                             void* stream);
+/* Active set of the following batched calls — the batched form of "this agent's replanCB timer fired" (neptune_ros.cpp:185,482;
+ * an agent that has arrived stops replanning, neptune.cpp:1701-1711).  d_active: device, [n_scenes][N] int32 by GLOBAL agent index
+ * (the layout of nep_batch_safety_commit); nonzero = the agent replans.  A handle reads entries [first_local, first_local + n_local)
+ * of each scene for its own slots and all N for the safety pass.  The pointer is kept, not copied; kernels read the contents when they
+ * RUN, so a captured graph replays with whatever the buffer holds at replay time.  The buffer must outlive every enqueued call and
+ * every graph that captured one.  NULL (the default) = every agent: the launch sequence and the results of a handle without a mask.
+ * Honoured by nep_batch_frontend / _ent / _hulls / _ent_hulls, nep_batch_replan / _lines / _solve / _hulls and
+ * nep_batch_safety_commit / _ent; nep_batch_hulls and nep_batch_next_starts build every record's hulls / starts as before.
+ * An INACTIVE slot:
+ *   - no input of it is read except its t_start (nep_guess / nep_fe_start): a scene's hull time grid is the t_start of the scene's
+ *     first local slot, so an inactive slot must still carry the round's clock.  Its guess coefficients, K, d_ent block and (safety
+ *     pass) d_new record are never read and raise no capacity flag;
+ *   - front end: result status NEP_FE_SKIPPED, every other result field zero; the guess gets K = 0 and t_start from the start record,
+ *     no other guess field is written;
+ *   - replan: d_solution stats.status NEP_SKIPPED, K = 0, n_states = 0, every other stats field zero; d_states rows untouched;
+ *     d_commit = the agent's previous record by the rule of a NEP_FAILED slot (left as passed under nep_batch_replan_hulls);
+ *   - safety commit: its record this round is its d_prev record, accepted before the id-ordered pass (d_final = d_prev,
+ *     d_accept = 1); an active agent is turned down when it conflicts with an inactive agent's held record (either direction,
+ *     any id) or with an accepted active agent of lower id; the conflict matrix is that of those records.
+ * Active slots come out bit-identical to a call without the mask.  Setting or clearing the mask (not its contents) changes the launch
+ * sequence of the calls that follow: a graph keeps the sequence it was captured with.                                       */
+int nep_batch_set_active(nep_batch_t* h, const int32_t* d_active);
+
 /* Test hook: the conflict matrix [N][N] of one scene from the last safety check. */
 /* Presolve of the separating-line rows (off by default, radius = 0).  With radius > 0 (metres) a line whose
  * boundary lies farther than `radius` from all four control points of the guess's segment is left out of the

@@ -95,6 +95,9 @@ int nep_batch_set_hull_kernel(nep_batch_t* h, int32_t mode);
 
 /* Test hook: the conflict matrix [N][N] of one scene as the last nep_batch_safety_commit saw it. */
 int nep_batch_debug_conflicts(nep_batch_t* h, int32_t scene, uint8_t* conflict_out);
+/* The same for the new-against-previous matrix of a check with nep_batch_set_safety_check_prev on: [a][j] = agent a's new
+ * trajectory hits the hulls of agent j's previous record. */
+int nep_batch_debug_conflicts_prev(nep_batch_t* h, int32_t scene, uint8_t* conflict_out);
 
 /* Average device time (ms) of the dominant kernel over the launches since the last call,
  * measured with HIP events on the launch stream; *n_launch = launches averaged.               */

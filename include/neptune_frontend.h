@@ -60,6 +60,7 @@ extern "C" {
 #define NEP_FE_DEPTH_REACHED 0    /* (RUNTIME_REACHED there): best node of the last depth         */
 #define NEP_FE_EMPTY 2            /* the beam died out: best node of the last non-empty depth     */
 #define NEP_FE_NO_SOLUTION 3      /* no feasible first segment: K = 0, nothing to optimise        */
+#define NEP_FE_SKIPPED 4          /* slot not in the active set (nep_batch_set_active): no search  */
 
 /* setMaxValuesAndSamples / setXYZMinMaxAndRa / setBias / setGoalSize / setTetherLength
  * (call sites neptune.cpp:92-97); bounds, bases and T_span come from the batch handle.          */

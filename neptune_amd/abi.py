@@ -15,6 +15,8 @@ NEP_MAX_BEND = 8
 NEP_STATE_DOUBLES = 12
 
 NEP_OK, NEP_RELAXED, NEP_FAILED = 0, 1, 2
+NEP_SKIPPED = 3          # nep_stats.status of a slot outside the active set (nep_batch_set_active)
+NEP_FE_SKIPPED = 4       # nep_fe_result.status of a slot outside the active set
 
 
 class nep_pwp(C.Structure):

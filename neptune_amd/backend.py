@@ -367,6 +367,18 @@ class BatchBackend:
         check(lib().nep_batch_safety_commit(self._h, d_prev.data_ptr(), d_new.data_ptr(), d_guess.data_ptr(), d_final.data_ptr(),
                                             d_accept.data_ptr() if d_accept is not None else None, st.cuda_stream))
 
+    def set_active(self, mask):
+        """Active set of the following front-end, replan and safety calls (nep_batch_set_active): `mask` is a torch int32 device
+        tensor [n_scenes, N] by global agent index, nonzero = the agent replans; None = every agent.  The handle reads the tensor's
+        contents when its kernels run (a captured graph replays with what it holds then); a reference is kept here so that it
+        outlives them."""
+        torch = self.torch
+        if mask is not None:
+            if mask.dtype != torch.int32 or mask.device != self.device or tuple(mask.shape) != (self.n_scenes, self.N) or not mask.is_contiguous():
+                raise ValueError("the active mask is a contiguous int32 tensor [n_scenes, N] on the handle's device")
+        check(lib().nep_batch_set_active(self._h, mask.data_ptr() if mask is not None else None))
+        self._active = mask
+
     def set_scene_statics(self, scene, statics):
         """scene `scene` gets its own static obstacles (same count as the handle's set; nep_batch_set_scene_statics)"""
         soff, sxy = _csr(statics)
@@ -491,6 +503,12 @@ class BatchBackend:
     def debug_conflicts(self, scene=0):
         out = np.zeros((self.N, self.N), dtype=np.uint8)
         check(lib().nep_batch_debug_conflicts(self._h, scene, out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    def debug_conflicts_prev(self, scene=0):
+        """new-against-previous conflict matrix of the last safety check with set_safety_check_prev on"""
+        out = np.zeros((self.N, self.N), dtype=np.uint8)
+        check(lib().nep_batch_debug_conflicts_prev(self._h, scene, out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out
 
     def solutions(self, timing=False):

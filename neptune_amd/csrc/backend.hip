@@ -118,6 +118,9 @@ struct Engine {
   DevBuf<double> d_fe_box;          // boxes of the front end's obstacles, made before every search launch
   DevBuf<int> d_fe_order, d_fe_order_key; DevBuf<float> d_fe_us; bool fe_history = false, fe_lpt = true;      // the same for the front end's searches (frontend_kernel)
   DevBuf<int> d_order, d_order_key; bool have_history = false, lpt = true, last_ordered = false;   // QP workgroups launched longest-expected-first (order_kernel)
+  const int* active = nullptr;       // the active set (nep_batch_set_active): device [scenes][N], or null
+  DevBuf<int> d_act, d_fe_act;       // [slots + 1] compacted active slots + count (active_list_kernel): the QP launches', the front end's
+  DevBuf<nep_traj_rec> d_safety_recs;      // [scenes][N] the records an active-set safety pass judges (select_records_kernel)
   bool use_reg = false;        // the QP runs as qp_reg_kernel (row state in registers, four workgroups per CU)
   double clock_hz = 1e8;       // wall_clock64() rate of the handle's device (set_clock)
   // (the short-step give-up rule's two numbers: run-time values for A/B, nep_*_debug_set_option "corr_from" / "corr_max"; never read from the environment)
@@ -271,6 +274,7 @@ struct Engine {
     ps.presolved = nullptr;      // (set by run() for a launch sequence in which qp_presolve_kernel goes first)
     ps.flags = d_flags.p;
     ps.fe_box = d_fe_box.p;
+    ps.active = active; ps.fe_count = nullptr;
     // the polish pass finishes what the register kernel leaves.  Under the presolve only on request (nep_batch_set_polish(h, 2): on the
     // near lines, and a certified point goes through the presolve's verification of the parked lines and the skipped LPs again —
     // polish_slot): a pass over a handful of slots is 0.03-0.06 ms, 8 % of a presolved step
@@ -418,6 +422,12 @@ struct Engine {
       if (!fused_order) launch_qp_order(slots, d_order_key.p, d_order.p, st, ps.polish_count);      // (zeroes the polish pass's counters on its way; fused_order: the hull launch has done both)
       ps.order = d_order.p; last_ordered = true;
     } else if (ps.polish_count && !(use_reg && slots == 1)) launch_qp_polish_zero(ps.polish_count, st);      // (a one-workgroup launch — the per-agent handle — sets the counters itself: qp_reg_kernel's last lines)
+    if (ps.active) {      // an active set: the QP launches run over the list of active slots (in the launch order made above), the inactive slots' outputs are written apart
+      if (int e = d_act.ensure((size_t)slots + 1)) return e;
+      launch_active_list(slots, sp, ps.active, ps.order, d_act.p, ps.polish_count, st);      // (zeroes the polish counters as well: a one-workgroup launch whose slot is inactive does not)
+      ps.order = d_act.p; ps.order_count = d_act.p + slots;
+      launch_skipped_replan(slots, sp, ps, st);
+    }
     // the presolve's zero-iteration certificate as a kernel of its own, one wave per replan: the replans it finishes (nine in ten of the
     // bench's scenes) cost the interior-point launch an immediate return (qp_presolve_kernel.hip)
     if (use_reg && presolve_kernel && ps.line_far != nullptr && !ps.lines_override && d_presolved.n >= (size_t)slots) {
@@ -431,7 +441,7 @@ struct Engine {
       // list is empty nearly always) get every LP solved and every row through the interior point
       launch_separator_redo(slots, sp, ps, st);
       ProblemSet pr = ps;
-      pr.line_far = nullptr; pr.line_skip = nullptr; pr.order = d_redo_list.p; pr.order_count = d_redo_count.p;
+      pr.line_far = nullptr; pr.line_skip = nullptr; pr.order = d_redo_list.p; pr.order_count = d_redo_count.p;      // (lists active slots only: no other slot ran)
       pr.scratch_by_block = ps.scratch_chunks > 0 ? 1 : 0;
       launch_qp_reg(slots, sp, pr, d_tables.p, sc, lds_bytes, st);
     }
@@ -443,7 +453,7 @@ struct Engine {
   }
   void release() {
     d_tables.release(); d_sched_n.release(); d_sched_seg.release(); d_sched_dt.release(); d_pb.release(); d_static_xy.release();
-    d_static_nv.release(); d_static_el.release(); d_hull_xy.release(); d_hull0_xy.release(); d_bend_xy.release(); d_line_nd.release(); d_row_scratch.release(); d_order.release(); d_order_key.release(); d_fe_order.release(); d_fe_order_key.release(); d_fe_us.release(); d_fe_box.release();
+    d_static_nv.release(); d_static_el.release(); d_hull_xy.release(); d_hull0_xy.release(); d_bend_xy.release(); d_line_nd.release(); d_row_scratch.release(); d_order.release(); d_order_key.release(); d_fe_order.release(); d_fe_order_key.release(); d_act.release(); d_fe_act.release(); d_safety_recs.release(); d_fe_us.release(); d_fe_box.release();
     d_sampled.release(); d_srep.release(); d_slong.release(); d_present.release(); d_entangles.release(); d_fe_nodes.release(); d_fe_work.release(); d_fe_saved.release(); d_fe_arc.release(); d_fe_packed.release(); d_fe_big.release(); d_fe_big_beta.release(); d_fe_stf.release(); d_fe_stvox.release(); d_fe_xpool.release(); d_fe_big_count.release(); d_fe_big_check.release(); d_fe_big_check_count.release();
     d_presolved.release(); d_line_skip.release(); d_redo_list.release(); d_redo_count.release(); d_polish_z.release(); d_polish_flag.release(); d_polish_list.release(); d_polish_count.release(); d_flags.release(); d_conflict.release(); d_conflict_prev.release(); d_hull_nv.release(); d_hull0_nv.release(); d_bend_n.release(); d_line_cnt.release(); d_line_far.release(); d_lp_stats.release();
     for (auto e : ev) hipEventDestroy(e);
@@ -1093,7 +1103,7 @@ int nep_batch_frontend(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_traj_rec
   E.fill(ps);
   h->fe_committed = d_committed;
   launch_hulls_ts(d_committed, h->cfg.n_scenes, h->cfg.num_agents, &d_start->t_start, (long)sizeof(nep_fe_start), E.sp, ps, (hipStream_t)stream);
-  launch_frontend(h->slots, E.sp, ps, *cfg, d_start, d_guess, d_result, nullptr, (hipStream_t)stream, E.lpt ? E.d_fe_order.p : nullptr, E.fe_history);
+  launch_frontend(h->slots, E.sp, ps, *cfg, d_start, d_guess, d_result, nullptr, (hipStream_t)stream, E.lpt ? E.d_fe_order.p : nullptr, E.fe_history, E.d_fe_act.p);
   E.fe_history = true;
   HIPCHK(hipGetLastError());
   return 0;
@@ -1114,9 +1124,21 @@ int nep_batch_frontend_hulls(nep_batch_t* h, const nep_fe_cfg* cfg, const void* 
   ps.hull_pb = h->cfg.n_local; ps.hull_bstride = (long)b.bytes;
   ps.hull_pb_magic = (h->cfg.n_local > 0 && h->cfg.num_agents < 65536) ? (1ull << 32) / (unsigned long long)h->cfg.n_local + 1ull : 0ull;
   h->fe_committed = nullptr;
-  launch_frontend(h->slots, E.sp, ps, *cfg, d_start, d_guess, d_result, nullptr, (hipStream_t)stream, E.lpt ? E.d_fe_order.p : nullptr, E.fe_history);
+  launch_frontend(h->slots, E.sp, ps, *cfg, d_start, d_guess, d_result, nullptr, (hipStream_t)stream, E.lpt ? E.d_fe_order.p : nullptr, E.fe_history, E.d_fe_act.p);
   E.fe_history = true;
   HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int nep_batch_set_active(nep_batch_t* h, const int32_t* d_active) {
+  if (!h) return fail(NEP_E_ARG, "null handle");
+  Engine& E = h->eng;
+  if (d_active) {
+    if (int e = E.d_act.ensure((size_t)h->slots + 1)) return e;
+    if (int e = E.d_fe_act.ensure((size_t)h->slots + 1)) return e;
+    if (int e = E.d_safety_recs.ensure((size_t)h->cfg.n_scenes * h->cfg.num_agents)) return e;
+  }
+  E.active = d_active;
   return 0;
 }
 
@@ -1131,7 +1153,11 @@ int nep_batch_safety_commit(nep_batch_t* h, const nep_traj_rec* d_prev, const ne
   E.fill(ps);
   ps.guess = d_guess;
   if (E.safety_check_prev) { if (int e = E.d_conflict_prev.ensure((size_t)h->cfg.n_scenes * N * N)) return e; }
-  launch_safety(d_prev, d_new, h->cfg.n_scenes, N, E.sp, ps, E.d_conflict.p, E.safety_check_prev ? E.d_conflict_prev.p : nullptr, nullptr, d_final, d_accept, (hipStream_t)stream);
+  if (E.active) {      // an active set: an inactive agent's record this round is its previous one (d_new of it is not read)
+    launch_select_records(h->cfg.n_scenes, N, E.active, d_prev, d_new, E.d_safety_recs.p, (hipStream_t)stream);
+    d_new = E.d_safety_recs.p;
+  }
+  launch_safety(d_prev, d_new, h->cfg.n_scenes, N, E.sp, ps, E.d_conflict.p, E.safety_check_prev ? E.d_conflict_prev.p : nullptr, nullptr, d_final, d_accept, (hipStream_t)stream, E.active);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1250,7 +1276,7 @@ int nep_batch_frontend_ent(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_traj
   if (int e = ent_prepare(h, cfg->ent_samples, cfg->beam_width, d_committed, &d_start->t_start, (long)sizeof(nep_fe_start) * E.sp.n_local, ea, (hipStream_t)stream)) return e;
   ea.init = d_ent_init; ea.case_out = d_case_out;
   if (int e = fe_ent_scratch(h, *cfg, ea)) return e;
-  launch_frontend(h->slots, E.sp, ps, *cfg, d_start, d_guess, d_result, &ea, (hipStream_t)stream, E.lpt ? E.d_fe_order.p : nullptr, E.fe_history);
+  launch_frontend(h->slots, E.sp, ps, *cfg, d_start, d_guess, d_result, &ea, (hipStream_t)stream, E.lpt ? E.d_fe_order.p : nullptr, E.fe_history, E.d_fe_act.p);
   E.fe_history = true;
   HIPCHK(hipGetLastError());
   return 0;
@@ -1282,7 +1308,7 @@ int nep_batch_frontend_ent_hulls(nep_batch_t* h, const nep_fe_cfg* cfg, const vo
   ea.srep = E.d_srep.p; ea.slong = E.d_slong.p; ea.nodes = E.d_fe_nodes.p; ea.work = E.d_fe_work.p; ea.ns = h->ent_ns;
   ea.init = d_ent_init; ea.case_out = d_case_out;
   if (int e = fe_ent_scratch(h, *cfg, ea)) return e;
-  launch_frontend(h->slots, E.sp, ps, *cfg, d_start, d_guess, d_result, &ea, (hipStream_t)stream, E.lpt ? E.d_fe_order.p : nullptr, E.fe_history);
+  launch_frontend(h->slots, E.sp, ps, *cfg, d_start, d_guess, d_result, &ea, (hipStream_t)stream, E.lpt ? E.d_fe_order.p : nullptr, E.fe_history, E.d_fe_act.p);
   E.fe_history = true;
   HIPCHK(hipGetLastError());
   return 0;
@@ -1302,6 +1328,10 @@ int nep_batch_safety_commit_ent(nep_batch_t* h, const nep_traj_rec* d_prev, cons
   E.fill(ps);
   ps.guess = d_guess;
   if (E.safety_check_prev) { if (int e = E.d_conflict_prev.ensure((size_t)h->cfg.n_scenes * N * N)) return e; }
+  if (E.active) {      // an active set: an inactive agent's record this round is its previous one (d_new of it is not read)
+    launch_select_records(h->cfg.n_scenes, N, E.active, d_prev, d_new, E.d_safety_recs.p, (hipStream_t)stream);
+    d_new = E.d_safety_recs.p;
+  }
   // everybody's NEW trajectory counts as received while optimising: their samples and bend points feed the re-check
   FeEntArgs ea{};
   if (int e = ent_prepare(h, ent_samples, 0, d_new, &d_guess->t_start, (long)sizeof(nep_guess) * E.sp.n_local, ea, (hipStream_t)stream)) return e;
@@ -1311,7 +1341,7 @@ int nep_batch_safety_commit_ent(nep_batch_t* h, const nep_traj_rec* d_prev, cons
   ea.packed = E.d_fe_packed.p;
   launch_hulls(d_new, h->cfg.n_scenes, N, d_guess, E.sp, ps, (hipStream_t)stream);     // (with the bend points: ent_enabled)
   launch_ent_check(E.sp, ps, ea, d_new, h->cfg.n_scenes, cable_length, E.d_entangles.p, (hipStream_t)stream);
-  launch_safety(d_prev, d_new, h->cfg.n_scenes, N, E.sp, ps, E.d_conflict.p, E.safety_check_prev ? E.d_conflict_prev.p : nullptr, E.d_entangles.p, d_final, d_accept, (hipStream_t)stream);
+  launch_safety(d_prev, d_new, h->cfg.n_scenes, N, E.sp, ps, E.d_conflict.p, E.safety_check_prev ? E.d_conflict_prev.p : nullptr, E.d_entangles.p, d_final, d_accept, (hipStream_t)stream, E.active);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1530,6 +1560,14 @@ int nep_batch_debug_conflicts(nep_batch_t* h, int32_t scene, uint8_t* conflict_o
   if (h->eng.d_conflict.n < (size_t)h->cfg.n_scenes * nn) return fail(NEP_E_STATE, "no safety check has run");
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(conflict_out, h->eng.d_conflict.p + (size_t)scene * nn, nn, hipMemcpyDeviceToHost));
+  return 0;
+}
+int nep_batch_debug_conflicts_prev(nep_batch_t* h, int32_t scene, uint8_t* conflict_out) {
+  if (!h || !conflict_out || scene < 0 || scene >= h->cfg.n_scenes) return fail(NEP_E_ARG, "bad arguments");
+  const size_t nn = (size_t)h->cfg.num_agents * h->cfg.num_agents;
+  if (h->eng.d_conflict_prev.n < (size_t)h->cfg.n_scenes * nn) return fail(NEP_E_STATE, "no safety check with nep_batch_set_safety_check_prev has run");
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(conflict_out, h->eng.d_conflict_prev.p + (size_t)scene * nn, nn, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -1088,6 +1088,7 @@ __device__ __forceinline__ void separator_body(const SceneParams& sp, const Prob
 }
 template <int RULE>
 __global__ __launch_bounds__(64, NEP_SEP_WAVES) void separator_kernel(SceneParams sp, ProblemSet ps, int pool_pairs) {
+  if (!slot_active(sp, ps.active, blockIdx.x / NEP_MAX_POL)) return;      // (an inactive slot of an active set: nothing of it is read)
   separator_body<RULE>(sp, ps, pool_pairs, blockIdx.x / NEP_MAX_POL, blockIdx.x % NEP_MAX_POL, true);
 }
 // The spatial presolve's separator (launched instead of separator_kernel<0> when LPs may be skipped, ps.skip_box != null): one wave
@@ -1150,6 +1151,7 @@ __global__ __launch_bounds__(64, NEP_SEP_WAVES) void separator_packed_kernel(Sce
   unsigned short* sAtt = (unsigned short*)(sCnt + 6 * NEP_MAX_POL);      // entries (segment << 13 | candidate)
   const int lane = threadIdx.x;
   const int slot = blockIdx.x / kSepGroups, grp = blockIdx.x % kSepGroups;
+  if (!slot_active(sp, ps.active, slot)) return;      // (an inactive slot of an active set: nothing of it is read)
   const int seg_lo = grp * kSepPack, seg_hi = seg_lo + kSepPack < NEP_MAX_POL ? seg_lo + kSepPack : NEP_MAX_POL;
   const nep_guess* g = ps.guess + slot;
   const int K = g->K;
@@ -1851,7 +1853,8 @@ __global__ __launch_bounds__(256) void safety_conflict_kernel(const nep_traj_rec
 constexpr int kResolveParts = 8;
 __global__ __launch_bounds__(256) void safety_resolve_kernel(const nep_traj_rec* __restrict__ prev, const nep_traj_rec* __restrict__ fresh, int N,
                                                              const unsigned char* __restrict__ conflict, const unsigned char* __restrict__ conflict_prev,
-                                                             const int* __restrict__ entangles, nep_traj_rec* __restrict__ final_out, int* __restrict__ accept_out) {
+                                                             const int* __restrict__ entangles, nep_traj_rec* __restrict__ final_out, int* __restrict__ accept_out,
+                                                             const int* __restrict__ active) {
   extern __shared__ int sAcc[];   // [N] accept flags, [N] forced-bad flags, [N][W] symmetric conflict rows (32-bit words), [W] accepted ids
   // (kResolveParts workgroups per scene: each works out the accept flags — a few thousand bytes — and writes its share of the final
   // records: the copy, 120 KB per 64-agent scene, is what takes time, and one workgroup per scene left half of the chip idle)
@@ -1864,6 +1867,9 @@ __global__ __launch_bounds__(256) void safety_resolve_kernel(const nep_traj_rec*
   const unsigned char* Cp = conflict_prev ? conflict_prev + (long)scene * N * N : nullptr;
   for (int e = tid; e < N * W + W; e += blockDim.x) sRow[e] = 0u;
   for (int a = tid; a < N; a += blockDim.x) sBad[a] = (entangles && entangles[(long)scene * N + a] != 0) ? 1 : 0;      // entangleCheckGivenPwp (neptune.cpp:746-754)
+  // an active set: the inactive agents hold their previous record (fresh == prev there, launch_safety's caller) and are accepted before
+  // the id-ordered pass — their bits are in the accepted set from the start (sAcc[a] = 1 marks them for the walk below)
+  for (int a = tid; a < N; a += blockDim.x) sAcc[a] = (active && active[(long)scene * N + a] == 0) ? 1 : 0;
   __syncthreads();
   for (long e = tid; e < (long)N * N; e += blockDim.x) {
     const int a = (int)(e / N), j = (int)(e % N);
@@ -1877,7 +1883,16 @@ __global__ __launch_bounds__(256) void safety_resolve_kernel(const nep_traj_rec*
     unsigned acc[8];                                  // accepted ids so far (N <= 256: the path's sizes; beyond that the words live in LDS)
 #pragma unroll
     for (int w = 0; w < 8; w++) acc[w] = 0u;
+    if (active)
+      for (int a = 0; a < N; a++)
+        if (sAcc[a]) {
+          if (W <= 8) {
+#pragma unroll
+            for (int w = 0; w < 8; w++) if (w == (a >> 5)) acc[w] |= 1u << (a & 31);
+          } else sBits[a >> 5] |= 1u << (a & 31);
+        }
     for (int a = 0; a < N; a++) {
+      if (active && sAcc[a]) continue;      // (inactive: accepted already)
       bool bad = sBad[a] != 0;
       if (W <= 8) {
 #pragma unroll
@@ -1905,7 +1920,8 @@ __global__ __launch_bounds__(256) void safety_resolve_kernel(const nep_traj_rec*
 }
 
 void launch_safety(const nep_traj_rec* prev, const nep_traj_rec* fresh, int n_scenes, int N, const SceneParams& sp, const ProblemSet& ps,
-                   unsigned char* conflict, unsigned char* conflict_prev, const int* entangles, nep_traj_rec* final_out, int* accept_out, hipStream_t st) {
+                   unsigned char* conflict, unsigned char* conflict_prev, const int* entangles, nep_traj_rec* final_out, int* accept_out, hipStream_t st,
+                   const int* active) {
   if (n_scenes * N <= 0) return;
   auto hulls_of = [&](const nep_traj_rec* recs) {      // interval hulls of one record set on the round's grid (eight per wave, as in the replan)
     if (sp.num_pol <= 8 && (sp.hull_mode ? sp.hull_mode == 2 : (long)n_scenes * N > 2048))
@@ -1927,7 +1943,18 @@ void launch_safety(const nep_traj_rec* prev, const nep_traj_rec* fresh, int n_sc
   const size_t resolve_lds = (size_t)(2 * N + (N + 1) * ((N + 31) / 32)) * sizeof(int);
   static DynLdsAttr resolve_attr;
   (void)resolve_attr.ensure((const void*)safety_resolve_kernel, resolve_lds);
-  hipLaunchKernelGGL(safety_resolve_kernel, dim3(n_scenes * kResolveParts), dim3(256), resolve_lds, st, prev, fresh, N, conflict, conflict_prev, entangles, final_out, accept_out);
+  hipLaunchKernelGGL(safety_resolve_kernel, dim3(n_scenes * kResolveParts), dim3(256), resolve_lds, st, prev, fresh, N, conflict, conflict_prev, entangles, final_out, accept_out, active);
+}
+// the records an active-set safety pass judges (nep_batch_set_active): an inactive agent's this round is its previous one
+__global__ __launch_bounds__(64) void select_records_kernel(int N, const int* __restrict__ active, const nep_traj_rec* __restrict__ prev,
+                                                            const nep_traj_rec* __restrict__ fresh, nep_traj_rec* __restrict__ out) {
+  const long r = blockIdx.x;
+  const double* src = (const double*)((active[r] != 0 ? fresh : prev) + r);
+  double* dst = (double*)(out + r);
+  for (int e = threadIdx.x; e < (int)(sizeof(nep_traj_rec) / sizeof(double)); e += 64) dst[e] = src[e];
+}
+void launch_select_records(int n_scenes, int N, const int* active, const nep_traj_rec* prev, const nep_traj_rec* fresh, nep_traj_rec* out, hipStream_t st) {
+  if (n_scenes * N > 0) hipLaunchKernelGGL(select_records_kernel, dim3(n_scenes * N), dim3(64), 0, st, N, active, prev, fresh, out);
 }
 
 
@@ -2186,6 +2213,7 @@ __global__ __launch_bounds__(256, WGS) void frontend_kernel(SceneParams sp, Prob
   // carries its nodes in big records takes several times the others': started last it would set the kernel's end by itself)
   const long long t_wg0 = (long long)wall_clock64();
   if constexpr (BIG) { if ((int)blockIdx.x >= *ea.redo_count) return; }      // (the list holds at most gridDim.x = ea.redo_cap entries)
+  else { if (ps.fe_count && (int)blockIdx.x >= *ps.fe_count) return; }      // (an active set: fe_order is the list of active slots, active_list_kernel)
   const int slot = BIG ? ea.redo_list[blockIdx.x] : (ps.fe_order ? ps.fe_order[blockIdx.x] : (int)blockIdx.x), scene = slot / sp.n_local, own = sp.first_local + (slot % sp.n_local);
   const int N = sp.num_agents, S = sp.n_static, W = fc.beam_width, ns = fc.num_samples, NC = ns * ns, D = sp.num_pol;
   const FeSizes fz = fe_sizes(W, ns, D);
@@ -2973,8 +3001,18 @@ size_t frontend_lds_bytes(const SceneParams& sp, const nep_fe_cfg& fc, bool ent)
   return (b + 15) & ~(size_t)15;
 }
 
+// The outputs of the inactive slots of a front-end launch (nep_batch_set_active): result NEP_FE_SKIPPED with every other field zero, the
+// guess K = 0 with the start's t_start (what a masked replan that follows reads of it) and nothing else of it written.
+__global__ __launch_bounds__(64) void skipped_fe_kernel(SceneParams sp, const int* __restrict__ active, int n_slots, const nep_fe_start* __restrict__ starts,
+                                                        nep_guess* __restrict__ guess_out, nep_fe_result* __restrict__ res_out) {
+  const int slot = blockIdx.x * 64 + threadIdx.x;
+  if (slot >= n_slots || slot_active(sp, active, slot)) return;
+  guess_out[slot].K = 0; guess_out[slot].t_start = starts[slot].t_start;
+  if (res_out) { nep_fe_result r{}; r.status = NEP_FE_SKIPPED; res_out[slot] = r; }
+}
 void launch_frontend(int n_slots, const SceneParams& sp, const ProblemSet& ps_in, const nep_fe_cfg& fc, const nep_fe_start* starts,
-                     nep_guess* guess_out, nep_fe_result* res_out, const FeEntArgs* ea, hipStream_t st, int* order_buf, bool have_history) {
+                     nep_guess* guess_out, nep_fe_result* res_out, const FeEntArgs* ea, hipStream_t st, int* order_buf, bool have_history,
+                     int* active_buf) {
   if (n_slots <= 0) return;
   ProblemSet ps = ps_in;
   ps.fe_order = nullptr;
@@ -2985,6 +3023,11 @@ void launch_frontend(int n_slots, const SceneParams& sp, const ProblemSet& ps_in
   } else if (ps.fe_order_key && order_buf && have_history && n_slots > 1024) {      // (more than one wave of workgroups)
     launch_qp_order(n_slots, ps.fe_order_key, order_buf, st);
     ps.fe_order = order_buf;
+  }
+  if (ps.active && active_buf) {      // an active set: the searches run over the list of active slots, in the launch order made above
+    launch_active_list(n_slots, sp, ps.active, ps.fe_order, active_buf, nullptr, st);
+    ps.fe_order = active_buf; ps.fe_count = active_buf + n_slots;
+    hipLaunchKernelGGL(skipped_fe_kernel, dim3((n_slots + 63) / 64), dim3(64), 0, st, sp, ps.active, n_slots, starts, guess_out, res_out);
   }
   const bool ent = ea != nullptr;
   const size_t lds = frontend_lds_bytes(sp, fc, ent);

@@ -109,7 +109,16 @@ struct ProblemSet {
   long long* dbg;                // [slots][16] phase cycle counters (development aid) or null
   int* flags;                    // [1] sticky NEP_FLAG_* bits raised by the kernels (capacity overflows), or null
   double* fe_box;                // [scenes][num_agents + n_static][num_pol][4] (x0, x1, y0, y1) of the front end's obstacles (fe_box_kernel)
+  // active set (nep_batch_set_active): [scenes][num_agents] int32 by GLOBAL agent index, nonzero = the agent replans; null = every slot.
+  // Inactive slots never reach the QP or front-end workgroups (they run over active_list_kernel's list: order / order_count, fe_order /
+  // fe_count) and the separators return at their first line; skipped_replan_kernel / skipped_fe_kernel write their outputs.
+  const int* active;
+  const int* fe_count;           // [1] or null: only the first *fe_count workgroups of the front-end launch have work
 };
+// slot -> is it in the active set (see ProblemSet::active)
+__device__ __forceinline__ bool slot_active(const SceneParams& sp, const int* active, int slot) {
+  return active == nullptr || active[(long)(slot / sp.n_local) * sp.num_agents + sp.first_local + slot % sp.n_local] != 0;
+}
 constexpr int NEP_FLAG_ENT_POOL = 16;       // the safety pass's entangle re-check needed a big record and the pool had none left (nep_batch_set_fe_ent_big_records): the trajectory was turned down
 constexpr int NEP_FLAG_LINES = 8;           // a segment got more separating lines than its bucket holds (nep_batch_set_line_capacity)
 constexpr int NEP_FLAG_SCRATCH = 4;         // more replans went through the presolve's redo pass with rows beyond the register slots than the handle has scratch areas for (nep_batch_reserve_row_scratch)
@@ -216,7 +225,8 @@ size_t frontend_ent_xpool_words(const SceneParams& sp, const nep_fe_cfg& fc, int
 // (order_buf: [slots] scratch for the launch order, used when the previous launch left its keys — have_history — and the launch is
 // more than one wave of workgroups; null: slot order)
 void launch_frontend(int n_slots, const SceneParams& sp, const ProblemSet& ps, const nep_fe_cfg& fc, const nep_fe_start* starts,
-                     nep_guess* guess_out, nep_fe_result* res_out, const FeEntArgs* ea, hipStream_t st, int* order_buf = nullptr, bool have_history = false);
+                     nep_guess* guess_out, nep_fe_result* res_out, const FeEntArgs* ea, hipStream_t st, int* order_buf = nullptr, bool have_history = false,
+                     int* active_buf = nullptr);      // (active_buf: [slots + 1] for the active list when ps.active is set)
 void launch_ent_sample(const nep_traj_rec* recs, int n_scenes, int N, const double* ts0, long ts_scene_stride, int num_pol, int ns, double T_span,
                        double* sampled, int* present, hipStream_t st, int* zero_this = nullptr);
 void launch_ent_check(const SceneParams& sp, const ProblemSet& ps, const FeEntArgs& ea, const nep_traj_rec* fresh, int n_scenes, double cable, int* entangles, hipStream_t st);
@@ -224,6 +234,14 @@ void launch_next_starts(const nep_traj_rec* recs, int n_scenes, int N, int first
                         double* alt, double r_switch, hipStream_t st);
 void launch_gjk_explicit(int n_prob, const int* a_off, const double* a_xy, const double* b_xy, int* hit, hipStream_t st);
 void launch_safety(const nep_traj_rec* prev, const nep_traj_rec* fresh, int n_scenes, int N, const SceneParams& sp, const ProblemSet& ps,
-                   unsigned char* conflict, unsigned char* conflict_prev, const int* entangles, nep_traj_rec* final_out, int* accept_out, hipStream_t st);
+                   unsigned char* conflict, unsigned char* conflict_prev, const int* entangles, nep_traj_rec* final_out, int* accept_out, hipStream_t st,
+                   const int* active = nullptr);      // (active: the inactive agents are accepted before the id-ordered pass, ProblemSet::active)
+// active set (ProblemSet::active): the compacted list of the active slots, in the order of `order_in` (null: slot order), with the count
+// at list[n_slots]; zero_these (four ints or null) are zeroed on the way.  One workgroup, no host synchronisation.
+void launch_active_list(int n_slots, const SceneParams& sp, const int* active, const int* order_in, int* list, int* zero_these, hipStream_t st);
+// the outputs of the inactive slots of a replan (d_solution: NEP_SKIPPED; d_commit: the previous record when ps.prev_commit is known)
+void launch_skipped_replan(int n_slots, const SceneParams& sp, const ProblemSet& ps, hipStream_t st);
+// the records the safety pass judges: recs[s][j] = active ? fresh : prev
+void launch_select_records(int n_scenes, int N, const int* active, const nep_traj_rec* prev, const nep_traj_rec* fresh, nep_traj_rec* out, hipStream_t st);
 
 }  // namespace nep

@@ -46,6 +46,7 @@ __global__ __launch_bounds__(BS, 2) void qp_kernel(SceneParams sp, ProblemSet ps
   // (the dynamic part — line coefficients, then line-row state — starts at smem + kFixedDoubles + 32: ldyn below)
 
   const int tid = threadIdx.x;
+  if (ps.order_count && (int)blockIdx.x >= *ps.order_count) return;     // (an active set: the list of active slots, active_list_kernel)
   const int slot = ps.order ? ps.order[blockIdx.x] : (int)blockIdx.x;   // (launch order: see order_kernel)
   const long long t_wg0 = (long long)wall_clock64();          // this workgroup's lifetime goes to stats.solve_us (wall-clock ticks: sp.us_per_tick)
   const nep_guess* __restrict__ g = ps.guess + slot;
@@ -874,6 +875,63 @@ void launch_order_xcd(int n_slots, const int* key, int* order, hipStream_t st) {
 }
 void launch_qp_order(int n_slots, const int* key, int* order, hipStream_t st, int* zero_these) {
   if (n_slots > 0) hipLaunchKernelGGL(order_kernel, dim3(1), dim3(1024), 0, st, n_slots, key, order, zero_these);
+}
+
+// Active set (nep_batch_set_active): the slots whose agent replans, compacted in the order they would be launched in (order_in: this
+// round's LPT order, or slot order), count at list[n].  One workgroup: a thread takes a run of up to eight consecutive launch positions
+// (every load of the pass issued before the first is used: two dependent global round trips for n <= 8 192, not one per 1 024), a wave
+// scan and a prefix over the 16 waves' sums place its active slots.  The QP and front-end launches then run over the list and their
+// workgroups beyond the count return at once (ProblemSet::order_count / fe_count).  The list keeps the LPT order of the active slots.
+__global__ __launch_bounds__(1024) void active_list_kernel(int n, SceneParams sp, const int* __restrict__ active, const int* __restrict__ order_in,
+                                                           int* __restrict__ list, int* __restrict__ zero_these) {
+  if (zero_these && threadIdx.x < 4) zero_these[threadIdx.x] = 0;
+  __shared__ int wsum[16];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  int base = 0;
+  for (int c0 = 0; c0 < n; c0 += 8 * 1024) {
+    const int left = n - c0, per = left >= 8 * 1024 ? 8 : (left + 1023) / 1024;
+    int slot[8]; int cnt = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) { const int i = c0 + tid * per + k; slot[k] = (k < per && i < n) ? (order_in ? order_in[i] : i) : -1; }
+#pragma unroll
+    for (int k = 0; k < 8; k++) { if (slot[k] >= 0 && !slot_active(sp, active, slot[k])) slot[k] = -1; cnt += slot[k] >= 0; }
+    int x = cnt;      // inclusive scan of the counts over the wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(x, o); if (lane >= o) x += y; }
+    if (lane == 63) wsum[w] = x;
+    __syncthreads();
+    int pos = base, total = base;
+    for (int v = 0; v < 16; v++) { const int c = wsum[v]; pos += v < w ? c : 0; total += c; }
+    pos += x - cnt;
+#pragma unroll
+    for (int k = 0; k < 8; k++) if (slot[k] >= 0) list[pos++] = slot[k];
+    base = total;
+    __syncthreads();
+  }
+  if (tid == 0) list[n] = base;
+}
+void launch_active_list(int n_slots, const SceneParams& sp, const int* active, const int* order_in, int* list, int* zero_these, hipStream_t st) {
+  if (n_slots > 0) hipLaunchKernelGGL(active_list_kernel, dim3(1), dim3(1024), 0, st, n_slots, sp, active, order_in, list, zero_these);
+}
+// The outputs of the inactive slots of a replan: d_solution says NEP_SKIPPED with nothing solved, d_commit carries the previous record
+// over by the rule of a failed replan (qp_kernel's tail).  One wave per slot; active slots return at once (their QP workgroups write).
+__global__ __launch_bounds__(64) void skipped_replan_kernel(SceneParams sp, ProblemSet ps) {
+  const int slot = blockIdx.x, tid = threadIdx.x;
+  if (slot_active(sp, ps.active, slot)) return;
+  nep_solution* sol = ps.solution + slot;
+  constexpr int kWords = (int)(sizeof(nep_solution) / sizeof(int));
+  for (int e = tid; e < kWords; e += 64) ((int*)sol)[e] = 0;      // (stats, K = 0, n_states = 0; times and coefficients zero)
+  __syncthreads();
+  if (tid == 0) sol->stats.status = NEP_SKIPPED;
+  if (ps.commit && ps.prev_commit) {
+    const int own = sp.first_local + (slot % sp.n_local);
+    const double* src = (const double*)(ps.prev_commit + (long)(slot / sp.n_local) * sp.num_agents + own);
+    double* dst = (double*)(ps.commit + slot);
+    for (int e = tid; e < (int)(sizeof(nep_traj_rec) / sizeof(double)); e += 64) dst[e] = src[e];
+  }
+}
+void launch_skipped_replan(int n_slots, const SceneParams& sp, const ProblemSet& ps, hipStream_t st) {
+  if (n_slots > 0 && ps.active) hipLaunchKernelGGL(skipped_replan_kernel, dim3(n_slots), dim3(64), 0, st, sp, ps);
 }
 
 }  // namespace nep

@@ -56,7 +56,8 @@ __device__ __forceinline__ double pre_wave_sum(double v) {
 __global__ __launch_bounds__(64, NEP_PRE_WAVES) void qp_presolve_kernel(SceneParams sp, ProblemSet ps, const QpTable* __restrict__ tables, SampleSched sched, int* __restrict__ presolved) {
   __builtin_amdgcn_s_setprio(3);      // (latency-bound waves: when another scene group's hull / separator waves share the SIMD — bench.py's pipelined groups — these issue first)
   const int lane = threadIdx.x;
-  const int slot = blockIdx.x;
+  if (ps.order_count && (int)blockIdx.x >= *ps.order_count) return;     // (an active set: the list of active slots, active_list_kernel)
+  const int slot = ps.order_count ? ps.order[blockIdx.x] : (int)blockIdx.x;      // (without an active set: slot order, whatever the QP launch's order)
   const long long t0 = (long long)wall_clock64();
   __shared__ double sCoef[96], sTheta[96], sA[2 * 32];
   __shared__ int sCnt[3 * NEP_MAX_POL + 4];

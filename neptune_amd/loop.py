@@ -13,7 +13,7 @@ from .backend import BatchBackend
 
 
 class FleetLoop:
-    def __init__(self, par, statics, starts, goals, beam_width=32, delta_t_states=6, replan_every=5, device=None):
+    def __init__(self, par, statics, starts, goals, beam_width=32, delta_t_states=6, replan_every=5, device=None, skip_arrived=False):
         import torch
         self.torch = torch
         self.p, self.statics = par, statics
@@ -35,9 +35,16 @@ class FleetLoop:
             self.plans[a].reset(self.state[a])
         self.prev_pwp = [None] * N             # composed committed trajectory (pwp_prev_)
         self.done = np.zeros(N, dtype=bool)
+        # skip_arrived: arrived agents leave the active set of the front end, the replan and the safety pass (nep_batch_set_active) —
+        # the reference's replanCB returns early for them (neptune.cpp:1701-1711) and their committed trajectory stays an obstacle.
+        # Off: every agent is solved every round and the arrived ones' results are discarded here.
+        self.skip_arrived = skip_arrived
+        self._d_active = torch.ones((1, N), dtype=torch.int32, device=self.be.device) if skip_arrived else None
+        if skip_arrived:
+            self.be.set_active(self._d_active)
         self.trace = None                      # set to a list to record (t, agent, outcome, K) of every replan
         self.stats = dict(rounds=0, replans=0, accepted=0, fe_no_solution=0, qp_failed=0, qp_relaxed=0, rejected_by_safety=0,
-                          min_pair_dist=np.inf, min_static_dist=np.inf)
+                          min_pair_dist=np.inf, min_static_dist=np.inf, solves=0)
         self._static_pts = [np.asarray(s, dtype=np.float64) for s in scene_raw(statics, par)]
 
     # ---- records every agent publishes (publishOwnTraj) ----
@@ -91,6 +98,9 @@ class FleetLoop:
             starts[a]["goal"] = self.goals[a]
             starts[a]["t_start"] = t_start      # one clock per round; an agent whose plan is shorter rests at its end
         rec = self._records(t_now)
+        if self.skip_arrived:
+            self._d_active.copy_(torch.from_numpy((~self.done).astype(np.int32)).reshape(1, N))
+        self.stats["solves"] += int((~self.done).sum()) if self.skip_arrived else N
         d_com = be.to_device(rec); d_start = be.to_device(starts)
         d_guess = torch.zeros(N * abi.GUESS_DTYPE.itemsize, dtype=torch.uint8, device=be.device)
         d_fres = torch.zeros(N * abi.FE_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=be.device)
@@ -103,6 +113,8 @@ class FleetLoop:
         self.stats["rounds"] += 1
         for a in range(N):
             if self.done[a]:
+                if self.skip_arrived and self.trace is not None:
+                    self.trace.append((t_now, a, "skipped", int(sol[a]["K"]), int(fres[a]["status"]), int(sol[a]["stats"]["status"])))
                 continue
             self.stats["replans"] += 1
             K = int(sol[a]["K"]); status = int(sol[a]["stats"]["status"])
