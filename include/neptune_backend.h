@@ -502,7 +502,8 @@ int nep_batch_check(nep_batch_t* h, void* stream);
 /* sizeof() of the POD records as compiled (0 nep_pwp, 1 nep_traj_rec, 2 nep_backend_cfg,
  * 3 nep_stats, 4 nep_batch_cfg, 5 nep_guess, 6 nep_solution, 7 nep_ent_view; from neptune_plan.h:
  * 8 nep_wire_header, 9 nep_plan_cfg, 10 nep_point_a; from neptune_frontend.h: 11 nep_fe_cfg,
- * 12 nep_fe_start, 13 nep_fe_result): lets a foreign-language binding verify its struct mirror. */
+ * 12 nep_fe_start, 13 nep_fe_result, 14 nep_fe_ent_state; from neptune_entangle.h: 15 nep_ent_track_inputs): lets a
+ * foreign-language binding verify its struct mirror. */
 int nep_abi_sizeof(int32_t which);
 
 const char* nep_last_error(void);

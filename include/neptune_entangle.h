@@ -17,6 +17,9 @@
  *                              returns for a path (kinodynamic_search.cpp:582-603), for a given guess
  *   nep_ent_case_ids           the (knot, agent) -> case id reduction of solver_gurobi_poly.cpp:624-631
  *                              in the dense layout nep_batch_replan consumes
+ *   nep_ent_track_step         NeptuneRos::updateEntStateStaticObs (neptune_ros.cpp:800-850): the state of the
+ *                              vehicle's own tether after one move, with eu::entangleHSigToAddAgentInd's nine-argument
+ *                              form (entangle_utils.cpp:820-1127) for an agent whose bend points changed
  */
 #ifndef NEPTUNE_ENTANGLE_H_
 #define NEPTUNE_ENTANGLE_H_
@@ -91,6 +94,41 @@ int nep_ent_propagate_guess(const nep_ent_cfg* cfg, const nep_ent_inputs* in, co
 /* case_id[i][j] for knots i < NEP_MAX_POL, agents j < num_agents (0 = no single active case).     */
 int nep_ent_case_ids(int32_t n_states, int32_t n_active, const int32_t* alpha_off, const int32_t* alphas,
                      const int32_t* active_cases, int32_t num_agents, int32_t* case_id);
+
+/* ---- Tracking the tether between rounds (nep_batch_track_ent is its device form, include/neptune_frontend.h) ---------------
+ * What updateEntStateStaticObs reads of the other agents at one check: previousCheckingPosAgent_ / latestCheckingPosAgent_
+ * and the bend points their trajectory messages carried at the previous check and now (bendPtsForAgents_prev_ /
+ * bendPtsForAgents_, base first).  An agent i with present[i] == 0 or no bend point is skipped, as there (:810).         */
+typedef struct nep_ent_track_inputs {
+  const double* pik;              /* [num_agents][2] every agent at the previous check                                  */
+  const double* pik1;             /* [num_agents][2] ... now                                                            */
+  const int32_t* present;         /* [num_agents]                                                                       */
+  const int32_t* bend_off;        /* [num_agents+1] CSR offsets into bend_xy: the current bend points                   */
+  const double* bend_xy;
+  const int32_t* bend_off_prev;   /* [num_agents+1] CSR offsets into bend_xy_prev: those of the previous check          */
+  const double* bend_xy_prev;
+} nep_ent_track_inputs;
+
+#define NEP_ENT_TRACK_ENTANGLED 1   /* some active_cases[i] > 2 (agents): what the reference reports as entangled (:842-849)   */
+#define NEP_ENT_TRACK_TWO_CASES 2   /* some active_cases[i] >= 2 (agents): a state the search never creates                    */
+#define NEP_ENT_TRACK_TOO_LONG 4    /* the tether is longer than cfg->cable_length (eu::getTetherLength)                      */
+#define NEP_ENT_TRACK_CAP 8         /* a capacity was exceeded: the state is left as it was before the move                    */
+#define NEP_ENT_TRACK_ABORT 16      /* the nine-argument form reached a branch after which the reference stops the process
+                                       (exit(-1), "stop1".."stop4"): its crossing is added as there and the update goes on   */
+
+/* Capacity (not a flag): new crossings one move may add — the device's list of a step's crossings (kEntAddCap, ent_device.h) */
+#define NEP_ENT_TRACK_ADD_CAP 32
+
+/* One check of the vehicle's own tether for the move pk -> pk1, updating *state in place: the crossings of the move with
+ * every other agent's tether (their move pik[i] -> pik1[i]; the nine-argument form when their bend-point count changed
+ * since the previous check) and with the static representatives, addAlphaBetaToList, updateBendPts.  No test stops the
+ * update (the reference's updateEntStateStaticObs has none).  cfg: num_agents, id, cable_length and the statics are
+ * read (num_pol, num_samples and T_span are not).  Capacities: state->cap list entries, NEP_MAX_BEND - 1 bend points (what
+ * a published record holds besides the base), NEP_ENT_TRACK_ADD_CAP new crossings; beyond any of them the state is left
+ * as it was and NEP_ENT_TRACK_CAP is returned alone.  Returns the NEP_ENT_TRACK_* bits of the updated state (>= 0), or
+ * NEP_E_ARG.                                                                                                            */
+int nep_ent_track_step(const nep_ent_cfg* cfg, const nep_ent_track_inputs* in, nep_ent_state* state, const double pk[2],
+                       const double pk1[2]);
 
 #ifdef __cplusplus
 }

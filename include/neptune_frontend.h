@@ -195,6 +195,31 @@ int nep_batch_safety_commit_ent(nep_batch_t* h, const nep_traj_rec* d_prev, cons
                                 const nep_fe_ent_state* d_ent_init, int32_t ent_samples, double cable_length,
                                 nep_traj_rec* d_final, int32_t* d_accept, void* stream);
 
+/* ---- Tracking the tethers between rounds (NeptuneRos::odomCB -> updateEntStateStaticObs, neptune_ros.cpp:781-850) ---------
+ * nep_batch_track_ent     every agent of every scene flies intervals 1..n_intervals (1 <= n_intervals <= num_pol) of the
+ *                         round's grid (t_start + i T_span, t_start from d_guess as in the safety pass) along its record in
+ *                         d_records (normally nep_batch_safety_commit_ent's d_final); each interval is cut into ent_samples
+ *                         steps, sampled like Neptune::SamplePointsOfIntervals (nep_ent_sample_points), and all agents move
+ *                         at once.  At every step each agent's state takes one nep_ent_track_step (include/neptune_entangle.h):
+ *                         its own move and every other agent's, the other agents' bend points from d_records and, at the
+ *                         round's FIRST step only (one trajectory message per round), from d_prev as the previous check's
+ *                         (an empty list there counts as the current one).  No test stops the update.
+ *   d_ent                 [n_scenes][N]: in, the state at this round's A (zeroed = empty); out, at the next round's A — the
+ *                         d_ent_init of the next nep_batch_frontend_ent / nep_batch_safety_commit_ent
+ *   d_records             [n_scenes][N] (in/out): afterwards every tracked agent's record publishes n_bend = 1 + state.n_bend,
+ *                         bend[0] = its base, then the anchors of its bend indices (publishOwnTraj, :457-476); nothing else
+ *                         in the record changes
+ *   d_flags               [n_scenes][N] (out, may be NULL): the NEP_ENT_TRACK_* bits of the round, ORed over its steps
+ * An agent without a valid record (valid, is_agent, n_seg >= 1) is neither tracked nor published.  The active mask does
+ * not apply: an inactive agent flies its kept record, and its tether moves with it.  A state that would outgrow
+ * NEP_FE_ENT_CAP crossings or NEP_MAX_BEND - 1 bend points, or a step with more than NEP_ENT_TRACK_ADD_CAP new crossings,
+ * keeps the state before that step: NEP_ENT_TRACK_CAP in d_flags and NEP_E_CAP from nep_batch_check; nothing is written past
+ * the record.  Bit-identical to chaining nep_ent_track_step on the host.  Unsharded handles created with enable_entangle
+ * only (else NEP_E_STATE).  Asynchronous; the first call allocates per-slot scratch, later ones nothing: capturable.    */
+int nep_batch_track_ent(nep_batch_t* h, const nep_traj_rec* d_prev, nep_traj_rec* d_records, const nep_guess* d_guess,
+                        int32_t n_intervals, int32_t ent_samples, double cable_length, nep_fe_ent_state* d_ent,
+                        int32_t* d_flags, void* stream);
+
 /* Point A of the NEXT round for every slot, on the device: d_start[slot].t_start advances by dt and pos / vel / accel become
  * the state of the agent's committed trajectory (d_records [n_scenes][N], e.g. nep_batch_safety_commit's d_final) at that
  * time — Neptune::replanFull's choice of A "deltaT ahead on the committed plan" (neptune.cpp:1366-1399) for a

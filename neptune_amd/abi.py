@@ -118,6 +118,18 @@ class nep_ent_state(C.Structure):
                 ("active_cases", C.POINTER(C.c_int32))]
 
 
+class nep_ent_track_inputs(C.Structure):
+    """include/neptune_entangle.h: the other agents at one tracking check (nep_ent_track_step)."""
+    _fields_ = [("pik", C.POINTER(C.c_double)), ("pik1", C.POINTER(C.c_double)), ("present", C.POINTER(C.c_int32)),
+                ("bend_off", C.POINTER(C.c_int32)), ("bend_xy", C.POINTER(C.c_double)),
+                ("bend_off_prev", C.POINTER(C.c_int32)), ("bend_xy_prev", C.POINTER(C.c_double))]
+
+
+# nep_ent_track_step / nep_batch_track_ent flags (include/neptune_entangle.h)
+NEP_ENT_TRACK_ENTANGLED, NEP_ENT_TRACK_TWO_CASES, NEP_ENT_TRACK_TOO_LONG, NEP_ENT_TRACK_CAP, NEP_ENT_TRACK_ABORT = 1, 2, 4, 8, 16
+NEP_ENT_TRACK_ADD_CAP = 32
+
+
 class nep_fe_cfg(C.Structure):
     """include/neptune_frontend.h: the KinodynamicSearch setters the batched front end needs."""
     _fields_ = [("j_max", C.c_double), ("voxel_size", C.c_double), ("bias", C.c_double), ("goal_size", C.c_double),

@@ -353,6 +353,14 @@ class BatchBackend:
                                                 d_ent_init.data_ptr() if d_ent_init is not None else None, ent_samples, float(cable),
                                                 d_final.data_ptr(), d_accept.data_ptr() if d_accept is not None else None, st.cuda_stream))
 
+    def track_ent(self, d_prev, d_records, d_guess, d_ent, d_flags=None, n_intervals=1, ent_samples=3, cable_length=None, stream=None):
+        """every tether's entangle state carried over the round's first n_intervals intervals, and the bend points published
+        into d_records (nep_batch_track_ent): d_ent [n_scenes*N] FE_ENT_STATE_DTYPE bytes in/out, d_flags [n_scenes*N] int32"""
+        st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        cable = self.par.tether_length if cable_length is None else cable_length
+        check(lib().nep_batch_track_ent(self._h, d_prev.data_ptr(), d_records.data_ptr(), d_guess.data_ptr(), int(n_intervals), int(ent_samples),
+                                        float(cable), d_ent.data_ptr(), d_flags.data_ptr() if d_flags is not None else None, st.cuda_stream))
+
     def next_starts(self, d_records, dt, d_start, d_alt_goal=None, switch_radius=0.0, stream=None):
         """point A of the next round on the device: d_start's clock advances by dt and its state becomes that of the committed
         trajectories d_records at the new time; with d_alt_goal ([slots][3] float64) arrived agents swap goals

@@ -15,6 +15,7 @@
 
 #include "nep_device.h"
 #include "../../include/neptune_plan.h"
+#include "../../include/neptune_entangle.h"
 
 using namespace nep;
 
@@ -120,6 +121,7 @@ struct Engine {
   DevBuf<int> d_order, d_order_key; bool have_history = false, lpt = true, last_ordered = false;   // QP workgroups launched longest-expected-first (order_kernel)
   const int* active = nullptr;       // the active set (nep_batch_set_active): device [scenes][N], or null
   DevBuf<int> d_act, d_fe_act;       // [slots + 1] compacted active slots + count (active_list_kernel): the QP launches', the front end's
+  DevBuf<nep_fe_ent_state> d_track_save; DevBuf<int> d_track_flags;      // nep_batch_track_ent: per-slot scratch, flags when the caller passes none
   DevBuf<nep_traj_rec> d_safety_recs;      // [scenes][N] the records an active-set safety pass judges (select_records_kernel)
   bool use_reg = false;        // the QP runs as qp_reg_kernel (row state in registers, four workgroups per CU)
   double clock_hz = 1e8;       // wall_clock64() rate of the handle's device (set_clock)
@@ -454,7 +456,7 @@ struct Engine {
   void release() {
     d_tables.release(); d_sched_n.release(); d_sched_seg.release(); d_sched_dt.release(); d_pb.release(); d_static_xy.release();
     d_static_nv.release(); d_static_el.release(); d_hull_xy.release(); d_hull0_xy.release(); d_bend_xy.release(); d_line_nd.release(); d_row_scratch.release(); d_order.release(); d_order_key.release(); d_fe_order.release(); d_fe_order_key.release(); d_act.release(); d_fe_act.release(); d_safety_recs.release(); d_fe_us.release(); d_fe_box.release();
-    d_sampled.release(); d_srep.release(); d_slong.release(); d_present.release(); d_entangles.release(); d_fe_nodes.release(); d_fe_work.release(); d_fe_saved.release(); d_fe_arc.release(); d_fe_packed.release(); d_fe_big.release(); d_fe_big_beta.release(); d_fe_stf.release(); d_fe_stvox.release(); d_fe_xpool.release(); d_fe_big_count.release(); d_fe_big_check.release(); d_fe_big_check_count.release();
+    d_sampled.release(); d_srep.release(); d_slong.release(); d_present.release(); d_entangles.release(); d_fe_nodes.release(); d_fe_work.release(); d_fe_saved.release(); d_fe_arc.release(); d_fe_packed.release(); d_fe_big.release(); d_fe_big_beta.release(); d_fe_stf.release(); d_fe_stvox.release(); d_fe_xpool.release(); d_fe_big_count.release(); d_fe_big_check.release(); d_fe_big_check_count.release(); d_track_save.release(); d_track_flags.release();
     d_presolved.release(); d_line_skip.release(); d_redo_list.release(); d_redo_count.release(); d_polish_z.release(); d_polish_flag.release(); d_polish_list.release(); d_polish_count.release(); d_flags.release(); d_conflict.release(); d_conflict_prev.release(); d_hull_nv.release(); d_hull0_nv.release(); d_bend_n.release(); d_line_cnt.release(); d_line_far.release(); d_lp_stats.release();
     for (auto e : ev) hipEventDestroy(e);
     ev.clear();
@@ -1346,6 +1348,35 @@ int nep_batch_safety_commit_ent(nep_batch_t* h, const nep_traj_rec* d_prev, cons
   return 0;
 }
 
+int nep_batch_track_ent(nep_batch_t* h, const nep_traj_rec* d_prev, nep_traj_rec* d_records, const nep_guess* d_guess, int32_t n_intervals,
+                        int32_t ent_samples, double cable_length, nep_fe_ent_state* d_ent, int32_t* d_flags, void* stream) {
+  if (!h || !d_prev || !d_records || !d_guess || !d_ent) return fail(NEP_E_ARG, "null argument");
+  if (n_intervals < 1 || n_intervals > h->cfg.num_pol) return fail(NEP_E_ARG, "n_intervals out of range (1..num_pol)");
+  if (ent_samples < 1 || ent_samples > 8) return fail(NEP_E_ARG, "ent_samples out of range (1..8)");
+  if (!h->cfg.enable_entangle) return fail(NEP_E_STATE, "handle created without enable_entangle");
+  if (h->cfg.n_local != h->cfg.num_agents) return fail(NEP_E_STATE, "tether tracking runs on an unsharded handle (n_local == num_agents)");
+  Engine& E = h->eng;
+  const int N = h->cfg.num_agents, S = h->cfg.n_scenes, np = h->cfg.num_pol;
+  if (E.sp.n_static > 0 && !E.have_reps) return fail(NEP_E_STATE, "tether tracking with static obstacles needs nep_batch_set_static_reps first");
+  if (E.sp.n_static > 0 && E.d_srep.n < (size_t)(E.sp.static_stride ? S : 1) * E.sp.n_static * 4) return fail(NEP_E_STATE, "static representatives do not cover every scene's obstacle set: call nep_batch_set_static_reps after nep_batch_set_scene_statics");
+  ProblemSet ps{};
+  E.fill(ps);
+  if (int e = E.d_sampled.ensure((size_t)S * N * np * (ent_samples + 1) * 2)) return e;
+  if (int e = E.d_present.ensure((size_t)S * N)) return e;
+  if (int e = E.d_track_save.ensure((size_t)S * N)) return e;
+  if (int e = E.d_track_flags.ensure((size_t)S * N)) return e;      // (whether or not this call passes d_flags: a later captured call may not)
+  if (!E.d_srep.p) { if (int e = E.d_srep.ensure(4)) return e; if (int e2 = E.d_slong.ensure(2)) return e2; }
+  launch_ent_sample(d_records, S, N, &d_guess->t_start, (long)sizeof(nep_guess) * h->cfg.n_local, np, ent_samples, E.sp.T_span, E.d_sampled.p, E.d_present.p,
+                    (hipStream_t)stream, nullptr);
+  TrackArgs ta{};
+  ta.N = N; ta.S = E.sp.n_static; ta.n_scenes = S; ta.num_pol = np; ta.ns = ent_samples; ta.n_iv = n_intervals; ta.static_stride = E.sp.static_stride;
+  ta.cable = cable_length; ta.pb = ps.pb; ta.srep = E.d_srep.p; ta.slong = E.d_slong.p; ta.sampled = E.d_sampled.p; ta.present = E.d_present.p;
+  ta.prev = d_prev; ta.recs = d_records; ta.ent = d_ent; ta.save = E.d_track_save.p; ta.flags = d_flags ? d_flags : E.d_track_flags.p; ta.gflags = ps.flags;
+  launch_ent_track(ta, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 int nep_batch_next_starts(nep_batch_t* h, const nep_traj_rec* d_records, double dt, nep_fe_start* d_start, double* d_alt_goal,
                           double switch_radius, void* stream) {
   if (!h || !d_records || !d_start || !(dt >= 0.0)) return fail(NEP_E_ARG, "bad arguments");
@@ -1584,6 +1615,7 @@ int nep_batch_check(nep_batch_t* h, void* stream) {
   if (flags & NEP_FLAG_LINES) return fail(NEP_E_CAP, "a segment got more separating lines than its bucket holds: nep_batch_set_line_capacity(h, -1) sizes the buckets for the reference's worst case");
   if (flags & NEP_FLAG_SCRATCH) return fail(NEP_E_CAP, "the presolve's redo pass listed more replans with rows beyond the register slots than the handle has scratch areas for: nep_batch_reserve_row_scratch");
   if (flags & NEP_FLAG_ENT_POOL) return fail(NEP_E_CAP, "the pool of big entangle-state records ran out (front end: children of a search were pruned for it, by claim order; safety re-check: a trajectory was turned down): nep_batch_set_fe_ent_big_records");
+  if (flags & NEP_FLAG_ENT_TRACK) return fail(NEP_E_CAP, "nep_batch_track_ent: a tether's state outgrew NEP_FE_ENT_CAP crossings, NEP_MAX_BEND - 1 bend points or 32 new crossings in one step (the step was dropped), or a state handed in was malformed");
   if (flags & NEP_FLAG_ENT_BETA) return fail(NEP_E_ARG, "an entangle state passed to the front end has a non-zero beta for an agent crossing (the reference's calculateBetaForCase makes it 0.0)");
   if (flags & NEP_FLAG_HULL_OVERFLOW) return fail(NEP_E_CAP, "an interval overlaps more than NEP_HULL_MAX_CP/4 committed segments (or its hull has more than NEP_HULL_MAX_V vertices)");
   return 0;
@@ -1676,6 +1708,7 @@ int nep_abi_sizeof(int32_t which) {
     case 12: return (int)sizeof(nep_fe_start);
     case 13: return (int)sizeof(nep_fe_result);
     case 14: return (int)sizeof(nep_fe_ent_state);
+    case 15: return (int)sizeof(nep_ent_track_inputs);
     default: return -1;
   }
 }

@@ -218,6 +218,91 @@ template <class ADD, class BP = const double*> __device__ __forceinline__ void e
   }
   if (base_addition && add.n >= 2 && ((add.get(add.n - 1) ^ add.get(add.n - 2)) & 0xffffffu) == 0u) add.n -= 2;      // (same id, same case)
 }
+// eu::entangleHSigToAddAgentInd's nine-argument form (entangle_utils.cpp:820-1127), taken when agent_id's bend-point count changed
+// since the previous check (tracking between rounds, ent_track_kernel): b[0..nb) its bend points now, q[0..nq) at the previous
+// check.  The crossings carry the CURRENT count (the merge reads it).  Returns true where the reference pushes a crossing and then
+// stops the process (exit(-1)).  Restated branch for branch by crossings_agent_changed in entangle_host.cpp.
+template <class ADD> __device__ bool ent_cross_agent_changed(ADD& add, Ev2 pk, Ev2 pk1, Ev2 pik, Ev2 pik1, Ev2 pb, int nb, const double* b, int nq, const double* q, int agent_id) {
+  if (nb == 0 || nq == 0) return false;
+  bool base_addition = false, abort = false;
+  auto B = [&](int k) { return Ev2{b[2 * k], b[2 * k + 1]}; };
+  const Ev2 ql{q[2 * (nq - 1)], q[2 * (nq - 1) + 1]};      // (the previous list's last bend point)
+  if (nb < nq) {                                           // released from a bend point
+    const Ev2 ql2{q[2 * (nq - 2)], q[2 * (nq - 2) + 1]};
+    for (int i = 0; i < nb; i++) {
+      const bool last = i == nb - 1;
+      Ev2 u{0, 0}, v{0, 0}, up{0, 0}, vp{0, 0};
+      double c1, c2, c1p = 0.0;
+      if (!last) { c1 = ent_wedge2(pk, B(i + 1), B(i), u, v); c2 = ent_wedge(pk1, B(i + 1), B(i)); }
+      else { c1 = ent_wedge2(pk, pik, ql, u, v); c2 = ent_wedge(pk1, pik1, B(i)); c1p = ent_wedge2(pk, ql, ql2, up, vp); }
+      if (last) {
+        Ev2 ub, vb;
+        const double f1 = ent_wedge(pb, pik, ql);
+        const double f2 = ent_wedge2(pb, pik1, B(i), ub, vb);
+        const double f1p = i == 0 ? ent_wedge(pb, ql, ql2) : 0.0;
+        if (f1 * f2 < 0) {
+          const double a = ent_ratio(ub, vb);
+          if (a < 0) { } else if (a < 1) ent_push(add, agent_id, 1, nb);
+          base_addition = true;
+        }
+        if (i == 0 && f1p * f2 < 0) {
+          const double a = ent_ratio(ub, vb);
+          if (a < 0) { } else if (a < 1) { } else { ent_push(add, agent_id, 0, nb); abort = true; }
+          base_addition = true;
+        }
+      }
+      bool added_inbtw = false;
+      if (c1 * c2 < 0) {
+        const double a = ent_ratio(u, v);
+        if (a < 0) { ent_push(add, agent_id, i + 2, nb); added_inbtw = true; }
+        else if (a < 1 && last) ent_push(add, agent_id, 1, nb);
+      }
+      if (last && c1p * c2 < 0) {
+        const double a = ent_ratio(up, vp);
+        if (a < 0 && !added_inbtw) ent_push(add, agent_id, i + 2, nb);
+        else if (a < 1) { }
+        else if (i == 0) { ent_push(add, agent_id, 0, nb); abort = true; }
+      }
+    }
+  } else {                                                 // a bend point added
+    for (int i = 0; i < nb; i++) {
+      const bool last = i == nb - 1;
+      Ev2 u{0, 0}, v{0, 0};
+      double c1, c2;
+      if (last) { c1 = ent_wedge(pk, pik, ql); c2 = ent_wedge2(pk1, pik1, B(i), u, v); }
+      else if (i == nb - 2) { c1 = ent_wedge(pk, pik, ql); c2 = ent_wedge2(pk1, B(i + 1), B(i), u, v); }
+      else { c1 = ent_wedge2(pk, B(i + 1), B(i), u, v); c2 = ent_wedge(pk1, B(i + 1), B(i)); }
+      if (last) {
+        Ev2 ub, vb;
+        const double f1 = ent_wedge(pb, pik, ql);
+        const double f2 = ent_wedge2(pb, pik1, B(i), ub, vb);
+        if (f1 * f2 < 0) {
+          const double a = ent_ratio(ub, vb);
+          if (a < 0) { } else if (a < 1) ent_push(add, agent_id, 1, nb);
+          base_addition = true;
+        }
+      }
+      if (i == 0 && nb == 2) {
+        Ev2 ub, vb;
+        const double f1 = ent_wedge(pb, pik, ql);
+        const double f2 = ent_wedge2(pb, B(i + 1), B(i), ub, vb);
+        if (f1 * f2 < 0) {
+          const double a = ent_ratio(ub, vb);
+          if (a < 0) { } else if (a < 1) { } else { ent_push(add, agent_id, 0, nb); abort = true; }
+          base_addition = true;
+        }
+      }
+      if (c1 * c2 < 0) {
+        const double a = ent_ratio(u, v);
+        if (a < 0) ent_push(add, agent_id, i + 2, nb);
+        else if (a < 1 && last) ent_push(add, agent_id, 1, nb);
+        else if (a >= 1 && i == 0) { ent_push(add, agent_id, 0, nb); abort = true; }
+      }
+    }
+  }
+  if (base_addition && add.n >= 2 && ((add.get(add.n - 1) ^ add.get(add.n - 2)) & 0xffffffu) == 0u) add.n -= 2;      // (same id, same case)
+  return abort;
+}
 template <class ADD> __device__ __forceinline__ void ent_cross_static(ADD& add, Ev2 pk, Ev2 pk1, const EntCtx& c) {
   if (c.m_static) {
     // (front end: the candidates of this parent in index order, the NEXT one's representative requested before the current one's

@@ -53,8 +53,20 @@ inline double cross_ratio(const V2& u, const V2& v) {
 }
 inline double dist(const V2& a, const V2& b) { return std::sqrt((a.x - b.x) * (a.x - b.x) + (a.y - b.y) * (a.y - b.y)); }
 
+// The crossings of one tracking step, at most NEP_ENT_TRACK_ADD_CAP of them: a push beyond drops the crossing and marks the
+// list, as the device's list of a step's crossings does (ent_push)
+struct CappedAdd {
+  std::vector<A2> v;
+  bool overflow = false;
+  void push_back(const A2& a) { if ((int)v.size() < NEP_ENT_TRACK_ADD_CAP) v.push_back(a); else overflow = true; }
+  size_t size() const { return v.size(); }
+  void resize(size_t n) { v.resize(n); }
+  const A2& operator[](size_t i) const { return v[i]; }
+};
+
 // crossings of the step pk -> pk1 with agent i's tether polyline base .. bend points .. agent
-void crossings_agent(std::vector<A2>& add, const V2& pk, const V2& pk1, const V2& pik, const V2& pik1, const V2& pb_self,
+template <class ADD>
+void crossings_agent(ADD& add, const V2& pk, const V2& pk1, const V2& pik, const V2& pik1, const V2& pb_self,
                      const Ctx& cx, int i, int agent_id) {
   const int nb = cx.nbend(i);
   bool base_addition = false;
@@ -87,7 +99,8 @@ void crossings_agent(std::vector<A2>& add, const V2& pk, const V2& pk1, const V2
   if (base_addition && add.size() >= 2 && same(add[add.size() - 1], add[add.size() - 2])) add.resize(add.size() - 2);
 }
 
-void crossings_static(std::vector<A2>& add, const V2& pk, const V2& pk1, const Ctx& cx) {
+template <class ADD>
+void crossings_static(ADD& add, const V2& pk, const V2& pk1, const Ctx& cx) {
   for (int s = 0; s < cx.S; s++) {
     const V2 pik = cx.srep(s, 1), pbi = cx.srep(s, 0);
     V2 u, v;
@@ -205,6 +218,121 @@ double tether_length(const State& st, V2 from, const V2& pk1, const Ctx& cx) {
     from = bp;
   }
   return len + dist(pk1, from);
+}
+
+// eu::entangleHSigToAddAgentInd's nine-argument form (entangle_utils.cpp:820-1127) when agent i's bend-point count changed since
+// the previous check: b[0..nb) its bend points now, q[0..nq) at the previous check.  Returns true where the reference pushes a
+// crossing and then stops the process (exit(-1)).
+bool crossings_agent_changed(CappedAdd& add, const V2& pk, const V2& pk1, const V2& pik, const V2& pik1, const V2& pb, const V2* b, int nb,
+                             const V2* q, int nq, int agent_id) {
+  bool base_addition = false, abort = false;
+  if (nb == 0 || nq == 0) return false;                      // ("bendpts empty!")
+  if (nb < nq) {                                           // released from a bend point
+    for (int i = 0; i < nb; i++) {
+      const bool last = i == nb - 1;
+      V2 u{0, 0}, v{0, 0}, up{0, 0}, vp{0, 0};
+      double c1, c2, c1p = 0.0;
+      if (!last) { c1 = wedge(pk, b[i + 1], b[i], u, v); c2 = wedge(pk1, b[i + 1], b[i]); }
+      else { c1 = wedge(pk, pik, q[nq - 1], u, v); c2 = wedge(pk1, pik1, b[i]); c1p = wedge(pk, q[nq - 1], q[nq - 2], up, vp); }
+      if (last) {
+        V2 ub, vb;
+        const double f1 = wedge(pb, pik, q[nq - 1]);
+        const double f2 = wedge(pb, pik1, b[i], ub, vb);
+        const double f1p = i == 0 ? wedge(pb, q[nq - 1], q[nq - 2]) : 0.0;
+        if (f1 * f2 < 0) {
+          const double a = cross_ratio(ub, vb);
+          if (a < 0) { } else if (a < 1) add.push_back(A2{agent_id, 1});
+          base_addition = true;
+        }
+        if (i == 0 && f1p * f2 < 0) {
+          const double a = cross_ratio(ub, vb);
+          if (a < 0) { } else if (a < 1) { } else { add.push_back(A2{agent_id, 0}); abort = true; }      // ("stop4")
+          base_addition = true;
+        }
+      }
+      bool added_inbtw = false;
+      if (c1 * c2 < 0) {
+        const double a = cross_ratio(u, v);
+        if (a < 0) { add.push_back(A2{agent_id, i + 2}); added_inbtw = true; }
+        else if (a < 1 && last) add.push_back(A2{agent_id, 1});
+      }
+      if (last && c1p * c2 < 0) {
+        const double a = cross_ratio(up, vp);
+        if (a < 0 && !added_inbtw) add.push_back(A2{agent_id, i + 2});
+        else if (a < 1) { }
+        else if (i == 0) { add.push_back(A2{agent_id, 0}); abort = true; }      // ("stop3")
+      }
+    }
+  } else {                                                 // a bend point added
+    for (int i = 0; i < nb; i++) {
+      const bool last = i == nb - 1;
+      V2 u{0, 0}, v{0, 0};
+      double c1, c2;
+      if (last) { c1 = wedge(pk, pik, q[nq - 1]); c2 = wedge(pk1, pik1, b[i], u, v); }
+      else if (i == nb - 2) { c1 = wedge(pk, pik, q[nq - 1]); c2 = wedge(pk1, b[i + 1], b[i], u, v); }
+      else { c1 = wedge(pk, b[i + 1], b[i], u, v); c2 = wedge(pk1, b[i + 1], b[i]); }
+      if (last) {
+        V2 ub, vb;
+        const double f1 = wedge(pb, pik, q[nq - 1]);
+        const double f2 = wedge(pb, pik1, b[i], ub, vb);
+        if (f1 * f2 < 0) {
+          const double a = cross_ratio(ub, vb);
+          if (a < 0) { } else if (a < 1) add.push_back(A2{agent_id, 1});
+          base_addition = true;
+        }
+      }
+      if (i == 0 && nb == 2) {
+        V2 ub, vb;
+        const double f1 = wedge(pb, pik, q[nq - 1]);
+        const double f2 = wedge(pb, b[i + 1], b[i], ub, vb);
+        if (f1 * f2 < 0) {
+          const double a = cross_ratio(ub, vb);
+          if (a < 0) { } else if (a < 1) { } else { add.push_back(A2{agent_id, 0}); abort = true; }      // ("stop2")
+          base_addition = true;
+        }
+      }
+      if (c1 * c2 < 0) {
+        const double a = cross_ratio(u, v);
+        if (a < 0) add.push_back(A2{agent_id, i + 2});
+        else if (a < 1 && last) add.push_back(A2{agent_id, 1});
+        else if (a >= 1 && i == 0) { add.push_back(A2{agent_id, 0}); abort = true; }      // ("stop1")
+      }
+    }
+  }
+  if (base_addition && add.size() >= 2 && same(add[add.size() - 1], add[add.size() - 2])) add.resize(add.size() - 2);
+  return abort;
+}
+
+// NeptuneRos::updateEntStateStaticObs (neptune_ros.cpp:800-850) for the move pk -> pk1, without early exit
+int track_step(const Ctx& cx, const nep_ent_track_inputs* in, State& st, const V2& pk, const V2& pk1, int cap) {
+  const nep_ent_cfg& c = *cx.c;
+  const V2 pb_self = cx.pb(c.id - 1);
+  CappedAdd add;
+  bool abort = false;
+  for (int i = 0; i < cx.N; i++) {
+    if (i == c.id - 1 || !in->present[i]) continue;
+    const int nb = cx.nbend(i), nq = in->bend_off_prev[i + 1] - in->bend_off_prev[i];
+    if (nb < 1) continue;
+    const V2 pik{in->pik[2 * i], in->pik[2 * i + 1]}, pik1{in->pik1[2 * i], in->pik1[2 * i + 1]};
+    if (nq == nb) { crossings_agent(add, pk, pk1, pik, pik1, pb_self, cx, i, i + 1); continue; }
+    std::vector<V2> b(nb), q(nq);
+    for (int k = 0; k < nb; k++) b[k] = cx.bendpt(i, k);
+    for (int k = 0; k < nq; k++) q[k] = V2{in->bend_xy_prev[2 * (in->bend_off_prev[i] + k)], in->bend_xy_prev[2 * (in->bend_off_prev[i] + k) + 1]};
+    abort |= crossings_agent_changed(add, pk, pk1, pik, pik1, pb_self, b.data(), nb, q.data(), nq, i + 1);
+  }
+  crossings_static(add, pk, pk1, cx);
+  if (add.overflow) return NEP_ENT_TRACK_CAP;
+  State before = st;
+  merge_crossings(add.v, st, pk, pb_self, cx);
+  update_bend_points(st, pk1, pb_self, cx);
+  if ((int)st.alphas.size() > cap || (int)st.bend.size() > NEP_MAX_BEND - 1) { st = before; return NEP_ENT_TRACK_CAP; }
+  int flags = abort ? NEP_ENT_TRACK_ABORT : 0;
+  for (int i = 0; i < cx.N; i++) {
+    if (st.active[i] > 2) flags |= NEP_ENT_TRACK_ENTANGLED;
+    if (st.active[i] >= 2) flags |= NEP_ENT_TRACK_TWO_CASES;
+  }
+  if (tether_length(st, pb_self, pk1, cx) > c.cable_length) flags |= NEP_ENT_TRACK_TOO_LONG;
+  return flags;
 }
 
 // KinodynamicSearch::entanglesWithOtherAgents for one segment
@@ -347,6 +475,20 @@ int nep_ent_propagate_guess(const nep_ent_cfg* cfg, const nep_ent_inputs* in, co
   if (entangled_at) *entangled_at = hit_at;
   if (final_state) { if (int e = store_state(st, final_state)) return e; }
   return NEP_OK;
+}
+
+int nep_ent_track_step(const nep_ent_cfg* cfg, const nep_ent_track_inputs* in, nep_ent_state* state, const double pk[2], const double pk1[2]) {
+  if (!cfg || !in || !cfg->pb || cfg->num_agents < 1 || cfg->id < 1 || cfg->id > cfg->num_agents || !pk || !pk1) return NEP_E_ARG;
+  if (cfg->n_static < 0 || (cfg->n_static && (!cfg->static_rep || !cfg->static_longest))) return NEP_E_ARG;
+  if (!in->pik || !in->pik1 || !in->present || !in->bend_off || !in->bend_off_prev) return NEP_E_ARG;
+  if ((!in->bend_xy && in->bend_off[cfg->num_agents] > 0) || (!in->bend_xy_prev && in->bend_off_prev[cfg->num_agents] > 0)) return NEP_E_ARG;
+  State st;
+  if (!load_state(state, st) || state->n_active < cfg->num_agents + cfg->n_static) return NEP_E_ARG;
+  const nep_ent_inputs cur{nullptr, in->present, in->bend_off, in->bend_xy};
+  Ctx cx{cfg, &cur, cfg->num_agents, cfg->n_static};
+  const int flags = track_step(cx, in, st, V2{pk[0], pk[1]}, V2{pk1[0], pk1[1]}, state->cap);
+  if (int e = store_state(st, state)) return e;
+  return flags;
 }
 
 int nep_ent_case_ids(int32_t n_states, int32_t n_active, const int32_t* alpha_off, const int32_t* alphas, const int32_t* active_cases,

@@ -119,6 +119,7 @@ struct ProblemSet {
 __device__ __forceinline__ bool slot_active(const SceneParams& sp, const int* active, int slot) {
   return active == nullptr || active[(long)(slot / sp.n_local) * sp.num_agents + sp.first_local + slot % sp.n_local] != 0;
 }
+constexpr int NEP_FLAG_ENT_TRACK = 32;      // nep_batch_track_ent: a tracked state outgrew the fixed record (list, bend points or a step's crossings; the step was dropped) or was handed in malformed
 constexpr int NEP_FLAG_ENT_POOL = 16;       // the safety pass's entangle re-check needed a big record and the pool had none left (nep_batch_set_fe_ent_big_records): the trajectory was turned down
 constexpr int NEP_FLAG_LINES = 8;           // a segment got more separating lines than its bucket holds (nep_batch_set_line_capacity)
 constexpr int NEP_FLAG_SCRATCH = 4;         // more replans went through the presolve's redo pass with rows beyond the register slots than the handle has scratch areas for (nep_batch_reserve_row_scratch)
@@ -229,6 +230,23 @@ void launch_frontend(int n_slots, const SceneParams& sp, const ProblemSet& ps, c
                      int* active_buf = nullptr);      // (active_buf: [slots + 1] for the active list when ps.active is set)
 void launch_ent_sample(const nep_traj_rec* recs, int n_scenes, int N, const double* ts0, long ts_scene_stride, int num_pol, int ns, double T_span,
                        double* sampled, int* present, hipStream_t st, int* zero_this = nullptr);
+// nep_batch_track_ent (track_kernels.hip): one round's tracking of every tether and the published bend points
+struct TrackArgs {
+  int N, S, n_scenes, num_pol, ns, n_iv, static_stride;
+  double cable;
+  const double* pb;              // [N][2]
+  const double* srep;            // [scenes or 1][S][2][2]
+  const double* slong;           // [scenes or 1][S][2]
+  const double* sampled;         // [scenes][N][num_pol][ns+1][2] every record sampled on the round's grid (ent_sample_kernel)
+  const int* present;            // [scenes][N]
+  const nep_traj_rec* prev;      // [scenes][N] the previous round's records (bend points at the previous check)
+  nep_traj_rec* recs;            // [scenes][N] the round's records (flown; bend points published into them)
+  nep_fe_ent_state* ent;         // [scenes][N] in: the state at this round's A; out: at the next one's
+  nep_fe_ent_state* save;        // [scenes][N] scratch: the state before a step that may outgrow the record
+  int* flags;                    // [scenes][N] NEP_ENT_TRACK_* bits of the round
+  int* gflags;                   // sticky NEP_FLAG_ENT_TRACK
+};
+void launch_ent_track(const TrackArgs& ta, hipStream_t st);
 void launch_ent_check(const SceneParams& sp, const ProblemSet& ps, const FeEntArgs& ea, const nep_traj_rec* fresh, int n_scenes, double cable, int* entangles, hipStream_t st);
 void launch_next_starts(const nep_traj_rec* recs, int n_scenes, int N, int first_local, int n_local, double dt, nep_fe_start* starts,
                         double* alt, double r_switch, hipStream_t st);

@@ -106,3 +106,24 @@ class EntangleCheck:
             "nep_ent_case_ids")
         return dict(alpha_off=alpha_off, alphas=alphas[:alpha_off[K + 1]].copy(), active_cases=active, entangled_at=int(hit.value),
                     final=final, case_id=case_id)
+
+    def track_step(self, state, pk, pk1, pik, pik1, present, bendpts, bendpts_prev):
+        """One updateEntStateStaticObs of the agent's own tether for its move pk -> pk1 (nep_ent_track_step): pik / pik1 [N][2]
+        the other agents at the previous check and now, bendpts / bendpts_prev lists per agent of (k,2) arrays now and at the
+        previous check.  Updates state in place; -> the NEP_ENT_TRACK_* bits."""
+        def csr(lists):
+            off = np.zeros(self.N + 1, dtype=np.int32)
+            for j, b in enumerate(lists):
+                off[j + 1] = off[j] + len(b)
+            xy = np.zeros((max(int(off[-1]), 1), 2))
+            for j, b in enumerate(lists):
+                if len(b):
+                    xy[off[j]:off[j + 1]] = np.asarray(b, dtype=np.float64).reshape(-1, 2)
+            return off, xy
+        off, xy = csr(bendpts)
+        offp, xyp = csr(bendpts_prev)
+        a = np.ascontiguousarray(pik, dtype=np.float64).reshape(self.N, 2); b = np.ascontiguousarray(pik1, dtype=np.float64).reshape(self.N, 2)
+        pr = np.ascontiguousarray(present, dtype=np.int32).reshape(self.N)
+        tin = abi.nep_ent_track_inputs(abi.dptr(a), abi.dptr(b), abi.iptr(pr), abi.iptr(off), abi.dptr(xy), abi.iptr(offp), abi.dptr(xyp))
+        p0 = np.ascontiguousarray(pk, dtype=np.float64); p1 = np.ascontiguousarray(pk1, dtype=np.float64)
+        return _ck(lib().nep_ent_track_step(C.byref(self.cfg), C.byref(tin), C.byref(state.c), abi.dptr(p0), abi.dptr(p1)), "nep_ent_track_step")

@@ -172,3 +172,119 @@ def scene_raw(statics, par):
         c = v.mean(axis=0)
         out.append(c + (v - c) * np.maximum(1.0 - sd / np.maximum(np.abs(v - c), 1e-9), 0.0))
     return out
+
+
+class TetherLoop:
+    """S tethered scenes flown on the device, one captured graph per round (include/neptune_frontend.h):
+    frontend_ent -> lines + QP with the entangle rows -> safety_commit_ent -> track_ent -> next_starts, every tether's entangle
+    state carried from round to round in `d_ent` ([S*N] FE_ENT_STATE_DTYPE bytes, the front end's and the safety pass's d_ent_init).
+    A round flies `n_intervals` planning intervals.  Every record is published with the bend points of its agent's state at the
+    round's A (publishOwnTraj at replan time); the tracking then sees the previous round's lists as the previous check's and
+    writes the bend points of the next A into the flown records.  `active` ([S, N] int32 device tensor) is the handle's active set
+    (nep_batch_set_active).  check=False flies the same rounds with the entangle check of
+    the front end and of the safety pass off (plain nep_batch_frontend / nep_batch_safety_commit) and the tracking still on."""
+
+    def __init__(self, scenes, beam_width=16, n_intervals=1, ent_samples=3, check=True, device=None, graph=True, active=None):
+        import dataclasses
+        import torch
+        from neptune_amd import dist as ndist
+        self.torch = torch
+        self.scenes = scenes
+        S = self.S = len(scenes)
+        p = self.p = dataclasses.replace(scenes[0]["par"], enable_entangle=True)
+        N = self.N = p.num_agents
+        self.n_intervals, self.ent_samples, self.check, self.graph = n_intervals, ent_samples, check, graph
+        be = self.be = BatchBackend(p, scenes[0]["statics"], n_scenes=S, device=device)
+        for s, sc in enumerate(scenes):
+            be.set_scene_statics(s, sc["statics"])
+            reps, longest = scene.static_reps(sc["statics"]) if len(sc["statics"]) else (np.zeros((0, 2, 2)), np.zeros((0, 2)))
+            be.set_static_reps(reps, longest, scene=s)
+        if active is not None:      # (torch int32 [S, N]: the front end, the replan and the safety pass skip the inactive agents,
+            be.set_active(active)   # who keep flying their records; the tracking moves every tether)
+        self.fe = scene.frontend_cfg(p, beam_width=beam_width, entangle=check, ent_samples=ent_samples)
+        com, _ = ndist.stack_scenes(scenes)
+        starts = np.stack([scene.frontend_starts(sc) for sc in scenes]).reshape(-1)
+        self.goals = np.stack([np.asarray(sc["goals"], dtype=np.float64).reshape(N, 3) for sc in scenes])
+        dev = be.device
+        self.d_rec = be.to_device(com); self.d_rec_prev = self.d_rec.clone(); self.d_final = torch.empty_like(self.d_rec)
+        self.d_start = be.to_device(starts)
+        self.d_guess = torch.zeros(S * N * abi.GUESS_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self.d_res = torch.zeros(S * N * abi.FE_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self.d_case = torch.zeros(S * N * abi.NEP_MAX_POL * N, dtype=torch.int32, device=dev)
+        self.d_acc = torch.zeros(S * N, dtype=torch.int32, device=dev)
+        self.d_ent = torch.zeros(S * N * abi.FE_ENT_STATE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self.d_flags = torch.zeros(S * N, dtype=torch.int32, device=dev)
+        f = abi.TRAJ_REC_DTYPE.fields
+        self._bend_cols = (f["n_bend"][1], f["n_bend"][1] + 4), (f["bend"][1], f["bend"][1] + f["bend"][0].itemsize)
+        self.rounds = 0
+        self.ever_flagged = np.zeros((S, N), dtype=np.int32)
+        self._g = None
+
+    def _publish(self, d_new):
+        """stamp the bend points of every agent's state at the round's A into its new records (publishOwnTraj at replan time): the
+        QP's commit records carry the base only"""
+        R = abi.TRAJ_REC_DTYPE.itemsize
+        vn, vr = d_new.view(-1, R), self.d_rec.view(-1, R)
+        for lo, hi in self._bend_cols:
+            vn[:, lo:hi].copy_(vr[:, lo:hi])
+
+    def _round_ops(self):
+        be = self.be
+        # the safety pass judges the new records with the tethers the others published (d_final inherits them: accepted agents
+        # from the commit records, rejected and inactive ones from d_rec)
+        if self.check:
+            be.frontend_ent(self.fe, self.d_rec, self.d_start, self.d_guess, self.d_res, self.d_case, d_ent_init=self.d_ent)
+            be.replan(None, self.d_guess, d_ent=self.d_case)
+            self._publish(be.d_commit)
+            be.safety_commit_ent(self.d_rec, be.d_commit, self.d_guess, self.d_final, self.d_acc, d_ent_init=self.d_ent,
+                                 ent_samples=self.ent_samples)
+        else:
+            be.frontend(self.fe, self.d_rec, self.d_start, self.d_guess, self.d_res)
+            be.replan(None, self.d_guess)
+            self._publish(be.d_commit)
+            be.safety_commit(self.d_rec, be.d_commit, self.d_guess, self.d_final, self.d_acc)
+        be.track_ent(self.d_rec_prev, self.d_final, self.d_guess, self.d_ent, self.d_flags, n_intervals=self.n_intervals,
+                     ent_samples=self.ent_samples)
+        self.d_rec_prev.copy_(self.d_rec)
+        self.d_rec.copy_(self.d_final)
+        be.next_starts(self.d_rec, self.n_intervals * self.p.T_span, self.d_start)
+
+    def round(self):
+        torch = self.torch
+        if self.graph and self.rounds >= 1:
+            if self._g is None:
+                torch.cuda.synchronize()
+                s = torch.cuda.Stream(self.be.device)
+                s.wait_stream(torch.cuda.current_stream(self.be.device))
+                self._g = torch.cuda.CUDAGraph()
+                with torch.cuda.stream(s):
+                    self._g.capture_begin()
+                    self._round_ops()
+                    self._g.capture_end()
+                torch.cuda.current_stream(self.be.device).wait_stream(s)
+            self._g.replay()
+        else:
+            self._round_ops()
+        self.rounds += 1
+        self.ever_flagged |= (self.d_flags.cpu().numpy().reshape(self.S, self.N) & abi.NEP_ENT_TRACK_ENTANGLED) != 0
+
+    def run(self, rounds):
+        for _ in range(rounds):
+            self.round()
+        self.torch.cuda.synchronize(self.be.device)
+        return self.report()
+
+    def states(self):
+        return self.d_ent.cpu().numpy().view(abi.FE_ENT_STATE_DTYPE).reshape(self.S, self.N)
+
+    def report(self):
+        st = self.d_start.cpu().numpy().view(abi.FE_START_DTYPE).reshape(self.S, self.N)
+        d = np.hypot(st["pos"][..., 0] - self.goals[..., 0], st["pos"][..., 1] - self.goals[..., 1])
+        nb = self.states()["n_bend"]
+        return dict(rounds=self.rounds, arrived=[int(x) for x in (d < 2 * self.fe.goal_size).sum(axis=1)],
+                    ever_entangled=[int(x) for x in self.ever_flagged.sum(axis=1)],
+                    bend_hist=[int(x) for x in np.bincount(nb.reshape(-1), minlength=abi.NEP_MAX_BEND)[:abi.NEP_MAX_BEND]])
+
+    def close(self):
+        self._g = None
+        self.be.close()

@@ -1,0 +1,293 @@
+"""GPU: tether tracking between rounds (nep_batch_track_ent) equals the host chain of nep_ent_track_step bit for bit — states, flags
+and published bend points — on config-5-size scenes and the crossing variant, over successive rounds and one or two intervals per
+round.  The tethered loop (neptune_amd.loop.TetherLoop): replayed as a graph it equals the same loop run eagerly; its safety pass
+judges records that carry the published bend points; with half the agents inactive its tracking still moves every tether; and
+with the entangle check it keeps every tether untangled where the same scene flown without the check gets entangled."""
+import dataclasses
+
+import numpy as np
+import pytest
+
+from neptune_amd import abi, entangle, scene
+from neptune_amd._lib import BackendError
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def torch():
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    return torch
+
+
+def _present(r):
+    return bool(r["valid"]) and bool(r["is_agent"]) and int(r["pwp"]["n_seg"]) >= 1
+
+
+def _bends(r):
+    return np.array(r["bend"][: min(max(int(r["n_bend"]), 0), abi.NEP_MAX_BEND)], dtype=np.float64)
+
+
+def host_round(p, reps, longest, prev, recs, t0, states, n_iv, ns, cable):
+    """one round of the device call restated with nep_ent_track_step: -> flags [N]; states and recs (published bend points) updated"""
+    N = p.num_agents
+    S = len(reps)
+    present = np.array([_present(r) for r in recs], dtype=np.int32)
+    smp = np.zeros((N, p.num_pol, ns + 1, 2))
+    for j in range(N):
+        if present[j]:
+            smp[j] = entangle.sample_points(recs[j]["pwp"], t0, t0 + p.num_pol * p.T_span, p.num_pol, ns)
+    cur = [_bends(recs[j]) for j in range(N)]
+    old = [_bends(prev[j]) if len(_bends(prev[j])) else cur[j] for j in range(N)]
+    seq = [smp[:, 0, 0]] + [smp[:, itv, j] for itv in range(n_iv) for j in range(1, ns + 1)]
+    flags = np.zeros(N, dtype=np.int32)
+    for a in range(N):
+        if not present[a]:
+            continue
+        chk = entangle.EntangleCheck(N, a + 1, p.num_pol, ns, p.T_span, cable, p.pb, reps, longest)
+        for q in range(1, len(seq)):
+            flags[a] |= chk.track_step(states[a], seq[q - 1][a], seq[q][a], seq[q - 1], seq[q], present, cur, old if q == 1 else cur)
+    for a in range(N):
+        if not present[a]:
+            continue
+        al, _, bi, _ = states[a].as_lists()
+        recs[a]["bend"][0] = p.pb[a]
+        for k, b in enumerate(bi):
+            i, c = al[b]
+            recs[a]["bend"][k + 1] = p.pb[i - 1] if i <= N else reps[i - N - 1][c]
+        recs[a]["n_bend"] = 1 + len(bi)
+    return flags
+
+
+def assert_state_equal(dev, st, where):
+    al, be_, bi, act = st.as_lists()
+    n = int(dev["n_alpha"])
+    assert n == len(al) and int(dev["n_bend"]) == len(bi), where
+    assert [(int(dev["id"][k]), int(dev["cs"][k])) for k in range(n)] == al, where
+    assert np.array_equal(np.array(dev["beta"][:n], dtype=np.float64).view(np.int64), np.array(be_, dtype=np.float64).view(np.int64)), where
+    assert [int(x) for x in dev["bend"][: len(bi)]] == bi, where
+
+
+def run_rounds(torch, scenes, n_iv, rounds, ns=3, active=None):
+    p = dataclasses.replace(scenes[0]["par"], enable_entangle=True)
+    from neptune_amd import dist as ndist
+    from neptune_amd.backend import BatchBackend
+    S_, N = len(scenes), p.num_agents
+    be = BatchBackend(p, scenes[0]["statics"], n_scenes=S_)
+    reps, longs = [], []
+    for s, sc in enumerate(scenes):
+        be.set_scene_statics(s, sc["statics"])
+        r, l = scene.static_reps(sc["statics"]) if len(sc["statics"]) else (np.zeros((0, 2, 2)), np.zeros((0, 2)))
+        be.set_static_reps(r, l, scene=s)
+        reps.append(r); longs.append(l)
+    if active is not None:
+        be.set_active(active)
+    com, gue = ndist.stack_scenes(scenes)
+    recs = com.reshape(S_, N).copy(); prev = recs.copy()
+    gue = gue.reshape(S_, N).copy()
+    d_ent = torch.zeros(S_ * N * abi.FE_ENT_STATE_DTYPE.itemsize, dtype=torch.uint8, device=be.device)
+    d_fl = torch.zeros(S_ * N, dtype=torch.int32, device=be.device)
+    states = [[entangle.State(N + len(reps[s]), cap=abi.NEP_FE_ENT_CAP) for _ in range(N)] for s in range(S_)]
+    out = []
+    rng = np.random.default_rng(7)
+    for r in range(rounds):
+        changed = 0
+        for s in range(S_):      # the previous check saw some tethers with a bend point more or less: the nine-argument form
+            for j in range(N):
+                nb = int(prev[s][j]["n_bend"])
+                if rng.uniform() < 0.3 and len(reps[s]):
+                    if nb > 1 and rng.uniform() < 0.5:
+                        prev[s][j]["n_bend"] = nb - 1
+                    elif 1 <= nb < abi.NEP_MAX_BEND:
+                        prev[s][j]["bend"][nb] = reps[s][int(rng.integers(len(reps[s])))][int(rng.integers(2))]
+                        prev[s][j]["n_bend"] = nb + 1
+                changed += len(_bends(prev[s][j])) != len(_bends(recs[s][j]))
+        d_prev = be.to_device(prev.reshape(-1)); d_rec = be.to_device(recs.reshape(-1)); d_g = be.to_device(gue.reshape(-1))
+        be.track_ent(d_prev, d_rec, d_g, d_ent, d_fl, n_intervals=n_iv, ent_samples=ns)
+        from neptune_amd._lib import lib
+        rc = lib().nep_batch_check(be._h, torch.cuda.current_stream(be.device).cuda_stream)
+        dev_st = d_ent.cpu().numpy().view(abi.FE_ENT_STATE_DTYPE).reshape(S_, N)
+        dev_rec = d_rec.cpu().numpy().view(abi.TRAJ_REC_DTYPE).reshape(S_, N)
+        dev_fl = d_fl.cpu().numpy().reshape(S_, N)
+        new_prev = recs.copy()
+        for s in range(S_):
+            t0 = float(gue[s][0]["t_start"])
+            fl = host_round(p, reps[s], longs[s], prev[s], recs[s], t0, states[s], n_iv, ns, p.tether_length)
+            for a in range(N):
+                assert_state_equal(dev_st[s, a], states[s][a], (r, s, a))
+            assert np.array_equal(dev_fl[s], fl), (r, s)
+            assert np.array_equal(dev_rec[s]["n_bend"], recs[s]["n_bend"]), (r, s)
+            for a in range(N):
+                k = int(recs[s][a]["n_bend"])
+                assert np.array_equal(dev_rec[s][a]["bend"][:k], recs[s][a]["bend"][:k]), (r, s, a)
+            assert dev_rec[s].tobytes() == recs[s].tobytes(), (r, s)      # nothing else in the record changed
+        assert rc == (-4 if (dev_fl & abi.NEP_ENT_TRACK_CAP).any() else 0), (r, rc)      # (a capacity is raised through nep_batch_check too)
+        out.append(dict(changed=changed, flags=dev_fl.copy(), n_bend=dev_st["n_bend"].copy(), n_alpha=dev_st["n_alpha"].copy()))
+        prev = new_prev
+        for s in range(S_):
+            for a in range(N):
+                gue[s][a]["t_start"] += n_iv * p.T_span
+    be.close()
+    return out
+
+
+@pytest.mark.parametrize("n_iv", [1, 2])
+def test_track_equals_host_chain_crossing_scene(torch, n_iv):
+    out = run_rounds(torch, [scene.tether_crossing_scene(16, 8, 61), scene.tether_crossing_scene(16, 8, 62)], n_iv, rounds=6)
+    assert sum(int((o["n_alpha"] > 0).sum()) for o in out) > 0, "no crossing was tracked"
+    assert sum(o["changed"] for o in out) > 0
+
+
+@pytest.fixture(scope="module")
+def config5_scenes():
+    return scene.make_scenes(256, 100, [0, 1])
+
+
+@pytest.mark.parametrize("n_iv", [1, 2])
+def test_track_equals_host_chain_config5(torch, config5_scenes, n_iv):
+    out = run_rounds(torch, config5_scenes, n_iv, rounds=4)
+    assert sum(int((o["n_alpha"] > 0).sum()) for o in out) > 0
+    assert sum(o["changed"] for o in out) > 0
+
+
+def test_active_mask_does_not_change_the_update(torch):
+    scenes = [scene.tether_crossing_scene(16, 8, 61)]
+    mask = (torch.arange(16, device="cuda") % 2).to(torch.int32).reshape(1, 16).contiguous()
+    a = run_rounds(torch, scenes, 2, rounds=3)
+    b = run_rounds(torch, scenes, 2, rounds=3, active=mask)
+    for x, y in zip(a, b):
+        assert np.array_equal(x["flags"], y["flags"]) and np.array_equal(x["n_alpha"], y["n_alpha"]) and np.array_equal(x["n_bend"], y["n_bend"])
+
+
+def test_arguments(torch):
+    from neptune_amd._lib import lib
+    from neptune_amd.backend import BatchBackend
+    sc = scene.tether_crossing_scene(8, 6, 60)
+    p = sc["par"]
+    be = BatchBackend(p, sc["statics"])
+    r, l = scene.static_reps(sc["statics"]); be.set_static_reps(r, l)
+    d_rec = be.to_device(sc["committed"]); d_g = be.to_device(sc["guesses"])
+    d_ent = torch.zeros(8 * abi.FE_ENT_STATE_DTYPE.itemsize, dtype=torch.uint8, device=be.device)
+    L = lib()
+    for n_iv in (0, p.num_pol + 1):
+        assert L.nep_batch_track_ent(be._h, d_rec.data_ptr(), d_rec.data_ptr(), d_g.data_ptr(), n_iv, 3, 10.0, d_ent.data_ptr(), None, None) == -1
+    assert L.nep_batch_track_ent(be._h, d_rec.data_ptr(), d_rec.data_ptr(), d_g.data_ptr(), 1, 9, 10.0, d_ent.data_ptr(), None, None) == -1
+    be.track_ent(d_rec, d_rec.clone(), d_g, d_ent, n_intervals=p.num_pol)
+    be.close()
+    be2 = BatchBackend(dataclasses.replace(p, enable_entangle=False), sc["statics"])
+    with pytest.raises(BackendError):
+        be2.track_ent(d_rec, d_rec.clone(), d_g, d_ent)
+    assert L.nep_batch_track_ent(be2._h, d_rec.data_ptr(), d_rec.data_ptr(), d_g.data_ptr(), 1, 3, 10.0, d_ent.data_ptr(), None, None) == -2
+    be2.close()
+    be3 = BatchBackend(p, sc["statics"], first_local=0, n_local=4)
+    assert L.nep_batch_track_ent(be3._h, d_rec.data_ptr(), d_rec.data_ptr(), d_g.data_ptr(), 1, 3, 10.0, d_ent.data_ptr(), None, None) == -2
+    be3.close()
+
+
+def _loop_bytes(lp):
+    return (lp.d_rec.cpu().numpy().tobytes(), lp.d_ent.cpu().numpy().tobytes(), lp.d_flags.cpu().numpy().tobytes(),
+            lp.d_start.cpu().numpy().tobytes(), lp.ever_flagged.tobytes())
+
+
+def test_tether_loop_graph_equals_eager(torch):
+    from neptune_amd.loop import TetherLoop
+    res = []
+    for graph in (True, False):
+        lp = TetherLoop([scene.tether_crossing_scene(16, 8, 61)], beam_width=8, graph=graph)
+        rep = lp.run(20)
+        res.append((rep, _loop_bytes(lp)))
+        lp.close()
+    assert res[0][0] == res[1][0]
+    for x, y in zip(res[0][1], res[1][1]):
+        assert x == y
+    assert res[0][0]["rounds"] == 20
+
+
+def test_entangle_check_keeps_tethers_untangled(torch):
+    from neptune_amd.loop import TetherLoop
+    rep = {}
+    for check in (True, False):
+        lp = TetherLoop([scene.tether_crossing_scene(16, 8, 58)], beam_width=8, check=check, n_intervals=2)
+        rep[check] = lp.run(30)
+        lp.close()
+    assert sum(rep[True]["ever_entangled"]) == 0, rep
+    assert sum(rep[False]["ever_entangled"]) > 0, rep
+
+
+def _host_state(dev, n_active):
+    """a device nep_fe_ent_state as the host's eu::ent_state"""
+    st = entangle.State(n_active, cap=abi.NEP_FE_ENT_CAP)
+    n, b = int(dev["n_alpha"]), int(dev["n_bend"])
+    for k in range(n):
+        st.alphas[k] = (int(dev["id"][k]), int(dev["cs"][k])); st.betas[k] = float(dev["beta"][k])
+        st.active[int(dev["id"][k]) - 1] += 1
+    st.bend_idx[:b] = np.array(dev["bend"][:b], dtype=np.int32)
+    st.c.n_alpha, st.c.n_bend = n, b
+    return st
+
+
+def _spy(lp, name, record):
+    """wrap lp.be.<name>: record(args) before the call, on the same stream"""
+    orig = getattr(lp.be, name)
+
+    def call(*a, **k):
+        record(*a, **k)
+        return orig(*a, **k)
+    setattr(lp.be, name, call)
+
+
+def test_safety_pass_judges_the_published_tethers(torch):
+    """the loop's safety pass re-checks every new trajectory against the other agents' tethers as published at the round's A (bend
+    points of the tracked states), not against straight base-to-agent tethers; the records flown and tracked carry the same"""
+    from neptune_amd.loop import TetherLoop
+    bent = 0
+    for seed in (61, 58):
+        lp = TetherLoop([scene.tether_crossing_scene(16, 8, seed)], beam_width=8, n_intervals=2, graph=False)
+        seen = {}
+        _spy(lp, "safety_commit_ent", lambda d_prev, d_new, *a, **k: seen.update(rec=lp.d_rec.clone(), judged=d_new.clone()))
+        _spy(lp, "track_ent", lambda d_prev, d_records, *a, **k: seen.update(flown=d_records.clone()))
+        for r in range(20):
+            lp.round()
+            rec0, judged, flown = (seen[k].cpu().numpy().view(abi.TRAJ_REC_DTYPE) for k in ("rec", "judged", "flown"))
+            for recs in (judged, flown):
+                assert np.array_equal(recs["n_bend"], rec0["n_bend"]), (seed, r)
+                for a in range(len(rec0)):
+                    k = int(rec0[a]["n_bend"])
+                    assert np.array_equal(recs[a]["bend"][:k], rec0[a]["bend"][:k]), (seed, r, a)
+            bent += int((rec0["n_bend"] > 1).sum())
+        lp.close()
+    assert bent > 0, "no tether had a bend point: the check saw nothing"
+
+
+def test_tether_loop_with_active_mask_tracks_every_tether(torch):
+    """a TetherLoop with half the agents inactive (the front end, the replan and the safety pass skip them, they keep flying their
+    records): every round's tracking equals the host chain on what the loop flew, inactive tethers included"""
+    from neptune_amd.loop import TetherLoop
+    N = 16
+    sc = scene.tether_crossing_scene(N, 8, 61)
+    p = sc["par"]
+    reps, longs = scene.static_reps(sc["statics"])
+    mask = (torch.arange(N, device="cuda") % 2 == 0).to(torch.int32).reshape(1, N).contiguous()      # the moving (odd) agents inactive
+    lp = TetherLoop([sc], beam_width=8, n_intervals=2, graph=False, active=mask)
+    seen = {}
+    _spy(lp, "track_ent", lambda d_prev, d_records, d_guess, d_ent, *a, **k: seen.update(
+        prev=d_prev.clone(), recs=d_records.clone(), guess=d_guess.clone(), ent=d_ent.clone()))
+    inactive_crossed = 0
+    for r in range(12):
+        lp.round()
+        prev = seen["prev"].cpu().numpy().view(abi.TRAJ_REC_DTYPE).copy()
+        recs = seen["recs"].cpu().numpy().view(abi.TRAJ_REC_DTYPE).copy()
+        t0 = float(seen["guess"].cpu().numpy().view(abi.GUESS_DTYPE)[0]["t_start"])
+        states = [_host_state(d, N + len(reps)) for d in seen["ent"].cpu().numpy().view(abi.FE_ENT_STATE_DTYPE)]
+        fl = host_round(p, reps, longs, prev, recs, t0, states, 2, 3, p.tether_length)
+        dev_st = lp.d_ent.cpu().numpy().view(abi.FE_ENT_STATE_DTYPE)
+        for a in range(N):
+            assert_state_equal(dev_st[a], states[a], (r, a))
+        assert np.array_equal(lp.d_flags.cpu().numpy(), fl), r
+        assert lp.d_rec.cpu().numpy().tobytes() == recs.tobytes(), r      # the flown records with the published bend points
+        inactive_crossed += int((dev_st["n_alpha"][1::2] > 0).sum())
+    lp.close()
+    assert inactive_crossed > 0, "no inactive agent's tether crossed anything: the test shows nothing"
+
