@@ -252,7 +252,14 @@ void nep_batch_destroy(nep_batch_t* h);
  * hull lists of nep_backend_set_hulls.
  *
  * nep_batch_set_scene_statics gives scene `scene` (0 <= scene < n_scenes) its own set of n_static == cfg.n_static
- * polygons (host CSR, copied); scenes never set keep the set of nep_batch_cfg.  Blocking (device synchronize).  */
+ * polygons (host CSR, copied); scenes never set keep the set of nep_batch_cfg.  Blocking (device synchronize).
+ *
+ * Captured graphs: an upload writes the polygons, and the bounding boxes the presolve's LP skipping reads, into the handle's
+ * buffers before it returns.  A graph captured after the handle's first nep_batch_set_scene_statics therefore stays valid
+ * across later uploads with the same count: its next replay solves against the new polygons.  The first per-scene upload
+ * reallocates the static buffers (one set per scene from then on), so graphs captured before it must be captured again.  So
+ * must graphs captured before an upload that turns LP skipping off (a polygon without an edge on every side of its bounding
+ * box, e.g. a diamond): a graph keeps the launch sequence it was captured with.  */
 int nep_batch_set_scene_statics(nep_batch_t* h, int32_t scene, int32_t n_static, const int32_t* static_off,
                                 const double* static_xy);
 

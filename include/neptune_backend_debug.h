@@ -105,6 +105,25 @@ int nep_batch_kernel_time(nep_batch_t* h, int32_t which, double* avg_ms, int32_t
 int nep_batch_enable_timing(nep_batch_t* h, int32_t on);
 int nep_batch_reset_timing(nep_batch_t* h);
 
+/* Test hooks of the geometry half's launch sequence.  nep_batch_debug_launch_path: what the last replan launched, as NEP_PATH_* bits
+ * (host booleans set when the launches are enqueued; of nep_batch_replan_lines / _solve, the QP half keeps its geometry half's bits) —
+ * tests prove with them that they ran the path they are about.  nep_batch_debug_boxes: scene `scene`'s block of the obstacle boxes the
+ * separator's LP skipping and the front end read, [num_agents + n_static][num_pol][4] doubles (x0, x1, y0, y1; an empty polygon's box is
+ * (+inf, -inf, +inf, -inf)) into out (cap doubles), after a device synchronize.  nep_batch_debug_order_keys: the QP launch order's keys
+ * [slots] as the last replan left them (the order of the next one sorts the slots by key & 63, largest first).                        */
+enum {
+  NEP_PATH_BOX_KERNEL = 1,        /* fe_box_kernel made every obstacle's box                                                        */
+  NEP_PATH_HULLS_GROUPED = 2,     /* the eight-hulls-per-wave hull kernel ran                                                       */
+  NEP_PATH_FUSED_BOXES = 4,       /* ... and made the hulls' boxes and zeroed the redo counters (no fe_box_kernel)                    */
+  NEP_PATH_FUSED_ORDER = 8,       /* ... and, in its block 0, the QP launch order, zeroing the polish counters (no order_kernel)      */
+  NEP_PATH_ORDERED_QP = 16,       /* the QP workgroups were launched longest-expected-first                                         */
+  NEP_PATH_PRESOLVE_KERNEL = 32,  /* qp_presolve_kernel ran                                                                          */
+  NEP_PATH_REDO_PASS = 64         /* the presolve's redo pass ran                                                                    */
+};
+int nep_batch_debug_launch_path(nep_batch_t* h, int32_t* bits);
+int nep_batch_debug_boxes(nep_batch_t* h, int32_t scene, double* out, int32_t cap);
+int nep_batch_debug_order_keys(nep_batch_t* h, int32_t* keys, int32_t cap);
+
 /* Test hooks: fetch intermediates of the last replan to host.                                 */
 int nep_batch_debug_hulls(nep_batch_t* h, int32_t scene, double* hull_xy, int32_t* hull_nv);
 int nep_batch_debug_lines(nep_batch_t* h, int32_t slot, int32_t cap, int32_t* seg, double* nd,

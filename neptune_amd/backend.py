@@ -231,6 +231,7 @@ class BatchBackend:
         N = par.num_agents
         n_local = N - first_local if n_local is None else n_local
         self.N, self.first_local, self.n_local, self.n_scenes = N, first_local, n_local, n_scenes
+        self.n_static = len(statics)
         self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
         self._pb = np.ascontiguousarray(par.pb, dtype=np.float64)
         soff, sxy = _csr(statics)
@@ -414,6 +415,29 @@ class BatchBackend:
         out = np.zeros(self.n_scenes * self.n_local, dtype=np.int32); n = C.c_int32(0)
         check(lib().nep_batch_debug_launch_order(self._h, abi.iptr(out), len(out), C.byref(n)))
         return out[:n.value].copy() if n.value else None
+
+    # NEP_PATH_* bits of include/neptune_backend_debug.h
+    LAUNCH_PATH = (("box_kernel", 1), ("grouped_hulls", 2), ("fused_boxes", 4), ("fused_order", 8), ("ordered_qp", 16),
+                   ("presolve_kernel", 32), ("redo_pass", 64))
+
+    def debug_launch_path(self):
+        """what the last replan launched (nep_batch_debug_launch_path) -> {name: bool}: fe_box_kernel, the eight-hulls-per-wave hull
+        kernel, the boxes / the launch order made by that kernel, the QP workgroups in launch order, the presolve kernel, the redo pass"""
+        b = C.c_int32(0)
+        check(lib().nep_batch_debug_launch_path(self._h, C.byref(b)))
+        return {name: bool(b.value & bit) for name, bit in self.LAUNCH_PATH}
+
+    def debug_boxes(self, scene=0):
+        """the obstacle boxes of scene `scene` as the device holds them: [N + n_static][num_pol][4] (x0, x1, y0, y1) (nep_batch_debug_boxes)"""
+        out = np.zeros((self.N + self.n_static, self.par.num_pol, 4))
+        check(lib().nep_batch_debug_boxes(self._h, int(scene), abi.dptr(out), out.size))
+        return out
+
+    def debug_order_keys(self):
+        """the QP launch order's keys [slots] as the last replan left them (nep_batch_debug_order_keys)"""
+        out = np.zeros(self.slots, dtype=np.int32)
+        check(lib().nep_batch_debug_order_keys(self._h, abi.iptr(out), len(out)))
+        return out
 
     def set_max_runtime(self, seconds):
         """wall-clock budget of one solve (Gurobi TimeLimit; 0 = off): nep_batch_set_max_runtime"""

@@ -164,7 +164,44 @@ struct Engine {
   // nep_batch_reserve_row_scratch asks for the worst case.
   static constexpr int kScratchPool = 1024;
   bool scratch_full = false; int scratch_chunks = 0;
-  bool static_boxes_ok = false;      // the static polygons' entries of d_fe_box are those of the polygons now uploaded (set by a fe_box_kernel launch of run())
+  // The static polygons' entries of d_fe_box ([scene][N + S][num_pol][4]: one box per polygon, the same in every interval) are written
+  // from the host at every upload and whenever the buffer or its layout changes — never by a launch of run(), which may be recorded
+  // into a graph and not execute — so that a replan without fe_box_kernel (the fused hull launch, eager or replayed) reads the boxes of
+  // the polygons now uploaded.  static_boxes_ok: they are in place (push_static_boxes).
+  std::vector<double> h_static_box;      // [n_scenes][S][4] (x0, x1, y0, y1) of the polygons now uploaded
+  const double* box_buf = nullptr; int box_N = -1, box_S = -1, box_np = -1;      // the buffer and layout they were written into
+  bool static_boxes_ok = false;
+  bool static_boxes_placed() const { return static_boxes_ok && box_buf == d_fe_box.p && box_N == sp.num_agents && box_S == sp.n_static && box_np == sp.num_pol; }
+  // the boxes fe_box_kernel makes of n packed polygons (min / max over the vertices: the same doubles on the host) -> out [n][4]
+  static void static_boxes_of(int n, const std::vector<double>& sx, const std::vector<int>& nv, double* out) {
+    for (int j = 0; j < n; j++) {
+      const double* q = &sx[(size_t)j * kHullV * 2];
+      double x0 = HUGE_VAL, x1 = -HUGE_VAL, y0 = HUGE_VAL, y1 = -HUGE_VAL;
+      if (nv[j] > 0) { x0 = x1 = q[0]; y0 = y1 = q[1]; }
+      for (int v = 1; v < nv[j]; v++) { x0 = std::fmin(x0, q[2 * v]); x1 = std::fmax(x1, q[2 * v]); y0 = std::fmin(y0, q[2 * v + 1]); y1 = std::fmax(y1, q[2 * v + 1]); }
+      out[4 * j] = x0; out[4 * j + 1] = x1; out[4 * j + 2] = y0; out[4 * j + 3] = y1;
+    }
+  }
+  // h_static_box -> the static entries of d_fe_box: every scene, or scene `scene` alone when the buffer and layout are those of the last
+  // write.  Blocking (a copy from pageable memory); without a buffer of the full size yet it writes nothing (size_scratch calls again).
+  int push_static_boxes(int scene = -1) {
+    const bool placed = static_boxes_placed();
+    static_boxes_ok = false;
+    const int N = sp.num_agents, S = sp.n_static, np = sp.num_pol;
+    const size_t row = (size_t)(N + S) * np * 4, blk = (size_t)S * np * 4;
+    if (!d_fe_box.p || d_fe_box.n < (size_t)n_scenes * row || h_static_box.size() < (size_t)n_scenes * S * 4) return 0;
+    if (S > 0) {
+      const int s0 = (scene >= 0 && placed) ? scene : 0, s1 = (scene >= 0 && placed) ? scene + 1 : n_scenes;
+      std::vector<double> b((size_t)(s1 - s0) * blk);
+      for (int s = s0; s < s1; s++)
+        for (int j = 0; j < S; j++)
+          for (int i = 0; i < np; i++) std::memcpy(&b[(((size_t)(s - s0) * S + j) * np + i) * 4], &h_static_box[((size_t)s * S + j) * 4], 4 * sizeof(double));
+      HIPCHK(hipMemcpy2D(d_fe_box.p + (size_t)s0 * row + (size_t)N * np * 4, row * sizeof(double), b.data(), blk * sizeof(double), blk * sizeof(double), (size_t)(s1 - s0), hipMemcpyHostToDevice));
+    }
+    box_buf = d_fe_box.p; box_N = N; box_S = S; box_np = np; static_boxes_ok = true;
+    return 0;
+  }
+  int last_path = 0;           // NEP_PATH_* bits: what the last run() launched (nep_batch_debug_launch_path)
   int lines_cap_user = 0;      // 0: the default budget; -1: the reference's worst case; n > 0: n lines per segment (nep_batch_set_line_capacity)
   bool skip_mode() const { return sp.cull_radius > 0.0 && use_reg && sp.sep_rule == 0 && sp.skip_own == 1 && sp.n_hull == sp.num_agents && skip_lps && statics_boxy && !no_redo; }
   int size_row_scratch() {
@@ -232,7 +269,7 @@ struct Engine {
     rows_cap = 4 * (int)lines_total; rows_cap = (rows_cap + 3) & ~3;
     if (int e = d_hull_xy.ensure((size_t)n_scenes * sp.n_hull * np * kHullV * 2)) return e;
     if (int e = d_fe_box.ensure((size_t)n_scenes * (N + (sp.n_static > 0 ? sp.n_static : 0)) * np * 4)) return e;
-    static_boxes_ok = false;      // (the buffer may be a new one)
+    if (!static_boxes_placed()) { if (int e = push_static_boxes()) return e; }      // (a new buffer or another layout)
     if (int e = d_hull_nv.ensure((size_t)n_scenes * sp.n_hull * np)) return e;
     if (int e = d_hull0_xy.ensure((size_t)n_scenes * N * np * 2)) return e;
     if (int e = d_hull0_nv.ensure((size_t)n_scenes * N * np)) return e;
@@ -337,14 +374,15 @@ struct Engine {
     HIPCHK(hipMemcpy(d_static_xy.p, sx.data(), sx.size() * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_static_nv.p, nv.data(), nv.size() * sizeof(int), hipMemcpyHostToDevice));
     sp.n_static = n; sp.static_stride = 0;
+    h_static_box.resize((size_t)n_scenes * n * 4);      // (the shared set: the same boxes in every scene)
+    for (int s = 0; s < n_scenes; s++) static_boxes_of(n, sx, nv, &h_static_box[(size_t)s * n * 4]);
     if (n_scenes > 0 && sp.num_agents > 0 && sp.num_pol > 0)      // (the front end's obstacle boxes: one per agent or static polygon and interval)
       if (int e = d_fe_box.ensure((size_t)n_scenes * (sp.num_agents + n) * sp.num_pol * 4)) return e;
-    return 0;
+    return push_static_boxes();
   }
   // One static-obstacle set per scene (same polygon count S in every scene): the first call replicates the handle's
   // shared set into [n_scenes][S] arrays, then scene `scene` gets its own polygons.
   int upload_scene_statics(int scene, int n, const int32_t* off, const double* xy) {
-    static_boxes_ok = false;
     const int S = sp.n_static;
     if (n != S) return fail(NEP_E_ARG, "every scene must have the handle's n_static polygons");
     if (S == 0) return 0;
@@ -379,7 +417,8 @@ struct Engine {
     HIPCHK(hipMemcpy(d_static_xy.p + (size_t)scene * S * kHullV * 2, sx.data(), (size_t)S * kHullV * 2 * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_static_el.p + (size_t)scene * S * kHullV, el.data(), (size_t)S * kHullV * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_static_nv.p + (size_t)scene * S, nv.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice));
-    return 0;
+    static_boxes_of(S, sx, nv, &h_static_box[(size_t)scene * S * 4]);
+    return push_static_boxes(scene);
   }
   hipEvent_t next_event() {
     if (ev_used == ev.size()) { hipEvent_t e; hipEventCreate(&e); ev.push_back(e); }
@@ -394,7 +433,7 @@ struct Engine {
     const bool geo = (phases & 1) != 0, qp = (phases & 2) != 0;
     if (timing) hipEventRecord(next_event(), st);
     // the hull kernel makes the hulls' boxes itself (and zeroes the redo counters) when it is the eight-hulls-per-wave kernel over one hull list
-    // per agent and the static polygons' boxes are in place from an earlier fe_box_kernel launch: one launch less per round
+    // per agent and the static polygons' boxes are in place (written at upload: push_static_boxes): one launch less per round
     const bool fused_boxes = d_recs && geo && ps.skip_box != nullptr && !ps.lines_override && static_boxes_ok && ps.hull_pb <= 0
                              && n_rec == sp.num_agents && sp.n_hull == sp.num_agents && hulls_grouped(sp, n_scenes, n_rec);
     // ... and, in one wave more, this round's launch order of the QP workgroups (order_kernel's counting sort: it only needs the previous
@@ -402,7 +441,11 @@ struct Engine {
     const bool want_order = qp && lpt && have_history && slots > 1024 && d_order_key.n >= (size_t)slots && d_order.n >= (size_t)slots;
     const bool fused_order = fused_boxes && want_order;
     if (fused_order) { ps.order = d_order.p; ps.order_key = d_order_key.p; }
+    if (geo) last_path = 0; else last_path &= NEP_PATH_BOX_KERNEL | NEP_PATH_HULLS_GROUPED | NEP_PATH_FUSED_BOXES | NEP_PATH_FUSED_ORDER;      // (a QP half keeps its geometry half's bits)
     if (d_recs && geo) launch_hulls(d_recs, n_scenes, n_rec, ps.guess, sp, ps, st, fused_boxes);
+    if (d_recs && geo && hulls_grouped(sp, n_scenes, n_rec)) last_path |= NEP_PATH_HULLS_GROUPED;
+    if (fused_boxes) last_path |= NEP_PATH_FUSED_BOXES;
+    if (fused_order) last_path |= NEP_PATH_FUSED_ORDER;
     if (timing) hipEventRecord(next_event(), st);
     if (ps.lines_override) { ps.skip_box = nullptr; ps.line_skip = nullptr; ps.redo_list = nullptr; ps.redo_count = nullptr; }
     if (scratch_chunks > 0 && ps.scratch_chunks == 0) {      // (a pooled handle asked for a replan without the redo pass — lines from the host, a rule or hull layout that cannot skip LPs: one area per slot after all)
@@ -413,7 +456,7 @@ struct Engine {
     }
     const bool skip = ps.skip_box != nullptr;
     if (!ps.lines_override && geo) {
-      if (skip && !fused_boxes) { launch_boxes(n_scenes, sp, ps, st); static_boxes_ok = true; }      // (zeroes the redo counters as well)
+      if (skip && !fused_boxes) { launch_boxes(n_scenes, sp, ps, st); last_path |= NEP_PATH_BOX_KERNEL; }      // (zeroes the redo counters as well)
       launch_separator(slots, sp, ps, st);
     }
     if (timing) hipEventRecord(next_event(), st);
@@ -422,7 +465,7 @@ struct Engine {
     ps.order_key = (lpt && d_order_key.n >= (size_t)slots) ? d_order_key.p : nullptr;
     if (ps.order_key && have_history && slots > 1024 && d_order.n >= (size_t)slots) {   // (more than one wave of workgroups)
       if (!fused_order) launch_qp_order(slots, d_order_key.p, d_order.p, st, ps.polish_count);      // (zeroes the polish pass's counters on its way; fused_order: the hull launch has done both)
-      ps.order = d_order.p; last_ordered = true;
+      ps.order = d_order.p; last_ordered = true; last_path |= NEP_PATH_ORDERED_QP;
     } else if (ps.polish_count && !(use_reg && slots == 1)) launch_qp_polish_zero(ps.polish_count, st);      // (a one-workgroup launch — the per-agent handle — sets the counters itself: qp_reg_kernel's last lines)
     if (ps.active) {      // an active set: the QP launches run over the list of active slots (in the launch order made above), the inactive slots' outputs are written apart
       if (int e = d_act.ensure((size_t)slots + 1)) return e;
@@ -435,6 +478,7 @@ struct Engine {
     if (use_reg && presolve_kernel && ps.line_far != nullptr && !ps.lines_override && d_presolved.n >= (size_t)slots) {
       ps.presolved = d_presolved.p;
       launch_qp_presolve(slots, sp, ps, d_tables.p, sc, d_presolved.p, st);
+      last_path |= NEP_PATH_PRESOLVE_KERNEL;
     }
     if (use_reg) launch_qp_reg(slots, sp, ps, d_tables.p, sc, lds_bytes, st);
     else launch_qp(slots, sp, ps, d_tables.p, sc, lds_bytes, st);
@@ -442,6 +486,7 @@ struct Engine {
       // the presolve's redo pass: replans whose solution did not verify the skipped / parked lines (listed by the kernel above; the
       // list is empty nearly always) get every LP solved and every row through the interior point
       launch_separator_redo(slots, sp, ps, st);
+      last_path |= NEP_PATH_REDO_PASS;
       ProblemSet pr = ps;
       pr.line_far = nullptr; pr.line_skip = nullptr; pr.order = d_redo_list.p; pr.order_count = d_redo_count.p;      // (lists active slots only: no other slot ran)
       pr.scratch_by_block = ps.scratch_chunks > 0 ? 1 : 0;
@@ -1449,6 +1494,30 @@ int nep_batch_debug_launch_order(nep_batch_t* h, int32_t* order, int32_t cap, in
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(order, h->eng.d_order.p, (size_t)h->slots * sizeof(int), hipMemcpyDeviceToHost));
   *n_out = h->slots;
+  return 0;
+}
+// Test hooks of the launch sequence (include/neptune_backend_debug.h): what the last replan launched, the obstacle boxes, the ordering keys
+int nep_batch_debug_launch_path(nep_batch_t* h, int32_t* bits) {
+  if (!h || !bits) return fail(NEP_E_ARG, "bad arguments");
+  *bits = h->eng.last_path;
+  return 0;
+}
+int nep_batch_debug_boxes(nep_batch_t* h, int32_t scene, double* out, int32_t cap) {
+  if (!h || !out || scene < 0 || scene >= h->cfg.n_scenes || cap < 0) return fail(NEP_E_ARG, "bad arguments");
+  const Engine& E = h->eng;
+  const size_t n = (size_t)(E.sp.num_agents + E.sp.n_static) * E.sp.num_pol * 4;
+  if ((size_t)cap < n) return fail(NEP_E_CAP, "box buffer smaller than (num_agents + n_static) x num_pol x 4 doubles");
+  if (!E.d_fe_box.p || E.d_fe_box.n < (size_t)h->cfg.n_scenes * n) return fail(NEP_E_STATE, "the handle has no obstacle boxes");
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(out, E.d_fe_box.p + (size_t)scene * n, n * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+int nep_batch_debug_order_keys(nep_batch_t* h, int32_t* keys, int32_t cap) {
+  if (!h || !keys || cap < 0) return fail(NEP_E_ARG, "bad arguments");
+  if (cap < h->slots) return fail(NEP_E_CAP, "key buffer smaller than the slot count");
+  if (!h->eng.d_order_key.p || h->eng.d_order_key.n < (size_t)h->slots) return fail(NEP_E_STATE, "the handle has no ordering keys (nep_batch_set_launch_order)");
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(keys, h->eng.d_order_key.p, (size_t)h->slots * sizeof(int), hipMemcpyDeviceToHost));
   return 0;
 }
 
