@@ -233,6 +233,61 @@ int nep_batch_track_ent(nep_batch_t* h, const nep_traj_rec* d_prev, nep_traj_rec
 int nep_batch_next_starts(nep_batch_t* h, const nep_traj_rec* d_records, double dt, nep_fe_start* d_start,
                           double* d_alt_goal, double switch_radius, void* stream);
 
+/* ---- Flight audit: what the fleets actually fly, measured on the device -----------------------------------------------------
+ * Every stage above plans; the audit looks at the committed records as a perfect tracker flies them.  For every (scene, agent) it
+ * evaluates the records at control ticks and accumulates how close the agent came to every other agent and to every static
+ * polygon of its scene, at which tick and to whom.  Only the ticks are looked at — no continuous-time minimum: the loops' perfect
+ * tracker (and FleetLoop's host log) is only ever at the control ticks.
+ *
+ * nep_audit               one entry per (scene, agent); calls ACCUMULATE into it.  Initial values (nep_audit_init): the minima
+ *                         and center_d2 +inf, partners and index -1, everything else 0.  nep_abi_sizeof(17) is its size.
+ *   min_center_dist, center_partner, t_center   smallest x-y distance between this agent's centre and another agent's; the
+ *                         partner as 1-based id; the tick's time
+ *   min_box_clear, box_partner, t_box           the planner's own invariant: against agent j,
+ *                         max(|dx| - (bbox_j[0]/2 + drone_radius), |dy| - (bbox_j[1]/2 + drone_radius)) — how far this centre
+ *                         lies outside j's inflated box (neptune.cpp:340, the box the hull kernels build).  >= 0: the invariant
+ *                         held.  Asymmetric when bboxes differ, so every agent keeps its own.
+ *   min_static_dist, static_index, t_static     signed x-y distance from the centre to the nearest static polygon (0-based
+ *                         index) of the agent's scene AS THE HANDLE HOLDS IT (already inflated by nep_inflate_static, made
+ *                         counter-clockwise): negative inside.  >= 0 is the invariant.
+ *   path_len              sum of the x-y step lengths between consecutive ticks, added in tick order (over calls too)
+ *   max_speed             largest x-y speed at a tick
+ *   n_ticks, n_pair_viol, n_static_viol         ticks audited; ticks with a box clearance < 0; ticks with a static distance < 0
+ *   center_d2, last_xy    carried from call to call: min_center_dist squared (centre distances are compared squared, with one
+ *                         root per call) and the position at the last audited tick (path_len's next step)
+ * Ties go to the earlier tick, then to the lower partner id or static index, so a minimum does not depend on the order of
+ * evaluation.  Records are evaluated like nep_batch_next_starts does: u clamped to 0 before the first knot, at rest on the end
+ * point beyond the last.  A record that is not (valid && is_agent && n_seg >= 1) is not audited and is nobody's partner (the rule
+ * of nep_batch_track_ent); the active mask does not apply: an inactive agent flies its kept record and can be hit.
+ *
+ * nep_audit_records       host form (no HIP call): one scene of n records at t0 + k*tick, k = 0 .. n_ticks-1, accumulated into
+ *                         out[n].  static_off / static_xy: the scene's (inflated) polygons in the CSR form of nep_batch_create.
+ * nep_batch_audit         device form, bit-identical to the host form.  d_records [n_scenes][N] (e.g. nep_batch_safety_commit's
+ *                         d_final); d_start [slots]: a scene's clock is the t_start of its first slot (as the safety pass reads
+ *                         d_guess), the value nep_batch_next_starts advances on the device — so a replayed graph audits the right
+ *                         stretch with no time written by the host.  The ticks are t_start + k*tick, k = 0 .. n_ticks-1 (n_ticks
+ *                         = 0: nothing happens): when a round lasts n_ticks*tick the rounds tile the time axis and no tick counts
+ *                         twice.  The call goes after the round's records are final and before nep_batch_next_starts.  The static
+ *                         polygons are the handle's (nep_batch_set_scene_statics), no second copy is made.  Unsharded handles
+ *                         only (else NEP_E_STATE; enable_entangle is not needed); up to 1024 agents.  Asynchronous on `stream`;
+ *                         the FIRST call allocates the handle's per-slot scratch, later ones nothing: capturable, the contract of
+ *                         nep_batch_track_ent.
+ * (Chained calls reproduce one long call bit for bit when they visit the same tick times as doubles — t0 + k*tick is rounded.) */
+typedef struct nep_audit {
+  double min_center_dist, t_center;
+  double min_box_clear, t_box;
+  double min_static_dist, t_static;
+  double path_len, max_speed;
+  double center_d2, last_xy[2];
+  int32_t center_partner, box_partner, static_index;
+  int32_t n_ticks, n_pair_viol, n_static_viol;
+} nep_audit;
+int nep_audit_init(nep_audit* out, int64_t n);
+int nep_audit_records(const nep_traj_rec* recs, int32_t n, const int32_t* static_off, const double* static_xy, int32_t n_static,
+                      double drone_radius, double t0, double tick, int32_t n_ticks, nep_audit* out);
+int nep_batch_audit(nep_batch_t* h, const nep_traj_rec* d_records, const nep_fe_start* d_start, double tick, int32_t n_ticks,
+                    nep_audit* d_audit, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -157,6 +157,15 @@ class nep_fe_result(C.Structure):
                 ("cost", C.c_double), ("dist_to_goal", C.c_double), ("n_entangled", C.c_int32), ("ent_overflow", C.c_int32)]
 
 
+class nep_audit(C.Structure):
+    """include/neptune_frontend.h: the flight audit of one (scene, agent); calls accumulate into it."""
+    _fields_ = [("min_center_dist", C.c_double), ("t_center", C.c_double), ("min_box_clear", C.c_double), ("t_box", C.c_double),
+                ("min_static_dist", C.c_double), ("t_static", C.c_double), ("path_len", C.c_double), ("max_speed", C.c_double),
+                ("center_d2", C.c_double), ("last_xy", C.c_double * 2),
+                ("center_partner", C.c_int32), ("box_partner", C.c_int32), ("static_index", C.c_int32),
+                ("n_ticks", C.c_int32), ("n_pair_viol", C.c_int32), ("n_static_viol", C.c_int32)]
+
+
 def np_dtype(struct):
     return np.dtype(struct)
 
@@ -167,6 +176,7 @@ SOLUTION_DTYPE = np.dtype(nep_solution)
 FE_START_DTYPE = np.dtype(nep_fe_start)
 FE_RESULT_DTYPE = np.dtype(nep_fe_result)
 FE_ENT_STATE_DTYPE = np.dtype(nep_fe_ent_state)
+AUDIT_DTYPE = np.dtype(nep_audit)
 
 
 def dptr(a):

@@ -362,6 +362,16 @@ class BatchBackend:
         check(lib().nep_batch_track_ent(self._h, d_prev.data_ptr(), d_records.data_ptr(), d_guess.data_ptr(), int(n_intervals), int(ent_samples),
                                         float(cable), d_ent.data_ptr(), d_flags.data_ptr() if d_flags is not None else None, st.cuda_stream))
 
+    def new_audit(self):
+        """device buffer of n_scenes*N flight-audit records with the initial values (AUDIT_DTYPE bytes; nep_audit_init)"""
+        from . import audit
+        return self.to_device(audit.new_audit(self.n_scenes * self.par.num_agents))
+
+    def audit(self, d_records, d_start, tick, n_ticks, d_audit, stream=None):
+        """the flight audit of d_records at the ticks t_start + k*tick, k < n_ticks, accumulated into d_audit (nep_batch_audit)"""
+        st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        check(lib().nep_batch_audit(self._h, d_records.data_ptr(), d_start.data_ptr(), float(tick), int(n_ticks), d_audit.data_ptr(), st.cuda_stream))
+
     def next_starts(self, d_records, dt, d_start, d_alt_goal=None, switch_radius=0.0, stream=None):
         """point A of the next round on the device: d_start's clock advances by dt and its state becomes that of the committed
         trajectories d_records at the new time; with d_alt_goal ([slots][3] float64) arrived agents swap goals

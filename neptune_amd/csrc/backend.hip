@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "nep_device.h"
+#include "audit_common.h"
 #include "../../include/neptune_plan.h"
 #include "../../include/neptune_entangle.h"
 
@@ -122,6 +123,8 @@ struct Engine {
   const int* active = nullptr;       // the active set (nep_batch_set_active): device [scenes][N], or null
   DevBuf<int> d_act, d_fe_act;       // [slots + 1] compacted active slots + count (active_list_kernel): the QP launches', the front end's
   DevBuf<nep_fe_ent_state> d_track_save; DevBuf<int> d_track_flags;      // nep_batch_track_ent: per-slot scratch, flags when the caller passes none
+  DevBuf<AuditPart> d_audit_part;      // nep_batch_audit: per (scene, run of ticks, agent) minima, sized once for the most runs a call can have
+  int static_nv_max = 0;               // most vertices of a static polygon uploaded so far (nep_batch_audit's LDS stride)
   DevBuf<nep_traj_rec> d_safety_recs;      // [scenes][N] the records an active-set safety pass judges (select_records_kernel)
   bool use_reg = false;        // the QP runs as qp_reg_kernel (row state in registers, four workgroups per CU)
   double clock_hz = 1e8;       // wall_clock64() rate of the handle's device (set_clock)
@@ -331,6 +334,7 @@ struct Engine {
       if (c > kHullV) return fail(NEP_E_CAP, "static obstacle with more than NEP_HULL_MAX_V vertices");
       if (c < 0) return fail(NEP_E_ARG, "static obstacle offsets must not decrease");
       nv[j] = c;
+      if (c > static_nv_max) static_nv_max = c;
       for (int v = 0; v < c; v++) { sx[((size_t)j * kHullV + v) * 2] = xy[2 * (off[j] + v)]; sx[((size_t)j * kHullV + v) * 2 + 1] = xy[2 * (off[j] + v) + 1]; }
       if (!normalize_ccw(&sx[(size_t)j * kHullV * 2], c)) return fail(NEP_E_ARG, "static obstacle polygon is not convex");
       // The spatial presolve skips the LP of an obstacle whose BOX is far (box_far, geom_kernels.hip): sound only when every side of
@@ -501,7 +505,7 @@ struct Engine {
   void release() {
     d_tables.release(); d_sched_n.release(); d_sched_seg.release(); d_sched_dt.release(); d_pb.release(); d_static_xy.release();
     d_static_nv.release(); d_static_el.release(); d_hull_xy.release(); d_hull0_xy.release(); d_bend_xy.release(); d_line_nd.release(); d_row_scratch.release(); d_order.release(); d_order_key.release(); d_fe_order.release(); d_fe_order_key.release(); d_act.release(); d_fe_act.release(); d_safety_recs.release(); d_fe_us.release(); d_fe_box.release();
-    d_sampled.release(); d_srep.release(); d_slong.release(); d_present.release(); d_entangles.release(); d_fe_nodes.release(); d_fe_work.release(); d_fe_saved.release(); d_fe_arc.release(); d_fe_packed.release(); d_fe_big.release(); d_fe_big_beta.release(); d_fe_stf.release(); d_fe_stvox.release(); d_fe_xpool.release(); d_fe_big_count.release(); d_fe_big_check.release(); d_fe_big_check_count.release(); d_track_save.release(); d_track_flags.release();
+    d_sampled.release(); d_srep.release(); d_slong.release(); d_present.release(); d_entangles.release(); d_fe_nodes.release(); d_fe_work.release(); d_fe_saved.release(); d_fe_arc.release(); d_fe_packed.release(); d_fe_big.release(); d_fe_big_beta.release(); d_fe_stf.release(); d_fe_stvox.release(); d_fe_xpool.release(); d_fe_big_count.release(); d_fe_big_check.release(); d_fe_big_check_count.release(); d_track_save.release(); d_track_flags.release(); d_audit_part.release();
     d_presolved.release(); d_line_skip.release(); d_redo_list.release(); d_redo_count.release(); d_polish_z.release(); d_polish_flag.release(); d_polish_list.release(); d_polish_count.release(); d_flags.release(); d_conflict.release(); d_conflict_prev.release(); d_hull_nv.release(); d_hull0_nv.release(); d_bend_n.release(); d_line_cnt.release(); d_line_far.release(); d_lp_stats.release();
     for (auto e : ev) hipEventDestroy(e);
     ev.clear();
@@ -1422,6 +1426,29 @@ int nep_batch_track_ent(nep_batch_t* h, const nep_traj_rec* d_prev, nep_traj_rec
   return 0;
 }
 
+int nep_batch_audit(nep_batch_t* h, const nep_traj_rec* d_records, const nep_fe_start* d_start, double tick, int32_t n_ticks, nep_audit* d_audit,
+                    void* stream) {
+  if (!h || !d_records || !d_start || !d_audit || n_ticks < 0 || !(tick >= 0.0)) return fail(NEP_E_ARG, "bad arguments");
+  if (h->cfg.n_local != h->cfg.num_agents) return fail(NEP_E_STATE, "the flight audit runs on an unsharded handle (n_local == num_agents)");
+  Engine& E = h->eng;
+  const int N = h->cfg.num_agents, S = h->cfg.n_scenes;
+  if (N > 1024) return fail(NEP_E_CAP, "the flight audit takes up to 1024 agents per scene");
+  const int vs = E.sp.n_static > 0 ? std::max(E.static_nv_max, 1) : 1;
+  if (audit_lds_bytes(N, E.sp.n_static, vs) > 64 * 1024) return fail(NEP_E_CAP, "the flight audit's agents and static polygons do not fit into 64 KB of LDS");
+  if (int e = E.d_audit_part.ensure((size_t)S * nep_audit_impl::kAuditMaxChunks * N)) return e;      // (before the n_ticks == 0 return: the first call allocates)
+  if (n_ticks == 0) return 0;
+  ProblemSet ps{};
+  E.fill(ps);
+  AuditArgs aa{};
+  aa.N = N; aa.S = E.sp.n_static; aa.n_scenes = S; aa.static_stride = E.sp.static_stride; aa.vstride = vs; aa.n_ticks = n_ticks;
+  aa.chunk_len = nep_audit_impl::audit_chunk_len(n_ticks); aa.n_chunks = (n_ticks + aa.chunk_len - 1) / aa.chunk_len;
+  aa.tick = tick; aa.drone_radius = E.sp.drone_radius;
+  aa.recs = d_records; aa.starts = d_start; aa.static_xy = ps.static_xy; aa.static_nv = ps.static_nv; aa.part = E.d_audit_part.p; aa.out = d_audit;
+  launch_audit(aa, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 int nep_batch_next_starts(nep_batch_t* h, const nep_traj_rec* d_records, double dt, nep_fe_start* d_start, double* d_alt_goal,
                           double switch_radius, void* stream) {
   if (!h || !d_records || !d_start || !(dt >= 0.0)) return fail(NEP_E_ARG, "bad arguments");
@@ -1778,6 +1805,7 @@ int nep_abi_sizeof(int32_t which) {
     case 13: return (int)sizeof(nep_fe_result);
     case 14: return (int)sizeof(nep_fe_ent_state);
     case 15: return (int)sizeof(nep_ent_track_inputs);
+    case 17: return (int)sizeof(nep_audit);      // (16 stays unassigned: tests/test_ent_track_cpu.py pins it to -1)
     default: return -1;
   }
 }

@@ -247,6 +247,20 @@ struct TrackArgs {
   int* gflags;                   // sticky NEP_FLAG_ENT_TRACK
 };
 void launch_ent_track(const TrackArgs& ta, hipStream_t st);
+// nep_batch_audit (audit_kernels.hip): the minima of one (scene, run of ticks, agent), ticks as indices of the call
+struct AuditPart { double c_d2, box, stat; int c_k, c_p, b_k, b_p, s_k, s_i, n_pair, n_stat; };
+struct AuditArgs {
+  int N, S, n_scenes, static_stride, vstride, n_ticks, chunk_len, n_chunks;
+  double tick, drone_radius;
+  const nep_traj_rec* recs;      // [scenes][N]
+  const nep_fe_start* starts;    // [scenes][N]: a scene's clock is its first slot's t_start
+  const double* static_xy;       // [scenes or 1][S][kHullV][2]
+  const int* static_nv;          // [scenes or 1][S]
+  AuditPart* part;               // [scenes][n_chunks][N] scratch
+  nep_audit* out;                // [scenes][N] accumulated into
+};
+size_t audit_lds_bytes(int N, int S, int vstride);
+void launch_audit(const AuditArgs& aa, hipStream_t st);
 void launch_ent_check(const SceneParams& sp, const ProblemSet& ps, const FeEntArgs& ea, const nep_traj_rec* fresh, int n_scenes, double cable, int* entangles, hipStream_t st);
 void launch_next_starts(const nep_traj_rec* recs, int n_scenes, int N, int first_local, int n_local, double dt, nep_fe_start* starts,
                         double* alt, double r_switch, hipStream_t st);

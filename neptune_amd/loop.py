@@ -9,11 +9,12 @@ Host side only orchestrates: every numeric step is a C-ABI call (device kernels 
 import numpy as np
 
 from . import abi, plan, scene
+from . import audit as audit_mod
 from .backend import BatchBackend
 
 
 class FleetLoop:
-    def __init__(self, par, statics, starts, goals, beam_width=32, delta_t_states=6, replan_every=5, device=None, skip_arrived=False):
+    def __init__(self, par, statics, starts, goals, beam_width=32, delta_t_states=6, replan_every=5, device=None, skip_arrived=False, audit=False):
         import torch
         self.torch = torch
         self.p, self.statics = par, statics
@@ -46,6 +47,9 @@ class FleetLoop:
         self.stats = dict(rounds=0, replans=0, accepted=0, fe_no_solution=0, qp_failed=0, qp_relaxed=0, rejected_by_safety=0,
                           min_pair_dist=np.inf, min_static_dist=np.inf, solves=0)
         self._static_pts = [np.asarray(s, dtype=np.float64) for s in scene_raw(statics, par)]
+        # audit: every round also audits, on the device, the records it uploads anyway over the replan_every ticks about to be flown
+        # (nep_batch_audit; those ticks lie before the round's point A, so the uploaded records describe them); _tick keeps its host log
+        self.d_audit = self.be.new_audit() if audit else None
 
     # ---- records every agent publishes (publishOwnTraj) ----
     def _records(self, t_from):
@@ -102,6 +106,10 @@ class FleetLoop:
             self._d_active.copy_(torch.from_numpy((~self.done).astype(np.int32)).reshape(1, N))
         self.stats["solves"] += int((~self.done).sum()) if self.skip_arrived else N
         d_com = be.to_device(rec); d_start = be.to_device(starts)
+        if self.d_audit is not None:
+            clock = np.zeros(N, dtype=abi.FE_START_DTYPE)
+            clock["t_start"] = t_now + self.dc      # the first tick about to be flown
+            be.audit(d_com, be.to_device(clock), self.dc, self.replan_every, self.d_audit)
         d_guess = torch.zeros(N * abi.GUESS_DTYPE.itemsize, dtype=torch.uint8, device=be.device)
         d_fres = torch.zeros(N * abi.FE_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=be.device)
         be.frontend(self.fe, d_com, d_start, d_guess, d_fres)
@@ -151,7 +159,13 @@ class FleetLoop:
         self.stats["sim_time"] = self.t
         self.stats["reached"] = int(self.done.sum())
         self.stats["dist_to_goal_mean"] = float(np.hypot(*(self.state[:, :2] - self.goals[:, :2]).T).mean())
+        if self.d_audit is not None:
+            self.stats["audit"] = audit_mod.summarize(self.audit_records())[0]
         return self.stats
+
+    def audit_records(self):
+        """the flight audit so far: [N] AUDIT_DTYPE"""
+        return self.d_audit.cpu().numpy().view(abi.AUDIT_DTYPE)
 
     def close(self):
         self.be.close()
@@ -182,9 +196,11 @@ class TetherLoop:
     round's A (publishOwnTraj at replan time); the tracking then sees the previous round's lists as the previous check's and
     writes the bend points of the next A into the flown records.  `active` ([S, N] int32 device tensor) is the handle's active set
     (nep_batch_set_active).  check=False flies the same rounds with the entangle check of
-    the front end and of the safety pass off (plain nep_batch_frontend / nep_batch_safety_commit) and the tracking still on."""
+    the front end and of the safety pass off (plain nep_batch_frontend / nep_batch_safety_commit) and the tracking still on.
+    audit=True adds the flight audit (nep_batch_audit) of the round's final records over the control ticks of the stretch the round
+    flies, inside the graph, after the copy into d_rec and before next_starts; report() then carries its summary."""
 
-    def __init__(self, scenes, beam_width=16, n_intervals=1, ent_samples=3, check=True, device=None, graph=True, active=None):
+    def __init__(self, scenes, beam_width=16, n_intervals=1, ent_samples=3, check=True, device=None, graph=True, active=None, audit=False):
         import dataclasses
         import torch
         from neptune_amd import dist as ndist
@@ -219,6 +235,11 @@ class TetherLoop:
         self.rounds = 0
         self.ever_flagged = np.zeros((S, N), dtype=np.int32)
         self._g = None
+        self.audit_ticks = int(round(n_intervals * p.T_span / p.dc))
+        self.d_audit = None
+        if audit:
+            self.d_audit = be.new_audit()
+            be.audit(self.d_rec, self.d_start, p.dc, 0, self.d_audit)      # (the call that allocates: made here, outside any capture)
 
     def _publish(self, d_new):
         """stamp the bend points of every agent's state at the round's A into its new records (publishOwnTraj at replan time): the
@@ -247,6 +268,8 @@ class TetherLoop:
                      ent_samples=self.ent_samples)
         self.d_rec_prev.copy_(self.d_rec)
         self.d_rec.copy_(self.d_final)
+        if self.d_audit is not None:
+            be.audit(self.d_rec, self.d_start, self.p.dc, self.audit_ticks, self.d_audit)
         be.next_starts(self.d_rec, self.n_intervals * self.p.T_span, self.d_start)
 
     def round(self):
@@ -281,9 +304,16 @@ class TetherLoop:
         st = self.d_start.cpu().numpy().view(abi.FE_START_DTYPE).reshape(self.S, self.N)
         d = np.hypot(st["pos"][..., 0] - self.goals[..., 0], st["pos"][..., 1] - self.goals[..., 1])
         nb = self.states()["n_bend"]
-        return dict(rounds=self.rounds, arrived=[int(x) for x in (d < 2 * self.fe.goal_size).sum(axis=1)],
-                    ever_entangled=[int(x) for x in self.ever_flagged.sum(axis=1)],
-                    bend_hist=[int(x) for x in np.bincount(nb.reshape(-1), minlength=abi.NEP_MAX_BEND)[:abi.NEP_MAX_BEND]])
+        rep = dict(rounds=self.rounds, arrived=[int(x) for x in (d < 2 * self.fe.goal_size).sum(axis=1)],
+                   ever_entangled=[int(x) for x in self.ever_flagged.sum(axis=1)],
+                   bend_hist=[int(x) for x in np.bincount(nb.reshape(-1), minlength=abi.NEP_MAX_BEND)[:abi.NEP_MAX_BEND]])
+        if self.d_audit is not None:
+            rep["audit"] = audit_mod.summarize(self.audit_records(), self.S)
+        return rep
+
+    def audit_records(self):
+        """the flight audit so far: [S, N] AUDIT_DTYPE"""
+        return self.d_audit.cpu().numpy().view(abi.AUDIT_DTYPE).reshape(self.S, self.N)
 
     def close(self):
         self._g = None

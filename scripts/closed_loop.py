@@ -2,7 +2,7 @@
 """Closed-loop flight of a fleet on the device path (neptune_amd/loop.py): every agent flies from its
 start next to its base to a random goal, replanning in bulk-synchronous rounds, the way the reference's
 benchmark driver logs a run (scripts/benchmark_mtlp.py:215-223: elapsed time, distance, success).
-  python scripts/closed_loop.py [--agents 16 --obstacles 8 --seed 0 --beam 32 --skip-arrived]"""
+  python scripts/closed_loop.py [--agents 16 --obstacles 8 --seed 0 --beam 32 --skip-arrived --audit]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from neptune_amd import scene
@@ -12,11 +12,25 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--agents", type=int, default=16); ap.add_argument("--obstacles", type=int, default=8)
 ap.add_argument("--seed", type=int, default=0); ap.add_argument("--beam", type=int, default=32); ap.add_argument("--max-rounds", type=int, default=400)
 ap.add_argument("--skip-arrived", action="store_true", help="arrived agents leave the active set (nep_batch_set_active) instead of being solved and discarded")
+ap.add_argument("--audit", action="store_true", help="flight audit on the device (nep_batch_audit) next to the host's distance log")
 a = ap.parse_args()
 sc = scene.make_scene(a.agents, a.obstacles, seed=a.seed)
 t0 = time.perf_counter()
-loop = FleetLoop(sc["par"], sc["statics"], sc["starts"], scene.reachable_goals(sc), beam_width=a.beam, skip_arrived=a.skip_arrived)
+loop = FleetLoop(sc["par"], sc["statics"], sc["starts"], scene.reachable_goals(sc), beam_width=a.beam, skip_arrived=a.skip_arrived, audit=a.audit)
+if a.audit:
+    loop.trace = []
 st = loop.run(a.max_rounds)
 st["wall_s"] = time.perf_counter() - t0
 st["success"] = bool(st["reached"] == a.agents)
+summary = st.pop("audit", None)
 print(json.dumps({k: (float(v) if hasattr(v, "dtype") else v) for k, v in st.items()}))
+if summary is not None:
+    from neptune_amd import audit
+    for line in audit.format_summary([summary]):
+        print(line)
+    # the replans of the round the smallest box clearance fell into, for the agent and its partner: (round start, agent, outcome, K, fe, qp)
+    m = summary["min_box_clear"]
+    if m is not None:
+        rounds = sorted({t for t, *_ in loop.trace})
+        t_r = max([t for t in rounds if t < m["t"] - 1e-9], default=rounds[0])
+        print("audit min_box_clear fell into the round at t = %.3f s:" % t_r, [e[1:] for e in loop.trace if e[0] == t_r and e[1] + 1 in (m["agent"], m["partner"])])
