@@ -4,14 +4,15 @@
 //   * projecting a feasible theta gives its z back
 //   * Hax HaxInv = I
 // Prints "ok" or the first violation; tests/test_abi.py compiles and runs it (no GPU, no HIP).
+// usage: tables_check [T_span [weight]]   (defaults 0.5 and 1000: the values of the shipped benchmark yaml)
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 
 #include "../../neptune_amd/csrc/nep_tables.h"
 
-int main() {
-  const double T = 0.5, w = 1000.0;
+int main(int argc, char** argv) {
+  const double T = argc > 1 ? std::atof(argv[1]) : 0.5, w = argc > 2 ? std::atof(argv[2]) : 1000.0;
   double worst = 0;
   for (int mode = 0; mode < 2; mode++) for (int K = 1; K <= nep::kMaxK; K++) {
     nep::QpTable t; nep::build_qp_table(K, T, w, mode, &t);
@@ -24,7 +25,9 @@ int main() {
     }
     for (int a = 0; a < nz; a++) for (int b = 0; b < nz; b++) {   // HaxInv is the inverse of Hax (the presolve's unconstrained minimiser)
       double v = 0; for (int c = 0; c < nz; c++) v += t.Hax[a][c] * t.HaxInv[c][b];
-      if (std::fabs(v - (a == b ? 1.0 : 0.0)) > 1e-9) { std::printf("Hax HaxInv != I at K=%d mode=%d (%d,%d): %g\n", K, mode, a, b, v); return 1; }
+      // (Hax's entries grow with the weight — 1.2e6 at 1000, 1.2e8 at 1e5 — and the residual of a Gauss-Jordan inverse with them: 5e-11 / 9e-9 measured,
+      //  1e-14 of the summed |terms| both times; the bar set at weight 1000 is kept there and scales with the weight above it)
+      if (std::fabs(v - (a == b ? 1.0 : 0.0)) > 1e-9 * std::fmax(1.0, w / 1000.0)) { std::printf("Hax HaxInv != I at K=%d mode=%d (%d,%d): %g\n", K, mode, a, b, v); return 1; }
     }
     // a feasible theta from a pseudo-random z and init
     double z[nep::kNZ], init[3] = {0.3, -1.1, 2.0}, th[4 * nep::kMaxK];

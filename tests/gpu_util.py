@@ -44,11 +44,15 @@ def solver_lines_match(s, r, ordered=False):
     assert got == want
 
 
-def _check_scene(be, oracle, sc, n_scenes=1, first_local=0, n_local=None):
+def _check_scene(be, oracle, sc, n_scenes=1, first_local=0, n_local=None, hull_kernel=0, replans=1, info=None):
     """Every replan of a scene against the oracle, on BOTH solve paths of the handle: `full` = every separating-line row through the
     interior point (nep_batch_set_line_cull(0): lines bit-exact in the reference's call order, LP / row counts), and the handle's
     default = the verified line presolve with the polish pass under it (statuses, coefficients, cost, samples, commit records to the
-    same tolerances; its line buckets hold the near lines first and never-made lines are absent, so lines are checked as a subset)."""
+    same tolerances; its line buckets hold the near lines first and never-made lines are absent, so lines are checked as a subset).
+    hull_kernel: nep_batch_set_hull_kernel on both handles; replans: the replan is enqueued that many times on the same handle and the
+    last one is checked (what a handle does from its second round on); info: a dict that receives what the caller asserts on top —
+    the oracle's results per agent id (`refs`), per mode the worst coefficient error (`worst`), the launch path (`path`) and the
+    presolve's redo count (`redo`)."""
     p = sc["par"]
     worst = 0.0
     refs = {}
@@ -58,9 +62,13 @@ def _check_scene(be, oracle, sc, n_scenes=1, first_local=0, n_local=None):
             bb.set_line_cull(0.0)
         else:
             assert bb.line_cull() == 4.0          # the default at every size (round 6)
+        if hull_kernel:
+            bb.set_hull_kernel(hull_kernel)
         nl = bb.n_local
         d_comm = bb.to_device(sc["committed"]); d_guess = bb.to_device(sc["guesses"][first_local:first_local + nl])
-        bb.replan(d_comm, d_guess)
+        for _ in range(replans):
+            bb.replan(d_comm, d_guess)
+        worst_mode = 0.0
         sol = bb.solutions(); states = bb.states(); com = bb.commits()
         hx, hn = bb.debug_hulls(0)
         for a in range(nl):
@@ -90,7 +98,7 @@ def _check_scene(be, oracle, sc, n_scenes=1, first_local=0, n_local=None):
             assert int(st["status"]) == r["status"] and int(st["n_lines"]) == r["n_lines"], (mode, aid)
             assert int(st["n_lp"]) == r["n_lp"] and int(st["n_lp_failed"]) == r["n_lp_failed"], (mode, aid)
             co = np.array(sol[a]["coeff"])[:, :K, :]
-            err = np.abs(co - r["coeff"]).max(); worst = max(worst, err)
+            err = np.abs(co - r["coeff"]).max(); worst = max(worst, err); worst_mode = max(worst_mode, err)
             assert err <= COEF_TOL, (mode, aid, err)
             if r["status"] != 2:
                 assert abs(float(st["objective"]) - r["objective"]) <= COST_RTOL * (1 + abs(r["objective"])), (mode, aid)
@@ -101,5 +109,94 @@ def _check_scene(be, oracle, sc, n_scenes=1, first_local=0, n_local=None):
             np.testing.assert_allclose(np.array(sol[a]["times"])[:K + 1], t0 + np.arange(K + 1) * p.T_span, atol=1e-12)
             assert int(com[a]["id"]) == aid and int(com[a]["pwp"]["n_seg"]) == K
             np.testing.assert_array_equal(np.array(com[a]["pwp"]["coeff"])[:, :K, :], co)
+        if info is not None:
+            info.setdefault("worst", {})[mode] = worst_mode
+            info.setdefault("path", {})[mode] = bb.debug_launch_path()
+            info.setdefault("redo", {})[mode] = bb.redo_count() if mode == "default" else 0
+            info["refs"] = refs
         bb.close()
     return worst
+
+
+def check_frontend_beam(be, oracle, sc, W, near=(0.9, 0.3)):
+    """The front-end kernel against the deterministic beam rule of the oracle: results and guesses (lattice primitives) identical,
+    the same with pad_hold on goals `near` the starts (short searches), then the back end on the device-made guesses against the
+    oracle.  -> (guesses found, short guesses padded)"""
+    p = sc["par"]; N = p.num_agents
+    fe = scene.frontend_cfg(p, beam_width=W)
+    starts = scene.frontend_starts(sc)
+    bb = be.BatchBackend(p, sc["statics"])
+    d_com = bb.to_device(sc["committed"])
+    d_start = bb.to_device(starts)
+    d_guess = bb.torch.zeros(N * abi.GUESS_DTYPE.itemsize, dtype=bb.torch.uint8, device=bb.device)
+    d_res = bb.torch.zeros(N * abi.FE_RESULT_DTYPE.itemsize, dtype=bb.torch.uint8, device=bb.device)
+    bb.frontend(fe, d_com, d_start, d_guess, d_res)
+    bb.torch.cuda.synchronize()
+    got_g = d_guess.cpu().numpy().view(abi.GUESS_DTYPE)
+    got_r = d_res.cpu().numpy().view(abi.FE_RESULT_DTYPE)
+    n_ok = 0
+    for a in range(N):
+        hx, hn = oracle.hulls_of_scene(p, a + 1, sc["committed"], float(starts[a]["t_start"]), sc["statics"])
+        g, r = oracle.frontend_beam(p, fe, a + 1, starts[a], hx, hn, sc["statics"])
+        for f in abi.FE_RESULT_DTYPE.names:
+            assert got_r[a][f] == r[f], (a, f, got_r[a][f], r[f])
+        assert int(got_g[a]["K"]) == int(g["K"]) and got_g[a]["t_start"] == g["t_start"]
+        np.testing.assert_array_equal(got_g[a]["coeff"], g["coeff"])
+        n_ok += int(g["K"]) > 0
+    # pad_hold: short guesses extended with segments holding their end point — same on both sides
+    fe_pad = scene.frontend_cfg(p, beam_width=W, pad_hold=1)
+    starts_near = starts.copy()
+    starts_near["goal"][:, :2] = starts_near["pos"][:, :2] + list(near)          # goals one or two segments away: short searches
+    d_g2 = bb.torch.zeros_like(d_guess)
+    bb.frontend(fe_pad, d_com, bb.to_device(starts_near), d_g2)
+    bb.torch.cuda.synchronize()
+    got2 = d_g2.cpu().numpy().view(abi.GUESS_DTYPE)
+    n_short = 0
+    for a in range(N):
+        hx, hn = oracle.hulls_of_scene(p, a + 1, sc["committed"], float(starts[a]["t_start"]), sc["statics"])
+        g, r = oracle.frontend_beam(p, fe_pad, a + 1, starts_near[a], hx, hn, sc["statics"])
+        assert int(got2[a]["K"]) == int(g["K"])
+        np.testing.assert_array_equal(got2[a]["coeff"], g["coeff"])
+        if 0 < r["K"] < p.num_pol:
+            n_short += 1
+            assert int(g["K"]) == p.num_pol and (np.array(g["coeff"])[:2, r["K"]:, :3] == 0).all()
+    # the back end on the device-made guesses
+    bb.replan(d_com, d_guess)
+    sol = bb.solutions()
+    for a in range(N):
+        K = int(got_g[a]["K"])
+        if K == 0:
+            continue
+        r = oracle.replan(p, a + 1, sc["committed"], got_g[a], sc["statics"])
+        assert int(sol[a]["stats"]["status"]) == r["status"], a
+        assert np.abs(np.array(sol[a]["coeff"])[:, :K, :] - r["coeff"]).max() <= COEF_TOL
+    bb.close()
+    return n_ok, n_short
+
+
+def check_safety_commit(be, oracle, scenes):
+    """Conflict matrix (GJK on the new trajectories' hulls), id-ordered resolution and the committed records of two 8-agent scenes,
+    bit for bit against the oracle.  Scene 0: agents 6 and 8 fly copies of agent 2's trajectory 0.5 / 0.6 m next to it; scene 1
+    untouched.  -> (handle, prev, fresh, d_prev, d_gue, d_final, d_acc, accept [2][8]): the caller closes the handle."""
+    p = scenes[0]["par"]
+    prev = np.stack([s["committed"] for s in scenes])
+    fresh = prev.copy()
+    for tgt, dx in ((5, 0.5), (7, -0.6)):
+        fresh[0, tgt] = fresh[0, 1]; fresh[0, tgt]["id"] = tgt + 1
+        fresh[0, tgt]["pwp"]["coeff"][0, :, 3] += dx
+    fresh["pos"][:] += 0.01                                      # make new != prev everywhere
+    gue = np.stack([s["guesses"] for s in scenes])
+    bb = be.BatchBackend(p, [], n_scenes=2)
+    d_prev = bb.to_device(prev); d_new = bb.to_device(fresh); d_gue = bb.to_device(gue)
+    d_final = bb.torch.zeros_like(d_prev); d_acc = bb.torch.zeros(2 * 8, dtype=bb.torch.int32, device=bb.device)
+    bb.safety_commit(d_prev, d_new, d_gue, d_final, d_acc)
+    acc = d_acc.cpu().numpy().reshape(2, 8)
+    fin = d_final.cpu().numpy().view(abi.TRAJ_REC_DTYPE).reshape(2, 8)
+    for s_ in range(2):
+        conflict, accept = oracle.safety_resolve(fresh[s_], 0.0, p.T_span, p.drone_radius)
+        np.testing.assert_array_equal(bb.debug_conflicts(s_), conflict)
+        np.testing.assert_array_equal(acc[s_], accept)
+        for a in range(8):
+            want = fresh[s_, a] if accept[a] else prev[s_, a]
+            assert fin[s_, a].tobytes() == want.tobytes()
+    return bb, prev, fresh, d_prev, d_gue, d_final, d_acc, acc

@@ -11,13 +11,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def load_qp_cases(name="qp_cases.npz"):
     """qp_cases.npz: the round-1 set (make_golden.py); qp_cases_r2.npz: BASELINE config-4 / config-5 sizes, K = 7 and
-    front-end guesses (make_golden_r2.py), each accepted on a KKT certificate."""
+    front-end guesses (make_golden_r2.py), each accepted on a KKT certificate; qp_cases_params.npz: away from the default
+    parameter point, with z motion (make_golden_params.py)."""
     d = np.load(os.path.join(ROOT, "tests", "golden", name), allow_pickle=True)
     out = []
     for i in range(int(d["n"])):
         c = {k[len("c%d_" % i):]: d[k] for k in d.files if k.startswith("c%d_" % i)}
         c["tag"] = str(c["tag"]); c["K"] = int(c["K"]); c["status"] = int(c["status"])
         c["cost"] = float(c["cost"]); c["dth"] = float(c["dth"]); c["dcost"] = float(c["dcost"])
+        if "set" in c:      # qp_cases_params.npz (make_golden_params.py): the set of tests/param_sets.py a case was drawn at
+            c["set"] = str(c["set"]); c["num_pol"] = int(c["num_pol"]); c["n_active_z"] = int(c["n_active_z"]); c["certified"] = bool(c["certified"])
         out.append(c)
     return out
 
@@ -28,6 +31,7 @@ def params_of_case(c):
     p.x_min, p.y_min, p.z_min = [float(x) for x in c["mins"]]
     p.x_max, p.y_max, p.z_max = [float(x) for x in c["maxs"]]
     p.T_span = float(c["T"]); p.weight = float(c["weight"]); p.v_max = float(c["v_max"]); p.a_max = float(c["a_max"])
+    p.num_pol = int(c["num_pol"]) if "num_pol" in c else 8
     return p
 
 

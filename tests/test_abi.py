@@ -117,6 +117,10 @@ def test_reduced_qp_tables_are_consistent(tmp_path):
     subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(ROOT, "tests", "cpp", "tables_check.cpp"), "-o", exe])
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout
+    # away from the shipped yaml's T_span / weight (tests/param_sets.py: exp, fast_long, heavy)
+    for T, w in ((0.3, 1000.0), (1.0, 10.0), (0.5, 1e5)):
+        out = subprocess.run([exe, repr(T), repr(w)], capture_output=True, text=True)
+        assert out.returncode == 0 and out.stdout.startswith("ok"), (T, w, out.stdout)
 
 
 def test_headers_are_plain_c99():

@@ -5,7 +5,7 @@ import pytest
 
 import helpers
 from neptune_amd import abi, scene
-from gpu_util import COEF_TOL
+from gpu_util import COEF_TOL, check_frontend_beam, check_safety_commit
 
 pytestmark = pytest.mark.gpu
 
@@ -44,57 +44,9 @@ def test_frontend_beam_matches_the_oracle_bit_for_bit(be, oracle, n_agents, n_st
     """the front-end kernel against the deterministic beam rule of the oracle — the
     guesses (lattice primitives) must be identical, then the back end runs on the device-made guesses."""
     sc = scene.make_scene(n_agents, n_static, seed=seed)
-    p = sc["par"]; N = p.num_agents
-    fe = scene.frontend_cfg(p, beam_width=W)
-    starts = scene.frontend_starts(sc)
-    bb = be.BatchBackend(p, sc["statics"])
-    d_com = bb.to_device(sc["committed"])
-    d_start = bb.to_device(starts)
-    d_guess = bb.torch.zeros(N * abi.GUESS_DTYPE.itemsize, dtype=bb.torch.uint8, device=bb.device)
-    d_res = bb.torch.zeros(N * abi.FE_RESULT_DTYPE.itemsize, dtype=bb.torch.uint8, device=bb.device)
-    bb.frontend(fe, d_com, d_start, d_guess, d_res)
-    bb.torch.cuda.synchronize()
-    got_g = d_guess.cpu().numpy().view(abi.GUESS_DTYPE)
-    got_r = d_res.cpu().numpy().view(abi.FE_RESULT_DTYPE)
-    n_ok = 0
-    for a in range(N):
-        hx, hn = oracle.hulls_of_scene(p, a + 1, sc["committed"], float(starts[a]["t_start"]), sc["statics"])
-        g, r = oracle.frontend_beam(p, fe, a + 1, starts[a], hx, hn, sc["statics"])
-        for f in abi.FE_RESULT_DTYPE.names:
-            assert got_r[a][f] == r[f], (a, f, got_r[a][f], r[f])
-        assert int(got_g[a]["K"]) == int(g["K"]) and got_g[a]["t_start"] == g["t_start"]
-        np.testing.assert_array_equal(got_g[a]["coeff"], g["coeff"])
-        n_ok += int(g["K"]) > 0
-    assert n_ok >= N - 1
-    # pad_hold: short guesses extended with segments holding their end point — same on both sides
-    fe_pad = scene.frontend_cfg(p, beam_width=W, pad_hold=1)
-    starts_near = starts.copy()
-    starts_near["goal"][:, :2] = starts_near["pos"][:, :2] + [0.9, 0.3]          # goals one or two segments away: short searches
-    d_g2 = bb.torch.zeros_like(d_guess)
-    bb.frontend(fe_pad, d_com, bb.to_device(starts_near), d_g2)
-    bb.torch.cuda.synchronize()
-    got2 = d_g2.cpu().numpy().view(abi.GUESS_DTYPE)
-    n_short = 0
-    for a in range(N):
-        hx, hn = oracle.hulls_of_scene(p, a + 1, sc["committed"], float(starts[a]["t_start"]), sc["statics"])
-        g, r = oracle.frontend_beam(p, fe_pad, a + 1, starts_near[a], hx, hn, sc["statics"])
-        assert int(got2[a]["K"]) == int(g["K"])
-        np.testing.assert_array_equal(got2[a]["coeff"], g["coeff"])
-        if 0 < r["K"] < p.num_pol:
-            n_short += 1
-            assert int(g["K"]) == p.num_pol and (np.array(g["coeff"])[:2, r["K"]:, :3] == 0).all()
+    n_ok, n_short = check_frontend_beam(be, oracle, sc, W)        # (the body is shared with test_gpu_param_sweep.py)
+    assert n_ok >= sc["par"].num_agents - 1
     assert n_short >= 1
-    # the back end on the device-made guesses
-    bb.replan(d_com, d_guess)
-    sol = bb.solutions()
-    for a in range(N):
-        K = int(got_g[a]["K"])
-        if K == 0:
-            continue
-        r = oracle.replan(p, a + 1, sc["committed"], got_g[a], sc["statics"])
-        assert int(sol[a]["stats"]["status"]) == r["status"], a
-        assert np.abs(np.array(sol[a]["coeff"])[:, :K, :] - r["coeff"]).max() <= COEF_TOL
-    bb.close()
 
 
 def test_frontend_multi_scene_and_agent_shard(be, oracle):
@@ -181,27 +133,7 @@ def test_safety_check_and_commit(be, oracle):
     resolution and the committed records, bit for bit against the oracle."""
     scenes = [scene.make_scene(8, 0, seed=60 + s) for s in range(2)]
     p = scenes[0]["par"]
-    prev = np.stack([s["committed"] for s in scenes])
-    fresh = prev.copy()
-    # scene 0: agent 6 and 8 fly copies of agent 2's trajectory next to it; scene 1 untouched
-    for tgt, dx in ((5, 0.5), (7, -0.6)):
-        fresh[0, tgt] = fresh[0, 1]; fresh[0, tgt]["id"] = tgt + 1
-        fresh[0, tgt]["pwp"]["coeff"][0, :, 3] += dx
-    fresh["pos"][:] += 0.01                                      # make new != prev everywhere
-    gue = np.stack([s["guesses"] for s in scenes])
-    bb = be.BatchBackend(p, [], n_scenes=2)
-    d_prev = bb.to_device(prev); d_new = bb.to_device(fresh); d_gue = bb.to_device(gue)
-    d_final = bb.torch.zeros_like(d_prev); d_acc = bb.torch.zeros(2 * 8, dtype=bb.torch.int32, device=bb.device)
-    bb.safety_commit(d_prev, d_new, d_gue, d_final, d_acc)
-    acc = d_acc.cpu().numpy().reshape(2, 8)
-    fin = d_final.cpu().numpy().view(abi.TRAJ_REC_DTYPE).reshape(2, 8)
-    for s_ in range(2):
-        conflict, accept = oracle.safety_resolve(fresh[s_], 0.0, p.T_span, p.drone_radius)
-        np.testing.assert_array_equal(bb.debug_conflicts(s_), conflict)
-        np.testing.assert_array_equal(acc[s_], accept)
-        for a in range(8):
-            want = fresh[s_, a] if accept[a] else prev[s_, a]
-            assert fin[s_, a].tobytes() == want.tobytes()
+    bb, prev, fresh, d_prev, d_gue, d_final, d_acc, acc = check_safety_commit(be, oracle, scenes)      # (shared with test_gpu_param_sweep.py)
     assert list(acc[0]) == [1, 1, 1, 1, 1, 0, 1, 0] and acc[1].all()
     # with the previous-record check: scene 1's agent 5 now flies along agent 3's PREVIOUS path while agent 3's new
     # trajectory is far away — no new-new conflict, but agent 3 might be turned down and keep that previous path

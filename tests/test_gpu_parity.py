@@ -142,10 +142,11 @@ def test_separator_edge_cases(be, oracle):
     assert list(ok) == [True, False, True, True, False]
 
 
-@pytest.mark.parametrize("fixture", ["qp_cases.npz", "qp_cases_r2.npz"])
+@pytest.mark.parametrize("fixture", ["qp_cases.npz", "qp_cases_r2.npz", "qp_cases_params.npz"])
 def test_qp_against_golden(be, oracle, fixture):
     """qp_cases_r2.npz: BASELINE config-4 size (~510 lines, LDS placement), config-5 size (~2 050 lines: the global-spill
-    placement of the row state), K = 7, front-end guesses — each a KKT-certified optimum."""
+    placement of the row state), K = 7, front-end guesses — each a KKT-certified optimum.  qp_cases_params.npz: away from the
+    default parameter point, with z motion (tests/param_sets.py, make_golden_params.py)."""
     seen = set()
     for c in helpers.load_qp_cases(fixture):
         p = helpers.params_of_case(c)
