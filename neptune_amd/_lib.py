@@ -48,6 +48,9 @@ PLAN_EXPORTS = [
 # every symbol include/neptune_entangle.h declares (host-only)
 # include/neptune_frontend.h
 FE_EXPORTS = ["nep_batch_frontend", "nep_batch_frontend_hulls", "nep_batch_set_static_reps", "nep_batch_set_fe_ent_big_records", "nep_batch_frontend_ent", "nep_batch_frontend_ent_hulls", "nep_batch_safety_commit_ent", "nep_batch_track_ent", "nep_batch_next_starts", "nep_batch_audit", "nep_audit_records", "nep_audit_init"]
+# include/neptune_fleet.h
+FLEET_EXPORTS = ["nep_batch_fleet_init", "nep_batch_fleet_select", "nep_batch_fleet_commit", "nep_batch_fleet_tick", "nep_batch_fleet_ring_cap",
+                 "nep_batch_fleet_plans", "nep_batch_fleet_state", "nep_batch_fleet_counters"]
 ENT_EXPORTS = ["nep_ent_sample_points", "nep_ent_propagate_segment", "nep_ent_propagate_guess", "nep_ent_case_ids", "nep_ent_track_step"]
 
 
@@ -187,6 +190,14 @@ def lib():
     L.nep_batch_audit.argtypes = [vp, vp, vp, d, i, vp, vp]
     L.nep_audit_records.argtypes = [vp, i, pi, pd, i, d, d, d, i, vp]
     L.nep_audit_init.argtypes = [vp, C.c_int64]
+    L.nep_batch_fleet_init.argtypes = [vp, C.POINTER(abi.nep_fleet_cfg), vp, vp, vp, vp, vp]
+    L.nep_batch_fleet_select.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.nep_batch_fleet_commit.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.nep_batch_fleet_tick.argtypes = [vp, vp]
+    L.nep_batch_fleet_ring_cap.argtypes = [vp]
+    L.nep_batch_fleet_plans.argtypes = [vp, i, i, pd, pi]
+    L.nep_batch_fleet_state.argtypes = [vp, pd, vp, pi, pi, pi, pi, pi]
+    L.nep_batch_fleet_counters.argtypes = [vp, pi, pd, pi]
     L.nep_batch_frontend_ent_hulls.argtypes = [vp, C.POINTER(abi.nep_fe_cfg), vp, i, vp, vp, vp, vp, vp, vp]
     L.nep_batch_exchange_slots.argtypes = [vp, vp, vp, vp, C.c_int64, vp]
     L.nep_batch_set_ent_samples.argtypes = [vp, i]
@@ -195,7 +206,7 @@ def lib():
     # them at another stride): fail loudly at load, not as wrong numbers later
     L.nep_abi_sizeof.argtypes = [i]; L.nep_abi_sizeof.restype = i
     for which, struct in ((1, abi.nep_traj_rec), (5, abi.nep_guess), (6, abi.nep_solution), (11, abi.nep_fe_cfg), (12, abi.nep_fe_start),
-                          (13, abi.nep_fe_result), (14, abi.nep_fe_ent_state), (17, abi.nep_audit)):
+                          (13, abi.nep_fe_result), (14, abi.nep_fe_ent_state), (17, abi.nep_audit), (18, abi.nep_fleet_cfg)):
         if L.nep_abi_sizeof(which) != C.sizeof(struct):
             raise BackendError("%s: sizeof(%s) is %d in the library, %d in neptune_amd/abi.py — rebuild the library from this tree's headers"
                                % (LIB_PATH, struct.__name__, L.nep_abi_sizeof(which), C.sizeof(struct)))

@@ -166,6 +166,21 @@ class nep_audit(C.Structure):
                 ("n_ticks", C.c_int32), ("n_pair_viol", C.c_int32), ("n_static_viol", C.c_int32)]
 
 
+class nep_fleet_cfg(C.Structure):
+    """include/neptune_fleet.h: nep_plan_cfg's fields plus what a bulk-synchronous round needs (nep_batch_fleet_init)."""
+    _fields_ = [("dc", C.c_double), ("T_span", C.c_double), ("lower_bound_runtime", C.c_double),
+                ("upper_bound_runtime", C.c_double), ("runtime_opt", C.c_double), ("factor_alpha", C.c_double),
+                ("deltaT0", C.c_int32), ("k_a", C.c_int32), ("round_ticks", C.c_int32), ("ring_cap", C.c_int32),
+                ("goal_radius", C.c_double), ("t0", C.c_double)]
+
+
+# nep_batch_fleet_commit's outcomes, the per-scene counters' order (include/neptune_fleet.h)
+NEP_FLEET_SKIPPED, NEP_FLEET_FE_NO_SOLUTION, NEP_FLEET_QP_FAILED, NEP_FLEET_REJECTED, NEP_FLEET_ACCEPTED, NEP_FLEET_CAP = range(6)
+NEP_FLEET_N_COUNTERS = 8
+FLEET_OUTCOMES = ("skipped", "fe_no_solution", "qp_failed", "rejected_by_safety", "accepted", "cap")
+NEP_FLEET_FLAG_SEG, NEP_FLEET_FLAG_RING, NEP_FLEET_FLAG_SPLICE = 1, 2, 4
+
+
 def np_dtype(struct):
     return np.dtype(struct)
 
@@ -177,6 +192,7 @@ FE_START_DTYPE = np.dtype(nep_fe_start)
 FE_RESULT_DTYPE = np.dtype(nep_fe_result)
 FE_ENT_STATE_DTYPE = np.dtype(nep_fe_ent_state)
 AUDIT_DTYPE = np.dtype(nep_audit)
+PWP_DTYPE = np.dtype(nep_pwp)
 
 
 def dptr(a):

@@ -372,6 +372,62 @@ class BatchBackend:
         st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
         check(lib().nep_batch_audit(self._h, d_records.data_ptr(), d_start.data_ptr(), float(tick), int(n_ticks), d_audit.data_ptr(), st.cuda_stream))
 
+    # ---- the committed plans on the device (include/neptune_fleet.h) ---------------------------------------------
+    def fleet_init(self, cfg, d_state0, d_goal, d_period=None, d_phase=None, stream=None):
+        """allocates / re-seeds the fleet state (nep_batch_fleet_init): cfg abi.nep_fleet_cfg, d_state0 [slots][12] and d_goal [slots][3]
+        float64, d_period / d_phase [slots] int32 device tensors (both or neither)"""
+        st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        check(lib().nep_batch_fleet_init(self._h, C.byref(cfg), d_state0.data_ptr(), d_goal.data_ptr(),
+                                         d_period.data_ptr() if d_period is not None else None,
+                                         d_phase.data_ptr() if d_phase is not None else None, st.cuda_stream))
+        self.fleet_ring_cap = int(check(lib().nep_batch_fleet_ring_cap(self._h)))
+
+    def fleet_select(self, d_start, d_records, d_active=None, d_clock=None, stream=None):
+        """point A of every slot into d_start, the published records into d_records, the round's mask into d_active and the clock
+        of the audit of the ticks about to be flown into d_clock (nep_batch_fleet_select)"""
+        st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        check(lib().nep_batch_fleet_select(self._h, d_start.data_ptr(), d_records.data_ptr(), d_active.data_ptr() if d_active is not None else None,
+                                           d_clock.data_ptr() if d_clock is not None else None, st.cuda_stream))
+
+    def fleet_commit(self, d_fe_result, d_accept, d_outcome=None, stream=None):
+        """outcome of every slot; splice and composition of the accepted ones from this handle's d_solution / d_states (nep_batch_fleet_commit)"""
+        st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        check(lib().nep_batch_fleet_commit(self._h, self.d_solution.data_ptr(), self.d_states.data_ptr(), d_fe_result.data_ptr(), d_accept.data_ptr(),
+                                           d_outcome.data_ptr() if d_outcome is not None else None, st.cuda_stream))
+
+    def fleet_tick(self, stream=None):
+        """round_ticks control periods, the arrival test, the round counter (nep_batch_fleet_tick)"""
+        st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        check(lib().nep_batch_fleet_tick(self._h, st.cuda_stream))
+
+    def fleet_plans(self):
+        """every slot's plan, front first (blocking): list of [size][12] arrays (nep_batch_fleet_plans)"""
+        out = np.zeros((self.slots, self.fleet_ring_cap, abi.NEP_STATE_DOUBLES)); sizes = np.zeros(self.slots, dtype=np.int32)
+        check(lib().nep_batch_fleet_plans(self._h, 0, self.slots, abi.dptr(out), abi.iptr(sizes)))
+        return [out[s, :sizes[s]].copy() for s in range(self.slots)]
+
+    def fleet_state(self, pwp=True):
+        """per-slot fleet state (blocking) -> dict: state [slots][12], pwp [slots] PWP_DTYPE, flown / done / outcome / flags / k_end [slots]"""
+        n = self.slots
+        out = dict(state=np.zeros((n, 12)), pwp=np.zeros(n, dtype=abi.PWP_DTYPE) if pwp else None)
+        for k in ("flown", "done", "outcome", "flags", "k_end"):
+            out[k] = np.zeros(n, dtype=np.int32)
+        check(lib().nep_batch_fleet_state(self._h, abi.dptr(out["state"]), out["pwp"].ctypes.data if pwp else None, abi.iptr(out["flown"]),
+                                          abi.iptr(out["done"]), abi.iptr(out["outcome"]), abi.iptr(out["flags"]), abi.iptr(out["k_end"])))
+        return out
+
+    def fleet_done(self):
+        """the sticky arrival flags [slots] alone (blocking; one small download)"""
+        done = np.zeros(self.slots, dtype=np.int32)
+        check(lib().nep_batch_fleet_state(self._h, None, None, None, abi.iptr(done), None, None, None))
+        return done
+
+    def fleet_counters(self):
+        """(counters [n_scenes][NEP_FLEET_N_COUNTERS], clocks [n_scenes], round counters [n_scenes]) (blocking)"""
+        c = np.zeros((self.n_scenes, abi.NEP_FLEET_N_COUNTERS), dtype=np.int32); t = np.zeros(self.n_scenes); r = np.zeros(self.n_scenes, dtype=np.int32)
+        check(lib().nep_batch_fleet_counters(self._h, abi.iptr(c), abi.dptr(t), abi.iptr(r)))
+        return c, t, r
+
     def next_starts(self, d_records, dt, d_start, d_alt_goal=None, switch_radius=0.0, stream=None):
         """point A of the next round on the device: d_start's clock advances by dt and its state becomes that of the committed
         trajectories d_records at the new time; with d_alt_goal ([slots][3] float64) arrived agents swap goals

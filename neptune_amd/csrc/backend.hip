@@ -992,6 +992,14 @@ struct nep_batch {
   int slots = 0;
   const nep_traj_rec* fe_committed = nullptr;   // the records nep_batch_frontend built this round's hulls from
   int ent_ns = 3;                               // num_sample_per_interval the hull blocks reserve room for (nep_batch_set_ent_samples; yaml: 3)
+  // nep_batch_fleet_* (include/neptune_fleet.h): the committed plans of every slot, allocated by nep_batch_fleet_init
+  struct Fleet {
+    bool ready = false, timers = false; int cap = 0; nep_fleet_cfg cfg{};
+    DevBuf<double> ring, state, goal, t_now; DevBuf<nep_pwp> pwp;
+    DevBuf<int> head, size, k_end, flown, done, outcome, sflags, period, phase, round, counters;
+    void release() { ring.release(); state.release(); goal.release(); t_now.release(); pwp.release(); head.release(); size.release(); k_end.release(); flown.release();
+                     done.release(); outcome.release(); sflags.release(); period.release(); phase.release(); round.release(); counters.release(); ready = false; }
+  } fleet;
 };
 
 extern "C" {
@@ -1024,7 +1032,7 @@ nep_batch_t* nep_batch_create(const nep_batch_cfg* c) {
   return h;
 }
 
-void nep_batch_destroy(nep_batch_t* h) { if (!h) return; h->eng.release(); delete h; }
+void nep_batch_destroy(nep_batch_t* h) { if (!h) return; h->fleet.release(); h->eng.release(); delete h; }
 
 int64_t nep_batch_ent_bytes(const nep_batch_t* h) { return h ? (int64_t)h->slots * NEP_MAX_POL * h->cfg.num_agents * sizeof(int32_t) : 0; }
 
@@ -1449,6 +1457,147 @@ int nep_batch_audit(nep_batch_t* h, const nep_traj_rec* d_records, const nep_fe_
   return 0;
 }
 
+// ---- the committed plans on the device (include/neptune_fleet.h; kernels: fleet_kernels.hip) ----
+namespace {
+// a null handle without a device is "no device" (nothing could have made a handle), with one it is a bad argument
+int fleet_guard(nep_batch_t* h, bool need_ready) {
+  if (!h) return have_device() ? fail(NEP_E_ARG, "null handle") : fail(NEP_E_HIP, "no HIP device: the back end has no CPU path");
+  if (h->cfg.n_local != h->cfg.num_agents) return fail(NEP_E_STATE, "the fleet state lives on an unsharded handle (n_local == num_agents)");
+  if (need_ready && !h->fleet.ready) return fail(NEP_E_STATE, "nep_batch_fleet_init has not run on this handle");
+  return 0;
+}
+void fleet_args(nep_batch_t* h, FleetArgs& fa) {
+  nep_batch::Fleet& F = h->fleet;
+  fa.N = h->cfg.num_agents; fa.n_scenes = h->cfg.n_scenes; fa.cap = F.cap; fa.max_states = h->cfg.max_states; fa.cfg = F.cfg;
+  fa.drone_radius = h->eng.sp.drone_radius; fa.pb = h->eng.d_pb.p;
+  fa.ring = F.ring.p; fa.head = F.head.p; fa.size = F.size.p; fa.k_end = F.k_end.p; fa.state = F.state.p; fa.goal = F.goal.p; fa.pwp = F.pwp.p;
+  fa.flown = F.flown.p; fa.done = F.done.p; fa.outcome = F.outcome.p; fa.sflags = F.sflags.p;
+  fa.period = F.timers ? F.period.p : nullptr; fa.phase = F.timers ? F.phase.p : nullptr;
+  fa.t_now = F.t_now.p; fa.round = F.round.p; fa.counters = F.counters.p; fa.gflags = h->eng.d_flags.p; fa.active = h->eng.active;
+}
+}  // namespace
+
+int nep_batch_fleet_init(nep_batch_t* h, const nep_fleet_cfg* cfg, const double* d_state0, const double* d_goal, const int32_t* d_period,
+                         const int32_t* d_phase, void* stream) {
+  if (int e = fleet_guard(h, false)) return e;
+  if (!cfg || !d_state0 || !d_goal || (d_period == nullptr) != (d_phase == nullptr)) return fail(NEP_E_ARG, "null argument (period and phase come together)");
+  if (!(cfg->dc > 0.0) || !(cfg->T_span > 0.0) || cfg->deltaT0 < 1 || cfg->round_ticks < 1 || cfg->ring_cap < 0 || cfg->k_a < 0) return fail(NEP_E_ARG, "bad fleet configuration");
+  nep_batch::Fleet& F = h->fleet;
+  const size_t slots = (size_t)h->slots, S = (size_t)h->cfg.n_scenes;
+  const int cap = cfg->ring_cap > 0 ? cfg->ring_cap : cfg->deltaT0 + h->cfg.max_states;
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));      // (a re-seed: kernels of the previous flight may still read the state)
+  F.ready = false;
+  if (int e = F.ring.ensure(slots * cap * 12)) return e;
+  if (int e = F.state.ensure(slots * 12)) return e;
+  if (int e = F.goal.ensure(slots * 3)) return e;
+  if (int e = F.pwp.ensure(slots)) return e;
+  if (int e = F.t_now.ensure(S)) return e;
+  if (int e = F.round.ensure(S)) return e;
+  if (int e = F.counters.ensure(S * NEP_FLEET_N_COUNTERS)) return e;
+  for (DevBuf<int>* b : {&F.head, &F.size, &F.k_end, &F.flown, &F.done, &F.outcome, &F.sflags, &F.period, &F.phase})
+    if (int e = b->ensure(slots)) return e;
+  F.cap = cap; F.cfg = *cfg; F.timers = d_period != nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(hipMemcpyAsync(F.goal.p, d_goal, slots * 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
+  if (F.timers) {
+    HIPCHK(hipMemcpyAsync(F.period.p, d_period, slots * sizeof(int), hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(F.phase.p, d_phase, slots * sizeof(int), hipMemcpyDeviceToDevice, st));
+  }
+  FleetArgs fa{};
+  fleet_args(h, fa);
+  launch_fleet_seed(fa, d_state0, st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
+  F.ready = true;
+  return 0;
+}
+
+int nep_batch_fleet_select(nep_batch_t* h, nep_fe_start* d_start, nep_traj_rec* d_records, int32_t* d_active, nep_fe_start* d_clock, void* stream) {
+  if (int e = fleet_guard(h, true)) return e;
+  if (!d_start || !d_records) return fail(NEP_E_ARG, "null argument");
+  FleetArgs fa{};
+  fleet_args(h, fa);
+  fa.start = d_start; fa.recs = d_records; fa.active_out = d_active; fa.clock = d_clock;
+  launch_fleet_select(fa, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int nep_batch_fleet_commit(nep_batch_t* h, const nep_solution* d_solution, const double* d_states, const nep_fe_result* d_fe_result,
+                           const int32_t* d_accept, int32_t* d_outcome, void* stream) {
+  if (int e = fleet_guard(h, true)) return e;
+  if (!d_solution || !d_states || !d_fe_result || !d_accept) return fail(NEP_E_ARG, "null argument");
+  FleetArgs fa{};
+  fleet_args(h, fa);
+  fa.sol = d_solution; fa.states_in = d_states; fa.fres = d_fe_result; fa.accept = d_accept; fa.outcome_out = d_outcome;
+  launch_fleet_commit(fa, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int nep_batch_fleet_tick(nep_batch_t* h, void* stream) {
+  if (int e = fleet_guard(h, true)) return e;
+  FleetArgs fa{};
+  fleet_args(h, fa);
+  launch_fleet_tick(fa, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int nep_batch_fleet_ring_cap(nep_batch_t* h) {
+  if (int e = fleet_guard(h, true)) return e;
+  return h->fleet.cap;
+}
+
+int nep_batch_fleet_plans(nep_batch_t* h, int32_t first, int32_t n, double* states_out, int32_t* sizes) {
+  if (int e = fleet_guard(h, true)) return e;
+  if (first < 0 || n < 0 || first + n > h->slots) return fail(NEP_E_ARG, "slot range out of bounds");
+  if (n == 0) return 0;
+  nep_batch::Fleet& F = h->fleet;
+  const size_t per = (size_t)F.cap * 12;
+  std::vector<double> ring((size_t)n * per); std::vector<int> head(n), size(n);
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(ring.data(), F.ring.p + (size_t)first * per, ring.size() * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(head.data(), F.head.p + first, n * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(size.data(), F.size.p + first, n * sizeof(int), hipMemcpyDeviceToHost));
+  for (int i = 0; i < n; i++) {
+    if (head[i] < 0 || head[i] >= F.cap || size[i] < 0 || size[i] > F.cap) return fail(NEP_E_STATE, "a plan ring's head or size is out of range");
+    if (sizes) sizes[i] = size[i];
+    if (!states_out) continue;
+    double* o = states_out + (size_t)i * per;
+    std::memset(o, 0, per * sizeof(double));
+    for (int k = 0; k < size[i]; k++) std::memcpy(o + (size_t)k * 12, ring.data() + (size_t)i * per + (size_t)((head[i] + k) % F.cap) * 12, 12 * sizeof(double));
+  }
+  return 0;
+}
+
+int nep_batch_fleet_state(nep_batch_t* h, double* state_out, nep_pwp* pwp_out, int32_t* flown_out, int32_t* done_out, int32_t* outcome_out,
+                          int32_t* flags_out, int32_t* k_end_out) {
+  if (int e = fleet_guard(h, true)) return e;
+  nep_batch::Fleet& F = h->fleet;
+  const size_t slots = (size_t)h->slots;
+  HIPCHK(hipDeviceSynchronize());
+  if (state_out) HIPCHK(hipMemcpy(state_out, F.state.p, slots * 12 * sizeof(double), hipMemcpyDeviceToHost));
+  if (pwp_out) HIPCHK(hipMemcpy(pwp_out, F.pwp.p, slots * sizeof(nep_pwp), hipMemcpyDeviceToHost));
+  if (flown_out) HIPCHK(hipMemcpy(flown_out, F.flown.p, slots * sizeof(int), hipMemcpyDeviceToHost));
+  if (done_out) HIPCHK(hipMemcpy(done_out, F.done.p, slots * sizeof(int), hipMemcpyDeviceToHost));
+  if (outcome_out) HIPCHK(hipMemcpy(outcome_out, F.outcome.p, slots * sizeof(int), hipMemcpyDeviceToHost));
+  if (flags_out) HIPCHK(hipMemcpy(flags_out, F.sflags.p, slots * sizeof(int), hipMemcpyDeviceToHost));
+  if (k_end_out) HIPCHK(hipMemcpy(k_end_out, F.k_end.p, slots * sizeof(int), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int nep_batch_fleet_counters(nep_batch_t* h, int32_t* counters_out, double* t_now_out, int32_t* round_out) {
+  if (int e = fleet_guard(h, true)) return e;
+  nep_batch::Fleet& F = h->fleet;
+  const size_t S = (size_t)h->cfg.n_scenes;
+  HIPCHK(hipDeviceSynchronize());
+  if (counters_out) HIPCHK(hipMemcpy(counters_out, F.counters.p, S * NEP_FLEET_N_COUNTERS * sizeof(int), hipMemcpyDeviceToHost));
+  if (t_now_out) HIPCHK(hipMemcpy(t_now_out, F.t_now.p, S * sizeof(double), hipMemcpyDeviceToHost));
+  if (round_out) HIPCHK(hipMemcpy(round_out, F.round.p, S * sizeof(int), hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int nep_batch_next_starts(nep_batch_t* h, const nep_traj_rec* d_records, double dt, nep_fe_start* d_start, double* d_alt_goal,
                           double switch_radius, void* stream) {
   if (!h || !d_records || !d_start || !(dt >= 0.0)) return fail(NEP_E_ARG, "bad arguments");
@@ -1712,6 +1861,7 @@ int nep_batch_check(nep_batch_t* h, void* stream) {
   if (flags & NEP_FLAG_SCRATCH) return fail(NEP_E_CAP, "the presolve's redo pass listed more replans with rows beyond the register slots than the handle has scratch areas for: nep_batch_reserve_row_scratch");
   if (flags & NEP_FLAG_ENT_POOL) return fail(NEP_E_CAP, "the pool of big entangle-state records ran out (front end: children of a search were pruned for it, by claim order; safety re-check: a trajectory was turned down): nep_batch_set_fe_ent_big_records");
   if (flags & NEP_FLAG_ENT_TRACK) return fail(NEP_E_CAP, "nep_batch_track_ent: a tether's state outgrew NEP_FE_ENT_CAP crossings, NEP_MAX_BEND - 1 bend points or 32 new crossings in one step (the step was dropped), or a state handed in was malformed");
+  if (flags & NEP_FLAG_FLEET) return fail(NEP_E_CAP, "nep_batch_fleet_commit: an accepted plan or composed trajectory would have outgrown the ring (ring_cap states), NEP_TRAJ_MAX_SEG intervals, or A was already flown (the slot kept its plan: outcome NEP_FLEET_CAP, flags in nep_batch_fleet_state)");
   if (flags & NEP_FLAG_ENT_BETA) return fail(NEP_E_ARG, "an entangle state passed to the front end has a non-zero beta for an agent crossing (the reference's calculateBetaForCase makes it 0.0)");
   if (flags & NEP_FLAG_HULL_OVERFLOW) return fail(NEP_E_CAP, "an interval overlaps more than NEP_HULL_MAX_CP/4 committed segments (or its hull has more than NEP_HULL_MAX_V vertices)");
   return 0;
@@ -1806,6 +1956,7 @@ int nep_abi_sizeof(int32_t which) {
     case 14: return (int)sizeof(nep_fe_ent_state);
     case 15: return (int)sizeof(nep_ent_track_inputs);
     case 17: return (int)sizeof(nep_audit);      // (16 stays unassigned: tests/test_ent_track_cpu.py pins it to -1)
+    case 18: return (int)sizeof(nep_fleet_cfg);
     default: return -1;
   }
 }

@@ -6,6 +6,7 @@
 
 #include "nep_tables.h"
 #include "../../include/neptune_frontend.h"
+#include "../../include/neptune_fleet.h"
 #include "../../include/neptune_backend_debug.h"
 
 namespace nep {
@@ -119,6 +120,7 @@ struct ProblemSet {
 __device__ __forceinline__ bool slot_active(const SceneParams& sp, const int* active, int slot) {
   return active == nullptr || active[(long)(slot / sp.n_local) * sp.num_agents + sp.first_local + slot % sp.n_local] != 0;
 }
+constexpr int NEP_FLAG_FLEET = 64;           // nep_batch_fleet_commit: an accepted slot's plan or composed trajectory would have outgrown its storage (the slot kept both; NEP_FLEET_CAP)
 constexpr int NEP_FLAG_ENT_TRACK = 32;      // nep_batch_track_ent: a tracked state outgrew the fixed record (list, bend points or a step's crossings; the step was dropped) or was handed in malformed
 constexpr int NEP_FLAG_ENT_POOL = 16;       // the safety pass's entangle re-check needed a big record and the pool had none left (nep_batch_set_fe_ent_big_records): the trajectory was turned down
 constexpr int NEP_FLAG_LINES = 8;           // a segment got more separating lines than its bucket holds (nep_batch_set_line_capacity)
@@ -261,6 +263,33 @@ struct AuditArgs {
 };
 size_t audit_lds_bytes(int N, int S, int vstride);
 void launch_audit(const AuditArgs& aa, hipStream_t st);
+// nep_batch_fleet_* (fleet_kernels.hip, include/neptune_fleet.h): the committed plans of every slot.  All device pointers.
+struct FleetArgs {
+  int N, n_scenes, cap, max_states;
+  nep_fleet_cfg cfg;
+  double drone_radius;
+  const double* pb;              // [N][2]
+  // state of the slots and of the scenes (owned by the handle)
+  double* ring;                  // [slots][cap][12]
+  int* head; int* size; int* k_end;      // [slots]
+  double* state;                 // [slots][12]
+  double* goal;                  // [slots][3]
+  nep_pwp* pwp;                  // [slots]
+  int* flown; int* done; int* outcome; int* sflags;      // [slots]
+  const int* period; const int* phase;   // [slots] or both null
+  double* t_now; int* round;     // [scenes]
+  int* counters;                 // [scenes][NEP_FLEET_N_COUNTERS]
+  int* gflags;                   // sticky NEP_FLAG_FLEET
+  // select
+  nep_fe_start* start; nep_traj_rec* recs; int* active_out; nep_fe_start* clock;
+  // commit
+  const nep_solution* sol; const double* states_in; const nep_fe_result* fres; const int* accept; int* outcome_out;
+  const int* active;             // the handle's mask ([scenes][N]) or null
+};
+void launch_fleet_seed(const FleetArgs& fa, const double* state0, hipStream_t st);
+void launch_fleet_select(const FleetArgs& fa, hipStream_t st);
+void launch_fleet_commit(const FleetArgs& fa, hipStream_t st);
+void launch_fleet_tick(const FleetArgs& fa, hipStream_t st);
 void launch_ent_check(const SceneParams& sp, const ProblemSet& ps, const FeEntArgs& ea, const nep_traj_rec* fresh, int n_scenes, double cable, int* entangles, hipStream_t st);
 void launch_next_starts(const nep_traj_rec* recs, int n_scenes, int N, int first_local, int n_local, double dt, nep_fe_start* starts,
                         double* alt, double r_switch, hipStream_t st);

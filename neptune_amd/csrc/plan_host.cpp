@@ -10,7 +10,7 @@
 #include <deque>
 #include <new>
 
-#include "../../include/neptune_plan.h"
+#include "plan_common.h"
 
 namespace {
 
@@ -126,58 +126,11 @@ int nep_pwp_compose(double t, double /*dc*/, nep_pwp* p1, nep_pwp* p2, nep_pwp* 
 
 // Composition that describes the flown path exactly (an extension; see neptune_plan.h): every interval
 // carries the coefficients of the source interval that actually covers it, re-based to its own knot.
-static void rebase(const double c[4], double s, double o[4]) {      // q(w) = p(w + s)
-  o[0] = c[0];
-  o[1] = 3 * c[0] * s + c[1];
-  o[2] = (3 * c[0] * s + 2 * c[1]) * s + c[2];
-  o[3] = ((c[0] * s + c[1]) * s + c[2]) * s + c[3];
-}
-// p restricted to [t0, t1] appended to res (t0 < t1); beyond p's last knot the end point is held
-static bool append_span(nep_pwp* res, const nep_pwp* p, double t0, double t1) {
-  const int n = p->n_seg;
-  double a = t0;
-  while (a < t1) {
-    int k = 0;
-    while (k < n && p->times[k + 1] <= a) k++;
-    if (res->n_seg >= NEP_TRAJ_MAX_SEG) return false;
-    const int o = res->n_seg++;
-    double b;
-    if (k >= n) {                                   // past the end: hold the final point
-      b = t1;
-      const double T = p->times[n] - p->times[n - 1];
-      for (int ax = 0; ax < 3; ax++) {
-        double e[4]; rebase(p->coeff[ax][n - 1], T, e);
-        res->coeff[ax][o][0] = res->coeff[ax][o][1] = res->coeff[ax][o][2] = 0.0; res->coeff[ax][o][3] = e[3];
-      }
-    } else {
-      b = p->times[k + 1] < t1 ? p->times[k + 1] : t1;
-      const double s = a - p->times[k] > 0 ? a - p->times[k] : 0.0;    // (a before p's first knot: p's start is extended backwards)
-      for (int ax = 0; ax < 3; ax++) rebase(p->coeff[ax][k], a - p->times[k] < 0 ? a - p->times[k] : s, res->coeff[ax][o]);
-    }
-    res->times[o + 1] = b;
-    a = b;
-  }
-  return true;
-}
-
+// The arithmetic is plan_common.h's, which the device form (fleet_kernels.hip) shares.
 int nep_pwp_compose_exact(double t, const nep_pwp* p1, const nep_pwp* p2, nep_pwp* out) {
   if (!pwp_ok(p1) || !pwp_ok(p2) || !out || p1->n_seg < 1 || p2->n_seg < 1) return NEP_E_ARG;
   nep_pwp res;
-  std::memset(&res, 0, sizeof(res));
-  const double t2 = p2->times[0];
-  if (t < t2) {                                       // the old trajectory until the new one takes over
-    res.times[0] = t;
-    if (!append_span(&res, p1, t, t2)) return NEP_E_CAP;
-    for (int i = 0; i < p2->n_seg; i++) {
-      if (res.n_seg >= NEP_TRAJ_MAX_SEG) return NEP_E_CAP;
-      const int o = res.n_seg++;
-      res.times[o + 1] = p2->times[i + 1];
-      for (int ax = 0; ax < 3; ax++) std::memcpy(res.coeff[ax][o], p2->coeff[ax][i], 4 * sizeof(double));
-    }
-  } else {                                            // the new trajectory has already started: its part from t on
-    res.times[0] = t;
-    if (!append_span(&res, p2, t, p2->times[p2->n_seg] > t ? p2->times[p2->n_seg] : t + 1.0)) return NEP_E_CAP;
-  }
+  if (!nep_plan_impl::compose_exact(t, p1, p2, &res)) return NEP_E_CAP;
   *out = res;
   return NEP_OK;
 }
@@ -258,20 +211,6 @@ struct nep_plan {
   int deltaT;
 };
 
-namespace {
-// mu::saturate(int&, const int, const int): the call sites pass doubles, which C++ truncates
-// to int because deltaT_ is an int lvalue (utils.cpp:744-754, neptune.cpp:1374).
-void saturate_int(int& v, double lo, double hi) {
-  int ilo = (int)lo, ihi = (int)hi;
-  if (v < ilo) v = ilo;
-  else if (v > ihi) v = ihi;
-}
-void saturate_dbl(double& v, double lo, double hi) {
-  if (v < lo) v = lo;
-  else if (v > hi) v = hi;
-}
-}  // namespace
-
 extern "C" {
 
 nep_plan_t* nep_plan_create(const nep_plan_cfg* cfg) {
@@ -319,33 +258,22 @@ int nep_plan_select_a(nep_plan_t* p, const double state_pos[3], double time_now,
   if (!p || !state_pos || !out) return NEP_E_ARG;
   if (p->q.empty()) return NEP_E_STATE;
   const nep_plan_cfg& c = p->cfg;
-  const int size = (int)p->q.size();
-  saturate_int(p->deltaT, c.lower_bound_runtime / c.dc, c.upper_bound_runtime / c.dc);
-  int future_index = size - p->deltaT;
-  int k_end = future_index > 0 ? future_index : 0;
-  if ((double)size < std::ceil(c.T_span / c.dc)) k_end = 0;
-  int k_index = size - 1 - k_end;
-  std::memcpy(out->A, p->q[(size_t)k_index].v, sizeof(PlanState));
-  if (future_index < 0)
-    for (int i = 3; i < 9; ++i) out->A[i] = 0.0;
-  const double* head = p->q.front().v;
-  double dx = head[0] - state_pos[0], dy = head[1] - state_pos[1], dz = head[2] - state_pos[2];
-  if (std::sqrt(dx * dx + dy * dy + dz * dz) > 1.0)
-    for (int i = 0; i < 3; ++i) out->A[i] = state_pos[i];
-  double rs = (k_end != 0) ? k_index * c.dc - c.runtime_opt : c.upper_bound_runtime;
-  saturate_dbl(rs, c.lower_bound_runtime - c.runtime_opt, c.upper_bound_runtime - c.runtime_opt);
-  out->k_index = k_index;
-  out->k_index_end = k_end;
-  out->runtime_search = rs;
-  out->t_start = k_index * c.dc + time_now;
+  const nep_plan_impl::SelectA s = nep_plan_impl::select_a_index(&c, (int)p->q.size(), p->deltaT);
+  p->deltaT = s.delta_t;
+  std::memcpy(out->A, p->q[(size_t)s.k_index].v, sizeof(PlanState));
+  nep_plan_impl::select_a_fix(out->A, s.future_index, p->q.front().v, state_pos);
+  out->k_index = s.k_index;
+  out->k_index_end = s.k_index_end;
+  out->runtime_search = nep_plan_impl::select_a_runtime(&c, s);
+  out->t_start = s.k_index * c.dc + time_now;
   return NEP_OK;
 }
 
 int nep_plan_splice(nep_plan_t* p, int32_t k_index_end, const double* traj_out, int32_t n_states) {
   if (!p || k_index_end < 0 || n_states < 0 || (n_states > 0 && !traj_out)) return NEP_E_ARG;
-  int size = (int)p->q.size();
-  if (size - 1 - k_index_end < 0) return NEP_E_STATE;
-  p->q.erase(p->q.end() - k_index_end - 1, p->q.end());
+  const int keep = nep_plan_impl::splice_keep((int)p->q.size(), k_index_end);
+  if (keep < 0) return NEP_E_STATE;
+  p->q.erase(p->q.begin() + keep, p->q.end());
   for (int i = 0; i < n_states; ++i) {
     PlanState s;
     std::memcpy(s.v, traj_out + 12 * (size_t)i, sizeof(s.v));

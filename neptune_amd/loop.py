@@ -188,6 +188,153 @@ def scene_raw(statics, par):
     return out
 
 
+class DeviceFleetLoop:
+    """FleetLoop's rounds for S scenes at once with nothing on the host (include/neptune_fleet.h): the plan deques, point A, the
+    splice, the composition and the control ticks of every (scene, agent) live in the batched handle, and a round
+
+        fleet_select -> frontend -> replan -> safety_commit -> fleet_commit -> [audit] -> fleet_tick
+
+    is one captured graph (graph=True: captured after the first eager round, replayed afterwards).  `scenes` are make_scene
+    dicts with the same agent and obstacle counts, each with its own statics; `goals` ([S][N][3], default: every scene's
+    scene.reachable_goals).  set_safety_check_prev(True) and set_line_cull(4.0) as in FleetLoop.  periods / phases (ints or
+    [S][N] arrays, in rounds): an agent replans in round r when it has not arrived and (r - phase) mod period == 0 — the mask is
+    written on the device by fleet_select into the buffer set_active got once; without them every agent is solved every round
+    and the results of the arrived ones are dropped (FleetLoop's default).  audit=True audits the records published at the
+    round's start over the replan_every ticks about to be flown, from t_now + dc: FleetLoop's placement and clock.  ring_cap: a
+    smaller plan ring than a splice can need (tests of the capacity path).
+    run() downloads the slots' arrival flags (4 bytes per slot) after every round to know when to stop; nothing else leaves the
+    device before report().  trace=True additionally downloads outcome, K and the two statuses per round (FleetLoop.trace)."""
+
+    def __init__(self, scenes, beam_width=32, delta_t_states=6, replan_every=5, periods=None, phases=None, audit=False, graph=True,
+                 goals=None, device=None, ring_cap=0, trace=False):
+        import torch
+        self.torch = torch
+        self.scenes = scenes
+        S = self.S = len(scenes)
+        p = self.p = scenes[0]["par"]
+        N = self.N = p.num_agents
+        self.graph, self.replan_every = graph, replan_every
+        be = self.be = BatchBackend(p, scenes[0]["statics"], n_scenes=S, device=device)
+        for s, sc in enumerate(scenes):
+            be.set_scene_statics(s, sc["statics"])
+        be.set_safety_check_prev(True)
+        be.set_line_cull(4.0)
+        self.fe = scene.frontend_cfg(p, beam_width=beam_width, pad_hold=1)
+        self.goals = np.stack([np.asarray(scene.reachable_goals(sc) if goals is None else goals[s], dtype=np.float64).reshape(N, 3)
+                               for s, sc in enumerate(scenes)])
+        state0 = np.zeros((S, N, 12))
+        for s, sc in enumerate(scenes):
+            state0[s, :, :2] = np.asarray(sc["starts"], dtype=np.float64)[:, :2]
+        state0[:, :, 2] = p.goal_height
+        lo = (delta_t_states + 0.5) * p.dc      # pins deltaT_ (mu::saturate truncates its bounds to int)
+        self.cfg = abi.nep_fleet_cfg(p.dc, p.T_span, lo, lo, 0.0, 1.0, delta_t_states, delta_t_states - 1, replan_every, ring_cap,
+                                     self.fe.goal_size, 0.0)
+        dev = be.device
+        dt = lambda a, t: torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=t)      # noqa: E731
+        self.masked = periods is not None or phases is not None
+        d_per = d_pha = None
+        if self.masked:
+            self.periods = np.broadcast_to(np.asarray(1 if periods is None else periods, dtype=np.int32), (S, N)).copy()
+            self.phases = np.broadcast_to(np.asarray(0 if phases is None else phases, dtype=np.int32), (S, N)).copy()
+            d_per, d_pha = dt(self.periods.reshape(-1), torch.int32), dt(self.phases.reshape(-1), torch.int32)
+        be.fleet_init(self.cfg, dt(state0.reshape(-1), torch.float64), dt(self.goals.reshape(-1), torch.float64), d_per, d_pha)
+        n = S * N
+        self.d_rec = torch.zeros(n * abi.TRAJ_REC_DTYPE.itemsize, dtype=torch.uint8, device=dev); self.d_final = torch.empty_like(self.d_rec)
+        self.d_start = torch.zeros(n * abi.FE_START_DTYPE.itemsize, dtype=torch.uint8, device=dev); self.d_clock = torch.zeros_like(self.d_start)
+        self.d_guess = torch.zeros(n * abi.GUESS_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self.d_res = torch.zeros(n * abi.FE_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self.d_acc = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.d_outcome = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.d_active = None
+        if self.masked:
+            self.d_active = torch.ones((S, N), dtype=torch.int32, device=dev)
+            be.set_active(self.d_active)
+        self.d_audit = None
+        if audit:
+            self.d_audit = be.new_audit()
+            be.audit(self.d_rec, self.d_clock, p.dc, 0, self.d_audit)      # (the call that allocates: made here, outside any capture)
+        self.rounds = 0
+        self._g = None
+        self.trace = [] if trace else None
+        self.after_commit = None      # test hook: called between fleet_commit and fleet_tick of an eager round
+        self.done = np.zeros((S, N), dtype=bool)
+
+    def _round_ops(self):
+        be = self.be
+        be.fleet_select(self.d_start, self.d_rec, self.d_active, self.d_clock if self.d_audit is not None else None)
+        be.frontend(self.fe, self.d_rec, self.d_start, self.d_guess, self.d_res)
+        be.replan(None, self.d_guess)
+        be.safety_commit(self.d_rec, be.d_commit, self.d_guess, self.d_final, self.d_acc)
+        be.fleet_commit(self.d_res, self.d_acc, self.d_outcome)
+        if self.after_commit is not None:
+            self.after_commit(self)
+        if self.d_audit is not None:
+            be.audit(self.d_rec, self.d_clock, self.p.dc, self.replan_every, self.d_audit)
+        be.fleet_tick()
+
+    def round(self):
+        """one bulk-synchronous round of every scene; True when every agent of every scene has arrived"""
+        torch = self.torch
+        if self.graph and self.rounds >= 1 and self.after_commit is None:
+            if self._g is None:
+                torch.cuda.synchronize()
+                s = torch.cuda.Stream(self.be.device)
+                s.wait_stream(torch.cuda.current_stream(self.be.device))
+                self._g = torch.cuda.CUDAGraph()
+                with torch.cuda.stream(s):
+                    self._g.capture_begin()
+                    self._round_ops()
+                    self._g.capture_end()
+                torch.cuda.current_stream(self.be.device).wait_stream(s)
+            self._g.replay()
+        else:
+            self._round_ops()
+        if self.trace is not None:
+            oc = self.d_outcome.cpu().numpy()
+            sol = self.be.solutions(); fres = self.d_res.cpu().numpy().view(abi.FE_RESULT_DTYPE)
+            self.trace.append([(int(oc[i]), int(sol[i]["K"]), int(fres[i]["status"]), int(sol[i]["stats"]["status"])) for i in range(self.S * self.N)])
+        self.rounds += 1
+        self.done = self.be.fleet_done().reshape(self.S, self.N) != 0      # (the one download of a round: 4 bytes per slot)
+        return bool(self.done.all())
+
+    def run(self, max_rounds=400):
+        for _ in range(max_rounds):
+            if self.round():
+                break
+        return self.report()
+
+    def report(self):
+        """per scene FleetLoop.stats' keys (min_pair_dist / min_static_dist come from the audit when it is on), plus `cap` and the
+        audit's summary"""
+        be = self.be
+        be.check()
+        cnt, t_now, rnd = be.fleet_counters()
+        st = be.fleet_state(pwp=False)
+        state = st["state"].reshape(self.S, self.N, 12); done = st["done"].reshape(self.S, self.N)
+        summ = audit_mod.summarize(self.audit_records(), self.S) if self.d_audit is not None else None
+        out = []
+        for s in range(self.S):
+            c = cnt[s]
+            d = dict(rounds=int(rnd[s]), replans=int(c[1] + c[2] + c[3] + c[4] + c[5]), accepted=int(c[4]), fe_no_solution=int(c[1]), qp_failed=int(c[2]),
+                     qp_relaxed=int(c[6]), rejected_by_safety=int(c[3]), cap=int(c[5]), skipped=int(c[0]),
+                     solves=int(c[1] + c[2] + c[3] + c[4] + c[5] + (0 if self.masked else c[0])), sim_time=float(t_now[s]), reached=int(done[s].sum()),
+                     dist_to_goal_mean=float(np.hypot(*(state[s, :, :2] - self.goals[s, :, :2]).T).mean()))
+            if summ is not None:
+                d["audit"] = summ[s]
+                d["min_pair_dist"] = summ[s]["min_center_dist"]["value"] if summ[s]["min_center_dist"] else np.inf
+                d["min_static_dist"] = summ[s]["min_static_dist"]["value"] if summ[s]["min_static_dist"] else np.inf
+            out.append(d)
+        return out
+
+    def audit_records(self):
+        """the flight audit so far: [S, N] AUDIT_DTYPE"""
+        return self.d_audit.cpu().numpy().view(abi.AUDIT_DTYPE).reshape(self.S, self.N)
+
+    def close(self):
+        self._g = None
+        self.be.close()
+
+
 class TetherLoop:
     """S tethered scenes flown on the device, one captured graph per round (include/neptune_frontend.h):
     frontend_ent -> lines + QP with the entangle rows -> safety_commit_ent -> track_ent -> next_starts, every tether's entangle

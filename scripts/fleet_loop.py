@@ -1,0 +1,91 @@
+"""The faithful closed loop on the device (neptune_amd.loop.DeviceFleetLoop, include/neptune_fleet.h): plan deques, point A, splice,
+composition and control ticks of every agent of every scene in the batched handle, one captured graph per round:
+fleet_select -> front end -> lines + QP -> safety pass -> fleet_commit -> [audit] -> fleet_tick.  Prints the per-scene report (FleetLoop's
+stats), the totals, the wall time per round and, with --audit, the worst clearances over all scenes.
+
+  python scripts/fleet_loop.py --agents 64 --obstacles 20 --scenes 128 --rounds 30 [--stagger 5] [--audit] [--host]
+
+--stagger P: every agent replans every P-th round, agent a in the rounds with (round - a) mod P == 0, and a round flies one control
+tick (FleetLoop's cadence at P = 5 with the agents' timers spread over the ticks).  --host flies scene 0 with FleetLoop as well and
+prints its wall time per round next to the device loop's (one scene each)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--agents", type=int, default=16)
+    ap.add_argument("--obstacles", type=int, default=8)
+    ap.add_argument("--scenes", type=int, default=4)
+    ap.add_argument("--seed0", type=int, default=0)
+    ap.add_argument("--rounds", type=int, default=400, help="at most; the flight stops when every agent of every scene has arrived")
+    ap.add_argument("--beam", type=int, default=32)
+    ap.add_argument("--stagger", type=int, default=0, metavar="P")
+    ap.add_argument("--audit", action="store_true", help="flight audit of every round, inside the graph")
+    ap.add_argument("--eager", action="store_true", help="no graph capture")
+    ap.add_argument("--host", action="store_true", help="also fly scene 0 with FleetLoop and with DeviceFleetLoop(S = 1): wall time per round of both")
+    a = ap.parse_args()
+    import numpy as np
+    import torch
+    from neptune_amd import audit, scene
+    from neptune_amd.loop import DeviceFleetLoop, FleetLoop
+    seeds = [a.seed0 + k for k in range(a.scenes)]
+    scenes = scene.make_scenes(a.agents, a.obstacles, seeds, workers=min(len(seeds), len(os.sched_getaffinity(0)), 16))
+    kw = dict(beam_width=a.beam, audit=a.audit, graph=not a.eager)
+    if a.stagger > 0:
+        kw.update(replan_every=1, periods=a.stagger, phases=np.tile(np.arange(a.agents) % a.stagger, (a.scenes, 1)))
+
+    def fly(scs, rounds):
+        lp = DeviceFleetLoop(scs, **kw)
+        lp.round(); lp.round()      # the eager round and the capture
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        n = 0
+        for _ in range(rounds - 2):
+            n += 1
+            if lp.round():
+                break
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        rep = lp.report()
+        lp.close()
+        return rep, dt / max(n, 1), n + 2
+
+    rep, per_round, n = fly(scenes, a.rounds)
+    for s, r in enumerate(rep):
+        print("scene %d (seed %d): %s" % (s, seeds[s], json.dumps({k: v for k, v in r.items() if k != "audit"})))
+    tot = {k: int(sum(r[k] for r in rep)) for k in ("replans", "accepted", "fe_no_solution", "qp_failed", "qp_relaxed", "rejected_by_safety", "cap", "skipped", "reached")}
+    print("total over %d scenes x %d agents, %d rounds: %s" % (a.scenes, a.agents, n, json.dumps(tot)))
+    print("wall time per round (rounds 3..%d, %s, arrival flags downloaded every round): %.3f ms = %.1f rounds/s, %.0f scene-rounds/s"
+          % (n, "eager" if a.eager else "one graph", per_round * 1e3, 1.0 / per_round, a.scenes / per_round))
+    if a.audit:
+        for line in audit.format_summary([r["audit"] for r in rep]):
+            print(line)
+        worst = min(r["audit"]["min_box_clear"]["value"] for r in rep if r["audit"]["min_box_clear"])
+        print("scenes with min_box_clear < 0: %d of %d; worst %.9f m" % (sum(1 for r in rep if r["audit"]["min_box_clear"] and r["audit"]["min_box_clear"]["value"] < 0), len(rep), worst))
+    if a.host:
+        sc = scenes[0]
+        _, dev1, n1 = fly([sc], a.rounds)
+        ref = FleetLoop(sc["par"], sc["statics"], sc["starts"], scene.reachable_goals(sc), beam_width=a.beam, audit=a.audit)
+        ref.round(); ref.round()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        m = 0
+        for _ in range(a.rounds - 2):
+            m += 1
+            if ref.round():
+                break
+        torch.cuda.synchronize()
+        host = (time.perf_counter() - t0) / max(m, 1)
+        ref.close()
+        print("one scene (seed %d): DeviceFleetLoop %.3f ms per round over %d rounds, FleetLoop %.3f ms per round over %d rounds"
+              % (seeds[0], dev1 * 1e3, n1, host * 1e3, m + 2))
+
+
+if __name__ == "__main__":
+    main()
