@@ -20,6 +20,8 @@
  *   nep_ent_track_step         NeptuneRos::updateEntStateStaticObs (neptune_ros.cpp:800-850): the state of the
  *                              vehicle's own tether after one move, with eu::entangleHSigToAddAgentInd's nine-argument
  *                              form (entangle_utils.cpp:820-1127) for an agent whose bend points changed
+ *   nep_ent_predict_a          Neptune::PredictAlphasBetas (neptune.cpp:976-1008): the state forwarded to point A in one
+ *                              move with the eight-argument form throughout, into a copy
  */
 #ifndef NEPTUNE_ENTANGLE_H_
 #define NEPTUNE_ENTANGLE_H_
@@ -129,6 +131,16 @@ typedef struct nep_ent_track_inputs {
  * NEP_E_ARG.                                                                                                            */
 int nep_ent_track_step(const nep_ent_cfg* cfg, const nep_ent_track_inputs* in, nep_ent_state* state, const double pk[2],
                        const double pk1[2]);
+
+/* Neptune::PredictAlphasBetas for one agent: the entangle_state_A the front end and the safety re-check start from.  The
+ * vehicle goes from where it is (pk) to point A (pk1) in one move while every other agent i goes from where it was last seen
+ * (pik[i]) to its first sampled point (pik1[i]); the CURRENT bend lists serve as the previous check's too, so the
+ * eight-argument crossing test runs for every agent.  *in (entangle_state_) is not touched; *out — caller-owned arrays like
+ * *in's, out->cap and out->n_active set by the caller, n_active == in->n_active — receives the result.  Exactly one
+ * nep_ent_track_step on a copy: the same flags, the same capacities (in->cap bounds the list as there, out->cap must hold it);
+ * on NEP_ENT_TRACK_CAP *out equals *in.  nep_batch_fleet_predict_ent (include/neptune_fleet.h) is its device form.          */
+int nep_ent_predict_a(const nep_ent_cfg* cfg, const double* pik, const double* pik1, const int32_t* present, const int32_t* bend_off,
+                      const double* bend_xy, const nep_ent_state* in, const double pk[2], const double pk1[2], nep_ent_state* out);
 
 #ifdef __cplusplus
 }

@@ -32,7 +32,22 @@
  *                    (include/neptune_plan.h).
  *   timers           the reference replans every agent on its own ROS timer; here a round is bulk-synchronous and an agent's timer
  *                    is a period and a phase in rounds (see nep_batch_fleet_select's mask).
- * Unsharded handles only (n_local == num_agents), else NEP_E_STATE.  Without a HIP device every call returns NEP_E_HIP.        */
+ * Unsharded handles only (n_local == num_agents), else NEP_E_STATE.  Without a HIP device every call returns NEP_E_HIP.
+ *
+ * Tethered fleets (nep_batch_fleet_init_ent, on a handle created with enable_entangle).  The handle then also owns, per slot, the
+ * entangle state of the tether at the TRACKED position (NeptuneRos's entangle_state_), the bend list the agent published at the
+ * last selection and the one before it (bendPtsForAgents_ / bendPtsForAgents_prev_ as the others see them: a count and
+ * NEP_MAX_BEND points each), the NEP_ENT_TRACK_* flags of the last tracked round and their sticky OR; per scene, counter [7] =
+ * slots ever flagged NEP_ENT_TRACK_ENTANGLED.  The round becomes
+ *
+ *   nep_batch_fleet_select -> nep_batch_fleet_predict_ent -> nep_batch_frontend_ent -> nep_batch_replan (entangle rows) ->
+ *     nep_batch_safety_commit_ent -> nep_batch_fleet_commit [-> nep_batch_audit] -> nep_batch_fleet_track_ent -> nep_batch_fleet_tick
+ *
+ * with the state at A (Neptune::PredictAlphasBetas, neptune.cpp:976-1008) made on the device and the state at the tracked
+ * position moved once per control tick flown (NeptuneRos::odomCB -> updateEntStateStaticObs, neptune_ros.cpp:781-850).  Both equal,
+ * bit for bit, the host chain of nep_ent_predict_a / nep_ent_track_step (include/neptune_entangle.h).  What differs from the
+ * reference: every agent's bend list changes at the round's select and nowhere else (one trajCB per agent and round), so the
+ * nine-argument crossing test can only run at a round's first tick.                                                          */
 #ifndef NEPTUNE_FLEET_H_
 #define NEPTUNE_FLEET_H_
 
@@ -52,7 +67,7 @@ extern "C" {
 #define NEP_FLEET_REJECTED 3            /* turned down by nep_batch_safety_commit                                           */
 #define NEP_FLEET_ACCEPTED 4            /* plan spliced, trajectory composed                                                 */
 #define NEP_FLEET_CAP 5                 /* accepted, but the plan or the trajectory would outgrow its storage: nothing changed */
-#define NEP_FLEET_N_COUNTERS 8          /* per scene: one per outcome above, [6] accepted solves with NEP_RELAXED, [7] unused */
+#define NEP_FLEET_N_COUNTERS 8          /* per scene: one per outcome above, [6] accepted solves with NEP_RELAXED, [7] slots ever entangled (tethered fleets, else 0) */
 
 #define NEP_FLEET_FLAG_SEG 1            /* sticky per slot: a composition needed more than NEP_TRAJ_MAX_SEG intervals        */
 #define NEP_FLEET_FLAG_RING 2           /* a splice needed more than ring_cap states (or n_states > max_states)              */
@@ -89,6 +104,10 @@ int nep_batch_fleet_init(nep_batch_t* h, const nep_fleet_cfg* cfg, const double*
  * the caller handed to nep_batch_set_active, so that the front end, the replan and the safety pass of the same graph skip the
  * others.  d_clock ([slots] nep_fe_start, may be NULL): t_start = t_now + dc in every entry, the clock of a nep_batch_audit of
  * d_records over the round_ticks ticks about to be flown (they lie before A, so the records published now describe them).
+ * On a handle with tether state (nep_batch_fleet_init_ent) the record publishes the bend points of the state at the tracked
+ * position (publishOwnTraj, neptune_ros.cpp:457-476: entangle_state_, not the state at A): n_bend = 1 + state.n_bend, bend[0] the
+ * base, then the anchor of every bend index — an agent's base, or the static representative's column — and the list published at
+ * the previous select becomes the "previous" one first.  Without tether state every byte is as described above.
  * Asynchronous on `stream`, capturable.                                                                                      */
 int nep_batch_fleet_select(nep_batch_t* h, nep_fe_start* d_start, nep_traj_rec* d_records, int32_t* d_active,
                            nep_fe_start* d_clock, void* stream);
@@ -109,6 +128,37 @@ int nep_batch_fleet_commit(nep_batch_t* h, const nep_solution* d_solution, const
  * Then the sticky arrival test — sqrt(dx*dx + dy*dy) < goal_radius && sqrt(vx*vx + vy*vy) < 0.05 on the tracked state, the
  * expression of nep_batch_next_starts — and the round counter's increment.  Asynchronous, capturable.                         */
 int nep_batch_fleet_tick(nep_batch_t* h, void* stream);
+
+/* ---- tethers ---------------------------------------------------------------------------------------------------------------- */
+/* Allocates (first call) or re-seeds the tether state: every slot's state d_ent0[slot] (device memory; NULL: empty), nothing
+ * published yet, flags and counts 0.  After nep_batch_fleet_init (which drops the tether state: call this again after a re-seed)
+ * and, with static obstacles, nep_batch_set_static_reps; on a handle created with enable_entangle.  Otherwise NEP_E_STATE.
+ * Up to 4096 agents and 2048 statics per scene (NEP_E_CAP).  Synchronises; not capturable.                                   */
+int nep_batch_fleet_init_ent(nep_batch_t* h, double cable_length, const nep_fe_ent_state* d_ent0, void* stream);
+
+/* After the select: d_ent_a[slot] = nep_ent_predict_a of the slot's state with pk = the tracked position, pk1 = d_start[slot].pos,
+ * and of every other agent i pik = its tracked position, pik1 = its record in d_records at the slot's t_start (the first sample of
+ * nep_ent_sample_points: the front end's sampled[i][0][0]) and its bend list in d_records; present = the record is valid, an
+ * agent's, and has a trajectory.  The handle's state is not touched.  d_flags_a ([slots], may be NULL): the NEP_ENT_TRACK_* bits;
+ * a CAP leaves d_ent_a[slot] = the state as it is and raises NEP_FLAG_ENT_TRACK (nep_batch_check).  d_ent_a is the d_ent_init of
+ * nep_batch_frontend_ent and nep_batch_safety_commit_ent.  Asynchronous, capturable.                                          */
+int nep_batch_fleet_predict_ent(nep_batch_t* h, const nep_fe_start* d_start, const nep_traj_rec* d_records, nep_fe_ent_state* d_ent_a,
+                                int32_t* d_flags_a, void* stream);
+
+/* Between nep_batch_fleet_commit and nep_batch_fleet_tick: for the ticks q = 1..round_ticks about to be flown, every slot's state
+ * takes one nep_ent_track_step.  A slot stands, after tick q, at ring[(head + min(q - 1, size - 1)) mod cap][0:2] and before tick 1
+ * at the tracked state (nep_batch_fleet_tick's pop rule: a plan down to one state stays put); the rings are read as the commit left
+ * them.  The others' bend lists are d_records' (published this round); at the first tick only, the list an agent published a round
+ * ago counts as the previous check's (an empty one: as the current one).  Every slot is tracked — active or not, arrived or not.
+ * The flags are ORed over the ticks into d_flags ([slots], may be NULL) and into the sticky word; a CAP (that tick's move is
+ * dropped) raises NEP_FLAG_ENT_TRACK.  Asynchronous, capturable.                                                              */
+int nep_batch_fleet_track_ent(nep_batch_t* h, const nep_traj_rec* d_records, int32_t* d_flags, void* stream);
+
+/* Blocking reader (host memory, each may be NULL): the states at the tracked positions, the last tracked round's flags, the sticky
+ * flags, and per slot the (other agent, tick) pairs the tracking has actually walked since nep_batch_fleet_init_ent — the rest was
+ * proven to add no crossing (nep_batch_debug_set_option "fleet_ent_proof" 0: everything is walked; same states).               */
+int nep_batch_fleet_ent_state(nep_batch_t* h, nep_fe_ent_state* states_out, int32_t* flags_round_out, int32_t* flags_ever_out,
+                              int32_t* walked_out);
 
 /* ---- readers: blocking (they wait for the device), for tests and reports; every output is host memory and may be NULL ------ */
 /* ring_cap of the handle's fleet state (NEP_E_STATE before nep_batch_fleet_init)                                              */

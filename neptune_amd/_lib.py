@@ -50,8 +50,9 @@ PLAN_EXPORTS = [
 FE_EXPORTS = ["nep_batch_frontend", "nep_batch_frontend_hulls", "nep_batch_set_static_reps", "nep_batch_set_fe_ent_big_records", "nep_batch_frontend_ent", "nep_batch_frontend_ent_hulls", "nep_batch_safety_commit_ent", "nep_batch_track_ent", "nep_batch_next_starts", "nep_batch_audit", "nep_audit_records", "nep_audit_init"]
 # include/neptune_fleet.h
 FLEET_EXPORTS = ["nep_batch_fleet_init", "nep_batch_fleet_select", "nep_batch_fleet_commit", "nep_batch_fleet_tick", "nep_batch_fleet_ring_cap",
-                 "nep_batch_fleet_plans", "nep_batch_fleet_state", "nep_batch_fleet_counters"]
-ENT_EXPORTS = ["nep_ent_sample_points", "nep_ent_propagate_segment", "nep_ent_propagate_guess", "nep_ent_case_ids", "nep_ent_track_step"]
+                 "nep_batch_fleet_plans", "nep_batch_fleet_state", "nep_batch_fleet_counters", "nep_batch_fleet_init_ent", "nep_batch_fleet_predict_ent",
+                 "nep_batch_fleet_track_ent", "nep_batch_fleet_ent_state"]
+ENT_EXPORTS = ["nep_ent_sample_points", "nep_ent_propagate_segment", "nep_ent_propagate_guess", "nep_ent_case_ids", "nep_ent_track_step", "nep_ent_predict_a"]
 
 
 class BackendError(RuntimeError):
@@ -180,6 +181,7 @@ def lib():
     L.nep_ent_propagate_guess.argtypes = [pcfg, pin, pst, vp, i, pi, pi, pi, pi, pst]
     L.nep_ent_case_ids.argtypes = [i, i, pi, pi, pi, i, pi]
     L.nep_ent_track_step.argtypes = [pcfg, C.POINTER(abi.nep_ent_track_inputs), pst, pd, pd]
+    L.nep_ent_predict_a.argtypes = [pcfg, pd, pd, pi, pi, pd, pst, pd, pd, pst]
     L.nep_batch_frontend.argtypes = [vp, C.POINTER(abi.nep_fe_cfg), vp, vp, vp, vp, vp]
     L.nep_batch_frontend_hulls.argtypes = [vp, C.POINTER(abi.nep_fe_cfg), vp, i, vp, vp, vp, vp]
     L.nep_batch_set_static_reps.argtypes = [vp, i, pd, pd]
@@ -198,6 +200,10 @@ def lib():
     L.nep_batch_fleet_plans.argtypes = [vp, i, i, pd, pi]
     L.nep_batch_fleet_state.argtypes = [vp, pd, vp, pi, pi, pi, pi, pi]
     L.nep_batch_fleet_counters.argtypes = [vp, pi, pd, pi]
+    L.nep_batch_fleet_init_ent.argtypes = [vp, d, vp, vp]
+    L.nep_batch_fleet_predict_ent.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.nep_batch_fleet_track_ent.argtypes = [vp, vp, vp, vp]
+    L.nep_batch_fleet_ent_state.argtypes = [vp, vp, pi, pi, pi]
     L.nep_batch_frontend_ent_hulls.argtypes = [vp, C.POINTER(abi.nep_fe_cfg), vp, i, vp, vp, vp, vp, vp, vp]
     L.nep_batch_exchange_slots.argtypes = [vp, vp, vp, vp, C.c_int64, vp]
     L.nep_batch_set_ent_samples.argtypes = [vp, i]

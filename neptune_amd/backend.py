@@ -428,6 +428,36 @@ class BatchBackend:
         check(lib().nep_batch_fleet_counters(self._h, abi.iptr(c), abi.dptr(t), abi.iptr(r)))
         return c, t, r
 
+    # ---- the tethers of the fleet state (include/neptune_fleet.h) ---------------------------------------------------
+    def fleet_init_ent(self, cable_length=None, d_ent0=None, stream=None):
+        """allocates / re-seeds the tether state of every slot (nep_batch_fleet_init_ent): d_ent0 [slots] FE_ENT_STATE_DTYPE bytes on
+        the device, or None for empty states; after fleet_init and set_static_reps, on a handle with enable_entangle"""
+        st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        cable = self.par.tether_length if cable_length is None else cable_length
+        check(lib().nep_batch_fleet_init_ent(self._h, float(cable), d_ent0.data_ptr() if d_ent0 is not None else None, st.cuda_stream))
+
+    def fleet_predict_ent(self, d_start, d_records, d_ent_a, d_flags_a=None, stream=None):
+        """the state at point A of every slot into d_ent_a (PredictAlphasBetas; nep_batch_fleet_predict_ent), after fleet_select"""
+        st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        check(lib().nep_batch_fleet_predict_ent(self._h, d_start.data_ptr(), d_records.data_ptr(), d_ent_a.data_ptr(),
+                                                d_flags_a.data_ptr() if d_flags_a is not None else None, st.cuda_stream))
+
+    def fleet_track_ent(self, d_records, d_flags=None, stream=None):
+        """every slot's tether state over the round_ticks ticks about to be flown (nep_batch_fleet_track_ent), between fleet_commit
+        and fleet_tick"""
+        st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        check(lib().nep_batch_fleet_track_ent(self._h, d_records.data_ptr(), d_flags.data_ptr() if d_flags is not None else None, st.cuda_stream))
+
+    def fleet_ent_state(self, states=True):
+        """the tether state of every slot (blocking) -> dict: state [slots] FE_ENT_STATE_DTYPE, flags / ever / walked [slots] int32"""
+        n = self.slots
+        out = dict(state=np.zeros(n, dtype=abi.FE_ENT_STATE_DTYPE) if states else None)
+        for k in ("flags", "ever", "walked"):
+            out[k] = np.zeros(n, dtype=np.int32)
+        check(lib().nep_batch_fleet_ent_state(self._h, out["state"].ctypes.data if states else None, abi.iptr(out["flags"]), abi.iptr(out["ever"]),
+                                              abi.iptr(out["walked"])))
+        return out
+
     def next_starts(self, d_records, dt, d_start, d_alt_goal=None, switch_radius=0.0, stream=None):
         """point A of the next round on the device: d_start's clock advances by dt and its state becomes that of the committed
         trajectories d_records at the new time; with d_alt_goal ([slots][3] float64) arrived agents swap goals

@@ -160,7 +160,7 @@ struct Engine {
   }
   // which interior-point kernel the next replan launches, and its LDS carve (see size_scratch)
   static constexpr double kAutoCullRadius = 4.0;
-  bool fits_reg = true, cull_user_set = false, skip_lps = true, no_redo = false; int lds_lines_lds = 0, sep_pack = 0, force_kernel = 0, opt_qp_key_decay = 2, opt_fe_key_decay = 1, opt_corr_from = kCorrFromItDefault, opt_corr_max = kCorrMaxCountDefault;      // (skip_lps, no_redo, sep_pack, force_kernel: development aids behind nep_*_debug_set_option, include/neptune_backend_debug.h)
+  bool fits_reg = true, cull_user_set = false, skip_lps = true, no_redo = false; int lds_lines_lds = 0, sep_pack = 0, force_kernel = 0, opt_qp_key_decay = 2, opt_fe_key_decay = 1, opt_corr_from = kCorrFromItDefault, opt_corr_max = kCorrMaxCountDefault, opt_fleet_ent_proof = 1;      // (skip_lps, no_redo, sep_pack, force_kernel: development aids behind nep_*_debug_set_option, include/neptune_backend_debug.h)
   // Row scratch (rows and coefficients beyond the register slots / the LDS carve): one area per slot in general.  With the presolve's
   // redo pass (skip_mode()) the first pass never needs one — a replan whose near lines exceed the slots is sent to the redo pass —
   // so the handle keeps a pool of kScratchPool areas for that pass (config 5: 1.9 GB instead of 15.3 per 32 scenes);
@@ -997,7 +997,13 @@ struct nep_batch {
     bool ready = false, timers = false; int cap = 0; nep_fleet_cfg cfg{};
     DevBuf<double> ring, state, goal, t_now; DevBuf<nep_pwp> pwp;
     DevBuf<int> head, size, k_end, flown, done, outcome, sflags, period, phase, round, counters;
-    void release() { ring.release(); state.release(); goal.release(); t_now.release(); pwp.release(); head.release(); size.release(); k_end.release(); flown.release();
+    // the tethers (nep_batch_fleet_init_ent): state at the tracked position, the published bend lists, flags, scratch
+    bool ent_ready = false; double cable = 0.0;
+    DevBuf<nep_fe_ent_state> ent, ent_save; DevBuf<double> pub_xy, pub_prev_xy, ent_pos;
+    DevBuf<int> pub_n, pub_prev_n, ent_flags, ent_ever, ent_walked, ent_flags_a;
+    void release_ent() { ent.release(); ent_save.release(); pub_xy.release(); pub_prev_xy.release(); ent_pos.release(); pub_n.release(); pub_prev_n.release();
+                         ent_flags.release(); ent_ever.release(); ent_walked.release(); ent_flags_a.release(); ent_ready = false; }
+    void release() { release_ent(); ring.release(); state.release(); goal.release(); t_now.release(); pwp.release(); head.release(); size.release(); k_end.release(); flown.release();
                      done.release(); outcome.release(); sflags.release(); period.release(); phase.release(); round.release(); counters.release(); ready = false; }
   } fleet;
 };
@@ -1475,6 +1481,15 @@ void fleet_args(nep_batch_t* h, FleetArgs& fa) {
   fa.period = F.timers ? F.period.p : nullptr; fa.phase = F.timers ? F.phase.p : nullptr;
   fa.t_now = F.t_now.p; fa.round = F.round.p; fa.counters = F.counters.p; fa.gflags = h->eng.d_flags.p; fa.active = h->eng.active;
 }
+void fleet_ent_args(nep_batch_t* h, FleetEntArgs& ea) {
+  nep_batch::Fleet& F = h->fleet; Engine& E = h->eng;
+  ea.N = h->cfg.num_agents; ea.S = E.sp.n_static; ea.n_scenes = h->cfg.n_scenes; ea.static_stride = E.sp.static_stride; ea.num_pol = h->cfg.num_pol;
+  ea.n_steps = F.cfg.round_ticks; ea.proof = E.opt_fleet_ent_proof; ea.cable = F.cable; ea.T_span = E.sp.T_span;
+  ea.pb = E.d_pb.p; ea.srep = E.d_srep.p; ea.slong = E.d_slong.p; ea.pos = F.ent_pos.p;
+  ea.pub_n = F.pub_n.p; ea.pub_xy = F.pub_xy.p; ea.pub_prev_n = F.pub_prev_n.p; ea.pub_prev_xy = F.pub_prev_xy.p;
+  ea.in = F.ent.p; ea.out = F.ent.p; ea.save = F.ent_save.p; ea.flags = F.ent_flags.p; ea.ever = F.ent_ever.p; ea.walked = F.ent_walked.p;
+  ea.counters = F.counters.p; ea.gflags = E.d_flags.p;
+}
 }  // namespace
 
 int nep_batch_fleet_init(nep_batch_t* h, const nep_fleet_cfg* cfg, const double* d_state0, const double* d_goal, const int32_t* d_period,
@@ -1486,7 +1501,7 @@ int nep_batch_fleet_init(nep_batch_t* h, const nep_fleet_cfg* cfg, const double*
   const size_t slots = (size_t)h->slots, S = (size_t)h->cfg.n_scenes;
   const int cap = cfg->ring_cap > 0 ? cfg->ring_cap : cfg->deltaT0 + h->cfg.max_states;
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));      // (a re-seed: kernels of the previous flight may still read the state)
-  F.ready = false;
+  F.ready = false; F.ent_ready = false;      // (a re-seeded fleet flies untethered until nep_batch_fleet_init_ent runs again)
   if (int e = F.ring.ensure(slots * cap * 12)) return e;
   if (int e = F.state.ensure(slots * 12)) return e;
   if (int e = F.goal.ensure(slots * 3)) return e;
@@ -1519,7 +1534,92 @@ int nep_batch_fleet_select(nep_batch_t* h, nep_fe_start* d_start, nep_traj_rec* 
   fleet_args(h, fa);
   fa.start = d_start; fa.recs = d_records; fa.active_out = d_active; fa.clock = d_clock;
   launch_fleet_select(fa, (hipStream_t)stream);
+  if (h->fleet.ent_ready) {      // the tethered fleet publishes its bend points (publishOwnTraj)
+    FleetEntArgs ea{};
+    fleet_ent_args(h, ea);
+    ea.recs = d_records; ea.recs_out = d_records;
+    launch_fleet_ent_publish(ea, (hipStream_t)stream);
+  }
   HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int nep_batch_fleet_init_ent(nep_batch_t* h, double cable_length, const nep_fe_ent_state* d_ent0, void* stream) {
+  if (int e = fleet_guard(h, true)) return e;
+  if (!h->cfg.enable_entangle) return fail(NEP_E_STATE, "handle created without enable_entangle");
+  Engine& E = h->eng;
+  const int S = h->cfg.n_scenes;
+  if (E.sp.n_static > 0 && !E.have_reps) return fail(NEP_E_STATE, "the fleet's tethers with static obstacles need nep_batch_set_static_reps first");
+  if (E.sp.n_static > 0 && E.d_srep.n < (size_t)(E.sp.static_stride ? S : 1) * E.sp.n_static * 4) return fail(NEP_E_STATE, "static representatives do not cover every scene's obstacle set: call nep_batch_set_static_reps after nep_batch_set_scene_statics");
+  if (!fleet_ent_fits(h->cfg.num_agents, E.sp.n_static)) return fail(NEP_E_CAP, "the fleet's tether kernels take up to 4096 agents and 2048 static obstacles per scene");
+  if (!(cable_length > 0.0)) return fail(NEP_E_ARG, "cable_length must be positive");
+  nep_batch::Fleet& F = h->fleet;
+  const size_t slots = (size_t)h->slots;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(hipStreamSynchronize(st));
+  F.ent_ready = false;
+  if (!E.d_srep.p) { if (int e = E.d_srep.ensure(4)) return e; if (int e2 = E.d_slong.ensure(2)) return e2; }
+  if (int e = F.ent.ensure(slots)) return e;
+  if (int e = F.ent_save.ensure(slots)) return e;
+  if (int e = F.pub_xy.ensure(slots * NEP_MAX_BEND * 2)) return e;
+  if (int e = F.pub_prev_xy.ensure(slots * NEP_MAX_BEND * 2)) return e;
+  if (int e = F.ent_pos.ensure(slots * ((size_t)F.cfg.round_ticks + 1) * 2)) return e;
+  for (DevBuf<int>* b : {&F.pub_n, &F.pub_prev_n, &F.ent_flags, &F.ent_ever, &F.ent_walked, &F.ent_flags_a})
+    if (int e = b->ensure(slots)) return e;
+  if (d_ent0) HIPCHK(hipMemcpyAsync(F.ent.p, d_ent0, slots * sizeof(nep_fe_ent_state), hipMemcpyDeviceToDevice, st));
+  else HIPCHK(hipMemsetAsync(F.ent.p, 0, slots * sizeof(nep_fe_ent_state), st));
+  HIPCHK(hipMemsetAsync(F.ent_save.p, 0, slots * sizeof(nep_fe_ent_state), st));
+  HIPCHK(hipMemsetAsync(F.pub_xy.p, 0, slots * NEP_MAX_BEND * 2 * sizeof(double), st));
+  HIPCHK(hipMemsetAsync(F.pub_prev_xy.p, 0, slots * NEP_MAX_BEND * 2 * sizeof(double), st));
+  for (DevBuf<int>* b : {&F.pub_n, &F.pub_prev_n, &F.ent_flags, &F.ent_ever, &F.ent_walked, &F.ent_flags_a})
+    HIPCHK(hipMemsetAsync(b->p, 0, slots * sizeof(int), st));
+  HIPCHK(hipStreamSynchronize(st));
+  F.cable = cable_length; F.ent_ready = true;
+  return 0;
+}
+
+int nep_batch_fleet_predict_ent(nep_batch_t* h, const nep_fe_start* d_start, const nep_traj_rec* d_records, nep_fe_ent_state* d_ent_a,
+                                int32_t* d_flags_a, void* stream) {
+  if (int e = fleet_guard(h, true)) return e;
+  if (!h->fleet.ent_ready) return fail(NEP_E_STATE, "nep_batch_fleet_init_ent has not run on this handle");
+  if (!d_start || !d_records || !d_ent_a) return fail(NEP_E_ARG, "null argument");
+  FleetArgs fa{};
+  fleet_args(h, fa);
+  FleetEntArgs ea{};
+  fleet_ent_args(h, ea);
+  ea.n_steps = 1; ea.start = d_start; ea.recs = d_records; ea.out = d_ent_a; ea.flags = d_flags_a ? d_flags_a : h->fleet.ent_flags_a.p;
+  ea.pub_prev_n = nullptr; ea.pub_prev_xy = nullptr; ea.ever = nullptr; ea.walked = nullptr; ea.counters = nullptr;
+  launch_fleet_ent_steps(ea, fa, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int nep_batch_fleet_track_ent(nep_batch_t* h, const nep_traj_rec* d_records, int32_t* d_flags, void* stream) {
+  if (int e = fleet_guard(h, true)) return e;
+  if (!h->fleet.ent_ready) return fail(NEP_E_STATE, "nep_batch_fleet_init_ent has not run on this handle");
+  if (!d_records) return fail(NEP_E_ARG, "null argument");
+  FleetArgs fa{};
+  fleet_args(h, fa);
+  FleetEntArgs ea{};
+  fleet_ent_args(h, ea);
+  ea.n_steps = h->fleet.cfg.round_ticks; ea.start = nullptr; ea.recs = d_records; ea.out = h->fleet.ent.p;
+  ea.flags = d_flags ? d_flags : h->fleet.ent_flags.p;
+  launch_fleet_ent_steps(ea, fa, (hipStream_t)stream);
+  if (d_flags) HIPCHK(hipMemcpyAsync(h->fleet.ent_flags.p, d_flags, (size_t)h->slots * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int nep_batch_fleet_ent_state(nep_batch_t* h, nep_fe_ent_state* states_out, int32_t* flags_round_out, int32_t* flags_ever_out, int32_t* walked_out) {
+  if (int e = fleet_guard(h, true)) return e;
+  nep_batch::Fleet& F = h->fleet;
+  if (!F.ent_ready) return fail(NEP_E_STATE, "nep_batch_fleet_init_ent has not run on this handle");
+  const size_t slots = (size_t)h->slots;
+  HIPCHK(hipDeviceSynchronize());
+  if (states_out) HIPCHK(hipMemcpy(states_out, F.ent.p, slots * sizeof(nep_fe_ent_state), hipMemcpyDeviceToHost));
+  if (flags_round_out) HIPCHK(hipMemcpy(flags_round_out, F.ent_flags.p, slots * sizeof(int), hipMemcpyDeviceToHost));
+  if (flags_ever_out) HIPCHK(hipMemcpy(flags_ever_out, F.ent_ever.p, slots * sizeof(int), hipMemcpyDeviceToHost));
+  if (walked_out) HIPCHK(hipMemcpy(walked_out, F.ent_walked.p, slots * sizeof(int), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -1713,6 +1813,7 @@ static int engine_option(Engine& E, const char* name, int32_t v) {
   else if (n == "sep_pack") { if (v < -1 || v > NEP_MAX_POL) return fail(NEP_E_ARG, "sep_pack: -1 unpacked, 0 automatic, 1..NEP_MAX_POL"); E.sep_pack = v; }
   else if (n == "corr_from") { if (v < 1) return fail(NEP_E_ARG, "corr_from >= 1"); E.opt_corr_from = v; E.sp.corr_from_it = v; }
   else if (n == "corr_max") { if (v < 1) return fail(NEP_E_ARG, "corr_max >= 1"); E.opt_corr_max = v; E.sp.corr_max_count = v; }
+  else if (n == "fleet_ent_proof") E.opt_fleet_ent_proof = v != 0;      // 0: nep_batch_fleet_predict_ent / _track_ent walk every other agent and static at every step (same states; A/B of the lanes' proofs)
   else if (n == "qp_profile") E.profile_phases = v != 0;
   else if (n == "presolve_kernel") E.presolve_kernel = v != 0;      // 0: the zero-iteration test only inside qp_reg_kernel<true> (rounds 3-5); same results up to the last place of the objective
   else return fail(NEP_E_ARG, "unknown debug option: " + n);

@@ -491,6 +491,25 @@ int nep_ent_track_step(const nep_ent_cfg* cfg, const nep_ent_track_inputs* in, n
   return flags;
 }
 
+int nep_ent_predict_a(const nep_ent_cfg* cfg, const double* pik, const double* pik1, const int32_t* present, const int32_t* bend_off,
+                      const double* bend_xy, const nep_ent_state* in, const double pk[2], const double pk1[2], nep_ent_state* out) {
+  if (!in || !out || out == in || out->n_active != in->n_active) return NEP_E_ARG;
+  if (in->n_alpha < 0 || in->n_bend < 0 || in->n_alpha > out->cap || in->n_bend > out->cap || in->n_alpha > in->cap || in->n_bend > in->cap) return NEP_E_ARG;
+  if ((in->n_alpha && (!out->alphas || !out->betas || !in->alphas || !in->betas)) || (in->n_bend && (!out->bend_idx || !in->bend_idx)) ||
+      (in->n_active && (!out->active_cases || !in->active_cases))) return NEP_E_ARG;
+  // the copy the one step works on: *in's lists in *out's arrays, under *in's capacity
+  const int32_t out_cap = out->cap;
+  for (int i = 0; i < in->n_alpha; i++) { out->alphas[2 * i] = in->alphas[2 * i]; out->alphas[2 * i + 1] = in->alphas[2 * i + 1]; out->betas[i] = in->betas[i]; }
+  for (int i = 0; i < in->n_bend; i++) out->bend_idx[i] = in->bend_idx[i];
+  for (int i = 0; i < in->n_active; i++) out->active_cases[i] = in->active_cases[i];
+  out->n_alpha = in->n_alpha; out->n_bend = in->n_bend;
+  out->cap = in->cap < out_cap ? in->cap : out_cap;
+  const nep_ent_track_inputs ti{pik, pik1, present, bend_off, bend_xy, bend_off, bend_xy};
+  const int rc = nep_ent_track_step(cfg, &ti, out, pk, pk1);
+  out->cap = out_cap;
+  return rc;
+}
+
 int nep_ent_case_ids(int32_t n_states, int32_t n_active, const int32_t* alpha_off, const int32_t* alphas, const int32_t* active_cases,
                      int32_t num_agents, int32_t* case_id) {
   if (n_states < 0 || !alpha_off || !active_cases || !case_id || num_agents < 1 || n_active < num_agents) return NEP_E_ARG;

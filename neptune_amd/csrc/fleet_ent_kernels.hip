@@ -1,0 +1,300 @@
+// fleet_ent_kernels.hip — the tethers of the device fleet loop (nep_batch_fleet_init_ent / _predict_ent / _track_ent and the bend
+// points nep_batch_fleet_select publishes; include/neptune_fleet.h).
+//
+// Two steps of the reference on the fleet state of fleet_kernels.hip:
+//   NeptuneRos::odomCB -> updateEntStateStaticObs (neptune_ros.cpp:781-850) once per control tick the round flies, and
+//   Neptune::PredictAlphasBetas (neptune.cpp:976-1008): the state forwarded to point A in one move, into a copy.
+// Both are chains of nep_ent_track_step (entangle_host.cpp), which the kernels equal bit for bit: the crossing tests, the list
+// surgery, the bend-point update and the tether length are ent_device.h's, and this file is built -ffp-contract=off like
+// track_kernels.hip.
+//
+// Layout: one wave (one 64-thread workgroup) per slot.  A pre-kernel writes every slot's positions of the call side by side
+// (round_ticks + 1 of them, or the pair a prediction needs), so nobody strides through the plan rings.  The 64 lanes then take the
+// other agents 64 at a time and each PROVES that its agent adds no crossing at any step of the call (ent_side on the box of the
+// slot's own positions: the same side of every tether segment, of the moving last segment at every tick, and the sweep over our base
+// evaluated as is — ent_agent_may_cross's argument over ticks instead of samples); the statics likewise.  What the __ballot leaves
+// is walked by lane 0 step by step and in increasing index, so the crossings enter the list in the host chain's order.  The working
+// state sits in LDS behind LDS-typed pointers (ds_read / ds_write, not FLAT); it goes to global scratch before a step that can
+// outgrow the record and comes back if it did.  Every barrier is reached by the whole wave: the branches around them depend on
+// kernel arguments and on values every lane loads from the same address.
+#include <hip/hip_runtime.h>
+
+#include "nep_device.h"
+#include "../../include/neptune_frontend.h"
+#include "../../include/neptune_entangle.h"
+#include "../../include/neptune_fleet.h"
+#include "ent_device.h"
+
+namespace nep {
+
+static_assert(kEntAddCap == NEP_ENT_TRACK_ADD_CAP, "nep_ent_track_step's and the kernel's caps on a move's new crossings differ");
+static_assert(sizeof(nep_fe_ent_state) % 4 == 0, "the state is copied in 4-byte units");
+
+namespace {
+
+constexpr int kMaskWords = 64;      // 64-bit ballot words of the candidates' mask: up to 4096 agents (FleetEntArgs is refused beyond)
+constexpr int kStatWords = 64;      // 32-bit words of the statics' mask (EntCtx::m_static): up to 2048 statics
+
+typedef __attribute__((address_space(3))) double* ent_lds_double;
+// The working state: nep_fe_ent_state's members behind LDS-typed pointers (counts in registers).  Betas handled as written, like the
+// fixed record: every byte of the result is compared with the host chain.
+struct EntWork { int n_alpha, n_bend; ent_lds_short id; ent_lds_char cs; ent_lds_double beta; ent_lds_char bend; };
+
+__device__ bool fleet_state_ok(const nep_fe_ent_state* st) {
+  if (st->n_alpha < 0 || st->n_alpha > NEP_FE_ENT_CAP || st->n_bend < 0 || st->n_bend > NEP_MAX_BEND - 1) return false;
+  for (int k = 0; k < st->n_bend; k++) if (st->bend[k] < 0 || st->bend[k] >= st->n_alpha) return false;
+  return true;
+}
+__device__ __forceinline__ int rec_nb(const nep_traj_rec* r) { return min(max(r->n_bend, 0), NEP_MAX_BEND); }
+__device__ __forceinline__ bool rec_present(const nep_traj_rec* r) { return r->valid && r->is_agent && r->pwp.n_seg >= 1; }      // (ent_sample_kernel's rule)
+
+// One thread per (slot, position).  Tracking (start == null): position q of a slot is where it stands after tick q of the round —
+// q = 0 the tracked state, q >= 1 ring[(head + min(q - 1, size - 1)) mod cap], fleet_tick_kernel's pop rule.  Prediction: position 0
+// is the tracked state, position 1 the published record at the slot's t_start by nep_ent_sample_points' first sample (the front end's
+// sampled[i][0][0]).
+__global__ void fleet_ent_pos_kernel(FleetEntArgs ea, FleetArgs fa) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int np = ea.n_steps + 1;
+  if (e >= (long)ea.n_scenes * ea.N * np) return;
+  const long slot = e / np; const int q = (int)(e - slot * np);
+  double x, y;
+  if (q == 0) { x = fa.state[slot * 12]; y = fa.state[slot * 12 + 1]; }
+  else if (!ea.start) {
+    const int size = fa.size[slot], head = fa.head[slot];
+    if (size < 1) { x = fa.state[slot * 12]; y = fa.state[slot * 12 + 1]; }
+    else {
+      const int k = (head + min(q - 1, size - 1)) % fa.cap;
+      const double* g = fa.ring + (slot * fa.cap + k) * 12;
+      x = g[0]; y = g[1];
+    }
+  } else {
+    const nep_traj_rec* rec = ea.recs + slot;
+    x = 0.0; y = 0.0;
+    if (rec_present(rec)) {
+      const double t_start = ea.start[slot].t_start, t_end = t_start + ea.num_pol * ea.T_span;
+      const double deltaT = (t_end - t_start) / (1.0 * ea.num_pol);
+      const double ts = t_start;
+      const int n = min(rec->pwp.n_seg, NEP_TRAJ_MAX_SEG);
+      int low = 0;                                 // std::upper_bound: first knot > ts
+      while (low <= n && !(rec->pwp.times[low] > ts)) low++;
+      int seg; double te;
+      if (low <= n) {
+        seg = low - 1;
+        if (seg < 0) seg = 0; else if (seg > n - 1) seg = n - 1;
+        te = ts - rec->pwp.times[seg];
+        if (te < 0) te = 0; else if (te > deltaT) te = deltaT;
+      } else { seg = n - 1; te = rec->pwp.times[n] - rec->pwp.times[n - 1]; }
+      const double t3 = te * te * te, t2 = te * te;
+      const double* cxp = rec->pwp.coeff[0][seg]; const double* cyp = rec->pwp.coeff[1][seg];
+      x = ((cxp[0] * t3 + cxp[1] * t2) + cxp[2] * te) + cxp[3] * 1.0; y = ((cyp[0] * t3 + cyp[1] * t2) + cyp[2] * te) + cyp[3] * 1.0;
+    }
+  }
+  ea.pos[e * 2] = x; ea.pos[e * 2 + 1] = y;
+}
+
+// publishOwnTraj's bend points (neptune_ros.cpp:457-476) at the select: the list published at the last select becomes the previous
+// one, and the record gets the base and the anchor of every bend index of the state at the tracked position (ent_publish_kernel's
+// rule).  One thread per slot, after fleet_select_kernel has written the record.
+__global__ void fleet_ent_publish_kernel(FleetEntArgs ea) {
+  const long slot = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int N = ea.N;
+  if (slot >= (long)ea.n_scenes * N) return;
+  const int scene = (int)(slot / N), a = (int)(slot % N);
+  double* cur = ea.pub_xy + slot * NEP_MAX_BEND * 2; double* prv = ea.pub_prev_xy + slot * NEP_MAX_BEND * 2;
+  for (int k = 0; k < NEP_MAX_BEND * 2; k++) prv[k] = cur[k];
+  ea.pub_prev_n[slot] = ea.pub_n[slot];
+  const nep_fe_ent_state* st = ea.in + slot;
+  const double* srep = ea.srep + (long)scene * ea.static_stride * 4;
+  nep_traj_rec* r = ea.recs_out + slot;
+  int nb = 1;
+  cur[0] = ea.pb[2 * a]; cur[1] = ea.pb[2 * a + 1];
+  if (fleet_state_ok(st)) {
+    for (int k = 0; k < st->n_bend; k++) {
+      const int id = st->id[st->bend[k]], cs = st->cs[st->bend[k]];
+      double x = 0.0, y = 0.0;
+      if (id >= 1 && id <= N) { x = ea.pb[2 * (id - 1)]; y = ea.pb[2 * (id - 1) + 1]; }
+      else if (id > N && id - N - 1 < ea.S && (cs == 0 || cs == 1)) { x = srep[((id - N - 1) * 2 + cs) * 2]; y = srep[((id - N - 1) * 2 + cs) * 2 + 1]; }
+      cur[2 * (k + 1)] = x; cur[2 * (k + 1) + 1] = y;
+    }
+    nb = 1 + st->n_bend;
+  }
+  for (int k = nb; k < NEP_MAX_BEND; k++) { cur[2 * k] = 0.0; cur[2 * k + 1] = 0.0; }
+  ea.pub_n[slot] = nb;
+  r->n_bend = nb;
+  for (int k = 0; k < NEP_MAX_BEND; k++) { r->bend[k][0] = cur[2 * k]; r->bend[k][1] = cur[2 * k + 1]; }
+}
+
+// One wave per slot: n_steps moves of the slot's own tether state (see the head of the file).
+__global__ __launch_bounds__(64) void fleet_ent_step_kernel(FleetEntArgs ea) {
+  __shared__ __attribute__((aligned(16))) nep_fe_ent_state s_st;
+  __shared__ unsigned long long s_mask[kMaskWords], s_chg[kMaskWords];
+  __shared__ unsigned s_stat[kStatWords];
+  const long slot = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int N = ea.N, T = ea.n_steps, np = T + 1;
+  const int scene = (int)(slot / N), a = (int)(slot - (long)scene * N);
+  const long base = (long)scene * N;
+  const bool predict = ea.start != nullptr;
+  const nep_fe_ent_state* src = ea.in + slot;
+  nep_fe_ent_state* dst = ea.out + slot;
+  for (int i = lane; i < (int)(sizeof(nep_fe_ent_state) / 4); i += 64) ((int*)&s_st)[i] = ((const int*)src)[i];
+  __syncthreads();
+  if (!fleet_state_ok(&s_st)) {      // (s_st is the same for every lane: a uniform branch.  The state stays; a prediction hands it on as it is)
+    if (dst != src) for (int i = lane; i < (int)(sizeof(nep_fe_ent_state) / 4); i += 64) ((int*)dst)[i] = ((const int*)&s_st)[i];
+    if (lane == 0) {
+      ea.flags[slot] = NEP_ENT_TRACK_CAP;
+      if (ea.ever) ea.ever[slot] |= NEP_ENT_TRACK_CAP;
+      atomicOr(ea.gflags, NEP_FLAG_ENT_TRACK);
+    }
+    return;
+  }
+  EntCtx ec;
+  ec.N = N; ec.S = ea.S; ec.own = a; ec.num_pol = ea.num_pol; ec.ns = 1; ec.T_span = 0.0; ec.cable = ea.cable;
+  ec.pb = ea.pb; ec.srep = ea.srep + (long)scene * ea.static_stride * 4; ec.slong = ea.slong + (long)scene * ea.static_stride * 2;
+  ec.sampled = nullptr; ec.present = nullptr; ec.ps = nullptr; ec.scene = scene; ec.n_hull = N;
+  const Ev2 pb_self = ent_pb(ec, a);
+  const double* __restrict__ pos = ea.pos;
+  // the slot's own position after step q (every lane reads the same addresses)
+  auto own = [&](int q) { if (predict && q == 1) return Ev2{ea.start[slot].pos[0], ea.start[slot].pos[1]}; const double* p = pos + (slot * np + q) * 2; return Ev2{p[0], p[1]}; };
+  auto at = [&](long j, int q) { const double* p = pos + ((base + j) * np + q) * 2; return Ev2{p[0], p[1]}; };
+  // ---- the proofs: 64 agents, then 64 statics, at a time -------------------------------------------------------------------
+  EntBox box;
+  { const Ev2 p0 = own(0); box.x0 = box.x1 = p0.x; box.y0 = box.y1 = p0.y; }
+  for (int q = 1; q <= T; q++) { const Ev2 p = own(q); box.x0 = fmin(box.x0, p.x); box.x1 = fmax(box.x1, p.x); box.y0 = fmin(box.y0, p.y); box.y1 = fmax(box.y1, p.y); }
+  const int n_words = (N + 63) >> 6;
+  for (int w = 0; w < n_words; w++) {
+    const int i = (w << 6) + lane;
+    bool maybe = false, changed = false;
+    if (i < N && i != a) {
+      const nep_traj_rec* ri = ea.recs + base + i;
+      const int nb = rec_nb(ri);
+      if (rec_present(ri) && nb >= 1) {
+        if (!ea.proof) maybe = true;
+        else {
+          const double* bp = &ri->bend[0][0];
+          for (int k = 0; k + 1 < nb; k++) maybe |= ent_side(box, Ev2{bp[2 * (k + 1)], bp[2 * (k + 1) + 1]}, Ev2{bp[2 * k], bp[2 * k + 1]}) == 0;
+          const Ev2 bk{bp[2 * (nb - 1)], bp[2 * (nb - 1) + 1]};
+          Ev2 pik = at(i, 0);
+          const int s0 = ent_side(box, pik, bk);
+          maybe |= s0 == 0;
+          for (int q = 1; q <= T; q++) {
+            const Ev2 pik1 = at(i, q);
+            maybe |= ent_side(box, pik1, bk) != s0;
+            const double f1 = ent_wedge(pb_self, pik, bk), f2 = ent_wedge(pb_self, pik1, bk);
+            maybe |= f1 * f2 < 0;
+            pik = pik1;
+          }
+        }
+        // the proof covers the eight-argument form: an agent whose published bend count changed is walked at the first step
+        if (ea.pub_prev_n) { const int n0 = min(max(ea.pub_prev_n[base + i], 0), NEP_MAX_BEND); changed = n0 >= 1 && n0 != nb; }
+      }
+    }
+    const unsigned long long m = __ballot(maybe), c = __ballot(changed);
+    if (lane == 0) { s_mask[w] = m; s_chg[w] = c & ~m; }
+  }
+  const int s_words = (ea.S + 31) >> 5;
+  for (int w2 = 0; w2 < (ea.S + 63) >> 6; w2++) {
+    const int s = (w2 << 6) + lane;
+    const bool maybe = s < ea.S && (!ea.proof || ent_static_may_cross(ec, box, s));
+    const unsigned long long m = __ballot(maybe);
+    if (lane == 0) { s_stat[2 * w2] = (unsigned)m; if (2 * w2 + 1 < s_words) s_stat[2 * w2 + 1] = (unsigned)(m >> 32); }
+  }
+  __syncthreads();
+  // ---- the walk: lane 0, step by step, the survivors in increasing index ---------------------------------------------------
+  if (lane == 0) {
+    ec.m_static = s_stat;
+    EntWork W;
+    W.n_alpha = s_st.n_alpha; W.n_bend = s_st.n_bend;
+    W.id = (ent_lds_short)&s_st.id[0]; W.cs = (ent_lds_char)&s_st.cs[0]; W.beta = (ent_lds_double)&s_st.beta[0]; W.bend = (ent_lds_char)&s_st.bend[0];
+    nep_fe_ent_state* B = ea.save + slot;
+    auto save = [&]() {
+      B->n_alpha = W.n_alpha; B->n_bend = W.n_bend;
+      for (int i = 0; i < W.n_alpha; i++) { B->id[i] = W.id[i]; B->cs[i] = W.cs[i]; B->beta[i] = W.beta[i]; }
+      for (int i = 0; i < W.n_bend; i++) B->bend[i] = W.bend[i];
+    };
+    auto restore = [&]() {
+      W.n_alpha = B->n_alpha; W.n_bend = B->n_bend;
+      for (int i = 0; i < W.n_alpha; i++) { W.id[i] = B->id[i]; W.cs[i] = B->cs[i]; W.beta[i] = B->beta[i]; }
+      for (int i = 0; i < W.n_bend; i++) W.bend[i] = B->bend[i];
+    };
+    unsigned add_tail[kEntAddCap - EntAdd::reg];
+    int fl = 0, walked = 0;
+    Ev2 pk = own(0);
+    for (int q = 1; q <= T; q++) {
+      const bool first = q == 1;
+      const Ev2 pk1 = own(q);
+      EntAdd add; add.attach(EntAdd::Store{add_tail, kEntAddCap}); add.clear();
+      bool abort = false;
+      for (int w = 0; w < n_words; w++) {
+        unsigned long long m = s_mask[w] | (first ? s_chg[w] : 0ull);
+        while (m) {
+          const int i = (w << 6) + __ffsll((long long)m) - 1; m &= m - 1ull;
+          walked++;
+          const nep_traj_rec* ri = ea.recs + base + i;
+          const int nb = rec_nb(ri);
+          const Ev2 pik = at(i, q - 1), pik1 = at(i, q);
+          // the other agent's bend points at the previous check: the list it published a round ago at the round's first tick (an empty
+          // one is taken as the current one, as trajCB does for a first message, neptune_ros.cpp:423), later the same list
+          int nq = nb;
+          if (first && ea.pub_prev_n) { const int n0 = min(max(ea.pub_prev_n[base + i], 0), NEP_MAX_BEND); nq = n0 >= 1 ? n0 : nb; }
+          if (nq == nb) ent_cross_agent(add, pk, pk1, pik, pik1, pb_self, nb, &ri->bend[0][0], i + 1);
+          else abort |= ent_cross_agent_changed(add, pk, pk1, pik, pik1, pb_self, nb, &ri->bend[0][0], nq, ea.pub_prev_xy + (base + i) * NEP_MAX_BEND * 2, i + 1);
+        }
+      }
+      ent_cross_static(add, pk, pk1, ec);
+      if (add.overflow) { fl |= NEP_ENT_TRACK_CAP; pk = pk1; continue; }
+      const bool may_outgrow = add.n > 0 || W.n_bend >= NEP_MAX_BEND - 1;
+      if (may_outgrow) save();
+      bool over = add.n > 0 && ent_merge(add, &W, pk, pb_self, ec);
+      if (!over) { over = ent_update_bends(&W, pk1, pb_self, ec); over |= W.n_bend > NEP_MAX_BEND - 1; }
+      if (over) { restore(); fl |= NEP_ENT_TRACK_CAP; pk = pk1; continue; }
+      if (abort) fl |= NEP_ENT_TRACK_ABORT;
+      for (int e = 0; e < W.n_alpha; e++) {      // active_cases of the agents: entries per id
+        const int id_ = W.id[e];
+        if (id_ > N) continue;
+        const int k = ent_count(W.id, W.n_alpha, id_);
+        if (k > 2) fl |= NEP_ENT_TRACK_ENTANGLED;
+        if (k >= 2) fl |= NEP_ENT_TRACK_TWO_CASES;
+      }
+      if (ent_tether(&W, pb_self, pk1, ec) > ea.cable) fl |= NEP_ENT_TRACK_TOO_LONG;
+      pk = pk1;
+    }
+    // what the record holds beyond its counts is zero: the bytes of a state depend on the state alone
+    for (int i = W.n_alpha; i < NEP_FE_ENT_CAP; i++) { W.id[i] = 0; W.cs[i] = 0; W.beta[i] = 0.0; }
+    for (int i = W.n_bend; i < NEP_MAX_BEND; i++) W.bend[i] = 0;
+    s_st.n_alpha = W.n_alpha; s_st.n_bend = W.n_bend;
+    ea.flags[slot] = fl;
+    if (ea.ever) ea.ever[slot] |= fl;
+    if (ea.walked) ea.walked[slot] += walked;
+    if (fl & NEP_ENT_TRACK_CAP) atomicOr(ea.gflags, NEP_FLAG_ENT_TRACK);
+  }
+  __syncthreads();
+  for (int i = lane; i < (int)(sizeof(nep_fe_ent_state) / 4); i += 64) ((int*)dst)[i] = ((const int*)&s_st)[i];
+}
+
+// One wave per scene: the slots ever flagged NEP_ENT_TRACK_ENTANGLED, into the scene's counter [7] (no atomics: recounted per call)
+__global__ __launch_bounds__(64) void fleet_ent_count_kernel(FleetEntArgs ea) {
+  const long scene = blockIdx.x;
+  int c = 0;
+  for (int a = threadIdx.x; a < ea.N; a += 64) c += (ea.ever[scene * ea.N + a] & NEP_ENT_TRACK_ENTANGLED) != 0;
+  for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m, 64);
+  if (threadIdx.x == 0) ea.counters[scene * NEP_FLEET_N_COUNTERS + 7] = c;
+}
+
+}  // namespace
+
+bool fleet_ent_fits(int N, int S) { return N <= kMaskWords * 64 && S <= kStatWords * 32; }
+
+void launch_fleet_ent_publish(const FleetEntArgs& ea, hipStream_t st) {
+  const long slots = (long)ea.n_scenes * ea.N;
+  hipLaunchKernelGGL(fleet_ent_publish_kernel, dim3((unsigned)((slots + 63) / 64)), dim3(64), 0, st, ea);
+}
+void launch_fleet_ent_steps(const FleetEntArgs& ea, const FleetArgs& fa, hipStream_t st) {
+  const long slots = (long)ea.n_scenes * ea.N;
+  const long total = slots * (ea.n_steps + 1);
+  hipLaunchKernelGGL(fleet_ent_pos_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, ea, fa);
+  hipLaunchKernelGGL(fleet_ent_step_kernel, dim3((unsigned)slots), dim3(64), 0, st, ea);
+  if (ea.ever && ea.counters) hipLaunchKernelGGL(fleet_ent_count_kernel, dim3((unsigned)ea.n_scenes), dim3(64), 0, st, ea);
+}
+
+}  // namespace nep

@@ -290,6 +290,33 @@ void launch_fleet_seed(const FleetArgs& fa, const double* state0, hipStream_t st
 void launch_fleet_select(const FleetArgs& fa, hipStream_t st);
 void launch_fleet_commit(const FleetArgs& fa, hipStream_t st);
 void launch_fleet_tick(const FleetArgs& fa, hipStream_t st);
+// the tethers of the fleet state (fleet_ent_kernels.hip): nep_batch_fleet_select's bend points, _predict_ent, _track_ent
+struct FleetEntArgs {
+  int N, S, n_scenes, static_stride, num_pol;
+  int n_steps;                   // moves of the call: round_ticks (tracking) or 1 (prediction)
+  int proof;                     // 0: every other agent and static is walked at every step (debug option fleet_ent_proof)
+  double cable, T_span;
+  const double* pb;              // [N][2]
+  const double* srep;            // [scenes or 1][S][2][2]
+  const double* slong;           // [scenes or 1][S][2]
+  double* pos;                   // [slots][n_steps + 1][2] scratch: every slot's positions of the call (fleet_ent_pos_kernel)
+  const nep_fe_start* start;     // prediction: [slots] point A and the clock; null: tracking
+  const nep_traj_rec* recs;      // [slots] the records published this round
+  nep_traj_rec* recs_out;        // select: the records the bend points are published into
+  int* pub_n; double* pub_xy;              // [slots], [slots][NEP_MAX_BEND][2] the list published at the last select
+  int* pub_prev_n; double* pub_prev_xy;    // and the one before it (the step kernel: null for a prediction)
+  const nep_fe_ent_state* in;    // [slots] the state at the tracked position
+  nep_fe_ent_state* out;         // [slots] tracking: the same buffer; prediction: the state at A
+  nep_fe_ent_state* save;        // [slots] scratch: the state before a step that may outgrow the record
+  int* flags;                    // [slots] NEP_ENT_TRACK_* bits of the call
+  int* ever;                     // [slots] sticky OR (tracking) or null
+  int* walked;                   // [slots] (other agent, step) pairs walked, accumulated (tracking) or null
+  int* counters;                 // [scenes][NEP_FLEET_N_COUNTERS]: [7] = slots ever flagged NEP_ENT_TRACK_ENTANGLED
+  int* gflags;                   // sticky NEP_FLAG_ENT_TRACK
+};
+bool fleet_ent_fits(int N, int S);
+void launch_fleet_ent_publish(const FleetEntArgs& ea, hipStream_t st);
+void launch_fleet_ent_steps(const FleetEntArgs& ea, const FleetArgs& fa, hipStream_t st);
 void launch_ent_check(const SceneParams& sp, const ProblemSet& ps, const FeEntArgs& ea, const nep_traj_rec* fresh, int n_scenes, double cable, int* entangles, hipStream_t st);
 void launch_next_starts(const nep_traj_rec* recs, int n_scenes, int N, int first_local, int n_local, double dt, nep_fe_start* starts,
                         double* alt, double r_switch, hipStream_t st);

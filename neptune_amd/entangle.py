@@ -127,3 +127,22 @@ class EntangleCheck:
         tin = abi.nep_ent_track_inputs(abi.dptr(a), abi.dptr(b), abi.iptr(pr), abi.iptr(off), abi.dptr(xy), abi.iptr(offp), abi.dptr(xyp))
         p0 = np.ascontiguousarray(pk, dtype=np.float64); p1 = np.ascontiguousarray(pk1, dtype=np.float64)
         return _ck(lib().nep_ent_track_step(C.byref(self.cfg), C.byref(tin), C.byref(state.c), abi.dptr(p0), abi.dptr(p1)), "nep_ent_track_step")
+
+    def predict_a(self, state, pk, pk1, pik, pik1, present, bendpts):
+        """Neptune::PredictAlphasBetas (nep_ent_predict_a): the state after the one move pk -> pk1 of the vehicle, the others going
+        pik -> pik1 with their current bend points as the previous check's too, in a NEW State; `state` is left as it is.
+        -> (State, the NEP_ENT_TRACK_* bits)"""
+        off = np.zeros(self.N + 1, dtype=np.int32)
+        for j, b in enumerate(bendpts):
+            off[j + 1] = off[j] + len(b)
+        xy = np.zeros((max(int(off[-1]), 1), 2))
+        for j, b in enumerate(bendpts):
+            if len(b):
+                xy[off[j]:off[j + 1]] = np.asarray(b, dtype=np.float64).reshape(-1, 2)
+        a = np.ascontiguousarray(pik, dtype=np.float64).reshape(self.N, 2); b = np.ascontiguousarray(pik1, dtype=np.float64).reshape(self.N, 2)
+        pr = np.ascontiguousarray(present, dtype=np.int32).reshape(self.N)
+        p0 = np.ascontiguousarray(pk, dtype=np.float64); p1 = np.ascontiguousarray(pk1, dtype=np.float64)
+        out = State(state.c.n_active, cap=state.c.cap)
+        rc = _ck(lib().nep_ent_predict_a(C.byref(self.cfg), abi.dptr(a), abi.dptr(b), abi.iptr(pr), abi.iptr(off), abi.dptr(xy), C.byref(state.c),
+                                         abi.dptr(p0), abi.dptr(p1), C.byref(out.c)), "nep_ent_predict_a")
+        return out, rc

@@ -10,20 +10,58 @@ import numpy as np
 
 from . import abi, plan, scene
 from . import audit as audit_mod
+from ._lib import BackendError
 from .backend import BatchBackend
 
 
+def ent_state_record(st):
+    """an entangle.State as one FE_ENT_STATE_DTYPE record (what the front end and the safety pass take as d_ent_init)"""
+    al, be_, bi, _ = st.as_lists()
+    r = np.zeros(1, dtype=abi.FE_ENT_STATE_DTYPE)
+    r["n_alpha"] = len(al); r["n_bend"] = len(bi)
+    for k, (i, c) in enumerate(al):
+        r["id"][0, k] = i; r["cs"][0, k] = c; r["beta"][0, k] = be_[k]
+    for k, b in enumerate(bi):
+        r["bend"][0, k] = b
+    return r[0]
+
+
+def ent_published_bends(st, pb, a, reps):
+    """publishOwnTraj's bend points of agent a's state: its base, then the anchor of every bend index (an agent's base or a static
+    representative's column) -> [1 + n_bend][2]"""
+    al, _, bi, _ = st.as_lists()
+    N = len(pb)
+    return np.array([pb[a]] + [pb[al[b][0] - 1] if al[b][0] <= N else reps[al[b][0] - N - 1][al[b][1]] for b in bi], dtype=np.float64).reshape(-1, 2)
+
+
 class FleetLoop:
-    def __init__(self, par, statics, starts, goals, beam_width=32, delta_t_states=6, replan_every=5, device=None, skip_arrived=False, audit=False):
+    def __init__(self, par, statics, starts, goals, beam_width=32, delta_t_states=6, replan_every=5, device=None, skip_arrived=False, audit=False,
+                 tethers=False, check=True, ent_samples=3):
         import torch
         self.torch = torch
+        self.tethers, self.check, self.ent_samples = tethers, check, ent_samples
+        if tethers:
+            import dataclasses
+            par = dataclasses.replace(par, enable_entangle=True)
         self.p, self.statics = par, statics
         self.N = N = par.num_agents
         self.goals = np.asarray(goals, dtype=np.float64).reshape(N, 3)
         self.be = BatchBackend(par, statics, n_scenes=1, device=device)
         self.be.set_safety_check_prev(True)    # nobody commits a trajectory that crosses what somebody else may keep flying
         self.be.set_line_cull(4.0)             # presolve: far separating lines are verified, not solved for (same optimum)
-        self.fe = scene.frontend_cfg(par, beam_width=beam_width, pad_hold=1)
+        self.fe = scene.frontend_cfg(par, beam_width=beam_width, pad_hold=1, entangle=tethers and check, ent_samples=ent_samples)
+        if tethers:
+            # the one-scene host form of DeviceFleetLoop(tethers=True): entangle_state_ of every agent at its tracked position is kept
+            # here (nep_ent_track_step per control tick), the state at A comes from nep_ent_predict_a every round
+            from . import entangle
+            self._reps, self._longest = scene.static_reps(statics) if len(statics) else (np.zeros((0, 2, 2)), np.zeros((0, 2)))
+            self.be.set_static_reps(self._reps, self._longest)
+            self._chk = [entangle.EntangleCheck(N, a + 1, par.num_pol, ent_samples, par.T_span, par.tether_length, par.pb, self._reps, self._longest)
+                         for a in range(N)]
+            self.ent = [entangle.State(N + len(self._reps), cap=abi.NEP_FE_ENT_CAP) for _ in range(N)]
+            self._bends_prev = None            # the lists published a round ago (bendPtsForAgents_prev_)
+            self.ent_ever = np.zeros(N, dtype=np.int32)
+            self.ent_flags = np.zeros(N, dtype=np.int32)
         self.dc, self.T = par.dc, par.T_span
         self.k_a = delta_t_states - 1          # index of point A in the plan (neptune.cpp:1376-1385 with deltaT_ states ahead)
         self.replan_every = replan_every       # control ticks between rounds (replan timer / dc)
@@ -60,6 +98,9 @@ class FleetLoop:
             r["bbox"] = 2 * self.p.drone_radius
             r["pos"] = self.state[a, :3]
             r["bend"][0] = self.p.pb[a]
+            if self.tethers:                    # the bend points of entangle_state_ (publishOwnTraj, neptune_ros.cpp:457-476)
+                b = ent_published_bends(self.ent[a], self.p.pb, a, self._reps)
+                r["n_bend"] = len(b); r["bend"][: len(b)] = b
             pw = self.prev_pwp[a]
             if pw is None:                      # not flying yet: a one-interval hover
                 r["pwp"]["n_seg"] = 1
@@ -112,10 +153,22 @@ class FleetLoop:
             be.audit(d_com, be.to_device(clock), self.dc, self.replan_every, self.d_audit)
         d_guess = torch.zeros(N * abi.GUESS_DTYPE.itemsize, dtype=torch.uint8, device=be.device)
         d_fres = torch.zeros(N * abi.FE_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=be.device)
-        be.frontend(self.fe, d_com, d_start, d_guess, d_fres)
-        be.replan(None, d_guess)
         d_final = torch.empty_like(d_com); d_acc = torch.zeros(N, dtype=torch.int32, device=be.device)
-        be.safety_commit(d_com, be.d_commit, d_guess, d_final, d_acc)
+        if self.tethers:
+            bends = self._predict_a(rec, starts, t_start)
+        if self.tethers and self.check:
+            d_ent_a = be.to_device(self.ent_a)
+            d_case = torch.zeros(N * abi.NEP_MAX_POL * N, dtype=torch.int32, device=be.device)
+            be.frontend_ent(self.fe, d_com, d_start, d_guess, d_fres, d_case, d_ent_init=d_ent_a)
+            be.replan(None, d_guess, d_ent=d_case)
+            self._stamp_bends(be.d_commit, d_com)
+            be.safety_commit_ent(d_com, be.d_commit, d_guess, d_final, d_acc, d_ent_init=d_ent_a, ent_samples=self.ent_samples)
+        else:
+            be.frontend(self.fe, d_com, d_start, d_guess, d_fres)
+            be.replan(None, d_guess)
+            if self.tethers:
+                self._stamp_bends(be.d_commit, d_com)
+            be.safety_commit(d_com, be.d_commit, d_guess, d_final, d_acc)
         sol = be.solutions(); states = be.states(); fres = d_fres.cpu().numpy().view(abi.FE_RESULT_DTYPE)
         acc = d_acc.cpu().numpy()
         self.stats["rounds"] += 1
@@ -144,18 +197,62 @@ class FleetLoop:
                 # what the others must avoid is the path actually flown: nep_pwp_compose_exact.  (mu::composePieceWisePol,
                 # nep_pwp_compose, describes the stretch up to point A with the wrong interval; include/neptune_plan.h)
                 self.prev_pwp[a] = plan.compose_exact(t_now, self.prev_pwp[a], new)
-        for _ in range(self.replan_every):
+        if self.tethers:
+            self.ent_flags[:] = 0
+        for q in range(self.replan_every):
+            before = self.state[:, :2].copy()
             self._tick()
+            if self.tethers:                    # odomCB -> updateEntStateStaticObs, once per control tick
+                self._track_tick(before, self.state[:, :2].copy(), bends, q == 0)
+        if self.tethers:
+            self._bends_prev = bends
         # arrived (sticky): inside the goal radius and practically at rest; such an agent stops replanning and its
         # committed trajectory keeps it where it is (DroneStatus GOAL_REACHED, neptune.cpp:1701-1711)
         slow = np.sqrt((self.state[:, 3:5] ** 2).sum(axis=1)) < 0.05
         self.done |= (np.hypot(*(self.state[:, :2] - self.goals[:, :2]).T) < p_goal_radius(self.fe)) & slow
         return self.done.all()
 
+    # ---- tethers (host form of nep_batch_fleet_predict_ent / nep_batch_fleet_track_ent) ----
+    def _predict_a(self, rec, starts, t_start):
+        """Neptune::PredictAlphasBetas per agent -> self.ent_a ([N] FE_ENT_STATE_DTYPE), self.flags_a; returns the round's published bend lists"""
+        from . import entangle
+        N, p = self.N, self.p
+        bends = [np.array(rec[j]["bend"][: int(rec[j]["n_bend"])], dtype=np.float64) for j in range(N)]
+        pik = self.state[:, :2].copy()
+        pik1 = np.stack([entangle.sample_points(rec[j]["pwp"], t_start, t_start + p.num_pol * p.T_span, p.num_pol, self.ent_samples)[0, 0] for j in range(N)])
+        present = np.ones(N, dtype=np.int32)
+        self.ent_a = np.zeros(N, dtype=abi.FE_ENT_STATE_DTYPE); self.flags_a = np.zeros(N, dtype=np.int32)
+        for a in range(N):
+            out, fl = self._chk[a].predict_a(self.ent[a], pik[a], starts[a]["pos"][:2], pik, pik1, present, bends)
+            self.ent_a[a] = ent_state_record(out); self.flags_a[a] = fl
+        return bends
+
+    def _stamp_bends(self, d_new, d_com):
+        """the published bend points into the commit records (TetherLoop._publish)"""
+        f = abi.TRAJ_REC_DTYPE.fields
+        R = abi.TRAJ_REC_DTYPE.itemsize
+        vn, vr = d_new.view(-1, R), d_com.view(-1, R)
+        for lo, hi in ((f["n_bend"][1], f["n_bend"][1] + 4), (f["bend"][1], f["bend"][1] + f["bend"][0].itemsize)):
+            vn[:, lo:hi].copy_(vr[:, lo:hi])
+
+    def _track_tick(self, before, after, bends, first):
+        N = self.N
+        old = bends
+        if first and self._bends_prev is not None:      # the previous check saw the lists published a round ago
+            old = [self._bends_prev[j] if len(self._bends_prev[j]) else bends[j] for j in range(N)]
+        present = np.ones(N, dtype=np.int32)
+        for a in range(N):
+            fl = self._chk[a].track_step(self.ent[a], before[a], after[a], before, after, present, bends, old)
+            self.ent_flags[a] |= fl; self.ent_ever[a] |= fl
+
     def run(self, max_rounds=400):
         for _ in range(max_rounds):
             if self.round():
                 break
+        if self.tethers:
+            self.stats["ever_entangled"] = int(((self.ent_ever & abi.NEP_ENT_TRACK_ENTANGLED) != 0).sum())
+            self.stats["too_long"] = int(((self.ent_ever & abi.NEP_ENT_TRACK_TOO_LONG) != 0).sum())
+            self.stats["track_cap"] = int(((self.ent_ever & abi.NEP_ENT_TRACK_CAP) != 0).sum())
         self.stats["sim_time"] = self.t
         self.stats["reached"] = int(self.done.sum())
         self.stats["dist_to_goal_mean"] = float(np.hypot(*(self.state[:, :2] - self.goals[:, :2]).T).mean())
@@ -203,23 +300,40 @@ class DeviceFleetLoop:
     round's start over the replan_every ticks about to be flown, from t_now + dc: FleetLoop's placement and clock.  ring_cap: a
     smaller plan ring than a splice can need (tests of the capacity path).
     run() downloads the slots' arrival flags (4 bytes per slot) after every round to know when to stop; nothing else leaves the
-    device before report().  trace=True additionally downloads outcome, K and the two statuses per round (FleetLoop.trace)."""
+    device before report().  trace=True additionally downloads outcome, K and the two statuses per round (FleetLoop.trace).
+
+    tethers=True flies tethered agents: the handle is created with enable_entangle and carries every tether's
+    entangle state at the tracked position, and the round becomes
+
+        fleet_select -> fleet_predict_ent -> frontend_ent -> replan (entangle rows) -> safety_commit_ent -> fleet_commit -> [audit]
+          -> fleet_track_ent -> fleet_tick
+
+    with the state at A (d_ent_a) predicted on the device and the commit records stamped with the published bend points before the
+    safety pass (TetherLoop._publish).  check=False keeps the plain front end and safety pass and leaves the tracking on: what the
+    same fleet does to its tethers when nobody looks.  report() then also gives ever_entangled, too_long and track_cap per scene."""
 
     def __init__(self, scenes, beam_width=32, delta_t_states=6, replan_every=5, periods=None, phases=None, audit=False, graph=True,
-                 goals=None, device=None, ring_cap=0, trace=False):
+                 goals=None, device=None, ring_cap=0, trace=False, tethers=False, check=True, ent_samples=3):
         import torch
         self.torch = torch
         self.scenes = scenes
         S = self.S = len(scenes)
         p = self.p = scenes[0]["par"]
+        self.tethers, self.check, self.ent_samples = tethers, check, ent_samples
+        if tethers:
+            import dataclasses
+            p = self.p = dataclasses.replace(p, enable_entangle=True)
         N = self.N = p.num_agents
         self.graph, self.replan_every = graph, replan_every
         be = self.be = BatchBackend(p, scenes[0]["statics"], n_scenes=S, device=device)
         for s, sc in enumerate(scenes):
             be.set_scene_statics(s, sc["statics"])
+            if tethers:
+                reps, longest = scene.static_reps(sc["statics"]) if len(sc["statics"]) else (np.zeros((0, 2, 2)), np.zeros((0, 2)))
+                be.set_static_reps(reps, longest, scene=s)
         be.set_safety_check_prev(True)
         be.set_line_cull(4.0)
-        self.fe = scene.frontend_cfg(p, beam_width=beam_width, pad_hold=1)
+        self.fe = scene.frontend_cfg(p, beam_width=beam_width, pad_hold=1, entangle=tethers and check, ent_samples=ent_samples)
         self.goals = np.stack([np.asarray(scene.reachable_goals(sc) if goals is None else goals[s], dtype=np.float64).reshape(N, 3)
                                for s, sc in enumerate(scenes)])
         state0 = np.zeros((S, N, 12))
@@ -253,29 +367,61 @@ class DeviceFleetLoop:
         if audit:
             self.d_audit = be.new_audit()
             be.audit(self.d_rec, self.d_clock, p.dc, 0, self.d_audit)      # (the call that allocates: made here, outside any capture)
+        if tethers:
+            be.fleet_init_ent()
+            self.d_ent_a = torch.zeros(n * abi.FE_ENT_STATE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            self.d_flags_a = torch.zeros(n, dtype=torch.int32, device=dev)
+            self.d_flags = torch.zeros(n, dtype=torch.int32, device=dev)
+            self.d_case = torch.zeros(n * abi.NEP_MAX_POL * N, dtype=torch.int32, device=dev)
+            f = abi.TRAJ_REC_DTYPE.fields
+            self._bend_cols = (f["n_bend"][1], f["n_bend"][1] + 4), (f["bend"][1], f["bend"][1] + f["bend"][0].itemsize)
         self.rounds = 0
         self._g = None
         self.trace = [] if trace else None
         self.after_commit = None      # test hook: called between fleet_commit and fleet_tick of an eager round
+        self.after_select = None      # test hook (tethered rounds): called after fleet_predict_ent of an eager round
         self.done = np.zeros((S, N), dtype=bool)
+
+    def _publish(self, d_new):
+        """stamp the bend points every agent published at the select into its commit record (the QP's records carry the base only):
+        the safety pass judges the new trajectories with the tethers the others see"""
+        R = abi.TRAJ_REC_DTYPE.itemsize
+        vn, vr = d_new.view(-1, R), self.d_rec.view(-1, R)
+        for lo, hi in self._bend_cols:
+            vn[:, lo:hi].copy_(vr[:, lo:hi])
 
     def _round_ops(self):
         be = self.be
         be.fleet_select(self.d_start, self.d_rec, self.d_active, self.d_clock if self.d_audit is not None else None)
-        be.frontend(self.fe, self.d_rec, self.d_start, self.d_guess, self.d_res)
-        be.replan(None, self.d_guess)
-        be.safety_commit(self.d_rec, be.d_commit, self.d_guess, self.d_final, self.d_acc)
+        if self.tethers:
+            be.fleet_predict_ent(self.d_start, self.d_rec, self.d_ent_a, self.d_flags_a)
+            if self.after_select is not None:
+                self.after_select(self)
+        if self.tethers and self.check:
+            be.frontend_ent(self.fe, self.d_rec, self.d_start, self.d_guess, self.d_res, self.d_case, d_ent_init=self.d_ent_a)
+            be.replan(None, self.d_guess, d_ent=self.d_case)
+            self._publish(be.d_commit)
+            be.safety_commit_ent(self.d_rec, be.d_commit, self.d_guess, self.d_final, self.d_acc, d_ent_init=self.d_ent_a,
+                                 ent_samples=self.ent_samples)
+        else:
+            be.frontend(self.fe, self.d_rec, self.d_start, self.d_guess, self.d_res)
+            be.replan(None, self.d_guess)
+            if self.tethers:
+                self._publish(be.d_commit)
+            be.safety_commit(self.d_rec, be.d_commit, self.d_guess, self.d_final, self.d_acc)
         be.fleet_commit(self.d_res, self.d_acc, self.d_outcome)
         if self.after_commit is not None:
             self.after_commit(self)
         if self.d_audit is not None:
             be.audit(self.d_rec, self.d_clock, self.p.dc, self.replan_every, self.d_audit)
+        if self.tethers:
+            be.fleet_track_ent(self.d_rec, self.d_flags)
         be.fleet_tick()
 
     def round(self):
         """one bulk-synchronous round of every scene; True when every agent of every scene has arrived"""
         torch = self.torch
-        if self.graph and self.rounds >= 1 and self.after_commit is None:
+        if self.graph and self.rounds >= 1 and self.after_commit is None and self.after_select is None:
             if self._g is None:
                 torch.cuda.synchronize()
                 s = torch.cuda.Stream(self.be.device)
@@ -307,11 +453,16 @@ class DeviceFleetLoop:
         """per scene FleetLoop.stats' keys (min_pair_dist / min_static_dist come from the audit when it is on), plus `cap` and the
         audit's summary"""
         be = self.be
-        be.check()
+        try:
+            be.check()
+        except BackendError:      # (a tether that dropped a move at a capacity is reported as track_cap, not raised)
+            if not (self.tethers and (be.fleet_ent_state(states=False)["ever"] & abi.NEP_ENT_TRACK_CAP).any()):
+                raise
         cnt, t_now, rnd = be.fleet_counters()
         st = be.fleet_state(pwp=False)
         state = st["state"].reshape(self.S, self.N, 12); done = st["done"].reshape(self.S, self.N)
         summ = audit_mod.summarize(self.audit_records(), self.S) if self.d_audit is not None else None
+        ever = be.fleet_ent_state(states=False)["ever"].reshape(self.S, self.N) if self.tethers else None
         out = []
         for s in range(self.S):
             c = cnt[s]
@@ -319,6 +470,10 @@ class DeviceFleetLoop:
                      qp_relaxed=int(c[6]), rejected_by_safety=int(c[3]), cap=int(c[5]), skipped=int(c[0]),
                      solves=int(c[1] + c[2] + c[3] + c[4] + c[5] + (0 if self.masked else c[0])), sim_time=float(t_now[s]), reached=int(done[s].sum()),
                      dist_to_goal_mean=float(np.hypot(*(state[s, :, :2] - self.goals[s, :, :2]).T).mean()))
+            if ever is not None:      # agents whose tether was ever entangled / longer than the cable / dropped a move at a capacity
+                d["ever_entangled"] = int(c[7])
+                d["too_long"] = int(((ever[s] & abi.NEP_ENT_TRACK_TOO_LONG) != 0).sum())
+                d["track_cap"] = int(((ever[s] & abi.NEP_ENT_TRACK_CAP) != 0).sum())
             if summ is not None:
                 d["audit"] = summ[s]
                 d["min_pair_dist"] = summ[s]["min_center_dist"]["value"] if summ[s]["min_center_dist"] else np.inf

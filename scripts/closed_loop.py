@@ -2,7 +2,9 @@
 """Closed-loop flight of a fleet on the device path (neptune_amd/loop.py): every agent flies from its
 start next to its base to a random goal, replanning in bulk-synchronous rounds, the way the reference's
 benchmark driver logs a run (scripts/benchmark_mtlp.py:215-223: elapsed time, distance, success).
-  python scripts/closed_loop.py [--agents 16 --obstacles 8 --seed 0 --beam 32 --skip-arrived --audit]"""
+  python scripts/closed_loop.py [--agents 16 --obstacles 8 --seed 0 --beam 32 --skip-arrived --audit --tethers [--no-check]]
+--tethers: tethered agents, the one-scene host form of DeviceFleetLoop(tethers=True) (entangle states kept on the host with
+nep_ent_track_step per control tick, nep_ent_predict_a per round)."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from neptune_amd import scene
@@ -13,10 +15,13 @@ ap.add_argument("--agents", type=int, default=16); ap.add_argument("--obstacles"
 ap.add_argument("--seed", type=int, default=0); ap.add_argument("--beam", type=int, default=32); ap.add_argument("--max-rounds", type=int, default=400)
 ap.add_argument("--skip-arrived", action="store_true", help="arrived agents leave the active set (nep_batch_set_active) instead of being solved and discarded")
 ap.add_argument("--audit", action="store_true", help="flight audit on the device (nep_batch_audit) next to the host's distance log")
+ap.add_argument("--tethers", action="store_true", help="tethered agents: entangle-aware front end and safety pass, tether states tracked per control tick")
+ap.add_argument("--no-check", action="store_true", help="with --tethers: plain front end and safety pass, the tracking stays on")
 a = ap.parse_args()
 sc = scene.make_scene(a.agents, a.obstacles, seed=a.seed)
 t0 = time.perf_counter()
-loop = FleetLoop(sc["par"], sc["statics"], sc["starts"], scene.reachable_goals(sc), beam_width=a.beam, skip_arrived=a.skip_arrived, audit=a.audit)
+loop = FleetLoop(sc["par"], sc["statics"], sc["starts"], scene.reachable_goals(sc), beam_width=a.beam, skip_arrived=a.skip_arrived, audit=a.audit, tethers=a.tethers,
+                 check=not a.no_check)
 if a.audit:
     loop.trace = []
 st = loop.run(a.max_rounds)

@@ -1,9 +1,11 @@
 """The faithful closed loop on the device (neptune_amd.loop.DeviceFleetLoop, include/neptune_fleet.h): plan deques, point A, splice,
 composition and control ticks of every agent of every scene in the batched handle, one captured graph per round:
-fleet_select -> front end -> lines + QP -> safety pass -> fleet_commit -> [audit] -> fleet_tick.  Prints the per-scene report (FleetLoop's
+fleet_select -> front end -> lines + QP -> safety pass -> fleet_commit -> [audit] -> fleet_tick; with --tethers the tethered round
+fleet_select -> fleet_predict_ent -> entangle-aware front end -> lines + QP with the entangle rows -> safety pass with the entangle
+re-check -> fleet_commit -> [audit] -> fleet_track_ent -> fleet_tick (--no-check: the plain front end and safety pass, tracking on).  Prints the per-scene report (FleetLoop's
 stats), the totals, the wall time per round and, with --audit, the worst clearances over all scenes.
 
-  python scripts/fleet_loop.py --agents 64 --obstacles 20 --scenes 128 --rounds 30 [--stagger 5] [--audit] [--host]
+  python scripts/fleet_loop.py --agents 64 --obstacles 20 --scenes 128 --rounds 30 [--stagger 5] [--audit] [--host] [--tethers [--no-check]]
 
 --stagger P: every agent replans every P-th round, agent a in the rounds with (round - a) mod P == 0, and a round flies one control
 tick (FleetLoop's cadence at P = 5 with the agents' timers spread over the ticks).  --host flies scene 0 with FleetLoop as well and
@@ -28,6 +30,9 @@ def main():
     ap.add_argument("--stagger", type=int, default=0, metavar="P")
     ap.add_argument("--audit", action="store_true", help="flight audit of every round, inside the graph")
     ap.add_argument("--eager", action="store_true", help="no graph capture")
+    ap.add_argument("--tethers", action="store_true", help="tethered agents: entangle states tracked per control tick, predicted at A, checked by the front end and the safety pass")
+    ap.add_argument("--no-check", action="store_true", help="with --tethers: plain front end and safety pass, the tracking stays on")
+    ap.add_argument("--no-proof", action="store_true", help="with --tethers: debug option fleet_ent_proof 0 (every other agent walked at every tick)")
     ap.add_argument("--host", action="store_true", help="also fly scene 0 with FleetLoop and with DeviceFleetLoop(S = 1): wall time per round of both")
     a = ap.parse_args()
     import numpy as np
@@ -37,11 +42,15 @@ def main():
     seeds = [a.seed0 + k for k in range(a.scenes)]
     scenes = scene.make_scenes(a.agents, a.obstacles, seeds, workers=min(len(seeds), len(os.sched_getaffinity(0)), 16))
     kw = dict(beam_width=a.beam, audit=a.audit, graph=not a.eager)
+    if a.tethers:
+        kw.update(tethers=True, check=not a.no_check)
     if a.stagger > 0:
         kw.update(replan_every=1, periods=a.stagger, phases=np.tile(np.arange(a.agents) % a.stagger, (a.scenes, 1)))
 
     def fly(scs, rounds):
         lp = DeviceFleetLoop(scs, **kw)
+        if a.tethers and a.no_proof:
+            lp.be.debug_option("fleet_ent_proof", 0)
         lp.round(); lp.round()      # the eager round and the capture
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -53,6 +62,10 @@ def main():
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         rep = lp.report()
+        if a.tethers:
+            w = lp.be.fleet_ent_state(states=False)["walked"]
+            print("tether tracking: %d of %d (other agent, tick) pairs walked, the rest proven free of crossings"
+                  % (int(w.sum()), len(scs) * lp.N * (lp.N - 1) * lp.replan_every * (n + 2)))
         lp.close()
         return rep, dt / max(n, 1), n + 2
 
@@ -60,6 +73,8 @@ def main():
     for s, r in enumerate(rep):
         print("scene %d (seed %d): %s" % (s, seeds[s], json.dumps({k: v for k, v in r.items() if k != "audit"})))
     tot = {k: int(sum(r[k] for r in rep)) for k in ("replans", "accepted", "fe_no_solution", "qp_failed", "qp_relaxed", "rejected_by_safety", "cap", "skipped", "reached")}
+    if a.tethers:
+        tot.update({k: int(sum(r[k] for r in rep)) for k in ("ever_entangled", "too_long", "track_cap")})
     print("total over %d scenes x %d agents, %d rounds: %s" % (a.scenes, a.agents, n, json.dumps(tot)))
     print("wall time per round (rounds 3..%d, %s, arrival flags downloaded every round): %.3f ms = %.1f rounds/s, %.0f scene-rounds/s"
           % (n, "eager" if a.eager else "one graph", per_round * 1e3, 1.0 / per_round, a.scenes / per_round))
@@ -71,7 +86,7 @@ def main():
     if a.host:
         sc = scenes[0]
         _, dev1, n1 = fly([sc], a.rounds)
-        ref = FleetLoop(sc["par"], sc["statics"], sc["starts"], scene.reachable_goals(sc), beam_width=a.beam, audit=a.audit)
+        ref = FleetLoop(sc["par"], sc["statics"], sc["starts"], scene.reachable_goals(sc), beam_width=a.beam, audit=a.audit, tethers=a.tethers, check=not a.no_check)
         ref.round(); ref.round()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
