@@ -150,6 +150,11 @@ int nep_batch_debug_polish_count(nep_batch_t* h, int32_t* listed, int32_t* certi
  * nep_stats.solve_us includes the pass's device time).                                                                                  */
 int nep_batch_debug_polish_flags(nep_batch_t* h, int32_t* flags, int32_t cap);
 
+/* Test hook of the library's ownership of memory: the bytes of device memory and of page-locked host memory that the handles and
+ * calls of this process hold right now (every buffer of the two handle kinds and of the stand-alone calls; the staging buffers of
+ * nep_comm_* are not counted).  A handle's destroy, a failed create and a returned stand-alone call leave both where they were.   */
+int nep_debug_live_bytes(int64_t* device_bytes, int64_t* pinned_bytes);
+
 #ifdef __cplusplus
 }
 #endif

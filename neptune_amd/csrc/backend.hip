@@ -5,11 +5,13 @@
 // every compute entry point returns NEP_E_HIP.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -29,35 +31,52 @@ int fail(int code, const std::string& msg) { g_err = msg; return code; }
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(NEP_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 #define HIPCHK_NULL(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { g_err = std::string(#x) + ": " + hipGetErrorString(e_); return nullptr; } } while (0)
 
+// bytes the process's DevBufs and PinnedArenas hold right now (nep_debug_live_bytes: what the ownership tests read)
+std::atomic<long long> g_live_device{0}, g_live_pinned{0};
+
+// Device memory with one owner: the destructor frees, a move hands the memory over, there is no copy.
 template <class T> struct DevBuf {
   T* p = nullptr; size_t n = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { release(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; } return *this; }
+  ~DevBuf() { release(); }
   int ensure(size_t count) {
     if (count <= n && p) return 0;
-    if (p) hipFree(p);
-    p = nullptr; n = 0;
+    release();
     if (count == 0) count = 1;
     hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
-    if (e != hipSuccess) { g_err = std::string("hipMalloc: ") + hipGetErrorString(e); return NEP_E_HIP; }
-    n = count;
+    if (e != hipSuccess) { p = nullptr; g_err = std::string("hipMalloc: ") + hipGetErrorString(e); return NEP_E_HIP; }
+    n = count; g_live_device += (long long)(n * sizeof(T));
     return 0;
   }
-  void release() { if (p) hipFree(p); p = nullptr; n = 0; }
+  void release() { if (p) { hipFree(p); g_live_device -= (long long)(n * sizeof(T)); } p = nullptr; n = 0; }
 };
 
-// Page-locked host memory (the per-agent handle's staging arenas: one DMA in, one out per replan).  Growth keeps the contents.
+// Page-locked host memory (the per-agent handle's staging arenas: one DMA in, one out per replan), owned like a DevBuf.  Growth keeps
+// the contents.
 struct PinnedArena {
   char* p = nullptr; size_t n = 0;
+  PinnedArena() = default;
+  PinnedArena(const PinnedArena&) = delete;
+  PinnedArena& operator=(const PinnedArena&) = delete;
+  PinnedArena(PinnedArena&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+  PinnedArena& operator=(PinnedArena&& o) noexcept { if (this != &o) { release(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; } return *this; }
+  ~PinnedArena() { release(); }
   int ensure(size_t bytes) {
     if (bytes <= n && p) return 0;
     char* q = nullptr;
     hipError_t e = hipHostMalloc((void**)&q, bytes ? bytes : 1, hipHostMallocDefault);
     if (e != hipSuccess) { g_err = std::string("hipHostMalloc: ") + hipGetErrorString(e); return NEP_E_HIP; }
-    if (p) { std::memcpy(q, p, n); hipHostFree(p); }
+    if (p) std::memcpy(q, p, n);
     if (bytes > n) std::memset(q + n, 0, bytes - n);
-    p = q; n = bytes;
+    release();
+    p = q; n = bytes; g_live_pinned += (long long)(bytes ? bytes : 1);
     return 0;
   }
-  void release() { if (p) hipHostFree(p); p = nullptr; n = 0; }
+  void release() { if (p) { hipHostFree(p); g_live_pinned -= (long long)(n ? n : 1); } p = nullptr; n = 0; }
 };
 
 constexpr size_t kLdsBudget = 150 * 1024;  // of the 160 KiB per CU
@@ -206,7 +225,11 @@ struct Engine {
   }
   int last_path = 0;           // NEP_PATH_* bits: what the last run() launched (nep_batch_debug_launch_path)
   int lines_cap_user = 0;      // 0: the default budget; -1: the reference's worst case; n > 0: n lines per segment (nep_batch_set_line_capacity)
-  bool skip_mode() const { return sp.cull_radius > 0.0 && use_reg && sp.sep_rule == 0 && sp.skip_own == 1 && sp.n_hull == sp.num_agents && skip_lps && statics_boxy && !no_redo; }
+  // LPs whose line is known to be far without solving them may be skipped when the presolve is on, the rule is the largest gap
+  // (box far => line far holds for that vertex only), the hull lists are the batch's (one per agent: the boxes are indexed
+  // by agent) and the interior point is the register kernel (the one that verifies them): see separator_body / qp_reg_kernel
+  bool can_skip_lps() const { return sp.cull_radius > 0.0 && use_reg && sp.sep_rule == 0 && sp.skip_own == 1 && sp.n_hull == sp.num_agents && skip_lps && statics_boxy; }
+  bool skip_mode() const { return can_skip_lps() && !no_redo; }      // ... and the replans that fail the verification go through the redo pass
   int size_row_scratch() {
     const long slots = (long)n_scenes * sp.n_local;
     const bool pooled = skip_mode() && !scratch_full && slots > kScratchPool;
@@ -303,11 +326,8 @@ struct Engine {
     ps.fe_order = nullptr; ps.fe_order_key = (lpt && fe_lpt && d_fe_order_key.n >= (size_t)n_scenes * (size_t)sp.n_local) ? d_fe_order_key.p : nullptr; ps.fe_us = d_fe_us.p;
     ps.line_nd = d_line_nd.p; ps.line_cnt = d_line_cnt.p; ps.lp_stats = d_lp_stats.p;
     ps.line_far = sp.cull_radius > 0.0 ? d_line_far.p : nullptr;
-    // LPs whose line is known to be far without solving them are skipped when the presolve is on, the rule is the largest gap
-    // (box far => line far holds for that vertex only), the hull lists are the batch's (one per agent: the boxes are indexed
-    // by agent) and the interior point is the register kernel (the one that verifies them): see separator_body / qp_reg_kernel
-    const bool skip = sp.cull_radius > 0.0 && use_reg && sp.sep_rule == 0 && sp.skip_own == 1 && sp.n_hull == sp.num_agents && skip_lps && statics_boxy;
-    ps.scratch_chunks = (skip && !no_redo) ? scratch_chunks : 0; ps.scratch_by_block = 0;
+    const bool skip = can_skip_lps();
+    ps.scratch_chunks = skip_mode() ? scratch_chunks : 0; ps.scratch_by_block = 0;
     ps.skip_box = skip ? d_fe_box.p : nullptr; ps.line_skip = skip ? d_line_skip.p : nullptr;
     ps.redo_list = skip ? d_redo_list.p : nullptr; ps.redo_count = skip ? d_redo_count.p : nullptr; ps.order_count = nullptr;
     ps.sep_pack = sep_pack;
@@ -402,8 +422,7 @@ struct Engine {
         HIPCHK(hipMemcpy(nel.p + (size_t)s * S * kHullV, d_static_el.p, (size_t)S * kHullV * sizeof(double), hipMemcpyDeviceToDevice));
         HIPCHK(hipMemcpy(nnv.p + (size_t)s * S, d_static_nv.p, (size_t)S * sizeof(int), hipMemcpyDeviceToDevice));
       }
-      d_static_xy.release(); d_static_el.release(); d_static_nv.release();
-      d_static_xy = nxy; d_static_el = nel; d_static_nv = nnv;
+      d_static_xy = std::move(nxy); d_static_el = std::move(nel); d_static_nv = std::move(nnv);
       sp.static_stride = S;
       // the entangle check's representatives (nep_batch_set_static_reps) are indexed like the polygons: one set per scene from
       // now on.  A set uploaded while the statics were shared is replicated; every scene can then be given its own.
@@ -415,7 +434,7 @@ struct Engine {
           HIPCHK(hipMemcpy(nr.p + (size_t)s * S * 4, d_srep.p, (size_t)S * 4 * sizeof(double), hipMemcpyDeviceToDevice));
           HIPCHK(hipMemcpy(nl.p + (size_t)s * S * 2, d_slong.p, (size_t)S * 2 * sizeof(double), hipMemcpyDeviceToDevice));
         }
-        d_srep.release(); d_slong.release(); d_srep = nr; d_slong = nl;
+        d_srep = std::move(nr); d_slong = std::move(nl);
       } else have_reps = false;
     }
     HIPCHK(hipMemcpy(d_static_xy.p + (size_t)scene * S * kHullV * 2, sx.data(), (size_t)S * kHullV * 2 * sizeof(double), hipMemcpyHostToDevice));
@@ -502,14 +521,7 @@ struct Engine {
     HIPCHK(hipGetLastError());
     return 0;
   }
-  void release() {
-    d_tables.release(); d_sched_n.release(); d_sched_seg.release(); d_sched_dt.release(); d_pb.release(); d_static_xy.release();
-    d_static_nv.release(); d_static_el.release(); d_hull_xy.release(); d_hull0_xy.release(); d_bend_xy.release(); d_line_nd.release(); d_row_scratch.release(); d_order.release(); d_order_key.release(); d_fe_order.release(); d_fe_order_key.release(); d_act.release(); d_fe_act.release(); d_safety_recs.release(); d_fe_us.release(); d_fe_box.release();
-    d_sampled.release(); d_srep.release(); d_slong.release(); d_present.release(); d_entangles.release(); d_fe_nodes.release(); d_fe_work.release(); d_fe_saved.release(); d_fe_arc.release(); d_fe_packed.release(); d_fe_big.release(); d_fe_big_beta.release(); d_fe_stf.release(); d_fe_stvox.release(); d_fe_xpool.release(); d_fe_big_count.release(); d_fe_big_check.release(); d_fe_big_check_count.release(); d_track_save.release(); d_track_flags.release(); d_audit_part.release();
-    d_presolved.release(); d_line_skip.release(); d_redo_list.release(); d_redo_count.release(); d_polish_z.release(); d_polish_flag.release(); d_polish_list.release(); d_polish_count.release(); d_flags.release(); d_conflict.release(); d_conflict_prev.release(); d_hull_nv.release(); d_hull0_nv.release(); d_bend_n.release(); d_line_cnt.release(); d_line_far.release(); d_lp_stats.release();
-    for (auto e : ev) hipEventDestroy(e);
-    ev.clear();
-  }
+  ~Engine() { for (auto e : ev) hipEventDestroy(e); }      // (the buffers free themselves)
 };
 
 bool have_device() { int n = 0; return hipGetDeviceCount(&n) == hipSuccess && n > 0; }
@@ -591,6 +603,7 @@ struct nep_backend {
   int override_n = -1; std::vector<int> ov_seg; std::vector<double> ov_nd;
   nep_solution h_sol{}; nep_stats stats{};
   hipStream_t stream = nullptr;
+  ~nep_backend() { if (stream) hipStreamDestroy(stream); }      // (work a failed call left on it still completes; the buffers free themselves after this, and hipFree synchronizes)
   // (re)lays the input arena out for `cap` hull lists, keeping what the setters have written
   int lay_out(int cap) {
     const int N = cfg.num_agents, np = cfg.num_pol;
@@ -605,9 +618,8 @@ struct nep_backend {
       std::memcpy(fresh.p + nl.nv, hin.p + L.nv, (size_t)in_cap * np * sizeof(int));
       std::memcpy(fresh.p + nl.cas, hin.p + L.cas, L.xy - L.cas);                    // the whole entangle block (same sizes: they depend on N only)
       std::memcpy(fresh.p + nl.xy, hin.p + L.xy, (size_t)in_cap * np * kHullV * 2 * sizeof(double));
-      hin.release();
     }
-    hin = fresh; L = nl; in_cap = cap;
+    hin = std::move(fresh); L = nl; in_cap = cap;
     return d_in.ensure(nl.cap_end);
   }
   template <class T> T* in(size_t off) { return (T*)(hin.p + off); }
@@ -625,7 +637,7 @@ nep_backend_t* nep_backend_create(const nep_backend_cfg* cfg) {
   if (cfg->num_pol < 1 || cfg->num_pol > NEP_MAX_POL) { g_err = "num_pol out of range"; return nullptr; }
   if (cfg->id < 1 || cfg->id > cfg->num_agents) { g_err = "id out of range"; return nullptr; }
   if (!have_device()) { g_err = "no HIP device: the back end has no CPU path"; return nullptr; }
-  nep_backend* h = new nep_backend();
+  std::unique_ptr<nep_backend> h(new nep_backend());      // (every return below but the last deletes it, and with it what it owns)
   h->cfg = *cfg; h->pb.assign(cfg->pb, cfg->pb + 2 * cfg->num_agents); h->cfg.pb = nullptr;
   Engine& E = h->eng;
   E.sp.num_agents = cfg->num_agents; E.sp.num_pol = cfg->num_pol; E.sp.n_static = 0; E.sp.n_hull = 0; E.sp.ent_enabled = 0;
@@ -634,21 +646,16 @@ nep_backend_t* nep_backend_create(const nep_backend_cfg* cfg) {
   E.lines_cap_user = -1;      // (one replan at a time: the buckets are sized for the reference's worst case, there is no flag to poll)
   E.set_clock();
   HIPCHK_NULL(hipStreamCreate(&h->stream));
-  if (h->lay_out(cfg->num_agents > 8 ? cfg->num_agents : 8)) { delete h; return nullptr; }
-  if (E.d_pb.ensure(h->pb.size())) { delete h; return nullptr; }
+  if (h->lay_out(cfg->num_agents > 8 ? cfg->num_agents : 8)) return nullptr;
+  if (E.d_pb.ensure(h->pb.size())) return nullptr;
   HIPCHK_NULL(hipMemcpy(E.d_pb.p, h->pb.data(), h->pb.size() * sizeof(double), hipMemcpyHostToDevice));
   int32_t off0[1] = {0};
-  if (E.upload_statics(0, off0, nullptr)) { delete h; return nullptr; }
-  if (E.build_tables()) { delete h; return nullptr; }
-  return h;
+  if (E.upload_statics(0, off0, nullptr)) return nullptr;
+  if (E.build_tables()) return nullptr;
+  return h.release();
 }
 
-void nep_backend_destroy(nep_backend_t* h) {
-  if (!h) return;
-  h->eng.release(); h->d_in.release(); h->d_out.release(); h->hin.release(); h->hout.release();
-  if (h->stream) hipStreamDestroy(h->stream);
-  delete h;
-}
+void nep_backend_destroy(nep_backend_t* h) { if (h) delete h; }
 
 int nep_backend_set_max_values(nep_backend_t* h, double x_min, double x_max, double y_min, double y_max, double z_min,
                                double z_max, double v_max, double a_max, double j_max) {
@@ -847,7 +854,6 @@ int nep_backend_generate_pwp_out(nep_backend_t* h, double t_start, double dc, ne
   if (states_out && states_cap > 0) {
     Engine& E = h->eng;
     DevBuf<nep_solution> d_sol_tmp; DevBuf<double> d_states_tmp;
-    struct Rel { DevBuf<nep_solution>& a; DevBuf<double>& b; ~Rel() { a.release(); b.release(); } } rel{d_sol_tmp, d_states_tmp};
     if (int e = d_sol_tmp.ensure(1)) return e;
     {  // another dc than the schedule's, or no solve yet: stage the trajectory to sample (the solution, else the guess)
       nep_solution s{}; s.K = K; std::memcpy(s.coeff, h->solved ? h->h_sol.coeff : h->guess.coeff, sizeof(s.coeff));
@@ -929,7 +935,6 @@ int nep_separator_batch_rule(int32_t rule, int32_t n_prob, const int32_t* a_off,
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpy(nd_out, dnd.p, (size_t)3 * n_prob * sizeof(double), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(solved_out, ds.p, (size_t)n_prob * sizeof(int), hipMemcpyDeviceToHost));
-  da.release(); db.release(); ds.release(); dax.release(); dbx.release(); dnd.release();
   return 0;
 }
 
@@ -952,7 +957,6 @@ int nep_gjk_batch(int32_t n_prob, const int32_t* a_off, const double* a_xy, cons
   launch_gjk_explicit(n_prob, da.p, dax.p, dbx.p, dh.p, nullptr);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpy(hit_out, dh.p, (size_t)n_prob * sizeof(int), hipMemcpyDeviceToHost));
-  da.release(); dh.release(); dax.release(); dbx.release();
   return 0;
 }
 
@@ -976,7 +980,6 @@ int nep_hulls_batch(int32_t n_traj, const nep_traj_rec* trajs, double t_start, i
   HIPCHK(hipMemcpy(hull0_nv, dn0.p, np * sizeof(int), hipMemcpyDeviceToHost));
   int flags = 0;
   HIPCHK(hipMemcpy(&flags, dfl.p, sizeof(int), hipMemcpyDeviceToHost));
-  dr.release(); dh.release(); dh0.release(); dn.release(); dn0.release(); dfl.release();
   if (flags & NEP_FLAG_HULL_OVERFLOW) return fail(NEP_E_CAP, "an interval overlaps more than NEP_HULL_MAX_CP/4 committed segments (or its hull has more than NEP_HULL_MAX_V vertices)");
   return 0;
 }
@@ -1001,12 +1004,29 @@ struct nep_batch {
     bool ent_ready = false; double cable = 0.0;
     DevBuf<nep_fe_ent_state> ent, ent_save; DevBuf<double> pub_xy, pub_prev_xy, ent_pos;
     DevBuf<int> pub_n, pub_prev_n, ent_flags, ent_ever, ent_walked, ent_flags_a;
-    void release_ent() { ent.release(); ent_save.release(); pub_xy.release(); pub_prev_xy.release(); ent_pos.release(); pub_n.release(); pub_prev_n.release();
-                         ent_flags.release(); ent_ever.release(); ent_walked.release(); ent_flags_a.release(); ent_ready = false; }
-    void release() { release_ent(); ring.release(); state.release(); goal.release(); t_now.release(); pwp.release(); head.release(); size.release(); k_end.release(); flown.release();
-                     done.release(); outcome.release(); sflags.release(); period.release(); phase.release(); round.release(); counters.release(); ready = false; }
   } fleet;
 };
+
+namespace {
+// the handle's scratch plus the caller's buffers of one round (each may be null: not every call has all of them)
+ProblemSet round_set(nep_batch* h, const nep_guess* d_guess = nullptr, nep_solution* d_solution = nullptr, double* d_states = nullptr,
+                     nep_traj_rec* d_commit = nullptr, const nep_traj_rec* d_prev_commit = nullptr, const void* d_ent = nullptr) {
+  ProblemSet ps{};
+  h->eng.fill(ps);
+  ps.guess = d_guess; ps.solution = d_solution; ps.states = d_states; ps.commit = d_commit; ps.prev_commit = d_prev_commit;
+  ps.case_id = (h->eng.sp.ent_enabled && d_ent) ? (const int*)d_ent : nullptr;
+  ps.lines_override = 0;
+  return ps;
+}
+// nep_batch_replan (phases 3) and its two halves (1: hulls + separating lines, 2: the QP on them) behind their own argument checks
+int replan_phases(nep_batch* h, int phases, const nep_traj_rec* d_committed, const nep_guess* d_guess, const void* d_ent,
+                  nep_solution* d_solution, double* d_states, nep_traj_rec* d_commit, void* stream) {
+  // d_committed == NULL (nep_batch_replan alone): the interval hulls of this round are already in the handle's scratch, made by
+  // nep_batch_frontend, whose records are this round's previous ones
+  ProblemSet ps = round_set(h, d_guess, d_solution, d_states, d_commit, d_committed ? d_committed : h->fe_committed, d_ent);
+  return h->eng.run(d_committed, h->cfg.num_agents, ps, (hipStream_t)stream, phases);
+}
+}  // namespace
 
 extern "C" {
 
@@ -1015,7 +1035,7 @@ nep_batch_t* nep_batch_create(const nep_batch_cfg* c) {
   if (c->num_pol < 1 || c->num_pol > NEP_MAX_POL || c->num_agents < 1 || c->n_local < 1 || c->first_local < 0 ||
       c->first_local + c->n_local > c->num_agents || c->n_scenes < 1 || c->max_states < 1) { g_err = "bad batch configuration"; return nullptr; }
   if (!have_device()) { g_err = "no HIP device: the back end has no CPU path"; return nullptr; }
-  nep_batch* h = new nep_batch();
+  std::unique_ptr<nep_batch> h(new nep_batch());
   h->cfg = *c; h->cfg.pb = nullptr; h->cfg.static_off = nullptr; h->cfg.static_xy = nullptr;
   Engine& E = h->eng; SceneParams& sp = E.sp;
   sp.num_agents = c->num_agents; sp.num_pol = c->num_pol; sp.n_hull = c->num_agents; sp.ent_enabled = c->enable_entangle;
@@ -1034,50 +1054,28 @@ nep_batch_t* nep_batch_create(const nep_batch_cfg* c) {
   if (ok) ok = !E.build_tables();
   if (ok) ok = !E.build_schedule(c->dc, c->max_states);
   if (ok) ok = !E.size_scratch();
-  if (!ok) { if (g_err.empty()) g_err = "batch setup failed"; E.release(); delete h; return nullptr; }
-  return h;
+  if (!ok) { if (g_err.empty()) g_err = "batch setup failed"; return nullptr; }
+  return h.release();
 }
 
-void nep_batch_destroy(nep_batch_t* h) { if (!h) return; h->fleet.release(); h->eng.release(); delete h; }
+void nep_batch_destroy(nep_batch_t* h) { if (h) delete h; }
 
 int64_t nep_batch_ent_bytes(const nep_batch_t* h) { return h ? (int64_t)h->slots * NEP_MAX_POL * h->cfg.num_agents * sizeof(int32_t) : 0; }
 
 int nep_batch_replan(nep_batch_t* h, const nep_traj_rec* d_committed, const nep_guess* d_guess, const void* d_ent,
                      nep_solution* d_solution, double* d_states, nep_traj_rec* d_commit, void* stream) {
   if (!h || !d_guess || !d_solution) return fail(NEP_E_ARG, "null argument");
-  Engine& E = h->eng;
-  ProblemSet ps{};
-  E.fill(ps);
-  ps.guess = d_guess; ps.solution = d_solution; ps.states = d_states; ps.commit = d_commit;
-  ps.prev_commit = d_committed ? d_committed : h->fe_committed;   // (hulls reused from nep_batch_frontend: its records are this round's previous ones)
-  ps.case_id = (E.sp.ent_enabled && d_ent) ? (const int*)d_ent : nullptr;
-  ps.lines_override = 0;
-  // d_committed == NULL: the interval hulls of this round are already in the handle's scratch (nep_batch_frontend)
-  return E.run(d_committed, h->cfg.num_agents, ps, (hipStream_t)stream);
+  return replan_phases(h, 3, d_committed, d_guess, d_ent, d_solution, d_states, d_commit, stream);
 }
-
 // The two halves of nep_batch_replan as calls of their own (include/neptune_backend.h): hulls + separating lines, then the QP on them
 int nep_batch_replan_lines(nep_batch_t* h, const nep_traj_rec* d_committed, const nep_guess* d_guess, const void* d_ent, void* stream) {
   if (!h || !d_guess || !d_committed) return fail(NEP_E_ARG, "null argument");
-  Engine& E = h->eng;
-  ProblemSet ps{};
-  E.fill(ps);
-  ps.guess = d_guess;
-  ps.case_id = (E.sp.ent_enabled && d_ent) ? (const int*)d_ent : nullptr;
-  ps.lines_override = 0;
-  return E.run(d_committed, h->cfg.num_agents, ps, (hipStream_t)stream, 1);
+  return replan_phases(h, 1, d_committed, d_guess, d_ent, nullptr, nullptr, nullptr, stream);
 }
 int nep_batch_replan_solve(nep_batch_t* h, const nep_traj_rec* d_committed, const nep_guess* d_guess, const void* d_ent,
                            nep_solution* d_solution, double* d_states, nep_traj_rec* d_commit, void* stream) {
   if (!h || !d_guess || !d_solution || !d_committed) return fail(NEP_E_ARG, "null argument");
-  Engine& E = h->eng;
-  ProblemSet ps{};
-  E.fill(ps);
-  ps.guess = d_guess; ps.solution = d_solution; ps.states = d_states; ps.commit = d_commit;
-  ps.prev_commit = d_committed;
-  ps.case_id = (E.sp.ent_enabled && d_ent) ? (const int*)d_ent : nullptr;
-  ps.lines_override = 0;
-  return E.run(d_committed, h->cfg.num_agents, ps, (hipStream_t)stream, 2);
+  return replan_phases(h, 2, d_committed, d_guess, d_ent, d_solution, d_states, d_commit, stream);
 }
 
 // ---- sharded hulls: a rank computes the interval hulls of its own agents' committed trajectories
@@ -1104,15 +1102,36 @@ HullBlock hull_block_layout(int n_scenes, int per, int np, int ent_ns = 0) {
   b.bytes = o;
   return b;
 }
-HullBlock block_of(const nep_batch* h);
+HullBlock block_of(const nep_batch* h) { return hull_block_layout(h->cfg.n_scenes, h->cfg.n_local, h->cfg.num_pol, h->cfg.enable_entangle ? h->ent_ns : 0); }
 void point_at_block(ProblemSet& ps, const HullBlock& b, void* base) {
   char* p = (char*)base;
   ps.hull_xy = (double*)(p + b.xy); ps.hull_nv = (int*)(p + b.nv); ps.hull0_xy = (double*)(p + b.xy0); ps.hull0_nv = (int*)(p + b.nv0);
   ps.bend_xy = (double*)(p + b.bend); ps.bend_n = (int*)(p + b.bend_n);
 }
-}  // namespace
+// ps reads its hulls from n_blocks all-gathered blocks of n_local agents each
+int use_blocks(ProblemSet& ps, const nep_batch* h, const void* d_blocks, int n_blocks) {
+  if (n_blocks < 1 || n_blocks * h->cfg.n_local != h->cfg.num_agents) return fail(NEP_E_ARG, "n_blocks * n_local must equal num_agents");
+  const HullBlock b = block_of(h);
+  point_at_block(ps, b, const_cast<void*>(d_blocks));
+  ps.hull_pb = h->cfg.n_local; ps.hull_bstride = (long)b.bytes;
+  ps.hull_pb_magic = (h->cfg.n_local > 0 && h->cfg.num_agents < 65536) ? (1ull << 32) / (unsigned long long)h->cfg.n_local + 1ull : 0ull;
+  return 0;
+}
 
-namespace { HullBlock block_of(const nep_batch* h) { return hull_block_layout(h->cfg.n_scenes, h->cfg.n_local, h->cfg.num_pol, h->cfg.enable_entangle ? h->ent_ns : 0); } }
+bool fe_cfg_ok(const nep_fe_cfg* cfg) {
+  return cfg->num_samples >= 2 && cfg->num_samples <= NEP_FE_MAX_SAMPLES && cfg->beam_width >= 1 && cfg->beam_width <= NEP_FE_MAX_BEAM &&
+         cfg->voxel_size > 0.0 && cfg->j_max > 0.0;
+}
+// the searches of every slot against the hulls ps points at (ea: the entangle-aware front end's arguments, or null)
+int run_frontend(nep_batch* h, const ProblemSet& ps, const nep_fe_cfg& cfg, const nep_fe_start* d_start, nep_guess* d_guess, nep_fe_result* d_result,
+                 const FeEntArgs* ea, void* stream) {
+  Engine& E = h->eng;
+  launch_frontend(h->slots, E.sp, ps, cfg, d_start, d_guess, d_result, ea, (hipStream_t)stream, E.lpt ? E.d_fe_order.p : nullptr, E.fe_history, E.d_fe_act.p);
+  E.fe_history = true;
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+}  // namespace
 
 int64_t nep_batch_hull_block_bytes(const nep_batch_t* h) {
   return h ? (int64_t)block_of(h).bytes : 0;
@@ -1122,10 +1141,8 @@ int nep_batch_hulls(nep_batch_t* h, const nep_traj_rec* d_committed_local, const
   if (!h || !d_committed_local || !d_guess || !d_block) return fail(NEP_E_ARG, "null argument");
   Engine& E = h->eng;
   const HullBlock b = block_of(h);
-  ProblemSet ps{};
-  E.fill(ps);
+  ProblemSet ps = round_set(h, d_guess);
   point_at_block(ps, b, d_block);
-  ps.guess = d_guess;
   launch_hulls(d_committed_local, h->cfg.n_scenes, h->cfg.n_local, d_guess, E.sp, ps, (hipStream_t)stream);
   if (h->cfg.enable_entangle)      // what the entangle check reads of my agents' trajectories travels in the same block
     launch_ent_sample(d_committed_local, h->cfg.n_scenes, h->cfg.n_local, &d_guess->t_start, (long)sizeof(nep_guess) * h->cfg.n_local, h->cfg.num_pol, h->ent_ns,
@@ -1143,56 +1160,31 @@ int nep_batch_set_ent_samples(nep_batch_t* h, int32_t ns) {
 int nep_batch_replan_hulls(nep_batch_t* h, const void* d_blocks, int32_t n_blocks, const nep_guess* d_guess, const void* d_ent,
                            nep_solution* d_solution, double* d_states, nep_traj_rec* d_commit, void* stream) {
   if (!h || !d_blocks || !d_guess || !d_solution) return fail(NEP_E_ARG, "null argument");
-  if (n_blocks < 1 || n_blocks * h->cfg.n_local != h->cfg.num_agents) return fail(NEP_E_ARG, "n_blocks * n_local must equal num_agents");
-  Engine& E = h->eng;
-  const HullBlock b = block_of(h);
-  ProblemSet ps{};
-  E.fill(ps);
-  point_at_block(ps, b, const_cast<void*>(d_blocks));
-  ps.hull_pb = h->cfg.n_local; ps.hull_bstride = (long)b.bytes;
-  ps.hull_pb_magic = (h->cfg.n_local > 0 && h->cfg.num_agents < 65536) ? (1ull << 32) / (unsigned long long)h->cfg.n_local + 1ull : 0ull;
-  ps.guess = d_guess; ps.solution = d_solution; ps.states = d_states; ps.commit = d_commit;
-  ps.case_id = (E.sp.ent_enabled && d_ent) ? (const int*)d_ent : nullptr;
-  ps.lines_override = 0;
-  return E.run(nullptr, 0, ps, (hipStream_t)stream);
+  ProblemSet ps = round_set(h, d_guess, d_solution, d_states, d_commit, nullptr, d_ent);
+  if (int e = use_blocks(ps, h, d_blocks, n_blocks)) return e;
+  return h->eng.run(nullptr, 0, ps, (hipStream_t)stream);
 }
 
 // hulls -> front-end beam search; the guesses land where nep_batch_replan reads them
 int nep_batch_frontend(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_traj_rec* d_committed, const nep_fe_start* d_start,
                        nep_guess* d_guess, nep_fe_result* d_result, void* stream) {
   if (!h || !cfg || !d_committed || !d_start || !d_guess) return fail(NEP_E_ARG, "null argument");
-  if (cfg->num_samples < 2 || cfg->num_samples > NEP_FE_MAX_SAMPLES || cfg->beam_width < 1 || cfg->beam_width > NEP_FE_MAX_BEAM ||
-      !(cfg->voxel_size > 0.0) || !(cfg->j_max > 0.0)) return fail(NEP_E_ARG, "bad front-end configuration");
-  Engine& E = h->eng;
-  ProblemSet ps{};
-  E.fill(ps);
+  if (!fe_cfg_ok(cfg)) return fail(NEP_E_ARG, "bad front-end configuration");
+  const ProblemSet ps = round_set(h);
   h->fe_committed = d_committed;
-  launch_hulls_ts(d_committed, h->cfg.n_scenes, h->cfg.num_agents, &d_start->t_start, (long)sizeof(nep_fe_start), E.sp, ps, (hipStream_t)stream);
-  launch_frontend(h->slots, E.sp, ps, *cfg, d_start, d_guess, d_result, nullptr, (hipStream_t)stream, E.lpt ? E.d_fe_order.p : nullptr, E.fe_history, E.d_fe_act.p);
-  E.fe_history = true;
-  HIPCHK(hipGetLastError());
-  return 0;
+  launch_hulls_ts(d_committed, h->cfg.n_scenes, h->cfg.num_agents, &d_start->t_start, (long)sizeof(nep_fe_start), h->eng.sp, ps, (hipStream_t)stream);
+  return run_frontend(h, ps, *cfg, d_start, d_guess, d_result, nullptr, stream);
 }
 
 // the same against all-gathered hull blocks (multi-GPU rounds: nep_batch_hulls -> all-gather -> this -> nep_batch_replan_hulls)
 int nep_batch_frontend_hulls(nep_batch_t* h, const nep_fe_cfg* cfg, const void* d_blocks, int32_t n_blocks, const nep_fe_start* d_start,
                              nep_guess* d_guess, nep_fe_result* d_result, void* stream) {
   if (!h || !cfg || !d_blocks || !d_start || !d_guess) return fail(NEP_E_ARG, "null argument");
-  if (n_blocks < 1 || n_blocks * h->cfg.n_local != h->cfg.num_agents) return fail(NEP_E_ARG, "n_blocks * n_local must equal num_agents");
-  if (cfg->num_samples < 2 || cfg->num_samples > NEP_FE_MAX_SAMPLES || cfg->beam_width < 1 || cfg->beam_width > NEP_FE_MAX_BEAM ||
-      !(cfg->voxel_size > 0.0) || !(cfg->j_max > 0.0)) return fail(NEP_E_ARG, "bad front-end configuration");
-  Engine& E = h->eng;
-  const HullBlock b = block_of(h);
-  ProblemSet ps{};
-  E.fill(ps);
-  point_at_block(ps, b, const_cast<void*>(d_blocks));
-  ps.hull_pb = h->cfg.n_local; ps.hull_bstride = (long)b.bytes;
-  ps.hull_pb_magic = (h->cfg.n_local > 0 && h->cfg.num_agents < 65536) ? (1ull << 32) / (unsigned long long)h->cfg.n_local + 1ull : 0ull;
+  ProblemSet ps = round_set(h);
+  if (int e = use_blocks(ps, h, d_blocks, n_blocks)) return e;
+  if (!fe_cfg_ok(cfg)) return fail(NEP_E_ARG, "bad front-end configuration");
   h->fe_committed = nullptr;
-  launch_frontend(h->slots, E.sp, ps, *cfg, d_start, d_guess, d_result, nullptr, (hipStream_t)stream, E.lpt ? E.d_fe_order.p : nullptr, E.fe_history, E.d_fe_act.p);
-  E.fe_history = true;
-  HIPCHK(hipGetLastError());
-  return 0;
+  return run_frontend(h, ps, *cfg, d_start, d_guess, d_result, nullptr, stream);
 }
 
 int nep_batch_set_active(nep_batch_t* h, const int32_t* d_active) {
@@ -1207,43 +1199,61 @@ int nep_batch_set_active(nep_batch_t* h, const int32_t* d_active) {
   return 0;
 }
 
+// ---- the safety pass, without and with the entangle re-check ----
+namespace {
+// what both passes start with: the conflict matrices, the round's ProblemSet and, with an active set, the records judged — an inactive
+// agent's record this round is its previous one (d_new of it is not read)
+int safety_begin(nep_batch* h, const nep_traj_rec* d_prev, const nep_traj_rec*& d_new, const nep_guess* d_guess, ProblemSet& ps, hipStream_t st) {
+  Engine& E = h->eng;
+  const int N = h->cfg.num_agents;
+  if (int e = E.d_conflict.ensure((size_t)h->cfg.n_scenes * N * N)) return e;
+  if (E.safety_check_prev) { if (int e = E.d_conflict_prev.ensure((size_t)h->cfg.n_scenes * N * N)) return e; }
+  ps = round_set(h, d_guess);
+  if (E.active) {
+    launch_select_records(h->cfg.n_scenes, N, E.active, d_prev, d_new, E.d_safety_recs.p, st);
+    d_new = E.d_safety_recs.p;
+  }
+  return 0;
+}
+// ... and end with (d_entangles: the re-check's verdicts, or null)
+int safety_end(nep_batch* h, const ProblemSet& ps, const nep_traj_rec* d_prev, const nep_traj_rec* d_new, const int* d_entangles, nep_traj_rec* d_final,
+               int32_t* d_accept, hipStream_t st) {
+  Engine& E = h->eng;
+  launch_safety(d_prev, d_new, h->cfg.n_scenes, h->cfg.num_agents, E.sp, ps, E.d_conflict.p, E.safety_check_prev ? E.d_conflict_prev.p : nullptr, d_entangles, d_final, d_accept, st, E.active);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+}  // namespace
+
 int nep_batch_safety_commit(nep_batch_t* h, const nep_traj_rec* d_prev, const nep_traj_rec* d_new, const nep_guess* d_guess,
                             nep_traj_rec* d_final, int32_t* d_accept, void* stream) {
   if (!h || !d_prev || !d_new || !d_guess || !d_final) return fail(NEP_E_ARG, "null argument");
-  Engine& E = h->eng;
-  const int N = h->cfg.num_agents;
-  if (E.sp.n_hull != N) return fail(NEP_E_STATE, "safety check needs the batched (all-agent) hull layout");
-  if (int e = E.d_conflict.ensure((size_t)h->cfg.n_scenes * N * N)) return e;
+  if (h->eng.sp.n_hull != h->cfg.num_agents) return fail(NEP_E_STATE, "safety check needs the batched (all-agent) hull layout");
   ProblemSet ps{};
-  E.fill(ps);
-  ps.guess = d_guess;
-  if (E.safety_check_prev) { if (int e = E.d_conflict_prev.ensure((size_t)h->cfg.n_scenes * N * N)) return e; }
-  if (E.active) {      // an active set: an inactive agent's record this round is its previous one (d_new of it is not read)
-    launch_select_records(h->cfg.n_scenes, N, E.active, d_prev, d_new, E.d_safety_recs.p, (hipStream_t)stream);
-    d_new = E.d_safety_recs.p;
-  }
-  launch_safety(d_prev, d_new, h->cfg.n_scenes, N, E.sp, ps, E.d_conflict.p, E.safety_check_prev ? E.d_conflict_prev.p : nullptr, nullptr, d_final, d_accept, (hipStream_t)stream, E.active);
-  HIPCHK(hipGetLastError());
-  return 0;
+  if (int e = safety_begin(h, d_prev, d_new, d_guess, ps, (hipStream_t)stream)) return e;
+  return safety_end(h, ps, d_prev, d_new, nullptr, d_final, d_accept, (hipStream_t)stream);
 }
 
 // ---- entangle check on: front end with per-node entangle states, safety pass with entangleCheckGivenPwp ----
 namespace {
-bool fe_cfg_ok(const nep_fe_cfg* cfg) {
-  return cfg->num_samples >= 2 && cfg->num_samples <= NEP_FE_MAX_SAMPLES && cfg->beam_width >= 1 && cfg->beam_width <= NEP_FE_MAX_BEAM &&
-         cfg->voxel_size > 0.0 && cfg->j_max > 0.0;
+// what every entangle-aware call asks of the static representatives (nep_batch_set_static_reps); a handle without static obstacles
+// gets placeholders for the kernels' arguments
+int ent_ready(nep_batch* h, const char* no_reps = "entangle check with static obstacles needs nep_batch_set_static_reps first") {
+  Engine& E = h->eng;
+  if (E.sp.n_static > 0 && !E.have_reps) return fail(NEP_E_STATE, no_reps);
+  if (E.sp.n_static > 0 && E.d_srep.n < (size_t)(E.sp.static_stride ? h->cfg.n_scenes : 1) * E.sp.n_static * 4) return fail(NEP_E_STATE, "static representatives do not cover every scene's obstacle set: call nep_batch_set_static_reps after nep_batch_set_scene_statics");
+  if (!E.d_srep.p) { if (int e = E.d_srep.ensure(4)) return e; if (int e = E.d_slong.ensure(2)) return e; }
+  return 0;
 }
 int ent_prepare(nep_batch* h, int ns, int beam_width, const nep_traj_rec* d_recs, const double* ts0, long ts_scene_stride, FeEntArgs& ea, hipStream_t st) {
   Engine& E = h->eng;
   const int N = h->cfg.num_agents, S = h->cfg.n_scenes, np = h->cfg.num_pol;
   if (ns < 1 || ns > 8) return fail(NEP_E_ARG, "ent_samples out of range");
-  if (E.sp.n_static > 0 && !E.have_reps) return fail(NEP_E_STATE, "entangle check with static obstacles needs nep_batch_set_static_reps first");
-  if (E.sp.n_static > 0 && E.d_srep.n < (size_t)(E.sp.static_stride ? S : 1) * E.sp.n_static * 4) return fail(NEP_E_STATE, "static representatives do not cover every scene's obstacle set: call nep_batch_set_static_reps after nep_batch_set_scene_statics");
+  if (int e = ent_ready(h)) return e;
   if (int e = E.d_sampled.ensure((size_t)S * N * np * (ns + 1) * 2)) return e;
   if (int e = E.d_present.ensure((size_t)S * N)) return e;
   if (int e = E.d_fe_work.ensure((size_t)std::max(h->slots * 256, S * N))) return e;
   if (beam_width > 0) { if (int e = E.d_fe_nodes.ensure((size_t)h->slots * (np + 1) * beam_width)) return e; }
-  if (!E.d_srep.p) { if (int e = E.d_srep.ensure(4)) return e; if (int e2 = E.d_slong.ensure(2)) return e2; }
   {   // the re-check's big records (three times the search's bound: entangleCheckGivenPwp); a sixteenth of the search's pool, at least 256
     const long n_rec = std::max(256L, (E.fe_big_records > 0 ? E.fe_big_records : std::max(4096L, 4L * h->slots)) / 16);
     const size_t rec = (size_t)ent_big_rec_bytes(N, E.sp.n_static, 3);
@@ -1271,7 +1281,7 @@ int nep_batch_set_static_reps(nep_batch_t* h, int32_t scene, const double* rep, 
     if (int e = nr.ensure((size_t)sets * S * 4)) return e;
     if (int e = nl.ensure((size_t)sets * S * 2)) return e;
     HIPCHK(hipMemset(nr.p, 0, (size_t)sets * S * 4 * sizeof(double))); HIPCHK(hipMemset(nl.p, 0, (size_t)sets * S * 2 * sizeof(double)));
-    E.d_srep.release(); E.d_slong.release(); E.d_srep = nr; E.d_slong = nl;
+    E.d_srep = std::move(nr); E.d_slong = std::move(nl);
   }
   for (int s = 0; s < sets; s++) {
     if (scene >= 0 && sets > 1 && s != scene) continue;
@@ -1333,18 +1343,14 @@ int nep_batch_frontend_ent(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_traj
   if (!cfg->enable_entangle || !h->cfg.enable_entangle) return fail(NEP_E_STATE, "nep_batch_frontend_ent needs enable_entangle in the front-end configuration and in the handle");
   if (h->cfg.n_local != h->cfg.num_agents) return fail(NEP_E_STATE, "the entangle-aware front end runs on an unsharded handle (n_local == num_agents)");
   Engine& E = h->eng;
-  ProblemSet ps{};
-  E.fill(ps);
+  const ProblemSet ps = round_set(h);
   h->fe_committed = d_committed;
   launch_hulls_ts(d_committed, h->cfg.n_scenes, h->cfg.num_agents, &d_start->t_start, (long)sizeof(nep_fe_start), E.sp, ps, (hipStream_t)stream);
   FeEntArgs ea{};
   if (int e = ent_prepare(h, cfg->ent_samples, cfg->beam_width, d_committed, &d_start->t_start, (long)sizeof(nep_fe_start) * E.sp.n_local, ea, (hipStream_t)stream)) return e;
   ea.init = d_ent_init; ea.case_out = d_case_out;
   if (int e = fe_ent_scratch(h, *cfg, ea)) return e;
-  launch_frontend(h->slots, E.sp, ps, *cfg, d_start, d_guess, d_result, &ea, (hipStream_t)stream, E.lpt ? E.d_fe_order.p : nullptr, E.fe_history, E.d_fe_act.p);
-  E.fe_history = true;
-  HIPCHK(hipGetLastError());
-  return 0;
+  return run_frontend(h, ps, *cfg, d_start, d_guess, d_result, &ea, stream);
 }
 
 // the same against all-gathered hull blocks (which carry the samples and the presence flags of every agent's trajectory when the
@@ -1352,31 +1358,23 @@ int nep_batch_frontend_ent(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_traj
 int nep_batch_frontend_ent_hulls(nep_batch_t* h, const nep_fe_cfg* cfg, const void* d_blocks, int32_t n_blocks, const nep_fe_start* d_start,
                                  const nep_fe_ent_state* d_ent_init, nep_guess* d_guess, nep_fe_result* d_result, int32_t* d_case_out, void* stream) {
   if (!h || !cfg || !d_blocks || !d_start || !d_guess) return fail(NEP_E_ARG, "null argument");
-  if (n_blocks < 1 || n_blocks * h->cfg.n_local != h->cfg.num_agents) return fail(NEP_E_ARG, "n_blocks * n_local must equal num_agents");
+  ProblemSet ps = round_set(h);
+  if (int e = use_blocks(ps, h, d_blocks, n_blocks)) return e;
   if (!fe_cfg_ok(cfg)) return fail(NEP_E_ARG, "bad front-end configuration");
   if (!cfg->enable_entangle || !h->cfg.enable_entangle) return fail(NEP_E_STATE, "nep_batch_frontend_ent_hulls needs enable_entangle in the front-end configuration and in the handle");
   if (cfg->ent_samples != h->ent_ns) return fail(NEP_E_ARG, "ent_samples differs from what the hull blocks were made with (nep_batch_set_ent_samples)");
+  if (int e = ent_ready(h)) return e;
   Engine& E = h->eng;
-  if (E.sp.n_static > 0 && !E.have_reps) return fail(NEP_E_STATE, "entangle check with static obstacles needs nep_batch_set_static_reps first");
   const HullBlock b = block_of(h);
-  ProblemSet ps{};
-  E.fill(ps);
-  point_at_block(ps, b, const_cast<void*>(d_blocks));
-  ps.hull_pb = h->cfg.n_local; ps.hull_bstride = (long)b.bytes;
-  ps.hull_pb_magic = (h->cfg.n_local > 0 && h->cfg.num_agents < 65536) ? (1ull << 32) / (unsigned long long)h->cfg.n_local + 1ull : 0ull;
   h->fe_committed = nullptr;
   if (int e = E.d_fe_work.ensure((size_t)std::max(h->slots * 256, h->cfg.n_scenes * h->cfg.num_agents))) return e;
   if (int e = E.d_fe_nodes.ensure((size_t)h->slots * (h->cfg.num_pol + 1) * cfg->beam_width)) return e;
-  if (!E.d_srep.p) { if (int e = E.d_srep.ensure(4)) return e; if (int e2 = E.d_slong.ensure(2)) return e2; }
   FeEntArgs ea{};
   ea.sampled = (const double*)((const char*)d_blocks + b.samp); ea.present = (const int*)((const char*)d_blocks + b.present);
   ea.srep = E.d_srep.p; ea.slong = E.d_slong.p; ea.nodes = E.d_fe_nodes.p; ea.work = E.d_fe_work.p; ea.ns = h->ent_ns;
   ea.init = d_ent_init; ea.case_out = d_case_out;
   if (int e = fe_ent_scratch(h, *cfg, ea)) return e;
-  launch_frontend(h->slots, E.sp, ps, *cfg, d_start, d_guess, d_result, &ea, (hipStream_t)stream, E.lpt ? E.d_fe_order.p : nullptr, E.fe_history, E.d_fe_act.p);
-  E.fe_history = true;
-  HIPCHK(hipGetLastError());
-  return 0;
+  return run_frontend(h, ps, *cfg, d_start, d_guess, d_result, &ea, stream);
 }
 
 int nep_batch_safety_commit_ent(nep_batch_t* h, const nep_traj_rec* d_prev, const nep_traj_rec* d_new, const nep_guess* d_guess,
@@ -1387,16 +1385,9 @@ int nep_batch_safety_commit_ent(nep_batch_t* h, const nep_traj_rec* d_prev, cons
   const int N = h->cfg.num_agents;
   if (E.sp.n_hull != N) return fail(NEP_E_STATE, "the entangle re-check needs the batched (all-agent) hull layout");
   if (!h->cfg.enable_entangle) return fail(NEP_E_STATE, "handle created without enable_entangle");
-  if (int e = E.d_conflict.ensure((size_t)h->cfg.n_scenes * N * N)) return e;
   if (int e = E.d_entangles.ensure((size_t)h->cfg.n_scenes * N)) return e;
   ProblemSet ps{};
-  E.fill(ps);
-  ps.guess = d_guess;
-  if (E.safety_check_prev) { if (int e = E.d_conflict_prev.ensure((size_t)h->cfg.n_scenes * N * N)) return e; }
-  if (E.active) {      // an active set: an inactive agent's record this round is its previous one (d_new of it is not read)
-    launch_select_records(h->cfg.n_scenes, N, E.active, d_prev, d_new, E.d_safety_recs.p, (hipStream_t)stream);
-    d_new = E.d_safety_recs.p;
-  }
+  if (int e = safety_begin(h, d_prev, d_new, d_guess, ps, (hipStream_t)stream)) return e;
   // everybody's NEW trajectory counts as received while optimising: their samples and bend points feed the re-check
   FeEntArgs ea{};
   if (int e = ent_prepare(h, ent_samples, 0, d_new, &d_guess->t_start, (long)sizeof(nep_guess) * E.sp.n_local, ea, (hipStream_t)stream)) return e;
@@ -1406,9 +1397,7 @@ int nep_batch_safety_commit_ent(nep_batch_t* h, const nep_traj_rec* d_prev, cons
   ea.packed = E.d_fe_packed.p;
   launch_hulls(d_new, h->cfg.n_scenes, N, d_guess, E.sp, ps, (hipStream_t)stream);     // (with the bend points: ent_enabled)
   launch_ent_check(E.sp, ps, ea, d_new, h->cfg.n_scenes, cable_length, E.d_entangles.p, (hipStream_t)stream);
-  launch_safety(d_prev, d_new, h->cfg.n_scenes, N, E.sp, ps, E.d_conflict.p, E.safety_check_prev ? E.d_conflict_prev.p : nullptr, E.d_entangles.p, d_final, d_accept, (hipStream_t)stream, E.active);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return safety_end(h, ps, d_prev, d_new, E.d_entangles.p, d_final, d_accept, (hipStream_t)stream);
 }
 
 int nep_batch_track_ent(nep_batch_t* h, const nep_traj_rec* d_prev, nep_traj_rec* d_records, const nep_guess* d_guess, int32_t n_intervals,
@@ -1420,15 +1409,12 @@ int nep_batch_track_ent(nep_batch_t* h, const nep_traj_rec* d_prev, nep_traj_rec
   if (h->cfg.n_local != h->cfg.num_agents) return fail(NEP_E_STATE, "tether tracking runs on an unsharded handle (n_local == num_agents)");
   Engine& E = h->eng;
   const int N = h->cfg.num_agents, S = h->cfg.n_scenes, np = h->cfg.num_pol;
-  if (E.sp.n_static > 0 && !E.have_reps) return fail(NEP_E_STATE, "tether tracking with static obstacles needs nep_batch_set_static_reps first");
-  if (E.sp.n_static > 0 && E.d_srep.n < (size_t)(E.sp.static_stride ? S : 1) * E.sp.n_static * 4) return fail(NEP_E_STATE, "static representatives do not cover every scene's obstacle set: call nep_batch_set_static_reps after nep_batch_set_scene_statics");
-  ProblemSet ps{};
-  E.fill(ps);
+  if (int e = ent_ready(h, "tether tracking with static obstacles needs nep_batch_set_static_reps first")) return e;
+  const ProblemSet ps = round_set(h);
   if (int e = E.d_sampled.ensure((size_t)S * N * np * (ent_samples + 1) * 2)) return e;
   if (int e = E.d_present.ensure((size_t)S * N)) return e;
   if (int e = E.d_track_save.ensure((size_t)S * N)) return e;
   if (int e = E.d_track_flags.ensure((size_t)S * N)) return e;      // (whether or not this call passes d_flags: a later captured call may not)
-  if (!E.d_srep.p) { if (int e = E.d_srep.ensure(4)) return e; if (int e2 = E.d_slong.ensure(2)) return e2; }
   launch_ent_sample(d_records, S, N, &d_guess->t_start, (long)sizeof(nep_guess) * h->cfg.n_local, np, ent_samples, E.sp.T_span, E.d_sampled.p, E.d_present.p,
                     (hipStream_t)stream, nullptr);
   TrackArgs ta{};
@@ -1451,8 +1437,7 @@ int nep_batch_audit(nep_batch_t* h, const nep_traj_rec* d_records, const nep_fe_
   if (audit_lds_bytes(N, E.sp.n_static, vs) > 64 * 1024) return fail(NEP_E_CAP, "the flight audit's agents and static polygons do not fit into 64 KB of LDS");
   if (int e = E.d_audit_part.ensure((size_t)S * nep_audit_impl::kAuditMaxChunks * N)) return e;      // (before the n_ticks == 0 return: the first call allocates)
   if (n_ticks == 0) return 0;
-  ProblemSet ps{};
-  E.fill(ps);
+  const ProblemSet ps = round_set(h);
   AuditArgs aa{};
   aa.N = N; aa.S = E.sp.n_static; aa.n_scenes = S; aa.static_stride = E.sp.static_stride; aa.vstride = vs; aa.n_ticks = n_ticks;
   aa.chunk_len = nep_audit_impl::audit_chunk_len(n_ticks); aa.n_chunks = (n_ticks + aa.chunk_len - 1) / aa.chunk_len;
@@ -1548,9 +1533,7 @@ int nep_batch_fleet_init_ent(nep_batch_t* h, double cable_length, const nep_fe_e
   if (int e = fleet_guard(h, true)) return e;
   if (!h->cfg.enable_entangle) return fail(NEP_E_STATE, "handle created without enable_entangle");
   Engine& E = h->eng;
-  const int S = h->cfg.n_scenes;
-  if (E.sp.n_static > 0 && !E.have_reps) return fail(NEP_E_STATE, "the fleet's tethers with static obstacles need nep_batch_set_static_reps first");
-  if (E.sp.n_static > 0 && E.d_srep.n < (size_t)(E.sp.static_stride ? S : 1) * E.sp.n_static * 4) return fail(NEP_E_STATE, "static representatives do not cover every scene's obstacle set: call nep_batch_set_static_reps after nep_batch_set_scene_statics");
+  if (int e = ent_ready(h, "the fleet's tethers with static obstacles need nep_batch_set_static_reps first")) return e;
   if (!fleet_ent_fits(h->cfg.num_agents, E.sp.n_static)) return fail(NEP_E_CAP, "the fleet's tether kernels take up to 4096 agents and 2048 static obstacles per scene");
   if (!(cable_length > 0.0)) return fail(NEP_E_ARG, "cable_length must be positive");
   nep_batch::Fleet& F = h->fleet;
@@ -1558,7 +1541,6 @@ int nep_batch_fleet_init_ent(nep_batch_t* h, double cable_length, const nep_fe_e
   hipStream_t st = (hipStream_t)stream;
   HIPCHK(hipStreamSynchronize(st));
   F.ent_ready = false;
-  if (!E.d_srep.p) { if (int e = E.d_srep.ensure(4)) return e; if (int e2 = E.d_slong.ensure(2)) return e2; }
   if (int e = F.ent.ensure(slots)) return e;
   if (int e = F.ent_save.ensure(slots)) return e;
   if (int e = F.pub_xy.ensure(slots * NEP_MAX_BEND * 2)) return e;
@@ -1843,34 +1825,40 @@ int nep_batch_set_max_runtime(nep_batch_t* h, double seconds) {
   return 0;
 }
 
-int nep_batch_set_line_cull(nep_batch_t* h, double radius) {
-  if (!h || !(radius >= 0.0)) return fail(NEP_E_ARG, "bad arguments");
-  h->eng.sp.cull_radius = radius; h->eng.cull_user_set = true;
-  h->eng.choose_placement();      // (a culled problem's near lines fit the register kernel whatever the scene size)
-  HIPCHK(hipDeviceSynchronize());
-  return h->eng.size_row_scratch();      // (the row scratch follows the mode: a pool with the redo pass, one area per slot without — never inside a capture)
-}
-double nep_batch_get_line_cull(nep_batch_t* h) { return h ? h->eng.sp.cull_radius : -1.0; }
-// (the per-agent handle sizes its scratch and picks its placement at every optimize(): nothing to re-size here)
-int nep_backend_set_line_cull(nep_backend_t* h, double radius) {
-  if (!h || !(radius >= 0.0)) return fail(NEP_E_ARG, "bad arguments");
-  h->eng.sp.cull_radius = radius; h->eng.cull_user_set = true;
+// Setters both handle kinds have (E: the handle's engine, or null for a null handle).  The batched handle's row scratch follows the
+// mode — a pool with the presolve's redo pass, one area per slot without — so its setters re-size it (never inside a capture); the
+// per-agent handle sizes its scratch and picks its placement at every optimize().
+namespace {
+int set_line_cull(Engine* E, double radius) {
+  if (!E || !(radius >= 0.0)) return fail(NEP_E_ARG, "bad arguments");
+  E->sp.cull_radius = radius; E->cull_user_set = true;
   return 0;
 }
+int set_separator_rule(Engine* E, int32_t rule) {
+  if (!E || (rule != 0 && rule != 1)) return fail(NEP_E_ARG, "separator rule: 0 largest gap, 1 GLPK-class simplex");
+  E->sp.sep_rule = rule;
+  return 0;
+}
+int resize_row_scratch(Engine& E) { HIPCHK(hipDeviceSynchronize()); return E.size_row_scratch(); }
+}  // namespace
+int nep_batch_set_line_cull(nep_batch_t* h, double radius) {
+  if (int e = set_line_cull(h ? &h->eng : nullptr, radius)) return e;
+  h->eng.choose_placement();      // (a culled problem's near lines fit the register kernel whatever the scene size)
+  return resize_row_scratch(h->eng);
+}
+double nep_batch_get_line_cull(nep_batch_t* h) { return h ? h->eng.sp.cull_radius : -1.0; }
+int nep_backend_set_line_cull(nep_backend_t* h, double radius) { return set_line_cull(h ? &h->eng : nullptr, radius); }
 
 int nep_batch_set_separator_rule(nep_batch_t* h, int32_t rule) {
-  if (!h || (rule != 0 && rule != 1)) return fail(NEP_E_ARG, "separator rule: 0 largest gap, 1 GLPK-class simplex");
-  h->eng.sp.sep_rule = rule;
-  HIPCHK(hipDeviceSynchronize());
-  return h->eng.size_row_scratch();
+  if (int e = set_separator_rule(h ? &h->eng : nullptr, rule)) return e;
+  return resize_row_scratch(h->eng);
 }
 // Row scratch for the worst case (one area per slot) whatever the mode: nep_batch_check reports NEP_E_CAP when the pool of the
 // presolve's redo pass ran out (more than 1 024 replans of one launch listed with rows beyond the register slots).
 int nep_batch_reserve_row_scratch(nep_batch_t* h) {
   if (!h) return fail(NEP_E_ARG, "null handle");
   h->eng.scratch_full = true;
-  HIPCHK(hipDeviceSynchronize());
-  return h->eng.size_row_scratch();
+  return resize_row_scratch(h->eng);
 }
 // Lines per (replan, segment) the line buckets hold: 0 the default budget, -1 the reference's worst case, n > 0 that many (see
 // size_scratch).  Re-sizes the buffers: not inside a graph capture.
@@ -1882,11 +1870,7 @@ int nep_batch_set_line_capacity(nep_batch_t* h, int32_t lines_per_segment) {
 }
 int64_t nep_batch_line_bucket_bytes(nep_batch_t* h) { return h ? (int64_t)h->slots * NEP_MAX_POL * h->eng.sp.lines_cap * 3 * (int64_t)sizeof(double) : 0; }
 int64_t nep_batch_row_scratch_bytes(nep_batch_t* h) { return h ? (int64_t)(h->eng.d_row_scratch.n * sizeof(double)) : 0; }
-int nep_backend_set_separator_rule(nep_backend_t* h, int32_t rule) {
-  if (!h || (rule != 0 && rule != 1)) return fail(NEP_E_ARG, "separator rule: 0 largest gap, 1 GLPK-class simplex");
-  h->eng.sp.sep_rule = rule;
-  return 0;
-}
+int nep_backend_set_separator_rule(nep_backend_t* h, int32_t rule) { return set_separator_rule(h ? &h->eng : nullptr, rule); }
 
 namespace { int set_tol(Engine& E, double res, double gap) {
   if (!(res >= 1e-12 && res <= 1e-6) || !(gap >= 1e-13 && gap <= 1e-7)) return fail(NEP_E_ARG, "tolerances: residuals in [1e-12, 1e-6], relative gap in [1e-13, 1e-7]");
@@ -1898,8 +1882,9 @@ int nep_batch_set_tolerances(nep_batch_t* h, double residual_tol, double gap_tol
 int nep_backend_set_tolerances(nep_backend_t* h, double residual_tol, double gap_tol) { if (!h) return fail(NEP_E_ARG, "null handle"); return set_tol(h->eng, residual_tol, gap_tol); }
 
 // (on: 0 off; 1 — the default — and 2 everywhere, under the presolve as well; 3: every-row solves only, round 5's default)
-int nep_batch_set_polish(nep_batch_t* h, int32_t on) { if (!h) return fail(NEP_E_ARG, "null handle"); h->eng.polish = on != 0; h->eng.polish_presolve = on == 1 || on == 2; return 0; }
-int nep_backend_set_polish(nep_backend_t* h, int32_t on) { if (!h) return fail(NEP_E_ARG, "null handle"); h->eng.polish = on != 0; h->eng.polish_presolve = on == 1 || on == 2; return 0; }
+namespace { int set_polish(Engine& E, int32_t on) { E.polish = on != 0; E.polish_presolve = on == 1 || on == 2; return 0; } }
+int nep_batch_set_polish(nep_batch_t* h, int32_t on) { if (!h) return fail(NEP_E_ARG, "null handle"); return set_polish(h->eng, on); }
+int nep_backend_set_polish(nep_backend_t* h, int32_t on) { if (!h) return fail(NEP_E_ARG, "null handle"); return set_polish(h->eng, on); }
 // Test hook: the last replan's polish pass — replans listed for it (solves that ended without the strict tests), replans certified
 int nep_batch_debug_polish_count(nep_batch_t* h, int32_t* listed, int32_t* certified) {
   if (!h) return fail(NEP_E_ARG, "null handle");
@@ -2010,12 +1995,17 @@ int nep_batch_debug_lines(nep_batch_t* h, int32_t slot, int32_t cap, int32_t* se
 // (box rows, separating-line rows).  Reads the handle's line buckets as that replan left them and d_solution as the caller got it.
 int nep_batch_active_rows(nep_batch_t* h, const nep_solution* d_solution, double tol, int32_t* d_out, void* stream) {
   if (!h || !d_solution || !d_out || !(tol >= 0.0)) return fail(NEP_E_ARG, "bad arguments");
-  Engine& E = h->eng;
-  ProblemSet ps{};
-  E.fill(ps);
-  ps.solution = const_cast<nep_solution*>(d_solution);
-  launch_active_rows(h->slots, E.sp, ps, tol, d_out, (hipStream_t)stream);
+  const ProblemSet ps = round_set(h, nullptr, const_cast<nep_solution*>(d_solution));
+  launch_active_rows(h->slots, h->eng.sp, ps, tol, d_out, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// Test hook: the device and page-locked bytes this process's handles and calls hold right now (counted at every allocation and free
+// of a DevBuf / PinnedArena; exchange.hip's staging buffers are not among them)
+int nep_debug_live_bytes(int64_t* device_bytes, int64_t* pinned_bytes) {
+  if (!device_bytes || !pinned_bytes) return fail(NEP_E_ARG, "null argument");
+  *device_bytes = g_live_device.load(); *pinned_bytes = g_live_pinned.load();
   return 0;
 }
 
