@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from neptune_amd import abi, scene
+from safety_cases import resolve as _resolve          # the header's rule in numpy (shared with test_gpu_safety_sizes.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -267,24 +268,6 @@ def test_sharded_masked_equals_full_handle(be):
         assert cm.tobytes() == ref[2][sl].tobytes()
     for h in hs + [full]:
         h.close()
-
-
-def _resolve(C, Cp, mask, ent=None):
-    """the header's rule: inactive agents accepted first; active ones in id order, turned down by a conflict (either direction) with
-    any accepted agent, by check_prev (Cp[a, j] for any j) or by the entangle verdict"""
-    N = len(mask)
-    acc = (mask == 0).copy()
-    for a in range(N):
-        if mask[a] == 0:
-            continue
-        bad = bool(ent is not None and ent[a])
-        if Cp is not None:
-            bad |= bool(np.any(np.delete(Cp[a], a)))
-        for j in range(N):
-            if j != a and acc[j] and (C[a, j] or C[j, a]):
-                bad = True
-        acc[a] = not bad
-    return acc.astype(np.int32)
 
 
 @pytest.mark.parametrize("check_prev", [False, True], ids=["plain", "check_prev"])
