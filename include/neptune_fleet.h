@@ -6,7 +6,7 @@
  * (scene, agent) slot, and three asynchronous calls move it — so a faithful round
  *
  *   nep_batch_fleet_select -> nep_batch_frontend -> nep_batch_replan -> nep_batch_safety_commit -> nep_batch_fleet_commit
- *     [-> nep_batch_audit] -> nep_batch_fleet_tick
+ *     [-> nep_batch_audit] [-> nep_batch_fleet_mission] -> nep_batch_fleet_tick
  *
  * is a fixed launch sequence on fixed buffers: one HIP graph for all scenes, no host synchronisation in it.  The arithmetic is the
  * host library's own (neptune_amd/csrc/plan_common.h is compiled into both), so the plans, tracked states and trajectories on the
@@ -19,7 +19,7 @@
  *   last selection   k_index_end of the last nep_batch_fleet_select (what the splice erases)
  *   tracked state    12 doubles: the goal the perfect tracker took last (Neptune::getNextGoal)
  *   trajectory       the composed committed trajectory (pwp_prev_) and whether the agent has committed one yet
- *   bookkeeping      sticky `done` (arrived), the last round's outcome, sticky NEP_FLEET_FLAG_* bits
+ *   bookkeeping      sticky `done` (arrived; a mission's new goal clears it), the last round's outcome, sticky NEP_FLEET_FLAG_* bits
  * State of a scene: the clock t_now, a round counter, and counters of every outcome.
  *
  * What differs from the reference:
@@ -159,6 +159,147 @@ int nep_batch_fleet_track_ent(nep_batch_t* h, const nep_traj_rec* d_records, int
  * proven to add no crossing (nep_batch_debug_set_option "fleet_ent_proof" 0: everything is walked; same states).               */
 int nep_batch_fleet_ent_state(nep_batch_t* h, nep_fe_ent_state* states_out, int32_t* flags_round_out, int32_t* flags_ever_out,
                               int32_t* walked_out);
+
+/* ---- missions: successive goals, timeouts, leg records -------------------------------------------------------------------------
+ * The two goal generators of the reference's experiments as a controller inside the round, so that a campaign of any length
+ * needs no host round trip:
+ *   NEP_MISSION_PER_AGENT    NeptuneRos::autoCMD (neptune_ros.cpp:1047-1102, yaml auto_cmd): every agent for itself.  Once
+ *                            min_interval has passed since its goal was issued and the agent is at rest — (el < timeout && v_xy >
+ *                            rest_v) || a_xy > rest_a holds it off, the reference's precedence — its leg ends when it is within
+ *                            arrive_radius of the goal (reached) or older than timeout (timed out), and it gets a new goal.
+ *   NEP_MISSION_FLEET_RUNS   scripts/benchmark_mtlp.py:167-281: the whole scene.  A run ends when every agent is `completed`
+ *                            (within arrive_radius of its goal; the flag is re-evaluated at every tick, in both directions) —
+ *                            a success — or after timeout — a failure; then every agent gets a new goal, in agent order.
+ * The round becomes  ... fleet_commit -> [audit] -> [fleet_track_ent] -> nep_batch_fleet_mission -> fleet_tick.
+ *
+ * The call looks at the round_ticks ticks about to be flown by nep_batch_fleet_track_ent's rule: p_0 the tracked state, p_q =
+ * ring[(head + min(q - 1, size - 1)) mod cap], the end state s_end = the 12 doubles of p_round_ticks, the end clock t_end = t_now
+ * after round_ticks times t += dc.  Per tick the slot's leg grows by |p_q - p_(q-1)| (3-D) while the agent is not arrived — mode
+ * PER_AGENT: |p_q - goal| > arrive_radius (neptune_ros.cpp:620); mode FLEET_RUNS: `completed` is 0 before the step — and in mode
+ * FLEET_RUNS completed = |p_q - goal| < arrive_radius afterwards.  The triggers are evaluated once per call on s_end and t_end.
+ *
+ * A leg that ends writes a record (nep_mission_leg) and its slot's totals.  max_goals is the number of legs per slot (runs per
+ * scene) that may end: the leg that uses the quota up draws nothing — the slot keeps its last goal and its `done` — and a scene
+ * is `finished` when every slot (mode FLEET_RUNS: the scene) has used its quota; the call does nothing on a finished scene.
+ * Otherwise a new goal is drawn, goal and t_issue are set (mode FLEET_RUNS: t_run, and every slot's t_issue), the leg length
+ * (and `completed`) zeroed, done[slot] cleared and `issued` incremented, so that issued == reached + timed_out + (1 while a leg
+ * is open) at all times.  The next select publishes the new goal; fleet_tick tests arrival against it.
+ *
+ * Drawing.  Candidate k = 0, 1, 2, ... of (global slot, goal index = the slot's `issued`) is (x, y) = lo + (hi - lo) * u with
+ * u = (bits >> 11) * 2^-53 and the splitmix64 finaliser
+ *   sm(x):  z = x + 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31
+ *   h1 = sm(sm(seed ^ sm(global_slot)) + goal_index);   bits_x = sm(h1 + 2k);   bits_y = sm(h1 + 2k + 1)
+ * (all in 64-bit unsigned arithmetic).  A candidate is accepted when (a parameter of 0 switches its test off)
+ *   1. it is at least min_dist_self (x-y) from the agent's s_end position (neptune_ros.cpp:1074),
+ *   2. at most tether_max (x-y) from the agent's base pb[a] (:1076; benchmark_mtlp.py:233),
+ *   3. on or inside none of the scene's keep-out polygons (counter-clockwise convex: every edge cross product >= 0 is inside,
+ *      boundary included, as cu::check_inside counts ON_BOUNDARY),
+ *   4. |(x, y, goal_z) - pos_j| >= close_pos for every agent j of the scene (the own one included) at its s_end position,
+ *   5. |new - new_j| >= close_goal for every j < a that received a goal in this same call.
+ * The goal is the accepted candidate of lowest k < max_attempts.  Without one the slot keeps its goal (it is issued again:
+ * t_issue reset, a new leg), its no_goal total and the sticky NEP_FLEET_FLAG_GOAL are raised, mode PER_AGENT logs a record with
+ * outcome NEP_MISSION_NO_GOAL, and nep_batch_check returns NEP_E_CAP.
+ *
+ * What differs from the reference:
+ *   randomness       the reference seeds from the wall clock (autoCMD) and numpy's global state (benchmark_mtlp): nothing
+ *                    deterministic to match.  The rules are kept one for one; the draws come from the counter-based generator above.
+ *   when it runs     autoCMD runs on its own timer, benchmark_mtlp on agent 0's odometry messages; here both are evaluated once per
+ *                    round, on the state the round's last tick will leave.
+ *   no gate          benchmark_mtlp waits for the MTLP comparator's acknowledgement before the next run; there is no comparator here.
+ *   one rule set     both modes share the five tests (autoCMD has 1-3, benchmark_mtlp 2, 4, 5); a test is off at parameter 0.
+ *   quota            max_goals ends a campaign (the reference's scripts are stopped from outside or after 100 runs).
+ *   use_moveback_, the single-agent A* benchmark branch of replanCB: not built.
+ * Limits: the kernel stages a scene's end positions, new goals and keep-outs in 64 KB of LDS, sized once at
+ * nep_batch_fleet_mission_init for 52 B per agent and a full keep-out set (NEP_MISSION_MAX_POLY polygons, NEP_MISSION_MAX_VERT
+ * vertices in all per scene), so that keep-outs uploaded later fit a round captured earlier: up to 1 097 agents; beyond: NEP_E_CAP. */
+#define NEP_MISSION_PER_AGENT 1
+#define NEP_MISSION_FLEET_RUNS 2
+#define NEP_MISSION_REACHED 1           /* nep_mission_leg.outcome (mode FLEET_RUNS: the run succeeded)                      */
+#define NEP_MISSION_TIMED_OUT 2         /* (mode FLEET_RUNS: the run failed)                                                 */
+#define NEP_MISSION_NO_GOAL 3           /* no candidate of max_attempts passed: the slot keeps its goal                      */
+#define NEP_FLEET_FLAG_GOAL 8           /* sticky per slot (nep_batch_fleet_state's flags): a draw found no goal             */
+#define NEP_MISSION_MAX_POLY 64
+#define NEP_MISSION_MAX_VERT 512
+
+/* nep_abi_sizeof(20) */
+typedef struct nep_mission_cfg {
+  int32_t mode;                   /* NEP_MISSION_PER_AGENT or NEP_MISSION_FLEET_RUNS                                         */
+  int32_t max_goals;              /* legs per slot (runs per scene) that may end, >= 1                                       */
+  int32_t max_attempts;           /* candidates per draw: a multiple of 64, 64 .. 4096                                       */
+  int32_t log_cap;                /* records kept per slot (per scene in mode FLEET_RUNS), >= 0                              */
+  uint64_t seed;
+  double lo[2], hi[2];            /* the box goals are drawn in (the caller shrinks the world)                               */
+  double goal_z, arrive_radius, min_interval, timeout, rest_v, rest_a;      /* (min_interval, rest_*: mode PER_AGENT only)  */
+  double min_dist_self, tether_max, close_pos, close_goal;                  /* the tests 1, 2, 4, 5; 0: off                 */
+} nep_mission_cfg;
+
+/* nep_abi_sizeof(21): 64 bytes.  Mode FLEET_RUNS: who = scene, index = run, t_issue = t_run, length = the mean of the slots'
+ * leg lengths summed in agent order, goal = 0, attempts = candidates examined by all the run's draws.                          */
+typedef struct nep_mission_leg {
+  int32_t who;                    /* global slot (mode PER_AGENT) or scene                                                   */
+  int32_t index;                  /* goal index of the leg (0: the goal given to nep_batch_fleet_init) or run index          */
+  int32_t outcome;                /* NEP_MISSION_*                                                                           */
+  int32_t attempts;               /* candidates examined by the draw that followed (accepted k + 1, or max_attempts)         */
+  double t_issue, t_end, length;
+  double goal[3];
+} nep_mission_leg;
+
+/* One scene's mission state and inputs in host memory, for nep_mission_step (slots are the scene's agents, in order). */
+typedef struct nep_mission_scene {
+  int32_t n_agents, scene;        /* global slot = scene * n_agents + agent                                                  */
+  int32_t round_ticks, n_poly;
+  double t_now, dc;
+  const double* pos;              /* [n_agents][round_ticks + 1][3]: p_0 .. p_round_ticks                                    */
+  const double* s_end;            /* [n_agents][12]                                                                          */
+  const double* pb;               /* [n_agents][2]                                                                           */
+  const int32_t* poly_off;        /* [n_poly + 1] */
+  const double* poly_xy;          /* counter-clockwise convex keep-outs                                                      */
+  double* goal;                   /* [n_agents][3]                                                                           */
+  int32_t* done;                  /* [n_agents]                                                                              */
+  int32_t* flags;                 /* [n_agents] sticky NEP_FLEET_FLAG_*                                                      */
+  double* t_issue;                /* [n_agents]                                                                              */
+  double* length;                 /* [n_agents]                                                                              */
+  int32_t* completed;             /* [n_agents]                                                                              */
+  int32_t* counts;                /* [n_agents][4]: issued, reached, timed out, no goal                                      */
+  double* sums;                   /* [n_agents][2]: leg time, leg length of the ended legs                                   */
+  int32_t* scene_i;               /* [4]: run index, runs succeeded, runs failed, finished                                   */
+  double* t_run;                  /* [1]                                                                                     */
+  nep_mission_leg* log;           /* [n_agents][log_cap] (mode FLEET_RUNS: [log_cap]); record i of an owner sits at i mod log_cap */
+  int32_t* log_n;                 /* [n_agents] (mode FLEET_RUNS: [1]) records ever written                                  */
+} nep_mission_scene;
+
+/* Host data, like nep_batch_set_scene_statics: the keep-out polygons of one scene (off [n_poly + 1], xy [off[n_poly]][2]).
+ * Clockwise input is reversed, non-convex input or a polygon of fewer than 3 vertices refused (NEP_E_ARG); more than
+ * NEP_MISSION_MAX_POLY polygons or NEP_MISSION_MAX_VERT vertices: NEP_E_CAP.  Convexity is judged with the tolerance of
+ * nep_batch_set_scene_statics (a turn of -1e-9 (1 + scale)^2 passes), test 3 is exact: at a vertex that is reflex within that
+ * tolerance, points within the same margin of it may fall on either side.  Hulls (scene.keepout_polygons) have no such vertex.
+ * Callable before nep_batch_fleet_init and before nep_batch_fleet_mission_init, and between rounds afterwards (also after a
+ * round was captured: the kernel reads the set from the handle's buffers); survives both inits.  Synchronises.                */
+int nep_batch_fleet_mission_keepout(nep_batch_t* h, int32_t scene, int32_t n_poly, const int32_t* off, const double* xy);
+
+/* Allocates (first call) or re-seeds the mission state, after nep_batch_fleet_init (which drops it, like the tether state): the
+ * first leg / run is on the goals given to nep_batch_fleet_init with t_issue = t_run = the scenes' clocks, issued = 1, everything
+ * else 0.  NEP_E_ARG on a bad configuration (mode PER_AGENT: min_dist_self <= goal_radius is one — a fresh goal must not count as
+ * reached), NEP_E_STATE without fleet state, NEP_E_CAP beyond the limits above.  Synchronises; not capturable.                  */
+int nep_batch_fleet_mission_init(nep_batch_t* h, const nep_mission_cfg* cfg, void* stream);
+
+/* The controller, one wave per scene; between nep_batch_fleet_commit (and the audit / tether tracking) and nep_batch_fleet_tick.
+ * Asynchronous, capturable.  NEP_E_STATE before nep_batch_fleet_mission_init.                                                  */
+int nep_batch_fleet_mission(nep_batch_t* h, void* stream);
+
+/* Blocking readers (host memory, each may be NULL).  Per slot: goal [slots][3], t_issue, length [slots], completed [slots], counts
+ * [slots][4] (issued, reached, timed out, no goal), sums [slots][2] (leg time, leg length).  Per scene: scene_i [n_scenes][4] (run
+ * index, runs succeeded, runs failed, finished), t_run [n_scenes].                                                              */
+int nep_batch_fleet_mission_state(nep_batch_t* h, double* goal_out, double* t_issue_out, double* length_out, int32_t* completed_out,
+                                  int32_t* counts_out, double* sums_out, int32_t* scene_out, double* t_run_out);
+/* The log: log_out [owners][log_cap] records as stored (record i of an owner at i mod log_cap), n_out [owners] records ever
+ * written; owners = slots (mode PER_AGENT) or scenes.  Returns log_cap.                                                          */
+int nep_batch_fleet_mission_log(nep_batch_t* h, nep_mission_leg* log_out, int32_t* n_out);
+
+/* Host form of nep_batch_fleet_mission for one scene (mission_host.cpp; no HIP call): the arithmetic is the kernel's
+ * (neptune_amd/csrc/mission_common.h) and the device equals a chain of these calls byte for byte.  NEP_E_ARG on a bad
+ * configuration or null pointers.                                                                                               */
+int nep_mission_step(const nep_mission_cfg* cfg, nep_mission_scene* sc);
 
 /* ---- readers: blocking (they wait for the device), for tests and reports; every output is host memory and may be NULL ------ */
 /* ring_cap of the handle's fleet state (NEP_E_STATE before nep_batch_fleet_init)                                              */

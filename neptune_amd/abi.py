@@ -179,6 +179,39 @@ NEP_FLEET_SKIPPED, NEP_FLEET_FE_NO_SOLUTION, NEP_FLEET_QP_FAILED, NEP_FLEET_REJE
 NEP_FLEET_N_COUNTERS = 8
 FLEET_OUTCOMES = ("skipped", "fe_no_solution", "qp_failed", "rejected_by_safety", "accepted", "cap")
 NEP_FLEET_FLAG_SEG, NEP_FLEET_FLAG_RING, NEP_FLEET_FLAG_SPLICE = 1, 2, 4
+NEP_FLEET_FLAG_GOAL = 8
+
+
+# ---- missions (include/neptune_fleet.h) ----
+NEP_MISSION_PER_AGENT, NEP_MISSION_FLEET_RUNS = 1, 2
+NEP_MISSION_REACHED, NEP_MISSION_TIMED_OUT, NEP_MISSION_NO_GOAL = 1, 2, 3
+NEP_MISSION_MAX_POLY, NEP_MISSION_MAX_VERT = 64, 512
+MISSION_COUNTS = ("issued", "reached", "timed_out", "no_goal")
+
+
+class nep_mission_cfg(C.Structure):
+    """include/neptune_fleet.h: the mission controller's configuration (nep_batch_fleet_mission_init, nep_mission_step)."""
+    _fields_ = [("mode", C.c_int32), ("max_goals", C.c_int32), ("max_attempts", C.c_int32), ("log_cap", C.c_int32),
+                ("seed", C.c_uint64), ("lo", C.c_double * 2), ("hi", C.c_double * 2),
+                ("goal_z", C.c_double), ("arrive_radius", C.c_double), ("min_interval", C.c_double), ("timeout", C.c_double),
+                ("rest_v", C.c_double), ("rest_a", C.c_double),
+                ("min_dist_self", C.c_double), ("tether_max", C.c_double), ("close_pos", C.c_double), ("close_goal", C.c_double)]
+
+
+class nep_mission_leg(C.Structure):
+    """include/neptune_fleet.h: one record of the mission log (a leg of a slot, or a run of a scene)."""
+    _fields_ = [("who", C.c_int32), ("index", C.c_int32), ("outcome", C.c_int32), ("attempts", C.c_int32),
+                ("t_issue", C.c_double), ("t_end", C.c_double), ("length", C.c_double), ("goal", C.c_double * 3)]
+
+
+class nep_mission_scene(C.Structure):
+    """include/neptune_fleet.h: one scene's mission state and inputs in host memory (nep_mission_step)."""
+    _fields_ = [("n_agents", C.c_int32), ("scene", C.c_int32), ("round_ticks", C.c_int32), ("n_poly", C.c_int32),
+                ("t_now", C.c_double), ("dc", C.c_double),
+                ("pos", C.c_void_p), ("s_end", C.c_void_p), ("pb", C.c_void_p), ("poly_off", C.c_void_p), ("poly_xy", C.c_void_p),
+                ("goal", C.c_void_p), ("done", C.c_void_p), ("flags", C.c_void_p), ("t_issue", C.c_void_p), ("length", C.c_void_p),
+                ("completed", C.c_void_p), ("counts", C.c_void_p), ("sums", C.c_void_p), ("scene_i", C.c_void_p), ("t_run", C.c_void_p),
+                ("log", C.c_void_p), ("log_n", C.c_void_p)]
 
 
 def np_dtype(struct):
@@ -193,6 +226,7 @@ FE_RESULT_DTYPE = np.dtype(nep_fe_result)
 FE_ENT_STATE_DTYPE = np.dtype(nep_fe_ent_state)
 AUDIT_DTYPE = np.dtype(nep_audit)
 PWP_DTYPE = np.dtype(nep_pwp)
+MISSION_LEG_DTYPE = np.dtype(nep_mission_leg)
 
 
 def dptr(a):

@@ -458,6 +458,53 @@ class BatchBackend:
                                               abi.iptr(out["walked"])))
         return out
 
+    # ---- the missions of the fleet state (include/neptune_fleet.h) --------------------------------------------------
+    def fleet_mission_keepout(self, scene, polys):
+        """the keep-out polygons of one scene (list of (n, 2) arrays, host data; nep_batch_fleet_mission_keepout)"""
+        off, xy = _csr(polys)
+        check(lib().nep_batch_fleet_mission_keepout(self._h, scene, len(polys), abi.iptr(off), abi.dptr(xy)))
+
+    def fleet_mission_init(self, cfg, stream=None):
+        """allocates / re-seeds the mission state (nep_batch_fleet_mission_init): cfg abi.nep_mission_cfg; after fleet_init"""
+        st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        check(lib().nep_batch_fleet_mission_init(self._h, C.byref(cfg), st.cuda_stream))
+        self.mission_cfg = cfg
+
+    def fleet_mission(self, stream=None):
+        """the mission controller's step of the round (nep_batch_fleet_mission), before fleet_tick"""
+        st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        check(lib().nep_batch_fleet_mission(self._h, st.cuda_stream))
+
+    def fleet_mission_state(self):
+        """the mission state (blocking) -> dict: goal [slots][3], t_issue / length / completed [slots], counts [slots][4] (abi.MISSION_COUNTS),
+        sums [slots][2] (leg time, leg length), scene [n_scenes][4] (run, runs succeeded, runs failed, finished), t_run [n_scenes]"""
+        n, S = self.slots, self.n_scenes
+        out = dict(goal=np.zeros((n, 3)), t_issue=np.zeros(n), length=np.zeros(n), completed=np.zeros(n, dtype=np.int32),
+                   counts=np.zeros((n, 4), dtype=np.int32), sums=np.zeros((n, 2)), scene=np.zeros((S, 4), dtype=np.int32), t_run=np.zeros(S))
+        check(lib().nep_batch_fleet_mission_state(self._h, abi.dptr(out["goal"]), abi.dptr(out["t_issue"]), abi.dptr(out["length"]),
+                                                  abi.iptr(out["completed"]), abi.iptr(out["counts"]), abi.dptr(out["sums"]),
+                                                  abi.iptr(out["scene"]), abi.dptr(out["t_run"])))
+        return out
+
+    def fleet_mission_finished(self):
+        """[n_scenes] bool: the scenes whose campaign is over (blocking; 16 bytes per scene)"""
+        sc = np.zeros((self.n_scenes, 4), dtype=np.int32)
+        check(lib().nep_batch_fleet_mission_state(self._h, None, None, None, None, None, None, abi.iptr(sc), None))
+        return sc[:, 3] != 0
+
+    def fleet_mission_log(self, ordered=True):
+        """the mission log (blocking) -> (records, n): n [owners] records ever written, records a list per owner (slot, or scene in mode
+        FLEET_RUNS) of the last min(n, log_cap) MISSION_LEG_DTYPE records, oldest first (ordered=False: the [owners][log_cap] array as stored)"""
+        cfg = self.mission_cfg
+        owners = self.slots if cfg.mode == abi.NEP_MISSION_PER_AGENT else self.n_scenes
+        cap = int(cfg.log_cap)
+        log = np.zeros((owners, max(cap, 1)), dtype=abi.MISSION_LEG_DTYPE); n = np.zeros(owners, dtype=np.int32)
+        check(lib().nep_batch_fleet_mission_log(self._h, log.ctypes.data, abi.iptr(n)))
+        log = log[:, :cap]
+        if not ordered:
+            return log, n
+        return [log[o, [i % cap for i in range(max(0, int(n[o]) - cap), int(n[o]))]] if cap else log[o, :0] for o in range(owners)], n
+
     def next_starts(self, d_records, dt, d_start, d_alt_goal=None, switch_radius=0.0, stream=None):
         """point A of the next round on the device: d_start's clock advances by dt and its state becomes that of the committed
         trajectories d_records at the new time; with d_alt_goal ([slots][3] float64) arrived agents swap goals

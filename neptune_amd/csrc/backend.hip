@@ -17,6 +17,7 @@
 
 #include "nep_device.h"
 #include "audit_common.h"
+#include "mission_common.h"
 #include "../../include/neptune_plan.h"
 #include "../../include/neptune_entangle.h"
 
@@ -1004,6 +1005,11 @@ struct nep_batch {
     bool ent_ready = false; double cable = 0.0;
     DevBuf<nep_fe_ent_state> ent, ent_save; DevBuf<double> pub_xy, pub_prev_xy, ent_pos;
     DevBuf<int> pub_n, pub_prev_n, ent_flags, ent_ever, ent_walked, ent_flags_a;
+    // the missions (nep_batch_fleet_mission_init): legs, totals, runs, the log; the keep-outs are staged by
+    // nep_batch_fleet_mission_keepout (before or after either init: no init drops them)
+    bool mis_ready = false; nep_mission_cfg mis_cfg{}; size_t mis_lds = 0;
+    DevBuf<double> mis_t_issue, mis_length, mis_sums, mis_t_run; DevBuf<int> mis_completed, mis_counts, mis_scene, mis_log_n; DevBuf<nep_mission_leg> mis_log;
+    DevBuf<int> keep_n, keep_off; DevBuf<double> keep_xy;
   } fleet;
 };
 
@@ -1487,6 +1493,7 @@ int nep_batch_fleet_init(nep_batch_t* h, const nep_fleet_cfg* cfg, const double*
   const int cap = cfg->ring_cap > 0 ? cfg->ring_cap : cfg->deltaT0 + h->cfg.max_states;
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));      // (a re-seed: kernels of the previous flight may still read the state)
   F.ready = false; F.ent_ready = false;      // (a re-seeded fleet flies untethered until nep_batch_fleet_init_ent runs again)
+  F.mis_ready = false;                       // (and without missions until nep_batch_fleet_mission_init does)
   if (int e = F.ring.ensure(slots * cap * 12)) return e;
   if (int e = F.state.ensure(slots * 12)) return e;
   if (int e = F.goal.ensure(slots * 3)) return e;
@@ -1603,6 +1610,135 @@ int nep_batch_fleet_ent_state(nep_batch_t* h, nep_fe_ent_state* states_out, int3
   if (flags_ever_out) HIPCHK(hipMemcpy(flags_ever_out, F.ent_ever.p, slots * sizeof(int), hipMemcpyDeviceToHost));
   if (walked_out) HIPCHK(hipMemcpy(walked_out, F.ent_walked.p, slots * sizeof(int), hipMemcpyDeviceToHost));
   return 0;
+}
+
+// ---- missions (include/neptune_fleet.h; kernels: fleet_mission_kernels.hip; host form: mission_host.cpp) ----
+namespace {
+int mission_keep_ensure(nep_batch_t* h) {
+  nep_batch::Fleet& F = h->fleet;
+  const size_t S = (size_t)h->cfg.n_scenes;
+  if (F.keep_n.p) return 0;
+  if (int e = F.keep_n.ensure(S)) return e;
+  if (int e = F.keep_off.ensure(S * (NEP_MISSION_MAX_POLY + 1))) return e;
+  if (int e = F.keep_xy.ensure(S * NEP_MISSION_MAX_VERT * 2)) return e;
+  HIPCHK(hipMemset(F.keep_n.p, 0, S * sizeof(int)));
+  HIPCHK(hipMemset(F.keep_off.p, 0, S * (NEP_MISSION_MAX_POLY + 1) * sizeof(int)));
+  HIPCHK(hipMemset(F.keep_xy.p, 0, S * NEP_MISSION_MAX_VERT * 2 * sizeof(double)));
+  return 0;
+}
+// the kernel's dynamic LDS, sized once per handle for the largest keep-out set a scene can hold: a captured graph keeps the size
+// it was captured with, whatever is uploaded later
+size_t mission_lds_need(nep_batch_t* h) { return mission_lds_bytes(h->cfg.num_agents, NEP_MISSION_MAX_VERT, NEP_MISSION_MAX_POLY); }
+void fleet_mission_args(nep_batch_t* h, FleetMissionArgs& ma) {
+  nep_batch::Fleet& F = h->fleet;
+  ma.cfg = F.mis_cfg; ma.lds_bytes = F.mis_lds;
+  ma.t_issue = F.mis_t_issue.p; ma.length = F.mis_length.p; ma.completed = F.mis_completed.p; ma.counts = F.mis_counts.p; ma.sums = F.mis_sums.p;
+  ma.scene_i = F.mis_scene.p; ma.t_run = F.mis_t_run.p; ma.log = F.mis_log.p; ma.log_n = F.mis_log_n.p;
+  ma.kn = F.keep_n.p; ma.koff = F.keep_off.p; ma.kxy = F.keep_xy.p;
+}
+constexpr size_t kMissionLds = 64 * 1024;
+}  // namespace
+
+int nep_batch_fleet_mission_keepout(nep_batch_t* h, int32_t scene, int32_t n_poly, const int32_t* off, const double* xy) {
+  if (int e = fleet_guard(h, false)) return e;
+  if (scene < 0 || scene >= h->cfg.n_scenes || n_poly < 0 || (n_poly > 0 && (!off || !xy))) return fail(NEP_E_ARG, "bad arguments");
+  if (n_poly > NEP_MISSION_MAX_POLY) return fail(NEP_E_CAP, "more than NEP_MISSION_MAX_POLY keep-out polygons in a scene");
+  std::vector<int> o(NEP_MISSION_MAX_POLY + 1, 0);
+  std::vector<double> q;
+  for (int j = 0; j < n_poly; j++) {
+    const int c = off[j + 1] - off[j];
+    if (off[0] != 0 || c < 3) return fail(NEP_E_ARG, "keep-out offsets start at 0 and every polygon has at least 3 vertices");
+    if (off[j + 1] > NEP_MISSION_MAX_VERT) return fail(NEP_E_CAP, "more than NEP_MISSION_MAX_VERT keep-out vertices in a scene");
+    std::vector<double> v(xy + 2 * (size_t)off[j], xy + 2 * (size_t)off[j + 1]);
+    if (!normalize_ccw(v.data(), c)) return fail(NEP_E_ARG, "a keep-out polygon is not convex");
+    q.insert(q.end(), v.begin(), v.end());
+    o[j + 1] = off[j + 1];
+  }
+  nep_batch::Fleet& F = h->fleet;
+  HIPCHK(hipDeviceSynchronize());     // the previous set may still be read by kernels in flight
+  if (int e = mission_keep_ensure(h)) return e;
+  const int nv = n_poly ? o[n_poly] : 0;
+  HIPCHK(hipMemcpy(F.keep_n.p + scene, &n_poly, sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(F.keep_off.p + (size_t)scene * (NEP_MISSION_MAX_POLY + 1), o.data(), o.size() * sizeof(int), hipMemcpyHostToDevice));
+  if (nv) HIPCHK(hipMemcpy(F.keep_xy.p + (size_t)scene * NEP_MISSION_MAX_VERT * 2, q.data(), q.size() * sizeof(double), hipMemcpyHostToDevice));
+  return 0;
+}
+
+int nep_batch_fleet_mission_init(nep_batch_t* h, const nep_mission_cfg* cfg, void* stream) {
+  if (int e = fleet_guard(h, true)) return e;
+  if (!cfg) return fail(NEP_E_ARG, "null argument");
+  if (!nep_mission_impl::mission_cfg_ok(*cfg)) return fail(NEP_E_ARG, "bad mission configuration (mode, max_goals >= 1, max_attempts a multiple of 64 in 64..4096, log_cap >= 0, lo < hi, arrive_radius and timeout > 0, nothing negative)");
+  nep_batch::Fleet& F = h->fleet;
+  if (cfg->mode == NEP_MISSION_PER_AGENT && !(cfg->min_dist_self > F.cfg.goal_radius)) return fail(NEP_E_ARG, "mode NEP_MISSION_PER_AGENT needs min_dist_self > the fleet's goal_radius: a fresh goal must not count as reached");
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(hipStreamSynchronize(st));
+  F.mis_ready = false;
+  if (int e = mission_keep_ensure(h)) return e;
+  if (mission_lds_need(h) > kMissionLds) return fail(NEP_E_CAP, "the agents of a scene do not fit into the mission kernel's 64 KB of LDS next to NEP_MISSION_MAX_VERT keep-out vertices (52 B per agent: up to 1 097 agents)");
+  const size_t slots = (size_t)h->slots, S = (size_t)h->cfg.n_scenes;
+  const size_t owners = cfg->mode == NEP_MISSION_PER_AGENT ? slots : S;
+  if (int e = F.mis_t_issue.ensure(slots)) return e;
+  if (int e = F.mis_length.ensure(slots)) return e;
+  if (int e = F.mis_sums.ensure(slots * 2)) return e;
+  if (int e = F.mis_completed.ensure(slots)) return e;
+  if (int e = F.mis_counts.ensure(slots * 4)) return e;
+  if (int e = F.mis_scene.ensure(S * 4)) return e;
+  if (int e = F.mis_t_run.ensure(S)) return e;
+  if (int e = F.mis_log_n.ensure(owners)) return e;
+  if (int e = F.mis_log.ensure(owners * (size_t)cfg->log_cap)) return e;
+  F.mis_cfg = *cfg; F.mis_lds = mission_lds_need(h);
+  HIPCHK(hipMemsetAsync(F.mis_log_n.p, 0, owners * sizeof(int), st));
+  HIPCHK(hipMemsetAsync(F.mis_log.p, 0, std::max<size_t>(1, owners * (size_t)cfg->log_cap) * sizeof(nep_mission_leg), st));
+  FleetArgs fa{};
+  fleet_args(h, fa);
+  FleetMissionArgs ma{};
+  fleet_mission_args(h, ma);
+  launch_fleet_mission_seed(ma, fa, st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
+  F.mis_ready = true;
+  return 0;
+}
+
+int nep_batch_fleet_mission(nep_batch_t* h, void* stream) {
+  if (int e = fleet_guard(h, true)) return e;
+  if (!h->fleet.mis_ready) return fail(NEP_E_STATE, "nep_batch_fleet_mission_init has not run on this handle");
+  FleetArgs fa{};
+  fleet_args(h, fa);
+  FleetMissionArgs ma{};
+  fleet_mission_args(h, ma);
+  launch_fleet_mission(ma, fa, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int nep_batch_fleet_mission_state(nep_batch_t* h, double* goal_out, double* t_issue_out, double* length_out, int32_t* completed_out,
+                                  int32_t* counts_out, double* sums_out, int32_t* scene_out, double* t_run_out) {
+  if (int e = fleet_guard(h, true)) return e;
+  nep_batch::Fleet& F = h->fleet;
+  if (!F.mis_ready) return fail(NEP_E_STATE, "nep_batch_fleet_mission_init has not run on this handle");
+  const size_t slots = (size_t)h->slots, S = (size_t)h->cfg.n_scenes;
+  HIPCHK(hipDeviceSynchronize());
+  if (goal_out) HIPCHK(hipMemcpy(goal_out, F.goal.p, slots * 3 * sizeof(double), hipMemcpyDeviceToHost));
+  if (t_issue_out) HIPCHK(hipMemcpy(t_issue_out, F.mis_t_issue.p, slots * sizeof(double), hipMemcpyDeviceToHost));
+  if (length_out) HIPCHK(hipMemcpy(length_out, F.mis_length.p, slots * sizeof(double), hipMemcpyDeviceToHost));
+  if (completed_out) HIPCHK(hipMemcpy(completed_out, F.mis_completed.p, slots * sizeof(int), hipMemcpyDeviceToHost));
+  if (counts_out) HIPCHK(hipMemcpy(counts_out, F.mis_counts.p, slots * 4 * sizeof(int), hipMemcpyDeviceToHost));
+  if (sums_out) HIPCHK(hipMemcpy(sums_out, F.mis_sums.p, slots * 2 * sizeof(double), hipMemcpyDeviceToHost));
+  if (scene_out) HIPCHK(hipMemcpy(scene_out, F.mis_scene.p, S * 4 * sizeof(int), hipMemcpyDeviceToHost));
+  if (t_run_out) HIPCHK(hipMemcpy(t_run_out, F.mis_t_run.p, S * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int nep_batch_fleet_mission_log(nep_batch_t* h, nep_mission_leg* log_out, int32_t* n_out) {
+  if (int e = fleet_guard(h, true)) return e;
+  nep_batch::Fleet& F = h->fleet;
+  if (!F.mis_ready) return fail(NEP_E_STATE, "nep_batch_fleet_mission_init has not run on this handle");
+  const size_t owners = F.mis_cfg.mode == NEP_MISSION_PER_AGENT ? (size_t)h->slots : (size_t)h->cfg.n_scenes;
+  HIPCHK(hipDeviceSynchronize());
+  if (log_out && F.mis_cfg.log_cap > 0) HIPCHK(hipMemcpy(log_out, F.mis_log.p, owners * (size_t)F.mis_cfg.log_cap * sizeof(nep_mission_leg), hipMemcpyDeviceToHost));
+  if (n_out) HIPCHK(hipMemcpy(n_out, F.mis_log_n.p, owners * sizeof(int), hipMemcpyDeviceToHost));
+  return F.mis_cfg.log_cap;
 }
 
 int nep_batch_fleet_commit(nep_batch_t* h, const nep_solution* d_solution, const double* d_states, const nep_fe_result* d_fe_result,
@@ -1948,6 +2084,7 @@ int nep_batch_check(nep_batch_t* h, void* stream) {
   if (flags & NEP_FLAG_ENT_POOL) return fail(NEP_E_CAP, "the pool of big entangle-state records ran out (front end: children of a search were pruned for it, by claim order; safety re-check: a trajectory was turned down): nep_batch_set_fe_ent_big_records");
   if (flags & NEP_FLAG_ENT_TRACK) return fail(NEP_E_CAP, "nep_batch_track_ent: a tether's state outgrew NEP_FE_ENT_CAP crossings, NEP_MAX_BEND - 1 bend points or 32 new crossings in one step (the step was dropped), or a state handed in was malformed");
   if (flags & NEP_FLAG_FLEET) return fail(NEP_E_CAP, "nep_batch_fleet_commit: an accepted plan or composed trajectory would have outgrown the ring (ring_cap states), NEP_TRAJ_MAX_SEG intervals, or A was already flown (the slot kept its plan: outcome NEP_FLEET_CAP, flags in nep_batch_fleet_state)");
+  if (flags & NEP_FLAG_MISSION) return fail(NEP_E_CAP, "nep_batch_fleet_mission: a draw found no goal among max_attempts candidates (the slot kept its goal: NEP_FLEET_FLAG_GOAL in nep_batch_fleet_state's flags, no_goal in nep_batch_fleet_mission_state's counts)");
   if (flags & NEP_FLAG_ENT_BETA) return fail(NEP_E_ARG, "an entangle state passed to the front end has a non-zero beta for an agent crossing (the reference's calculateBetaForCase makes it 0.0)");
   if (flags & NEP_FLAG_HULL_OVERFLOW) return fail(NEP_E_CAP, "an interval overlaps more than NEP_HULL_MAX_CP/4 committed segments (or its hull has more than NEP_HULL_MAX_V vertices)");
   return 0;
@@ -2048,6 +2185,8 @@ int nep_abi_sizeof(int32_t which) {
     case 15: return (int)sizeof(nep_ent_track_inputs);
     case 17: return (int)sizeof(nep_audit);      // (16 stays unassigned: tests/test_ent_track_cpu.py pins it to -1)
     case 18: return (int)sizeof(nep_fleet_cfg);
+    case 20: return (int)sizeof(nep_mission_cfg);      // (19 stays unassigned: tests/test_fleet_plan_cpu.py pins it to -1)
+    case 21: return (int)sizeof(nep_mission_leg);
     default: return -1;
   }
 }

@@ -120,6 +120,7 @@ struct ProblemSet {
 __device__ __forceinline__ bool slot_active(const SceneParams& sp, const int* active, int slot) {
   return active == nullptr || active[(long)(slot / sp.n_local) * sp.num_agents + sp.first_local + slot % sp.n_local] != 0;
 }
+constexpr int NEP_FLAG_MISSION = 128;       // nep_batch_fleet_mission: a draw found no goal among max_attempts candidates (the slot kept its goal; NEP_FLEET_FLAG_GOAL)
 constexpr int NEP_FLAG_FLEET = 64;           // nep_batch_fleet_commit: an accepted slot's plan or composed trajectory would have outgrown its storage (the slot kept both; NEP_FLEET_CAP)
 constexpr int NEP_FLAG_ENT_TRACK = 32;      // nep_batch_track_ent: a tracked state outgrew the fixed record (list, bend points or a step's crossings; the step was dropped) or was handed in malformed
 constexpr int NEP_FLAG_ENT_POOL = 16;       // the safety pass's entangle re-check needed a big record and the pool had none left (nep_batch_set_fe_ent_big_records): the trajectory was turned down
@@ -290,6 +291,24 @@ void launch_fleet_seed(const FleetArgs& fa, const double* state0, hipStream_t st
 void launch_fleet_select(const FleetArgs& fa, hipStream_t st);
 void launch_fleet_commit(const FleetArgs& fa, hipStream_t st);
 void launch_fleet_tick(const FleetArgs& fa, hipStream_t st);
+// the mission controller of the fleet state (fleet_mission_kernels.hip): nep_batch_fleet_mission.  Goals, done and the slots' sticky
+// flags are FleetArgs'; everything else is the handle's mission state.  All device pointers.
+struct FleetMissionArgs {
+  nep_mission_cfg cfg;
+  size_t lds_bytes;              // mission_lds_bytes of the handle's largest scene
+  double* t_issue; double* length; int* completed;      // [slots]
+  int* counts;                   // [slots][4]: issued, reached, timed out, no goal
+  double* sums;                  // [slots][2]: leg time, leg length
+  int* scene_i;                  // [scenes][4]: run index, runs succeeded, runs failed, finished
+  double* t_run;                 // [scenes]
+  nep_mission_leg* log; int* log_n;      // [owners][log_cap], [owners]: owners = slots (mode PER_AGENT) or scenes
+  const int* kn;                 // [scenes] keep-out polygons of the scene
+  const int* koff;               // [scenes][NEP_MISSION_MAX_POLY + 1]
+  const double* kxy;             // [scenes][NEP_MISSION_MAX_VERT][2]
+};
+size_t mission_lds_bytes(int N, int n_vert, int n_poly);
+void launch_fleet_mission_seed(const FleetMissionArgs& ma, const FleetArgs& fa, hipStream_t st);
+void launch_fleet_mission(const FleetMissionArgs& ma, const FleetArgs& fa, hipStream_t st);
 // the tethers of the fleet state (fleet_ent_kernels.hip): nep_batch_fleet_select's bend points, _predict_ent, _track_ent
 struct FleetEntArgs {
   int N, S, n_scenes, static_stride, num_pol;

@@ -310,10 +310,16 @@ class DeviceFleetLoop:
 
     with the state at A (d_ent_a) predicted on the device and the commit records stamped with the published bend points before the
     safety pass (TetherLoop._publish).  check=False keeps the plain front end and safety pass and leaves the tracking on: what the
-    same fleet does to its tethers when nobody looks.  report() then also gives ever_entangled, too_long and track_cap per scene."""
+    same fleet does to its tethers when nobody looks.  report() then also gives ever_entangled, too_long and track_cap per scene.
+
+    missions=mission.MissionSpec(...) flies a campaign: fleet_mission goes between the commit (audit, tether
+    tracking) and fleet_tick, ends legs (mode "agent": NeptuneRos::autoCMD) or runs (mode "runs": benchmark_mtlp.py) and draws
+    the next goals on the device, inside the graph.  run() then stops when every scene's campaign is finished (it downloads the
+    scenes' flags instead of the slots' arrival flags), and report() adds `mission` per scene: legs or runs reached / timed out /
+    without a goal, mean leg time and length, the success rate.  Without missions nothing of this is allocated or launched."""
 
     def __init__(self, scenes, beam_width=32, delta_t_states=6, replan_every=5, periods=None, phases=None, audit=False, graph=True,
-                 goals=None, device=None, ring_cap=0, trace=False, tethers=False, check=True, ent_samples=3):
+                 goals=None, device=None, ring_cap=0, trace=False, tethers=False, check=True, ent_samples=3, missions=None):
         import torch
         self.torch = torch
         self.scenes = scenes
@@ -375,11 +381,20 @@ class DeviceFleetLoop:
             self.d_case = torch.zeros(n * abi.NEP_MAX_POL * N, dtype=torch.int32, device=dev)
             f = abi.TRAJ_REC_DTYPE.fields
             self._bend_cols = (f["n_bend"][1], f["n_bend"][1] + 4), (f["bend"][1], f["bend"][1] + f["bend"][0].itemsize)
+        self.missions = missions
+        if missions is not None:
+            from . import mission
+            self.mission_cfg = mission.mission_cfg(missions, p)
+            if mission.uses_keepouts(missions):
+                for s, sc in enumerate(scenes):
+                    be.fleet_mission_keepout(s, scene.keepout_polygons(sc))
+            be.fleet_mission_init(self.mission_cfg)
         self.rounds = 0
         self._g = None
         self.trace = [] if trace else None
         self.after_commit = None      # test hook: called between fleet_commit and fleet_tick of an eager round
         self.after_select = None      # test hook (tethered rounds): called after fleet_predict_ent of an eager round
+        self.after_mission = None     # test hook (missions): called between fleet_mission and fleet_tick of an eager round
         self.done = np.zeros((S, N), dtype=bool)
 
     def _publish(self, d_new):
@@ -416,12 +431,16 @@ class DeviceFleetLoop:
             be.audit(self.d_rec, self.d_clock, self.p.dc, self.replan_every, self.d_audit)
         if self.tethers:
             be.fleet_track_ent(self.d_rec, self.d_flags)
+        if self.missions is not None:
+            be.fleet_mission()
+            if self.after_mission is not None:
+                self.after_mission(self)
         be.fleet_tick()
 
     def round(self):
         """one bulk-synchronous round of every scene; True when every agent of every scene has arrived"""
         torch = self.torch
-        if self.graph and self.rounds >= 1 and self.after_commit is None and self.after_select is None:
+        if self.graph and self.rounds >= 1 and self.after_commit is None and self.after_select is None and self.after_mission is None:
             if self._g is None:
                 torch.cuda.synchronize()
                 s = torch.cuda.Stream(self.be.device)
@@ -440,6 +459,9 @@ class DeviceFleetLoop:
             sol = self.be.solutions(); fres = self.d_res.cpu().numpy().view(abi.FE_RESULT_DTYPE)
             self.trace.append([(int(oc[i]), int(sol[i]["K"]), int(fres[i]["status"]), int(sol[i]["stats"]["status"])) for i in range(self.S * self.N)])
         self.rounds += 1
+        if self.missions is not None:      # a campaign ends with its scenes, not with an arrival (the one download: 16 bytes per scene)
+            self.finished = self.be.fleet_mission_finished()
+            return bool(self.finished.all())
         self.done = self.be.fleet_done().reshape(self.S, self.N) != 0      # (the one download of a round: 4 bytes per slot)
         return bool(self.done.all())
 
@@ -463,17 +485,25 @@ class DeviceFleetLoop:
         state = st["state"].reshape(self.S, self.N, 12); done = st["done"].reshape(self.S, self.N)
         summ = audit_mod.summarize(self.audit_records(), self.S) if self.d_audit is not None else None
         ever = be.fleet_ent_state(states=False)["ever"].reshape(self.S, self.N) if self.tethers else None
+        msum, goals_now = None, self.goals
+        if self.missions is not None:
+            from . import mission
+            ms = be.fleet_mission_state()
+            msum = mission.summarize(ms, None, self.N, self.mission_cfg.mode)
+            goals_now = ms["goal"].reshape(self.S, self.N, 3)      # (dist_to_goal_mean below: to the goals the agents have now)
         out = []
         for s in range(self.S):
             c = cnt[s]
             d = dict(rounds=int(rnd[s]), replans=int(c[1] + c[2] + c[3] + c[4] + c[5]), accepted=int(c[4]), fe_no_solution=int(c[1]), qp_failed=int(c[2]),
                      qp_relaxed=int(c[6]), rejected_by_safety=int(c[3]), cap=int(c[5]), skipped=int(c[0]),
                      solves=int(c[1] + c[2] + c[3] + c[4] + c[5] + (0 if self.masked else c[0])), sim_time=float(t_now[s]), reached=int(done[s].sum()),
-                     dist_to_goal_mean=float(np.hypot(*(state[s, :, :2] - self.goals[s, :, :2]).T).mean()))
+                     dist_to_goal_mean=float(np.hypot(*(state[s, :, :2] - goals_now[s, :, :2]).T).mean()))
             if ever is not None:      # agents whose tether was ever entangled / longer than the cable / dropped a move at a capacity
                 d["ever_entangled"] = int(c[7])
                 d["too_long"] = int(((ever[s] & abi.NEP_ENT_TRACK_TOO_LONG) != 0).sum())
                 d["track_cap"] = int(((ever[s] & abi.NEP_ENT_TRACK_CAP) != 0).sum())
+            if msum is not None:
+                d["mission"] = msum[s]
             if summ is not None:
                 d["audit"] = summ[s]
                 d["min_pair_dist"] = summ[s]["min_center_dist"]["value"] if summ[s]["min_center_dist"] else np.inf

@@ -1,0 +1,125 @@
+"""Missions of the device fleet loop (include/neptune_fleet.h: nep_batch_fleet_mission): successive goals, timeouts and leg
+records.  MissionSpec carries the reference's values per mode — NeptuneRos::autoCMD (neptune_ros.cpp:1047-1102) and
+scripts/benchmark_mtlp.py:167-281 —, mission_cfg turns it into the C record for a scene's world, and HostMission is the host chain
+of nep_mission_step that the device is compared with byte for byte."""
+import ctypes as C
+import dataclasses
+
+import numpy as np
+
+from . import abi
+from ._lib import check, lib
+
+
+@dataclasses.dataclass
+class MissionSpec:
+    """mode "agent" (autoCMD) or "runs" (benchmark_mtlp); None takes the reference's value for the mode."""
+    mode: str = "agent"
+    goals: int = 2                    # legs per agent ("agent") or runs per scene ("runs")
+    seed: int = 1
+    max_attempts: int = 256
+    log_cap: int = 16
+    arrive_radius: float = None       # 0.5 m in both scripts
+    min_interval: float = None        # "agent": 5 s
+    timeout: float = None             # "agent": 45 s, "runs": 40 s
+    rest_v: float = None              # "agent": 0.1 m/s
+    rest_a: float = None              # "agent": 0.1 m/s^2
+    min_dist_self: float = None       # "agent": 5 m
+    tether_factor: float = None       # tether_max = factor * tether_length; "agent": 0.85, "runs": 1.0
+    shrink: float = None              # the world less this on every side; "agent": 3 * drone_radius, "runs": 4 m
+    close_range: float = None         # "runs": 3 m -> close_pos = close_range / 4, close_goal = close_range
+    keepouts: bool = None             # "agent": the scene's keep-out polygons (scene.keepout_polygons); "runs": none
+
+
+def mission_cfg(spec, par):
+    """MissionSpec + a scene's Params -> abi.nep_mission_cfg"""
+    if spec.mode not in ("agent", "runs"):
+        raise ValueError("mission mode must be 'agent' or 'runs'")
+    agent = spec.mode == "agent"
+    pick = lambda v, a, r: (a if agent else r) if v is None else v      # noqa: E731
+    shrink = pick(spec.shrink, 3.0 * par.drone_radius, 4.0)
+    close = pick(spec.close_range, 0.0, 3.0)
+    c = abi.nep_mission_cfg()
+    c.mode = abi.NEP_MISSION_PER_AGENT if agent else abi.NEP_MISSION_FLEET_RUNS
+    c.max_goals, c.max_attempts, c.log_cap, c.seed = spec.goals, spec.max_attempts, spec.log_cap, spec.seed
+    c.lo[0], c.lo[1], c.hi[0], c.hi[1] = par.x_min + shrink, par.y_min + shrink, par.x_max - shrink, par.y_max - shrink
+    c.goal_z = par.goal_height
+    c.arrive_radius = pick(spec.arrive_radius, 0.5, 0.5)
+    c.min_interval = pick(spec.min_interval, 5.0, 0.0)
+    c.timeout = pick(spec.timeout, 45.0, 40.0)
+    c.rest_v, c.rest_a = pick(spec.rest_v, 0.1, 0.0), pick(spec.rest_a, 0.1, 0.0)
+    c.min_dist_self = pick(spec.min_dist_self, 5.0, 0.0)
+    c.tether_max = pick(spec.tether_factor, 0.85, 1.0) * par.tether_length
+    c.close_pos, c.close_goal = close / 4.0, close
+    return c
+
+
+def uses_keepouts(spec):
+    return (spec.mode == "agent") if spec.keepouts is None else bool(spec.keepouts)
+
+
+def summarize(state, log_n, N, mode):
+    """per scene, from BatchBackend.fleet_mission_state(): legs (or runs) reached / timed out / without a goal, mean leg time and
+    length over the ended legs, the success rate"""
+    cnt = state["counts"].reshape(-1, N, 4); sums = state["sums"].reshape(-1, N, 2)
+    out = []
+    for s in range(cnt.shape[0]):
+        ended = int(cnt[s, :, 1].sum() + cnt[s, :, 2].sum())
+        d = dict(legs_issued=int(cnt[s, :, 0].sum()), legs_reached=int(cnt[s, :, 1].sum()), legs_timed_out=int(cnt[s, :, 2].sum()),
+                 no_goal=int(cnt[s, :, 3].sum()), mean_leg_time=float(sums[s, :, 0].sum() / ended) if ended else None,
+                 mean_leg_length=float(sums[s, :, 1].sum() / ended) if ended else None, finished=bool(state["scene"][s, 3]))
+        if mode == abi.NEP_MISSION_FLEET_RUNS:
+            ok, bad = int(state["scene"][s, 1]), int(state["scene"][s, 2])
+            d.update(runs=int(state["scene"][s, 0]), runs_succeeded=ok, runs_failed=bad, success_rate=ok / (ok + bad) if ok + bad else None)
+        else:
+            d["success_rate"] = d["legs_reached"] / ended if ended else None
+        out.append(d)
+    return out
+
+
+class HostMission:
+    """The mission state of S scenes of N agents in host arrays, moved by nep_mission_step — the host chain.  goals [S*N][3],
+    keepouts: per scene a list of counter-clockwise convex (n, 2) arrays."""
+
+    def __init__(self, cfg, S, N, pb, goals, t0=0.0, keepouts=None):
+        self.cfg, self.S, self.N = cfg, S, N
+        n = S * N
+        self.pb = np.ascontiguousarray(pb, dtype=np.float64).reshape(N, 2)
+        self.goal = np.ascontiguousarray(goals, dtype=np.float64).reshape(n, 3).copy()
+        self.done = np.zeros(n, dtype=np.int32); self.flags = np.zeros(n, dtype=np.int32)
+        self.t_issue = np.full(n, float(t0)); self.length = np.zeros(n); self.completed = np.zeros(n, dtype=np.int32)
+        self.counts = np.zeros((n, 4), dtype=np.int32); self.counts[:, 0] = 1
+        self.sums = np.zeros((n, 2))
+        self.scene = np.zeros((S, 4), dtype=np.int32); self.t_run = np.full(S, float(t0))
+        self.per_agent = cfg.mode == abi.NEP_MISSION_PER_AGENT
+        self.owners = n if self.per_agent else S
+        self.log = np.zeros((self.owners, max(int(cfg.log_cap), 1)), dtype=abi.MISSION_LEG_DTYPE)
+        self.log_n = np.zeros(self.owners, dtype=np.int32)
+        self.keep = []
+        for s in range(S):
+            polys = [] if keepouts is None else keepouts[s]
+            off = np.zeros(len(polys) + 1, dtype=np.int32)
+            for k, q in enumerate(polys):
+                off[k + 1] = off[k] + len(q)
+            xy = np.ascontiguousarray(np.concatenate([np.asarray(q, dtype=np.float64).reshape(-1, 2) for q in polys]) if len(polys) else np.zeros((1, 2)))
+            self.keep.append((len(polys), off, xy))
+
+    def step(self, pos, s_end, t_now, dc):
+        """one call for every scene: pos [S*N][T+1][3] tick positions, s_end [S*N][12], t_now [S] the scenes' clocks"""
+        N = self.N
+        pos = np.ascontiguousarray(pos, dtype=np.float64); s_end = np.ascontiguousarray(s_end, dtype=np.float64)
+        T = pos.shape[1] - 1
+        vp = lambda a, i0=0: a[i0:].ctypes.data      # noqa: E731
+        for s in range(self.S):
+            npoly, off, xy = self.keep[s]
+            lo = s * N
+            o = lo if self.per_agent else s
+            sc = abi.nep_mission_scene(N, s, T, npoly, float(t_now[s]), float(dc), vp(pos, lo), vp(s_end, lo), self.pb.ctypes.data, off.ctypes.data,
+                                       xy.ctypes.data, vp(self.goal, lo), vp(self.done, lo), vp(self.flags, lo), vp(self.t_issue, lo), vp(self.length, lo),
+                                       vp(self.completed, lo), vp(self.counts, lo), vp(self.sums, lo), vp(self.scene, s), vp(self.t_run, s),
+                                       vp(self.log, o), vp(self.log_n, o))
+            check(lib().nep_mission_step(C.byref(self.cfg), C.byref(sc)))
+
+    def state(self):
+        return dict(goal=self.goal, t_issue=self.t_issue, length=self.length, completed=self.completed, counts=self.counts, sums=self.sums,
+                    scene=self.scene, t_run=self.t_run)

@@ -607,3 +607,15 @@ def reachable_goals(sc, margin=0.4):
             if not moved:
                 break
     return goals
+
+
+def keepout_polygons(sc):
+    """The polygons a mission's goals must stay out of (NeptuneRos's inflatedStaticObsLarger_, neptune_ros.cpp:314-343): every
+    vertex of every un-inflated footprint moved by +-4*drone_radius in x and y, then the hull, counter-clockwise."""
+    d = 4.0 * sc["par"].drone_radius
+    out = []
+    for raw in sc["statics_raw"]:
+        v = np.asarray(raw, dtype=np.float64).reshape(-1, 2)
+        pts = np.concatenate([v + np.array([sx * d, sy * d]) for sx in (-1.0, 1.0) for sy in (-1.0, 1.0)])
+        out.append(hull_ccw_lexmin(pts))
+    return out

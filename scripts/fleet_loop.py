@@ -7,6 +7,9 @@ stats), the totals, the wall time per round and, with --audit, the worst clearan
 
   python scripts/fleet_loop.py --agents 64 --obstacles 20 --scenes 128 --rounds 30 [--stagger 5] [--audit] [--host] [--tethers [--no-check]]
 
+--missions {agent,runs} --goals G: fleet_mission joins the round before fleet_tick and flies a campaign of G goals per agent (runs per
+scene); the report gains the legs' accounts.
+
 --stagger P: every agent replans every P-th round, agent a in the rounds with (round - a) mod P == 0, and a round flies one control
 tick (FleetLoop's cadence at P = 5 with the agents' timers spread over the ticks).  --host flies scene 0 with FleetLoop as well and
 prints its wall time per round next to the device loop's (one scene each)."""
@@ -33,6 +36,8 @@ def main():
     ap.add_argument("--tethers", action="store_true", help="tethered agents: entangle states tracked per control tick, predicted at A, checked by the front end and the safety pass")
     ap.add_argument("--no-check", action="store_true", help="with --tethers: plain front end and safety pass, the tracking stays on")
     ap.add_argument("--no-proof", action="store_true", help="with --tethers: debug option fleet_ent_proof 0 (every other agent walked at every tick)")
+    ap.add_argument("--missions", choices=("agent", "runs"), help="a campaign (DESIGN section 23): per-agent successive goals (NeptuneRos::autoCMD) or fleet-wide runs (benchmark_mtlp.py), drawn on the device inside the graph; the flight stops when every scene's campaign is over")
+    ap.add_argument("--goals", type=int, default=2, metavar="G", help="with --missions: legs per agent / runs per scene")
     ap.add_argument("--host", action="store_true", help="also fly scene 0 with FleetLoop and with DeviceFleetLoop(S = 1): wall time per round of both")
     a = ap.parse_args()
     import numpy as np
@@ -44,6 +49,9 @@ def main():
     kw = dict(beam_width=a.beam, audit=a.audit, graph=not a.eager)
     if a.tethers:
         kw.update(tethers=True, check=not a.no_check)
+    if a.missions:
+        from neptune_amd import mission
+        kw.update(missions=mission.MissionSpec(a.missions, goals=a.goals, seed=a.seed0 + 1))
     if a.stagger > 0:
         kw.update(replan_every=1, periods=a.stagger, phases=np.tile(np.arange(a.agents) % a.stagger, (a.scenes, 1)))
 
@@ -76,8 +84,14 @@ def main():
     if a.tethers:
         tot.update({k: int(sum(r[k] for r in rep)) for k in ("ever_entangled", "too_long", "track_cap")})
     print("total over %d scenes x %d agents, %d rounds: %s" % (a.scenes, a.agents, n, json.dumps(tot)))
-    print("wall time per round (rounds 3..%d, %s, arrival flags downloaded every round): %.3f ms = %.1f rounds/s, %.0f scene-rounds/s"
-          % (n, "eager" if a.eager else "one graph", per_round * 1e3, 1.0 / per_round, a.scenes / per_round))
+    if a.missions:
+        ms = [r["mission"] for r in rep]
+        ended = sum(m["legs_reached"] + m["legs_timed_out"] for m in ms)
+        print("missions (%s, %d goals): legs issued %d, reached %d, timed out %d, no goal %d; share reached %s; scenes finished %d of %d"
+              % (a.missions, a.goals, sum(m["legs_issued"] for m in ms), sum(m["legs_reached"] for m in ms), sum(m["legs_timed_out"] for m in ms),
+                 sum(m["no_goal"] for m in ms), "%.3f" % (sum(m["legs_reached"] for m in ms) / ended) if ended else "-", sum(m["finished"] for m in ms), len(ms)))
+    print("wall time per round (rounds 3..%d, %s, %s downloaded every round): %.3f ms = %.1f rounds/s, %.0f scene-rounds/s"
+          % (n, "eager" if a.eager else "one graph", "the scenes' finished flags" if a.missions else "arrival flags", per_round * 1e3, 1.0 / per_round, a.scenes / per_round))
     if a.audit:
         for line in audit.format_summary([r["audit"] for r in rep]):
             print(line)
