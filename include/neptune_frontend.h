@@ -215,7 +215,11 @@ int nep_batch_safety_commit_ent(nep_batch_t* h, const nep_traj_rec* d_prev, cons
  * NEP_FE_ENT_CAP crossings or NEP_MAX_BEND - 1 bend points, or a step with more than NEP_ENT_TRACK_ADD_CAP new crossings,
  * keeps the state before that step: NEP_ENT_TRACK_CAP in d_flags and NEP_E_CAP from nep_batch_check; nothing is written past
  * the record.  Bit-identical to chaining nep_ent_track_step on the host.  Unsharded handles created with enable_entangle
- * only (else NEP_E_STATE).  Asynchronous; the first call allocates per-slot scratch, later ones nothing: capturable.    
+ * only (else NEP_E_STATE); NEP_E_CAP beyond 4096 agents or 2048 static obstacles per scene.  Asynchronous; the first call
+ * allocates per-slot scratch, sized for the largest call, later ones nothing: capturable.
+ * A tracked slot's state comes back with id / cs / beta beyond n_alpha and bend beyond n_bend ZEROED (the bytes of a state
+ * depend on the state alone, as with nep_batch_fleet_track_ent, whose kernel this call runs); earlier versions left there
+ * what the list surgery had left.  Nothing reads those entries.  The debug option fleet_ent_proof applies (same states).
  * (The faithful fleet loop tracks per control tick instead: nep_batch_fleet_track_ent, include/neptune_fleet.h.)              */
 int nep_batch_track_ent(nep_batch_t* h, const nep_traj_rec* d_prev, nep_traj_rec* d_records, const nep_guess* d_guess,
                         int32_t n_intervals, int32_t ent_samples, double cable_length, nep_fe_ent_state* d_ent,

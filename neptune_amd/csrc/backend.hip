@@ -142,7 +142,7 @@ struct Engine {
   DevBuf<int> d_order, d_order_key; bool have_history = false, lpt = true, last_ordered = false;   // QP workgroups launched longest-expected-first (order_kernel)
   const int* active = nullptr;       // the active set (nep_batch_set_active): device [scenes][N], or null
   DevBuf<int> d_act, d_fe_act;       // [slots + 1] compacted active slots + count (active_list_kernel): the QP launches', the front end's
-  DevBuf<nep_fe_ent_state> d_track_save; DevBuf<int> d_track_flags;      // nep_batch_track_ent: per-slot scratch, flags when the caller passes none
+  DevBuf<nep_fe_ent_state> d_track_save; DevBuf<int> d_track_flags; DevBuf<double> d_track_pos;      // nep_batch_track_ent: per-slot scratch, flags when the caller passes none, the positions of the largest call
   DevBuf<AuditPart> d_audit_part;      // nep_batch_audit: per (scene, run of ticks, agent) minima, sized once for the most runs a call can have
   int static_nv_max = 0;               // most vertices of a static polygon uploaded so far (nep_batch_audit's LDS stride)
   DevBuf<nep_traj_rec> d_safety_recs;      // [scenes][N] the records an active-set safety pass judges (select_records_kernel)
@@ -1416,18 +1416,26 @@ int nep_batch_track_ent(nep_batch_t* h, const nep_traj_rec* d_prev, nep_traj_rec
   Engine& E = h->eng;
   const int N = h->cfg.num_agents, S = h->cfg.n_scenes, np = h->cfg.num_pol;
   if (int e = ent_ready(h, "tether tracking with static obstacles needs nep_batch_set_static_reps first")) return e;
+  if (!fleet_ent_fits(N, E.sp.n_static)) return fail(NEP_E_CAP, "the tether kernels take up to 4096 agents and 2048 static obstacles per scene");
   const ProblemSet ps = round_set(h);
   if (int e = E.d_sampled.ensure((size_t)S * N * np * (ent_samples + 1) * 2)) return e;
   if (int e = E.d_present.ensure((size_t)S * N)) return e;
   if (int e = E.d_track_save.ensure((size_t)S * N)) return e;
   if (int e = E.d_track_flags.ensure((size_t)S * N)) return e;      // (whether or not this call passes d_flags: a later captured call may not)
+  if (int e = E.d_track_pos.ensure((size_t)S * N * ((size_t)np * 8 + 1) * 2)) return e;      // (the largest call's: a later captured one may fly more steps)
   launch_ent_sample(d_records, S, N, &d_guess->t_start, (long)sizeof(nep_guess) * h->cfg.n_local, np, ent_samples, E.sp.T_span, E.d_sampled.p, E.d_present.p,
                     (hipStream_t)stream, nullptr);
-  TrackArgs ta{};
-  ta.N = N; ta.S = E.sp.n_static; ta.n_scenes = S; ta.num_pol = np; ta.ns = ent_samples; ta.n_iv = n_intervals; ta.static_stride = E.sp.static_stride;
-  ta.cable = cable_length; ta.pb = ps.pb; ta.srep = E.d_srep.p; ta.slong = E.d_slong.p; ta.sampled = E.d_sampled.p; ta.present = E.d_present.p;
-  ta.prev = d_prev; ta.recs = d_records; ta.ent = d_ent; ta.save = E.d_track_save.p; ta.flags = d_flags ? d_flags : E.d_track_flags.p; ta.gflags = ps.flags;
-  launch_ent_track(ta, (hipStream_t)stream);
+  // the round's sampled steps side by side, the moves on them (the other agents' lists at the previous check: the previous round's
+  // records), then the bend points of the states just tracked into the flown records
+  TetherArgs ea{};
+  ea.N = N; ea.S = E.sp.n_static; ea.n_scenes = S; ea.static_stride = E.sp.static_stride; ea.num_pol = np; ea.ns = ent_samples;
+  ea.n_steps = n_intervals * ent_samples; ea.proof = E.opt_fleet_ent_proof; ea.skip_absent = 1; ea.cable = cable_length; ea.T_span = E.sp.T_span;
+  ea.pb = ps.pb; ea.srep = E.d_srep.p; ea.slong = E.d_slong.p; ea.pos = E.d_track_pos.p; ea.sampled = E.d_sampled.p;
+  ea.recs = d_records; ea.recs_out = d_records;
+  ea.prev_n = (const char*)&d_prev->n_bend; ea.prev_xy = (const char*)&d_prev->bend[0][0]; ea.prev_n_stride = ea.prev_xy_stride = (long)sizeof(nep_traj_rec);
+  ea.in = d_ent; ea.out = d_ent; ea.save = E.d_track_save.p; ea.flags = d_flags ? d_flags : E.d_track_flags.p; ea.gflags = ps.flags;
+  launch_tether_steps(ea, FleetArgs{}, (hipStream_t)stream);
+  launch_tether_publish(ea, false, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1472,12 +1480,13 @@ void fleet_args(nep_batch_t* h, FleetArgs& fa) {
   fa.period = F.timers ? F.period.p : nullptr; fa.phase = F.timers ? F.phase.p : nullptr;
   fa.t_now = F.t_now.p; fa.round = F.round.p; fa.counters = F.counters.p; fa.gflags = h->eng.d_flags.p; fa.active = h->eng.active;
 }
-void fleet_ent_args(nep_batch_t* h, FleetEntArgs& ea) {
+void fleet_ent_args(nep_batch_t* h, TetherArgs& ea) {
   nep_batch::Fleet& F = h->fleet; Engine& E = h->eng;
   ea.N = h->cfg.num_agents; ea.S = E.sp.n_static; ea.n_scenes = h->cfg.n_scenes; ea.static_stride = E.sp.static_stride; ea.num_pol = h->cfg.num_pol;
   ea.n_steps = F.cfg.round_ticks; ea.proof = E.opt_fleet_ent_proof; ea.cable = F.cable; ea.T_span = E.sp.T_span;
   ea.pb = E.d_pb.p; ea.srep = E.d_srep.p; ea.slong = E.d_slong.p; ea.pos = F.ent_pos.p;
   ea.pub_n = F.pub_n.p; ea.pub_xy = F.pub_xy.p; ea.pub_prev_n = F.pub_prev_n.p; ea.pub_prev_xy = F.pub_prev_xy.p;
+  ea.prev_n = (const char*)F.pub_prev_n.p; ea.prev_n_stride = (long)sizeof(int); ea.prev_xy = (const char*)F.pub_prev_xy.p; ea.prev_xy_stride = (long)sizeof(double) * NEP_MAX_BEND * 2;
   ea.in = F.ent.p; ea.out = F.ent.p; ea.save = F.ent_save.p; ea.flags = F.ent_flags.p; ea.ever = F.ent_ever.p; ea.walked = F.ent_walked.p;
   ea.counters = F.counters.p; ea.gflags = E.d_flags.p;
 }
@@ -1527,10 +1536,10 @@ int nep_batch_fleet_select(nep_batch_t* h, nep_fe_start* d_start, nep_traj_rec* 
   fa.start = d_start; fa.recs = d_records; fa.active_out = d_active; fa.clock = d_clock;
   launch_fleet_select(fa, (hipStream_t)stream);
   if (h->fleet.ent_ready) {      // the tethered fleet publishes its bend points (publishOwnTraj)
-    FleetEntArgs ea{};
+    TetherArgs ea{};
     fleet_ent_args(h, ea);
     ea.recs = d_records; ea.recs_out = d_records;
-    launch_fleet_ent_publish(ea, (hipStream_t)stream);
+    launch_tether_publish(ea, true, (hipStream_t)stream);
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -1574,11 +1583,11 @@ int nep_batch_fleet_predict_ent(nep_batch_t* h, const nep_fe_start* d_start, con
   if (!d_start || !d_records || !d_ent_a) return fail(NEP_E_ARG, "null argument");
   FleetArgs fa{};
   fleet_args(h, fa);
-  FleetEntArgs ea{};
+  TetherArgs ea{};
   fleet_ent_args(h, ea);
   ea.n_steps = 1; ea.start = d_start; ea.recs = d_records; ea.out = d_ent_a; ea.flags = d_flags_a ? d_flags_a : h->fleet.ent_flags_a.p;
-  ea.pub_prev_n = nullptr; ea.pub_prev_xy = nullptr; ea.ever = nullptr; ea.walked = nullptr; ea.counters = nullptr;
-  launch_fleet_ent_steps(ea, fa, (hipStream_t)stream);
+  ea.prev_n = nullptr; ea.prev_xy = nullptr; ea.ever = nullptr; ea.walked = nullptr; ea.counters = nullptr;
+  launch_tether_steps(ea, fa, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1589,11 +1598,11 @@ int nep_batch_fleet_track_ent(nep_batch_t* h, const nep_traj_rec* d_records, int
   if (!d_records) return fail(NEP_E_ARG, "null argument");
   FleetArgs fa{};
   fleet_args(h, fa);
-  FleetEntArgs ea{};
+  TetherArgs ea{};
   fleet_ent_args(h, ea);
   ea.n_steps = h->fleet.cfg.round_ticks; ea.start = nullptr; ea.recs = d_records; ea.out = h->fleet.ent.p;
   ea.flags = d_flags ? d_flags : h->fleet.ent_flags.p;
-  launch_fleet_ent_steps(ea, fa, (hipStream_t)stream);
+  launch_tether_steps(ea, fa, (hipStream_t)stream);
   if (d_flags) HIPCHK(hipMemcpyAsync(h->fleet.ent_flags.p, d_flags, (size_t)h->slots * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   HIPCHK(hipGetLastError());
   return 0;

@@ -6,11 +6,14 @@
 // getTetherLength (:1649-1743), getIz / power_int (kinodynamic_search.cpp:2006-2031).  One thread carries one node: the
 // crossing list lives in a fixed-size record (nep_fe_ent_state, NEP_FE_ENT_CAP entries) in global memory; active_cases[i]
 // is the number of list entries of agent i and is derived.  Written in the association order of the CPU checker under
-// oracle/ (this header is only included by geom_kernels.hip, which is built -ffp-contract=off): betas match bit for bit.
+// oracle/ (this header is included by geom_kernels.hip and tether_kernels.hip, both built -ffp-contract=off): betas match bit for bit.
+// The tracking of a tether between checks (tether_kernels.hip) shares the crossing tests and the list surgery, and has its one
+// move, its validity test and its published bend point here: ent_track_move, ent_state_ok, ent_publish_point.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "nep_device.h"
+#include "../../include/neptune_entangle.h"
 
 namespace nep {
 
@@ -219,7 +222,7 @@ template <class ADD, class BP = const double*> __device__ __forceinline__ void e
   if (base_addition && add.n >= 2 && ((add.get(add.n - 1) ^ add.get(add.n - 2)) & 0xffffffu) == 0u) add.n -= 2;      // (same id, same case)
 }
 // eu::entangleHSigToAddAgentInd's nine-argument form (entangle_utils.cpp:820-1127), taken when agent_id's bend-point count changed
-// since the previous check (tracking between rounds, ent_track_kernel): b[0..nb) its bend points now, q[0..nq) at the previous
+// since the previous check (tracking between rounds and ticks, tether_step_kernel): b[0..nb) its bend points now, q[0..nq) at the previous
 // check.  The crossings carry the CURRENT count (the merge reads it).  Returns true where the reference pushes a crossing and then
 // stops the process (exit(-1)).  Restated branch for branch by crossings_agent_changed in entangle_host.cpp.
 template <class ADD> __device__ bool ent_cross_agent_changed(ADD& add, Ev2 pk, Ev2 pk1, Ev2 pik, Ev2 pik1, Ev2 pb, int nb, const double* b, int nq, const double* q, int agent_id) {
@@ -496,6 +499,42 @@ template <class ST> __device__ double ent_tether(const ST* st, Ev2 from, Ev2 pk1
   return len + ent_dist(pk1, from);
 }
 template <class P> __device__ __forceinline__ int ent_count(P ids, int n, int id) { int k = 0; for (int i = 0; i < n; i++) k += ids[i] == id; return k; }
+
+// ---- Tracking a tether between checks (tether_kernels.hip): NeptuneRos::odomCB -> updateEntStateStaticObs (neptune_ros.cpp:781-850)
+// and publishOwnTraj's bend points (:457-476).
+// a state is valid input to the tracking: counts within the fixed record and the bend points a record publishes, bend indices on the list
+__device__ bool ent_state_ok(const nep_fe_ent_state* st) {
+  if (st->n_alpha < 0 || st->n_alpha > NEP_FE_ENT_CAP || st->n_bend < 0 || st->n_bend > NEP_MAX_BEND - 1) return false;
+  for (int k = 0; k < st->n_bend; k++) if (st->bend[k] < 0 || st->bend[k] >= st->n_alpha) return false;
+  return true;
+}
+// One tracked move pk -> pk1 of the state W (nep_ent_track_step, entangle_host.cpp, is the host restatement): `add` holds the crossings
+// the caller collected for the move, `abort` what ent_cross_agent_changed returned for them.  save() runs before a move that can
+// outgrow the record and restore() when it did; such a move is dropped, as is one with more new crossings than `add` takes.
+// -> the move's NEP_ENT_TRACK_* bits.
+template <class ST, class SAVE, class RESTORE>
+__device__ __forceinline__ int ent_track_move(EntAdd& add, ST* W, SAVE save, RESTORE restore, Ev2 pk, Ev2 pk1, Ev2 pb_self, const EntCtx& c, double cable, bool abort) {
+  if (add.overflow) return NEP_ENT_TRACK_CAP;
+  if (add.n > 0 || W->n_bend >= NEP_MAX_BEND - 1) save();
+  bool over = add.n > 0 && ent_merge(add, W, pk, pb_self, c);
+  if (!over) { over = ent_update_bends(W, pk1, pb_self, c); over |= W->n_bend > NEP_MAX_BEND - 1; }
+  if (over) { restore(); return NEP_ENT_TRACK_CAP; }
+  int fl = abort ? NEP_ENT_TRACK_ABORT : 0;
+  for (int e = 0; e < W->n_alpha; e++) {      // active_cases of the agents: entries per id
+    const int id_ = W->id[e];
+    if (id_ > c.N) continue;
+    const int k = ent_count(W->id, W->n_alpha, id_);
+    if (k > 2) fl |= NEP_ENT_TRACK_ENTANGLED;
+    if (k >= 2) fl |= NEP_ENT_TRACK_TWO_CASES;
+  }
+  if (ent_tether(W, pb_self, pk1, c) > cable) fl |= NEP_ENT_TRACK_TOO_LONG;
+  return fl;
+}
+// the bend point a record publishes for list entry (id, cs): its anchor, or (0, 0) for an entry that names nobody (c: N, S, pb, srep)
+__device__ __forceinline__ Ev2 ent_publish_point(int id, int cs, const EntCtx& c) {
+  const bool named = id >= 1 && (id <= c.N || (id - c.N - 1 < c.S && (cs == 0 || cs == 1)));
+  return named ? ent_anchor(id, cs, c) : Ev2{0.0, 0.0};
+}
 
 // 0: fine; 1: the reference's function returns true (prune); 2, 3, 4: a capacity exceeded (pruned, flagged; which one: see the returns)
 // (ADD, store: the form of the list of a step's new crossings and its storage — EntAdd with its tail, or EntAddBig on a big record)

@@ -233,23 +233,6 @@ void launch_frontend(int n_slots, const SceneParams& sp, const ProblemSet& ps, c
                      int* active_buf = nullptr);      // (active_buf: [slots + 1] for the active list when ps.active is set)
 void launch_ent_sample(const nep_traj_rec* recs, int n_scenes, int N, const double* ts0, long ts_scene_stride, int num_pol, int ns, double T_span,
                        double* sampled, int* present, hipStream_t st, int* zero_this = nullptr);
-// nep_batch_track_ent (track_kernels.hip): one round's tracking of every tether and the published bend points
-struct TrackArgs {
-  int N, S, n_scenes, num_pol, ns, n_iv, static_stride;
-  double cable;
-  const double* pb;              // [N][2]
-  const double* srep;            // [scenes or 1][S][2][2]
-  const double* slong;           // [scenes or 1][S][2]
-  const double* sampled;         // [scenes][N][num_pol][ns+1][2] every record sampled on the round's grid (ent_sample_kernel)
-  const int* present;            // [scenes][N]
-  const nep_traj_rec* prev;      // [scenes][N] the previous round's records (bend points at the previous check)
-  nep_traj_rec* recs;            // [scenes][N] the round's records (flown; bend points published into them)
-  nep_fe_ent_state* ent;         // [scenes][N] in: the state at this round's A; out: at the next one's
-  nep_fe_ent_state* save;        // [scenes][N] scratch: the state before a step that may outgrow the record
-  int* flags;                    // [scenes][N] NEP_ENT_TRACK_* bits of the round
-  int* gflags;                   // sticky NEP_FLAG_ENT_TRACK
-};
-void launch_ent_track(const TrackArgs& ta, hipStream_t st);
 // nep_batch_audit (audit_kernels.hip): the minima of one (scene, run of ticks, agent), ticks as indices of the call
 struct AuditPart { double c_d2, box, stat; int c_k, c_p, b_k, b_p, s_k, s_i, n_pair, n_stat; };
 struct AuditArgs {
@@ -309,33 +292,40 @@ struct FleetMissionArgs {
 size_t mission_lds_bytes(int N, int n_vert, int n_poly);
 void launch_fleet_mission_seed(const FleetMissionArgs& ma, const FleetArgs& fa, hipStream_t st);
 void launch_fleet_mission(const FleetMissionArgs& ma, const FleetArgs& fa, hipStream_t st);
-// the tethers of the fleet state (fleet_ent_kernels.hip): nep_batch_fleet_select's bend points, _predict_ent, _track_ent
-struct FleetEntArgs {
+// the tethers' entangle states (tether_kernels.hip): nep_batch_track_ent between two rounds; on the fleet state nep_batch_fleet_select's
+// bend points, _predict_ent, _track_ent
+struct TetherArgs {
   int N, S, n_scenes, static_stride, num_pol;
-  int n_steps;                   // moves of the call: round_ticks (tracking) or 1 (prediction)
+  int n_steps;                   // moves of the call: n_intervals * ns (between rounds), round_ticks (the fleet's tracking) or 1 (prediction)
   int proof;                     // 0: every other agent and static is walked at every step (debug option fleet_ent_proof)
+  int skip_absent;               // 1 (between rounds): a slot whose own record holds no trajectory gets flags 0 and keeps its state
+  int ns;                        // with `sampled`: steps per interval
   double cable, T_span;
   const double* pb;              // [N][2]
   const double* srep;            // [scenes or 1][S][2][2]
   const double* slong;           // [scenes or 1][S][2]
-  double* pos;                   // [slots][n_steps + 1][2] scratch: every slot's positions of the call (fleet_ent_pos_kernel)
+  double* pos;                   // [slots][n_steps + 1][2] scratch: every slot's positions of the call (tether_pos_kernel)
+  const double* sampled;         // between rounds: [slots][num_pol][ns + 1][2], every record on the round's grid (ent_sample_kernel); else null
   const nep_fe_start* start;     // prediction: [slots] point A and the clock; null: tracking
   const nep_traj_rec* recs;      // [slots] the records published this round
-  nep_traj_rec* recs_out;        // select: the records the bend points are published into
+  nep_traj_rec* recs_out;        // the publish kernels: the records the bend points are published into
   int* pub_n; double* pub_xy;              // [slots], [slots][NEP_MAX_BEND][2] the list published at the last select
-  int* pub_prev_n; double* pub_prev_xy;    // and the one before it (the step kernel: null for a prediction)
+  int* pub_prev_n; double* pub_prev_xy;    // and the one before it (the fleet's publish kernel rotates the two)
+  // the step kernel: every slot's bend list at the previous check, count and points a byte stride apart — the fleet's pub_prev_*, or
+  // the previous round's records between rounds; null for a prediction
+  const char* prev_n; const char* prev_xy; long prev_n_stride, prev_xy_stride;
   const nep_fe_ent_state* in;    // [slots] the state at the tracked position
   nep_fe_ent_state* out;         // [slots] tracking: the same buffer; prediction: the state at A
   nep_fe_ent_state* save;        // [slots] scratch: the state before a step that may outgrow the record
   int* flags;                    // [slots] NEP_ENT_TRACK_* bits of the call
-  int* ever;                     // [slots] sticky OR (tracking) or null
-  int* walked;                   // [slots] (other agent, step) pairs walked, accumulated (tracking) or null
+  int* ever;                     // [slots] sticky OR (the fleet's tracking) or null
+  int* walked;                   // [slots] (other agent, step) pairs walked, accumulated (the fleet's tracking) or null
   int* counters;                 // [scenes][NEP_FLEET_N_COUNTERS]: [7] = slots ever flagged NEP_ENT_TRACK_ENTANGLED
   int* gflags;                   // sticky NEP_FLAG_ENT_TRACK
 };
 bool fleet_ent_fits(int N, int S);
-void launch_fleet_ent_publish(const FleetEntArgs& ea, hipStream_t st);
-void launch_fleet_ent_steps(const FleetEntArgs& ea, const FleetArgs& fa, hipStream_t st);
+void launch_tether_publish(const TetherArgs& ea, bool fleet, hipStream_t st);      // (fleet: nep_batch_fleet_select's contract, else nep_batch_track_ent's)
+void launch_tether_steps(const TetherArgs& ea, const FleetArgs& fa, hipStream_t st);      // (fa: read by the fleet's two position modes only)
 void launch_ent_check(const SceneParams& sp, const ProblemSet& ps, const FeEntArgs& ea, const nep_traj_rec* fresh, int n_scenes, double cable, int* entangles, hipStream_t st);
 void launch_next_starts(const nep_traj_rec* recs, int n_scenes, int N, int first_local, int n_local, double dt, nep_fe_start* starts,
                         double* alt, double r_switch, hipStream_t st);

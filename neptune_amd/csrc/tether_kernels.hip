@@ -1,16 +1,17 @@
-// fleet_ent_kernels.hip — the tethers of the device fleet loop (nep_batch_fleet_init_ent / _predict_ent / _track_ent and the bend
-// points nep_batch_fleet_select publishes; include/neptune_fleet.h).
+// tether_kernels.hip — every tether's entangle state carried along what its agent flies: between two bulk-synchronous rounds
+// (nep_batch_track_ent, include/neptune_frontend.h) and in the device fleet loop (nep_batch_fleet_init_ent / _predict_ent /
+// _track_ent and the bend points nep_batch_fleet_select publishes; include/neptune_fleet.h).
 //
-// Two steps of the reference on the fleet state of fleet_kernels.hip:
-//   NeptuneRos::odomCB -> updateEntStateStaticObs (neptune_ros.cpp:781-850) once per control tick the round flies, and
+// Two steps of the reference:
+//   NeptuneRos::odomCB -> updateEntStateStaticObs (neptune_ros.cpp:781-850) once per sampled step or control tick flown, and
 //   Neptune::PredictAlphasBetas (neptune.cpp:976-1008): the state forwarded to point A in one move, into a copy.
-// Both are chains of nep_ent_track_step (entangle_host.cpp), which the kernels equal bit for bit: the crossing tests, the list
-// surgery, the bend-point update and the tether length are ent_device.h's, and this file is built -ffp-contract=off like
-// track_kernels.hip.
+// Both are chains of nep_ent_track_step (entangle_host.cpp), which the step kernel equals bit for bit: the crossing tests, the list
+// surgery, one tracked move and the tether length are ent_device.h's, and this file is built -ffp-contract=off like
+// geom_kernels.hip.  publishOwnTraj's bend points (:457-476) have a kernel per entry point: the two contracts differ.
 //
 // Layout: one wave (one 64-thread workgroup) per slot.  A pre-kernel writes every slot's positions of the call side by side
-// (round_ticks + 1 of them, or the pair a prediction needs), so nobody strides through the plan rings.  The 64 lanes then take the
-// other agents 64 at a time and each PROVES that its agent adds no crossing at any step of the call (ent_side on the box of the
+// (the round's sampled steps, round_ticks + 1 tick positions, or the pair a prediction needs), so nobody strides through the
+// samples or the plan rings.  The 64 lanes then take the other agents 64 at a time and each PROVES that its agent adds no crossing at any step of the call (ent_side on the box of the
 // slot's own positions: the same side of every tether segment, of the moving last segment at every tick, and the sweep over our base
 // evaluated as is — ent_agent_may_cross's argument over ticks instead of samples); the statics likewise.  What the __ballot leaves
 // is walked by lane 0 step by step and in increasing index, so the crossings enter the list in the host chain's order.  The working
@@ -28,11 +29,12 @@
 namespace nep {
 
 static_assert(kEntAddCap == NEP_ENT_TRACK_ADD_CAP, "nep_ent_track_step's and the kernel's caps on a move's new crossings differ");
+static_assert(kEntAddCap <= 32, "EntAdd's cancellation bits are one 32-bit word");
 static_assert(sizeof(nep_fe_ent_state) % 4 == 0, "the state is copied in 4-byte units");
 
 namespace {
 
-constexpr int kMaskWords = 64;      // 64-bit ballot words of the candidates' mask: up to 4096 agents (FleetEntArgs is refused beyond)
+constexpr int kMaskWords = 64;      // 64-bit ballot words of the candidates' mask: up to 4096 agents (fleet_ent_fits: refused beyond)
 constexpr int kStatWords = 64;      // 32-bit words of the statics' mask (EntCtx::m_static): up to 2048 statics
 
 typedef __attribute__((address_space(3))) double* ent_lds_double;
@@ -40,25 +42,36 @@ typedef __attribute__((address_space(3))) double* ent_lds_double;
 // fixed record: every byte of the result is compared with the host chain.
 struct EntWork { int n_alpha, n_bend; ent_lds_short id; ent_lds_char cs; ent_lds_double beta; ent_lds_char bend; };
 
-__device__ bool fleet_state_ok(const nep_fe_ent_state* st) {
-  if (st->n_alpha < 0 || st->n_alpha > NEP_FE_ENT_CAP || st->n_bend < 0 || st->n_bend > NEP_MAX_BEND - 1) return false;
-  for (int k = 0; k < st->n_bend; k++) if (st->bend[k] < 0 || st->bend[k] >= st->n_alpha) return false;
-  return true;
-}
 __device__ __forceinline__ int rec_nb(const nep_traj_rec* r) { return min(max(r->n_bend, 0), NEP_MAX_BEND); }
 __device__ __forceinline__ bool rec_present(const nep_traj_rec* r) { return r->valid && r->is_agent && r->pwp.n_seg >= 1; }      // (ent_sample_kernel's rule)
+// the bend list agent i showed at the previous check (TetherArgs::prev_n / prev_xy)
+__device__ __forceinline__ int prev_nb(const TetherArgs& ea, long i) { return min(max(*(const int*)(ea.prev_n + i * ea.prev_n_stride), 0), NEP_MAX_BEND); }
+__device__ __forceinline__ const double* prev_bends(const TetherArgs& ea, long i) { return (const double*)(ea.prev_xy + i * ea.prev_xy_stride); }
+// what the publish kernels read of EntCtx (ent_publish_point)
+__device__ __forceinline__ EntCtx publish_ctx(const TetherArgs& ea, int scene) {
+  EntCtx ec{};
+  ec.N = ea.N; ec.S = ea.S; ec.pb = ea.pb; ec.srep = ea.srep + (long)scene * ea.static_stride * 4;
+  return ec;
+}
 
-// One thread per (slot, position).  Tracking (start == null): position q of a slot is where it stands after tick q of the round —
+// One thread per (slot, position).  Between rounds (sampled != null): position q = itv * ns + j of a slot is ent_sample_kernel's
+// sample j of interval itv, q = 0 the first sample of all — the end of an interval stands for the start of the next one.  The fleet's
+// tracking (start == null): position q of a slot is where it stands after tick q of the round —
 // q = 0 the tracked state, q >= 1 ring[(head + min(q - 1, size - 1)) mod cap], fleet_tick_kernel's pop rule.  Prediction: position 0
 // is the tracked state, position 1 the published record at the slot's t_start by nep_ent_sample_points' first sample (the front end's
 // sampled[i][0][0]).
-__global__ void fleet_ent_pos_kernel(FleetEntArgs ea, FleetArgs fa) {
+__global__ void tether_pos_kernel(TetherArgs ea, FleetArgs fa) {
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const int np = ea.n_steps + 1;
   if (e >= (long)ea.n_scenes * ea.N * np) return;
   const long slot = e / np; const int q = (int)(e - slot * np);
   double x, y;
-  if (q == 0) { x = fa.state[slot * 12]; y = fa.state[slot * 12 + 1]; }
+  if (ea.sampled) {
+    const int itv = q == 0 ? 0 : (q - 1) / ea.ns, col = q == 0 ? 0 : (q - 1) % ea.ns + 1;
+    const double* g = ea.sampled + ((slot * ea.num_pol + itv) * (ea.ns + 1) + col) * 2;
+    x = g[0]; y = g[1];
+  }
+  else if (q == 0) { x = fa.state[slot * 12]; y = fa.state[slot * 12 + 1]; }
   else if (!ea.start) {
     const int size = fa.size[slot], head = fa.head[slot];
     if (size < 1) { x = fa.state[slot * 12]; y = fa.state[slot * 12 + 1]; }
@@ -93,9 +106,9 @@ __global__ void fleet_ent_pos_kernel(FleetEntArgs ea, FleetArgs fa) {
 }
 
 // publishOwnTraj's bend points (neptune_ros.cpp:457-476) at the select: the list published at the last select becomes the previous
-// one, and the record gets the base and the anchor of every bend index of the state at the tracked position (ent_publish_kernel's
-// rule).  One thread per slot, after fleet_select_kernel has written the record.
-__global__ void fleet_ent_publish_kernel(FleetEntArgs ea) {
+// one, and the record gets the base and the anchor of every bend index of the state at the tracked position; an invalid state
+// publishes the base alone.  One thread per slot, after fleet_select_kernel has written the record.
+__global__ void fleet_ent_publish_kernel(TetherArgs ea) {
   const long slot = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const int N = ea.N;
   if (slot >= (long)ea.n_scenes * N) return;
@@ -104,17 +117,14 @@ __global__ void fleet_ent_publish_kernel(FleetEntArgs ea) {
   for (int k = 0; k < NEP_MAX_BEND * 2; k++) prv[k] = cur[k];
   ea.pub_prev_n[slot] = ea.pub_n[slot];
   const nep_fe_ent_state* st = ea.in + slot;
-  const double* srep = ea.srep + (long)scene * ea.static_stride * 4;
+  const EntCtx ec = publish_ctx(ea, scene);
   nep_traj_rec* r = ea.recs_out + slot;
   int nb = 1;
   cur[0] = ea.pb[2 * a]; cur[1] = ea.pb[2 * a + 1];
-  if (fleet_state_ok(st)) {
+  if (ent_state_ok(st)) {
     for (int k = 0; k < st->n_bend; k++) {
-      const int id = st->id[st->bend[k]], cs = st->cs[st->bend[k]];
-      double x = 0.0, y = 0.0;
-      if (id >= 1 && id <= N) { x = ea.pb[2 * (id - 1)]; y = ea.pb[2 * (id - 1) + 1]; }
-      else if (id > N && id - N - 1 < ea.S && (cs == 0 || cs == 1)) { x = srep[((id - N - 1) * 2 + cs) * 2]; y = srep[((id - N - 1) * 2 + cs) * 2 + 1]; }
-      cur[2 * (k + 1)] = x; cur[2 * (k + 1) + 1] = y;
+      const Ev2 b = ent_publish_point(st->id[st->bend[k]], st->cs[st->bend[k]], ec);
+      cur[2 * (k + 1)] = b.x; cur[2 * (k + 1) + 1] = b.y;
     }
     nb = 1 + st->n_bend;
   }
@@ -124,8 +134,28 @@ __global__ void fleet_ent_publish_kernel(FleetEntArgs ea) {
   for (int k = 0; k < NEP_MAX_BEND; k++) { r->bend[k][0] = cur[2 * k]; r->bend[k][1] = cur[2 * k + 1]; }
 }
 
+// The same between rounds (nep_batch_track_ent): the base, then the anchor of every bend index of the state just tracked, into
+// bend[0..n_bend) and n_bend of the flown record and nothing else; a slot without a trajectory or with an invalid state keeps its
+// record.  A kernel of its own: the tracking reads every record's current bend points, so none may change before all of them have run.
+__global__ void ent_publish_kernel(TetherArgs ea) {
+  const long slot = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int N = ea.N;
+  if (slot >= (long)ea.n_scenes * N) return;
+  nep_traj_rec* r = ea.recs_out + slot;
+  const nep_fe_ent_state* st = ea.in + slot;
+  if (!rec_present(r) || !ent_state_ok(st)) return;
+  const int scene = (int)(slot / N), a = (int)(slot % N);
+  const EntCtx ec = publish_ctx(ea, scene);
+  r->bend[0][0] = ea.pb[2 * a]; r->bend[0][1] = ea.pb[2 * a + 1];
+  for (int k = 0; k < st->n_bend; k++) {
+    const Ev2 b = ent_publish_point(st->id[st->bend[k]], st->cs[st->bend[k]], ec);
+    r->bend[k + 1][0] = b.x; r->bend[k + 1][1] = b.y;
+  }
+  r->n_bend = 1 + st->n_bend;
+}
+
 // One wave per slot: n_steps moves of the slot's own tether state (see the head of the file).
-__global__ __launch_bounds__(64) void fleet_ent_step_kernel(FleetEntArgs ea) {
+__global__ __launch_bounds__(64) void tether_step_kernel(TetherArgs ea) {
   __shared__ __attribute__((aligned(16))) nep_fe_ent_state s_st;
   __shared__ unsigned long long s_mask[kMaskWords], s_chg[kMaskWords];
   __shared__ unsigned s_stat[kStatWords];
@@ -137,9 +167,13 @@ __global__ __launch_bounds__(64) void fleet_ent_step_kernel(FleetEntArgs ea) {
   const bool predict = ea.start != nullptr;
   const nep_fe_ent_state* src = ea.in + slot;
   nep_fe_ent_state* dst = ea.out + slot;
+  if (ea.skip_absent && !rec_present(ea.recs + slot)) {      // (no trajectory to fly: state and record stay.  Every lane reads the same record: a uniform branch)
+    if (lane == 0) ea.flags[slot] = 0;
+    return;
+  }
   for (int i = lane; i < (int)(sizeof(nep_fe_ent_state) / 4); i += 64) ((int*)&s_st)[i] = ((const int*)src)[i];
   __syncthreads();
-  if (!fleet_state_ok(&s_st)) {      // (s_st is the same for every lane: a uniform branch.  The state stays; a prediction hands it on as it is)
+  if (!ent_state_ok(&s_st)) {      // (s_st is the same for every lane: a uniform branch.  The state stays; a prediction hands it on as it is)
     if (dst != src) for (int i = lane; i < (int)(sizeof(nep_fe_ent_state) / 4); i += 64) ((int*)dst)[i] = ((const int*)&s_st)[i];
     if (lane == 0) {
       ea.flags[slot] = NEP_ENT_TRACK_CAP;
@@ -186,7 +220,7 @@ __global__ __launch_bounds__(64) void fleet_ent_step_kernel(FleetEntArgs ea) {
           }
         }
         // the proof covers the eight-argument form: an agent whose published bend count changed is walked at the first step
-        if (ea.pub_prev_n) { const int n0 = min(max(ea.pub_prev_n[base + i], 0), NEP_MAX_BEND); changed = n0 >= 1 && n0 != nb; }
+        if (ea.prev_n) { const int n0 = prev_nb(ea, base + i); changed = n0 >= 1 && n0 != nb; }
       }
     }
     const unsigned long long m = __ballot(maybe), c = __ballot(changed);
@@ -233,30 +267,16 @@ __global__ __launch_bounds__(64) void fleet_ent_step_kernel(FleetEntArgs ea) {
           const nep_traj_rec* ri = ea.recs + base + i;
           const int nb = rec_nb(ri);
           const Ev2 pik = at(i, q - 1), pik1 = at(i, q);
-          // the other agent's bend points at the previous check: the list it published a round ago at the round's first tick (an empty
+          // the other agent's bend points at the previous check: the list it published a round ago at the call's first step (an empty
           // one is taken as the current one, as trajCB does for a first message, neptune_ros.cpp:423), later the same list
           int nq = nb;
-          if (first && ea.pub_prev_n) { const int n0 = min(max(ea.pub_prev_n[base + i], 0), NEP_MAX_BEND); nq = n0 >= 1 ? n0 : nb; }
+          if (first && ea.prev_n) { const int n0 = prev_nb(ea, base + i); nq = n0 >= 1 ? n0 : nb; }
           if (nq == nb) ent_cross_agent(add, pk, pk1, pik, pik1, pb_self, nb, &ri->bend[0][0], i + 1);
-          else abort |= ent_cross_agent_changed(add, pk, pk1, pik, pik1, pb_self, nb, &ri->bend[0][0], nq, ea.pub_prev_xy + (base + i) * NEP_MAX_BEND * 2, i + 1);
+          else abort |= ent_cross_agent_changed(add, pk, pk1, pik, pik1, pb_self, nb, &ri->bend[0][0], nq, prev_bends(ea, base + i), i + 1);
         }
       }
       ent_cross_static(add, pk, pk1, ec);
-      if (add.overflow) { fl |= NEP_ENT_TRACK_CAP; pk = pk1; continue; }
-      const bool may_outgrow = add.n > 0 || W.n_bend >= NEP_MAX_BEND - 1;
-      if (may_outgrow) save();
-      bool over = add.n > 0 && ent_merge(add, &W, pk, pb_self, ec);
-      if (!over) { over = ent_update_bends(&W, pk1, pb_self, ec); over |= W.n_bend > NEP_MAX_BEND - 1; }
-      if (over) { restore(); fl |= NEP_ENT_TRACK_CAP; pk = pk1; continue; }
-      if (abort) fl |= NEP_ENT_TRACK_ABORT;
-      for (int e = 0; e < W.n_alpha; e++) {      // active_cases of the agents: entries per id
-        const int id_ = W.id[e];
-        if (id_ > N) continue;
-        const int k = ent_count(W.id, W.n_alpha, id_);
-        if (k > 2) fl |= NEP_ENT_TRACK_ENTANGLED;
-        if (k >= 2) fl |= NEP_ENT_TRACK_TWO_CASES;
-      }
-      if (ent_tether(&W, pb_self, pk1, ec) > ea.cable) fl |= NEP_ENT_TRACK_TOO_LONG;
+      fl |= ent_track_move(add, &W, save, restore, pk, pk1, pb_self, ec, ea.cable, abort);
       pk = pk1;
     }
     // what the record holds beyond its counts is zero: the bytes of a state depend on the state alone
@@ -273,7 +293,7 @@ __global__ __launch_bounds__(64) void fleet_ent_step_kernel(FleetEntArgs ea) {
 }
 
 // One wave per scene: the slots ever flagged NEP_ENT_TRACK_ENTANGLED, into the scene's counter [7] (no atomics: recounted per call)
-__global__ __launch_bounds__(64) void fleet_ent_count_kernel(FleetEntArgs ea) {
+__global__ __launch_bounds__(64) void fleet_ent_count_kernel(TetherArgs ea) {
   const long scene = blockIdx.x;
   int c = 0;
   for (int a = threadIdx.x; a < ea.N; a += 64) c += (ea.ever[scene * ea.N + a] & NEP_ENT_TRACK_ENTANGLED) != 0;
@@ -285,15 +305,17 @@ __global__ __launch_bounds__(64) void fleet_ent_count_kernel(FleetEntArgs ea) {
 
 bool fleet_ent_fits(int N, int S) { return N <= kMaskWords * 64 && S <= kStatWords * 32; }
 
-void launch_fleet_ent_publish(const FleetEntArgs& ea, hipStream_t st) {
+void launch_tether_publish(const TetherArgs& ea, bool fleet, hipStream_t st) {
   const long slots = (long)ea.n_scenes * ea.N;
-  hipLaunchKernelGGL(fleet_ent_publish_kernel, dim3((unsigned)((slots + 63) / 64)), dim3(64), 0, st, ea);
+  if (slots <= 0) return;
+  hipLaunchKernelGGL(fleet ? fleet_ent_publish_kernel : ent_publish_kernel, dim3((unsigned)((slots + 63) / 64)), dim3(64), 0, st, ea);
 }
-void launch_fleet_ent_steps(const FleetEntArgs& ea, const FleetArgs& fa, hipStream_t st) {
+void launch_tether_steps(const TetherArgs& ea, const FleetArgs& fa, hipStream_t st) {
   const long slots = (long)ea.n_scenes * ea.N;
+  if (slots <= 0) return;
   const long total = slots * (ea.n_steps + 1);
-  hipLaunchKernelGGL(fleet_ent_pos_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, ea, fa);
-  hipLaunchKernelGGL(fleet_ent_step_kernel, dim3((unsigned)slots), dim3(64), 0, st, ea);
+  hipLaunchKernelGGL(tether_pos_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, ea, fa);
+  hipLaunchKernelGGL(tether_step_kernel, dim3((unsigned)slots), dim3(64), 0, st, ea);
   if (ea.ever && ea.counters) hipLaunchKernelGGL(fleet_ent_count_kernel, dim3((unsigned)ea.n_scenes), dim3(64), 0, st, ea);
 }
 

@@ -34,7 +34,75 @@ def ent_published_bends(st, pb, a, reps):
     return np.array([pb[a]] + [pb[al[b][0] - 1] if al[b][0] <= N else reps[al[b][0] - N - 1][al[b][1]] for b in bi], dtype=np.float64).reshape(-1, 2)
 
 
-class FleetLoop:
+def static_reps(statics):
+    """scene.static_reps, or empty arrays for a scene without static obstacles"""
+    return scene.static_reps(statics) if len(statics) else (np.zeros((0, 2, 2)), np.zeros((0, 2)))
+
+
+def upload_statics(be, scenes, tethers):
+    """every scene's static obstacles, and with tethers their representatives, into the handle"""
+    for s, sc in enumerate(scenes):
+        be.set_scene_statics(s, sc["statics"])
+        if tethers:
+            be.set_static_reps(*static_reps(sc["statics"]), scene=s)
+
+
+_REC = abi.TRAJ_REC_DTYPE.itemsize
+_F = abi.TRAJ_REC_DTYPE.fields
+_BEND_COLS = (_F["n_bend"][1], _F["n_bend"][1] + 4), (_F["bend"][1], _F["bend"][1] + _F["bend"][0].itemsize)      # byte ranges of a record
+
+
+def stamp_bends(d_new, d_rec):
+    """stamp the bend points every agent published in its record (d_rec: publishOwnTraj at replan time) into its commit record
+    (d_new: the QP's records carry the base only): the safety pass judges the new trajectories with the tethers the others see"""
+    vn, vr = d_new.view(-1, _REC), d_rec.view(-1, _REC)
+    for lo, hi in _BEND_COLS:
+        vn[:, lo:hi].copy_(vr[:, lo:hi])
+
+
+def plan_round(be, fe, d_rec, d_start, d_guess, d_res, d_final, d_acc, tethers=False, d_case=None, d_ent=None, ent_samples=3):
+    """the plan half of a round: front end -> lines + QP -> safety pass, from the records d_rec and the starts d_start into d_final
+    and d_acc.  With d_case the entangle check is on (d_ent: every tether's state at A): the QP gets the entangle rows and the safety
+    pass re-checks.  Tethered rounds stamp the published bend points into the commit records before the safety pass."""
+    if d_case is not None:
+        be.frontend_ent(fe, d_rec, d_start, d_guess, d_res, d_case, d_ent_init=d_ent)
+        be.replan(None, d_guess, d_ent=d_case)
+        stamp_bends(be.d_commit, d_rec)
+        be.safety_commit_ent(d_rec, be.d_commit, d_guess, d_final, d_acc, d_ent_init=d_ent, ent_samples=ent_samples)
+    else:
+        be.frontend(fe, d_rec, d_start, d_guess, d_res)
+        be.replan(None, d_guess)
+        if tethers:
+            stamp_bends(be.d_commit, d_rec)
+        be.safety_commit(d_rec, be.d_commit, d_guess, d_final, d_acc)
+
+
+def run_round_ops(lp, eager):
+    """lp._round_ops() of one round: eagerly when `eager` (the first round allocates), else as the graph lp._g, captured at the
+    first such round and replayed from then on"""
+    if eager:
+        return lp._round_ops()
+    torch, dev = lp.torch, lp.be.device
+    if lp._g is None:
+        torch.cuda.synchronize()
+        s = torch.cuda.Stream(dev)
+        s.wait_stream(torch.cuda.current_stream(dev))
+        lp._g = torch.cuda.CUDAGraph()
+        with torch.cuda.stream(s):
+            lp._g.capture_begin()
+            lp._round_ops()
+            lp._g.capture_end()
+        torch.cuda.current_stream(dev).wait_stream(s)
+    lp._g.replay()
+
+
+class _Audited:
+    def audit_records(self):
+        """the flight audit so far: AUDIT_DTYPE, [N] (FleetLoop) or [S, N]"""
+        return self.d_audit.cpu().numpy().view(abi.AUDIT_DTYPE).reshape(self._audit_shape)
+
+
+class FleetLoop(_Audited):
     def __init__(self, par, statics, starts, goals, beam_width=32, delta_t_states=6, replan_every=5, device=None, skip_arrived=False, audit=False,
                  tethers=False, check=True, ent_samples=3):
         import torch
@@ -54,7 +122,7 @@ class FleetLoop:
             # the one-scene host form of DeviceFleetLoop(tethers=True): entangle_state_ of every agent at its tracked position is kept
             # here (nep_ent_track_step per control tick), the state at A comes from nep_ent_predict_a every round
             from . import entangle
-            self._reps, self._longest = scene.static_reps(statics) if len(statics) else (np.zeros((0, 2, 2)), np.zeros((0, 2)))
+            self._reps, self._longest = static_reps(statics)
             self.be.set_static_reps(self._reps, self._longest)
             self._chk = [entangle.EntangleCheck(N, a + 1, par.num_pol, ent_samples, par.T_span, par.tether_length, par.pb, self._reps, self._longest)
                          for a in range(N)]
@@ -88,6 +156,7 @@ class FleetLoop:
         # audit: every round also audits, on the device, the records it uploads anyway over the replan_every ticks about to be flown
         # (nep_batch_audit; those ticks lie before the round's point A, so the uploaded records describe them); _tick keeps its host log
         self.d_audit = self.be.new_audit() if audit else None
+        self._audit_shape = (N,)
 
     # ---- records every agent publishes (publishOwnTraj) ----
     def _records(self, t_from):
@@ -156,19 +225,11 @@ class FleetLoop:
         d_final = torch.empty_like(d_com); d_acc = torch.zeros(N, dtype=torch.int32, device=be.device)
         if self.tethers:
             bends = self._predict_a(rec, starts, t_start)
+        d_case = d_ent_a = None
         if self.tethers and self.check:
             d_ent_a = be.to_device(self.ent_a)
             d_case = torch.zeros(N * abi.NEP_MAX_POL * N, dtype=torch.int32, device=be.device)
-            be.frontend_ent(self.fe, d_com, d_start, d_guess, d_fres, d_case, d_ent_init=d_ent_a)
-            be.replan(None, d_guess, d_ent=d_case)
-            self._stamp_bends(be.d_commit, d_com)
-            be.safety_commit_ent(d_com, be.d_commit, d_guess, d_final, d_acc, d_ent_init=d_ent_a, ent_samples=self.ent_samples)
-        else:
-            be.frontend(self.fe, d_com, d_start, d_guess, d_fres)
-            be.replan(None, d_guess)
-            if self.tethers:
-                self._stamp_bends(be.d_commit, d_com)
-            be.safety_commit(d_com, be.d_commit, d_guess, d_final, d_acc)
+        plan_round(be, self.fe, d_com, d_start, d_guess, d_fres, d_final, d_acc, self.tethers, d_case, d_ent_a, self.ent_samples)
         sol = be.solutions(); states = be.states(); fres = d_fres.cpu().numpy().view(abi.FE_RESULT_DTYPE)
         acc = d_acc.cpu().numpy()
         self.stats["rounds"] += 1
@@ -227,14 +288,6 @@ class FleetLoop:
             self.ent_a[a] = ent_state_record(out); self.flags_a[a] = fl
         return bends
 
-    def _stamp_bends(self, d_new, d_com):
-        """the published bend points into the commit records (TetherLoop._publish)"""
-        f = abi.TRAJ_REC_DTYPE.fields
-        R = abi.TRAJ_REC_DTYPE.itemsize
-        vn, vr = d_new.view(-1, R), d_com.view(-1, R)
-        for lo, hi in ((f["n_bend"][1], f["n_bend"][1] + 4), (f["bend"][1], f["bend"][1] + f["bend"][0].itemsize)):
-            vn[:, lo:hi].copy_(vr[:, lo:hi])
-
     def _track_tick(self, before, after, bends, first):
         N = self.N
         old = bends
@@ -260,10 +313,6 @@ class FleetLoop:
             self.stats["audit"] = audit_mod.summarize(self.audit_records())[0]
         return self.stats
 
-    def audit_records(self):
-        """the flight audit so far: [N] AUDIT_DTYPE"""
-        return self.d_audit.cpu().numpy().view(abi.AUDIT_DTYPE)
-
     def close(self):
         self.be.close()
         for pl in self.plans:
@@ -285,7 +334,7 @@ def scene_raw(statics, par):
     return out
 
 
-class DeviceFleetLoop:
+class DeviceFleetLoop(_Audited):
     """FleetLoop's rounds for S scenes at once with nothing on the host (include/neptune_fleet.h): the plan deques, point A, the
     splice, the composition and the control ticks of every (scene, agent) live in the batched handle, and a round
 
@@ -309,7 +358,7 @@ class DeviceFleetLoop:
           -> fleet_track_ent -> fleet_tick
 
     with the state at A (d_ent_a) predicted on the device and the commit records stamped with the published bend points before the
-    safety pass (TetherLoop._publish).  check=False keeps the plain front end and safety pass and leaves the tracking on: what the
+    safety pass (stamp_bends).  check=False keeps the plain front end and safety pass and leaves the tracking on: what the
     same fleet does to its tethers when nobody looks.  report() then also gives ever_entangled, too_long and track_cap per scene.
 
     missions=mission.MissionSpec(...) flies a campaign: fleet_mission goes between the commit (audit, tether
@@ -332,11 +381,7 @@ class DeviceFleetLoop:
         N = self.N = p.num_agents
         self.graph, self.replan_every = graph, replan_every
         be = self.be = BatchBackend(p, scenes[0]["statics"], n_scenes=S, device=device)
-        for s, sc in enumerate(scenes):
-            be.set_scene_statics(s, sc["statics"])
-            if tethers:
-                reps, longest = scene.static_reps(sc["statics"]) if len(sc["statics"]) else (np.zeros((0, 2, 2)), np.zeros((0, 2)))
-                be.set_static_reps(reps, longest, scene=s)
+        upload_statics(be, scenes, tethers)
         be.set_safety_check_prev(True)
         be.set_line_cull(4.0)
         self.fe = scene.frontend_cfg(p, beam_width=beam_width, pad_hold=1, entangle=tethers and check, ent_samples=ent_samples)
@@ -369,7 +414,7 @@ class DeviceFleetLoop:
         if self.masked:
             self.d_active = torch.ones((S, N), dtype=torch.int32, device=dev)
             be.set_active(self.d_active)
-        self.d_audit = None
+        self.d_audit, self._audit_shape = None, (S, N)
         if audit:
             self.d_audit = be.new_audit()
             be.audit(self.d_rec, self.d_clock, p.dc, 0, self.d_audit)      # (the call that allocates: made here, outside any capture)
@@ -379,8 +424,6 @@ class DeviceFleetLoop:
             self.d_flags_a = torch.zeros(n, dtype=torch.int32, device=dev)
             self.d_flags = torch.zeros(n, dtype=torch.int32, device=dev)
             self.d_case = torch.zeros(n * abi.NEP_MAX_POL * N, dtype=torch.int32, device=dev)
-            f = abi.TRAJ_REC_DTYPE.fields
-            self._bend_cols = (f["n_bend"][1], f["n_bend"][1] + 4), (f["bend"][1], f["bend"][1] + f["bend"][0].itemsize)
         self.missions = missions
         if missions is not None:
             from . import mission
@@ -397,14 +440,6 @@ class DeviceFleetLoop:
         self.after_mission = None     # test hook (missions): called between fleet_mission and fleet_tick of an eager round
         self.done = np.zeros((S, N), dtype=bool)
 
-    def _publish(self, d_new):
-        """stamp the bend points every agent published at the select into its commit record (the QP's records carry the base only):
-        the safety pass judges the new trajectories with the tethers the others see"""
-        R = abi.TRAJ_REC_DTYPE.itemsize
-        vn, vr = d_new.view(-1, R), self.d_rec.view(-1, R)
-        for lo, hi in self._bend_cols:
-            vn[:, lo:hi].copy_(vr[:, lo:hi])
-
     def _round_ops(self):
         be = self.be
         be.fleet_select(self.d_start, self.d_rec, self.d_active, self.d_clock if self.d_audit is not None else None)
@@ -412,18 +447,8 @@ class DeviceFleetLoop:
             be.fleet_predict_ent(self.d_start, self.d_rec, self.d_ent_a, self.d_flags_a)
             if self.after_select is not None:
                 self.after_select(self)
-        if self.tethers and self.check:
-            be.frontend_ent(self.fe, self.d_rec, self.d_start, self.d_guess, self.d_res, self.d_case, d_ent_init=self.d_ent_a)
-            be.replan(None, self.d_guess, d_ent=self.d_case)
-            self._publish(be.d_commit)
-            be.safety_commit_ent(self.d_rec, be.d_commit, self.d_guess, self.d_final, self.d_acc, d_ent_init=self.d_ent_a,
-                                 ent_samples=self.ent_samples)
-        else:
-            be.frontend(self.fe, self.d_rec, self.d_start, self.d_guess, self.d_res)
-            be.replan(None, self.d_guess)
-            if self.tethers:
-                self._publish(be.d_commit)
-            be.safety_commit(self.d_rec, be.d_commit, self.d_guess, self.d_final, self.d_acc)
+        ent = (self.d_case, self.d_ent_a) if self.tethers and self.check else (None, None)
+        plan_round(be, self.fe, self.d_rec, self.d_start, self.d_guess, self.d_res, self.d_final, self.d_acc, self.tethers, *ent, self.ent_samples)
         be.fleet_commit(self.d_res, self.d_acc, self.d_outcome)
         if self.after_commit is not None:
             self.after_commit(self)
@@ -439,21 +464,8 @@ class DeviceFleetLoop:
 
     def round(self):
         """one bulk-synchronous round of every scene; True when every agent of every scene has arrived"""
-        torch = self.torch
-        if self.graph and self.rounds >= 1 and self.after_commit is None and self.after_select is None and self.after_mission is None:
-            if self._g is None:
-                torch.cuda.synchronize()
-                s = torch.cuda.Stream(self.be.device)
-                s.wait_stream(torch.cuda.current_stream(self.be.device))
-                self._g = torch.cuda.CUDAGraph()
-                with torch.cuda.stream(s):
-                    self._g.capture_begin()
-                    self._round_ops()
-                    self._g.capture_end()
-                torch.cuda.current_stream(self.be.device).wait_stream(s)
-            self._g.replay()
-        else:
-            self._round_ops()
+        hooked = self.after_commit is not None or self.after_select is not None or self.after_mission is not None
+        run_round_ops(self, not self.graph or self.rounds < 1 or hooked)
         if self.trace is not None:
             oc = self.d_outcome.cpu().numpy()
             sol = self.be.solutions(); fres = self.d_res.cpu().numpy().view(abi.FE_RESULT_DTYPE)
@@ -511,16 +523,12 @@ class DeviceFleetLoop:
             out.append(d)
         return out
 
-    def audit_records(self):
-        """the flight audit so far: [S, N] AUDIT_DTYPE"""
-        return self.d_audit.cpu().numpy().view(abi.AUDIT_DTYPE).reshape(self.S, self.N)
-
     def close(self):
         self._g = None
         self.be.close()
 
 
-class TetherLoop:
+class TetherLoop(_Audited):
     """S tethered scenes flown on the device, one captured graph per round (include/neptune_frontend.h):
     frontend_ent -> lines + QP with the entangle rows -> safety_commit_ent -> track_ent -> next_starts, every tether's entangle
     state carried from round to round in `d_ent` ([S*N] FE_ENT_STATE_DTYPE bytes, the front end's and the safety pass's d_ent_init).
@@ -543,10 +551,7 @@ class TetherLoop:
         N = self.N = p.num_agents
         self.n_intervals, self.ent_samples, self.check, self.graph = n_intervals, ent_samples, check, graph
         be = self.be = BatchBackend(p, scenes[0]["statics"], n_scenes=S, device=device)
-        for s, sc in enumerate(scenes):
-            be.set_scene_statics(s, sc["statics"])
-            reps, longest = scene.static_reps(sc["statics"]) if len(sc["statics"]) else (np.zeros((0, 2, 2)), np.zeros((0, 2)))
-            be.set_static_reps(reps, longest, scene=s)
+        upload_statics(be, scenes, True)
         if active is not None:      # (torch int32 [S, N]: the front end, the replan and the safety pass skip the inactive agents,
             be.set_active(active)   # who keep flying their records; the tracking moves every tether)
         self.fe = scene.frontend_cfg(p, beam_width=beam_width, entangle=check, ent_samples=ent_samples)
@@ -562,40 +567,21 @@ class TetherLoop:
         self.d_acc = torch.zeros(S * N, dtype=torch.int32, device=dev)
         self.d_ent = torch.zeros(S * N * abi.FE_ENT_STATE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         self.d_flags = torch.zeros(S * N, dtype=torch.int32, device=dev)
-        f = abi.TRAJ_REC_DTYPE.fields
-        self._bend_cols = (f["n_bend"][1], f["n_bend"][1] + 4), (f["bend"][1], f["bend"][1] + f["bend"][0].itemsize)
         self.rounds = 0
         self.ever_flagged = np.zeros((S, N), dtype=np.int32)
         self._g = None
         self.audit_ticks = int(round(n_intervals * p.T_span / p.dc))
-        self.d_audit = None
+        self.d_audit, self._audit_shape = None, (S, N)
         if audit:
             self.d_audit = be.new_audit()
             be.audit(self.d_rec, self.d_start, p.dc, 0, self.d_audit)      # (the call that allocates: made here, outside any capture)
-
-    def _publish(self, d_new):
-        """stamp the bend points of every agent's state at the round's A into its new records (publishOwnTraj at replan time): the
-        QP's commit records carry the base only"""
-        R = abi.TRAJ_REC_DTYPE.itemsize
-        vn, vr = d_new.view(-1, R), self.d_rec.view(-1, R)
-        for lo, hi in self._bend_cols:
-            vn[:, lo:hi].copy_(vr[:, lo:hi])
 
     def _round_ops(self):
         be = self.be
         # the safety pass judges the new records with the tethers the others published (d_final inherits them: accepted agents
         # from the commit records, rejected and inactive ones from d_rec)
-        if self.check:
-            be.frontend_ent(self.fe, self.d_rec, self.d_start, self.d_guess, self.d_res, self.d_case, d_ent_init=self.d_ent)
-            be.replan(None, self.d_guess, d_ent=self.d_case)
-            self._publish(be.d_commit)
-            be.safety_commit_ent(self.d_rec, be.d_commit, self.d_guess, self.d_final, self.d_acc, d_ent_init=self.d_ent,
-                                 ent_samples=self.ent_samples)
-        else:
-            be.frontend(self.fe, self.d_rec, self.d_start, self.d_guess, self.d_res)
-            be.replan(None, self.d_guess)
-            self._publish(be.d_commit)
-            be.safety_commit(self.d_rec, be.d_commit, self.d_guess, self.d_final, self.d_acc)
+        plan_round(be, self.fe, self.d_rec, self.d_start, self.d_guess, self.d_res, self.d_final, self.d_acc, True,
+                   self.d_case if self.check else None, self.d_ent, self.ent_samples)
         be.track_ent(self.d_rec_prev, self.d_final, self.d_guess, self.d_ent, self.d_flags, n_intervals=self.n_intervals,
                      ent_samples=self.ent_samples)
         self.d_rec_prev.copy_(self.d_rec)
@@ -605,21 +591,7 @@ class TetherLoop:
         be.next_starts(self.d_rec, self.n_intervals * self.p.T_span, self.d_start)
 
     def round(self):
-        torch = self.torch
-        if self.graph and self.rounds >= 1:
-            if self._g is None:
-                torch.cuda.synchronize()
-                s = torch.cuda.Stream(self.be.device)
-                s.wait_stream(torch.cuda.current_stream(self.be.device))
-                self._g = torch.cuda.CUDAGraph()
-                with torch.cuda.stream(s):
-                    self._g.capture_begin()
-                    self._round_ops()
-                    self._g.capture_end()
-                torch.cuda.current_stream(self.be.device).wait_stream(s)
-            self._g.replay()
-        else:
-            self._round_ops()
+        run_round_ops(self, not self.graph or self.rounds < 1)
         self.rounds += 1
         self.ever_flagged |= (self.d_flags.cpu().numpy().reshape(self.S, self.N) & abi.NEP_ENT_TRACK_ENTANGLED) != 0
 
@@ -642,10 +614,6 @@ class TetherLoop:
         if self.d_audit is not None:
             rep["audit"] = audit_mod.summarize(self.audit_records(), self.S)
         return rep
-
-    def audit_records(self):
-        """the flight audit so far: [S, N] AUDIT_DTYPE"""
-        return self.d_audit.cpu().numpy().view(abi.AUDIT_DTYPE).reshape(self.S, self.N)
 
     def close(self):
         self._g = None

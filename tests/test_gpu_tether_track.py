@@ -70,7 +70,9 @@ def assert_state_equal(dev, st, where):
     assert [int(x) for x in dev["bend"][: len(bi)]] == bi, where
 
 
-def run_rounds(torch, scenes, n_iv, rounds, ns=3, active=None):
+def run_rounds(torch, scenes, n_iv, rounds, ns=3, active=None, absent=(), absent_from=0):
+    """`rounds` rounds of nep_batch_track_ent against host_round; the (scene, agent) pairs of `absent` publish no trajectory
+    (valid = 0) from round `absent_from` on"""
     p = dataclasses.replace(scenes[0]["par"], enable_entangle=True)
     from neptune_amd import dist as ndist
     from neptune_amd.backend import BatchBackend
@@ -93,6 +95,9 @@ def run_rounds(torch, scenes, n_iv, rounds, ns=3, active=None):
     out = []
     rng = np.random.default_rng(7)
     for r in range(rounds):
+        if r == absent_from:
+            for s, a in absent:
+                recs[s][a]["valid"] = 0
         changed = 0
         for s in range(S_):      # the previous check saw some tethers with a bend point more or less: the nine-argument form
             for j in range(N):
@@ -136,6 +141,28 @@ def run_rounds(torch, scenes, n_iv, rounds, ns=3, active=None):
 @pytest.mark.parametrize("n_iv", [1, 2])
 def test_track_equals_host_chain_crossing_scene(torch, n_iv):
     out = run_rounds(torch, [scene.tether_crossing_scene(16, 8, 61), scene.tether_crossing_scene(16, 8, 62)], n_iv, rounds=6)
+    assert sum(int((o["n_alpha"] > 0).sum()) for o in out) > 0, "no crossing was tracked"
+    assert sum(o["changed"] for o in out) > 0
+
+
+def test_track_leaves_slots_without_a_trajectory_alone(torch):
+    """one record per scene stops being valid after the first round, when its tether has crossings on its list: from then on the
+    slot's flags are 0 and its state and record stay as they are (run_rounds compares both with the host chain, which skips the
+    slot), and the others no longer cross its tether"""
+    absent = [(0, 10), (1, 14)]
+    out = run_rounds(torch, [scene.tether_crossing_scene(16, 8, 61), scene.tether_crossing_scene(16, 8, 62)], 2, rounds=3, absent=absent, absent_from=1)
+    for s, a in absent:
+        assert out[0]["n_alpha"][s, a] > 0, "the slot had nothing on its list when it went absent"
+        for o in out[1:]:
+            assert o["flags"][s, a] == 0 and o["n_alpha"][s, a] == out[0]["n_alpha"][s, a] and o["n_bend"][s, a] == out[0]["n_bend"][s, a]
+    assert sum(int((o["n_alpha"] > 0).sum()) for o in out[1:]) > 2, "nobody else tracked a crossing"
+
+
+def test_track_largest_step_count(torch):
+    """n_intervals = num_pol and ent_samples = 8: the most steps a call accepts (the positions of num_pol * 8 + 1 sampled points
+    per slot), first call of the handle"""
+    scenes = [scene.tether_crossing_scene(16, 8, 61), scene.tether_crossing_scene(16, 8, 62)]
+    out = run_rounds(torch, scenes, scenes[0]["par"].num_pol, rounds=2, ns=8)
     assert sum(int((o["n_alpha"] > 0).sum()) for o in out) > 0, "no crossing was tracked"
     assert sum(o["changed"] for o in out) > 0
 
