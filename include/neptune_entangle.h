@@ -117,6 +117,8 @@ typedef struct nep_ent_track_inputs {
 #define NEP_ENT_TRACK_CAP 8         /* a capacity was exceeded: the state is left as it was before the move                    */
 #define NEP_ENT_TRACK_ABORT 16      /* the nine-argument form reached a branch after which the reference stops the process
                                        (exit(-1), "stop1".."stop4"): its crossing is added as there and the update goes on   */
+#define NEP_ENT_TRACK_HELD 32       /* device, list form only (nep_batch_fleet_predict_ent): the state at point A holds more than
+                                       NEP_FE_ENT_CAP crossings, the slot does not plan this round.  Not a capacity: nothing is lost */
 
 /* Capacity (not a flag): new crossings one move may add — the device's list of a step's crossings (kEntAddCap, ent_device.h) */
 #define NEP_ENT_TRACK_ADD_CAP 32

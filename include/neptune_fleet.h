@@ -160,6 +160,27 @@ int nep_batch_fleet_track_ent(nep_batch_t* h, const nep_traj_rec* d_records, int
 int nep_batch_fleet_ent_state(nep_batch_t* h, nep_fe_ent_state* states_out, int32_t* flags_round_out, int32_t* flags_ever_out,
                               int32_t* walked_out);
 
+/* ---- tethers beyond NEP_FE_ENT_CAP crossings: the list form (nep_ent_lists, include/neptune_frontend.h) ------------------------
+ * nep_batch_fleet_init_ent_lists   like nep_batch_fleet_init_ent, but the states come from HOST arrays in the list form (all arrays
+ *                         NULL: empty states) and host_lists->cap (NEP_FE_ENT_CAP < cap <= NEP_ENT_LISTS_MAX_CAP, else NEP_E_CAP) is
+ *                         the handle's capacity from then on: nep_batch_fleet_track_ent, the bend points nep_batch_fleet_select
+ *                         publishes and nep_batch_fleet_predict_ent run on lists of that many entries, bit-identical to the host
+ *                         chain with state->cap = cap.  nep_batch_fleet_init_ent puts the handle back on the fixed record.
+ *                         Synchronises; not capturable.
+ * Point A: the front end and the safety re-check take the fixed record.  nep_batch_fleet_predict_ent on such a handle predicts in
+ * the list form; where the result holds at most NEP_FE_ENT_CAP crossings d_ent_a[slot] receives it as before.  Where it holds
+ * more the slot is HELD for the round: d_ent_a[slot] is zeroed, d_flags_a[slot] gets NEP_ENT_TRACK_HELD, the slot's held rounds
+ * count up, and its entry in the mask registered with nep_batch_set_active is cleared — it takes the inactive-slot path
+ * (NEP_FE_SKIPPED, NEP_SKIPPED, record kept, NEP_FLEET_SKIPPED), keeps flying its plan, its tether keeps being tracked exactly,
+ * and it plans again in the first round whose state at A fits.  The caller refills (or nep_batch_fleet_select rewrites) the mask
+ * before the next prediction; no registered mask is NEP_E_STATE.  A hold is no capacity: nep_batch_check reports nothing.
+ * nep_batch_fleet_ent_lists   blocking reader: host_out's arrays (host_out->cap == the handle's, else NEP_E_ARG; may be NULL) and
+ *                         held_rounds_out ([slots], may be NULL).  NEP_E_STATE on a handle that is not on the list form.
+ * nep_batch_fleet_ent_state on such a handle fills states_out for the slots that fit a fixed record; a slot that does not gets
+ * n_alpha = -1 and zeros.                                                                                                        */
+int nep_batch_fleet_init_ent_lists(nep_batch_t* h, double cable_length, const nep_ent_lists* host_lists, void* stream);
+int nep_batch_fleet_ent_lists(nep_batch_t* h, nep_ent_lists* host_out, int32_t* held_rounds_out);
+
 /* ---- missions: successive goals, timeouts, leg records -------------------------------------------------------------------------
  * The two goal generators of the reference's experiments as a controller inside the round, so that a campaign of any length
  * needs no host round trip:

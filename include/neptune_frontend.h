@@ -225,6 +225,51 @@ int nep_batch_track_ent(nep_batch_t* h, const nep_traj_rec* d_prev, nep_traj_rec
                         int32_t n_intervals, int32_t ent_samples, double cable_length, nep_fe_ent_state* d_ent,
                         int32_t* d_flags, void* stream);
 
+/* ---- The tracked state beyond NEP_FE_ENT_CAP crossings: a list form ------------------------------------------------------
+ * The reference's updateEntStateStaticObs keeps its list in a std::vector; the fixed record above drops a tracked move that
+ * would outgrow NEP_FE_ENT_CAP entries (NEP_ENT_TRACK_CAP) and the state lies behind the tether from then on.  nep_ent_lists
+ * is the same state as a struct of arrays with `cap` entries per slot, NEP_FE_ENT_CAP < cap <= NEP_ENT_LISTS_MAX_CAP
+ * (else NEP_E_CAP).  The struct itself lives in host memory; its members point to arrays of `slots` = n_scenes * N slots:
+ *   n_alpha, n_bend       [slots]
+ *   id, cs, beta          [slots][cap]   the crossing list (agent or static id, case, beta: as in nep_fe_ent_state)
+ *   bend                  [slots][NEP_MAX_BEND]   indices into the list, 16 bit
+ * Entries beyond the counts are zero, on the way in and on the way out: the bytes of a state depend on the state alone.
+ * The other two capacities are the fixed record's and the host form's: NEP_MAX_BEND - 1 bend points (a published record
+ * holds no more) and NEP_ENT_TRACK_ADD_CAP new crossings per move.  nep_abi_sizeof(23) is the struct's size.                */
+#define NEP_ENT_LISTS_MAX_CAP 4096
+typedef struct nep_ent_lists {
+  int32_t cap;
+  int32_t _pad;
+  int32_t* n_alpha;
+  int32_t* n_bend;
+  int16_t* id;
+  int8_t* cs;
+  double* beta;
+  int16_t* bend;
+} nep_ent_lists;
+
+/* nep_batch_track_ent on the list form: d_lists (a host struct) names DEVICE arrays, updated in place; everything else —
+ * the steps flown, d_prev / d_records / d_guess, the published bend points, d_flags, the validation and its error codes, the
+ * first call allocating and later ones being capturable (with the same cap), fleet_ent_proof — is nep_batch_track_ent's.  A move that
+ * would outgrow d_lists->cap crossings, NEP_MAX_BEND - 1 bend points or NEP_ENT_TRACK_ADD_CAP new crossings is dropped:
+ * NEP_ENT_TRACK_CAP in d_flags, NEP_E_CAP from nep_batch_check.  A slot whose counts or bend indices are out of range on the way
+ * in keeps its state and gets NEP_ENT_TRACK_CAP, like a malformed fixed record.  Bit-identical to chaining nep_ent_track_step
+ * with state->cap = d_lists->cap.  The working list of a slot sits in LDS: 11 bytes per entry (45 KB at the largest cap).   */
+int nep_batch_track_ent_lists(nep_batch_t* h, const nep_traj_rec* d_prev, nep_traj_rec* d_records, const nep_guess* d_guess,
+                              int32_t n_intervals, int32_t ent_samples, double cable_length, const nep_ent_lists* d_lists,
+                              int32_t* d_flags, void* stream);
+
+/* The state at A the front end and the safety re-check take, from the list form, for a loop that tracks between rounds (the
+ * fleet's nep_batch_fleet_predict_ent has the same rule, include/neptune_fleet.h): d_ent_a[slot] receives the slot's list as a
+ * fixed record where it holds at most NEP_FE_ENT_CAP crossings and d_mask_out[slot] = d_mask_in[slot] (1 with d_mask_in NULL).
+ * Where it holds more the slot is HELD: a zeroed record, NEP_ENT_TRACK_HELD in d_flags_a[slot] (may be NULL; else 0),
+ * d_held[slot] += 1 (may be NULL) and d_mask_out[slot] = 0 — registered with nep_batch_set_active, the mask takes the slot out of
+ * the round's front end, replan and safety pass; it keeps flying its record and nep_batch_track_ent_lists keeps tracking it.
+ * d_lists as in nep_batch_track_ent_lists (not changed); a malformed list gives a zeroed record and is not held.  Same handles
+ * and error codes as nep_batch_track_ent_lists.  Asynchronous, allocates nothing, capturable.                                   */
+int nep_batch_ent_lists_at_a(nep_batch_t* h, const nep_ent_lists* d_lists, nep_fe_ent_state* d_ent_a, int32_t* d_flags_a,
+                             const int32_t* d_mask_in, int32_t* d_mask_out, int32_t* d_held, void* stream);
+
 /* Point A of the NEXT round for every slot, on the device: d_start[slot].t_start advances by dt and pos / vel / accel become
  * the state of the agent's committed trajectory (d_records [n_scenes][N], e.g. nep_batch_safety_commit's d_final) at that
  * time — Neptune::replanFull's choice of A "deltaT ahead on the committed plan" (neptune.cpp:1366-1399) for a

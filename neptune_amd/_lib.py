@@ -47,11 +47,11 @@ PLAN_EXPORTS = [
 ]
 # every symbol include/neptune_entangle.h declares (host-only)
 # include/neptune_frontend.h
-FE_EXPORTS = ["nep_batch_frontend", "nep_batch_frontend_hulls", "nep_batch_set_static_reps", "nep_batch_set_fe_ent_big_records", "nep_batch_frontend_ent", "nep_batch_frontend_ent_hulls", "nep_batch_safety_commit_ent", "nep_batch_track_ent", "nep_batch_next_starts", "nep_batch_audit", "nep_audit_records", "nep_audit_init"]
+FE_EXPORTS = ["nep_batch_frontend", "nep_batch_frontend_hulls", "nep_batch_set_static_reps", "nep_batch_set_fe_ent_big_records", "nep_batch_frontend_ent", "nep_batch_frontend_ent_hulls", "nep_batch_safety_commit_ent", "nep_batch_track_ent", "nep_batch_track_ent_lists", "nep_batch_ent_lists_at_a", "nep_batch_next_starts", "nep_batch_audit", "nep_audit_records", "nep_audit_init"]
 # include/neptune_fleet.h
 FLEET_EXPORTS = ["nep_batch_fleet_init", "nep_batch_fleet_select", "nep_batch_fleet_commit", "nep_batch_fleet_tick", "nep_batch_fleet_ring_cap",
                  "nep_batch_fleet_plans", "nep_batch_fleet_state", "nep_batch_fleet_counters", "nep_batch_fleet_init_ent", "nep_batch_fleet_predict_ent",
-                 "nep_batch_fleet_track_ent", "nep_batch_fleet_ent_state", "nep_batch_fleet_mission_keepout", "nep_batch_fleet_mission_init",
+                 "nep_batch_fleet_track_ent", "nep_batch_fleet_ent_state", "nep_batch_fleet_init_ent_lists", "nep_batch_fleet_ent_lists", "nep_batch_fleet_mission_keepout", "nep_batch_fleet_mission_init",
                  "nep_batch_fleet_mission", "nep_batch_fleet_mission_state", "nep_batch_fleet_mission_log", "nep_mission_step"]
 ENT_EXPORTS = ["nep_ent_sample_points", "nep_ent_propagate_segment", "nep_ent_propagate_guess", "nep_ent_case_ids", "nep_ent_track_step", "nep_ent_predict_a"]
 
@@ -191,6 +191,8 @@ def lib():
     L.nep_batch_safety_commit_ent.argtypes = [vp, vp, vp, vp, vp, i, d, vp, vp, vp]
     L.nep_batch_next_starts.argtypes = [vp, vp, d, vp, vp, d, vp]
     L.nep_batch_track_ent.argtypes = [vp, vp, vp, vp, i, i, d, vp, vp, vp]
+    L.nep_batch_track_ent_lists.argtypes = [vp, vp, vp, vp, i, i, d, C.POINTER(abi.nep_ent_lists), vp, vp]
+    L.nep_batch_ent_lists_at_a.argtypes = [vp, C.POINTER(abi.nep_ent_lists), vp, vp, vp, vp, vp, vp]
     L.nep_batch_audit.argtypes = [vp, vp, vp, d, i, vp, vp]
     L.nep_audit_records.argtypes = [vp, i, pi, pd, i, d, d, d, i, vp]
     L.nep_audit_init.argtypes = [vp, C.c_int64]
@@ -206,6 +208,8 @@ def lib():
     L.nep_batch_fleet_predict_ent.argtypes = [vp, vp, vp, vp, vp, vp]
     L.nep_batch_fleet_track_ent.argtypes = [vp, vp, vp, vp]
     L.nep_batch_fleet_ent_state.argtypes = [vp, vp, pi, pi, pi]
+    L.nep_batch_fleet_init_ent_lists.argtypes = [vp, d, C.POINTER(abi.nep_ent_lists), vp]
+    L.nep_batch_fleet_ent_lists.argtypes = [vp, C.POINTER(abi.nep_ent_lists), pi]
     L.nep_batch_fleet_mission_keepout.argtypes = [vp, i, i, pi, pd]
     L.nep_batch_fleet_mission_init.argtypes = [vp, C.POINTER(abi.nep_mission_cfg), vp]
     L.nep_batch_fleet_mission.argtypes = [vp, vp]
@@ -221,7 +225,7 @@ def lib():
     L.nep_abi_sizeof.argtypes = [i]; L.nep_abi_sizeof.restype = i
     for which, struct in ((1, abi.nep_traj_rec), (5, abi.nep_guess), (6, abi.nep_solution), (11, abi.nep_fe_cfg), (12, abi.nep_fe_start),
                           (13, abi.nep_fe_result), (14, abi.nep_fe_ent_state), (17, abi.nep_audit), (18, abi.nep_fleet_cfg),
-                          (20, abi.nep_mission_cfg), (21, abi.nep_mission_leg)):
+                          (20, abi.nep_mission_cfg), (21, abi.nep_mission_leg), (23, abi.nep_ent_lists)):
         if L.nep_abi_sizeof(which) != C.sizeof(struct):
             raise BackendError("%s: sizeof(%s) is %d in the library, %d in neptune_amd/abi.py — rebuild the library from this tree's headers"
                                % (LIB_PATH, struct.__name__, L.nep_abi_sizeof(which), C.sizeof(struct)))

@@ -128,6 +128,7 @@ class nep_ent_track_inputs(C.Structure):
 # nep_ent_track_step / nep_batch_track_ent flags (include/neptune_entangle.h)
 NEP_ENT_TRACK_ENTANGLED, NEP_ENT_TRACK_TWO_CASES, NEP_ENT_TRACK_TOO_LONG, NEP_ENT_TRACK_CAP, NEP_ENT_TRACK_ABORT = 1, 2, 4, 8, 16
 NEP_ENT_TRACK_ADD_CAP = 32
+NEP_ENT_TRACK_HELD = 32      # (a flag of the device's list form: the state at A does not fit the fixed record)
 
 
 class nep_fe_cfg(C.Structure):
@@ -144,6 +145,44 @@ class nep_fe_ent_state(C.Structure):
     """eu::ent_state of a search node / of point A in a fixed-size record (include/neptune_frontend.h)."""
     _fields_ = [("n_alpha", C.c_int32), ("n_bend", C.c_int32), ("id", C.c_int16 * NEP_FE_ENT_CAP), ("cs", C.c_int8 * NEP_FE_ENT_CAP),
                 ("beta", C.c_double * NEP_FE_ENT_CAP), ("bend", C.c_int8 * 8)]
+
+
+NEP_ENT_LISTS_MAX_CAP = 4096
+
+
+class nep_ent_lists(C.Structure):
+    """the tracked tether states as a struct of arrays, `cap` entries per slot (include/neptune_frontend.h)"""
+    _fields_ = [("cap", C.c_int32), ("_pad", C.c_int32), ("n_alpha", C.POINTER(C.c_int32)), ("n_bend", C.POINTER(C.c_int32)),
+                ("id", C.POINTER(C.c_int16)), ("cs", C.POINTER(C.c_int8)), ("beta", C.POINTER(C.c_double)), ("bend", C.POINTER(C.c_int16))]
+
+
+ENT_LISTS_FIELDS = (("n_alpha", np.int32, 0), ("n_bend", np.int32, 0), ("id", np.int16, 1), ("cs", np.int8, 1), ("beta", np.float64, 1),
+                    ("bend", np.int16, 2))      # (name, dtype, per slot: 0 = one, 1 = cap, 2 = NEP_MAX_BEND)
+
+
+class EntLists:
+    """nep_ent_lists in host arrays: n_alpha / n_bend [slots], id / cs / beta [slots][cap], bend [slots][NEP_MAX_BEND]; .c is the struct"""
+
+    def __init__(self, slots, cap):
+        self.slots, self.cap = int(slots), int(cap)
+        for name, dt, kind in ENT_LISTS_FIELDS:
+            setattr(self, name, np.zeros((self.slots,) + ((), (self.cap,), (NEP_MAX_BEND,))[kind], dtype=dt))
+        self.c = nep_ent_lists(self.cap, 0, *[C.cast(getattr(self, name).ctypes.data, t) for (name, _, _), (_, t) in
+                                               zip(ENT_LISTS_FIELDS, nep_ent_lists._fields_[2:])])
+
+    def set_state(self, slot, st):
+        """slot <- a host eu::ent_state (entangle.State)"""
+        al, be_, bi, _ = st.as_lists()
+        assert len(al) <= self.cap and len(bi) <= NEP_MAX_BEND
+        for name, _, _ in ENT_LISTS_FIELDS[2:]:
+            getattr(self, name)[slot] = 0
+        self.n_alpha[slot], self.n_bend[slot] = len(al), len(bi)
+        if al:
+            self.id[slot, :len(al)] = [a[0] for a in al]; self.cs[slot, :len(al)] = [a[1] for a in al]; self.beta[slot, :len(al)] = be_
+        self.bend[slot, :len(bi)] = bi
+
+    def tobytes(self):
+        return b"".join(getattr(self, name).tobytes() for name, _, _ in ENT_LISTS_FIELDS)
 
 
 class nep_fe_start(C.Structure):

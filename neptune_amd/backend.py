@@ -362,6 +362,24 @@ class BatchBackend:
         check(lib().nep_batch_track_ent(self._h, d_prev.data_ptr(), d_records.data_ptr(), d_guess.data_ptr(), int(n_intervals), int(ent_samples),
                                         float(cable), d_ent.data_ptr(), d_flags.data_ptr() if d_flags is not None else None, st.cuda_stream))
 
+    def new_ent_lists(self, cap, host=None):
+        """the tracked states in the list form on the device (DeviceEntLists): empty, or a copy of the abi.EntLists `host`"""
+        return DeviceEntLists(self, cap, host)
+
+    def track_ent_lists(self, d_prev, d_records, d_guess, lists, d_flags=None, n_intervals=1, ent_samples=3, cable_length=None, stream=None):
+        """track_ent on the list form (nep_batch_track_ent_lists): lists a DeviceEntLists, updated in place"""
+        st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        cable = self.par.tether_length if cable_length is None else cable_length
+        check(lib().nep_batch_track_ent_lists(self._h, d_prev.data_ptr(), d_records.data_ptr(), d_guess.data_ptr(), int(n_intervals), int(ent_samples),
+                                              float(cable), C.byref(lists.c), d_flags.data_ptr() if d_flags is not None else None, st.cuda_stream))
+
+    def ent_lists_at_a(self, lists, d_ent_a, d_mask_out, d_flags_a=None, d_mask_in=None, d_held=None, stream=None):
+        """the fixed record at A of every slot whose list fits it; the others held: zeroed, flagged, counted and cleared in d_mask_out
+        (nep_batch_ent_lists_at_a)"""
+        st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+        check(lib().nep_batch_ent_lists_at_a(self._h, C.byref(lists.c), d_ent_a.data_ptr(), ptr(d_flags_a), ptr(d_mask_in), d_mask_out.data_ptr(), ptr(d_held), st.cuda_stream))
+
     def new_audit(self):
         """device buffer of n_scenes*N flight-audit records with the initial values (AUDIT_DTYPE bytes; nep_audit_init)"""
         from . import audit
@@ -435,6 +453,20 @@ class BatchBackend:
         st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
         cable = self.par.tether_length if cable_length is None else cable_length
         check(lib().nep_batch_fleet_init_ent(self._h, float(cable), d_ent0.data_ptr() if d_ent0 is not None else None, st.cuda_stream))
+
+    def fleet_init_ent_lists(self, cap, cable_length=None, host=None, stream=None):
+        """the tether state of every slot in the list form, `cap` entries per slot (nep_batch_fleet_init_ent_lists): host an
+        abi.EntLists of that cap, or None for empty states"""
+        st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        cable = self.par.tether_length if cable_length is None else cable_length
+        assert host is None or (host.cap == cap and host.slots == self.slots)
+        check(lib().nep_batch_fleet_init_ent_lists(self._h, float(cable), C.byref(host.c if host is not None else abi.nep_ent_lists(int(cap))), st.cuda_stream))
+
+    def fleet_ent_lists(self, cap):
+        """the list-form tether states and the held rounds of every slot (blocking) -> (abi.EntLists, held [slots] int32)"""
+        out = abi.EntLists(self.slots, cap); held = np.zeros(self.slots, dtype=np.int32)
+        check(lib().nep_batch_fleet_ent_lists(self._h, C.byref(out.c), abi.iptr(held)))
+        return out, held
 
     def fleet_predict_ent(self, d_start, d_records, d_ent_a, d_flags_a=None, stream=None):
         """the state at point A of every slot into d_ent_a (PredictAlphasBetas; nep_batch_fleet_predict_ent), after fleet_select"""
@@ -736,3 +768,28 @@ class BatchBackend:
         seg = np.zeros(cap, dtype=np.int32); nd = np.zeros((cap, 3)); n = C.c_int32(0)
         check(lib().nep_batch_debug_lines(self._h, slot, cap, abi.iptr(seg), abi.dptr(nd), C.byref(n)))
         return seg[:n.value].copy(), nd[:n.value].copy()
+
+
+class DeviceEntLists:
+    """nep_ent_lists in device tensors (one per member, named like them); .c is the host struct nep_batch_track_ent_lists takes"""
+
+    def __init__(self, be, cap, host=None):
+        torch = be.torch
+        self.slots, self.cap = be.slots, int(cap)
+        tdt = {np.int32: torch.int32, np.int16: torch.int16, np.int8: torch.int8, np.float64: torch.float64}
+        for name, dt, kind in abi.ENT_LISTS_FIELDS:
+            shape = (self.slots,) + ((), (self.cap,), (abi.NEP_MAX_BEND,))[kind]
+            if host is not None:
+                assert host.cap == self.cap and host.slots == self.slots
+                t = torch.from_numpy(getattr(host, name).copy()).to(be.device)
+            else:
+                t = torch.zeros(shape, dtype=tdt[dt], device=be.device)
+            setattr(self, name, t)
+        self.c = abi.nep_ent_lists(self.cap, 0, *[C.cast(getattr(self, name).data_ptr(), t) for (name, _, _), (_, t) in
+                                                   zip(abi.ENT_LISTS_FIELDS, abi.nep_ent_lists._fields_[2:])])
+
+    def to_host(self):
+        out = abi.EntLists(self.slots, self.cap)
+        for name, _, _ in abi.ENT_LISTS_FIELDS:
+            getattr(out, name)[...] = getattr(self, name).cpu().numpy()
+        return out

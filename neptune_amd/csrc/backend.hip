@@ -56,6 +56,22 @@ template <class T> struct DevBuf {
   void release() { if (p) { hipFree(p); g_live_device -= (long long)(n * sizeof(T)); } p = nullptr; n = 0; }
 };
 
+// The list form of the tracked tether states (nep_ent_lists) in device memory: `slots` slots of `cap` entries
+struct ListBuf {
+  DevBuf<int> n_alpha, n_bend; DevBuf<int16_t> id, bend; DevBuf<int8_t> cs; DevBuf<double> beta; int cap = 0;
+  int ensure(size_t slots, int cap_) {
+    if (int e = n_alpha.ensure(slots)) return e;
+    if (int e = n_bend.ensure(slots)) return e;
+    if (int e = id.ensure(slots * cap_)) return e;
+    if (int e = cs.ensure(slots * cap_)) return e;
+    if (int e = beta.ensure(slots * cap_)) return e;
+    if (int e = bend.ensure(slots * NEP_MAX_BEND)) return e;
+    cap = cap_;
+    return 0;
+  }
+  nep_ent_lists view() const { nep_ent_lists v{}; v.cap = cap; v.n_alpha = n_alpha.p; v.n_bend = n_bend.p; v.id = id.p; v.cs = cs.p; v.beta = beta.p; v.bend = bend.p; return v; }
+};
+
 // Page-locked host memory (the per-agent handle's staging arenas: one DMA in, one out per replan), owned like a DevBuf.  Growth keeps
 // the contents.
 struct PinnedArena {
@@ -142,6 +158,7 @@ struct Engine {
   DevBuf<int> d_order, d_order_key; bool have_history = false, lpt = true, last_ordered = false;   // QP workgroups launched longest-expected-first (order_kernel)
   const int* active = nullptr;       // the active set (nep_batch_set_active): device [scenes][N], or null
   DevBuf<int> d_act, d_fe_act;       // [slots + 1] compacted active slots + count (active_list_kernel): the QP launches', the front end's
+  ListBuf d_track_lsave;      // nep_batch_track_ent_lists: the same scratch in the list form, of the largest cap seen
   DevBuf<nep_fe_ent_state> d_track_save; DevBuf<int> d_track_flags; DevBuf<double> d_track_pos;      // nep_batch_track_ent: per-slot scratch, flags when the caller passes none, the positions of the largest call
   DevBuf<AuditPart> d_audit_part;      // nep_batch_audit: per (scene, run of ticks, agent) minima, sized once for the most runs a call can have
   int static_nv_max = 0;               // most vertices of a static polygon uploaded so far (nep_batch_audit's LDS stride)
@@ -1005,6 +1022,8 @@ struct nep_batch {
     bool ent_ready = false; double cable = 0.0;
     DevBuf<nep_fe_ent_state> ent, ent_save; DevBuf<double> pub_xy, pub_prev_xy, ent_pos;
     DevBuf<int> pub_n, pub_prev_n, ent_flags, ent_ever, ent_walked, ent_flags_a;
+    // the list form of the same (nep_batch_fleet_init_ent_lists): ent_cap != 0 = the state lives in ent_lists, not in ent
+    int ent_cap = 0; ListBuf ent_lists, ent_lsave; DevBuf<int> ent_held;
     // the missions (nep_batch_fleet_mission_init): legs, totals, runs, the log; the keep-outs are staged by
     // nep_batch_fleet_mission_keepout (before or after either init: no init drops them)
     bool mis_ready = false; nep_mission_cfg mis_cfg{}; size_t mis_lds = 0;
@@ -1406,9 +1425,14 @@ int nep_batch_safety_commit_ent(nep_batch_t* h, const nep_traj_rec* d_prev, cons
   return safety_end(h, ps, d_prev, d_new, E.d_entangles.p, d_final, d_accept, (hipStream_t)stream);
 }
 
-int nep_batch_track_ent(nep_batch_t* h, const nep_traj_rec* d_prev, nep_traj_rec* d_records, const nep_guess* d_guess, int32_t n_intervals,
-                        int32_t ent_samples, double cable_length, nep_fe_ent_state* d_ent, int32_t* d_flags, void* stream) {
-  if (!h || !d_prev || !d_records || !d_guess || !d_ent) return fail(NEP_E_ARG, "null argument");
+namespace {
+bool ent_lists_cap_ok(int cap) { return cap > NEP_FE_ENT_CAP && cap <= NEP_ENT_LISTS_MAX_CAP; }
+bool ent_lists_complete(const nep_ent_lists* l) { return l->n_alpha && l->n_bend && l->id && l->cs && l->beta && l->bend; }
+// nep_batch_track_ent / nep_batch_track_ent_lists: the state in d_ent (the fixed record) or in *lists
+int track_ent_round(nep_batch_t* h, const nep_traj_rec* d_prev, nep_traj_rec* d_records, const nep_guess* d_guess, int32_t n_intervals,
+                    int32_t ent_samples, double cable_length, nep_fe_ent_state* d_ent, const nep_ent_lists* lists, int32_t* d_flags, void* stream) {
+  if (!h || !d_prev || !d_records || !d_guess || (!d_ent && !lists)) return fail(NEP_E_ARG, "null argument");
+  if (lists && !ent_lists_complete(lists)) return fail(NEP_E_ARG, "null array in nep_ent_lists");
   if (n_intervals < 1 || n_intervals > h->cfg.num_pol) return fail(NEP_E_ARG, "n_intervals out of range (1..num_pol)");
   if (ent_samples < 1 || ent_samples > 8) return fail(NEP_E_ARG, "ent_samples out of range (1..8)");
   if (!h->cfg.enable_entangle) return fail(NEP_E_STATE, "handle created without enable_entangle");
@@ -1417,10 +1441,12 @@ int nep_batch_track_ent(nep_batch_t* h, const nep_traj_rec* d_prev, nep_traj_rec
   const int N = h->cfg.num_agents, S = h->cfg.n_scenes, np = h->cfg.num_pol;
   if (int e = ent_ready(h, "tether tracking with static obstacles needs nep_batch_set_static_reps first")) return e;
   if (!fleet_ent_fits(N, E.sp.n_static)) return fail(NEP_E_CAP, "the tether kernels take up to 4096 agents and 2048 static obstacles per scene");
+  if (lists && !ent_lists_cap_ok(lists->cap)) return fail(NEP_E_CAP, "nep_ent_lists: cap out of range (NEP_FE_ENT_CAP < cap <= NEP_ENT_LISTS_MAX_CAP)");
   const ProblemSet ps = round_set(h);
   if (int e = E.d_sampled.ensure((size_t)S * N * np * (ent_samples + 1) * 2)) return e;
   if (int e = E.d_present.ensure((size_t)S * N)) return e;
-  if (int e = E.d_track_save.ensure((size_t)S * N)) return e;
+  if (lists) { if (E.d_track_lsave.cap < lists->cap) if (int e = E.d_track_lsave.ensure((size_t)S * N, lists->cap)) return e; }
+  else if (int e = E.d_track_save.ensure((size_t)S * N)) return e;
   if (int e = E.d_track_flags.ensure((size_t)S * N)) return e;      // (whether or not this call passes d_flags: a later captured call may not)
   if (int e = E.d_track_pos.ensure((size_t)S * N * ((size_t)np * 8 + 1) * 2)) return e;      // (the largest call's: a later captured one may fly more steps)
   launch_ent_sample(d_records, S, N, &d_guess->t_start, (long)sizeof(nep_guess) * h->cfg.n_local, np, ent_samples, E.sp.T_span, E.d_sampled.p, E.d_present.p,
@@ -1434,8 +1460,36 @@ int nep_batch_track_ent(nep_batch_t* h, const nep_traj_rec* d_prev, nep_traj_rec
   ea.recs = d_records; ea.recs_out = d_records;
   ea.prev_n = (const char*)&d_prev->n_bend; ea.prev_xy = (const char*)&d_prev->bend[0][0]; ea.prev_n_stride = ea.prev_xy_stride = (long)sizeof(nep_traj_rec);
   ea.in = d_ent; ea.out = d_ent; ea.save = E.d_track_save.p; ea.flags = d_flags ? d_flags : E.d_track_flags.p; ea.gflags = ps.flags;
+  if (lists) { ea.lists = *lists; ea.lsave = E.d_track_lsave.view(); ea.lsave.cap = lists->cap; }      // (the scratch is indexed at the call's cap)
   launch_tether_steps(ea, FleetArgs{}, (hipStream_t)stream);
   launch_tether_publish(ea, false, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+}  // namespace
+
+int nep_batch_track_ent(nep_batch_t* h, const nep_traj_rec* d_prev, nep_traj_rec* d_records, const nep_guess* d_guess, int32_t n_intervals,
+                        int32_t ent_samples, double cable_length, nep_fe_ent_state* d_ent, int32_t* d_flags, void* stream) {
+  if (!d_ent) return fail(NEP_E_ARG, "null argument");
+  return track_ent_round(h, d_prev, d_records, d_guess, n_intervals, ent_samples, cable_length, d_ent, nullptr, d_flags, stream);
+}
+
+int nep_batch_track_ent_lists(nep_batch_t* h, const nep_traj_rec* d_prev, nep_traj_rec* d_records, const nep_guess* d_guess, int32_t n_intervals,
+                              int32_t ent_samples, double cable_length, const nep_ent_lists* d_lists, int32_t* d_flags, void* stream) {
+  if (!d_lists) return fail(NEP_E_ARG, "null argument");
+  return track_ent_round(h, d_prev, d_records, d_guess, n_intervals, ent_samples, cable_length, nullptr, d_lists, d_flags, stream);
+}
+
+int nep_batch_ent_lists_at_a(nep_batch_t* h, const nep_ent_lists* d_lists, nep_fe_ent_state* d_ent_a, int32_t* d_flags_a, const int32_t* d_mask_in,
+                             int32_t* d_mask_out, int32_t* d_held, void* stream) {
+  if (!h || !d_lists || !d_ent_a || !d_mask_out) return fail(NEP_E_ARG, "null argument");
+  if (!ent_lists_complete(d_lists)) return fail(NEP_E_ARG, "null array in nep_ent_lists");
+  if (!h->cfg.enable_entangle) return fail(NEP_E_STATE, "handle created without enable_entangle");
+  if (h->cfg.n_local != h->cfg.num_agents) return fail(NEP_E_STATE, "tether tracking runs on an unsharded handle (n_local == num_agents)");
+  if (!ent_lists_cap_ok(d_lists->cap)) return fail(NEP_E_CAP, "nep_ent_lists: cap out of range (NEP_FE_ENT_CAP < cap <= NEP_ENT_LISTS_MAX_CAP)");
+  TetherArgs ea{};
+  ea.N = h->cfg.num_agents; ea.n_scenes = h->cfg.n_scenes; ea.lists = *d_lists; ea.out = d_ent_a; ea.flags = d_flags_a; ea.held = d_held; ea.hold_mask = d_mask_out;
+  launch_ent_lists_at_a(ea, d_mask_in, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1489,6 +1543,7 @@ void fleet_ent_args(nep_batch_t* h, TetherArgs& ea) {
   ea.prev_n = (const char*)F.pub_prev_n.p; ea.prev_n_stride = (long)sizeof(int); ea.prev_xy = (const char*)F.pub_prev_xy.p; ea.prev_xy_stride = (long)sizeof(double) * NEP_MAX_BEND * 2;
   ea.in = F.ent.p; ea.out = F.ent.p; ea.save = F.ent_save.p; ea.flags = F.ent_flags.p; ea.ever = F.ent_ever.p; ea.walked = F.ent_walked.p;
   ea.counters = F.counters.p; ea.gflags = E.d_flags.p;
+  if (F.ent_cap) { ea.lists = F.ent_lists.view(); ea.lists.cap = F.ent_cap; ea.lsave = F.ent_lsave.view(); ea.lsave.cap = F.ent_cap; }
 }
 }  // namespace
 
@@ -1545,18 +1600,45 @@ int nep_batch_fleet_select(nep_batch_t* h, nep_fe_start* d_start, nep_traj_rec* 
   return 0;
 }
 
-int nep_batch_fleet_init_ent(nep_batch_t* h, double cable_length, const nep_fe_ent_state* d_ent0, void* stream) {
+namespace {
+// nep_batch_fleet_init_ent / nep_batch_fleet_init_ent_lists: the state from d_ent0 (device, fixed records; null = empty) or, with
+// host_lists, from host arrays in the list form (null arrays = empty)
+int fleet_init_ent_any(nep_batch_t* h, double cable_length, const nep_fe_ent_state* d_ent0, const nep_ent_lists* host_lists, void* stream) {
   if (int e = fleet_guard(h, true)) return e;
   if (!h->cfg.enable_entangle) return fail(NEP_E_STATE, "handle created without enable_entangle");
   Engine& E = h->eng;
   if (int e = ent_ready(h, "the fleet's tethers with static obstacles need nep_batch_set_static_reps first")) return e;
   if (!fleet_ent_fits(h->cfg.num_agents, E.sp.n_static)) return fail(NEP_E_CAP, "the fleet's tether kernels take up to 4096 agents and 2048 static obstacles per scene");
   if (!(cable_length > 0.0)) return fail(NEP_E_ARG, "cable_length must be positive");
+  const int cap = host_lists ? host_lists->cap : 0;
+  if (host_lists && !ent_lists_cap_ok(cap)) return fail(NEP_E_CAP, "nep_ent_lists: cap out of range (NEP_FE_ENT_CAP < cap <= NEP_ENT_LISTS_MAX_CAP)");
+  const bool seeded = host_lists && (host_lists->n_alpha || host_lists->n_bend || host_lists->id || host_lists->cs || host_lists->beta || host_lists->bend);
+  if (seeded && !ent_lists_complete(host_lists)) return fail(NEP_E_ARG, "nep_ent_lists: all arrays or none");
   nep_batch::Fleet& F = h->fleet;
   const size_t slots = (size_t)h->slots;
   hipStream_t st = (hipStream_t)stream;
   HIPCHK(hipStreamSynchronize(st));
-  F.ent_ready = false;
+  F.ent_ready = false; F.ent_cap = 0;
+  if (cap) {
+    if (F.ent_lists.cap < cap) if (int e = F.ent_lists.ensure(slots, cap)) return e;
+    if (F.ent_lsave.cap < cap) if (int e = F.ent_lsave.ensure(slots, cap)) return e;
+    if (int e = F.ent_held.ensure(slots)) return e;
+    for (ListBuf* b : {&F.ent_lists, &F.ent_lsave}) {
+      HIPCHK(hipMemsetAsync(b->n_alpha.p, 0, slots * sizeof(int), st)); HIPCHK(hipMemsetAsync(b->n_bend.p, 0, slots * sizeof(int), st));
+      HIPCHK(hipMemsetAsync(b->id.p, 0, slots * cap * sizeof(int16_t), st)); HIPCHK(hipMemsetAsync(b->cs.p, 0, slots * cap, st));
+      HIPCHK(hipMemsetAsync(b->beta.p, 0, slots * cap * sizeof(double), st)); HIPCHK(hipMemsetAsync(b->bend.p, 0, slots * NEP_MAX_BEND * sizeof(int16_t), st));
+    }
+    HIPCHK(hipMemsetAsync(F.ent_held.p, 0, slots * sizeof(int), st));
+    if (seeded) {
+      HIPCHK(hipStreamSynchronize(st));
+      HIPCHK(hipMemcpy(F.ent_lists.n_alpha.p, host_lists->n_alpha, slots * sizeof(int), hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(F.ent_lists.n_bend.p, host_lists->n_bend, slots * sizeof(int), hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(F.ent_lists.id.p, host_lists->id, slots * cap * sizeof(int16_t), hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(F.ent_lists.cs.p, host_lists->cs, slots * cap, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(F.ent_lists.beta.p, host_lists->beta, slots * cap * sizeof(double), hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(F.ent_lists.bend.p, host_lists->bend, slots * NEP_MAX_BEND * sizeof(int16_t), hipMemcpyHostToDevice));
+    }
+  }
   if (int e = F.ent.ensure(slots)) return e;
   if (int e = F.ent_save.ensure(slots)) return e;
   if (int e = F.pub_xy.ensure(slots * NEP_MAX_BEND * 2)) return e;
@@ -1572,8 +1654,19 @@ int nep_batch_fleet_init_ent(nep_batch_t* h, double cable_length, const nep_fe_e
   for (DevBuf<int>* b : {&F.pub_n, &F.pub_prev_n, &F.ent_flags, &F.ent_ever, &F.ent_walked, &F.ent_flags_a})
     HIPCHK(hipMemsetAsync(b->p, 0, slots * sizeof(int), st));
   HIPCHK(hipStreamSynchronize(st));
-  F.cable = cable_length; F.ent_ready = true;
+  F.cable = cable_length; F.ent_cap = cap; F.ent_ready = true;
   return 0;
+}
+}  // namespace
+
+int nep_batch_fleet_init_ent(nep_batch_t* h, double cable_length, const nep_fe_ent_state* d_ent0, void* stream) {
+  return fleet_init_ent_any(h, cable_length, d_ent0, nullptr, stream);
+}
+
+int nep_batch_fleet_init_ent_lists(nep_batch_t* h, double cable_length, const nep_ent_lists* host_lists, void* stream) {
+  if (int e = fleet_guard(h, true)) return e;
+  if (!host_lists) return fail(NEP_E_ARG, "null argument");
+  return fleet_init_ent_any(h, cable_length, nullptr, host_lists, stream);
 }
 
 int nep_batch_fleet_predict_ent(nep_batch_t* h, const nep_fe_start* d_start, const nep_traj_rec* d_records, nep_fe_ent_state* d_ent_a,
@@ -1581,10 +1674,12 @@ int nep_batch_fleet_predict_ent(nep_batch_t* h, const nep_fe_start* d_start, con
   if (int e = fleet_guard(h, true)) return e;
   if (!h->fleet.ent_ready) return fail(NEP_E_STATE, "nep_batch_fleet_init_ent has not run on this handle");
   if (!d_start || !d_records || !d_ent_a) return fail(NEP_E_ARG, "null argument");
+  if (h->fleet.ent_cap && !h->eng.active) return fail(NEP_E_STATE, "a prediction in the list form needs the round's mask (nep_batch_set_active): a state that does not fit the fixed record holds its slot");
   FleetArgs fa{};
   fleet_args(h, fa);
   TetherArgs ea{};
   fleet_ent_args(h, ea);
+  if (h->fleet.ent_cap) { ea.held = h->fleet.ent_held.p; ea.hold_mask = const_cast<int*>(h->eng.active); }
   ea.n_steps = 1; ea.start = d_start; ea.recs = d_records; ea.out = d_ent_a; ea.flags = d_flags_a ? d_flags_a : h->fleet.ent_flags_a.p;
   ea.prev_n = nullptr; ea.prev_xy = nullptr; ea.ever = nullptr; ea.walked = nullptr; ea.counters = nullptr;
   launch_tether_steps(ea, fa, (hipStream_t)stream);
@@ -1608,12 +1703,50 @@ int nep_batch_fleet_track_ent(nep_batch_t* h, const nep_traj_rec* d_records, int
   return 0;
 }
 
+namespace {
+int fleet_lists_to_host(const ListBuf& B, size_t slots, size_t cap, nep_ent_lists* out) {
+  HIPCHK(hipMemcpy(out->n_alpha, B.n_alpha.p, slots * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out->n_bend, B.n_bend.p, slots * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out->id, B.id.p, slots * cap * sizeof(int16_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out->cs, B.cs.p, slots * cap, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out->beta, B.beta.p, slots * cap * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out->bend, B.bend.p, slots * NEP_MAX_BEND * sizeof(int16_t), hipMemcpyDeviceToHost));
+  return 0;
+}
+}  // namespace
+
+// the handle's tether states in the list form (blocking): host_out's arrays of host_out->cap == the handle's cap entries per slot
+int nep_batch_fleet_ent_lists(nep_batch_t* h, nep_ent_lists* host_out, int32_t* held_rounds_out) {
+  if (int e = fleet_guard(h, true)) return e;
+  nep_batch::Fleet& F = h->fleet;
+  if (!F.ent_ready || !F.ent_cap) return fail(NEP_E_STATE, "nep_batch_fleet_init_ent_lists has not run on this handle");
+  if (host_out && (host_out->cap != F.ent_cap || !ent_lists_complete(host_out))) return fail(NEP_E_ARG, "host_out: cap must be the handle's, every array present");
+  HIPCHK(hipDeviceSynchronize());
+  if (host_out) if (int e = fleet_lists_to_host(F.ent_lists, (size_t)h->slots, (size_t)F.ent_cap, host_out)) return e;
+  if (held_rounds_out) HIPCHK(hipMemcpy(held_rounds_out, F.ent_held.p, (size_t)h->slots * sizeof(int), hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int nep_batch_fleet_ent_state(nep_batch_t* h, nep_fe_ent_state* states_out, int32_t* flags_round_out, int32_t* flags_ever_out, int32_t* walked_out) {
   if (int e = fleet_guard(h, true)) return e;
   nep_batch::Fleet& F = h->fleet;
   if (!F.ent_ready) return fail(NEP_E_STATE, "nep_batch_fleet_init_ent has not run on this handle");
   const size_t slots = (size_t)h->slots;
   HIPCHK(hipDeviceSynchronize());
+  if (states_out && F.ent_cap) {      // the list form: the slots that fit as fixed records, the others marked n_alpha = -1
+    const size_t cap = (size_t)F.ent_cap;
+    std::vector<int> na(slots), nb(slots); std::vector<int16_t> id(slots * cap), bend(slots * NEP_MAX_BEND); std::vector<int8_t> cs(slots * cap); std::vector<double> beta(slots * cap);
+    nep_ent_lists hl{}; hl.cap = F.ent_cap; hl.n_alpha = na.data(); hl.n_bend = nb.data(); hl.id = id.data(); hl.cs = cs.data(); hl.beta = beta.data(); hl.bend = bend.data();
+    if (int e = fleet_lists_to_host(F.ent_lists, slots, cap, &hl)) return e;
+    std::memset(states_out, 0, slots * sizeof(nep_fe_ent_state));
+    for (size_t s = 0; s < slots; s++) {
+      nep_fe_ent_state& o = states_out[s];
+      if (na[s] < 0 || na[s] > NEP_FE_ENT_CAP || nb[s] < 0 || nb[s] > NEP_MAX_BEND) { o.n_alpha = -1; continue; }
+      o.n_alpha = na[s]; o.n_bend = nb[s];
+      for (int i = 0; i < na[s]; i++) { o.id[i] = id[s * cap + i]; o.cs[i] = cs[s * cap + i]; o.beta[i] = beta[s * cap + i]; }
+      for (int i = 0; i < nb[s]; i++) o.bend[i] = (int8_t)bend[s * NEP_MAX_BEND + i];
+    }
+  } else
   if (states_out) HIPCHK(hipMemcpy(states_out, F.ent.p, slots * sizeof(nep_fe_ent_state), hipMemcpyDeviceToHost));
   if (flags_round_out) HIPCHK(hipMemcpy(flags_round_out, F.ent_flags.p, slots * sizeof(int), hipMemcpyDeviceToHost));
   if (flags_ever_out) HIPCHK(hipMemcpy(flags_ever_out, F.ent_ever.p, slots * sizeof(int), hipMemcpyDeviceToHost));
@@ -2196,6 +2329,7 @@ int nep_abi_sizeof(int32_t which) {
     case 18: return (int)sizeof(nep_fleet_cfg);
     case 20: return (int)sizeof(nep_mission_cfg);      // (19 stays unassigned: tests/test_fleet_plan_cpu.py pins it to -1)
     case 21: return (int)sizeof(nep_mission_leg);
+    case 23: return (int)sizeof(nep_ent_lists);      // (22 stays unassigned: tests/test_fleet_mission_cpu.py pins it to -1)
     default: return -1;
   }
 }

@@ -789,6 +789,25 @@ template <> struct ent_tr<EntLds> {
 template <> __device__ __forceinline__ bool ent_sig_may_have<EntLds>(const EntLds* st, int id) { return (st->sig >> (id & 63)) & 1ull; }
 template <> __device__ __forceinline__ void ent_sig_add<EntLds>(EntLds* st, int id) { st->sig |= 1ull << (id & 63); }
 template <> __device__ __forceinline__ unsigned long long ent_sig_of<EntLds>(const EntLds* st) { return st->sig; }
+// The list form of the tracked state (nep_ent_lists, include/neptune_frontend.h) while tether_step_lists_kernel works on it: one
+// slot's list in dynamic LDS behind LDS-typed pointers, `cap` entries — [beta[cap] | id[cap] | bend[NEP_MAX_BEND] (16 bit) | cs[cap]],
+// 11 bytes per entry plus the bend indices — counts in registers.  Betas handled as written, like the fixed record's view.
+typedef __attribute__((address_space(3))) double* ent_lds_double;
+struct EntListLds { int n_alpha, n_bend; ent_lds_short id; ent_lds_char cs; ent_lds_double beta; ent_lds_short bend; int cap; };
+template <> struct ent_tr<EntListLds> {
+  typedef short bend_t;
+  static __device__ __forceinline__ int cap(const EntListLds* st) { return st->cap; }
+  static __device__ __forceinline__ int bend_cap(const EntListLds*) { return NEP_MAX_BEND; }
+};
+__host__ __device__ constexpr size_t ent_list_lds_bytes(int cap) { return (size_t)cap * 11 + NEP_MAX_BEND * 2; }
+// ent_state_ok for slot `slot` of the list form: counts within cap and the bend points a record publishes, bend indices on the list
+__device__ bool ent_lists_ok(const nep_ent_lists& L, long slot) {
+  const int na = L.n_alpha[slot], nb = L.n_bend[slot];
+  if (na < 0 || na > L.cap || nb < 0 || nb > NEP_MAX_BEND - 1) return false;
+  const short* b = L.bend + slot * NEP_MAX_BEND;
+  for (int k = 0; k < nb; k++) if (b[k] < 0 || b[k] >= na) return false;
+  return true;
+}
 constexpr int kEntLdsBytes = ((NEP_FE_ENT_CAP * 3 + NEP_MAX_BEND + 3) & ~3) | 4;      // per thread; an odd number of dwords, so that the threads' lists fall into different banks
 // (false: the record is a big record's marker, or holds more than the view takes — the caller goes to the big form)
 __device__ __forceinline__ bool ent_lds_load(EntLds& L, const nep_fe_ent_state* __restrict__ src, int N) {

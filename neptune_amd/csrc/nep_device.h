@@ -317,6 +317,12 @@ struct TetherArgs {
   const nep_fe_ent_state* in;    // [slots] the state at the tracked position
   nep_fe_ent_state* out;         // [slots] tracking: the same buffer; prediction: the state at A
   nep_fe_ent_state* save;        // [slots] scratch: the state before a step that may outgrow the record
+  // the list form (tether_step_lists_kernel, the publish kernels): lists.cap != 0 = the state is there, not in `in` — tracked in place;
+  // a prediction reads it and writes the fixed record at A into `out`
+  nep_ent_lists lists;           // device arrays, [slots] and [slots][cap]
+  nep_ent_lists lsave;           // scratch of the same form (id, cs, beta, bend; the counts stay in registers)
+  int* held;                     // [slots] prediction in the list form: rounds the slot's state at A did not fit the fixed record, or null
+  int* hold_mask;                // [slots] ... the round's active mask, cleared for such a slot, or null
   int* flags;                    // [slots] NEP_ENT_TRACK_* bits of the call
   int* ever;                     // [slots] sticky OR (the fleet's tracking) or null
   int* walked;                   // [slots] (other agent, step) pairs walked, accumulated (the fleet's tracking) or null
@@ -325,6 +331,7 @@ struct TetherArgs {
 };
 bool fleet_ent_fits(int N, int S);
 void launch_tether_publish(const TetherArgs& ea, bool fleet, hipStream_t st);      // (fleet: nep_batch_fleet_select's contract, else nep_batch_track_ent's)
+void launch_ent_lists_at_a(const TetherArgs& ea, const int* mask_in, hipStream_t st);      // (reads lists, n_scenes, N; writes out, flags, held, hold_mask)
 void launch_tether_steps(const TetherArgs& ea, const FleetArgs& fa, hipStream_t st);      // (fa: read by the fleet's two position modes only)
 void launch_ent_check(const SceneParams& sp, const ProblemSet& ps, const FeEntArgs& ea, const nep_traj_rec* fresh, int n_scenes, double cable, int* entangles, hipStream_t st);
 void launch_next_starts(const nep_traj_rec* recs, int n_scenes, int N, int first_local, int n_local, double dt, nep_fe_start* starts,

@@ -1,5 +1,6 @@
 // tether_kernels.hip — every tether's entangle state carried along what its agent flies: between two bulk-synchronous rounds
-// (nep_batch_track_ent, include/neptune_frontend.h) and in the device fleet loop (nep_batch_fleet_init_ent / _predict_ent /
+// (nep_batch_track_ent and, on lists of more than NEP_FE_ENT_CAP crossings, nep_batch_track_ent_lists / nep_batch_ent_lists_at_a;
+// include/neptune_frontend.h) and in the device fleet loop (nep_batch_fleet_init_ent / _predict_ent /
 // _track_ent and the bend points nep_batch_fleet_select publishes; include/neptune_fleet.h).
 //
 // Two steps of the reference:
@@ -20,6 +21,8 @@
 // kernel arguments and on values every lane loads from the same address.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "nep_device.h"
 #include "../../include/neptune_frontend.h"
 #include "../../include/neptune_entangle.h"
@@ -37,7 +40,6 @@ namespace {
 constexpr int kMaskWords = 64;      // 64-bit ballot words of the candidates' mask: up to 4096 agents (fleet_ent_fits: refused beyond)
 constexpr int kStatWords = 64;      // 32-bit words of the statics' mask (EntCtx::m_static): up to 2048 statics
 
-typedef __attribute__((address_space(3))) double* ent_lds_double;
 // The working state: nep_fe_ent_state's members behind LDS-typed pointers (counts in registers).  Betas handled as written, like the
 // fixed record: every byte of the result is compared with the host chain.
 struct EntWork { int n_alpha, n_bend; ent_lds_short id; ent_lds_char cs; ent_lds_double beta; ent_lds_char bend; };
@@ -52,6 +54,22 @@ __device__ __forceinline__ EntCtx publish_ctx(const TetherArgs& ea, int scene) {
   EntCtx ec{};
   ec.N = ea.N; ec.S = ea.S; ec.pb = ea.pb; ec.srep = ea.srep + (long)scene * ea.static_stride * 4;
   return ec;
+}
+
+// The bend anchors a slot publishes, from either form of its state (TetherArgs::lists.cap != 0: the list form): f(k, id, cs) for
+// every bend index k in order -> the state's n_bend, or -1 for a state that is no valid input to the tracking.
+template <class F> __device__ __forceinline__ int publish_bends(const TetherArgs& ea, long slot, F f) {
+  if (ea.lists.cap) {
+    const nep_ent_lists& L = ea.lists;
+    if (!ent_lists_ok(L, slot)) return -1;
+    const int nb = L.n_bend[slot];
+    for (int k = 0; k < nb; k++) { const long e = slot * L.cap + L.bend[slot * NEP_MAX_BEND + k]; f(k, (int)L.id[e], (int)L.cs[e]); }
+    return nb;
+  }
+  const nep_fe_ent_state* st = ea.in + slot;
+  if (!ent_state_ok(st)) return -1;
+  for (int k = 0; k < st->n_bend; k++) f(k, (int)st->id[st->bend[k]], (int)st->cs[st->bend[k]]);
+  return st->n_bend;
 }
 
 // One thread per (slot, position).  Between rounds (sampled != null): position q = itv * ns + j of a slot is ent_sample_kernel's
@@ -116,18 +134,13 @@ __global__ void fleet_ent_publish_kernel(TetherArgs ea) {
   double* cur = ea.pub_xy + slot * NEP_MAX_BEND * 2; double* prv = ea.pub_prev_xy + slot * NEP_MAX_BEND * 2;
   for (int k = 0; k < NEP_MAX_BEND * 2; k++) prv[k] = cur[k];
   ea.pub_prev_n[slot] = ea.pub_n[slot];
-  const nep_fe_ent_state* st = ea.in + slot;
   const EntCtx ec = publish_ctx(ea, scene);
   nep_traj_rec* r = ea.recs_out + slot;
-  int nb = 1;
   cur[0] = ea.pb[2 * a]; cur[1] = ea.pb[2 * a + 1];
-  if (ent_state_ok(st)) {
-    for (int k = 0; k < st->n_bend; k++) {
-      const Ev2 b = ent_publish_point(st->id[st->bend[k]], st->cs[st->bend[k]], ec);
-      cur[2 * (k + 1)] = b.x; cur[2 * (k + 1) + 1] = b.y;
-    }
-    nb = 1 + st->n_bend;
-  }
+  const int nb = 1 + max(publish_bends(ea, slot, [&](int k, int id, int cs) {
+    const Ev2 b = ent_publish_point(id, cs, ec);
+    cur[2 * (k + 1)] = b.x; cur[2 * (k + 1) + 1] = b.y;
+  }), 0);
   for (int k = nb; k < NEP_MAX_BEND; k++) { cur[2 * k] = 0.0; cur[2 * k + 1] = 0.0; }
   ea.pub_n[slot] = nb;
   r->n_bend = nb;
@@ -142,21 +155,28 @@ __global__ void ent_publish_kernel(TetherArgs ea) {
   const int N = ea.N;
   if (slot >= (long)ea.n_scenes * N) return;
   nep_traj_rec* r = ea.recs_out + slot;
-  const nep_fe_ent_state* st = ea.in + slot;
-  if (!rec_present(r) || !ent_state_ok(st)) return;
+  if (!rec_present(r)) return;
   const int scene = (int)(slot / N), a = (int)(slot % N);
   const EntCtx ec = publish_ctx(ea, scene);
-  r->bend[0][0] = ea.pb[2 * a]; r->bend[0][1] = ea.pb[2 * a + 1];
-  for (int k = 0; k < st->n_bend; k++) {
-    const Ev2 b = ent_publish_point(st->id[st->bend[k]], st->cs[st->bend[k]], ec);
+  // (an invalid state writes nothing: the walk below has not run, and the base is written after it)
+  const int nbs = publish_bends(ea, slot, [&](int k, int id, int cs) {
+    const Ev2 b = ent_publish_point(id, cs, ec);
     r->bend[k + 1][0] = b.x; r->bend[k + 1][1] = b.y;
-  }
-  r->n_bend = 1 + st->n_bend;
+  });
+  if (nbs < 0) return;
+  r->bend[0][0] = ea.pb[2 * a]; r->bend[0][1] = ea.pb[2 * a + 1];
+  r->n_bend = 1 + nbs;
 }
 
-// One wave per slot: n_steps moves of the slot's own tether state (see the head of the file).
-__global__ __launch_bounds__(64) void tether_step_kernel(TetherArgs ea) {
-  __shared__ __attribute__((aligned(16))) nep_fe_ent_state s_st;
+// One wave per slot: n_steps moves of the slot's own tether state (see the head of the file).  Two forms of the state, one body:
+// LISTS = false, the fixed record (ea.in / out / save), copied whole into LDS; LISTS = true, the list form (ea.lists, in place; scratch
+// ea.lsave), one slot's list of ea.lists.cap entries in dynamic LDS (EntListLds).  A prediction in the list form leaves the lists alone
+// and writes the fixed record at A the front end takes — or, where the result holds more than NEP_FE_ENT_CAP crossings, a zeroed one
+// with NEP_ENT_TRACK_HELD, and takes the slot out of the round's active mask.
+extern __shared__ __attribute__((aligned(16))) unsigned char s_ent_list[];
+template <bool LISTS> __device__ __forceinline__ void tether_step(const TetherArgs& ea) {
+  __shared__ __attribute__((aligned(16))) nep_fe_ent_state s_st;      // (LISTS: unused)
+  __shared__ int s_cnt[2];                                            // (LISTS: the counts after the walk)
   __shared__ unsigned long long s_mask[kMaskWords], s_chg[kMaskWords];
   __shared__ unsigned s_stat[kStatWords];
   const long slot = blockIdx.x;
@@ -171,6 +191,28 @@ __global__ __launch_bounds__(64) void tether_step_kernel(TetherArgs ea) {
     if (lane == 0) ea.flags[slot] = 0;
     return;
   }
+  const nep_ent_lists& L = ea.lists;
+  const int cap = LISTS ? L.cap : NEP_FE_ENT_CAP;
+  int n_in = 0;
+  EntListLds WL{};
+  if constexpr (LISTS) {
+    if (!ent_lists_ok(L, slot)) {      // (every lane reads the same counts and indices: a uniform branch.  The lists stay; a prediction plans from an empty record)
+      if (predict) for (int i = lane; i < (int)(sizeof(nep_fe_ent_state) / 4); i += 64) ((int*)dst)[i] = 0;
+      if (lane == 0) {
+        ea.flags[slot] = NEP_ENT_TRACK_CAP;
+        if (ea.ever) ea.ever[slot] |= NEP_ENT_TRACK_CAP;
+        atomicOr(ea.gflags, NEP_FLAG_ENT_TRACK);
+      }
+      return;
+    }
+    n_in = L.n_alpha[slot];
+    WL.n_alpha = n_in; WL.n_bend = L.n_bend[slot]; WL.cap = cap;
+    WL.beta = (ent_lds_double)&s_ent_list[0]; WL.id = (ent_lds_short)&s_ent_list[8 * (size_t)cap];
+    WL.bend = (ent_lds_short)&s_ent_list[10 * (size_t)cap]; WL.cs = (ent_lds_char)&s_ent_list[10 * (size_t)cap + 2 * NEP_MAX_BEND];
+    for (int i = lane; i < n_in; i += 64) { const long e = slot * cap + i; WL.id[i] = L.id[e]; WL.cs[i] = L.cs[e]; WL.beta[i] = L.beta[e]; }
+    if (lane < NEP_MAX_BEND) WL.bend[lane] = lane < WL.n_bend ? L.bend[slot * NEP_MAX_BEND + lane] : (short)0;
+    // (lane 0 reads the list after the barrier that ends the proofs)
+  } else {
   for (int i = lane; i < (int)(sizeof(nep_fe_ent_state) / 4); i += 64) ((int*)&s_st)[i] = ((const int*)src)[i];
   __syncthreads();
   if (!ent_state_ok(&s_st)) {      // (s_st is the same for every lane: a uniform branch.  The state stays; a prediction hands it on as it is)
@@ -181,6 +223,7 @@ __global__ __launch_bounds__(64) void tether_step_kernel(TetherArgs ea) {
       atomicOr(ea.gflags, NEP_FLAG_ENT_TRACK);
     }
     return;
+  }
   }
   EntCtx ec;
   ec.N = N; ec.S = ea.S; ec.own = a; ec.num_pol = ea.num_pol; ec.ns = 1; ec.T_span = 0.0; ec.cable = ea.cable;
@@ -237,19 +280,40 @@ __global__ __launch_bounds__(64) void tether_step_kernel(TetherArgs ea) {
   // ---- the walk: lane 0, step by step, the survivors in increasing index ---------------------------------------------------
   if (lane == 0) {
     ec.m_static = s_stat;
-    EntWork W;
-    W.n_alpha = s_st.n_alpha; W.n_bend = s_st.n_bend;
-    W.id = (ent_lds_short)&s_st.id[0]; W.cs = (ent_lds_char)&s_st.cs[0]; W.beta = (ent_lds_double)&s_st.beta[0]; W.bend = (ent_lds_char)&s_st.bend[0];
-    nep_fe_ent_state* B = ea.save + slot;
+    typename std::conditional<LISTS, EntListLds, EntWork>::type W;
+    // the scratch a dropped move comes back from: the fixed record's in ea.save, the list form's in ea.lsave (counts in registers)
+    nep_fe_ent_state* B = nullptr;
+    short* b_id = nullptr; signed char* b_cs = nullptr; double* b_beta = nullptr; short* b_bend = nullptr;
+    int b_na = 0, b_nb = 0;
+    if constexpr (LISTS) {
+      W = WL;
+      b_id = ea.lsave.id + slot * cap; b_cs = ea.lsave.cs + slot * cap; b_beta = ea.lsave.beta + slot * cap; b_bend = ea.lsave.bend + slot * NEP_MAX_BEND;
+    } else {
+      W.n_alpha = s_st.n_alpha; W.n_bend = s_st.n_bend;
+      W.id = (ent_lds_short)&s_st.id[0]; W.cs = (ent_lds_char)&s_st.cs[0]; W.beta = (ent_lds_double)&s_st.beta[0]; W.bend = (ent_lds_char)&s_st.bend[0];
+      B = ea.save + slot;
+    }
     auto save = [&]() {
+      if constexpr (LISTS) {
+        b_na = W.n_alpha; b_nb = W.n_bend;
+        for (int i = 0; i < W.n_alpha; i++) { b_id[i] = W.id[i]; b_cs[i] = W.cs[i]; b_beta[i] = W.beta[i]; }
+        for (int i = 0; i < W.n_bend; i++) b_bend[i] = W.bend[i];
+      } else {
       B->n_alpha = W.n_alpha; B->n_bend = W.n_bend;
       for (int i = 0; i < W.n_alpha; i++) { B->id[i] = W.id[i]; B->cs[i] = W.cs[i]; B->beta[i] = W.beta[i]; }
       for (int i = 0; i < W.n_bend; i++) B->bend[i] = W.bend[i];
+      }
     };
     auto restore = [&]() {
+      if constexpr (LISTS) {
+        W.n_alpha = b_na; W.n_bend = b_nb;
+        for (int i = 0; i < W.n_alpha; i++) { W.id[i] = b_id[i]; W.cs[i] = b_cs[i]; W.beta[i] = b_beta[i]; }
+        for (int i = 0; i < W.n_bend; i++) W.bend[i] = b_bend[i];
+      } else {
       W.n_alpha = B->n_alpha; W.n_bend = B->n_bend;
       for (int i = 0; i < W.n_alpha; i++) { W.id[i] = B->id[i]; W.cs[i] = B->cs[i]; W.beta[i] = B->beta[i]; }
       for (int i = 0; i < W.n_bend; i++) W.bend[i] = B->bend[i];
+      }
     };
     unsigned add_tail[kEntAddCap - EntAdd::reg];
     int fl = 0, walked = 0;
@@ -279,17 +343,72 @@ __global__ __launch_bounds__(64) void tether_step_kernel(TetherArgs ea) {
       fl |= ent_track_move(add, &W, save, restore, pk, pk1, pb_self, ec, ea.cable, abort);
       pk = pk1;
     }
+    if constexpr (LISTS) {
+      for (int i = W.n_bend; i < NEP_MAX_BEND; i++) W.bend[i] = 0;
+      s_cnt[0] = W.n_alpha; s_cnt[1] = W.n_bend;
+      if (predict && W.n_alpha > NEP_FE_ENT_CAP) {      // the state at A does not fit the record the front end takes: the slot sits this round out
+        fl |= NEP_ENT_TRACK_HELD;
+        if (ea.held) ea.held[slot] += 1;
+        if (ea.hold_mask) ea.hold_mask[slot] = 0;
+      }
+    } else {
     // what the record holds beyond its counts is zero: the bytes of a state depend on the state alone
     for (int i = W.n_alpha; i < NEP_FE_ENT_CAP; i++) { W.id[i] = 0; W.cs[i] = 0; W.beta[i] = 0.0; }
     for (int i = W.n_bend; i < NEP_MAX_BEND; i++) W.bend[i] = 0;
     s_st.n_alpha = W.n_alpha; s_st.n_bend = W.n_bend;
+    }
     ea.flags[slot] = fl;
     if (ea.ever) ea.ever[slot] |= fl;
     if (ea.walked) ea.walked[slot] += walked;
     if (fl & NEP_ENT_TRACK_CAP) atomicOr(ea.gflags, NEP_FLAG_ENT_TRACK);
   }
   __syncthreads();
+  if constexpr (LISTS) {
+    const int n_out = s_cnt[0], nb_out = s_cnt[1];
+    if (predict) {      // the fixed record at A: the list where it fits, zeros where it does not (and beyond the counts)
+      const bool fits = n_out <= NEP_FE_ENT_CAP;
+      for (int i = lane; i < NEP_FE_ENT_CAP; i += 64) {
+        const bool on = fits && i < n_out;
+        dst->id[i] = on ? (short)WL.id[i] : (short)0; dst->cs[i] = on ? (signed char)WL.cs[i] : (signed char)0; dst->beta[i] = on ? (double)WL.beta[i] : 0.0;
+      }
+      if (lane < NEP_MAX_BEND) dst->bend[lane] = fits && lane < nb_out ? (signed char)WL.bend[lane] : (signed char)0;
+      if (lane == 0) { dst->n_alpha = fits ? n_out : 0; dst->n_bend = fits ? nb_out : 0; }
+    } else {            // the lists in place; what a shorter list leaves behind is zeroed (beyond n_in they are zero as they came)
+      for (int i = lane; i < max(n_out, n_in); i += 64) {
+        const long e = slot * cap + i; const bool on = i < n_out;
+        L.id[e] = on ? (short)WL.id[i] : (short)0; L.cs[e] = on ? (signed char)WL.cs[i] : (signed char)0; L.beta[e] = on ? (double)WL.beta[i] : 0.0;
+      }
+      if (lane < NEP_MAX_BEND) L.bend[slot * NEP_MAX_BEND + lane] = WL.bend[lane];
+      if (lane == 0) { L.n_alpha[slot] = n_out; L.n_bend[slot] = nb_out; }
+    }
+  } else {
   for (int i = lane; i < (int)(sizeof(nep_fe_ent_state) / 4); i += 64) ((int*)dst)[i] = ((const int*)&s_st)[i];
+  }
+}
+__global__ __launch_bounds__(64) void tether_step_kernel(TetherArgs ea) { tether_step<false>(ea); }
+__global__ __launch_bounds__(64) void tether_step_lists_kernel(TetherArgs ea) { tether_step<true>(ea); }
+
+// The bulk-synchronous loop's state at A from the list form (nep_batch_ent_lists_at_a), one thread per slot: the fixed record where the
+// list fits it; where it holds more than NEP_FE_ENT_CAP crossings a zeroed record, NEP_ENT_TRACK_HELD, one more held round and a
+// cleared entry in the round's mask — the rule of the fleet's prediction.  A malformed list gives a zeroed record and is not held:
+// the tracking flags it.
+__global__ void ent_lists_at_a_kernel(TetherArgs ea, const int* mask_in) {
+  const long slot = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (slot >= (long)ea.n_scenes * ea.N) return;
+  const nep_ent_lists& L = ea.lists;
+  nep_fe_ent_state* dst = ea.out + slot;
+  const bool ok = ent_lists_ok(L, slot);
+  const int na = ok ? L.n_alpha[slot] : 0, nb = ok ? L.n_bend[slot] : 0;
+  const bool fits = na <= NEP_FE_ENT_CAP;
+  dst->n_alpha = fits ? na : 0; dst->n_bend = fits ? nb : 0;
+  for (int i = 0; i < NEP_FE_ENT_CAP; i++) {
+    const bool on = fits && i < na; const long e = slot * L.cap + i;
+    dst->id[i] = on ? L.id[e] : (short)0; dst->cs[i] = on ? L.cs[e] : (signed char)0; dst->beta[i] = on ? L.beta[e] : 0.0;
+  }
+  for (int k = 0; k < NEP_MAX_BEND; k++) dst->bend[k] = fits && k < nb ? (signed char)L.bend[slot * NEP_MAX_BEND + k] : (signed char)0;
+  if (ea.flags) ea.flags[slot] = fits ? 0 : NEP_ENT_TRACK_HELD;
+  if (!fits && ea.held) ea.held[slot] += 1;
+  ea.hold_mask[slot] = (mask_in ? mask_in[slot] != 0 : true) && fits ? 1 : 0;
 }
 
 // One wave per scene: the slots ever flagged NEP_ENT_TRACK_ENTANGLED, into the scene's counter [7] (no atomics: recounted per call)
@@ -310,12 +429,18 @@ void launch_tether_publish(const TetherArgs& ea, bool fleet, hipStream_t st) {
   if (slots <= 0) return;
   hipLaunchKernelGGL(fleet ? fleet_ent_publish_kernel : ent_publish_kernel, dim3((unsigned)((slots + 63) / 64)), dim3(64), 0, st, ea);
 }
+void launch_ent_lists_at_a(const TetherArgs& ea, const int* mask_in, hipStream_t st) {
+  const long slots = (long)ea.n_scenes * ea.N;
+  if (slots <= 0) return;
+  hipLaunchKernelGGL(ent_lists_at_a_kernel, dim3((unsigned)((slots + 63) / 64)), dim3(64), 0, st, ea, mask_in);
+}
 void launch_tether_steps(const TetherArgs& ea, const FleetArgs& fa, hipStream_t st) {
   const long slots = (long)ea.n_scenes * ea.N;
   if (slots <= 0) return;
   const long total = slots * (ea.n_steps + 1);
   hipLaunchKernelGGL(tether_pos_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, ea, fa);
-  hipLaunchKernelGGL(tether_step_kernel, dim3((unsigned)slots), dim3(64), 0, st, ea);
+  if (ea.lists.cap) hipLaunchKernelGGL(tether_step_lists_kernel, dim3((unsigned)slots), dim3(64), ent_list_lds_bytes(ea.lists.cap), st, ea);
+  else hipLaunchKernelGGL(tether_step_kernel, dim3((unsigned)slots), dim3(64), 0, st, ea);
   if (ea.ever && ea.counters) hipLaunchKernelGGL(fleet_ent_count_kernel, dim3((unsigned)ea.n_scenes), dim3(64), 0, st, ea);
 }
 

@@ -360,6 +360,11 @@ class DeviceFleetLoop(_Audited):
     with the state at A (d_ent_a) predicted on the device and the commit records stamped with the published bend points before the
     safety pass (stamp_bends).  check=False keeps the plain front end and safety pass and leaves the tracking on: what the
     same fleet does to its tethers when nobody looks.  report() then also gives ever_entangled, too_long and track_cap per scene.
+    ent_cap=K (or "auto": 2 (N + statics)) carries the tether states in the list form of K entries per slot (DESIGN section 24;
+    ent_lists0: an abi.EntLists to seed them from) instead of the 40-entry record; the default None is the fixed record's round,
+    unchanged.  A slot whose state at A holds more than 40 crossings is held for the round: fleet_predict_ent clears its entry in
+    the round's mask — fleet_select's with periods or phases, else an all-ones mask of the loop's own that is refilled inside the
+    round before the prediction — and it comes out skipped.  report() then adds `held` (slot-rounds), `max_list` (the longest list now) and `bend_full` (tethers at the bend-point limit) per scene.
 
     missions=mission.MissionSpec(...) flies a campaign: fleet_mission goes between the commit (audit, tether
     tracking) and fleet_tick, ends legs (mode "agent": NeptuneRos::autoCMD) or runs (mode "runs": benchmark_mtlp.py) and draws
@@ -368,7 +373,8 @@ class DeviceFleetLoop(_Audited):
     without a goal, mean leg time and length, the success rate.  Without missions nothing of this is allocated or launched."""
 
     def __init__(self, scenes, beam_width=32, delta_t_states=6, replan_every=5, periods=None, phases=None, audit=False, graph=True,
-                 goals=None, device=None, ring_cap=0, trace=False, tethers=False, check=True, ent_samples=3, missions=None):
+                 goals=None, device=None, ring_cap=0, trace=False, tethers=False, check=True, ent_samples=3, missions=None, ent_cap=None,
+                 ent_lists0=None):
         import torch
         self.torch = torch
         self.scenes = scenes
@@ -418,8 +424,18 @@ class DeviceFleetLoop(_Audited):
         if audit:
             self.d_audit = be.new_audit()
             be.audit(self.d_rec, self.d_clock, p.dc, 0, self.d_audit)      # (the call that allocates: made here, outside any capture)
+        self.ent_cap = None
+        self.d_hold = None
+        if tethers and ent_cap is not None:
+            self.ent_cap = 2 * (N + len(scenes[0]["statics"])) if ent_cap == "auto" else int(ent_cap)
+            if not self.masked:      # the mask a held slot is cleared in: the loop's own, refilled inside the round
+                self.d_hold = torch.ones((S, N), dtype=torch.int32, device=dev)
+                be.set_active(self.d_hold)
         if tethers:
-            be.fleet_init_ent()
+            if self.ent_cap is not None:
+                be.fleet_init_ent_lists(self.ent_cap, host=ent_lists0)
+            else:
+                be.fleet_init_ent()
             self.d_ent_a = torch.zeros(n * abi.FE_ENT_STATE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
             self.d_flags_a = torch.zeros(n, dtype=torch.int32, device=dev)
             self.d_flags = torch.zeros(n, dtype=torch.int32, device=dev)
@@ -444,6 +460,8 @@ class DeviceFleetLoop(_Audited):
         be = self.be
         be.fleet_select(self.d_start, self.d_rec, self.d_active, self.d_clock if self.d_audit is not None else None)
         if self.tethers:
+            if self.d_hold is not None:
+                self.d_hold.fill_(1)
             be.fleet_predict_ent(self.d_start, self.d_rec, self.d_ent_a, self.d_flags_a)
             if self.after_select is not None:
                 self.after_select(self)
@@ -497,6 +515,10 @@ class DeviceFleetLoop(_Audited):
         state = st["state"].reshape(self.S, self.N, 12); done = st["done"].reshape(self.S, self.N)
         summ = audit_mod.summarize(self.audit_records(), self.S) if self.d_audit is not None else None
         ever = be.fleet_ent_state(states=False)["ever"].reshape(self.S, self.N) if self.tethers else None
+        lists = held = None
+        if self.ent_cap is not None:
+            lists, held = be.fleet_ent_lists(self.ent_cap)
+            held = held.reshape(self.S, self.N)
         msum, goals_now = None, self.goals
         if self.missions is not None:
             from . import mission
@@ -510,6 +532,9 @@ class DeviceFleetLoop(_Audited):
                      qp_relaxed=int(c[6]), rejected_by_safety=int(c[3]), cap=int(c[5]), skipped=int(c[0]),
                      solves=int(c[1] + c[2] + c[3] + c[4] + c[5] + (0 if self.masked else c[0])), sim_time=float(t_now[s]), reached=int(done[s].sum()),
                      dist_to_goal_mean=float(np.hypot(*(state[s, :, :2] - goals_now[s, :, :2]).T).mean()))
+            if lists is not None:      # slot-rounds held at point A and the longest list now
+                d["held"] = int(held[s].sum()); d["max_list"] = int(lists.n_alpha.reshape(self.S, self.N)[s].max())
+                d["bend_full"] = int((lists.n_bend.reshape(self.S, self.N)[s] >= abi.NEP_MAX_BEND - 1).sum())      # (tethers at the bend-point limit)
             if ever is not None:      # agents whose tether was ever entangled / longer than the cable / dropped a move at a capacity
                 d["ever_entangled"] = int(c[7])
                 d["too_long"] = int(((ever[s] & abi.NEP_ENT_TRACK_TOO_LONG) != 0).sum())
@@ -538,9 +563,14 @@ class TetherLoop(_Audited):
     (nep_batch_set_active).  check=False flies the same rounds with the entangle check of
     the front end and of the safety pass off (plain nep_batch_frontend / nep_batch_safety_commit) and the tracking still on.
     audit=True adds the flight audit (nep_batch_audit) of the round's final records over the control ticks of the stretch the round
-    flies, inside the graph, after the copy into d_rec and before next_starts; report() then carries its summary."""
+    flies, inside the graph, after the copy into d_rec and before next_starts; report() then carries its summary.
+    ent_cap=K (or "auto": 2 (N + statics); ent_lists0: an abi.EntLists to start from) tracks the states in the list form of K entries
+    per slot (`lists`, nep_batch_track_ent_lists).  d_ent is then written at the start of every round: a slot's
+    list where it fits the fixed record, and a slot whose list holds more than 40 crossings is held for the round through the
+    handle's mask (`d_mask` = `active` and the fit; nep_batch_ent_lists_at_a), flying its record on.  report() adds held, max_list."""
 
-    def __init__(self, scenes, beam_width=16, n_intervals=1, ent_samples=3, check=True, device=None, graph=True, active=None, audit=False):
+    def __init__(self, scenes, beam_width=16, n_intervals=1, ent_samples=3, check=True, device=None, graph=True, active=None, audit=False,
+                 ent_cap=None, ent_lists0=None):
         import dataclasses
         import torch
         from neptune_amd import dist as ndist
@@ -567,6 +597,17 @@ class TetherLoop(_Audited):
         self.d_acc = torch.zeros(S * N, dtype=torch.int32, device=dev)
         self.d_ent = torch.zeros(S * N * abi.FE_ENT_STATE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         self.d_flags = torch.zeros(S * N, dtype=torch.int32, device=dev)
+        # ent_cap: the states tracked in the list form; d_ent is then each round's state at A where the list fits
+        # the fixed record, and a slot where it does not is held through the handle's mask (the caller's `active` and the fit)
+        self.ent_cap = None
+        if ent_cap is not None:
+            self.ent_cap = 2 * (N + len(scenes[0]["statics"])) if ent_cap == "auto" else int(ent_cap)
+            self.lists = be.new_ent_lists(self.ent_cap, ent_lists0)
+            self.d_active_in = active
+            self.d_mask = torch.ones((S, N), dtype=torch.int32, device=dev)
+            be.set_active(self.d_mask)
+            self.d_flags_a = torch.zeros(S * N, dtype=torch.int32, device=dev)
+            self.d_held = torch.zeros(S * N, dtype=torch.int32, device=dev)
         self.rounds = 0
         self.ever_flagged = np.zeros((S, N), dtype=np.int32)
         self._g = None
@@ -580,10 +621,16 @@ class TetherLoop(_Audited):
         be = self.be
         # the safety pass judges the new records with the tethers the others published (d_final inherits them: accepted agents
         # from the commit records, rejected and inactive ones from d_rec)
+        if self.ent_cap is not None:
+            be.ent_lists_at_a(self.lists, self.d_ent, self.d_mask, self.d_flags_a, self.d_active_in, self.d_held)
         plan_round(be, self.fe, self.d_rec, self.d_start, self.d_guess, self.d_res, self.d_final, self.d_acc, True,
                    self.d_case if self.check else None, self.d_ent, self.ent_samples)
-        be.track_ent(self.d_rec_prev, self.d_final, self.d_guess, self.d_ent, self.d_flags, n_intervals=self.n_intervals,
-                     ent_samples=self.ent_samples)
+        if self.ent_cap is not None:
+            be.track_ent_lists(self.d_rec_prev, self.d_final, self.d_guess, self.lists, self.d_flags, n_intervals=self.n_intervals,
+                               ent_samples=self.ent_samples)
+        else:
+            be.track_ent(self.d_rec_prev, self.d_final, self.d_guess, self.d_ent, self.d_flags, n_intervals=self.n_intervals,
+                         ent_samples=self.ent_samples)
         self.d_rec_prev.copy_(self.d_rec)
         self.d_rec.copy_(self.d_final)
         if self.d_audit is not None:
@@ -607,10 +654,13 @@ class TetherLoop(_Audited):
     def report(self):
         st = self.d_start.cpu().numpy().view(abi.FE_START_DTYPE).reshape(self.S, self.N)
         d = np.hypot(st["pos"][..., 0] - self.goals[..., 0], st["pos"][..., 1] - self.goals[..., 1])
-        nb = self.states()["n_bend"]
+        nb = self.states()["n_bend"] if self.ent_cap is None else self.lists.n_bend.cpu().numpy().reshape(self.S, self.N)
         rep = dict(rounds=self.rounds, arrived=[int(x) for x in (d < 2 * self.fe.goal_size).sum(axis=1)],
                    ever_entangled=[int(x) for x in self.ever_flagged.sum(axis=1)],
                    bend_hist=[int(x) for x in np.bincount(nb.reshape(-1), minlength=abi.NEP_MAX_BEND)[:abi.NEP_MAX_BEND]])
+        if self.ent_cap is not None:      # slot-rounds held at A and the longest list now, per scene
+            rep["held"] = [int(x) for x in self.d_held.cpu().numpy().reshape(self.S, self.N).sum(axis=1)]
+            rep["max_list"] = [int(x) for x in self.lists.n_alpha.cpu().numpy().reshape(self.S, self.N).max(axis=1)]
         if self.d_audit is not None:
             rep["audit"] = audit_mod.summarize(self.audit_records(), self.S)
         return rep

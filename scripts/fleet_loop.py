@@ -36,6 +36,8 @@ def main():
     ap.add_argument("--tethers", action="store_true", help="tethered agents: entangle states tracked per control tick, predicted at A, checked by the front end and the safety pass")
     ap.add_argument("--no-check", action="store_true", help="with --tethers: plain front end and safety pass, the tracking stays on")
     ap.add_argument("--no-proof", action="store_true", help="with --tethers: debug option fleet_ent_proof 0 (every other agent walked at every tick)")
+    ap.add_argument("--ent-cap", metavar="K", help="with --tethers: the tracked states in the list form of K entries per slot (DESIGN section 24) instead of the 40-entry record; 'auto' = 2 (agents + obstacles)")
+    ap.add_argument("--fe-big-records", type=int, default=0, metavar="R", help="with --tethers: records in the front end's pool of big entangle-state records (nep_batch_set_fe_ent_big_records; 0: the default, 4 per slot)")
     ap.add_argument("--missions", choices=("agent", "runs"), help="a campaign (DESIGN section 23): per-agent successive goals (NeptuneRos::autoCMD) or fleet-wide runs (benchmark_mtlp.py), drawn on the device inside the graph; the flight stops when every scene's campaign is over")
     ap.add_argument("--goals", type=int, default=2, metavar="G", help="with --missions: legs per agent / runs per scene")
     ap.add_argument("--host", action="store_true", help="also fly scene 0 with FleetLoop and with DeviceFleetLoop(S = 1): wall time per round of both")
@@ -43,12 +45,15 @@ def main():
     import numpy as np
     import torch
     from neptune_amd import audit, scene
+    from neptune_amd._lib import BackendError
     from neptune_amd.loop import DeviceFleetLoop, FleetLoop
     seeds = [a.seed0 + k for k in range(a.scenes)]
     scenes = scene.make_scenes(a.agents, a.obstacles, seeds, workers=min(len(seeds), len(os.sched_getaffinity(0)), 16))
     kw = dict(beam_width=a.beam, audit=a.audit, graph=not a.eager)
     if a.tethers:
         kw.update(tethers=True, check=not a.no_check)
+        if a.ent_cap:
+            kw.update(ent_cap="auto" if a.ent_cap == "auto" else int(a.ent_cap))
     if a.missions:
         from neptune_amd import mission
         kw.update(missions=mission.MissionSpec(a.missions, goals=a.goals, seed=a.seed0 + 1))
@@ -59,6 +64,8 @@ def main():
         lp = DeviceFleetLoop(scs, **kw)
         if a.tethers and a.no_proof:
             lp.be.debug_option("fleet_ent_proof", 0)
+        if a.tethers and a.fe_big_records:
+            lp.be.set_fe_ent_big_records(a.fe_big_records)
         lp.round(); lp.round()      # the eager round and the capture
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -69,7 +76,11 @@ def main():
                 break
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        rep = lp.report()
+        try:
+            rep = lp.report()
+        except BackendError as e:      # (a capacity other than the tracking's: said, not hidden — the read has cleared the sticky flags)
+            print("nep_batch_check after the flight:", e)
+            rep = lp.report()
         if a.tethers:
             w = lp.be.fleet_ent_state(states=False)["walked"]
             print("tether tracking: %d of %d (other agent, tick) pairs walked, the rest proven free of crossings"
@@ -83,6 +94,8 @@ def main():
     tot = {k: int(sum(r[k] for r in rep)) for k in ("replans", "accepted", "fe_no_solution", "qp_failed", "qp_relaxed", "rejected_by_safety", "cap", "skipped", "reached")}
     if a.tethers:
         tot.update({k: int(sum(r[k] for r in rep)) for k in ("ever_entangled", "too_long", "track_cap")})
+        if a.ent_cap:
+            tot.update(held=int(sum(r["held"] for r in rep)), max_list=int(max(r["max_list"] for r in rep)), bend_full=int(sum(r["bend_full"] for r in rep)))
     print("total over %d scenes x %d agents, %d rounds: %s" % (a.scenes, a.agents, n, json.dumps(tot)))
     if a.missions:
         ms = [r["mission"] for r in rep]

@@ -28,6 +28,7 @@ def main():
     ap.add_argument("--intervals", type=int, default=1, help="planning intervals flown per round")
     ap.add_argument("--crossing", action="store_true", help="scene.tether_crossing_scene: agents hover beyond each other's paths")
     ap.add_argument("--no-check", action="store_true", help="the front end and the safety pass without the entangle check")
+    ap.add_argument("--ent-cap", metavar="K", help="the tracked states in the list form of K entries per slot (DESIGN section 24); 'auto' = 2 (agents + obstacles)")
     ap.add_argument("--audit", action="store_true", help="flight audit of every round, inside the graph (reads each round's replan outcomes back)")
     a = ap.parse_args()
     import numpy as np
@@ -37,7 +38,8 @@ def main():
     seeds = [a.seed + k for k in range(a.scenes)]
     scenes = [scene.tether_crossing_scene(a.agents, a.obstacles, s) for s in seeds] if a.crossing else \
         scene.make_scenes(a.agents, a.obstacles, seeds, workers=min(len(seeds), len(os.sched_getaffinity(0))))
-    lp = TetherLoop(scenes, beam_width=a.beam, n_intervals=a.intervals, check=not a.no_check, audit=a.audit)
+    lp = TetherLoop(scenes, beam_width=a.beam, n_intervals=a.intervals, check=not a.no_check, audit=a.audit,
+                    ent_cap=None if not a.ent_cap else "auto" if a.ent_cap == "auto" else int(a.ent_cap))
     t_first = float(lp.d_start.cpu().numpy().view(abi.FE_START_DTYPE)["t_start"][0])
     outcomes = []                               # --audit: per round [S, N, 3] front-end status, QP status, accepted
     # The scenes' initial records are part of the input, and an agent whose first replans fail keeps flying them: the audit of the
