@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "nep_device.h"
+#include "qp_outputs.h"
 #include "audit_common.h"
 #include "mission_common.h"
 #include "../../include/neptune_plan.h"
@@ -530,6 +531,7 @@ struct Engine {
       last_path |= NEP_PATH_REDO_PASS;
       ProblemSet pr = ps;
       pr.line_far = nullptr; pr.line_skip = nullptr; pr.order = d_redo_list.p; pr.order_count = d_redo_count.p;      // (lists active slots only: no other slot ran)
+      pr.presolved = nullptr;      // (every listed replan is solved again, whatever the presolve kernel marked)
       pr.scratch_by_block = ps.scratch_chunks > 0 ? 1 : 0;
       launch_qp_reg(slots, sp, pr, d_tables.p, sc, lds_bytes, st);
     }
@@ -548,15 +550,7 @@ bool have_device() { int n = 0; return hipGetDeviceCount(&n) == hipSuccess && n 
 __global__ void sample_kernel(const nep_solution* __restrict__ sol, int K, const int* __restrict__ seg, const double* __restrict__ dt, int ns, double* __restrict__ out) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= ns) return;
-  const int i = seg[s]; const double d = dt[s];
-  double* st = out + (long)s * NEP_STATE_DOUBLES;
-  for (int ax = 0; ax < 3; ax++) {  // solver_gurobi_poly.cpp:921-929
-    const double* c = sol->coeff[ax][i];
-    st[ax] = ((c[0] * (d * d * d) + c[1] * (d * d)) + c[2] * d) + c[3];
-    st[3 + ax] = (c[0] * (3 * d * d) + c[1] * (2 * d)) + c[2];
-    st[6 + ax] = c[0] * (6 * d) + c[1] * 2;
-    st[9 + ax] = c[0] * 6;
-  }
+  sample_state(&sol->coeff[0][0][0], seg[s], dt[s], out + (long)s * NEP_STATE_DOUBLES);
 }
 
 // Test hook behind both debug line readers: the lines of one slot in row order — per segment the lines at the front of the

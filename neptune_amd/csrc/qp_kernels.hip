@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include "qp_common.h"
+#include "qp_outputs.h"
 
 namespace nep {
 
@@ -750,69 +751,38 @@ __global__ __launch_bounds__(BS, 2) void qp_kernel(SceneParams sp, ProblemSet ps
   if (status == NEP_FAILED) { if (tid < 96) sTheta[tid] = sCoef[tid]; }                    // :856-859
   else if (z_override) { if (tid < 32) sTheta[64 + tid] = sCoef[64 + tid]; }             // :879-880
   __syncthreads();
-  if (tid < 96) (&sol->coeff[0][0][0])[tid] = ((tid % 32) / 4 < Ko) ? sTheta[tid] : 0.0;
-  if (tid <= NEP_MAX_POL) sol->times[tid] = (tid <= Ko) ? g->t_start + tid * T : 0.0;      // :898 (times = i*T_span + t_start)
-  const int ns_all = sched.n[Ko];
-  const int ns = ns_all < sp.max_states ? ns_all : sp.max_states;
+  write_trajectory<BS>(sol, sTheta, Ko, &g->t_start, T, tid);
+  const int ns = sched_states(sp, sched, Ko);
   if (tid == 0) {
     sol->stats.status = status; sol->stats.iters = iters_total; sol->stats.iters_first = iters_first;
     // bucket entries of LPs without a separating line are (0,0,0) = null rows (constraint skipped)
-    int n_lp = 0, n_lpf = 0;
-    if (ps.lp_stats && !ps.lines_override) {
-      int v[2 * NEP_MAX_POL];
-#pragma unroll
-      for (int i = 0; i < 2 * NEP_MAX_POL; i++) v[i] = ps.lp_stats[(long)slot * NEP_MAX_POL * 2 + i];   // one round trip
-#pragma unroll
-      for (int i = 0; i < NEP_MAX_POL; i++) { n_lp += v[2 * i]; n_lpf += v[2 * i + 1]; }
-    }
+    int n_lp, n_lpf;
+    lp_totals(ps, slot, n_lp, n_lpf);
     sol->stats.n_lines = L_all - n_lpf; sol->stats.n_lp = n_lp; sol->stats.n_lp_failed = n_lpf;
     sol->stats.n_rows = K_ok ? 48 * K + 4 * ((culled && L_used < L_all) ? L_used : L_used - n_lpf) : 0; sol->stats.qc_active = has_qc ? 1 : 0;   // rows solved for (null rows of failed LPs excluded)
-    sol->stats.objective = objective; { const long long dt_ = (long long)wall_clock64() - t_wg0; const double us_ = (double)dt_ * sp.us_per_tick; sol->stats.solve_us = us_; if (ps.order_key) { const double k_ = us_ * 0.125; const int kn = k_ > 63.0 ? 63 : (int)k_, ko = ps.order_key[slot] - sp.qp_key_decay; ps.order_key[slot] = (sp.qp_key_decay > 0 && ko > kn) ? ko : kn; } }   // the per-replan device time, and the next launch's ordering key (8 us bins)
+    sol->stats.objective = objective;
+    write_solve_time(sp, ps, sol, slot, t_wg0);
     sol->K = Ko; sol->n_states = ns;
   }
-  if (ps.states) {  // generatePwpOut's samples (:911-934)
-    for (int s = tid; s < ns; s += BS) {
-      const int i = sched.seg[K * sp.max_states + s]; const double dt = sched.dt[K * sp.max_states + s];
-      double* st = ps.states + ((long)slot * sp.max_states + s) * NEP_STATE_DOUBLES;
-      for (int ax = 0; ax < 3; ax++) {
-        const double* c = sTheta + (ax * 8 + i) * 4;
-        st[ax] = ((c[0] * (dt * dt * dt) + c[1] * (dt * dt)) + c[2] * dt) + c[3];
-        st[3 + ax] = (c[0] * (3 * dt * dt) + c[1] * (2 * dt)) + c[2];
-        st[6 + ax] = c[0] * (6 * dt) + c[1] * 2;
-        st[9 + ax] = c[0] * 6;
-      }
-    }
-  }
+  write_states<BS>(sp, ps, sched, slot, sTheta, K, ns, tid);
 #ifdef NEP_PROFILE_PHASES
   if (prof) tph[11] = clock64() - tstart;   // [11]: workgroup lifetime up to here
 #ifndef NEP_QP_ITERDBG
   if (prof && tid == 0) { for (int k = 0; k < 12; k++) ps.dbg[(long)slot * 16 + k] = tph[k]; ps.dbg[(long)slot * 16 + 12] = iters_total; for (int k = 0; k < 3; k++) ps.dbg[(long)slot * 16 + 13 + k] = tset[k]; }
 #endif
 #endif
-  if (ps.commit) {  // the record the agent would publish (neptune_ros.cpp:434-480)
+  if (ps.commit) {
     nep_traj_rec* cr = ps.commit + slot;
     const int own = sp.first_local + (slot % sp.n_local);
+    // A failed replan publishes nothing: the agent keeps flying its committed trajectory (neptune_ros.cpp:651-663)
     if (status == NEP_FAILED) {
-      // A failed replan publishes nothing: the agent keeps flying its committed trajectory (neptune_ros.cpp:651-663).  With
-      // the previous records at hand (nep_batch_replan's d_committed) that record is carried over; otherwise d_commit[slot]
-      // is left as the caller passed it (the usual round loop hands the buffer that holds the previous round's records).
-      if (ps.prev_commit) {
+      if (ps.prev_commit) {      // (carry_commit's loop, inline: the call moves this kernel's spilled SGPRs to other lanes all through the iteration loops)
         const double* src = (const double*)(ps.prev_commit + (long)(slot / sp.n_local) * sp.num_agents + own);
         for (int e = tid; e < (int)(sizeof(nep_traj_rec) / sizeof(double)); e += BS) ((double*)cr)[e] = src[e];
       }
       return;
     }
-    if (tid == 0) {
-      cr->id = own + 1; cr->is_agent = 1; cr->n_bend = 1; cr->valid = 1;
-      for (int a = 0; a < 3; a++) { cr->bbox[a] = 2 * sp.drone_radius; cr->pos[a] = sTheta[(a * 8) * 4 + 3]; }
-      cr->bend[0][0] = ps.pb[2 * own]; cr->bend[0][1] = ps.pb[2 * own + 1];
-      cr->pwp.n_seg = K;
-    }
-    if (tid <= NEP_TRAJ_MAX_SEG) cr->pwp.times[tid] = (tid <= K) ? g->t_start + tid * T : 0.0;
-    for (int e = tid; e < 3 * NEP_TRAJ_MAX_SEG * 4; e += BS) {
-      const int ax = e / (NEP_TRAJ_MAX_SEG * 4), r = e % (NEP_TRAJ_MAX_SEG * 4), seg = r / 4, j = r % 4;
-      (&cr->pwp.coeff[0][0][0])[e] = (seg < K) ? sTheta[(ax * 8 + seg) * 4 + j] : 0.0;
-    }
+    write_commit<BS>(sp, ps, slot, sTheta, K, &g->t_start, T, tid);
   }
 }
 
@@ -914,7 +884,7 @@ void launch_active_list(int n_slots, const SceneParams& sp, const int* active, c
   if (n_slots > 0) hipLaunchKernelGGL(active_list_kernel, dim3(1), dim3(1024), 0, st, n_slots, sp, active, order_in, list, zero_these);
 }
 // The outputs of the inactive slots of a replan: d_solution says NEP_SKIPPED with nothing solved, d_commit carries the previous record
-// over by the rule of a failed replan (qp_kernel's tail).  One wave per slot; active slots return at once (their QP workgroups write).
+// over by the rule of a failed replan.  One wave per slot; active slots return at once (their QP workgroups write).
 __global__ __launch_bounds__(64) void skipped_replan_kernel(SceneParams sp, ProblemSet ps) {
   const int slot = blockIdx.x, tid = threadIdx.x;
   if (slot_active(sp, ps.active, slot)) return;
@@ -923,12 +893,7 @@ __global__ __launch_bounds__(64) void skipped_replan_kernel(SceneParams sp, Prob
   for (int e = tid; e < kWords; e += 64) ((int*)sol)[e] = 0;      // (stats, K = 0, n_states = 0; times and coefficients zero)
   __syncthreads();
   if (tid == 0) sol->stats.status = NEP_SKIPPED;
-  if (ps.commit && ps.prev_commit) {
-    const int own = sp.first_local + (slot % sp.n_local);
-    const double* src = (const double*)(ps.prev_commit + (long)(slot / sp.n_local) * sp.num_agents + own);
-    double* dst = (double*)(ps.commit + slot);
-    for (int e = tid; e < (int)(sizeof(nep_traj_rec) / sizeof(double)); e += 64) dst[e] = src[e];
-  }
+  if (ps.commit) carry_commit<64>(sp, ps, slot, tid);
 }
 void launch_skipped_replan(int n_slots, const SceneParams& sp, const ProblemSet& ps, hipStream_t st) {
   if (n_slots > 0 && ps.active) hipLaunchKernelGGL(skipped_replan_kernel, dim3(n_slots), dim3(64), 0, st, sp, ps);

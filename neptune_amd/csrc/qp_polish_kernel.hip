@@ -25,6 +25,7 @@
 #include <cstdlib>
 
 #include "nep_device.h"
+#include "qp_outputs.h"
 
 namespace nep {
 namespace {
@@ -278,7 +279,7 @@ __device__ bool polish_slot(const SceneParams& sp, const ProblemSet& ps, const Q
       na++;
     }
     if (!certified) continue;
-    // ---- the optimum: coefficients, objective, outputs — as the interior-point kernels write them ----
+    // ---- the optimum: coefficients, objective, outputs ----
     __syncthreads();
     for (int t = lane; t < 12 * K; t += NT) {      // theta = Th z + ThU init
       const int ax = t / (4 * K), r = t - ax * 4 * K;
@@ -344,27 +345,18 @@ __device__ bool polish_slot(const SceneParams& sp, const ProblemSet& ps, const Q
     const double dix = sCoef[3] - sFin[0], diy = sCoef[32 + 3] - sFin[1];
     if (sqrt(dix * dix + diy * diy) < 1.0) { if (lane < 32) sTheta[64 + lane] = sCoef[64 + lane]; }      // :879-880
     __syncthreads();
+    // The trajectory and, below, the record are stored by this kernel's own lines: through qp_outputs.h's write_trajectory or write_commit
+    // it takes 356 VGPRs (100 AGPRs) for 354 (98).  The bytes are write_trajectory's: sTheta is zero beyond K — "if ((t % 32) / 4 >= K)
+    // sTheta[t] = 0.0" after theta is formed, and the z rows copied just above come from sCoef, which the kernel's first load masks with
+    // "(lane % 32) / 4 < K".
     for (int t = lane; t < 96; t += NT) (&sol->coeff[0][0][0])[t] = sTheta[t];
     if (lane <= NEP_MAX_POL) sol->times[lane] = (lane <= K) ? g->t_start + lane * T : 0.0;
-    const int ns_all = sched.n[K];
-    const int ns = ns_all < sp.max_states ? ns_all : sp.max_states;
+    const int ns = sched_states(sp, sched, K);
     if (lane == 0) {
       sol->stats.status = mode; sol->stats.objective = obj; sol->K = K; sol->n_states = ns;
     }
-    if (ps.states) {
-      for (int s = lane; s < ns; s += NT) {      // generatePwpOut's samples (:911-934)
-        const int i = sched.seg[K * sp.max_states + s]; const double dt = sched.dt[K * sp.max_states + s];
-        double* st = ps.states + ((long)slot * sp.max_states + s) * NEP_STATE_DOUBLES;
-        for (int ax = 0; ax < 3; ax++) {
-          const double* c = sTheta + (ax * 8 + i) * 4;
-          st[ax] = ((c[0] * (dt * dt * dt) + c[1] * (dt * dt)) + c[2] * dt) + c[3];
-          st[3 + ax] = (c[0] * (3 * dt * dt) + c[1] * (2 * dt)) + c[2];
-          st[6 + ax] = c[0] * (6 * dt) + c[1] * 2;
-          st[9 + ax] = c[0] * 6;
-        }
-      }
-    }
-    if (ps.commit) {      // the record the agent publishes (neptune_ros.cpp:434-480), as the interior-point kernels write it
+    write_states<NT>(sp, ps, sched, slot, sTheta, K, ns, lane);
+    if (ps.commit) {      // the record the agent publishes (neptune_ros.cpp:434-480)
       nep_traj_rec* cr = ps.commit + slot;
       const int own = sp.first_local + (slot % sp.n_local);
       if (lane == 0) {

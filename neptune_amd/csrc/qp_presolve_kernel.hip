@@ -9,8 +9,8 @@
 // matrix-vector product and a pass over ~500 rows (profiles/r06_qp_phases_default.txt: line gather 26 %, start point 16 %, outputs
 // 18 % of the workgroups' lifetime, the iteration loop a third).  Here ONE WAVE per replan does exactly that and nothing else, eight
 // waves per SIMD deep (<= 64 registers, 6 KB of LDS): every replan of a launch is resident at once, the kernel lasts as long as one
-// wave's chain of global round trips.  A replan whose certificate holds is finished here — trajectory and statistics written as qp_reg_kernel writes
-// them — and marked in ps.presolved; the slot's workgroup of the interior-point launch that follows only samples the states and writes
+// wave's chain of global round trips.  A replan whose certificate holds is finished here — trajectory and statistics
+// written — and marked in ps.presolved; the slot's workgroup of the interior-point launch that follows only samples the states and writes
 // the commit record from the returned coefficients (pure stores, overlapped with the iterating replans' arithmetic) and returns, so that
 // launch's interior-point work is the replans that do iterate (one in eleven), all resident from the start.
 //
@@ -23,6 +23,7 @@
 
 #include "nep_device.h"
 #include "nep_tables.h"
+#include "qp_outputs.h"
 
 namespace nep {
 
@@ -161,16 +162,14 @@ __global__ __launch_bounds__(64, NEP_PRE_WAVES) void qp_presolve_kernel(ScenePar
   if (!(pre_wave_max(viol) <= 0.0)) return;             // some row is violated at z*: the interior point's job
   if (__ballot(bad) != 0ull) return;                    // moved too far to be sure: qp_reg_kernel solves it and checks every parked line
 
-  // ---- the certificate holds: this is the optimum.  Trajectory and statistics as qp_reg_kernel writes them. ----
+  // ---- the certificate holds: this is the optimum ----
   int n_lp = (lane & 1) == 0 ? lpv : 0, n_lpf = (lane & 1) == 1 ? lpv : 0;
 #pragma unroll
   for (int o_ = 8; o_ > 0; o_ >>= 1) { n_lp += __shfl_xor(n_lp, o_); n_lpf += __shfl_xor(n_lpf, o_); }      // (lanes 0..15 hold the values: the sums land in lane 0)
   if (z_override) { if (lane < 32) sTheta[64 + lane] = sCoef[64 + lane]; }      // :879-880
   __syncthreads();
-  for (int t = lane; t < 96; t += 64) (&sol->coeff[0][0][0])[t] = ((t % 32) / 4 < K) ? sTheta[t] : 0.0;
-  if (lane <= NEP_MAX_POL) sol->times[lane] = (lane <= K) ? g->t_start + lane * T : 0.0;
-  const int ns_all = sched.n[K];
-  const int ns = ns_all < sp.max_states ? ns_all : sp.max_states;
+  write_trajectory<64>(sol, sTheta, K, &g->t_start, T, lane);
+  const int ns = sched_states(sp, sched, K);
   if (lane == 0) {
     double o = 0;      // the cost at z*: v' ObjQ v per axis (the first problem's cost, :322-383)
     for (int ax = 0; ax < 3; ax++) for (int a = 0; a < 4; a++) { double r_ = 0; for (int b = 0; b < 4; b++) r_ += tb->ObjQ[a][b] * vv[ax][b]; o += vv[ax][a] * r_; }

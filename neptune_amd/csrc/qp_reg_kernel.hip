@@ -31,6 +31,7 @@
 #include <hip/hip_runtime.h>
 
 #include "qp_common.h"
+#include "qp_outputs.h"
 
 static_assert(nep::kCorrFromIt == nep::kCorrFromItDefault && nep::kCorrMaxCount == nep::kCorrMaxCountDefault, "the give-up rule's constants are stated twice");
 
@@ -99,7 +100,7 @@ __global__ __launch_bounds__(BS, NEP_QP_REG_WGS) void qp_reg_kernel(SceneParams 
   const int slot = ps.order ? ps.order[blockIdx.x] : (int)blockIdx.x;   // (launch order: see order_kernel)
   if (CULL && ps.presolved && ps.presolved[slot] != 0) {
     // qp_presolve_kernel certified and returned this replan's trajectory (round 6): what is left are the stores that depend on nothing
-    // but the coefficients — generatePwpOut's samples (:911-934) and the record the agent publishes (neptune_ros.cpp:434-480) — written
+    // but the coefficients — generatePwpOut's samples and the record the agent publishes — written
     // here, beside the iterating replans' workgroups, and not by the wave that made the certificate
     if (gridDim.x == 1 && tid == 0 && ps.polish_list) { ps.polish_count[0] = 0; ps.polish_count[3] = 0; }      // (a one-workgroup launch is its own, empty, polish list)
     const nep_solution* __restrict__ so = ps.solution + slot;
@@ -107,37 +108,8 @@ __global__ __launch_bounds__(BS, NEP_QP_REG_WGS) void qp_reg_kernel(SceneParams 
     double* sTh = smem;                                       // [3][8][4]
     if (tid < 96) sTh[tid] = (&so->coeff[0][0][0])[tid];
     __syncthreads();
-    if (ps.states) {
-      const int ns_all = sched.n[Kp];
-      const int ns = ns_all < sp.max_states ? ns_all : sp.max_states;
-      for (int s = tid; s < ns; s += BS) {
-        const int i = sched.seg[Kp * sp.max_states + s]; const double dt = sched.dt[Kp * sp.max_states + s];
-        double* st = ps.states + ((long)slot * sp.max_states + s) * NEP_STATE_DOUBLES;
-        for (int ax = 0; ax < 3; ax++) {
-          const double* c = sTh + (ax * 8 + i) * 4;
-          st[ax] = ((c[0] * (dt * dt * dt) + c[1] * (dt * dt)) + c[2] * dt) + c[3];
-          st[3 + ax] = (c[0] * (3 * dt * dt) + c[1] * (2 * dt)) + c[2];
-          st[6 + ax] = c[0] * (6 * dt) + c[1] * 2;
-          st[9 + ax] = c[0] * 6;
-        }
-      }
-    }
-    if (ps.commit) {
-      nep_traj_rec* cr = ps.commit + slot;
-      const int own = sp.first_local + (slot % sp.n_local);
-      const double t_start = ps.guess[slot].t_start, Tp = sp.T_span;
-      if (tid == 0) {
-        cr->id = own + 1; cr->is_agent = 1; cr->n_bend = 1; cr->valid = 1;
-        for (int a = 0; a < 3; a++) { cr->bbox[a] = 2 * sp.drone_radius; cr->pos[a] = sTh[(a * 8) * 4 + 3]; }
-        cr->bend[0][0] = ps.pb[2 * own]; cr->bend[0][1] = ps.pb[2 * own + 1];
-        cr->pwp.n_seg = Kp;
-      }
-      if (tid <= NEP_TRAJ_MAX_SEG) cr->pwp.times[tid] = (tid <= Kp) ? t_start + tid * Tp : 0.0;
-      for (int e = tid; e < 3 * NEP_TRAJ_MAX_SEG * 4; e += BS) {
-        const int ax = e / (NEP_TRAJ_MAX_SEG * 4), r = e % (NEP_TRAJ_MAX_SEG * 4), seg = r / 4, j = r % 4;
-        (&cr->pwp.coeff[0][0][0])[e] = (seg < Kp) ? sTh[(ax * 8 + seg) * 4 + j] : 0.0;
-      }
-    }
+    if (ps.states) write_states<BS>(sp, ps, sched, slot, sTh, Kp, sched_states(sp, sched, Kp), tid);
+    if (ps.commit) { const double t_start = ps.guess[slot].t_start; write_commit<BS>(sp, ps, slot, sTh, Kp, &t_start, sp.T_span, tid); }      // (loaded by every thread ahead of the stores: behind write_commit's guard the load would wait for them)
     return;
   }
   const long long t_wg0 = (long long)wall_clock64();          // this workgroup's lifetime goes to stats.solve_us (wall-clock ticks: sp.us_per_tick)
@@ -1090,27 +1062,20 @@ __global__ __launch_bounds__(BS, NEP_QP_REG_WGS) void qp_reg_kernel(SceneParams 
   }
   __syncthreads();
   const int Ko = K_ok ? K : 0;
-  // ---- outputs (as qp_kernel) ---------------------------------------------------------------------
+  // ---- outputs -----------------------------------------------------------------------------------
   if (status == NEP_FAILED) { if (tid < 96) sTheta[tid] = sCoef[tid]; }                    // :856-859
   else if (z_override) { if (tid < 32) sTheta[64 + tid] = sCoef[64 + tid]; }             // :879-880
   __syncthreads();
-  if (tid < 96) (&sol->coeff[0][0][0])[tid] = ((tid % 32) / 4 < Ko) ? sTheta[tid] : 0.0;
-  if (tid <= NEP_MAX_POL) sol->times[tid] = (tid <= Ko) ? g->t_start + tid * T : 0.0;
-  const int ns_all = sched.n[Ko];
-  const int ns = ns_all < sp.max_states ? ns_all : sp.max_states;
+  write_trajectory<BS>(sol, sTheta, Ko, &g->t_start, T, tid);
+  const int ns = sched_states(sp, sched, Ko);
   if (tid == 0) {
     sol->stats.status = status; sol->stats.iters = sI[31]; sol->stats.iters_first = sI[32];
-    int n_lp = 0, n_lpf = 0;
-    if (ps.lp_stats && !ps.lines_override) {
-      int v[2 * NEP_MAX_POL];
-#pragma unroll
-      for (int i = 0; i < 2 * NEP_MAX_POL; i++) v[i] = ps.lp_stats[(long)slot * NEP_MAX_POL * 2 + i];
-#pragma unroll
-      for (int i = 0; i < NEP_MAX_POL; i++) { n_lp += v[2 * i]; n_lpf += v[2 * i + 1]; }
-    }
+    int n_lp, n_lpf;
+    lp_totals(ps, slot, n_lp, n_lpf);
     sol->stats.n_lines = L_all - n_lpf; sol->stats.n_lp = n_lp; sol->stats.n_lp_failed = n_lpf;
     sol->stats.n_rows = K_ok ? 48 * K + 4 * ((CULL && L_used < L_all) ? L_used : L_used - n_lpf) : 0; sol->stats.qc_active = has_qc ? 1 : 0;
-    sol->stats.objective = sc[sObjOut]; { const long long dt_ = (long long)wall_clock64() - t_wg0; const double us_ = (double)dt_ * sp.us_per_tick; sol->stats.solve_us = us_; if (ps.order_key) { const double k_ = us_ * 0.125; const int kn = k_ > 63.0 ? 63 : (int)k_, ko = ps.order_key[slot] - sp.qp_key_decay; ps.order_key[slot] = (sp.qp_key_decay > 0 && ko > kn) ? ko : kn; } }   // the per-replan device time, and the next launch's ordering key (8 us bins)
+    sol->stats.objective = sc[sObjOut];
+    write_solve_time(sp, ps, sol, slot, t_wg0);
     sol->K = Ko; sol->n_states = ns;
     if (ps.polish_list) {
       const bool listed = sI[29] != 0 && !(CULL && sI[26] != 0);      // (a replan sent to the redo pass is listed there, if at all)
@@ -1119,19 +1084,7 @@ __global__ __launch_bounds__(BS, NEP_QP_REG_WGS) void qp_reg_kernel(SceneParams 
       else if (listed) { ps.polish_flag[slot] = sI[29]; ps.polish_list[atomicAdd(ps.polish_count, 1)] = slot; }
     }
   }
-  if (ps.states) {  // generatePwpOut's samples (:911-934)
-    for (int s = tid; s < ns; s += BS) {
-      const int i = sched.seg[K * sp.max_states + s]; const double dt = sched.dt[K * sp.max_states + s];
-      double* st = ps.states + ((long)slot * sp.max_states + s) * NEP_STATE_DOUBLES;
-      for (int ax = 0; ax < 3; ax++) {
-        const double* c = sTheta + (ax * 8 + i) * 4;
-        st[ax] = ((c[0] * (dt * dt * dt) + c[1] * (dt * dt)) + c[2] * dt) + c[3];
-        st[3 + ax] = (c[0] * (3 * dt * dt) + c[1] * (2 * dt)) + c[2];
-        st[6 + ax] = c[0] * (6 * dt) + c[1] * 2;
-        st[9 + ax] = c[0] * 6;
-      }
-    }
-  }
+  write_states<BS>(sp, ps, sched, slot, sTheta, K, ns, tid);
 #ifdef NEP_PROFILE_PHASES
   if (prof && tid == 0) {   // [0..9] loop phases, [10] workgroup lifetime, [12] iterations, [13] line gather, [14] mode staging, [15] start point
     for (int k = 0; k < 16; k++) ps.dbg[(long)slot * 16 + k] = sProf[k];
@@ -1139,27 +1092,18 @@ __global__ __launch_bounds__(BS, NEP_QP_REG_WGS) void qp_reg_kernel(SceneParams 
     ps.dbg[(long)slot * 16 + 11] = (tstart_wall << 20) | ((long long)wall_clock64() - tstart_wall);   // start (100 MHz ticks) << 20 | duration
   }
 #endif
-  if (ps.commit) {  // the record the agent would publish (neptune_ros.cpp:434-480); a failed replan publishes nothing (see qp_kernel)
+  if (ps.commit) {
     nep_traj_rec* cr = ps.commit + slot;
     const int own = sp.first_local + (slot % sp.n_local);
+    // A failed replan publishes nothing: the agent keeps flying its committed trajectory (neptune_ros.cpp:651-663)
     if (status == NEP_FAILED || (CULL && __builtin_amdgcn_readfirstlane(sI[26]) != 0)) {
-      if (ps.prev_commit) {
+      if (ps.prev_commit) {      // (carry_commit's loop, inline, with cr and own computed above the branch: the call, or moving those two lines in here, costs qp_reg_kernel<false> 64 B more scratch per lane)
         const double* src = (const double*)(ps.prev_commit + (long)(slot / sp.n_local) * sp.num_agents + own);
         for (int e = tid; e < (int)(sizeof(nep_traj_rec) / sizeof(double)); e += BS) ((double*)cr)[e] = src[e];
       }
       return;
     }
-    if (tid == 0) {
-      cr->id = own + 1; cr->is_agent = 1; cr->n_bend = 1; cr->valid = 1;
-      for (int a = 0; a < 3; a++) { cr->bbox[a] = 2 * sp.drone_radius; cr->pos[a] = sTheta[(a * 8) * 4 + 3]; }
-      cr->bend[0][0] = ps.pb[2 * own]; cr->bend[0][1] = ps.pb[2 * own + 1];
-      cr->pwp.n_seg = K;
-    }
-    if (tid <= NEP_TRAJ_MAX_SEG) cr->pwp.times[tid] = (tid <= K) ? g->t_start + tid * T : 0.0;
-    for (int e = tid; e < 3 * NEP_TRAJ_MAX_SEG * 4; e += BS) {
-      const int ax = e / (NEP_TRAJ_MAX_SEG * 4), r = e % (NEP_TRAJ_MAX_SEG * 4), seg = r / 4, j = r % 4;
-      (&cr->pwp.coeff[0][0][0])[e] = (seg < K) ? sTheta[(ax * 8 + seg) * 4 + j] : 0.0;
-    }
+    write_commit<BS>(sp, ps, slot, sTheta, K, &g->t_start, T, tid);
   }
 }
 

@@ -44,6 +44,46 @@ def solver_lines_match(s, r, ordered=False):
     assert got == want
 
 
+def check_slot_outputs(oracle, p, own, guess, sol, states, com, prev=None):
+    """What a replan leaves behind for ONE slot — the sampled states and the published record — against the slot's own nep_solution,
+    which is taken as the truth for the trajectory.  own: the agent's global index; guess: the nep_guess the slot was given; sol, states
+    [max_states][12], com: the slot's entries of solutions(), states(), commits(); prev: the record of (scene, own) handed to the replan
+    as d_committed, or None when none was.  A slot that solved publishes its trajectory; a failed or skipped one keeps the previous
+    record, byte for byte (without previous records its commit slot is left as passed: nothing to check here)."""
+    status, K = int(sol["stats"]["status"]), int(sol["K"])
+    if status == abi.NEP_SKIPPED:                          # nothing solved: the solution is zero apart from the status
+        z = sol.copy(); z["stats"]["status"] = 0
+        assert not np.frombuffer(z.tobytes(), dtype=np.uint8).any(), own
+    else:
+        co = np.array(sol["coeff"])[:, :K, :]
+        assert not np.array(sol["coeff"])[:, K:, :].any() and not np.array(sol["times"])[K + 1:].any(), own
+        t0 = float(guess["t_start"])
+        if K > 0:
+            np.testing.assert_allclose(np.array(sol["times"])[:K + 1], t0 + np.arange(K + 1) * p.T_span, atol=1e-12)
+            ref = oracle.sample(co, p.T_span, p.dc, cap=4096)      # the whole schedule of K
+            n = min(len(ref), p.max_states)
+        else:
+            ref, n = np.zeros((0, abi.NEP_STATE_DOUBLES)), 0
+        assert int(sol["n_states"]) == n, (own, int(sol["n_states"]), len(ref), p.max_states)
+        np.testing.assert_allclose(states[:n], ref[:n], rtol=0, atol=1e-12)
+    if status in (abi.NEP_FAILED, abi.NEP_SKIPPED):
+        if prev is not None:
+            assert com.tobytes() == prev.tobytes(), (own, status)
+        return
+    assert int(com["id"]) == own + 1 and int(com["is_agent"]) == 1 and int(com["n_bend"]) == 1 and int(com["valid"]) == 1, own
+    np.testing.assert_array_equal(com["bbox"], np.full(3, 2 * p.drone_radius))
+    np.testing.assert_array_equal(com["pos"], co[:, 0, 3])
+    np.testing.assert_array_equal(com["bend"][0], np.asarray(p.pb)[own])
+    assert int(com["pwp"]["n_seg"]) == K
+    rt = np.array(com["pwp"]["times"])
+    np.testing.assert_array_equal(rt[:K + 1], np.array(sol["times"])[:K + 1])      # (= t_start + i T: the solution's, checked above)
+    assert not rt[K + 1:].any()
+    rc = np.array(com["pwp"]["coeff"])
+    assert rc.shape == (3, abi.NEP_TRAJ_MAX_SEG, 4)
+    assert rc[:, :K, :].tobytes() == co.tobytes()                                   # bit-equal to the solution's
+    assert not rc[:, K:, :].any()
+
+
 def _check_scene(be, oracle, sc, n_scenes=1, first_local=0, n_local=None, hull_kernel=0, replans=1, info=None):
     """Every replan of a scene against the oracle, on BOTH solve paths of the handle: `full` = every separating-line row through the
     interior point (nep_batch_set_line_cull(0): lines bit-exact in the reference's call order, LP / row counts), and the handle's
@@ -102,13 +142,7 @@ def _check_scene(be, oracle, sc, n_scenes=1, first_local=0, n_local=None, hull_k
             assert err <= COEF_TOL, (mode, aid, err)
             if r["status"] != 2:
                 assert abs(float(st["objective"]) - r["objective"]) <= COST_RTOL * (1 + abs(r["objective"])), (mode, aid)
-            ref = oracle.sample(co, p.T_span, p.dc, cap=p.max_states)
-            assert int(sol[a]["n_states"]) == len(ref)
-            np.testing.assert_allclose(states[a, :len(ref)], ref, rtol=0, atol=1e-12)
-            t0 = float(sc["guesses"][aid - 1]["t_start"])
-            np.testing.assert_allclose(np.array(sol[a]["times"])[:K + 1], t0 + np.arange(K + 1) * p.T_span, atol=1e-12)
-            assert int(com[a]["id"]) == aid and int(com[a]["pwp"]["n_seg"]) == K
-            np.testing.assert_array_equal(np.array(com[a]["pwp"]["coeff"])[:, :K, :], co)
+            check_slot_outputs(oracle, p, aid - 1, sc["guesses"][aid - 1], sol[a], states[a], com[a], prev=sc["committed"][aid - 1])
         if info is not None:
             info.setdefault("worst", {})[mode] = worst_mode
             info.setdefault("path", {})[mode] = bb.debug_launch_path()
