@@ -117,7 +117,12 @@ typedef struct nep_stats {
   int32_t qc_active;              /* terminal ball constraint present (solver_gurobi_poly.cpp:699) */
   double objective;               /* objective_value (solver_gurobi_poly.cpp:882)               */
   double solve_us;                /* batched handle: device time of the replan's QP workgroup; per-agent handle: wall time of
-                                     optimize() as the caller's clock sees it (neptune.cpp:1504,1528), microseconds */
+                                     optimize() as the caller's clock sees it (neptune.cpp:1504,1528), microseconds.  A replan
+                                     finished by the zero-iteration certificate (iters == 0 under the presolve): the time of
+                                     the wave that certified it — the whole of qp_presolve_kernel's wave, or, when the
+                                     certificate runs in the separator's wave (NEP_PATH_FUSED_PRESOLVE), only that wave's
+                                     closing after its last LP: the start point and the per-line tests are spread through
+                                     the separator's work and are not counted */
 } nep_stats;
 
 /* ------------------------------------------------------------------------------------------ */

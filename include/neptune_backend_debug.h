@@ -81,7 +81,11 @@ int nep_batch_debug_launch_order(nep_batch_t* h, int32_t* order, int32_t cap, in
  *                  these two DO change which hard replans are given up on; they exist for that trade's A/B only
  *   "qp_profile"   1: collect the phase counters (PROFILE builds)
  *   "presolve_kernel"  1 (default): the presolve's zero-iteration certificate runs as a kernel of its own before the interior point
- *                  (qp_presolve_kernel.hip, one wave per replan) | 0: only inside qp_reg_kernel<true>, as in rounds 3-5
+ *                  (qp_presolve_kernel.hip, one wave per replan) or in the separator's wave | 0: only inside qp_reg_kernel<true>, as in
+ *                  rounds 3-5 (turns "presolve_fused" off as well)
+ *   "presolve_fused"   1 (default): when one wave of the packed separator holds every segment of a slot (launches of some 4 096 slots
+ *                  and more; nep_batch_replan, no active set) that wave runs the certificate itself and qp_presolve_kernel is not
+ *                  launched | 0: always the kernel of its own.  Same bytes either way (tests/test_gpu_presolve_fused.py)
  * Process-wide (launcher choices, results do not depend on them): "fe_three" (keep the three-workgroup front-end instantiation),
  * "fe_xcd" (0: no XCD placement of the searches), "polish_grid" (workgroups of the polish pass, default 256).
  * Unknown names are refused (NEP_E_ARG).                                                                                      */
@@ -100,7 +104,9 @@ int nep_batch_debug_conflicts(nep_batch_t* h, int32_t scene, uint8_t* conflict_o
 int nep_batch_debug_conflicts_prev(nep_batch_t* h, int32_t scene, uint8_t* conflict_out);
 
 /* Average device time (ms) of the dominant kernel over the launches since the last call,
- * measured with HIP events on the launch stream; *n_launch = launches averaged.               */
+ * measured with HIP events on the launch stream; *n_launch = launches averaged.  The presolve's zero-iteration certificate counts
+ * towards the `qp` interval when it runs as qp_presolve_kernel and towards `separator` when it runs in the separator's wave
+ * (NEP_PATH_FUSED_PRESOLVE).                                                                  */
 int nep_batch_kernel_time(nep_batch_t* h, int32_t which, double* avg_ms, int32_t* n_launch);
 int nep_batch_enable_timing(nep_batch_t* h, int32_t on);
 int nep_batch_reset_timing(nep_batch_t* h);
@@ -110,19 +116,23 @@ int nep_batch_reset_timing(nep_batch_t* h);
  * tests prove with them that they ran the path they are about.  nep_batch_debug_boxes: scene `scene`'s block of the obstacle boxes the
  * separator's LP skipping and the front end read, [num_agents + n_static][num_pol][4] doubles (x0, x1, y0, y1; an empty polygon's box is
  * (+inf, -inf, +inf, -inf)) into out (cap doubles), after a device synchronize.  nep_batch_debug_order_keys: the QP launch order's keys
- * [slots] as the last replan left them (the order of the next one sorts the slots by key & 63, largest first).                        */
+ * [slots] as the last replan left them (the order of the next one sorts the slots by key & 63, largest first).
+ * nep_batch_debug_presolved: the zero-iteration certificate's marks [slots] of the last replan with NEP_PATH_PRESOLVE_KERNEL set
+ * (1: the certificate finished the slot, 0: the interior point decided; slots outside an active set keep an older mark).          */
 enum {
   NEP_PATH_BOX_KERNEL = 1,        /* fe_box_kernel made every obstacle's box                                                        */
   NEP_PATH_HULLS_GROUPED = 2,     /* the eight-hulls-per-wave hull kernel ran                                                       */
   NEP_PATH_FUSED_BOXES = 4,       /* ... and made the hulls' boxes and zeroed the redo counters (no fe_box_kernel)                    */
   NEP_PATH_FUSED_ORDER = 8,       /* ... and, in its block 0, the QP launch order, zeroing the polish counters (no order_kernel)      */
   NEP_PATH_ORDERED_QP = 16,       /* the QP workgroups were launched longest-expected-first                                         */
-  NEP_PATH_PRESOLVE_KERNEL = 32,  /* qp_presolve_kernel ran                                                                          */
-  NEP_PATH_REDO_PASS = 64         /* the presolve's redo pass ran                                                                    */
+  NEP_PATH_PRESOLVE_KERNEL = 32,  /* the zero-iteration certificate ran ahead of the interior-point launch (either form)             */
+  NEP_PATH_REDO_PASS = 64,        /* the presolve's redo pass ran                                                                    */
+  NEP_PATH_FUSED_PRESOLVE = 128   /* ... in the separator's wave: qp_presolve_kernel was not launched                                */
 };
 int nep_batch_debug_launch_path(nep_batch_t* h, int32_t* bits);
 int nep_batch_debug_boxes(nep_batch_t* h, int32_t scene, double* out, int32_t cap);
 int nep_batch_debug_order_keys(nep_batch_t* h, int32_t* keys, int32_t cap);
+int nep_batch_debug_presolved(nep_batch_t* h, int32_t* marks, int32_t cap);
 
 /* Test hooks: fetch intermediates of the last replan to host.                                 */
 int nep_batch_debug_hulls(nep_batch_t* h, int32_t scene, double* hull_xy, int32_t* hull_nv);

@@ -37,7 +37,7 @@ DEBUG_EXPORTS = [
     "nep_batch_kernel_time", "nep_batch_enable_timing", "nep_batch_reset_timing", "nep_batch_debug_hulls",
     "nep_batch_debug_lines", "nep_batch_debug_phase_cycles", "nep_batch_fe_search_us",
     "nep_batch_set_fe_ent_fast_caps", "nep_batch_debug_set_option", "nep_backend_debug_set_option", "nep_debug_set_global_option",
-    "nep_batch_debug_launch_path", "nep_batch_debug_boxes", "nep_batch_debug_order_keys", "nep_debug_live_bytes",
+    "nep_batch_debug_launch_path", "nep_batch_debug_boxes", "nep_batch_debug_order_keys", "nep_batch_debug_presolved", "nep_debug_live_bytes",
 ]
 # every symbol include/neptune_plan.h declares (host-only: no HIP call behind them)
 PLAN_EXPORTS = [
@@ -146,6 +146,7 @@ def lib():
     L.nep_batch_debug_launch_path.argtypes = [vp, pi]
     L.nep_batch_debug_boxes.argtypes = [vp, i, pd, i]
     L.nep_batch_debug_order_keys.argtypes = [vp, pi, i]
+    L.nep_batch_debug_presolved.argtypes = [vp, pi, i]
     L.nep_debug_live_bytes.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.nep_batch_set_scene_statics.argtypes = [vp, i, i, pi, pd]
     L.nep_batch_check.argtypes = [vp, vp]

@@ -593,11 +593,12 @@ class BatchBackend:
 
     # NEP_PATH_* bits of include/neptune_backend_debug.h
     LAUNCH_PATH = (("box_kernel", 1), ("grouped_hulls", 2), ("fused_boxes", 4), ("fused_order", 8), ("ordered_qp", 16),
-                   ("presolve_kernel", 32), ("redo_pass", 64))
+                   ("presolve_kernel", 32), ("redo_pass", 64), ("fused_presolve", 128))
 
     def debug_launch_path(self):
         """what the last replan launched (nep_batch_debug_launch_path) -> {name: bool}: fe_box_kernel, the eight-hulls-per-wave hull
-        kernel, the boxes / the launch order made by that kernel, the QP workgroups in launch order, the presolve kernel, the redo pass"""
+        kernel, the boxes / the launch order made by that kernel, the QP workgroups in launch order, the presolve's certificate ahead of the interior point (as a kernel or in the separator's
+        wave), the redo pass, the certificate in the separator's wave"""
         b = C.c_int32(0)
         check(lib().nep_batch_debug_launch_path(self._h, C.byref(b)))
         return {name: bool(b.value & bit) for name, bit in self.LAUNCH_PATH}
@@ -612,6 +613,13 @@ class BatchBackend:
         """the QP launch order's keys [slots] as the last replan left them (nep_batch_debug_order_keys)"""
         out = np.zeros(self.slots, dtype=np.int32)
         check(lib().nep_batch_debug_order_keys(self._h, abi.iptr(out), len(out)))
+        return out
+
+    def debug_presolved(self):
+        """the zero-iteration certificate's marks [slots] of the last replan that ran it ahead of the interior point
+        (nep_batch_debug_presolved): 1 = finished by the certificate"""
+        out = np.zeros(self.slots, dtype=np.int32)
+        check(lib().nep_batch_debug_presolved(self._h, abi.iptr(out), len(out)))
         return out
 
     def set_max_runtime(self, seconds):

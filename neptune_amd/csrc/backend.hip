@@ -139,7 +139,7 @@ struct Engine {
   DevBuf<double> d_pb, d_static_xy, d_static_el; DevBuf<int> d_static_nv;
   DevBuf<double> d_hull_xy, d_hull0_xy, d_bend_xy, d_line_nd, d_row_scratch;
   DevBuf<int> d_hull_nv, d_hull0_nv, d_bend_n, d_line_cnt, d_line_far, d_lp_stats;
-  DevBuf<int> d_presolved; bool presolve_kernel = true;      // qp_presolve_kernel's marks (one per slot); debug option "presolve_kernel" = 0: the test runs inside qp_reg_kernel<true> as in rounds 3-5
+  DevBuf<int> d_presolved; bool presolve_kernel = true, presolve_fused = true;      // the zero-iteration certificate's marks (one per slot); debug option "presolve_kernel" = 0: the test runs inside qp_reg_kernel<true> as in rounds 3-5; "presolve_fused" = 0: always as qp_presolve_kernel, never in the separator's wave
   DevBuf<int> d_line_skip, d_redo_list, d_redo_count;   // spatial presolve: skipped LPs per segment, replans listed for the redo pass
   DevBuf<double> d_polish_z; DevBuf<int> d_polish_flag, d_polish_list, d_polish_count; bool polish = true, polish_presolve = true, last_polish_armed = false;      // the active-set polish of solves that end without the strict tests (qp_polish_kernel.hip; nep_*_set_polish)
   DevBuf<long long> d_dbg; bool profile_phases = false;
@@ -352,7 +352,7 @@ struct Engine {
     ps.sep_pack = sep_pack;
     ps.row_scratch = d_row_scratch.p; ps.rows_cap = rows_cap; ps.lds_rows = lds_rows; ps.lds_lines = lds_lines;
     ps.dbg = profile_phases ? d_dbg.p : nullptr;
-    ps.presolved = nullptr;      // (set by run() for a launch sequence in which qp_presolve_kernel goes first)
+    ps.presolved = nullptr; ps.pre_tables = nullptr; ps.pre_sched_n = nullptr;      // (set by run() for a launch sequence in which the zero-iteration certificate goes first)
     ps.flags = d_flags.p;
     ps.fe_box = d_fe_box.p;
     ps.active = active; ps.fe_count = nullptr;
@@ -497,9 +497,25 @@ struct Engine {
       ps.row_scratch = d_row_scratch.p;
     }
     const bool skip = ps.skip_box != nullptr;
+    // the presolve's zero-iteration certificate ahead of the interior-point launch: the replans it finishes (nine in ten of the bench's
+    // scenes) cost that launch an immediate return.  In the separator's own wave when that wave holds every segment of its slot (the
+    // packed kernel at eight segments a wave: launches of some 4 096 slots and more) — everything the certificate reads is in that
+    // wave's hands (qp_presolve.h) —, as a kernel of its own otherwise (qp_presolve_kernel.hip).  The fused form keeps to the cases it
+    // is tested in: one call for both halves, no active set, and the launch order either made by the hull launch or not made at all
+    // (a certified slot's key decays when it is certified: an order kernel between the separator and the QP launch would read the
+    // decayed keys, where it reads the previous round's with the kernel of its own).
+    const bool pre = qp && use_reg && presolve_kernel && ps.line_far != nullptr && !ps.lines_override && d_presolved.n >= (size_t)slots;
+    const bool fused_pre = pre && presolve_fused && phases == 3 && !ps.active && skip && sp.cull_radius > 0.0 && (!want_order || fused_order)
+                           && separator_pack(slots, sp, ps) == NEP_MAX_POL;
     if (!ps.lines_override && geo) {
       if (skip && !fused_boxes) { launch_boxes(n_scenes, sp, ps, st); last_path |= NEP_PATH_BOX_KERNEL; }      // (zeroes the redo counters as well)
+      if (fused_pre) {
+        ps.presolved = d_presolved.p; ps.pre_tables = d_tables.p; ps.pre_sched_n = d_sched_n.p;
+        ps.order_key = (lpt && d_order_key.n >= (size_t)slots) ? d_order_key.p : nullptr;      // (as below: the certified slots' keys decay)
+        last_path |= NEP_PATH_PRESOLVE_KERNEL | NEP_PATH_FUSED_PRESOLVE;
+      }
       launch_separator(slots, sp, ps, st);
+      ps.pre_tables = nullptr; ps.pre_sched_n = nullptr;
     }
     if (timing) hipEventRecord(next_event(), st);
     if (!qp) { if (timing) hipEventRecord(next_event(), st); HIPCHK(hipGetLastError()); return 0; }
@@ -515,9 +531,7 @@ struct Engine {
       ps.order = d_act.p; ps.order_count = d_act.p + slots;
       launch_skipped_replan(slots, sp, ps, st);
     }
-    // the presolve's zero-iteration certificate as a kernel of its own, one wave per replan: the replans it finishes (nine in ten of the
-    // bench's scenes) cost the interior-point launch an immediate return (qp_presolve_kernel.hip)
-    if (use_reg && presolve_kernel && ps.line_far != nullptr && !ps.lines_override && d_presolved.n >= (size_t)slots) {
+    if (pre && !fused_pre) {      // the certificate as a kernel of its own, one wave per replan
       ps.presolved = d_presolved.p;
       launch_qp_presolve(slots, sp, ps, d_tables.p, sc, d_presolved.p, st);
       last_path |= NEP_PATH_PRESOLVE_KERNEL;
@@ -2042,6 +2056,15 @@ int nep_batch_debug_boxes(nep_batch_t* h, int32_t scene, double* out, int32_t ca
   HIPCHK(hipMemcpy(out, E.d_fe_box.p + (size_t)scene * n, n * sizeof(double), hipMemcpyDeviceToHost));
   return 0;
 }
+int nep_batch_debug_presolved(nep_batch_t* h, int32_t* marks, int32_t cap) {
+  if (!h || !marks || cap < 0) return fail(NEP_E_ARG, "bad arguments");
+  if (cap < h->slots) return fail(NEP_E_CAP, "mark buffer smaller than the slot count");
+  if (!h->eng.d_presolved.p || h->eng.d_presolved.n < (size_t)h->slots) return fail(NEP_E_STATE, "the handle has no certificate marks");
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(marks, h->eng.d_presolved.p, (size_t)h->slots * sizeof(int), hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int nep_batch_debug_order_keys(nep_batch_t* h, int32_t* keys, int32_t cap) {
   if (!h || !keys || cap < 0) return fail(NEP_E_ARG, "bad arguments");
   if (cap < h->slots) return fail(NEP_E_CAP, "key buffer smaller than the slot count");
@@ -2069,6 +2092,7 @@ static int engine_option(Engine& E, const char* name, int32_t v) {
   else if (n == "corr_max") { if (v < 1) return fail(NEP_E_ARG, "corr_max >= 1"); E.opt_corr_max = v; E.sp.corr_max_count = v; }
   else if (n == "fleet_ent_proof") E.opt_fleet_ent_proof = v != 0;      // 0: nep_batch_fleet_predict_ent / _track_ent walk every other agent and static at every step (same states; A/B of the lanes' proofs)
   else if (n == "qp_profile") E.profile_phases = v != 0;
+  else if (n == "presolve_fused") E.presolve_fused = v != 0;        // 0: the certificate always runs as qp_presolve_kernel, never in the separator's wave (A/B, tests; same bytes)
   else if (n == "presolve_kernel") E.presolve_kernel = v != 0;      // 0: the zero-iteration test only inside qp_reg_kernel<true> (rounds 3-5); same results up to the last place of the objective
   else return fail(NEP_E_ARG, "unknown debug option: " + n);
   return 0;

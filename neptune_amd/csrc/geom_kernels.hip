@@ -21,14 +21,11 @@
 #include "nep_device.h"
 #include "../../include/neptune_frontend.h"
 #include "ent_device.h"
+#include "qp_presolve.h"
 
 namespace nep {
 
-__constant__ double cAPosInv[4][4] = {
-    {-0.03203276669713047, -0.09273093424558249, 0.3420572455666699, 1.1023313949144335},
-    {-0.05111494245568798, -0.046272612998418894, 0.5458234872124772, 1.0979806946005568},
-    {-0.07454781852812224, 0.203951949894552, 0.796048050105448, 1.0745478185281223},
-    {1.0, 1.0, 0.9999999999999996, 0.9999999999999993}};
+__constant__ double cAPosInv[4][4] = NEP_APOS_INV_LITERALS;      // (nep_tables.h)
 
 #define SEP_MIN_GAP 1e-7
 #define NEP_INF (__builtin_huge_val())
@@ -1166,6 +1163,14 @@ __global__ __launch_bounds__(64, NEP_SEP_WAVES) void separator_packed_kernel(Sce
   cx.skip_box = cull ? ps.skip_box : nullptr; cx.skip_r = sp.cull_radius;      // (the spatial presolve on top: LPs known to give a far line are not solved)
   const int total = cx.total, cap = sep_packed_cap(cx.nH + cx.N + cx.S);
   int seg_end = seg_hi < K ? seg_hi : K; if (seg_end > sp.num_pol) seg_end = sp.num_pol;      // segments [seg_lo, seg_end) exist
+  // The zero-iteration certificate of the line presolve in this wave (qp_presolve.h; ps.pre_tables: the host gives them only when the wave
+  // holds every segment of its slot and the cull is on): what qp_presolve_kernel would read back through a chain of global round trips
+  // — the guess, the counts, every near line — is in this wave's hands.  (a) here, (b) on the lines in flush(), (c) after the counts.
+  // The control points at z* (sPre: x, y of [segment][4]) live behind the list's entries; the coefficients at z* stay in three
+  // registers of a lane while the point-set pool is in use.
+  const bool cert = ps.pre_tables != nullptr && K >= 3 && K <= NEP_MAX_POL && K <= sp.num_pol;      // (anything else abstains, as the kernel of its own does)
+  double* sPre = sdyn + (((const char*)(sAtt + cap + (sp.ent_enabled ? sp.num_agents : 0)) - (const char*)sdyn + 7) >> 3);
+  PreStart pre; pre.viol = -1.0; pre.th[0] = pre.th[1] = pre.th[2] = 0.0; pre.obj = 0.0; pre.moved = false; pre.has_qc = false; pre.z_override = false;
   if (lane < 6 * NEP_MAX_POL) sCnt[lane] = 0;
   if (lane < 4 * (seg_hi - seg_lo)) {  // ctrlPtsInit_[seg] (solver_gurobi_poly.cpp:232-243)
     const int seg = seg_lo + (lane >> 2), k = lane & 3;
@@ -1331,6 +1336,9 @@ __global__ __launch_bounds__(64, NEP_SEP_WAVES) void separator_packed_kernel(Sce
     }
     SEP_PT(3);
   }
+  // (a) the start point, before the first batch of LPs: the point-set pool is free to hold the coefficients at z* for a moment, and
+  // everything the certificate needs of the guess and the tables comes in one round trip — nothing is read for it after the lines
+  if (cert) pre = pre_start(sp, ps.pre_tables + K, g, K, lane, sPre, sdyn, cAPosInv);
   __syncthreads();
   int n_list = 0;
   // ---- the LPs gathered so far, 64 to a batch across the segments ----
@@ -1371,6 +1379,8 @@ __global__ __launch_bounds__(64, NEP_SEP_WAVES) void separator_packed_kernel(Sce
           for (int k = 0; k < 4; k++) { const double v = (nd[0] * B4.x[k] + nd[1] * B4.y[k]) + (nd[2] - 1.0); if (v > worst) worst = v; }
           const double len = sqrt(nd[0] * nd[0] + nd[1] * nd[1]);
           far = !ok || -worst > sp.cull_radius * len;
+          // (b) a near line against the control points at z* (a failed LP's null line is far and constrains nothing)
+          if (cert && !far) pre.viol = fmax(pre.viol, pre_line_viol(nd[0], nd[1], nd[2], sPre + sl * 4, sPre + 32 + sl * 4));
         }
       }
       // Near lines keep their call order at the front of their segment's bucket, far ones from its end.  The list is segment-major, so
@@ -1571,16 +1581,34 @@ __global__ __launch_bounds__(64, NEP_SEP_WAVES) void separator_packed_kernel(Sce
     flush();
   }
   __syncthreads();
+  int cn_ = 0, cf_ = 0;
+  bool spill_ = false;
   if (lane < seg_hi - seg_lo) {
     const int seg = seg_lo + lane;
     const long o = (long)slot * NEP_MAX_POL + seg;
-    int cn_ = sCnt[seg * 6], cf_ = sCnt[seg * 6 + 1];
-    bool spill_ = false;
+    cn_ = sCnt[seg * 6]; cf_ = sCnt[seg * 6 + 1];
     if (cn_ + cf_ > sp.lines_cap) { spill_ = true; if (ps.flags) atomicOr(ps.flags, NEP_FLAG_LINES); if (cn_ > sp.lines_cap) cn_ = sp.lines_cap; if (cf_ > sp.lines_cap - cn_) cf_ = sp.lines_cap - cn_; }      // (bucket smaller than the worst case: flagged, and the replan fails — see separator_body)
     ps.line_cnt[o] = spill_ ? -1 - cn_ : cn_;
     if (ps.line_far) ps.line_far[o] = cf_;
     if (ps.line_skip) ps.line_skip[o] = sCnt[seg * 6 + 4];
     ps.lp_stats[o * 2] = sCnt[seg * 6 + 3] + sCnt[seg * 6 + 4]; ps.lp_stats[o * 2 + 1] = sCnt[seg * 6 + 2];
+  }
+  // (c) the certificate's closing, on the counts just stored (the clamped ones of an overflowed bucket never get here: that replan
+  // fails).  The mark is written on every path: a replayed graph never reads a stale one.
+  if (ps.pre_tables) {
+    bool done = false;
+    if (cert && __ballot(spill_) == 0ull) {
+      const long long t0 = (long long)wall_clock64();      // (stats.solve_us of a slot certified here is this closing alone: the start point and the line tests ran amid the separator's own work — include/neptune_backend.h)
+      int L_near = cn_, n_far = cf_, n_sk = (lane < NEP_MAX_POL && ps.line_skip) ? sCnt[lane * 6 + 4] : 0;      // (lanes 0..7 hold a segment each, the rest nothing)
+#pragma unroll
+      for (int o_ = 4; o_ > 0; o_ >>= 1) { L_near += __shfl_xor(L_near, o_); n_far += __shfl_xor(n_far, o_); n_sk += __shfl_xor(n_sk, o_); }
+      L_near = __builtin_amdgcn_readfirstlane(L_near); n_far = __builtin_amdgcn_readfirstlane(n_far); n_sk = __builtin_amdgcn_readfirstlane(n_sk);
+      int lpv = 0;      // what lp_stats holds of the slot: (attempted + skipped, failed) per segment
+      if (lane < 2 * NEP_MAX_POL) lpv = (lane & 1) ? sCnt[(lane >> 1) * 6 + 2] : sCnt[(lane >> 1) * 6 + 3] + sCnt[(lane >> 1) * 6 + 4];
+      SampleSched sched_; sched_.n = ps.pre_sched_n; sched_.seg = nullptr; sched_.dt = nullptr;
+      done = pre_close(sp, ps, sched_, slot, K, lane, pre, L_near, n_far, n_sk, lpv, sdyn, g, t0, ps.presolved);      // (the point-set pool is free after the last batch of LPs: 96 of its doubles)
+    }
+    if (!done && lane == 0) ps.presolved[slot] = 0;
   }
   SEP_PT(8);
 #ifdef NEP_SEP_PROF
@@ -1624,31 +1652,41 @@ static int separator_pool_pairs(const SceneParams& sp) {
   return (int)((separator_lds_bytes(sp) - tail) / 16);
 }
 
-void launch_separator(int n_slots, const SceneParams& sp, const ProblemSet& ps, hipStream_t st) {
-  if (n_slots <= 0) return;
+// segments per wave of the packed kernel for this launch, 0 when the launch takes the unpacked kernel
+int separator_pack(int n_slots, const SceneParams& sp, const ProblemSet& ps) {
   // (only with the spatial presolve: with every LP to solve a segment fills its wave by itself — 64 to 68 LPs — and the packed form is
   // slower, 0.53 against 0.41 ms per 4.2 M LPs: its step 1 is serial over the segments and its lanes hold different control points)
   const int total = sp.n_hull + sp.num_agents + sp.n_static + (sp.ent_enabled ? sp.num_agents * kBend : 0);
   // the packed kernel's list entries are (segment << 13 | candidate) in 16 bits: candidates beyond 8 191 (about 800 agents with the
   // entangle rows, 4 000 without) take the unpacked kernel, whose entries hold 65 535 (size_scratch refuses more)
-  if (((ps.skip_box && ps.line_far && sp.cull_radius > 0.0 && ps.sep_pack >= 0) || (sp.cull_radius == 0.0 && ps.sep_pack >= 1)) && sp.sep_rule == 0 && total <= 8191) {
+  if (!(((ps.skip_box && ps.line_far && sp.cull_radius > 0.0 && ps.sep_pack >= 0) || (sp.cull_radius == 0.0 && ps.sep_pack >= 1)) && sp.sep_rule == 0 && total <= 8191)) return 0;
+  int pack = 1; while (pack < NEP_MAX_POL && (long)n_slots * (NEP_MAX_POL / (pack * 2)) >= 4096) pack *= 2;      // (at least ~4 000 waves while the launch allows it)
+  if (ps.sep_pack >= 1 && ps.sep_pack <= NEP_MAX_POL) pack = ps.sep_pack;
+  return pack;
+}
+void launch_separator(int n_slots, const SceneParams& sp, const ProblemSet& ps_in, hipStream_t st) {
+  if (n_slots <= 0) return;
+  const int pack = separator_pack(n_slots, sp, ps_in);
+  if (pack > 0) {
+    ProblemSet ps = ps_in;
+    if (pack != NEP_MAX_POL || !(sp.cull_radius > 0.0) || !ps.line_far || !ps.presolved || !ps.pre_sched_n || ps.active) ps.pre_tables = nullptr;      // (the certificate needs the whole slot in one wave; the wave of an inactive slot returns at its first line and would leave a stale mark)
     // (the wave's LDS stays within the 10 KB sixteen waves per CU allow: the pool of point sets takes what the tables leave, 64 x 8 pairs at least)
     const size_t rounds_ = (size_t)((sp.n_hull + 63) / 64 + (sp.num_agents + 63) / 64 + (sp.n_static + 63) / 64);
     const size_t extras = 15 * NEP_MAX_POL * sizeof(double) + 2 * NEP_MAX_POL * rounds_ * sizeof(unsigned long long) + 6 * NEP_MAX_POL * sizeof(int)
                           + ((sp.ent_enabled && ps.case_id) ? (size_t)NEP_MAX_POL * ((sp.num_agents + 63) / 64) * sizeof(unsigned long long) : 0)
-                          + (size_t)(sep_packed_cap(sp.n_hull + sp.num_agents + sp.n_static) + (sp.ent_enabled ? sp.num_agents : 0)) * sizeof(unsigned short);
+                          + (size_t)(sep_packed_cap(sp.n_hull + sp.num_agents + sp.n_static) + (sp.ent_enabled ? sp.num_agents : 0)) * sizeof(unsigned short)
+                          + (ps.pre_tables ? (size_t)8 * NEP_MAX_POL * sizeof(double) + 8 : 0);      // (the certificate's control points at z*, live through the LP batches: x, y of [segment][4], 8-byte aligned behind the entries)
     size_t pool_b = extras + 64 * 6 * 16 <= (size_t)kSepLdsTarget ? (size_t)kSepLdsTarget - extras : (size_t)64 * 6 * 16;
     pool_b &= ~(size_t)15;
     const int pairs = (int)(pool_b / 16);
     const size_t lds_p = (pool_b + extras + 15) & ~(size_t)15;
     static DynLdsAttr attr_p;
     (void)attr_p.ensure((const void*)separator_packed_kernel, lds_p);
-    int pack = 1; while (pack < NEP_MAX_POL && (long)n_slots * (NEP_MAX_POL / (pack * 2)) >= 4096) pack *= 2;      // (at least ~4 000 waves while the launch allows it)
-    if (ps.sep_pack >= 1 && ps.sep_pack <= NEP_MAX_POL) pack = ps.sep_pack;
     const int groups = (NEP_MAX_POL + pack - 1) / pack;
     hipLaunchKernelGGL(separator_packed_kernel, dim3(n_slots * groups), dim3(64), lds_p, st, sp, ps, pairs, pack);
     return;
   }
+  const ProblemSet& ps = ps_in;
   const size_t lds = separator_lds_bytes(sp);
   static DynLdsAttr attr[2];
   if (sp.sep_rule == 1) {

@@ -106,7 +106,11 @@ struct ProblemSet {
   double* polish_z;              // [slots][2][24] last iterate of the first / relaxed solve (axis stride nz), or null: no polish
   int* polish_flag;              // [slots] bit m: mode m's solve ended on the loose snapshot or gave up
   int* polish_list; int* polish_count;      // [slots] listed slots; counters (see qp_polish_kernel)
-  int* presolved;                // [slots] 1: qp_presolve_kernel finished this replan (its certificate held); the interior-point kernel returns at once.  Null: that kernel did not run
+  int* presolved;                // [slots] 1: the zero-iteration certificate finished this replan (qp_presolve.h: qp_presolve_kernel, or the separator's wave); the interior-point kernel returns at once.  Null: the certificate did not run ahead of that kernel
+  // the certificate in the separator's wave: non-null only for a launch of separator_packed_kernel in which one wave holds every segment
+  // of a slot, with the line cull on and `presolved` given (Engine::run); the wave then writes presolved[slot] = 0 or 1 for every slot it reaches
+  const QpTable* pre_tables;     // the QP tables (indexed by K), or null: the separator makes lines only
+  const int* pre_sched_n;        // SampleSched::n (states of the schedule of K)
   long long* dbg;                // [slots][16] phase cycle counters (development aid) or null
   int* flags;                    // [1] sticky NEP_FLAG_* bits raised by the kernels (capacity overflows), or null
   double* fe_box;                // [scenes][num_agents + n_static][num_pol][4] (x0, x1, y0, y1) of the front end's obstacles (fe_box_kernel)
@@ -175,6 +179,7 @@ void launch_hulls_explicit(const nep_traj_rec* recs, int n_traj, double t_start,
                            double T_span, double drone_radius, double* hull_xy, int* hull_nv,
                            double* hull0_xy, int* hull0_nv, int* flags, hipStream_t st);
 void launch_separator(int n_slots, const SceneParams& sp, const ProblemSet& ps, hipStream_t st);
+int separator_pack(int n_slots, const SceneParams& sp, const ProblemSet& ps);      // segments per wave of the packed separator for this launch, 0: the unpacked kernel
 void launch_separator_redo(int n_slots, const SceneParams& sp, const ProblemSet& ps, hipStream_t st);
 void launch_boxes(int n_scenes, const SceneParams& sp, const ProblemSet& ps, hipStream_t st);
 void launch_active_rows(int n_slots, const SceneParams& sp, const ProblemSet& ps, double tol, int* out, hipStream_t st);

@@ -20,11 +20,13 @@ namespace nep {
 // (reference neptune/include/mader_types.hpp:152-163): exact rational inverse of the
 // double-rounded literals, rounded to double.  (A*diag(T^-3,T^-2,T^-1,1))^-1 = diag(T^3,..)*A^-1
 // gives A_rest_pos_basis_inverse_ of solver_gurobi_poly.cpp:93.
-static const double kAPosInv[4][4] = {
-    {-0.03203276669713047, -0.09273093424558249, 0.3420572455666699, 1.1023313949144335},
-    {-0.05111494245568798, -0.046272612998418894, 0.5458234872124772, 1.0979806946005568},
-    {-0.07454781852812224, 0.203951949894552, 0.796048050105448, 1.0745478185281223},
-    {1.0, 1.0, 0.9999999999999996, 0.9999999999999993}};
+// (one set of literals: the host table here and the kernels' __constant__ copies — a device symbol belongs to its translation unit — are initialised from it)
+#define NEP_APOS_INV_LITERALS { \
+    {-0.03203276669713047, -0.09273093424558249, 0.3420572455666699, 1.1023313949144335}, \
+    {-0.05111494245568798, -0.046272612998418894, 0.5458234872124772, 1.0979806946005568}, \
+    {-0.07454781852812224, 0.203951949894552, 0.796048050105448, 1.0745478185281223}, \
+    {1.0, 1.0, 0.9999999999999996, 0.9999999999999993}}
+static const double kAPosInv[4][4] = NEP_APOS_INV_LITERALS;
 static const double kAVelInv[3][3] = {
     {-0.07735026918962577, 0.16666666666666635, 1.077350269189625},
     {-0.07735026918962577, 0.49999999999999967, 1.077350269189625},

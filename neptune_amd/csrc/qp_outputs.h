@@ -1,14 +1,15 @@
 // qp_outputs.h — the writers of what a replan leaves behind: the trajectory (nep_solution: coefficients, knot times), generatePwpOut's
 // sampled states, and the record the agent publishes (d_commit).  Called by NT cooperating threads of which the caller is thread `tid`;
 // theta is the trajectory as [3][NEP_MAX_POL][4] (axis, segment, a b c d).  Callers: qp_kernel and skipped_replan_kernel (everything
-// they write), qp_presolve_kernel (write_trajectory), qp_reg_kernel (everything but the exceptions below), polish_slot (sched_states,
+// they write), the certificate of qp_presolve.h (write_trajectory, sched_states), qp_reg_kernel (everything but the exceptions below), polish_slot (sched_states,
 // write_states), sample_kernel (sample_state).
 // Sites that keep their own lines, each for a reason stated there (profiles/qp_outputs_kernel_resources.txt, profiles/qp_outputs_ab.txt):
 // the carry-over loop in the main tails of qp_kernel and qp_reg_kernel (carry_commit serves skipped_replan_kernel), and the trajectory
 // and record stores of polish_slot.  A field added to nep_traj_rec is added in write_commit and in polish_slot;
 // tests/test_gpu_replan_outputs.py checks every site field by field.
-// The translation units that include this compile with fp contraction on: the bracketing of the sampling expressions is what the
-// oracle is compared against at 1e-12 and stays exactly as it is.
+// The translation units that sample states or write records through this compile with fp contraction on: the bracketing of the
+// sampling expressions is what the oracle is compared against at 1e-12 and stays exactly as it is.  geom_kernels.hip (no contraction)
+// includes it through qp_presolve.h for write_trajectory and sched_states alone, which do not depend on the flag.
 #pragma once
 #include "nep_device.h"
 
@@ -44,7 +45,9 @@ __device__ __forceinline__ void write_states(const SceneParams& sp, const Proble
 template <int NT>
 __device__ __forceinline__ void write_trajectory(nep_solution* sol, const double* theta, int K, const double* t_start, double T, int tid) {
   for (int t = tid; t < 3 * NEP_MAX_POL * 4; t += NT) (&sol->coeff[0][0][0])[t] = ((t % (NEP_MAX_POL * 4)) / 4 < K) ? theta[t] : 0.0;
-  if (tid <= NEP_MAX_POL) sol->times[tid] = (tid <= K) ? *t_start + tid * T : 0.0;
+  // (the knot time as every contracting caller always compiled it, one fused operation, written out: the certificate's tail in
+  // geom_kernels.hip, a translation unit without contraction, must store the same bytes — qp_presolve.h)
+  if (tid <= NEP_MAX_POL) sol->times[tid] = (tid <= K) ? __builtin_fma((double)tid, T, *t_start) : 0.0;
 }
 
 // the record the agent would publish (neptune_ros.cpp:434-480)
