@@ -267,7 +267,7 @@ typedef struct nep_mission_leg {
 
 /* One scene's mission state and inputs in host memory, for nep_mission_step (slots are the scene's agents, in order). */
 typedef struct nep_mission_scene {
-  int32_t n_agents, scene;        /* global slot = scene * n_agents + agent                                                  */
+  int32_t n_agents, scene;        /* global slot = scene * n_agents + agent; the scene's ORIGIN index (see the recorder)     */
   int32_t round_ticks, n_poly;
   double t_now, dc;
   const double* pos;              /* [n_agents][round_ticks + 1][3]: p_0 .. p_round_ticks                                    */
@@ -321,6 +321,103 @@ int nep_batch_fleet_mission_log(nep_batch_t* h, nep_mission_leg* log_out, int32_
  * (neptune_amd/csrc/mission_common.h) and the device equals a chain of these calls byte for byte.  NEP_E_ARG on a bad
  * configuration or null pointers.                                                                                               */
 int nep_mission_step(const nep_mission_cfg* cfg, nep_mission_scene* sc);
+
+/* ---- recorder: snapshot, restore and replay ------------------------------------------------------------------------------------
+ * A snapshot is the complete fleet state of a handle as one blob: whatever decides what the fleet calls do next.  A handle restored
+ * from it continues byte for byte like the flight the snapshot was taken from (what that leaves out: nep_stats.solve_us, a measured
+ * time, and the order in which slots are launched).
+ *
+ * Blob layout.  nep_fleet_snapshot_hdr (NEP_SNAPSHOT_HDR_BYTES = 80), then n_scenes scene blocks of scene_bytes each, scene 0
+ * first.  A block is self-contained and contiguous — one scene of a blob is a slice — and is a sequence of NEP_SNAPSHOT_N_SECTIONS
+ * sections in the order of the NEP_SNAP_* indices below.  A section holds the scene's part of one array of the handle, raw
+ * ([N] slots of the scene, or one per-scene entry), padded with zeros to a multiple of 16 bytes: every section starts on a 16-byte
+ * boundary (relative to the blob, which itself must be 16-byte aligned in device memory), scene_bytes is a multiple of 16, and the
+ * same state gives the same bytes.  A section the state does not have is 0 bytes long.  The sizes follow from the header's
+ * fields alone (nep_fleet_snapshot_describe gives offsets and sizes; neptune_amd/csrc/recorder_common.h is the one statement of
+ * the arithmetic, shared by the library's host code and its kernels):
+ *   the block's header  ORIGIN 4 (the scene's origin index, below), ROUND 4 (the round counter)
+ *   fleet               RING N*ring_cap*96 (raw: stale entries included), HEAD SIZE K_END N*4, STATE N*96, GOAL N*24, PWP N*sizeof(nep_pwp),
+ *                       FLOWN DONE OUTCOME SFLAGS N*4, PERIOD PHASE N*4 (timers != 0), T_NOW 8, COUNTERS 4*NEP_FLEET_N_COUNTERS
+ *   tethers             form 1: ENT N*sizeof(nep_fe_ent_state).  form 2 (lists of tether_cap entries): L_N_ALPHA L_N_BEND N*4,
+ *                       L_ID N*cap*2, L_CS N*cap, L_BETA N*cap*8, L_BEND N*NEP_MAX_BEND*2, HELD N*4.  Both: PUB_N N*4, PUB_XY
+ *                       N*NEP_MAX_BEND*16 (the list published at the last select), PUB_PREV_N, PUB_PREV_XY (the one before), ENT_FLAGS
+ *                       (last tracked round) ENT_EVER (sticky) ENT_WALKED N*4
+ *   missions            T_ISSUE LENGTH N*8, COMPLETED N*4, COUNTS N*16, SUMS N*16, SCENE_I 16, T_RUN 8, LOG owners*log_cap*64,
+ *                       LOG_N owners*4 with owners = N (mode PER_AGENT) or 1 (mode FLEET_RUNS)
+ * cfg_hash is FNV-1a 64 (offset basis 0xcbf29ce484222325, prime 0x100000001b3) over the bytes of the nep_fleet_cfg given to
+ * nep_batch_fleet_init, the 8 bytes of the cable length (0.0 without tethers) and the bytes of the nep_mission_cfg (zeros without
+ * missions), in that order.
+ *
+ * Not in a snapshot: the scene geometry (statics, static representatives, keep-outs, bases); the handle's options; the handle-wide
+ * sticky word nep_batch_check reports; the launch-order keys and other history that only changes the order of launches; the scratch
+ * of the calls; and every buffer the caller owns — the audit records among them: nep_audit accumulates, so who resumes a flight
+ * saves and restores that buffer himself.
+ *
+ * Origin.  The mission generator hashes the global slot, and a scene flown alone in a one-scene handle sits at scene 0 whatever
+ * it was in its batch.  Every scene of the fleet state therefore carries an origin index: nep_batch_fleet_init sets it to the
+ * scene's own index, a restore copies it from the block, and the mission controller uses origin * N + agent as the generator's
+ * global slot and as `who` of a leg record (mode FLEET_RUNS: the origin), as nep_mission_scene.scene does on the host side.
+ *
+ * nep_batch_fleet_snapshot_bytes       header + n_scenes blocks for the state the handle has now (it grows when tethers or missions
+ *                          are initialised afterwards).
+ * nep_batch_fleet_snapshot             writes the blob to d_blob (device memory, 16-byte aligned) with one kernel, header included.
+ *                          Asynchronous, capturable.  NEP_E_STATE before nep_batch_fleet_init; unsharded handles only.
+ * nep_batch_fleet_snapshot_ring        the same kernel into a ring of the last n_entries rounds: d_ring is a header (n_scenes as the
+ *                          handle's), a stamp table [n_entries][n_scenes] of nep_fleet_snapshot_stamp, then [n_entries][n_scenes]
+ *                          scene blocks.  Scene s goes to entry round[s] mod n_entries, read on the device from the handle's round
+ *                          counter, and its stamp becomes {1, round, origin, 0}; a table zeroed by the caller means empty.  The header
+ *                          followed by the n_scenes blocks of one entry is a blob.  Asynchronous, capturable.
+ * nep_batch_fleet_restore              puts a blob (host or device memory) back.  The handle has been through nep_batch_fleet_init,
+ *                          the tether init of the blob's form and capacity and nep_batch_fleet_mission_init when the blob has mission
+ *                          state, with the same configurations: the header is checked against the handle (N, num_pol, ring_cap,
+ *                          max_states, timers, tether form and capacity, mission mode, log_cap, scene_bytes, cfg_hash) and `bytes`
+ *                          against the header; any mismatch is NEP_E_ARG and leaves the handle's state exactly as it was.
+ *                          src_scene = dst_scene = -1: all scenes (equal scene counts).  Otherwise block src_scene of the blob goes
+ *                          into scene dst_scene of the handle.  Blocking; NEP_E_STATE while the calling thread's stream capture is on.
+ * nep_fleet_snapshot_describe          host only: checks a header (magic, version, sizes, bytes >= header + blocks, scene_bytes a
+ *                          multiple of 16 that holds every section: else NEP_E_ARG) and gives the sections' offsets in a block.   */
+#define NEP_SNAPSHOT_MAGIC 0x5046454eu   /* "NEFP" */
+#define NEP_SNAPSHOT_VERSION 1
+#define NEP_SNAPSHOT_HDR_BYTES 80
+#define NEP_SNAPSHOT_N_SECTIONS 41
+enum {
+  NEP_SNAP_ORIGIN = 0, NEP_SNAP_ROUND, NEP_SNAP_RING, NEP_SNAP_HEAD, NEP_SNAP_SIZE, NEP_SNAP_K_END, NEP_SNAP_STATE, NEP_SNAP_GOAL, NEP_SNAP_PWP,
+  NEP_SNAP_FLOWN, NEP_SNAP_DONE, NEP_SNAP_OUTCOME, NEP_SNAP_SFLAGS, NEP_SNAP_PERIOD, NEP_SNAP_PHASE, NEP_SNAP_T_NOW, NEP_SNAP_COUNTERS,
+  NEP_SNAP_ENT, NEP_SNAP_L_N_ALPHA, NEP_SNAP_L_N_BEND, NEP_SNAP_L_ID, NEP_SNAP_L_CS, NEP_SNAP_L_BETA, NEP_SNAP_L_BEND, NEP_SNAP_HELD,
+  NEP_SNAP_PUB_N, NEP_SNAP_PUB_XY, NEP_SNAP_PUB_PREV_N, NEP_SNAP_PUB_PREV_XY, NEP_SNAP_ENT_FLAGS, NEP_SNAP_ENT_EVER, NEP_SNAP_ENT_WALKED,
+  NEP_SNAP_T_ISSUE, NEP_SNAP_LENGTH, NEP_SNAP_COMPLETED, NEP_SNAP_COUNTS, NEP_SNAP_SUMS, NEP_SNAP_SCENE_I, NEP_SNAP_T_RUN, NEP_SNAP_LOG, NEP_SNAP_LOG_N
+};
+
+/* nep_abi_sizeof(25): NEP_SNAPSHOT_HDR_BYTES */
+typedef struct nep_fleet_snapshot_hdr {
+  uint32_t magic;                 /* NEP_SNAPSHOT_MAGIC                                                                      */
+  int32_t version, hdr_bytes;     /* NEP_SNAPSHOT_VERSION, NEP_SNAPSHOT_HDR_BYTES                                            */
+  int32_t n_scenes, N, num_pol, ring_cap, max_states;
+  int32_t tether_form;            /* 0 none, 1 the fixed record, 2 lists                                                     */
+  int32_t tether_cap;             /* form 1: NEP_FE_ENT_CAP, form 2: the lists' capacity, else 0                             */
+  int32_t mission_mode;           /* 0 none, else NEP_MISSION_*                                                              */
+  int32_t log_cap;
+  int32_t timers;                 /* 1: the handle has periods and phases                                                    */
+  int32_t _pad[3];
+  int64_t scene_bytes;
+  uint64_t cfg_hash;
+} nep_fleet_snapshot_hdr;
+
+/* one (entry, scene) of a ring's stamp table: 16 bytes */
+typedef struct nep_fleet_snapshot_stamp { int32_t used, round, origin, _pad; } nep_fleet_snapshot_stamp;
+
+typedef struct nep_fleet_snapshot_info {
+  nep_fleet_snapshot_hdr hdr;
+  int64_t offset[NEP_SNAPSHOT_N_SECTIONS];      /* of a section in its block                                                */
+  int64_t bytes[NEP_SNAPSHOT_N_SECTIONS];       /* unpadded; 0: the state has no such section                               */
+} nep_fleet_snapshot_info;
+
+int64_t nep_batch_fleet_snapshot_bytes(const nep_batch_t* h);
+int nep_batch_fleet_snapshot(nep_batch_t* h, void* d_blob, void* stream);
+int64_t nep_batch_fleet_snapshot_ring_bytes(const nep_batch_t* h, int32_t n_entries);
+int nep_batch_fleet_snapshot_ring(nep_batch_t* h, void* d_ring, int32_t n_entries, void* stream);
+int nep_batch_fleet_restore(nep_batch_t* h, const void* blob, int64_t bytes, int32_t src_scene, int32_t dst_scene);
+int nep_fleet_snapshot_describe(const void* host_blob, int64_t bytes, nep_fleet_snapshot_info* out);
 
 /* ---- readers: blocking (they wait for the device), for tests and reports; every output is host memory and may be NULL ------ */
 /* ring_cap of the handle's fleet state (NEP_E_STATE before nep_batch_fleet_init)                                              */

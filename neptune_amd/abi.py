@@ -253,6 +253,29 @@ class nep_mission_scene(C.Structure):
                 ("log", C.c_void_p), ("log_n", C.c_void_p)]
 
 
+# ---- the recorder (include/neptune_fleet.h) ----
+NEP_SNAPSHOT_MAGIC, NEP_SNAPSHOT_VERSION, NEP_SNAPSHOT_HDR_BYTES, NEP_SNAPSHOT_N_SECTIONS = 0x5046454e, 1, 80, 41
+SNAPSHOT_SECTIONS = ("origin", "round", "ring", "head", "size", "k_end", "state", "goal", "pwp", "flown", "done", "outcome", "sflags", "period", "phase",
+                     "t_now", "counters", "ent", "l_n_alpha", "l_n_bend", "l_id", "l_cs", "l_beta", "l_bend", "held", "pub_n", "pub_xy", "pub_prev_n",
+                     "pub_prev_xy", "ent_flags", "ent_ever", "ent_walked", "t_issue", "length", "completed", "counts", "sums", "scene_i", "t_run", "log", "log_n")
+
+
+class nep_fleet_snapshot_hdr(C.Structure):
+    """include/neptune_fleet.h: what a fleet snapshot starts with."""
+    _fields_ = [("magic", C.c_uint32), ("version", C.c_int32), ("hdr_bytes", C.c_int32), ("n_scenes", C.c_int32), ("N", C.c_int32),
+                ("num_pol", C.c_int32), ("ring_cap", C.c_int32), ("max_states", C.c_int32), ("tether_form", C.c_int32), ("tether_cap", C.c_int32),
+                ("mission_mode", C.c_int32), ("log_cap", C.c_int32), ("timers", C.c_int32), ("_pad", C.c_int32 * 3),
+                ("scene_bytes", C.c_int64), ("cfg_hash", C.c_uint64)]
+
+
+class nep_fleet_snapshot_info(C.Structure):
+    """include/neptune_fleet.h: nep_fleet_snapshot_describe's answer — the header, and every section's offset in a block and size."""
+    _fields_ = [("hdr", nep_fleet_snapshot_hdr), ("offset", C.c_int64 * NEP_SNAPSHOT_N_SECTIONS), ("bytes", C.c_int64 * NEP_SNAPSHOT_N_SECTIONS)]
+
+
+SNAPSHOT_STAMP_DTYPE = np.dtype([("used", np.int32), ("round", np.int32), ("origin", np.int32), ("_pad", np.int32)])
+
+
 def np_dtype(struct):
     return np.dtype(struct)
 

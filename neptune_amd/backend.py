@@ -537,6 +537,54 @@ class BatchBackend:
             return log, n
         return [log[o, [i % cap for i in range(max(0, int(n[o]) - cap), int(n[o]))]] if cap else log[o, :0] for o in range(owners)], n
 
+    # ---- the recorder of the fleet state (include/neptune_fleet.h) --------------------------------------------------
+    def fleet_snapshot_bytes(self):
+        """bytes of a snapshot of the fleet state the handle has now (nep_batch_fleet_snapshot_bytes)"""
+        return int(check(lib().nep_batch_fleet_snapshot_bytes(self._h)))
+
+    def fleet_snapshot(self, d_blob=None, stream=None):
+        """the complete fleet state as one blob -> d_blob (uint8 device tensor of fleet_snapshot_bytes(), made when None);
+        asynchronous, capturable (nep_batch_fleet_snapshot)"""
+        st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        if d_blob is None:
+            d_blob = self.torch.zeros(self.fleet_snapshot_bytes(), dtype=self.torch.uint8, device=self.device)
+        check(lib().nep_batch_fleet_snapshot(self._h, d_blob.data_ptr(), st.cuda_stream))
+        return d_blob
+
+    def fleet_snapshot_ring_bytes(self, n_entries):
+        return int(check(lib().nep_batch_fleet_snapshot_ring_bytes(self._h, int(n_entries))))
+
+    def new_snapshot_ring(self, n_entries):
+        """a zeroed (= empty) ring of the last n_entries rounds' snapshots"""
+        return self.torch.zeros(self.fleet_snapshot_ring_bytes(n_entries), dtype=self.torch.uint8, device=self.device)
+
+    def fleet_snapshot_ring(self, d_ring, n_entries, stream=None):
+        """every scene's state into entry round mod n_entries of d_ring, stamped; asynchronous, capturable (nep_batch_fleet_snapshot_ring)"""
+        st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        check(lib().nep_batch_fleet_snapshot_ring(self._h, d_ring.data_ptr(), int(n_entries), st.cuda_stream))
+
+    def snapshot_ring_stamps(self, d_ring, n_entries):
+        """the ring's stamp table (blocking) -> [n_entries][n_scenes] abi.SNAPSHOT_STAMP_DTYPE"""
+        n = n_entries * self.n_scenes * abi.SNAPSHOT_STAMP_DTYPE.itemsize
+        return d_ring[abi.NEP_SNAPSHOT_HDR_BYTES:abi.NEP_SNAPSHOT_HDR_BYTES + n].cpu().numpy().view(abi.SNAPSHOT_STAMP_DTYPE).reshape(n_entries, self.n_scenes)
+
+    def snapshot_ring_entry(self, d_ring, n_entries, entry):
+        """entry `entry` of a ring as a blob of its own (device tensor: the ring's header and the entry's n_scenes blocks)"""
+        hdr = abi.NEP_SNAPSHOT_HDR_BYTES
+        per = (d_ring.numel() - hdr) // n_entries - self.n_scenes * abi.SNAPSHOT_STAMP_DTYPE.itemsize
+        at = hdr + n_entries * self.n_scenes * abi.SNAPSHOT_STAMP_DTYPE.itemsize + entry * per
+        return self.torch.cat([d_ring[:hdr], d_ring[at:at + per]])
+
+    def fleet_restore(self, blob, src_scene=-1, dst_scene=-1):
+        """puts a snapshot back: blob a uint8 device tensor or a host array / bytes; all scenes, or block src_scene into scene dst_scene
+        (blocking; nep_batch_fleet_restore)"""
+        if hasattr(blob, "data_ptr"):
+            ptr, n = blob.data_ptr(), blob.numel()
+        else:
+            blob = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8))
+            ptr, n = blob.ctypes.data, blob.size
+        check(lib().nep_batch_fleet_restore(self._h, ptr, n, int(src_scene), int(dst_scene)))
+
     def next_starts(self, d_records, dt, d_start, d_alt_goal=None, switch_radius=0.0, stream=None):
         """point A of the next round on the device: d_start's clock advances by dt and its state becomes that of the committed
         trajectories d_records at the new time; with d_alt_goal ([slots][3] float64) arrived agents swap goals

@@ -19,6 +19,7 @@
 #include "qp_outputs.h"
 #include "audit_common.h"
 #include "mission_common.h"
+#include "recorder_common.h"
 #include "../../include/neptune_plan.h"
 #include "../../include/neptune_entangle.h"
 
@@ -1025,7 +1026,7 @@ struct nep_batch {
   struct Fleet {
     bool ready = false, timers = false; int cap = 0; nep_fleet_cfg cfg{};
     DevBuf<double> ring, state, goal, t_now; DevBuf<nep_pwp> pwp;
-    DevBuf<int> head, size, k_end, flown, done, outcome, sflags, period, phase, round, counters;
+    DevBuf<int> head, size, k_end, flown, done, outcome, sflags, period, phase, round, counters, origin;
     // the tethers (nep_batch_fleet_init_ent): state at the tracked position, the published bend lists, flags, scratch
     bool ent_ready = false; double cable = 0.0;
     DevBuf<nep_fe_ent_state> ent, ent_save; DevBuf<double> pub_xy, pub_prev_xy, ent_pos;
@@ -1037,6 +1038,9 @@ struct nep_batch {
     bool mis_ready = false; nep_mission_cfg mis_cfg{}; size_t mis_lds = 0;
     DevBuf<double> mis_t_issue, mis_length, mis_sums, mis_t_run; DevBuf<int> mis_completed, mis_counts, mis_scene, mis_log_n; DevBuf<nep_mission_leg> mis_log;
     DevBuf<int> keep_n, keep_off; DevBuf<double> keep_xy;
+    DevBuf<char> rec_stage;      // nep_batch_fleet_restore: the blob (or the one block of it) on its way in
+    std::vector<hipStream_t> seen;      // the streams nep_batch_fleet_select and the snapshot calls were given (restore refuses while one captures)
+    void saw(void* stream) { hipStream_t st = (hipStream_t)stream; if (!st) return; for (hipStream_t q : seen) if (q == st) return; if (seen.size() < 16) seen.push_back(st); }      // (the null stream cannot capture)
   } fleet;
 };
 
@@ -1540,7 +1544,7 @@ void fleet_args(nep_batch_t* h, FleetArgs& fa) {
   fa.ring = F.ring.p; fa.head = F.head.p; fa.size = F.size.p; fa.k_end = F.k_end.p; fa.state = F.state.p; fa.goal = F.goal.p; fa.pwp = F.pwp.p;
   fa.flown = F.flown.p; fa.done = F.done.p; fa.outcome = F.outcome.p; fa.sflags = F.sflags.p;
   fa.period = F.timers ? F.period.p : nullptr; fa.phase = F.timers ? F.phase.p : nullptr;
-  fa.t_now = F.t_now.p; fa.round = F.round.p; fa.counters = F.counters.p; fa.gflags = h->eng.d_flags.p; fa.active = h->eng.active;
+  fa.t_now = F.t_now.p; fa.round = F.round.p; fa.origin = F.origin.p; fa.counters = F.counters.p; fa.gflags = h->eng.d_flags.p; fa.active = h->eng.active;
 }
 void fleet_ent_args(nep_batch_t* h, TetherArgs& ea) {
   nep_batch::Fleet& F = h->fleet; Engine& E = h->eng;
@@ -1572,11 +1576,13 @@ int nep_batch_fleet_init(nep_batch_t* h, const nep_fleet_cfg* cfg, const double*
   if (int e = F.pwp.ensure(slots)) return e;
   if (int e = F.t_now.ensure(S)) return e;
   if (int e = F.round.ensure(S)) return e;
+  if (int e = F.origin.ensure(S)) return e;
   if (int e = F.counters.ensure(S * NEP_FLEET_N_COUNTERS)) return e;
   for (DevBuf<int>* b : {&F.head, &F.size, &F.k_end, &F.flown, &F.done, &F.outcome, &F.sflags, &F.period, &F.phase})
     if (int e = b->ensure(slots)) return e;
   F.cap = cap; F.cfg = *cfg; F.timers = d_period != nullptr;
   hipStream_t st = (hipStream_t)stream;
+  HIPCHK(hipMemsetAsync(F.ring.p, 0, slots * cap * 12 * sizeof(double), st));      // (a snapshot copies the rings raw: the entries no plan has reached yet are zeros)
   HIPCHK(hipMemcpyAsync(F.goal.p, d_goal, slots * 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
   if (F.timers) {
     HIPCHK(hipMemcpyAsync(F.period.p, d_period, slots * sizeof(int), hipMemcpyDeviceToDevice, st));
@@ -1594,6 +1600,7 @@ int nep_batch_fleet_init(nep_batch_t* h, const nep_fleet_cfg* cfg, const double*
 int nep_batch_fleet_select(nep_batch_t* h, nep_fe_start* d_start, nep_traj_rec* d_records, int32_t* d_active, nep_fe_start* d_clock, void* stream) {
   if (int e = fleet_guard(h, true)) return e;
   if (!d_start || !d_records) return fail(NEP_E_ARG, "null argument");
+  h->fleet.saw(stream);
   FleetArgs fa{};
   fleet_args(h, fa);
   fa.start = d_start; fa.recs = d_records; fa.active_out = d_active; fa.clock = d_clock;
@@ -1889,6 +1896,130 @@ int nep_batch_fleet_mission_log(nep_batch_t* h, nep_mission_leg* log_out, int32_
   if (log_out && F.mis_cfg.log_cap > 0) HIPCHK(hipMemcpy(log_out, F.mis_log.p, owners * (size_t)F.mis_cfg.log_cap * sizeof(nep_mission_leg), hipMemcpyDeviceToHost));
   if (n_out) HIPCHK(hipMemcpy(n_out, F.mis_log_n.p, owners * sizeof(int), hipMemcpyDeviceToHost));
   return F.mis_cfg.log_cap;
+}
+
+// ---- the recorder (include/neptune_fleet.h; kernels: fleet_recorder_kernels.hip; layout: recorder_common.h) ----
+namespace {
+// the header of a snapshot of the state the handle has now
+nep_fleet_snapshot_hdr recorder_header(const nep_batch_t* h) {
+  const nep_batch::Fleet& F = h->fleet;
+  nep_fleet_snapshot_hdr hd{};
+  hd.magic = NEP_SNAPSHOT_MAGIC; hd.version = NEP_SNAPSHOT_VERSION; hd.hdr_bytes = NEP_SNAPSHOT_HDR_BYTES;
+  hd.n_scenes = h->cfg.n_scenes; hd.N = h->cfg.num_agents; hd.num_pol = h->cfg.num_pol; hd.ring_cap = F.cap; hd.max_states = h->cfg.max_states;
+  hd.tether_form = !F.ent_ready ? 0 : F.ent_cap ? 2 : 1; hd.tether_cap = !F.ent_ready ? 0 : F.ent_cap ? F.ent_cap : NEP_FE_ENT_CAP;
+  hd.mission_mode = F.mis_ready ? F.mis_cfg.mode : 0; hd.log_cap = F.mis_ready ? F.mis_cfg.log_cap : 0;
+  hd.timers = F.timers ? 1 : 0;
+  hd.scene_bytes = nep_recorder::layout(hd, nullptr, nullptr);
+  nep_mission_cfg none{};
+  hd.cfg_hash = nep_recorder::config_hash(F.cfg, F.ent_ready ? F.cable : 0.0, F.mis_ready ? F.mis_cfg : none);
+  return hd;
+}
+// the sections of hd's layout on the handle's arrays; every section is checked against its allocation
+int recorder_args(nep_batch_t* h, const nep_fleet_snapshot_hdr& hd, RecorderArgs& ra) {
+  nep_batch::Fleet& F = h->fleet;
+  int64_t off[NEP_SNAPSHOT_N_SECTIONS], bytes[NEP_SNAPSHOT_N_SECTIONS];
+  nep_recorder::layout(hd, off, bytes);
+  struct Arr { void* p; size_t have; };
+  auto arr = [](auto& b) { return Arr{(void*)b.p, b.n * sizeof(*b.p)}; };
+  Arr a[NEP_SNAPSHOT_N_SECTIONS] = {};
+  a[NEP_SNAP_ORIGIN] = arr(F.origin); a[NEP_SNAP_ROUND] = arr(F.round); a[NEP_SNAP_RING] = arr(F.ring); a[NEP_SNAP_HEAD] = arr(F.head); a[NEP_SNAP_SIZE] = arr(F.size);
+  a[NEP_SNAP_K_END] = arr(F.k_end); a[NEP_SNAP_STATE] = arr(F.state); a[NEP_SNAP_GOAL] = arr(F.goal); a[NEP_SNAP_PWP] = arr(F.pwp); a[NEP_SNAP_FLOWN] = arr(F.flown);
+  a[NEP_SNAP_DONE] = arr(F.done); a[NEP_SNAP_OUTCOME] = arr(F.outcome); a[NEP_SNAP_SFLAGS] = arr(F.sflags); a[NEP_SNAP_PERIOD] = arr(F.period); a[NEP_SNAP_PHASE] = arr(F.phase);
+  a[NEP_SNAP_T_NOW] = arr(F.t_now); a[NEP_SNAP_COUNTERS] = arr(F.counters);
+  a[NEP_SNAP_ENT] = arr(F.ent); a[NEP_SNAP_L_N_ALPHA] = arr(F.ent_lists.n_alpha); a[NEP_SNAP_L_N_BEND] = arr(F.ent_lists.n_bend); a[NEP_SNAP_L_ID] = arr(F.ent_lists.id);
+  a[NEP_SNAP_L_CS] = arr(F.ent_lists.cs); a[NEP_SNAP_L_BETA] = arr(F.ent_lists.beta); a[NEP_SNAP_L_BEND] = arr(F.ent_lists.bend); a[NEP_SNAP_HELD] = arr(F.ent_held);
+  a[NEP_SNAP_PUB_N] = arr(F.pub_n); a[NEP_SNAP_PUB_XY] = arr(F.pub_xy); a[NEP_SNAP_PUB_PREV_N] = arr(F.pub_prev_n); a[NEP_SNAP_PUB_PREV_XY] = arr(F.pub_prev_xy);
+  a[NEP_SNAP_ENT_FLAGS] = arr(F.ent_flags); a[NEP_SNAP_ENT_EVER] = arr(F.ent_ever); a[NEP_SNAP_ENT_WALKED] = arr(F.ent_walked);
+  a[NEP_SNAP_T_ISSUE] = arr(F.mis_t_issue); a[NEP_SNAP_LENGTH] = arr(F.mis_length); a[NEP_SNAP_COMPLETED] = arr(F.mis_completed); a[NEP_SNAP_COUNTS] = arr(F.mis_counts);
+  a[NEP_SNAP_SUMS] = arr(F.mis_sums); a[NEP_SNAP_SCENE_I] = arr(F.mis_scene); a[NEP_SNAP_T_RUN] = arr(F.mis_t_run); a[NEP_SNAP_LOG] = arr(F.mis_log); a[NEP_SNAP_LOG_N] = arr(F.mis_log_n);
+  ra = RecorderArgs{};
+  ra.hdr = hd; ra.src_scene = -1; ra.dst_scene = -1; ra.round = F.round.p; ra.origin = F.origin.p;
+  for (int i = 0; i < NEP_SNAPSHOT_N_SECTIONS; i++) {
+    if (bytes[i] > (int64_t)0x7fffffff) return fail(NEP_E_CAP, "a scene's part of a fleet array is 2 GiB or more: the recorder copies up to 2 GiB per scene and section");
+    // (a list buffer that was allocated for a larger capacity than the handle's has another stride: init allocates exactly, so this holds)
+    if (bytes[i] && (!a[i].p || a[i].have < (size_t)bytes[i] * (size_t)h->cfg.n_scenes)) return fail(NEP_E_STATE, "the recorder's layout does not fit the handle's fleet arrays");
+    ra.sec[i].p = (char*)a[i].p; ra.sec[i].off = (long)off[i]; ra.sec[i].bytes = (unsigned)bytes[i];
+  }
+  return 0;
+}
+int recorder_guard(const nep_batch_t* h) { return fleet_guard(const_cast<nep_batch_t*>(h), true); }
+}  // namespace
+
+int64_t nep_batch_fleet_snapshot_bytes(const nep_batch_t* h) {
+  if (int e = recorder_guard(h)) return e;
+  const nep_fleet_snapshot_hdr hd = recorder_header(h);
+  return NEP_SNAPSHOT_HDR_BYTES + (int64_t)hd.n_scenes * hd.scene_bytes;
+}
+
+int64_t nep_batch_fleet_snapshot_ring_bytes(const nep_batch_t* h, int32_t n_entries) {
+  if (int e = recorder_guard(h)) return e;
+  if (n_entries < 1) return fail(NEP_E_ARG, "a ring has at least one entry");
+  return nep_recorder::ring_bytes(recorder_header(h), n_entries);
+}
+
+int nep_batch_fleet_snapshot_ring(nep_batch_t* h, void* d_ring, int32_t n_entries, void* stream) {
+  if (int e = fleet_guard(h, true)) return e;
+  if (!d_ring || n_entries < 1 || ((uintptr_t)d_ring & 15)) return fail(NEP_E_ARG, "the ring is device memory on a 16-byte boundary and has at least one entry");
+  if (h->fleet.ent_ready && h->fleet.ent_cap && h->fleet.ent_lists.cap != h->fleet.ent_cap) return fail(NEP_E_STATE, "the handle's tether lists were allocated for another capacity: the recorder needs a handle whose list form was initialised once");
+  RecorderArgs ra;
+  if (int e = recorder_args(h, recorder_header(h), ra)) return e;
+  ra.n_entries = n_entries; ra.blob = (char*)d_ring;
+  h->fleet.saw(stream);
+  launch_fleet_snapshot(ra, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int nep_batch_fleet_snapshot(nep_batch_t* h, void* d_blob, void* stream) {
+  if (int e = fleet_guard(h, true)) return e;
+  if (!d_blob || ((uintptr_t)d_blob & 15)) return fail(NEP_E_ARG, "the blob is device memory on a 16-byte boundary");
+  if (h->fleet.ent_ready && h->fleet.ent_cap && h->fleet.ent_lists.cap != h->fleet.ent_cap) return fail(NEP_E_STATE, "the handle's tether lists were allocated for another capacity: the recorder needs a handle whose list form was initialised once");
+  RecorderArgs ra;
+  if (int e = recorder_args(h, recorder_header(h), ra)) return e;
+  ra.n_entries = 0; ra.blob = (char*)d_blob;
+  h->fleet.saw(stream);
+  launch_fleet_snapshot(ra, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int nep_batch_fleet_restore(nep_batch_t* h, const void* blob, int64_t bytes, int32_t src_scene, int32_t dst_scene) {
+  if (int e = fleet_guard(h, true)) return e;
+  for (hipStream_t st : h->fleet.seen) {      // a blocking call: not while a stream this handle's fleet calls run on is capturing
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return fail(NEP_E_STATE, "nep_batch_fleet_restore blocks: not while a stream of the handle's fleet calls is capturing");
+  }
+  (void)hipGetLastError();
+  if (!blob || bytes < (int64_t)NEP_SNAPSHOT_HDR_BYTES) return fail(NEP_E_ARG, "a blob is at least a snapshot header");
+  if ((src_scene < 0) != (dst_scene < 0) || src_scene < -1 || dst_scene < -1) return fail(NEP_E_ARG, "src_scene and dst_scene: both -1 (all scenes) or both a scene");
+  nep_fleet_snapshot_hdr hb;
+  HIPCHK(hipMemcpy(&hb, blob, sizeof(hb), hipMemcpyDefault));
+  const char* why = nullptr;
+  if (nep_recorder::check_header(hb, &why)) return fail(NEP_E_ARG, why);
+  if ((bytes - NEP_SNAPSHOT_HDR_BYTES) / hb.scene_bytes < hb.n_scenes) return fail(NEP_E_ARG, "fewer bytes than the header and its scene blocks");
+  const nep_fleet_snapshot_hdr hh = recorder_header(h);
+  if (hb.N != hh.N || hb.num_pol != hh.num_pol || hb.ring_cap != hh.ring_cap || hb.max_states != hh.max_states || hb.timers != hh.timers)
+    return fail(NEP_E_ARG, "the snapshot is of another fleet (agents, num_pol, ring_cap, max_states or timers differ from the handle's)");
+  if (hb.tether_form != hh.tether_form || hb.tether_cap != hh.tether_cap) return fail(NEP_E_ARG, "the snapshot's tether state has another form or capacity than the handle's (run the same tether init first)");
+  if (hb.mission_mode != hh.mission_mode || hb.log_cap != hh.log_cap) return fail(NEP_E_ARG, "the snapshot's mission state has another mode or log_cap than the handle's (run nep_batch_fleet_mission_init first)");
+  if (hb.scene_bytes != hh.scene_bytes) return fail(NEP_E_ARG, "the snapshot's scene blocks have another size than the handle's state");
+  if (hb.cfg_hash != hh.cfg_hash) return fail(NEP_E_ARG, "the snapshot was taken under another configuration (nep_fleet_cfg, cable length or nep_mission_cfg)");
+  if (src_scene < 0 ? hb.n_scenes != hh.n_scenes : (src_scene >= hb.n_scenes || dst_scene >= hh.n_scenes)) return fail(NEP_E_ARG, "scene out of range (all scenes: the scene counts must be equal)");
+  if (h->fleet.ent_ready && h->fleet.ent_cap && h->fleet.ent_lists.cap != h->fleet.ent_cap) return fail(NEP_E_STATE, "the handle's tether lists were allocated for another capacity: the recorder needs a handle whose list form was initialised once");
+  nep_batch::Fleet& F = h->fleet;
+  // the blocks on their way in: one block or all of them, behind a header, in a buffer of the handle's (16-byte aligned)
+  const size_t n_blocks = src_scene < 0 ? (size_t)hb.n_scenes : 1, first = src_scene < 0 ? 0 : (size_t)src_scene;
+  RecorderArgs ra;
+  if (int e = recorder_args(h, hh, ra)) return e;
+  HIPCHK(hipDeviceSynchronize());      // (kernels in flight may still read or write the state)
+  if (int e = F.rec_stage.ensure(NEP_SNAPSHOT_HDR_BYTES + n_blocks * (size_t)hb.scene_bytes)) return e;
+  HIPCHK(hipMemcpy(F.rec_stage.p + NEP_SNAPSHOT_HDR_BYTES, (const char*)blob + NEP_SNAPSHOT_HDR_BYTES + first * (size_t)hb.scene_bytes, n_blocks * (size_t)hb.scene_bytes, hipMemcpyDefault));
+  ra.hdr = hb; ra.blob = F.rec_stage.p;
+  if (src_scene >= 0) { ra.src_scene = 0; ra.dst_scene = dst_scene; ra.hdr.n_scenes = 1; }
+  launch_fleet_restore(ra, nullptr);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+  return 0;
 }
 
 int nep_batch_fleet_commit(nep_batch_t* h, const nep_solution* d_solution, const double* d_states, const nep_fe_result* d_fe_result,
@@ -2348,6 +2479,7 @@ int nep_abi_sizeof(int32_t which) {
     case 20: return (int)sizeof(nep_mission_cfg);      // (19 stays unassigned: tests/test_fleet_plan_cpu.py pins it to -1)
     case 21: return (int)sizeof(nep_mission_leg);
     case 23: return (int)sizeof(nep_ent_lists);      // (22 stays unassigned: tests/test_fleet_mission_cpu.py pins it to -1)
+    case 25: return (int)sizeof(nep_fleet_snapshot_hdr);      // (24 stays unassigned: tests/test_ent_lists_cpu.py pins it to -1)
     default: return -1;
   }
 }

@@ -41,7 +41,7 @@ __global__ void fleet_seed_kernel(FleetArgs fa, const double* __restrict__ state
   for (int i = 0; i < kPwpDoubles; i++) w[i] = 0.0;
   if (slot % fa.N == 0) {
     const long scene = slot / fa.N;
-    fa.t_now[scene] = fa.cfg.t0; fa.round[scene] = 0;
+    fa.t_now[scene] = fa.cfg.t0; fa.round[scene] = 0; fa.origin[scene] = (int)scene;
     for (int i = 0; i < NEP_FLEET_N_COUNTERS; i++) fa.counters[scene * NEP_FLEET_N_COUNTERS + i] = 0;
   }
 }

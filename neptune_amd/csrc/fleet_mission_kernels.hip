@@ -67,6 +67,8 @@ __global__ __launch_bounds__(64) void fleet_mission_kernel(FleetMissionArgs ma, 
   for (int i = lane; i < 2 * n_vert; i += 64) s_kxy[i] = ma.kxy[(long)scene * NEP_MISSION_MAX_VERT * 2 + i];
   for (int i = lane; i <= n_poly; i += 64) s_off[i] = g_off[i];
   const long base = (long)scene * N;
+  const int origin = fa.origin[scene];                 // the scene's index in the flight it comes from: the generator's global slot and the log's `who`
+  const long gbase = (long)origin * N;
   const double t_end = mission_t_end(fa.t_now[scene], fa.cfg.dc, T);
   const bool per_agent = c.mode == NEP_MISSION_PER_AGENT;
   // ---- the ticks and the triggers: lanes stride over the agents ----------------------------------------------------------------
@@ -117,10 +119,10 @@ __global__ __launch_bounds__(64) void fleet_mission_kernel(FleetMissionArgs ma, 
         const bool draws = mission_agent_draws(c, ma.counts + slot * 4);
         double gx = 0.0, gy = 0.0;
         int k = -1;
-        if (draws) k = mission_draw(c, lane, mission_h1(c.seed, (uint64_t)slot, (uint64_t)ma.counts[slot * 4 + kIssued]), a, N, s_end, pb, n_poly, s_off, s_kxy, s_new, s_got, gx, gy);
+        if (draws) k = mission_draw(c, lane, mission_h1(c.seed, (uint64_t)(gbase + a), (uint64_t)ma.counts[slot * 4 + kIssued]), a, N, s_end, pb, n_poly, s_off, s_kxy, s_new, s_got, gx, gy);
         __syncthreads();      // (every lane has read the slot's counts and the LDS lists before the owner changes them)
         if (lane == (a & 63)) {
-          const bool none = mission_end_leg(c, mission_slot(ma, fa, slot), ma.log + slot * c.log_cap, ma.log_n + slot, (int)slot, outcome, t_end, draws, k, gx, gy);
+          const bool none = mission_end_leg(c, mission_slot(ma, fa, slot), ma.log + slot * c.log_cap, ma.log_n + slot, (int)(gbase + a), outcome, t_end, draws, k, gx, gy);
           if (none) atomicOr(fa.gflags, NEP_FLAG_MISSION);
           s_got[a] = draws && k >= 0 ? kGotNew : kNoNew;
           if (draws && k >= 0) { s_new[3 * a] = gx; s_new[3 * a + 1] = gy; s_new[3 * a + 2] = c.goal_z; }
@@ -145,7 +147,7 @@ __global__ __launch_bounds__(64) void fleet_mission_kernel(FleetMissionArgs ma, 
     double gx = 0.0, gy = 0.0;
     int k = -1;
     if (draws) {
-      k = mission_draw(c, lane, mission_h1(c.seed, (uint64_t)slot, (uint64_t)ma.counts[slot * 4 + kIssued]), a, N, s_end, pb, n_poly, s_off, s_kxy, s_new, s_got, gx, gy);
+      k = mission_draw(c, lane, mission_h1(c.seed, (uint64_t)(gbase + a), (uint64_t)ma.counts[slot * 4 + kIssued]), a, N, s_end, pb, n_poly, s_off, s_kxy, s_new, s_got, gx, gy);
       attempts += k >= 0 ? k + 1 : c.max_attempts;
     }
     __syncthreads();
@@ -156,7 +158,7 @@ __global__ __launch_bounds__(64) void fleet_mission_kernel(FleetMissionArgs ma, 
     }
     __syncthreads();
   }
-  if (lane == 0) mission_end_run(c, scene_i, ma.t_run + scene, ma.log + (long)scene * c.log_cap, ma.log_n + scene, scene, all_completed, t_end, sum, N, attempts);
+  if (lane == 0) mission_end_run(c, scene_i, ma.t_run + scene, ma.log + (long)scene * c.log_cap, ma.log_n + scene, origin, all_completed, t_end, sum, N, attempts);
 }
 
 // the first leg of every slot: nep_batch_fleet_mission_init

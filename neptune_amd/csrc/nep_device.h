@@ -267,6 +267,7 @@ struct FleetArgs {
   int* flown; int* done; int* outcome; int* sflags;      // [slots]
   const int* period; const int* phase;   // [slots] or both null
   double* t_now; int* round;     // [scenes]
+  int* origin;                   // [scenes] the scene's index in the flight it comes from (its own, until a restore says otherwise): the mission generator's global slot
   int* counters;                 // [scenes][NEP_FLEET_N_COUNTERS]
   int* gflags;                   // sticky NEP_FLAG_FLEET
   // select
@@ -297,6 +298,20 @@ struct FleetMissionArgs {
 size_t mission_lds_bytes(int N, int n_vert, int n_poly);
 void launch_fleet_mission_seed(const FleetMissionArgs& ma, const FleetArgs& fa, hipStream_t st);
 void launch_fleet_mission(const FleetMissionArgs& ma, const FleetArgs& fa, hipStream_t st);
+// the fleet recorder (fleet_recorder_kernels.hip): nep_batch_fleet_snapshot / _snapshot_ring / _restore.  Section i of a scene block
+// (recorder_common.h) is the scene's part — `bytes` bytes — of the handle's array `p`, at `off` in the block.  All device pointers.
+struct RecorderSection { char* p; long off; unsigned bytes; unsigned pad_; };
+struct RecorderArgs {
+  nep_fleet_snapshot_hdr hdr;    // what the snapshot kernel writes in front (hdr.n_scenes: the handle's)
+  int n_entries;                 // 0: a plain blob; > 0: a ring, scene s goes to entry round[s] mod n_entries
+  int src_scene, dst_scene;      // restore: block src_scene of the blob into scene dst_scene (-1, -1: every scene into its own)
+  int parts;                     // workgroups that share a scene
+  const int* round; const int* origin;      // [scenes] the handle's (the ring's entry and stamp)
+  char* blob;                    // the blob or ring (16-byte aligned)
+  RecorderSection sec[NEP_SNAPSHOT_N_SECTIONS];
+};
+void launch_fleet_snapshot(const RecorderArgs& ra, hipStream_t st);
+void launch_fleet_restore(const RecorderArgs& ra, hipStream_t st);
 // the tethers' entangle states (tether_kernels.hip): nep_batch_track_ent between two rounds; on the fleet state nep_batch_fleet_select's
 // bend points, _predict_ent, _track_ent
 struct TetherArgs {

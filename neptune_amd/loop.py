@@ -370,14 +370,24 @@ class DeviceFleetLoop(_Audited):
     tracking) and fleet_tick, ends legs (mode "agent": NeptuneRos::autoCMD) or runs (mode "runs": benchmark_mtlp.py) and draws
     the next goals on the device, inside the graph.  run() then stops when every scene's campaign is finished (it downloads the
     scenes' flags instead of the slots' arrival flags), and report() adds `mission` per scene: legs or runs reached / timed out /
-    without a goal, mean leg time and length, the success rate.  Without missions nothing of this is allocated or launched."""
+    without a goal, mean leg time and length, the success rate.  Without missions nothing of this is allocated or launched.
+
+    recorder=R keeps the complete fleet state before each of the last R rounds in a device ring: fleet_snapshot_ring
+    is the first call of the round, inside the graph, and entry r mod R holds the state before round r.  rewind(scene, round)
+    then gives a one-scene eager loop with tracing on, restored to the state before that round; save_checkpoint(path) and
+    resume(path, scenes) carry a flight over the end of the process.  With recorder=None nothing is allocated or launched."""
+
+    # the options a restored flight must share with the flight the snapshot was taken from
+    _MUST_MATCH = ("beam_width", "delta_t_states", "replan_every", "audit", "ring_cap", "tethers", "check", "ent_samples", "ent_cap")
 
     def __init__(self, scenes, beam_width=32, delta_t_states=6, replan_every=5, periods=None, phases=None, audit=False, graph=True,
                  goals=None, device=None, ring_cap=0, trace=False, tethers=False, check=True, ent_samples=3, missions=None, ent_cap=None,
-                 ent_lists0=None):
+                 ent_lists0=None, recorder=None):
         import torch
         self.torch = torch
         self.scenes = scenes
+        self._opts = dict(beam_width=beam_width, delta_t_states=delta_t_states, replan_every=replan_every, audit=audit, ring_cap=ring_cap,
+                          tethers=tethers, check=check, ent_samples=ent_samples, ent_cap=ent_cap, missions=missions, goals=goals)
         S = self.S = len(scenes)
         p = self.p = scenes[0]["par"]
         self.tethers, self.check, self.ent_samples = tethers, check, ent_samples
@@ -448,7 +458,12 @@ class DeviceFleetLoop(_Audited):
                 for s, sc in enumerate(scenes):
                     be.fleet_mission_keepout(s, scene.keepout_polygons(sc))
             be.fleet_mission_init(self.mission_cfg)
+        self.recorder, self.d_ring = None, None
+        if recorder is not None:      # (allocated here, outside any capture, for the state the handle has now: tethers and missions included)
+            self.recorder = int(recorder)
+            self.d_ring = be.new_snapshot_ring(self.recorder)
         self.rounds = 0
+        self._flown = 0               # rounds this object has flown (rounds: the flight's, which a restore sets)
         self._g = None
         self.trace = [] if trace else None
         self.after_commit = None      # test hook: called between fleet_commit and fleet_tick of an eager round
@@ -458,6 +473,8 @@ class DeviceFleetLoop(_Audited):
 
     def _round_ops(self):
         be = self.be
+        if self.d_ring is not None:      # the state before this round -> entry round mod R
+            be.fleet_snapshot_ring(self.d_ring, self.recorder)
         be.fleet_select(self.d_start, self.d_rec, self.d_active, self.d_clock if self.d_audit is not None else None)
         if self.tethers:
             if self.d_hold is not None:
@@ -483,7 +500,8 @@ class DeviceFleetLoop(_Audited):
     def round(self):
         """one bulk-synchronous round of every scene; True when every agent of every scene has arrived"""
         hooked = self.after_commit is not None or self.after_select is not None or self.after_mission is not None
-        run_round_ops(self, not self.graph or self.rounds < 1 or hooked)
+        run_round_ops(self, not self.graph or self._flown < 1 or hooked)      # (_flown, not rounds: a restored loop's first round allocates too)
+        self._flown += 1
         if self.trace is not None:
             oc = self.d_outcome.cpu().numpy()
             sol = self.be.solutions(); fres = self.d_res.cpu().numpy().view(abi.FE_RESULT_DTYPE)
@@ -548,8 +566,99 @@ class DeviceFleetLoop(_Audited):
             out.append(d)
         return out
 
+    # ---- the recorder ---------------------------------------------------------------------------------------
+    def _options(self):
+        """the options a snapshot's flight and the flight restored from it must share, as plain data"""
+        import dataclasses
+        o = {k: self._opts[k] for k in self._MUST_MATCH}
+        o["ent_cap"] = self.ent_cap
+        o["missions"] = dataclasses.asdict(self.missions) if self.missions is not None else None
+        o["masked"] = bool(self.masked)
+        o["N"], o["n_statics"] = int(self.N), len(self.scenes[0]["statics"])
+        return o
+
+    def _twin(self, scenes, rows, **kw):
+        """a loop with this one's options over `scenes` (this loop's scenes `rows`)"""
+        o = dict(self._opts)
+        o["ent_cap"] = self.ent_cap
+        if o["goals"] is not None:
+            o["goals"] = [o["goals"][s] for s in rows]
+        if self.masked:
+            o.update(periods=self.periods[rows], phases=self.phases[rows])
+        o.update(kw)
+        return DeviceFleetLoop(scenes, device=self.be.device, **o)
+
+    def rewind(self, scene, round):
+        """a new DeviceFleetLoop over scene `scene` alone — eager, trace on, this loop's options, the scene's statics and keep-outs —
+        restored to the state before round `round` from the recorder's ring.  ValueError when the ring does not hold that round
+        (overwritten, or not flown yet)."""
+        if self.d_ring is None:
+            raise ValueError("rewind needs DeviceFleetLoop(recorder=R)")
+        if not 0 <= scene < self.S:
+            raise ValueError("scene out of range")
+        self.torch.cuda.synchronize(self.be.device)
+        e = round % self.recorder
+        st = self.be.snapshot_ring_stamps(self.d_ring, self.recorder)[e, scene]
+        if round < 0 or not st["used"] or int(st["round"]) != round:
+            held = sorted(int(x["round"]) for x in self.be.snapshot_ring_stamps(self.d_ring, self.recorder)[:, scene] if x["used"])
+            raise ValueError("the recorder does not hold the state before round %d of scene %d (it holds rounds %s)" % (round, scene, held))
+        lp = self._twin([self.scenes[scene]], [scene], graph=False, trace=True)
+        try:
+            lp.be.fleet_restore(self.be.snapshot_ring_entry(self.d_ring, self.recorder, e), scene, 0)
+        except Exception:
+            lp.close()
+            raise
+        lp.rounds = round
+        return lp
+
+    def save_checkpoint(self, path):
+        """the flight as it stands into one .npz: the snapshot, the audit buffer when auditing, the loop's round count and the
+        options a resumed flight must share"""
+        import json
+        blob = self.be.fleet_snapshot()
+        self.torch.cuda.synchronize(self.be.device)
+        data = dict(blob=blob.cpu().numpy(), rounds=np.int64(self.rounds), options=np.array(json.dumps(self._options())))
+        if self.d_audit is not None:
+            data["audit"] = self.d_audit.cpu().numpy()
+        with open(path, "wb") as f:
+            np.savez(f, **data)
+
+    @classmethod
+    def resume(cls, path, scenes, **kw):
+        """the flight of save_checkpoint(path) over the same `scenes`, continued: a loop built with the file's options (kw: graph,
+        trace, recorder, device; periods / phases / goals as the first flight got them) and restored.  ValueError for a file whose
+        options differ from kw's or from the scenes."""
+        import json
+        from . import mission
+        with np.load(path, allow_pickle=False) as z:
+            blob, rounds, opts = z["blob"], int(z["rounds"]), json.loads(str(z["options"]))
+            aud = z["audit"] if "audit" in z.files else None
+        for k in cls._MUST_MATCH:
+            if k in kw and kw[k] != opts[k] and not (k == "ent_cap" and kw[k] == "auto"):
+                raise ValueError("checkpoint %s was flown with %s=%r, not %r" % (path, k, opts[k], kw[k]))
+        if "missions" in kw and (None if kw["missions"] is None else __import__("dataclasses").asdict(kw["missions"])) != opts["missions"]:
+            raise ValueError("checkpoint %s was flown with other missions" % path)
+        if scenes[0]["par"].num_agents != opts["N"] or len(scenes[0]["statics"]) != opts["n_statics"]:
+            raise ValueError("checkpoint %s was flown with %d agents and %d statics per scene" % (path, opts["N"], opts["n_statics"]))
+        if opts["masked"] != ("periods" in kw or "phases" in kw):
+            raise ValueError("checkpoint %s was flown %s periods / phases" % (path, "with" if opts["masked"] else "without"))
+        o = {k: opts[k] for k in cls._MUST_MATCH}
+        o["missions"] = mission.MissionSpec(**opts["missions"]) if opts["missions"] is not None else None
+        o.update({k: v for k, v in kw.items() if k not in o})
+        lp = cls(scenes, **o)
+        try:
+            lp.be.fleet_restore(blob)      # (refuses another scene count, another configuration, another state)
+            if aud is not None:
+                lp.d_audit.copy_(lp.torch.from_numpy(aud))
+        except Exception:
+            lp.close()
+            raise
+        lp.rounds = rounds
+        return lp
+
     def close(self):
         self._g = None
+        self.d_ring = None
         self.be.close()
 
 

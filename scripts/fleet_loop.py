@@ -10,6 +10,12 @@ stats), the totals, the wall time per round and, with --audit, the worst clearan
 --missions {agent,runs} --goals G: fleet_mission joins the round before fleet_tick and flies a campaign of G goals per agent (runs per
 scene); the report gains the legs' accounts.
 
+--record R keeps the fleet state before each of the last R rounds in a device ring, written inside the graph.
+--rewind SCENE:ROUND flies the recorded flight for ROUND + 1 rounds, takes that scene alone back to the state before ROUND, flies the
+one round eagerly with tracing on and prints every agent's outcome, K and statuses next to what the batch's round gave.  With --audit
+the summary names the --rewind argument of the round in which the worst box clearance was flown.  --save PATH writes a checkpoint
+when the flight stops (at --rounds); --resume PATH continues one, up to --rounds rounds of the whole flight.
+
 --stagger P: every agent replans every P-th round, agent a in the rounds with (round - a) mod P == 0, and a round flies one control
 tick (FleetLoop's cadence at P = 5 with the agents' timers spread over the ticks).  --host flies scene 0 with FleetLoop as well and
 prints its wall time per round next to the device loop's (one scene each)."""
@@ -40,11 +46,15 @@ def main():
     ap.add_argument("--fe-big-records", type=int, default=0, metavar="R", help="with --tethers: records in the front end's pool of big entangle-state records (nep_batch_set_fe_ent_big_records; 0: the default, 4 per slot)")
     ap.add_argument("--missions", choices=("agent", "runs"), help="a campaign (DESIGN section 23): per-agent successive goals (NeptuneRos::autoCMD) or fleet-wide runs (benchmark_mtlp.py), drawn on the device inside the graph; the flight stops when every scene's campaign is over")
     ap.add_argument("--goals", type=int, default=2, metavar="G", help="with --missions: legs per agent / runs per scene")
+    ap.add_argument("--record", type=int, default=0, metavar="R", help="flight recorder: the state before each of the last R rounds in a device ring, inside the graph")
+    ap.add_argument("--rewind", metavar="SCENE:ROUND", help="fly ROUND + 1 rounds recorded (default --record 8), then that scene alone from the state before ROUND: one eager round, traced")
+    ap.add_argument("--save", metavar="PATH", help="write a checkpoint (.npz) when the flight stops")
+    ap.add_argument("--resume", metavar="PATH", help="continue the flight of a checkpoint up to --rounds rounds in all")
     ap.add_argument("--host", action="store_true", help="also fly scene 0 with FleetLoop and with DeviceFleetLoop(S = 1): wall time per round of both")
     a = ap.parse_args()
     import numpy as np
     import torch
-    from neptune_amd import audit, scene
+    from neptune_amd import abi, audit, scene
     from neptune_amd._lib import BackendError
     from neptune_amd.loop import DeviceFleetLoop, FleetLoop
     seeds = [a.seed0 + k for k in range(a.scenes)]
@@ -60,22 +70,52 @@ def main():
     if a.stagger > 0:
         kw.update(replan_every=1, periods=a.stagger, phases=np.tile(np.arange(a.agents) % a.stagger, (a.scenes, 1)))
 
-    def fly(scs, rounds):
-        lp = DeviceFleetLoop(scs, **kw)
+    if a.record or a.rewind:
+        kw.update(recorder=a.record if a.record else 8)
+
+    def make(scs, resume=None):
+        lp = DeviceFleetLoop.resume(resume, scs, **kw) if resume else DeviceFleetLoop(scs, **kw)
         if a.tethers and a.no_proof:
             lp.be.debug_option("fleet_ent_proof", 0)
         if a.tethers and a.fe_big_records:
             lp.be.set_fe_ent_big_records(a.fe_big_records)
-        lp.round(); lp.round()      # the eager round and the capture
+        return lp
+
+    if a.rewind:
+        sc_i, rnd = (int(x) for x in a.rewind.split(":"))
+        lp = make(scenes)
+        for _ in range(rnd + 1):
+            lp.round()
+        N = lp.N
+        sol = lp.be.solutions()[sc_i * N:(sc_i + 1) * N]
+        fres = lp.d_res.cpu().numpy().view(abi.FE_RESULT_DTYPE)[sc_i * N:(sc_i + 1) * N]
+        batch = [(int(o), int(q["K"]), int(f["status"]), int(q["stats"]["status"])) for o, q, f in zip(lp.d_outcome.cpu().numpy()[sc_i * N:(sc_i + 1) * N], sol, fres)]
+        one = lp.rewind(sc_i, rnd)
+        one.round()
+        print("scene %d (seed %d), round %d, flown alone from the recorder's ring (agent: outcome, K, front-end status, QP status):" % (sc_i, seeds[sc_i], rnd))
+        for i, (got, want) in enumerate(zip(one.trace[0], batch)):
+            print("  agent %2d: %-18s K %d  fe %d  qp %d   %s" % (i + 1, abi.FLEET_OUTCOMES[got[0]], got[1], got[2], got[3], "= the batch's round" if got == want else "the batch's round gave %s" % (want,)))
+        print("the round %s" % ("reproduces the batch's outcomes" if list(one.trace[0]) == batch else "DIFFERS from the batch's"))
+        one.close(); lp.close()
+        return
+
+    def fly(scs, rounds, resume=None):
+        lp = make(scs, resume)
+        for _ in range(2):      # the eager round and the capture
+            if lp.rounds < rounds:
+                lp.round()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         n = 0
-        for _ in range(rounds - 2):
+        while lp.rounds < rounds:
             n += 1
             if lp.round():
                 break
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        if a.save and scs is scenes:
+            lp.save_checkpoint(a.save)
+            print("checkpoint after round %d: %s" % (lp.rounds, a.save))
         try:
             rep = lp.report()
         except BackendError as e:      # (a capacity other than the tracking's: said, not hidden — the read has cleared the sticky flags)
@@ -84,11 +124,12 @@ def main():
         if a.tethers:
             w = lp.be.fleet_ent_state(states=False)["walked"]
             print("tether tracking: %d of %d (other agent, tick) pairs walked, the rest proven free of crossings"
-                  % (int(w.sum()), len(scs) * lp.N * (lp.N - 1) * lp.replan_every * (n + 2)))
+                  % (int(w.sum()), len(scs) * lp.N * (lp.N - 1) * lp.replan_every * lp.rounds))
+        flown = lp.rounds
         lp.close()
-        return rep, dt / max(n, 1), n + 2
+        return rep, dt / max(n, 1), flown
 
-    rep, per_round, n = fly(scenes, a.rounds)
+    rep, per_round, n = fly(scenes, a.rounds, a.resume)
     for s, r in enumerate(rep):
         print("scene %d (seed %d): %s" % (s, seeds[s], json.dumps({k: v for k, v in r.items() if k != "audit"})))
     tot = {k: int(sum(r[k] for r in rep)) for k in ("replans", "accepted", "fe_no_solution", "qp_failed", "qp_relaxed", "rejected_by_safety", "cap", "skipped", "reached")}
@@ -110,6 +151,12 @@ def main():
             print(line)
         worst = min(r["audit"]["min_box_clear"]["value"] for r in rep if r["audit"]["min_box_clear"])
         print("scenes with min_box_clear < 0: %d of %d; worst %.9f m" % (sum(1 for r in rep if r["audit"]["min_box_clear"] and r["audit"]["min_box_clear"]["value"] < 0), len(rep), worst))
+        # the round that flew the worst box clearance: the audit's ticks of round r are t0 + (r T + 1 .. r T + T) dc
+        s_w, m_w = min(((s, r["audit"]["min_box_clear"]) for s, r in enumerate(rep) if r["audit"]["min_box_clear"]), key=lambda x: x[1]["value"])
+        par = scenes[0]["par"]
+        ticks = kw.get("replan_every", 5)
+        print("to look at that round (scene %d, agent %d, partner %d, t %.3f s): --rewind %d:%d"
+              % (s_w, m_w["agent"], m_w["partner"], m_w["t"], s_w, (int(round(m_w["t"] / par.dc)) - 1) // ticks))
     if a.host:
         sc = scenes[0]
         _, dev1, n1 = fly([sc], a.rounds)
