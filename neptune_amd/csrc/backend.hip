@@ -142,7 +142,7 @@ struct Engine {
   DevBuf<int> d_hull_nv, d_hull0_nv, d_bend_n, d_line_cnt, d_line_far, d_lp_stats;
   DevBuf<int> d_presolved; bool presolve_kernel = true, presolve_fused = true;      // the zero-iteration certificate's marks (one per slot); debug option "presolve_kernel" = 0: the test runs inside qp_reg_kernel<true> as in rounds 3-5; "presolve_fused" = 0: always as qp_presolve_kernel, never in the separator's wave
   DevBuf<int> d_line_skip, d_redo_list, d_redo_count;   // spatial presolve: skipped LPs per segment, replans listed for the redo pass
-  DevBuf<double> d_polish_z; DevBuf<int> d_polish_flag, d_polish_list, d_polish_count; bool polish = true, polish_presolve = true, last_polish_armed = false;      // the active-set polish of solves that end without the strict tests (qp_polish_kernel.hip; nep_*_set_polish)
+  DevBuf<double> d_polish_z; DevBuf<int> d_polish_flag, d_polish_list, d_polish_count; bool polish = true, polish_presolve = true;      // the active-set polish of solves that end without the strict tests (qp_polish_kernel.hip; nep_*_set_polish)
   DevBuf<long long> d_dbg; bool profile_phases = false;
   DevBuf<int> d_flags;
   // entangle-aware front end / safety re-check (nep_batch_frontend_ent, nep_batch_safety_commit_ent)
@@ -157,7 +157,7 @@ struct Engine {
   int lds_lines = 0, lds_rows = 0, rows_cap = 0; size_t lds_bytes = 0;
   DevBuf<double> d_fe_box;          // boxes of the front end's obstacles, made before every search launch
   DevBuf<int> d_fe_order, d_fe_order_key; DevBuf<float> d_fe_us; bool fe_history = false, fe_lpt = true;      // the same for the front end's searches (frontend_kernel)
-  DevBuf<int> d_order, d_order_key; bool have_history = false, lpt = true, last_ordered = false;   // QP workgroups launched longest-expected-first (order_kernel)
+  DevBuf<int> d_order, d_order_key; bool have_history = false, lpt = true;   // QP workgroups launched longest-expected-first (order_kernel)
   const int* active = nullptr;       // the active set (nep_batch_set_active): device [scenes][N], or null
   DevBuf<int> d_act, d_fe_act;       // [slots + 1] compacted active slots + count (active_list_kernel): the QP launches', the front end's
   ListBuf d_track_lsave;      // nep_batch_track_ent_lists: the same scratch in the list form, of the largest cap seen
@@ -201,7 +201,7 @@ struct Engine {
   static constexpr double kAutoCullRadius = 4.0;
   bool fits_reg = true, cull_user_set = false, skip_lps = true, no_redo = false; int lds_lines_lds = 0, sep_pack = 0, force_kernel = 0, opt_qp_key_decay = 2, opt_fe_key_decay = 1, opt_corr_from = kCorrFromItDefault, opt_corr_max = kCorrMaxCountDefault, opt_fleet_ent_proof = 1;      // (skip_lps, no_redo, sep_pack, force_kernel: development aids behind nep_*_debug_set_option, include/neptune_backend_debug.h)
   // Row scratch (rows and coefficients beyond the register slots / the LDS carve): one area per slot in general.  With the presolve's
-  // redo pass (skip_mode()) the first pass never needs one — a replan whose near lines exceed the slots is sent to the redo pass —
+  // redo pass (skip_mode(), launch_plan.h) the first pass never needs one — a replan whose near lines exceed the slots is sent to the redo pass —
   // so the handle keeps a pool of kScratchPool areas for that pass (config 5: 1.9 GB instead of 15.3 per 32 scenes);
   // nep_batch_reserve_row_scratch asks for the worst case.
   static constexpr int kScratchPool = 1024;
@@ -243,16 +243,24 @@ struct Engine {
     box_buf = d_fe_box.p; box_N = N; box_S = S; box_np = np; static_boxes_ok = true;
     return 0;
   }
-  int last_path = 0;           // NEP_PATH_* bits: what the last run() launched (nep_batch_debug_launch_path)
+  ReplanPlan last_plan;        // what the last run() launched (launch_plan.h; the nep_batch_debug_launch_* and _polish_* calls read it)
   int lines_cap_user = 0;      // 0: the default budget; -1: the reference's worst case; n > 0: n lines per segment (nep_batch_set_line_capacity)
-  // LPs whose line is known to be far without solving them may be skipped when the presolve is on, the rule is the largest gap
-  // (box far => line far holds for that vertex only), the hull lists are the batch's (one per agent: the boxes are indexed
-  // by agent) and the interior point is the register kernel (the one that verifies them): see separator_body / qp_reg_kernel
-  bool can_skip_lps() const { return sp.cull_radius > 0.0 && use_reg && sp.sep_rule == 0 && sp.skip_own == 1 && sp.n_hull == sp.num_agents && skip_lps && statics_boxy; }
-  bool skip_mode() const { return can_skip_lps() && !no_redo; }      // ... and the replans that fail the verification go through the redo pass
+  // what the launch plan reads of the handle (launch_plan.h); run() adds the call's own facts
+  ReplanFacts facts() const {
+    ReplanFacts f;
+    f.num_agents = sp.num_agents; f.num_pol = sp.num_pol; f.n_hull = sp.n_hull; f.n_static = sp.n_static; f.ent_enabled = sp.ent_enabled;
+    f.hull_mode = sp.hull_mode; f.skip_own = sp.skip_own; f.sep_rule = sp.sep_rule; f.cull_radius = sp.cull_radius;
+    f.use_reg = use_reg; f.lpt = lpt; f.have_history = have_history; f.presolve_kernel = presolve_kernel; f.presolve_fused = presolve_fused;
+    f.skip_lps = skip_lps; f.no_redo = no_redo; f.statics_boxy = statics_boxy; f.static_boxes_ok = static_boxes_ok; f.sep_pack = sep_pack;
+    f.polish = polish; f.polish_presolve = polish_presolve; f.polish_buffers = d_polish_z.p != nullptr;
+    f.n_scenes = n_scenes; f.slots = n_scenes * sp.n_local;
+    f.order_ok = d_order.n >= (size_t)f.slots; f.order_key_ok = d_order_key.n >= (size_t)f.slots; f.presolved_ok = d_presolved.n >= (size_t)f.slots;
+    f.scratch_chunks = scratch_chunks;
+    return f;
+  }
   int size_row_scratch() {
     const long slots = (long)n_scenes * sp.n_local;
-    const bool pooled = skip_mode() && !scratch_full && slots > kScratchPool;
+    const bool pooled = skip_mode(facts()) && !scratch_full && slots > kScratchPool;
     scratch_chunks = pooled ? kScratchPool : 0;
     return d_row_scratch.ensure((size_t)(pooled ? kScratchPool : slots) * (11L * (rows_cap / 4 + 2)));
   }
@@ -346,24 +354,21 @@ struct Engine {
     ps.fe_order = nullptr; ps.fe_order_key = (lpt && fe_lpt && d_fe_order_key.n >= (size_t)n_scenes * (size_t)sp.n_local) ? d_fe_order_key.p : nullptr; ps.fe_us = d_fe_us.p;
     ps.line_nd = d_line_nd.p; ps.line_cnt = d_line_cnt.p; ps.lp_stats = d_lp_stats.p;
     ps.line_far = sp.cull_radius > 0.0 ? d_line_far.p : nullptr;
-    const bool skip = can_skip_lps();
-    ps.scratch_chunks = skip_mode() ? scratch_chunks : 0; ps.scratch_by_block = 0;
+    const ReplanFacts f = facts();
+    const bool skip = can_skip_lps(f);      // (launch_plan.h, as pol below)
+    ps.scratch_chunks = skip_mode(f) ? scratch_chunks : 0; ps.scratch_by_block = 0;
     ps.skip_box = skip ? d_fe_box.p : nullptr; ps.line_skip = skip ? d_line_skip.p : nullptr;
     ps.redo_list = skip ? d_redo_list.p : nullptr; ps.redo_count = skip ? d_redo_count.p : nullptr; ps.order_count = nullptr;
     ps.sep_pack = sep_pack;
     ps.row_scratch = d_row_scratch.p; ps.rows_cap = rows_cap; ps.lds_rows = lds_rows; ps.lds_lines = lds_lines;
     ps.dbg = profile_phases ? d_dbg.p : nullptr;
-    ps.presolved = nullptr; ps.pre_tables = nullptr; ps.pre_sched_n = nullptr;      // (set by run() for a launch sequence in which the zero-iteration certificate goes first)
+    ps.presolved = nullptr; ps.pre_tables = nullptr; ps.pre_sched_n = nullptr;      // (run() gives them to the launches of a sequence in which the zero-iteration certificate goes first)
     ps.flags = d_flags.p;
     ps.fe_box = d_fe_box.p;
     ps.active = active; ps.fe_count = nullptr;
-    // the polish pass finishes what the register kernel leaves.  Under the presolve only on request (nep_batch_set_polish(h, 2): on the
-    // near lines, and a certified point goes through the presolve's verification of the parked lines and the skipped LPs again —
-    // polish_slot): a pass over a handful of slots is 0.03-0.06 ms, 8 % of a presolved step
-    const bool pol = polish && use_reg && (polish_presolve || !(sp.cull_radius > 0.0)) && d_polish_z.p != nullptr;
+    const bool pol = polish_armed(f);
     ps.polish_z = pol ? d_polish_z.p : nullptr; ps.polish_flag = pol ? d_polish_flag.p : nullptr;
     ps.polish_list = pol ? d_polish_list.p : nullptr; ps.polish_count = pol ? d_polish_count.p : nullptr;
-    last_polish_armed = pol;
   }
   // packs n polygons into the fixed-stride device layout (vertices, vertex counts, edge lengths)
   bool statics_boxy = true;      // every static polygon uploaded so far has an edge on each side of its bounding box (see pack_statics)
@@ -470,88 +475,66 @@ struct Engine {
   // separator + QP (+ hulls when recs != nullptr) on `st`
   // phases: 1 = the geometry half (hulls, boxes, separating lines into the handle's scratch), 2 = the QP half on the lines that are there,
   // 3 = both (nep_batch_replan); the halves of one round may be enqueued on different streams, ordered by the caller (nep_batch_replan_lines)
-  int run(const nep_traj_rec* d_recs, int n_rec, ProblemSet& ps, hipStream_t st, int phases = 3) {
-    const int slots = n_scenes * sp.n_local;
+  // The launch topology is plan_replan's (launch_plan.h: every condition and its reason); here the facts are copied out, the plan is
+  // followed in order, and each launch's ProblemSet is derived from the caller's (`base`, as fill() and the caller made it) and the plan.
+  int run(const nep_traj_rec* d_recs, int n_rec, const ProblemSet& base, hipStream_t st, int phases = 3) {
+    ReplanFacts f = facts();
+    f.n_rec = n_rec; f.phases = phases; f.hull_pb = base.hull_pb; f.have_recs = d_recs != nullptr; f.lines_override = base.lines_override != 0;
+    f.active = base.active != nullptr;
+    const ReplanPlan plan = plan_replan(f);
+    const int slots = f.slots;
     SampleSched sc{d_sched_n.p, d_sched_seg.p, d_sched_dt.p};
-    const bool geo = (phases & 1) != 0, qp = (phases & 2) != 0;
+    last_plan = record_of(plan, last_plan);
     if (timing) hipEventRecord(next_event(), st);
-    // the hull kernel makes the hulls' boxes itself (and zeroes the redo counters) when it is the eight-hulls-per-wave kernel over one hull list
-    // per agent and the static polygons' boxes are in place (written at upload: push_static_boxes): one launch less per round
-    const bool fused_boxes = d_recs && geo && ps.skip_box != nullptr && !ps.lines_override && static_boxes_ok && ps.hull_pb <= 0
-                             && n_rec == sp.num_agents && sp.n_hull == sp.num_agents && hulls_grouped(sp, n_scenes, n_rec);
-    // ... and, in one wave more, this round's launch order of the QP workgroups (order_kernel's counting sort: it only needs the previous
-    // round's measured times), when the same call goes on to the QP half
-    const bool want_order = qp && lpt && have_history && slots > 1024 && d_order_key.n >= (size_t)slots && d_order.n >= (size_t)slots;
-    const bool fused_order = fused_boxes && want_order;
-    if (fused_order) { ps.order = d_order.p; ps.order_key = d_order_key.p; }
-    if (geo) last_path = 0; else last_path &= NEP_PATH_BOX_KERNEL | NEP_PATH_HULLS_GROUPED | NEP_PATH_FUSED_BOXES | NEP_PATH_FUSED_ORDER;      // (a QP half keeps its geometry half's bits)
-    if (d_recs && geo) launch_hulls(d_recs, n_scenes, n_rec, ps.guess, sp, ps, st, fused_boxes);
-    if (d_recs && geo && hulls_grouped(sp, n_scenes, n_rec)) last_path |= NEP_PATH_HULLS_GROUPED;
-    if (fused_boxes) last_path |= NEP_PATH_FUSED_BOXES;
-    if (fused_order) last_path |= NEP_PATH_FUSED_ORDER;
+    if (plan.hulls) {      // (fused_order: the launch order and the polish counters' zeroes come out of the launch's block 0)
+      ProblemSet ph = base;
+      if (plan.fused_order) { ph.order = d_order.p; ph.order_key = d_order_key.p; }
+      launch_hulls(d_recs, n_scenes, n_rec, ph.guess, sp, ph, st, plan.grouped_hulls, plan.fused_boxes, plan.fused_order);
+    }
     if (timing) hipEventRecord(next_event(), st);
-    if (ps.lines_override) { ps.skip_box = nullptr; ps.line_skip = nullptr; ps.redo_list = nullptr; ps.redo_count = nullptr; }
-    if (scratch_chunks > 0 && ps.scratch_chunks == 0) {      // (a pooled handle asked for a replan without the redo pass — lines from the host, a rule or hull layout that cannot skip LPs: one area per slot after all)
+    if (plan.grow_scratch) {
       scratch_full = true;
       HIPCHK(hipStreamSynchronize(st));
       if (int e = size_row_scratch()) return e;
-      ps.row_scratch = d_row_scratch.p;
     }
-    const bool skip = ps.skip_box != nullptr;
-    // the presolve's zero-iteration certificate ahead of the interior-point launch: the replans it finishes (nine in ten of the bench's
-    // scenes) cost that launch an immediate return.  In the separator's own wave when that wave holds every segment of its slot (the
-    // packed kernel at eight segments a wave: launches of some 4 096 slots and more) — everything the certificate reads is in that
-    // wave's hands (qp_presolve.h) —, as a kernel of its own otherwise (qp_presolve_kernel.hip).  The fused form keeps to the cases it
-    // is tested in: one call for both halves, no active set, and the launch order either made by the hull launch or not made at all
-    // (a certified slot's key decays when it is certified: an order kernel between the separator and the QP launch would read the
-    // decayed keys, where it reads the previous round's with the kernel of its own).
-    const bool pre = qp && use_reg && presolve_kernel && ps.line_far != nullptr && !ps.lines_override && d_presolved.n >= (size_t)slots;
-    const bool fused_pre = pre && presolve_fused && phases == 3 && !ps.active && skip && sp.cull_radius > 0.0 && (!want_order || fused_order)
-                           && separator_pack(slots, sp, ps) == NEP_MAX_POL;
-    if (!ps.lines_override && geo) {
-      if (skip && !fused_boxes) { launch_boxes(n_scenes, sp, ps, st); last_path |= NEP_PATH_BOX_KERNEL; }      // (zeroes the redo counters as well)
-      if (fused_pre) {
-        ps.presolved = d_presolved.p; ps.pre_tables = d_tables.p; ps.pre_sched_n = d_sched_n.p;
-        ps.order_key = (lpt && d_order_key.n >= (size_t)slots) ? d_order_key.p : nullptr;      // (as below: the certified slots' keys decay)
-        last_path |= NEP_PATH_PRESOLVE_KERNEL | NEP_PATH_FUSED_PRESOLVE;
-      }
-      launch_separator(slots, sp, ps, st);
-      ps.pre_tables = nullptr; ps.pre_sched_n = nullptr;
+    // the geometry half's set: no skipped LPs with lines from the host
+    ProblemSet pg = base;
+    pg.row_scratch = d_row_scratch.p;
+    if (!plan.skip) { pg.skip_box = nullptr; pg.line_skip = nullptr; pg.redo_list = nullptr; pg.redo_count = nullptr; }
+    if (plan.box_kernel) launch_boxes(n_scenes, sp, pg, st);
+    if (plan.separator) {      // (the certificate in its wave: the marks, the tables, and the keys, which decay for the slots it certifies)
+      ProblemSet psep = pg;
+      if (plan.certificate == kCertWave) { psep.presolved = d_presolved.p; psep.pre_tables = d_tables.p; psep.pre_sched_n = d_sched_n.p; psep.order_key = plan.keyed ? d_order_key.p : nullptr; }
+      launch_separator(slots, sp, psep, plan.sep_pack, plan.certificate == kCertWave, st);
     }
     if (timing) hipEventRecord(next_event(), st);
-    if (!qp) { if (timing) hipEventRecord(next_event(), st); HIPCHK(hipGetLastError()); return 0; }
-    ps.order = nullptr; last_ordered = false;
-    ps.order_key = (lpt && d_order_key.n >= (size_t)slots) ? d_order_key.p : nullptr;
-    if (ps.order_key && have_history && slots > 1024 && d_order.n >= (size_t)slots) {   // (more than one wave of workgroups)
-      if (!fused_order) launch_qp_order(slots, d_order_key.p, d_order.p, st, ps.polish_count);      // (zeroes the polish pass's counters on its way; fused_order: the hull launch has done both)
-      ps.order = d_order.p; last_ordered = true; last_path |= NEP_PATH_ORDERED_QP;
-    } else if (ps.polish_count && !(use_reg && slots == 1)) launch_qp_polish_zero(ps.polish_count, st);      // (a one-workgroup launch — the per-agent handle — sets the counters itself: qp_reg_kernel's last lines)
-    if (ps.active) {      // an active set: the QP launches run over the list of active slots (in the launch order made above), the inactive slots' outputs are written apart
+    if (!plan.qp) { if (timing) hipEventRecord(next_event(), st); HIPCHK(hipGetLastError()); return 0; }
+    if (plan.order_kernel) launch_qp_order(slots, d_order_key.p, d_order.p, st, pg.polish_count);
+    if (plan.polish_zero) launch_qp_polish_zero(pg.polish_count, st);
+    if (plan.active_list) {
       if (int e = d_act.ensure((size_t)slots + 1)) return e;
-      launch_active_list(slots, sp, ps.active, ps.order, d_act.p, ps.polish_count, st);      // (zeroes the polish counters as well: a one-workgroup launch whose slot is inactive does not)
-      ps.order = d_act.p; ps.order_count = d_act.p + slots;
-      launch_skipped_replan(slots, sp, ps, st);
+      launch_active_list(slots, sp, pg.active, plan.ordered_qp ? d_order.p : nullptr, d_act.p, pg.polish_count, st);      // (zeroes the polish counters as well: a one-workgroup launch whose slot is inactive does not)
     }
-    if (pre && !fused_pre) {      // the certificate as a kernel of its own, one wave per replan
-      ps.presolved = d_presolved.p;
-      launch_qp_presolve(slots, sp, ps, d_tables.p, sc, d_presolved.p, st);
-      last_path |= NEP_PATH_PRESOLVE_KERNEL;
-    }
-    if (use_reg) launch_qp_reg(slots, sp, ps, d_tables.p, sc, lds_bytes, st);
-    else launch_qp(slots, sp, ps, d_tables.p, sc, lds_bytes, st);
-    if (skip && !no_redo) {      // (NEP_SEP_NO_REDO, read in size_scratch: development aid — the flagged replans keep their presolved result for inspection)
-      // the presolve's redo pass: replans whose solution did not verify the skipped / parked lines (listed by the kernel above; the
-      // list is empty nearly always) get every LP solved and every row through the interior point
-      launch_separator_redo(slots, sp, ps, st);
-      last_path |= NEP_PATH_REDO_PASS;
-      ProblemSet pr = ps;
+    // the QP half's set: the keys, the certificate's marks, and the workgroup -> slot order (the active list, the launch order, or slot order)
+    ProblemSet pq = pg;
+    pq.presolved = plan.certificate != kCertNone ? d_presolved.p : nullptr;
+    pq.order_key = plan.keyed ? d_order_key.p : nullptr;
+    pq.order = plan.active_list ? d_act.p : plan.ordered_qp ? d_order.p : nullptr;
+    pq.order_count = plan.active_list ? d_act.p + slots : nullptr;
+    if (plan.active_list) launch_skipped_replan(slots, sp, pq, st);
+    if (plan.certificate == kCertKernel) launch_qp_presolve(slots, sp, pq, d_tables.p, sc, d_presolved.p, st);      // one wave per replan
+    if (plan.qp_kernel == kQpLds) launch_qp(slots, sp, pq, d_tables.p, sc, lds_bytes, st);
+    else launch_qp_reg(slots, sp, pq, plan.qp_kernel, d_tables.p, sc, lds_bytes, st);
+    if (plan.redo_pass) {
+      launch_separator_redo(slots, sp, pq, st);
+      ProblemSet pr = pq;      // every row, no parked lines, no marks; over the redo list
       pr.line_far = nullptr; pr.line_skip = nullptr; pr.order = d_redo_list.p; pr.order_count = d_redo_count.p;      // (lists active slots only: no other slot ran)
       pr.presolved = nullptr;      // (every listed replan is solved again, whatever the presolve kernel marked)
-      pr.scratch_by_block = ps.scratch_chunks > 0 ? 1 : 0;
-      launch_qp_reg(slots, sp, pr, d_tables.p, sc, lds_bytes, st);
+      pr.scratch_by_block = pq.scratch_chunks > 0 ? 1 : 0;
+      launch_qp_reg(slots, sp, pr, kQpReg, d_tables.p, sc, lds_bytes, st);
     }
-    if (ps.polish_list) launch_qp_polish(slots, sp, ps, d_tables.p, sc, st);      // (the slots the QP kernel listed: nearly always none — workgroups beyond the count return at once)
-    have_history = ps.order_key != nullptr;
+    if (plan.polish_pass) launch_qp_polish(slots, sp, pq, d_tables.p, sc, st);
+    have_history = plan.have_history;
     if (timing) hipEventRecord(next_event(), st);
     HIPCHK(hipGetLastError());
     return 0;
@@ -559,6 +542,7 @@ struct Engine {
   ~Engine() { for (auto e : ev) hipEventDestroy(e); }      // (the buffers free themselves)
 };
 
+bool grouped_hulls(const SceneParams& sp, int n_scenes, int n_rec) { return eight_hulls_per_wave(sp.num_pol, sp.hull_mode, n_scenes, n_rec); }      // (the hull launches outside run(): the same rule, launch_plan.h)
 bool have_device() { int n = 0; return hipGetDeviceCount(&n) == hipSuccess && n > 0; }
 
 
@@ -1180,7 +1164,7 @@ int nep_batch_hulls(nep_batch_t* h, const nep_traj_rec* d_committed_local, const
   const HullBlock b = block_of(h);
   ProblemSet ps = round_set(h, d_guess);
   point_at_block(ps, b, d_block);
-  launch_hulls(d_committed_local, h->cfg.n_scenes, h->cfg.n_local, d_guess, E.sp, ps, (hipStream_t)stream);
+  launch_hulls(d_committed_local, h->cfg.n_scenes, h->cfg.n_local, d_guess, E.sp, ps, (hipStream_t)stream, grouped_hulls(E.sp, h->cfg.n_scenes, h->cfg.n_local));
   if (h->cfg.enable_entangle)      // what the entangle check reads of my agents' trajectories travels in the same block
     launch_ent_sample(d_committed_local, h->cfg.n_scenes, h->cfg.n_local, &d_guess->t_start, (long)sizeof(nep_guess) * h->cfg.n_local, h->cfg.num_pol, h->ent_ns,
                       E.sp.T_span, (double*)((char*)d_block + b.samp), (int*)((char*)d_block + b.present), (hipStream_t)stream);
@@ -1209,7 +1193,7 @@ int nep_batch_frontend(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_traj_rec
   if (!fe_cfg_ok(cfg)) return fail(NEP_E_ARG, "bad front-end configuration");
   const ProblemSet ps = round_set(h);
   h->fe_committed = d_committed;
-  launch_hulls_ts(d_committed, h->cfg.n_scenes, h->cfg.num_agents, &d_start->t_start, (long)sizeof(nep_fe_start), h->eng.sp, ps, (hipStream_t)stream);
+  launch_hulls_ts(d_committed, h->cfg.n_scenes, h->cfg.num_agents, &d_start->t_start, (long)sizeof(nep_fe_start), h->eng.sp, ps, (hipStream_t)stream, grouped_hulls(h->eng.sp, h->cfg.n_scenes, h->cfg.num_agents));
   return run_frontend(h, ps, *cfg, d_start, d_guess, d_result, nullptr, stream);
 }
 
@@ -1382,7 +1366,7 @@ int nep_batch_frontend_ent(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_traj
   Engine& E = h->eng;
   const ProblemSet ps = round_set(h);
   h->fe_committed = d_committed;
-  launch_hulls_ts(d_committed, h->cfg.n_scenes, h->cfg.num_agents, &d_start->t_start, (long)sizeof(nep_fe_start), E.sp, ps, (hipStream_t)stream);
+  launch_hulls_ts(d_committed, h->cfg.n_scenes, h->cfg.num_agents, &d_start->t_start, (long)sizeof(nep_fe_start), E.sp, ps, (hipStream_t)stream, grouped_hulls(E.sp, h->cfg.n_scenes, h->cfg.num_agents));
   FeEntArgs ea{};
   if (int e = ent_prepare(h, cfg->ent_samples, cfg->beam_width, d_committed, &d_start->t_start, (long)sizeof(nep_fe_start) * E.sp.n_local, ea, (hipStream_t)stream)) return e;
   ea.init = d_ent_init; ea.case_out = d_case_out;
@@ -1432,7 +1416,7 @@ int nep_batch_safety_commit_ent(nep_batch_t* h, const nep_traj_rec* d_prev, cons
   ea.pk_stride = 2 + 2 * kBend + 2 * (ea.ns + 1);
   if (int e = E.d_fe_packed.ensure((size_t)h->cfg.n_scenes * N * h->cfg.num_pol * ea.pk_stride)) return e;
   ea.packed = E.d_fe_packed.p;
-  launch_hulls(d_new, h->cfg.n_scenes, N, d_guess, E.sp, ps, (hipStream_t)stream);     // (with the bend points: ent_enabled)
+  launch_hulls(d_new, h->cfg.n_scenes, N, d_guess, E.sp, ps, (hipStream_t)stream, grouped_hulls(E.sp, h->cfg.n_scenes, N));     // (with the bend points: ent_enabled)
   launch_ent_check(E.sp, ps, ea, d_new, h->cfg.n_scenes, cable_length, E.d_entangles.p, (hipStream_t)stream);
   return safety_end(h, ps, d_prev, d_new, E.d_entangles.p, d_final, d_accept, (hipStream_t)stream);
 }
@@ -2164,7 +2148,7 @@ int nep_batch_fe_search_us(nep_batch_t* h, float* us, int32_t cap) {
 int nep_batch_debug_launch_order(nep_batch_t* h, int32_t* order, int32_t cap, int32_t* n_out) {
   if (!h || !order || !n_out || cap < 0) return fail(NEP_E_ARG, "bad arguments");
   *n_out = 0;
-  if (!h->eng.last_ordered) return 0;
+  if (!h->eng.last_plan.ordered_qp) return 0;
   if (cap < h->slots) return fail(NEP_E_CAP, "order buffer smaller than the slot count");
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(order, h->eng.d_order.p, (size_t)h->slots * sizeof(int), hipMemcpyDeviceToHost));
@@ -2174,7 +2158,7 @@ int nep_batch_debug_launch_order(nep_batch_t* h, int32_t* order, int32_t cap, in
 // Test hooks of the launch sequence (include/neptune_backend_debug.h): what the last replan launched, the obstacle boxes, the ordering keys
 int nep_batch_debug_launch_path(nep_batch_t* h, int32_t* bits) {
   if (!h || !bits) return fail(NEP_E_ARG, "bad arguments");
-  *bits = h->eng.last_path;
+  *bits = path_bits(h->eng.last_plan);
   return 0;
 }
 int nep_batch_debug_boxes(nep_batch_t* h, int32_t scene, double* out, int32_t cap) {
@@ -2319,7 +2303,7 @@ int nep_batch_debug_polish_count(nep_batch_t* h, int32_t* listed, int32_t* certi
   HIPCHK(hipDeviceSynchronize());
   // (a launch whose pass was not armed — polish off, or the LDS-placement kernel, which has no hooks — leaves the counters of an earlier
   // launch behind: reported as (0, 0), round-5 advisor finding)
-  if (h->eng.d_polish_count.p && h->eng.last_polish_armed) HIPCHK(hipMemcpy(c, h->eng.d_polish_count.p, sizeof(c), hipMemcpyDeviceToHost));
+  if (h->eng.d_polish_count.p && h->eng.last_plan.polish_armed) HIPCHK(hipMemcpy(c, h->eng.d_polish_count.p, sizeof(c), hipMemcpyDeviceToHost));
   if (listed) *listed = c[0];
   if (certified) *certified = c[3];
   return 0;
@@ -2329,7 +2313,7 @@ int nep_batch_debug_polish_count(nep_batch_t* h, int32_t* listed, int32_t* certi
 int nep_batch_debug_polish_flags(nep_batch_t* h, int32_t* flags, int32_t cap) {
   if (!h || !flags || cap < h->slots) return fail(NEP_E_ARG, "bad arguments");
   for (int i = 0; i < h->slots; i++) flags[i] = 0;
-  if (!h->eng.d_polish_count.p || !h->eng.last_polish_armed) return 0;
+  if (!h->eng.d_polish_count.p || !h->eng.last_plan.polish_armed) return 0;
   int c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(c, h->eng.d_polish_count.p, sizeof(c), hipMemcpyDeviceToHost));

@@ -493,27 +493,17 @@ __global__ __launch_bounds__(64) void hull_group_kernel(const nep_traj_rec* __re
   }
 }
 
-bool hulls_grouped(const SceneParams& sp, int n_scenes, int n_rec) {
-  return sp.num_pol <= 8 && (sp.hull_mode ? sp.hull_mode == 2 : (long)n_scenes * n_rec > 2048);
-}
 void launch_hulls(const nep_traj_rec* recs, int n_scenes, int n_rec, const nep_guess* guess,
-                  const SceneParams& sp, const ProblemSet& ps, hipStream_t st, bool boxes) {
-  launch_hulls_ts(recs, n_scenes, n_rec, &guess->t_start, (long)sizeof(nep_guess), sp, ps, st, boxes);
+                  const SceneParams& sp, const ProblemSet& ps, hipStream_t st, bool grouped, bool boxes, bool ord) {
+  launch_hulls_ts(recs, n_scenes, n_rec, &guess->t_start, (long)sizeof(nep_guess), sp, ps, st, grouped, boxes, ord);
 }
 void launch_hulls_ts(const nep_traj_rec* recs, int n_scenes, int n_rec, const double* ts0, long ts_slot_stride,
-                     const SceneParams& sp, const ProblemSet& ps, hipStream_t st, bool boxes) {
+                     const SceneParams& sp, const ProblemSet& ps, hipStream_t st, bool grouped, bool boxes, bool ord) {
   int blocks = n_scenes * n_rec * sp.num_pol;
   if (blocks <= 0) return;
   // the uninflated hull is read only by the entangle rows (col(0), solver_gurobi_poly.cpp:722-734)
   const bool need0 = sp.ent_enabled != 0;
-  // Eight hulls per wave when there are enough trajectories to fill the chip with such waves (a wave of eight takes ~60 us,
-  // one hull per wave ~26 us: below ~2 000 trajectories the launch is one round of waves either way and the short waves
-  // finish first — 0.026 against 0.058 ms for one 64-agent scene; 0.077 both at 32 scenes; 0.271 against 0.183 ms at 128).
-  // nep_batch_set_hull_kernel forces one (tests, A/B).
-  const bool grouped = sp.hull_mode ? sp.hull_mode == 2 : (long)n_scenes * n_rec > 2048;
-  if (sp.num_pol <= 8 && grouped) {
-    // (ps.order != null on the way in: the caller wants this round's QP launch order made in the launch's shadow — ps.order_key / ps.order_n)
-    const bool ord = boxes && ps.order != nullptr && ps.order_key != nullptr;
+  if (grouped) {      // (ord: this round's QP launch order is made in the launch's shadow, from ps.order_key into ps.order)
     hipLaunchKernelGGL(hull_group_kernel, dim3(n_scenes * n_rec + (ord ? 1 : 0)), dim3(64), 0, st, recs, n_rec, ts0, ts_slot_stride * sp.n_local,
                        sp.num_pol, sp.T_span, sp.drone_radius, ps.hull_xy, ps.hull_nv, need0 ? ps.hull0_xy : nullptr,
                        need0 ? ps.hull0_nv : nullptr, need0 ? ps.bend_xy : nullptr, need0 ? ps.bend_n : nullptr, ps.flags,
@@ -1652,30 +1642,17 @@ static int separator_pool_pairs(const SceneParams& sp) {
   return (int)((separator_lds_bytes(sp) - tail) / 16);
 }
 
-// segments per wave of the packed kernel for this launch, 0 when the launch takes the unpacked kernel
-int separator_pack(int n_slots, const SceneParams& sp, const ProblemSet& ps) {
-  // (only with the spatial presolve: with every LP to solve a segment fills its wave by itself — 64 to 68 LPs — and the packed form is
-  // slower, 0.53 against 0.41 ms per 4.2 M LPs: its step 1 is serial over the segments and its lanes hold different control points)
-  const int total = sp.n_hull + sp.num_agents + sp.n_static + (sp.ent_enabled ? sp.num_agents * kBend : 0);
-  // the packed kernel's list entries are (segment << 13 | candidate) in 16 bits: candidates beyond 8 191 (about 800 agents with the
-  // entangle rows, 4 000 without) take the unpacked kernel, whose entries hold 65 535 (size_scratch refuses more)
-  if (!(((ps.skip_box && ps.line_far && sp.cull_radius > 0.0 && ps.sep_pack >= 0) || (sp.cull_radius == 0.0 && ps.sep_pack >= 1)) && sp.sep_rule == 0 && total <= 8191)) return 0;
-  int pack = 1; while (pack < NEP_MAX_POL && (long)n_slots * (NEP_MAX_POL / (pack * 2)) >= 4096) pack *= 2;      // (at least ~4 000 waves while the launch allows it)
-  if (ps.sep_pack >= 1 && ps.sep_pack <= NEP_MAX_POL) pack = ps.sep_pack;
-  return pack;
-}
-void launch_separator(int n_slots, const SceneParams& sp, const ProblemSet& ps_in, hipStream_t st) {
+// pack: segments per wave of the packed kernel, 0: the unpacked kernel; cert: the wave runs the zero-iteration certificate (ps.pre_tables,
+// ps.pre_sched_n and ps.presolved are given) — both are the launch plan's (launch_plan.h)
+void launch_separator(int n_slots, const SceneParams& sp, const ProblemSet& ps, int pack, bool cert, hipStream_t st) {
   if (n_slots <= 0) return;
-  const int pack = separator_pack(n_slots, sp, ps_in);
   if (pack > 0) {
-    ProblemSet ps = ps_in;
-    if (pack != NEP_MAX_POL || !(sp.cull_radius > 0.0) || !ps.line_far || !ps.presolved || !ps.pre_sched_n || ps.active) ps.pre_tables = nullptr;      // (the certificate needs the whole slot in one wave; the wave of an inactive slot returns at its first line and would leave a stale mark)
     // (the wave's LDS stays within the 10 KB sixteen waves per CU allow: the pool of point sets takes what the tables leave, 64 x 8 pairs at least)
     const size_t rounds_ = (size_t)((sp.n_hull + 63) / 64 + (sp.num_agents + 63) / 64 + (sp.n_static + 63) / 64);
     const size_t extras = 15 * NEP_MAX_POL * sizeof(double) + 2 * NEP_MAX_POL * rounds_ * sizeof(unsigned long long) + 6 * NEP_MAX_POL * sizeof(int)
                           + ((sp.ent_enabled && ps.case_id) ? (size_t)NEP_MAX_POL * ((sp.num_agents + 63) / 64) * sizeof(unsigned long long) : 0)
                           + (size_t)(sep_packed_cap(sp.n_hull + sp.num_agents + sp.n_static) + (sp.ent_enabled ? sp.num_agents : 0)) * sizeof(unsigned short)
-                          + (ps.pre_tables ? (size_t)8 * NEP_MAX_POL * sizeof(double) + 8 : 0);      // (the certificate's control points at z*, live through the LP batches: x, y of [segment][4], 8-byte aligned behind the entries)
+                          + (cert ? (size_t)8 * NEP_MAX_POL * sizeof(double) + 8 : 0);      // (the certificate's control points at z*, live through the LP batches: x, y of [segment][4], 8-byte aligned behind the entries)
     size_t pool_b = extras + 64 * 6 * 16 <= (size_t)kSepLdsTarget ? (size_t)kSepLdsTarget - extras : (size_t)64 * 6 * 16;
     pool_b &= ~(size_t)15;
     const int pairs = (int)(pool_b / 16);
@@ -1686,7 +1663,6 @@ void launch_separator(int n_slots, const SceneParams& sp, const ProblemSet& ps_i
     hipLaunchKernelGGL(separator_packed_kernel, dim3(n_slots * groups), dim3(64), lds_p, st, sp, ps, pairs, pack);
     return;
   }
-  const ProblemSet& ps = ps_in;
   const size_t lds = separator_lds_bytes(sp);
   static DynLdsAttr attr[2];
   if (sp.sep_rule == 1) {
@@ -1965,7 +1941,7 @@ void launch_safety(const nep_traj_rec* prev, const nep_traj_rec* fresh, int n_sc
                    const int* active) {
   if (n_scenes * N <= 0) return;
   auto hulls_of = [&](const nep_traj_rec* recs) {      // interval hulls of one record set on the round's grid (eight per wave, as in the replan)
-    if (sp.num_pol <= 8 && (sp.hull_mode ? sp.hull_mode == 2 : (long)n_scenes * N > 2048))
+    if (eight_hulls_per_wave(sp.num_pol, sp.hull_mode, n_scenes, N))
       hipLaunchKernelGGL(hull_group_kernel, dim3(n_scenes * N), dim3(64), 0, st, recs, N, &ps.guess->t_start, (long)sizeof(nep_guess) * sp.n_local, sp.num_pol, sp.T_span,
                          sp.drone_radius, ps.hull_xy, ps.hull_nv, (double*)nullptr, (int*)nullptr, (double*)nullptr, (int*)nullptr, ps.flags,
                          (double*)nullptr, 0, (int*)nullptr, n_scenes * N, 0, (const int*)nullptr, (int*)nullptr, (int*)nullptr);
@@ -3058,10 +3034,10 @@ void launch_frontend(int n_slots, const SceneParams& sp, const ProblemSet& ps_in
   ProblemSet ps = ps_in;
   ps.fe_order = nullptr;
   const int xcd_mode = g_debug.fe_xcd;      // (A/B, nep_debug_set_global_option "fe_xcd": 0 = the launch order without the XCD placement)
-  if (order_buf && n_slots > 1024 && n_slots % 8 == 0 && xcd_mode) {      // a few whole scenes per XCD, the longest expected searches first within each (order_xcd_kernel)
+  if (order_buf && more_than_one_wave(n_slots) && n_slots % 8 == 0 && xcd_mode) {      // a few whole scenes per XCD, the longest expected searches first within each (order_xcd_kernel)
     launch_order_xcd(n_slots, (ps.fe_order_key && have_history) ? ps.fe_order_key : nullptr, order_buf, st);
     ps.fe_order = order_buf;
-  } else if (ps.fe_order_key && order_buf && have_history && n_slots > 1024) {      // (more than one wave of workgroups)
+  } else if (ps.fe_order_key && order_buf && have_history && more_than_one_wave(n_slots)) {
     launch_qp_order(n_slots, ps.fe_order_key, order_buf, st);
     ps.fe_order = order_buf;
   }

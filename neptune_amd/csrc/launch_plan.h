@@ -1,0 +1,157 @@
+// launch_plan.h — the launch topology of one replan (Engine::run, backend.hip), decided once: the caller copies the facts out of its
+// handle and its call (ReplanFacts), plan_replan says what will be launched (ReplanPlan), the launch code follows the plan and the debug
+// calls read it back (path_bits).  Every rule of the sequence is stated here and nowhere else.  Plain C++, no HIP: tests/cpp/launch_plan_check.cpp
+// runs the rules without a GPU.  plan_replan allocates nothing and loops over nothing (the per-agent handle calls it on every optimize()).
+#ifndef NEP_LAUNCH_PLAN_H_
+#define NEP_LAUNCH_PLAN_H_
+
+#include "../../include/neptune_backend.h"
+#include "../../include/neptune_backend_debug.h"
+
+namespace nep {
+
+struct ReplanFacts {
+  // the scene parameters
+  int num_agents = 0, num_pol = 0, n_hull = 0, n_static = 0, ent_enabled = 0, hull_mode = 0, skip_own = 0, sep_rule = 0;
+  double cull_radius = 0.0;
+  // the handle's switches and state
+  bool use_reg = false, lpt = true, have_history = false, presolve_kernel = true, presolve_fused = true, skip_lps = true, no_redo = false;
+  bool statics_boxy = true, static_boxes_ok = false;
+  int sep_pack = 0;                                  // 0 by launch size, -1 the unpacked kernel, 1..NEP_MAX_POL forced
+  bool polish = true, polish_presolve = true, polish_buffers = false;      // (nep_*_set_polish; the pass's buffers exist)
+  bool order_ok = false, order_key_ok = false, presolved_ok = false;       // d_order, d_order_key, d_presolved hold one entry per slot
+  int scratch_chunks = 0;                            // > 0: the row scratch is the redo pass's pool of that many areas
+  // the call
+  int slots = 0, n_scenes = 0, n_rec = 0, phases = 3, hull_pb = 0;
+  bool have_recs = false, lines_override = false, active = false;
+};
+
+enum Certificate { kCertNone = 0, kCertKernel = 1, kCertWave = 2 };      // the zero-iteration certificate: not ahead of the QP launch, qp_presolve_kernel, the separator's wave
+enum QpKernel { kQpLds = 0, kQpReg = 1, kQpRegCull = 2, kQpRegCullPolish = 3 };      // qp_kernel, qp_reg_kernel<false>, <true, false>, <true, true>
+
+struct ReplanPlan {
+  bool geo = false, qp = false;                      // the halves of this call (phases & 1, phases & 2)
+  bool hulls = false, grouped_hulls = false;         // the hull launch, and whether it is the eight-hulls-per-wave kernel
+  bool fused_boxes = false, fused_order = false, box_kernel = false;
+  bool skip = false;                                 // LPs whose box is far are skipped (and verified after the solve)
+  bool separator = false; int sep_pack = 0;          // the separator launch; its segments per wave, 0: the unpacked kernel
+  Certificate certificate = kCertNone;
+  bool keyed = false;                                // the QP workgroups write their measured time into the ordering keys
+  bool order_kernel = false, ordered_qp = false, polish_zero = false, active_list = false;
+  QpKernel qp_kernel = kQpLds;
+  bool redo_pass = false;                            // ... over the redo list, every row: qp_reg_kernel<false>
+  bool polish_armed = false, polish_pass = false;    // the QP kernels list solves for the polish pass; the pass is launched
+  bool grow_scratch = false;                         // the row scratch must first grow to one area per slot
+  bool have_history = false;                         // what the call leaves behind for the next one
+};
+
+// --- the rules ---------------------------------------------------------------------------------------------------------------------
+
+// "More than one wave of workgroups": below that a launch order changes nothing, every workgroup starts at once.
+inline bool more_than_one_wave(long slots) { return slots > 1024; }
+
+// Eight hulls per wave when there are enough trajectories to fill the chip with such waves (a wave of eight takes ~60 us,
+// one hull per wave ~26 us: below ~2 000 trajectories the launch is one round of waves either way and the short waves
+// finish first — 0.026 against 0.058 ms for one 64-agent scene; 0.077 both at 32 scenes; 0.271 against 0.183 ms at 128).
+// nep_batch_set_hull_kernel forces one (tests, A/B).
+inline bool eight_hulls_per_wave(int num_pol, int hull_mode, int n_scenes, int n_rec) {
+  return num_pol <= 8 && (hull_mode ? hull_mode == 2 : (long)n_scenes * n_rec > 2048);
+}
+
+// LPs whose line is known to be far without solving them may be skipped when the presolve is on, the rule is the largest gap
+// (box far => line far holds for that vertex only), the hull lists are the batch's (one per agent: the boxes are indexed
+// by agent) and the interior point is the register kernel (the one that verifies them): see separator_body / qp_reg_kernel
+inline bool can_skip_lps(const ReplanFacts& f) {
+  return f.cull_radius > 0.0 && f.use_reg && f.sep_rule == 0 && f.skip_own == 1 && f.n_hull == f.num_agents && f.skip_lps && f.statics_boxy;
+}
+inline bool skip_mode(const ReplanFacts& f) { return can_skip_lps(f) && !f.no_redo; }      // ... and the replans that fail the verification go through the redo pass
+
+// the polish pass finishes what the register kernel leaves.  Under the presolve only on request (nep_batch_set_polish(h, 2): on the
+// near lines, and a certified point goes through the presolve's verification of the parked lines and the skipped LPs again —
+// polish_slot): a pass over a handful of slots is 0.03-0.06 ms, 8 % of a presolved step
+inline bool polish_armed(const ReplanFacts& f) {
+  return f.polish && f.use_reg && (f.polish_presolve || !(f.cull_radius > 0.0)) && f.polish_buffers;
+}
+
+// segments per wave of the packed separator for this launch, 0 when the launch takes the unpacked kernel (skip: the plan's)
+inline int segments_per_wave(const ReplanFacts& f, bool skip) {
+  // (only with the spatial presolve: with every LP to solve a segment fills its wave by itself — 64 to 68 LPs — and the packed form is
+  // slower, 0.53 against 0.41 ms per 4.2 M LPs: its step 1 is serial over the segments and its lanes hold different control points)
+  const int total = f.n_hull + f.num_agents + f.n_static + (f.ent_enabled ? f.num_agents * NEP_MAX_BEND : 0);
+  // the packed kernel's list entries are (segment << 13 | candidate) in 16 bits: candidates beyond 8 191 (about 800 agents with the
+  // entangle rows, 4 000 without) take the unpacked kernel, whose entries hold 65 535 (size_scratch refuses more)
+  if (!(((skip && f.cull_radius > 0.0 && f.sep_pack >= 0) || (f.cull_radius == 0.0 && f.sep_pack >= 1)) && f.sep_rule == 0 && total <= 8191)) return 0;
+  int pack = 1; while (pack < NEP_MAX_POL && (long)f.slots * (NEP_MAX_POL / (pack * 2)) >= 4096) pack *= 2;      // (at least ~4 000 waves while the launch allows it)
+  if (f.sep_pack >= 1 && f.sep_pack <= NEP_MAX_POL) pack = f.sep_pack;
+  return pack;
+}
+
+inline ReplanPlan plan_replan(const ReplanFacts& f) {
+  ReplanPlan p;
+  const bool cull = f.cull_radius > 0.0;
+  p.geo = (f.phases & 1) != 0; p.qp = (f.phases & 2) != 0;
+  p.hulls = f.have_recs && p.geo;
+  p.grouped_hulls = p.hulls && eight_hulls_per_wave(f.num_pol, f.hull_mode, f.n_scenes, f.n_rec);
+  // the hull kernel makes the hulls' boxes itself (and zeroes the redo counters) when it is the eight-hulls-per-wave kernel over one hull list
+  // per agent and the static polygons' boxes are in place (written at upload: push_static_boxes): one launch less per round
+  p.fused_boxes = p.grouped_hulls && can_skip_lps(f) && !f.lines_override && f.static_boxes_ok && f.hull_pb <= 0
+                  && f.n_rec == f.num_agents && f.n_hull == f.num_agents;
+  // ... and, in one wave more, this round's launch order of the QP workgroups (order_kernel's counting sort: it only needs the previous
+  // round's measured times), when the same call goes on to the QP half
+  p.keyed = p.qp && f.lpt && f.order_key_ok;
+  p.ordered_qp = p.keyed && f.have_history && more_than_one_wave(f.slots) && f.order_ok;
+  p.fused_order = p.fused_boxes && p.ordered_qp;
+  p.order_kernel = p.ordered_qp && !p.fused_order;      // (zeroes the polish pass's counters on its way; fused_order: the hull launch has done both)
+  p.skip = can_skip_lps(f) && !f.lines_override;        // (lines from the host: no LP ran, none was skipped)
+  // (a pooled handle asked for a replan without the redo pass — lines from the host, a rule or hull layout that cannot skip LPs: one area per slot after all)
+  p.grow_scratch = f.scratch_chunks > 0 && !skip_mode(f);
+  p.separator = p.geo && !f.lines_override;
+  p.box_kernel = p.separator && p.skip && !p.fused_boxes;      // (zeroes the redo counters as well)
+  p.sep_pack = segments_per_wave(f, p.skip);
+  // the presolve's zero-iteration certificate ahead of the interior-point launch: the replans it finishes (nine in ten of the bench's
+  // scenes) cost that launch an immediate return.  In the separator's own wave when that wave holds every segment of its slot (the
+  // packed kernel at eight segments a wave: launches of some 4 096 slots and more) — everything the certificate reads is in that
+  // wave's hands (qp_presolve.h) —, as a kernel of its own otherwise (qp_presolve_kernel.hip).  The fused form keeps to the cases it
+  // is tested in: one call for both halves, no active set, and the launch order either made by the hull launch or not made at all
+  // (a certified slot's key decays when it is certified: an order kernel between the separator and the QP launch would read the
+  // decayed keys, where it reads the previous round's with the kernel of its own).  (The wave of an inactive slot returns at its
+  // first line and would leave a stale mark.)
+  const bool pre = p.qp && f.use_reg && f.presolve_kernel && cull && !f.lines_override && f.presolved_ok;
+  const bool wave = pre && f.presolve_fused && f.phases == 3 && !f.active && p.skip && !p.order_kernel && p.sep_pack == NEP_MAX_POL;
+  p.certificate = !pre ? kCertNone : wave ? kCertWave : kCertKernel;
+  p.polish_armed = polish_armed(f);
+  p.polish_zero = p.qp && !p.ordered_qp && p.polish_armed && !(f.use_reg && f.slots == 1);      // (a one-workgroup launch — the per-agent handle — sets the counters itself: qp_reg_kernel's last lines)
+  p.active_list = p.qp && f.active;      // an active set: the QP launches run over the list of active slots (in the launch order made above), the inactive slots' outputs are written apart
+  // the register kernel's instantiation: <CULL> with parked lines to verify (never with lines from the host), <.., POLISH> when it lists for the polish pass
+  p.qp_kernel = !f.use_reg ? kQpLds : !(cull && !f.lines_override) ? kQpReg : p.polish_armed ? kQpRegCullPolish : kQpRegCull;
+  // the presolve's redo pass: replans whose solution did not verify the skipped / parked lines (listed by the kernel above; the
+  // list is empty nearly always) get every LP solved and every row through the interior point — qp_reg_kernel<false>, whatever the
+  // certificate marked.  (no_redo: development aid — the flagged replans keep their presolved result for inspection)
+  p.redo_pass = p.qp && p.skip && !f.no_redo;
+  p.polish_pass = p.qp && p.polish_armed;      // (the slots the QP kernel listed: nearly always none — workgroups beyond the count return at once)
+  p.have_history = p.qp ? p.keyed : f.have_history;
+  return p;
+}
+
+// The record a call leaves of itself (the handle's last_plan): a QP half (phases == 2) keeps its geometry half's fields.
+inline ReplanPlan record_of(ReplanPlan p, const ReplanPlan& before) {
+  if (!p.geo) { p.box_kernel = before.box_kernel; p.grouped_hulls = before.grouped_hulls; p.fused_boxes = before.fused_boxes; p.fused_order = before.fused_order; }
+  return p;
+}
+
+// NEP_PATH_* of a record
+inline int path_bits(const ReplanPlan& p) {
+  int b = 0;
+  if (p.grouped_hulls) b |= NEP_PATH_HULLS_GROUPED;
+  if (p.fused_boxes) b |= NEP_PATH_FUSED_BOXES;
+  if (p.fused_order) b |= NEP_PATH_FUSED_ORDER;
+  if (p.box_kernel) b |= NEP_PATH_BOX_KERNEL;
+  if (p.certificate != kCertNone) b |= NEP_PATH_PRESOLVE_KERNEL;
+  if (p.certificate == kCertWave) b |= NEP_PATH_FUSED_PRESOLVE;
+  if (p.ordered_qp) b |= NEP_PATH_ORDERED_QP;
+  if (p.redo_pass) b |= NEP_PATH_REDO_PASS;
+  return b;
+}
+
+}  // namespace nep
+#endif

@@ -5,6 +5,7 @@
 #include <mutex>
 
 #include "nep_tables.h"
+#include "launch_plan.h"
 #include "../../include/neptune_frontend.h"
 #include "../../include/neptune_fleet.h"
 #include "../../include/neptune_backend_debug.h"
@@ -168,18 +169,17 @@ struct SampleSched {             // per K: n, seg[], dt[]
   const double* dt;              // [kMaxK+1][max_states]
 };
 
-// boxes: the hull kernel also writes the hulls' boxes (ps.fe_box, entries of the agents: what fe_box_kernel would make of them) and zeroes the
-// presolve's redo counters — only honoured by the eight-hulls-per-wave kernel (hulls_grouped) with one hull list per agent of the scene
-bool hulls_grouped(const SceneParams& sp, int n_scenes, int n_rec);
+// grouped: the eight-hulls-per-wave kernel (launch_plan.h: eight_hulls_per_wave).  boxes: that kernel also writes the hulls' boxes (ps.fe_box, entries
+// of the agents: what fe_box_kernel would make of them) and zeroes the presolve's redo counters — one hull list per agent of the scene; ord: and
+// its block 0 makes the QP launch order (ps.order_key -> ps.order) and zeroes the polish counters.  Both are the launch plan's, with grouped only
 void launch_hulls(const nep_traj_rec* recs, int n_scenes, int n_rec, const nep_guess* guess,
-                  const SceneParams& sp, const ProblemSet& ps, hipStream_t st, bool boxes = false);
+                  const SceneParams& sp, const ProblemSet& ps, hipStream_t st, bool grouped, bool boxes = false, bool ord = false);
 void launch_hulls_ts(const nep_traj_rec* recs, int n_scenes, int n_rec, const double* ts0, long ts_slot_stride,
-                     const SceneParams& sp, const ProblemSet& ps, hipStream_t st, bool boxes = false);
+                     const SceneParams& sp, const ProblemSet& ps, hipStream_t st, bool grouped, bool boxes = false, bool ord = false);
 void launch_hulls_explicit(const nep_traj_rec* recs, int n_traj, double t_start, int num_pol,
                            double T_span, double drone_radius, double* hull_xy, int* hull_nv,
                            double* hull0_xy, int* hull0_nv, int* flags, hipStream_t st);
-void launch_separator(int n_slots, const SceneParams& sp, const ProblemSet& ps, hipStream_t st);
-int separator_pack(int n_slots, const SceneParams& sp, const ProblemSet& ps);      // segments per wave of the packed separator for this launch, 0: the unpacked kernel
+void launch_separator(int n_slots, const SceneParams& sp, const ProblemSet& ps, int pack, bool cert, hipStream_t st);
 void launch_separator_redo(int n_slots, const SceneParams& sp, const ProblemSet& ps, hipStream_t st);
 void launch_boxes(int n_scenes, const SceneParams& sp, const ProblemSet& ps, hipStream_t st);
 void launch_active_rows(int n_slots, const SceneParams& sp, const ProblemSet& ps, double tol, int* out, hipStream_t st);
@@ -192,7 +192,7 @@ size_t qp_lds_fixed_bytes();
 void launch_qp_order(int n_slots, const int* key, int* order, hipStream_t st, int* zero_these = nullptr);      // (zero_these: four ints zeroed on the way, or null)
 void launch_qp_polish_zero(int* counters, hipStream_t st);
 void launch_order_xcd(int n_slots, const int* key, int* order, hipStream_t st);      // (key may be null: the XCD placement alone; n_slots % 8 == 0)
-void launch_qp_reg(int n_slots, const SceneParams& sp, const ProblemSet& ps, const QpTable* tables,
+void launch_qp_reg(int n_slots, const SceneParams& sp, const ProblemSet& ps, QpKernel inst, const QpTable* tables,
                    const SampleSched& sched, size_t lds_bytes, hipStream_t st);
 void launch_qp_polish(int n_slots, const SceneParams& sp, const ProblemSet& ps, const QpTable* tables, const SampleSched& sched, hipStream_t st);
 void launch_qp_presolve(int n_slots, const SceneParams& sp, const ProblemSet& ps, const QpTable* tables, const SampleSched& sched, int* presolved, hipStream_t st);

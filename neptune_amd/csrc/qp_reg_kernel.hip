@@ -1119,11 +1119,11 @@ size_t qp_reg_lds_bytes() {
   return b;
 }
 
-void launch_qp_reg(int n_slots, const SceneParams& sp, const ProblemSet& ps, const QpTable* tables,
+// inst: the instantiation (launch_plan.h: kQpReg <false>, kQpRegCull <true, false>, kQpRegCullPolish <true, true>)
+void launch_qp_reg(int n_slots, const SceneParams& sp, const ProblemSet& ps, QpKernel inst, const QpTable* tables,
                    const SampleSched& sched, size_t lds_bytes, hipStream_t st) {
   if (n_slots <= 0) return;
-  const bool cull = ps.line_far != nullptr && !ps.lines_override;
-  const int which = !cull ? 0 : (ps.polish_z ? 2 : 1);
+  const int which = inst == kQpRegCullPolish ? 2 : inst == kQpRegCull ? 1 : 0;
   static DynLdsAttr attr[3];
   (void)attr[which].ensure(which == 0 ? (const void*)qp_reg_kernel<false, kRegSlots> : which == 1 ? (const void*)qp_reg_kernel<true, kRegSlots, false> : (const void*)qp_reg_kernel<true, kRegSlots, true>, lds_bytes);
   if (which == 2) hipLaunchKernelGGL((qp_reg_kernel<true, kRegSlots, true>), dim3(n_slots), dim3(BS), lds_bytes, st, sp, ps, tables, sched);

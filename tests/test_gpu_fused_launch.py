@@ -5,8 +5,12 @@ is not launched).  Here: the boxes against an exact host reference, the fused se
 headline's inputs, config-5 style inputs with the entangle rows, an active set), the launch order's contract, the counters of every
 round, and the static polygons' boxes across uploads of new polygons between eager rounds, under a captured graph and before a
 capture (the graph contract of nep_batch_set_scene_statics, include/neptune_backend.h).  Every test proves from
-nep_batch_debug_launch_path that it ran the path it is about."""
+nep_batch_debug_launch_path that it ran the path it is about.  Last, the launch topology itself: the table of scripts/launch_paths.py
+against the answers recorded before the launch plan existed (tests/golden/launch_paths.json)."""
 import dataclasses
+import importlib.util
+import json
+import os
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -443,3 +447,37 @@ def test_eager_replan_after_an_upload_and_a_capture_reads_the_new_static_boxes(b
     assert not boxes and not diff, (boxes, diff)
     del g
     bb.close()
+
+
+# ---- H. the launch topology against the recorded one ------------------------------------------------------------------------------
+
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+with open(os.path.join(_ROOT, "tests", "golden", "launch_paths.json")) as _f:
+    _RECORDED = json.load(_f)["cases"]
+
+
+@pytest.fixture(scope="module")
+def launch_paths(be):
+    """scripts/launch_paths.py as a module, and its four base scenes (made once)"""
+    spec = importlib.util.spec_from_file_location("launch_paths", os.path.join(_ROOT, "scripts", "launch_paths.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod, scene.make_scenes(mod.N_AGENTS, mod.N_STATIC, mod.SEEDS, workers=1)
+
+
+def test_launch_path_table_is_the_recorded_one(launch_paths):
+    mod, _ = launch_paths
+    assert [(n, s, v) for n, s, v in mod.cases()] == [(c["name"], c["scenes"], c["variant"]) for c in _RECORDED]
+
+
+@pytest.mark.parametrize("case", _RECORDED, ids=["%s-%d" % (c["name"], c["scenes"]) for c in _RECORDED])
+def test_launch_paths_equal_the_recorded_ones(be, launch_paths, case):
+    """three replans of the case's handle: the launch-path bits, launch_order() is None, the polish counters seen armed and
+    qp_kernel_name() of every call as recorded at the commit before Engine::run followed a plan (8 agents, 2 statics, 1 to 512 scenes:
+    both sides of the 1 024-slot, 2 048-record and 4 096-slot thresholds)"""
+    import torch
+    mod, base = launch_paths
+    got = mod.run_case(be, scene, torch, base, case["scenes"], case["variant"])
+    assert len(got) == len(case["calls"]) == 3
+    for r, (g, w) in enumerate(zip(got, case["calls"])):
+        assert all(g[k] == w[k] for k in mod.ANSWERS), (r, g, w)
