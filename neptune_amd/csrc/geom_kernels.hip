@@ -22,6 +22,7 @@
 #include "../../include/neptune_frontend.h"
 #include "ent_device.h"
 #include "qp_presolve.h"
+#include "hull_chain.h"
 
 namespace nep {
 
@@ -258,8 +259,19 @@ template <int J, int K_> __device__ __forceinline__ void grp_bitonic(double (&kx
   grp_bitonic_merge<J, K_, K_ / 2>(kx, ky, sub);
 }
 
+// 64 bits of the group's eight lanes ORed together, in its lanes 0-3 (the chain lanes are 0 and 1): lanes 0-3 take lanes 4-7 by a row
+// shift, then two quad permutes — DPP moves only (a lane the shift finds nothing for reads 0; lanes 4-7 end with bits of the next group)
+__device__ __forceinline__ unsigned long long grp_or_low(unsigned long long v) {
+  unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
+  lo |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)lo, 0x104, 0xf, 0xf, true); hi |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)hi, 0x104, 0xf, 0xf, true);   // row_shl:4
+  lo |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)lo, 0x4E, 0xf, 0xf, true); hi |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)hi, 0x4E, 0xf, 0xf, true);     // quad_perm [2,3,0,1]
+  lo |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)lo, 0xB1, 0xf, 0xf, true); hi |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)hi, 0xB1, 0xf, 0xf, true);     // quad_perm [1,0,3,2]
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+// cmax: no coordinate of the n points is larger in magnitude (what the chains' skip rule takes its gap from: hull_chain.h)
 template <int J>
-__device__ __forceinline__ int group_hull(int n, const double (&px)[J], const double (&py)[J], double* sxy, int g, int sub,
+__device__ __forceinline__ int group_hull(int n, const double (&px)[J], const double (&py)[J], double cmax, double* sxy, int g, int sub,
                                           bool write, double* __restrict__ out_xy, int cap) {
   constexpr int kGrpPts = J;          // (points per lane in this instantiation: 8 for the inflated hull's <= 64 points, 2 for the <= 16 control points)
   __syncthreads();
@@ -273,50 +285,43 @@ __device__ __forceinline__ int group_hull(int n, const double (&px)[J], const do
   }
   __syncthreads();
   // unique: sorted position p survives if it differs from its predecessor; new position = number of survivors before it
+  // (and on its way the chains' skip flags, hull_chain.h: a kept point's predecessor in the de-duplicated array equals its predecessor
+  // here — duplicates are identical under == — so the pass has both points in hand.  Each lane collects bit pos[j] of its flagged
+  // points; `tiny`: some pair of consecutive x is closer than the rule's proof allows, and the whole hull skips nothing.)
+  const double thr = chain_skip_threshold(cmax);
   double ux[kGrpPts], uy[kGrpPts]; int pos[kGrpPts]; bool keep[kGrpPts];
   int m = 0;
+  unsigned long long flg = 0; unsigned tiny = 0;
 #pragma unroll
   for (int j = 0; j < kGrpPts; j++) {
     const int p = sub + 8 * j;
     ux[j] = 0; uy[j] = 0; keep[j] = false;
-    if (p < n) { ux[j] = sxy[2 * p]; uy[j] = sxy[2 * p + 1]; keep[j] = p == 0 || ux[j] != sxy[2 * p - 2] || uy[j] != sxy[2 * p - 1]; }
+    bool fl = false, tn = false;
+    if (p < n) {
+      ux[j] = sxy[2 * p]; uy[j] = sxy[2 * p + 1]; keep[j] = true;
+      if (p != 0) {
+        const double vx = sxy[2 * p - 2], vy = sxy[2 * p - 1];
+        keep[j] = ux[j] != vx || uy[j] != vy;
+        fl = chain_skip_flag(ux[j], uy[j], vx, vy, thr); tn = chain_gap_tiny(ux[j], vx);
+      }
+    }
     const unsigned bits = (unsigned)(__ballot(keep[j]) >> (8 * g)) & 0xffu;
+    tiny |= (unsigned)(__ballot(tn) >> (8 * g)) & 0xffu;
     pos[j] = m + __popc(bits & ((1u << sub) - 1u));
     m += __popc(bits);
+    flg |= fl ? 1ull << pos[j] : 0ull;       // (a flagged point is a kept one: its y differs)
   }
+  flg = grp_or_low(flg);
+  if (tiny) flg = 0;
   __syncthreads();
 #pragma unroll
   for (int j = 0; j < kGrpPts; j++) { if (keep[j]) { sxy[2 * pos[j]] = ux[j]; sxy[2 * pos[j] + 1] = uy[j]; } }
   __syncthreads();
+  // lane 0 of the group: lower chain (indices ascending); lane 1: upper chain (descending).  The mask is kept in PUSH order — bit i =
+  // the i-th point of the chain's order, i.e. sorted index i for the lower chain and m - 1 - i for the upper one — so that the top of
+  // either stack is the highest set bit.  A point the chain does not visit is a bit that is never set.
   unsigned long long mask = 0;
-  if (sub < 2 && m >= 2) {          // lane 0 of the group: lower chain (indices ascending); lane 1: upper chain (descending)
-    const bool lower = sub == 0;
-    int kc = 0;
-    int i1 = 0, i2 = 0;                      // push indices of the top entry and of the one under it (valid from kc = 1 / kc = 2 on)
-    double ax = 0, ay = 0, bx = 0, by = 0;   // the two top entries
-    for (int i = 0; i < m; i++) {
-      const double2 c = *(const double2*)(sxy + 2 * (lower ? i : m - 1 - i));
-      const double x = c.x, y = c.y;
-      // (the mask is kept in PUSH order — bit i = the i-th point this chain visited, i.e. sorted index i for the lower chain and
-      // m - 1 - i for the upper one — so that the top of either stack is the highest set bit)
-      // The kernel is bound by the instructions its waves issue (four waves to a SIMD): the two top indices
-      // travel in registers, so that a pop clears a known bit and finds the entry under the new top with ONE 64-bit
-      // count-leading-zeros (three of them, each five instructions, when every pop searched the mask for the top, the new top and the
-      // entry under it: 0.1006 -> 0.0958 ms per 65 536 hulls).  Same cross products on the same operands in the same order.
-      while (kc >= 2 && cross3(ax, ay, bx, by, x, y) <= 0.0) {
-        mask &= ~(1ull << i1);
-        kc--; bx = ax; by = ay; i1 = i2;
-        if (kc >= 2) {
-          i2 = 63 - __clzll((long long)(mask & ((1ull << i2) - 1ull)));      // the highest entry under the new top
-          const double2 a = *(const double2*)(sxy + 2 * (lower ? i2 : m - 1 - i2));
-          ax = a.x; ay = a.y;
-        }
-      }
-      mask |= 1ull << i; kc++;
-      ax = bx; ay = by; bx = x; by = y;
-      i2 = i1; i1 = i;
-    }
-  }
+  if (sub < 2 && m >= 2) mask = chain_walk(sxy, m, sub == 0, chain_todo(flg, m, sub == 0));
   const unsigned long long L = __shfl(mask, 8 * g), U = __shfl(mask, 8 * g + 1);
   const int kl = __popcll(L), ku = __popcll(U);
   const int k = m >= 2 ? kl + ku - 2 : m;
@@ -461,33 +466,39 @@ __global__ __launch_bounds__(64) void hull_group_kernel(const nep_traj_rec* __re
       } else { px[j] = cpx[p]; py[j] = cpy[p]; }
     }
   }
-  if (box) {
-    // The box of the hull's vertices is the box of the points it is the hull of (an extreme point is a vertex), and x -> x +- dx is monotone
-    // in floating point too: min over the corners (x - dx) = (min x) - dx.  So: extremes of the control points over the group's lanes
-    // (two points a lane, three exchange steps), then the corner offsets — the same four doubles fe_box_kernel reads off the vertices
-    // (a hull of more than kHullV vertices is cut and flagged either way).
-    double x0 = NEP_INF, x1 = -NEP_INF, y0 = NEP_INF, y1 = -NEP_INF;
+  // The box of the hull's vertices is the box of the points it is the hull of (an extreme point is a vertex), and x -> x +- dx is monotone
+  // in floating point too: min over the corners (x - dx) = (min x) - dx.  So: extremes of the control points over the group's lanes
+  // (two points a lane, three exchange steps), then the corner offsets — the same four doubles fe_box_kernel reads off the vertices
+  // (a hull of more than kHullV vertices is cut and flagged either way).  Made without box_out too: the chains' skip rule takes its
+  // gap from the largest magnitude among them (hull_chain.h).
+  double x0 = NEP_INF, x1 = -NEP_INF, y0 = NEP_INF, y1 = -NEP_INF;
 #pragma unroll
-    for (int j = 0; j < 2; j++) { const int p = sub + 8 * j; if (p < np0) { const double x = cpx[p], y = cpy[p]; x0 = fmin(x0, x); x1 = fmax(x1, x); y0 = fmin(y0, y); y1 = fmax(y1, y); } }
-    // (towards the group's lane 0, which writes: lanes 0-3 take lanes 4-7 by a row shift, then two quad permutes — DPP moves only)
+  for (int j = 0; j < 2; j++) { const int p = sub + 8 * j; if (p < np0) { const double x = cpx[p], y = cpy[p]; x0 = fmin(x0, x); x1 = fmax(x1, x); y0 = fmin(y0, y); y1 = fmax(y1, y); } }
+  {
+    // (towards the group's lanes 0-3 — lane 0 writes, lanes 0 and 1 walk the chains: lanes 0-3 take lanes 4-7 by a row shift, then two quad permutes — DPP moves only)
     auto shl4 = [](double v) { return __hiloint2double(__builtin_amdgcn_mov_dpp(__double2hiint(v), 0x104, 0xf, 0xf, false), __builtin_amdgcn_mov_dpp(__double2loint(v), 0x104, 0xf, 0xf, false)); };      // row_shl:4
     x0 = fmin(x0, shl4(x0)); x1 = fmax(x1, shl4(x1)); y0 = fmin(y0, shl4(y0)); y1 = fmax(y1, shl4(y1));
     x0 = fmin(x0, grp_xor<2>(x0)); x1 = fmax(x1, grp_xor<2>(x1)); y0 = fmin(y0, grp_xor<2>(y0)); y1 = fmax(y1, grp_xor<2>(y1));
     x0 = fmin(x0, grp_xor<1>(x0)); x1 = fmax(x1, grp_xor<1>(x1)); y0 = fmin(y0, grp_xor<1>(y0)); y1 = fmax(y1, grp_xor<1>(y1));
-    if (act && sub == 0) {
-      if (np0 <= 0) { box[0] = NEP_INF; box[1] = -NEP_INF; box[2] = NEP_INF; box[3] = -NEP_INF; }
-      else if (inflate) { box[0] = x0 - dx; box[1] = x1 + dx; box[2] = y0 - dy; box[3] = y1 + dy; }
-      else { box[0] = x0; box[1] = x1; box[2] = y0; box[3] = y1; }
-    }
   }
-  int k = group_hull<kGrpPts>(np, px, py, s_sxy[g], g, sub, act, hull_xy + out * kHullV * 2, kHullV);
+  if (box && act && sub == 0) {
+    if (np0 <= 0) { box[0] = NEP_INF; box[1] = -NEP_INF; box[2] = NEP_INF; box[3] = -NEP_INF; }
+    else if (inflate) { box[0] = x0 - dx; box[1] = x1 + dx; box[2] = y0 - dy; box[3] = y1 + dy; }
+    else { box[0] = x0; box[1] = x1; box[2] = y0; box[3] = y1; }
+  }
+  // (every lane of the group makes flags, so every lane needs the magnitude: lanes 0-3 hold the group's extremes, lanes 4-7 take theirs
+  // from them by a row shift written to the upper bank of each eight alone)
+  double cm0 = fmax(fmax(fabs(x0), fabs(x1)), fmax(fabs(y0), fabs(y1)));
+  cm0 = __hiloint2double(__builtin_amdgcn_update_dpp(__double2hiint(cm0), __double2hiint(cm0), 0x114, 0xf, 0xa, false),
+                         __builtin_amdgcn_update_dpp(__double2loint(cm0), __double2loint(cm0), 0x114, 0xf, 0xa, false));      // row_shr:4, banks 1 and 3
+  int k = group_hull<kGrpPts>(np, px, py, inflate ? cm0 + fmax(fabs(dx), fabs(dy)) : cm0, s_sxy[g], g, sub, act, hull_xy + out * kHullV * 2, kHullV);
   if (k > kHullV) { k = kHullV; if (act && sub == 0 && flags) atomicOr(flags, NEP_FLAG_HULL_OVERFLOW); }
   if (act && sub == 0) hull_nv[out] = k;
   if (hull0_nv) {
     double qx[2], qy[2];              // (<= 16 control points: two per lane)
 #pragma unroll
     for (int j = 0; j < 2; j++) { const int p = sub + 8 * j; qx[j] = p < np0 ? cpx[p] : 0; qy[j] = p < np0 ? cpy[p] : 0; }
-    int k0 = group_hull<2>(np0, qx, qy, s_sxy[g], g, sub, act, hull0_xy + out * 2, 1);      // only col(0) is read (:722-734)
+    int k0 = group_hull<2>(np0, qx, qy, cm0, s_sxy[g], g, sub, act, hull0_xy + out * 2, 1);      // only col(0) is read (:722-734)
     if (k0 > kHullV) k0 = kHullV;
     if (act && sub == 0) hull0_nv[out] = k0;
   }
