@@ -23,14 +23,20 @@
  *                       ramp from A's height state to the goal height (neptune.cpp:1727-1810; as there,
  *                       the first three control points are placed for a clamped basis but evaluated with
  *                       the uniform one, so only a start at rest is reproduced exactly)
- * What differs — this is a level-synchronous BEAM over the same lattice, not the reference's A*:
+ * What differs — the default search is a level-synchronous BEAM over the same lattice, not the reference's A*:
  *   the reference's open list is a wall-clock-bounded best-first search whose expansion order is
  *   shuffled with a time seed (:321-322, :1462-1463) and whose closed-set update toggles with a call
- *   counter (:1190-1203); it is not reproducible even against itself.  Here depth d keeps the
+ *   counter (:1190-1203); it is not reproducible even against itself.  In the beam depth d keeps the
  *   beam_width best children (ties by parent rank, then lattice index), a voxel holds one node per
  *   depth and is closed to later depths, the depth is num_pol, and without reaching the goal the best
  *   node of the last depth is returned.  The deterministic rule is stated in oracle/ and the kernel
  *   matches it bit for bit.
+ * The reference's own strategy is available next to it (nep_batch_set_fe_astar, nep_batch_frontend_astar
+ *   below): best-first on g + bias*h over a binary heap, unbounded depth, one node per voxel with the
+ *   in-place update of an open node on every second such event, the "nearest the start" fallback node —
+ *   with the two things that make the reference irreproducible turned into parameters (the lattice
+ *   order, and a budget of pops in place of the wall clock).  Bit-identical to oracle/'s
+ *   orc_frontend_astar.  Entangle check off only: an entangle-aware A* has no oracle yet.
  */
 #ifndef NEPTUNE_FRONTEND_H_
 #define NEPTUNE_FRONTEND_H_
@@ -111,7 +117,8 @@ typedef struct nep_fe_result {
   int32_t n_collision_free;       /* ... and the collision tests                                   */
   int32_t goal_occupied;          /* setUp's goal_occupied_ (:210-226)                             */
   int32_t _pad;                   /* entangle check on: bit 3 = the pool of big records ran out (ent_overflow); bits 8
-                                     and up = children of this search whose state went into a big record; else 0    */
+                                     and up = children of this search whose state went into a big record; nep_batch_frontend_astar:
+                                     bit 4 = the search ran into a node pool smaller than the reference's; else 0    */
   double cost;                    /* g + bias*h of the returned node                               */
   double dist_to_goal;
   int32_t n_entangled;            /* children pruned by entanglesWithOtherAgents (entangle check on)        */
@@ -130,6 +137,43 @@ typedef struct nep_fe_result {
 int nep_batch_frontend(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_traj_rec* d_committed,
                        const nep_fe_start* d_start, nep_guess* d_guess, nep_fe_result* d_result,
                        void* stream);
+
+/* ---- The reference's best-first search (KinodynamicSearch::run, kinodynamic_search.cpp:1629-1827) -------------------------------
+ * One wave per slot runs the search orc_frontend_astar (oracle/neptune_oracle.c) states, entangle check off:
+ *   root expansion       without the velocity-control-point test (the reference's initial overload); later ones with it
+ *   lattice order        children are visited in the order q = 0 .. num_samples^2 - 1, child q being lattice point order[q]
+ *                        (jx = order[q] / num_samples, jy = order[q] % num_samples); the reference shuffles that list
+ *   open list            a binary heap with libstdc++'s push_heap / pop_heap mechanics under CompareCost
+ *                        (|cl - cr| < 1e-5 ? h_l > h_r : cl > cr), so ties pop as they do there
+ *   voxel table          one node per voxel, the first insert wins; a child that hits an open node of its own index
+ *                        overwrites it in place on every second such event when its g + bias*h is smaller, and the heap is
+ *                        NOT re-ordered (:1190-1203); any other child of an occupied voxel is dropped
+ *   pop                  budget first (max_pops pops: NEP_FE_DEPTH_REACHED), then the collision test of the node (:1514-1553),
+ *                        the closest-so-far rule (:1683-1690), the goal test, the expansion
+ *   result               the goal node, else the closest-so-far node; none: NEP_FE_NO_SOLUTION, K = 0.  The path's nodes of
+ *                        index <= num_pol are the guess, z as in nep_batch_frontend.  nep_fe_result: n_children = pops,
+ *                        n_feasible = nodes created, depth = index of the returned node (it may exceed num_pol),
+ *                        n_collision_free = n_entangled = ent_overflow = 0, cost / dist_to_goal of the returned node
+ *   pad_hold             as in nep_batch_frontend (the oracle's A* ignores it): segments beyond the plan hold the returned
+ *                        node's end point, K = num_pol
+ * nep_batch_set_fe_astar   the budget, the order and the per-slot pools.  Eager (it allocates and uploads): not capturable.
+ *   max_pops >= 0; order: host, n_order = num_samples^2 entries, a permutation of 0 .. n_order - 1 (else NEP_E_ARG), or NULL:
+ *   lattice order 0, 1, 2, ...  max_nodes: nodes per slot, 2 .. NEP_FE_ASTAR_MAX_NODES; 0 = min(NEP_FE_ASTAR_MAX_NODES,
+ *   25 * (max_pops + 1) + 1), which no search of that budget can fill.  The reference stops creating nodes at 19 999
+ *   (node_num_max_, kinodynamic_search.hpp:345); a smaller pool is a budget in the same sense — an expansion stops creating
+ *   nodes at max_nodes - 1 and the search goes on with what it has — and a search cut that way says so: bit 4 of
+ *   nep_fe_result._pad, and NEP_E_CAP from nep_batch_check.  Nothing is written past a pool.  Device memory per slot:
+ *   max_nodes * (NEP_FE_ASTAR_NODE_BYTES + 4) bytes of nodes and heap plus 12 bytes per entry of the voxel table (the power of
+ *   two at or above 2 * max_nodes): 4.1 MB at 20 000 nodes, 0.5 MB at the default of max_pops = 100.
+ * nep_batch_frontend_astar asynchronous on `stream`, allocates nothing, capturable; arguments, hulls, active set
+ *   (nep_batch_set_active: an inactive slot gets what nep_batch_frontend gives it), agent shards and several scenes per launch as
+ *   nep_batch_frontend.  cfg->beam_width is not read.  NEP_E_STATE before nep_batch_set_fe_astar; NEP_E_ARG with
+ *   cfg->enable_entangle != 0, or when an order is set and cfg->num_samples^2 != n_order.                                        */
+#define NEP_FE_ASTAR_MAX_NODES 20000
+#define NEP_FE_ASTAR_NODE_BYTES 160
+int nep_batch_set_fe_astar(nep_batch_t* h, int32_t max_pops, int32_t max_nodes, const int32_t* order, int32_t n_order);
+int nep_batch_frontend_astar(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_traj_rec* d_committed, const nep_fe_start* d_start,
+                             nep_guess* d_guess, nep_fe_result* d_result, void* stream);
 
 /* The same against all-gathered hull blocks (multi-GPU rounds, include/neptune_backend.h:
  * nep_batch_hulls -> all-gather -> nep_batch_frontend_hulls -> nep_batch_replan_hulls).            */

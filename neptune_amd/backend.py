@@ -318,6 +318,20 @@ class BatchBackend:
         check(lib().nep_batch_frontend_hulls(self._h, C.byref(fe_cfg), d_blocks.data_ptr(), self.N // self.n_local, d_start.data_ptr(),
                                              d_guess.data_ptr(), d_result.data_ptr() if d_result is not None else None, st.cuda_stream))
 
+    # ---- the reference's best-first search (include/neptune_frontend.h: nep_batch_set_fe_astar / nep_batch_frontend_astar) ----
+    def set_fe_astar(self, max_pops, max_nodes=0, order=None):
+        """Budget (pops per search), node pool per slot (0: the default, which no search of that budget fills) and lattice order
+        (a permutation of range(num_samples ** 2), None: 0, 1, 2, ...) of frontend_astar.  Allocates: call it before any capture."""
+        od = np.ascontiguousarray(order, dtype=np.int32).reshape(-1) if order is not None else None
+        check(lib().nep_batch_set_fe_astar(self._h, int(max_pops), int(max_nodes), abi.iptr(od) if od is not None else None,
+                                           len(od) if od is not None else 0))
+
+    def frontend_astar(self, fe_cfg, d_committed, d_start, d_guess, d_result=None, stream=None):
+        """frontend() with the reference's best-first search in place of the beam (one wave per slot; fe_cfg.beam_width is not read)"""
+        st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        check(lib().nep_batch_frontend_astar(self._h, C.byref(fe_cfg), d_committed.data_ptr(), d_start.data_ptr(), d_guess.data_ptr(),
+                                             d_result.data_ptr() if d_result is not None else None, st.cuda_stream))
+
     # ---- entangle check on (include/neptune_frontend.h) ------------------------------------------------------------
     def set_static_reps(self, reps, longest, scene=-1):
         """staticObsRep_ [S][2][2] and staticObsLongestDist_ [S][2] (nep_batch_set_static_reps)"""

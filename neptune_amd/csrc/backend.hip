@@ -159,6 +159,9 @@ struct Engine {
   DevBuf<int> d_fe_order, d_fe_order_key; DevBuf<float> d_fe_us; bool fe_history = false, fe_lpt = true;      // the same for the front end's searches (frontend_kernel)
   DevBuf<int> d_order, d_order_key; bool have_history = false, lpt = true;   // QP workgroups launched longest-expected-first (order_kernel)
   const int* active = nullptr;       // the active set (nep_batch_set_active): device [scenes][N], or null
+  // the best-first front end (nep_batch_set_fe_astar): per-slot node pools, heaps and voxel tables; the budget and the lattice order
+  DevBuf<unsigned char> d_as_nodes; DevBuf<int> d_as_heap, d_as_val, d_as_order; DevBuf<unsigned long long> d_as_key;
+  bool as_ready = false; int as_max_pops = 0, as_pool = 0, as_tab = 0, as_n_order = 0;
   DevBuf<int> d_act, d_fe_act;       // [slots + 1] compacted active slots + count (active_list_kernel): the QP launches', the front end's
   ListBuf d_track_lsave;      // nep_batch_track_ent_lists: the same scratch in the list form, of the largest cap seen
   DevBuf<nep_fe_ent_state> d_track_save; DevBuf<int> d_track_flags; DevBuf<double> d_track_pos;      // nep_batch_track_ent: per-slot scratch, flags when the caller passes none, the positions of the largest call
@@ -1206,6 +1209,57 @@ int nep_batch_frontend_hulls(nep_batch_t* h, const nep_fe_cfg* cfg, const void* 
   if (!fe_cfg_ok(cfg)) return fail(NEP_E_ARG, "bad front-end configuration");
   h->fe_committed = nullptr;
   return run_frontend(h, ps, *cfg, d_start, d_guess, d_result, nullptr, stream);
+}
+
+// ---- the reference's best-first search (fe_astar.h) ----
+int nep_batch_set_fe_astar(nep_batch_t* h, int32_t max_pops, int32_t max_nodes, const int32_t* order, int32_t n_order) {
+  if (!h) return fail(NEP_E_ARG, "null handle");
+  if (max_pops < 0) return fail(NEP_E_ARG, "max_pops must not be negative");
+  if (max_nodes != 0 && (max_nodes < 2 || max_nodes > NEP_FE_ASTAR_MAX_NODES)) return fail(NEP_E_ARG, "max_nodes must be 0 or 2 .. NEP_FE_ASTAR_MAX_NODES");
+  if (order) {
+    bool square = false;
+    for (int ns = 2; ns <= NEP_FE_MAX_SAMPLES; ns++) square |= n_order == ns * ns;
+    if (!square) return fail(NEP_E_ARG, "n_order must be num_samples^2 of a lattice (4, 9, 16 or 25)");
+    bool seen[NEP_FE_MAX_SAMPLES * NEP_FE_MAX_SAMPLES] = {};
+    for (int q = 0; q < n_order; q++) {
+      if (order[q] < 0 || order[q] >= n_order || seen[order[q]]) return fail(NEP_E_ARG, "order is not a permutation of 0 .. n_order - 1");
+      seen[order[q]] = true;
+    }
+  }
+  Engine& E = h->eng;
+  // (no search of max_pops pops creates more than 25 nodes per expansion, the root's included; + 1 because node creation stops one short of the pool)
+  const long long dflt = 25LL * ((long long)max_pops + 1) + 1;
+  const int pool = max_nodes ? max_nodes : (int)std::min<long long>(NEP_FE_ASTAR_MAX_NODES, dflt);
+  int tab = 64; while (tab < 2 * pool) tab *= 2;
+  E.as_ready = false;
+  if (int e = E.d_as_nodes.ensure((size_t)h->slots * pool * NEP_FE_ASTAR_NODE_BYTES)) return e;
+  if (int e = E.d_as_heap.ensure((size_t)h->slots * pool)) return e;
+  if (int e = E.d_as_key.ensure((size_t)h->slots * tab)) return e;
+  if (int e = E.d_as_val.ensure((size_t)h->slots * tab)) return e;
+  if (int e = E.d_as_order.ensure((size_t)NEP_FE_MAX_SAMPLES * NEP_FE_MAX_SAMPLES)) return e;
+  if (order) HIPCHK(hipMemcpy(E.d_as_order.p, order, (size_t)n_order * sizeof(int), hipMemcpyHostToDevice));
+  E.as_max_pops = max_pops; E.as_pool = pool; E.as_tab = tab; E.as_n_order = order ? n_order : 0;
+  E.as_ready = true;
+  return 0;
+}
+
+int nep_batch_frontend_astar(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_traj_rec* d_committed, const nep_fe_start* d_start,
+                             nep_guess* d_guess, nep_fe_result* d_result, void* stream) {
+  if (!h || !cfg || !d_committed || !d_start || !d_guess) return fail(NEP_E_ARG, "null argument");
+  Engine& E = h->eng;
+  if (!E.as_ready) return fail(NEP_E_STATE, "nep_batch_frontend_astar: call nep_batch_set_fe_astar first (it allocates the searches' pools)");
+  if (cfg->enable_entangle) return fail(NEP_E_ARG, "nep_batch_frontend_astar: the best-first search has no entangle check (enable_entangle must be 0)");
+  if (!(cfg->num_samples >= 2 && cfg->num_samples <= NEP_FE_MAX_SAMPLES && cfg->voxel_size > 0.0 && cfg->j_max > 0.0)) return fail(NEP_E_ARG, "bad front-end configuration");
+  if (E.as_n_order && cfg->num_samples * cfg->num_samples != E.as_n_order) return fail(NEP_E_ARG, "nep_batch_frontend_astar: num_samples^2 differs from the n_order of nep_batch_set_fe_astar");
+  const ProblemSet ps = round_set(h);
+  h->fe_committed = d_committed;
+  launch_hulls_ts(d_committed, h->cfg.n_scenes, h->cfg.num_agents, &d_start->t_start, (long)sizeof(nep_fe_start), E.sp, ps, (hipStream_t)stream, grouped_hulls(E.sp, h->cfg.n_scenes, h->cfg.num_agents));
+  FeAstarArgs aa{};
+  aa.max_pops = E.as_max_pops; aa.pool = E.as_pool; aa.tab_cap = E.as_tab; aa.order = E.as_n_order ? E.d_as_order.p : nullptr;
+  aa.nodes = E.d_as_nodes.p; aa.heap = E.d_as_heap.p; aa.tab_key = E.d_as_key.p; aa.tab_val = E.d_as_val.p;
+  launch_frontend_astar(h->slots, E.sp, ps, *cfg, aa, d_start, d_guess, d_result, (hipStream_t)stream, E.d_fe_act.p);
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 
 int nep_batch_set_active(nep_batch_t* h, const int32_t* d_active) {
@@ -2360,6 +2414,7 @@ int nep_batch_check(nep_batch_t* h, void* stream) {
   if (flags & NEP_FLAG_ENT_TRACK) return fail(NEP_E_CAP, "nep_batch_track_ent: a tether's state outgrew NEP_FE_ENT_CAP crossings, NEP_MAX_BEND - 1 bend points or 32 new crossings in one step (the step was dropped), or a state handed in was malformed");
   if (flags & NEP_FLAG_FLEET) return fail(NEP_E_CAP, "nep_batch_fleet_commit: an accepted plan or composed trajectory would have outgrown the ring (ring_cap states), NEP_TRAJ_MAX_SEG intervals, or A was already flown (the slot kept its plan: outcome NEP_FLEET_CAP, flags in nep_batch_fleet_state)");
   if (flags & NEP_FLAG_MISSION) return fail(NEP_E_CAP, "nep_batch_fleet_mission: a draw found no goal among max_attempts candidates (the slot kept its goal: NEP_FLEET_FLAG_GOAL in nep_batch_fleet_state's flags, no_goal in nep_batch_fleet_mission_state's counts)");
+  if (flags & NEP_FLAG_FE_ASTAR_POOL) return fail(NEP_E_CAP, "nep_batch_frontend_astar: a search ran into its node pool (it stopped creating nodes there: bit 4 of nep_fe_result._pad): nep_batch_set_fe_astar's max_nodes");
   if (flags & NEP_FLAG_ENT_BETA) return fail(NEP_E_ARG, "an entangle state passed to the front end has a non-zero beta for an agent crossing (the reference's calculateBetaForCase makes it 0.0)");
   if (flags & NEP_FLAG_HULL_OVERFLOW) return fail(NEP_E_CAP, "an interval overlaps more than NEP_HULL_MAX_CP/4 committed segments (or its hull has more than NEP_HULL_MAX_V vertices)");
   return 0;

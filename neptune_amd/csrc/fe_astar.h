@@ -1,0 +1,309 @@
+// fe_astar.h — the reference's best-first search as a device kernel.  Included by geom_kernels.hip, inside
+// namespace nep, below the beam front end: it uses that file's fe_child, fe_lattice_fill, fe_pos_cps, gjk_collision, hull_ref,
+// fe_initial_z and skipped_fe_kernel, and that object's -ffp-contract=off.
+//
+// KinodynamicSearch::run (kinodynamic_search.cpp:1629-1827) as oracle/neptune_oracle.c restates it (orc_frontend_astar, entangle
+// check off): best-first on g + bias h over a binary heap with libstdc++'s push_heap / pop_heap mechanics, one node per voxel
+// (the first insert wins), the in-place update of an open node of the same index on every second such event, the
+// closest-so-far fallback node, a pop budget in place of the wall clock and the lattice order as a parameter.  Bit-identical to
+// the oracle.
+//
+// One wave per search.  What is parallel: the ns^2 lattice children of an expansion (one lane each: fe_child, the child's
+// voxel lookup with what the commit reads of the voxel's holder, the child's voxel group) and the popped node's collision test
+// (one lane per obstacle, a ballot).  What is serial, on lane 0: the heap and the commit of an expansion's surviving children in
+// lattice order — siblings see each other through the voxel table, the update toggle counts events in that order and the node
+// cap cuts the expansion at a child.
+// Per slot, in global memory: the node pool (160 B per node), the heap beyond its first kAsHeapLds entries (those are in LDS)
+// and the voxel -> node table (open addressing, a power of two >= twice the pool; the result does not depend on its hashing).
+#pragma once
+
+constexpr int kAsMaxNodes = 20000;      // node_num_max_ (kinodynamic_search.hpp:345): an expansion stops creating nodes at kAsMaxNodes - 1
+constexpr int kAsHeapLds = 2048;        // heap entries kept in LDS (levels 0-10 of the heap: every sift starts or ends there)
+constexpr int kAsNC = NEP_FE_MAX_SAMPLES * NEP_FE_MAX_SAMPLES;
+constexpr int kAsPadPool = 16;          // nep_fe_result._pad bit 4: the search ran into a pool smaller than kAsMaxNodes
+
+// (h and cost first: the heap's comparisons read just these two, one 16-byte load)
+struct AsNode { double h, cost, g, end[6], cx[4], cy[4]; int prev, state, index, vx, vy, _pad; };
+static_assert(sizeof(AsNode) == NEP_FE_ASTAR_NODE_BYTES, "AsNode's size is part of nep_batch_set_fe_astar's memory contract");
+
+// CompareCost(left, right) (kinodynamic_search.hpp:163-179)
+__device__ __forceinline__ bool as_comp(double cl, double hl, double cr, double hr) { return fabs(cl - cr) < 1e-5 ? hl > hr : cl > cr; }
+
+struct AsHeap {
+  int* lds; int* glb;
+  __device__ __forceinline__ int get(int i) const { return i < kAsHeapLds ? lds[i] : glb[i]; }
+  __device__ __forceinline__ void set(int i, int v) const { if (i < kAsHeapLds) lds[i] = v; else glb[i] = v; }
+};
+// std::__push_heap(first, hole, top = 0, value); the comparisons read the nodes' CURRENT costs (an open node updated in place
+// stays where it is in the heap, as in the reference)
+__device__ __forceinline__ void as_push_heap(const AsHeap& hp, const AsNode* pool, int hole, int value, double vc, double vh) {
+  while (hole > 0) {
+    const int parent = (hole - 1) / 2, pn = hp.get(parent);
+    if (!as_comp(pool[pn].cost, pool[pn].h, vc, vh)) break;
+    hp.set(hole, pn); hole = parent;
+  }
+  hp.set(hole, value);
+}
+// top(); pop(): std::pop_heap + pop_back
+__device__ __forceinline__ int as_pop(const AsHeap& hp, const AsNode* pool, int& heap_n) {
+  const int top = hp.get(0), len = heap_n - 1, value = hp.get(len);
+  int hole = 0, second = 0;
+  while (second < (len - 1) / 2) {        // std::__adjust_heap(first, 0, len, value)
+    second = 2 * (second + 1);
+    const int a = hp.get(second), b = hp.get(second - 1);
+    const double ah = pool[a].h, ac = pool[a].cost, bh = pool[b].h, bc = pool[b].cost;
+    const bool left = as_comp(ac, ah, bc, bh);
+    if (left) second--;
+    hp.set(hole, left ? b : a); hole = second;
+  }
+  if ((len & 1) == 0 && second == (len - 2) / 2) { second = 2 * (second + 1); hp.set(hole, hp.get(second - 1)); hole = second - 1; }
+  if (len > 0) as_push_heap(hp, pool, hole, value, pool[value].cost, pool[value].h);
+  heap_n = len;
+  return top;
+}
+
+__device__ __forceinline__ unsigned long long as_key(int vx, int vy) { return ((unsigned long long)(unsigned)vx << 32) | (unsigned long long)(unsigned)vy; }
+// node of voxel `key`, or -1; pos: where it is / where it would go (the table is never more than half full: the walk ends)
+__device__ __forceinline__ int as_find(const unsigned long long* tkey, const int* tval, int mask, unsigned long long key, int start, int& pos) {
+  int p = start;
+  for (int it = 0; it <= mask; it++, p = (p + 1) & mask) {
+    const int v = tval[p];
+    if (v < 0 || tkey[p] == key) { pos = p; return v < 0 ? -1 : v; }
+  }
+  pos = -1; return -1;
+}
+
+__global__ __launch_bounds__(64) void frontend_astar_kernel(SceneParams sp, ProblemSet ps, nep_fe_cfg fc, FeAstarArgs aa, const nep_fe_start* __restrict__ starts,
+                                                            nep_guess* __restrict__ guess_out, nep_fe_result* __restrict__ res_out) {
+  __shared__ int s_heap[kAsHeapLds];
+  __shared__ double s_ch[kAsNC][17];      // a child of the expansion at hand: end state [6], cx [4], cy [4], g, h, cost
+  __shared__ double s_lat[4 * NEP_FE_MAX_SAMPLES];
+  __shared__ double s_hcost[kAsNC];      // per voxel group (indexed by its first child): g + bias h of the voxel's holder, kept current through the commit
+  __shared__ int s_vx[kAsNC], s_vy[kAsNC], s_f[kAsNC], s_pos[kAsNC], s_hst[kAsNC], s_hidx[kAsNC], s_new[kAsNC], s_grp[kAsNC];
+  const int lane = threadIdx.x;
+  if (ps.fe_count && (int)blockIdx.x >= *ps.fe_count) return;      // (an active set: fe_order is the list of active slots)
+  const int slot = ps.fe_order ? ps.fe_order[blockIdx.x] : (int)blockIdx.x, scene = slot / sp.n_local, own = sp.first_local + (slot % sp.n_local);
+  const int N = sp.num_agents, S = sp.n_static, ns = fc.num_samples, NC = ns * ns, D = sp.num_pol;
+  const int cap = aa.pool, mask = aa.tab_cap - 1;
+  AsNode* const pool = (AsNode*)aa.nodes + (size_t)slot * cap;
+  const AsHeap hp{s_heap, aa.heap + (size_t)slot * cap};
+  unsigned long long* const tkey = aa.tab_key + (size_t)slot * aa.tab_cap;
+  int* const tval = aa.tab_val + (size_t)slot * aa.tab_cap;
+  const nep_fe_start* st = starts + slot;
+  const double gx = st->goal[0], gy = st->goal[1];
+  const double bx = ps.pb[2 * own], by = ps.pb[2 * own + 1];
+  const double init[6] = {st->pos[0], st->pos[1], st->vel[0], st->vel[1], st->accel[0], st->accel[1]};
+#ifdef NEP_PROFILE_PHASES
+  long long tph[6] = {0, 0, 0, 0, 0, 0}; long long tlast = clock64();      // pop, GJK, fe_child + lookup, commit + push, (setup), (result)
+#define AS_TICK(k) do { const long long t_ = clock64(); tph[k] += t_ - tlast; tlast = t_; } while (0)
+#else
+#define AS_TICK(k) do { } while (0)
+#endif
+  for (int k = lane; k <= mask; k += 64) tval[k] = -1;
+  if (lane < NEP_FE_MAX_SAMPLES) fe_lattice_fill(sp, fc, s_lat, lane);
+  const FeLattice lat{s_lat, s_lat + NEP_FE_MAX_SAMPLES, s_lat + 2 * NEP_FE_MAX_SAMPLES, s_lat + 3 * NEP_FE_MAX_SAMPLES};
+  // goal_occupied_ (setUp :210-226)
+  bool occ = false;
+  {
+    Pts4 G; const double r = 0.5;
+    G.x[0] = gx + r; G.y[0] = gy + r; G.x[1] = gx + r; G.y[1] = gy - r; G.x[2] = gx - r; G.y[2] = gy + r; G.x[3] = gx - r; G.y[3] = gy - r;
+    for (int j = lane; j < N; j += 64) {
+      if (j == own) continue;
+      const HullRef hr = hull_ref(ps, sp.n_hull, scene, j);
+      const long h = hr.e * sp.num_pol + (D - 1);
+      const int nv = blk(ps.hull_nv, hr.boff)[h];
+      if (nv > 0 && gjk_collision(nv, blk(ps.hull_xy, hr.boff) + h * kHullV * 2, G)) occ = true;
+    }
+  }
+  const bool goal_occupied = __ballot(occ) != 0ull;
+  __syncthreads();
+
+  // what lane 0 keeps (the other lanes get what they need of it by __shfl): the heap's length, nodes created, the update toggle
+  int heap_n = 0, used = 0, ran_trigger = 0, capped = 0;
+  int status = NEP_FE_EMPTY, cur = -1, closest = -1, pops = 0;
+  double smallest = 1.7976931348623157e308;
+  AS_TICK(4);
+
+  // both expandAndAddToQueue overloads (:1045-1228, :1240-1385): e_cur < 0 = from the initial state
+  auto expand = [&](int e_cur, const double* pe, double pg, int pindex) {
+    const bool first = e_cur < 0;
+    // (1) every lane its child, the node that holds the child's voxel before this expansion (with what the commit reads of it) and
+    // the child's voxel group: the first child of this expansion with the same voxel
+    int my_f = -2, my_vx = 0, my_vy = 0;
+    if (lane < NC) {
+      const int comb = aa.order ? aa.order[lane] : lane;
+      FeChild ch;
+      if (fe_child(sp, fc, lat, pe, pg, first, comb / ns, comb % ns, gx, gy, bx, by, ch)) {
+        double* o = s_ch[lane];
+#pragma unroll
+        for (int i = 0; i < 6; i++) o[i] = ch.e[i];
+#pragma unroll
+        for (int i = 0; i < 4; i++) { o[6 + i] = ch.cx[i]; o[10 + i] = ch.cy[i]; }
+        o[14] = ch.g; o[15] = ch.dist; o[16] = ch.f;
+        my_vx = ch.vx; my_vy = ch.vy;
+        s_vx[lane] = ch.vx; s_vy[lane] = ch.vy;
+        const unsigned long long key = as_key(ch.vx, ch.vy);
+        int pos = -1;
+        my_f = as_find(tkey, tval, mask, key, (int)(fe_hash((long long)key) & (unsigned)mask), pos);
+        s_pos[lane] = pos;
+        // (state and index do not change during the commit below; the cost only by an update of that commit, which keeps the group's entry current)
+        if (my_f >= 0) { s_hst[lane] = pool[my_f].state; s_hidx[lane] = pool[my_f].index; s_hcost[lane] = pool[my_f].cost; }
+      }
+      s_f[lane] = my_f; s_new[lane] = -1;
+    }
+    {
+      int grp = lane;
+      for (int r = 0; r < NC; r++) {      // (r is wave-uniform: the shuffles are lane reads)
+        const int fr = __shfl(my_f, r), xr = __shfl(my_vx, r), yr = __shfl(my_vy, r);
+        if (r < lane && grp == lane && fr != -2 && xr == my_vx && yr == my_vy) grp = r;
+      }
+      if (lane < NC) s_grp[lane] = grp;
+    }
+    __syncthreads();
+    AS_TICK(2);
+    // (2) lane 0 commits the survivors in lattice order.  Nothing in this loop scans: what a child needs of its voxel's holder is
+    // one LDS entry of its group.  (A version that found siblings and updated holders by scanning r < q per child, all in LDS, was
+    // measured 19 % slower per launch than reading the holder's cost from memory: one lane's dependent LDS reads add up.)
+    if (lane == 0) {
+      for (int q = 0; q < NC; q++) {
+        if (used >= cap - 1) { if (cap < kAsMaxNodes) capped = 1; break; }      // "run out of memory" (:1061-1065), at the handle's pool when that is smaller
+        int f = s_f[q];
+        if (f == -2) continue;
+        const double* c = s_ch[q];
+        const int vx = s_vx[q], vy = s_vy[q], grp = s_grp[q];
+        int pos = s_pos[q];
+        if (!first) {
+          int hst, hidx;
+          if (f >= 0) { hst = s_hst[q]; hidx = s_hidx[q]; }
+          else { hst = 1; hidx = pindex + 1; if (grp != q) f = s_new[grp]; }      // (the group's first child took the voxel in this commit: open, of this index)
+          if (f >= 0) {
+            if (hst == 1 && hidx == pindex + 1) {
+              if (c[16] < s_hcost[grp] && (ran_trigger & 1) == 0) {      // update the open node in place (:1190-1203); the heap is not re-ordered
+                AsNode* o = pool + f;
+                o->prev = e_cur; o->g = c[14]; o->h = c[15]; o->cost = c[16];
+                for (int i = 0; i < 6; i++) o->end[i] = c[i];
+                for (int i = 0; i < 4; i++) { o->cx[i] = c[6 + i]; o->cy[i] = c[10 + i]; }
+                s_hcost[grp] = c[16];
+              }
+              ran_trigger++;
+            }
+            continue;
+          }
+        }
+        AsNode* nb = pool + used;
+        nb->h = c[15]; nb->cost = c[16]; nb->g = c[14];
+        for (int i = 0; i < 6; i++) nb->end[i] = c[i];
+        for (int i = 0; i < 4; i++) { nb->cx[i] = c[6 + i]; nb->cy[i] = c[10 + i]; }
+        nb->prev = e_cur; nb->state = 1; nb->index = pindex + 1; nb->vx = vx; nb->vy = vy; nb->_pad = 0;
+        as_push_heap(hp, pool, heap_n, used, c[16], c[15]); heap_n++;
+        // unordered_map::insert keeps the first: the walk goes on from where the lookup ended (entries are never removed)
+        const unsigned long long key = as_key(vx, vy);
+        if (as_find(tkey, tval, mask, key, pos >= 0 ? pos : 0, pos) < 0 && pos >= 0) { tkey[pos] = key; tval[pos] = used; }
+        s_new[q] = used; s_hcost[q] = c[16];
+        used++;
+      }
+    }
+    __syncthreads();
+    AS_TICK(3);
+  };
+
+  expand(-1, init, 0.0, 0);
+  const int max_pops = aa.max_pops;
+  for (;;) {
+    if (__shfl(heap_n, 0) <= 0) break;
+    if (pops >= max_pops) { status = NEP_FE_DEPTH_REACHED; break; }       // RUNTIME_REACHED: the budget (:1644-1651)
+    if (lane == 0) { cur = as_pop(hp, pool, heap_n); pool[cur].state = -1; }
+    cur = __shfl(cur, 0); pops++;
+    __syncthreads();
+    AS_TICK(0);
+    const AsNode* nd = pool + cur;
+    const int index = nd->index;
+    double pe[6], cx[4], cy[4];
+#pragma unroll
+    for (int i = 0; i < 6; i++) pe[i] = nd->end[i];
+#pragma unroll
+    for (int i = 0; i < 4; i++) { cx[i] = nd->cx[i]; cy[i] = nd->cy[i]; }
+    const double pg = nd->g;
+    // collidesWithObstacles2dSolve (:1514-1553): the control polygon against every other agent's hull of the node's interval and
+    // every static polygon, one per lane
+    Pts4 B;
+    fe_pos_cps(cx, sp.T_span, B.x); fe_pos_cps(cy, sp.T_span, B.y);
+    const int idx = (index > D ? D : index) - 1;
+    bool hit = false;
+    for (int o = lane; o < N + S; o += 64) {
+      int nv; const double* V;
+      if (o < N) {
+        if (o == own) continue;
+        const HullRef hr = hull_ref(ps, sp.n_hull, scene, o); const long h = hr.e * sp.num_pol + idx;
+        nv = blk(ps.hull_nv, hr.boff)[h]; V = blk(ps.hull_xy, hr.boff) + h * kHullV * 2;
+      } else { const long js = (long)scene * sp.static_stride + (o - N); nv = ps.static_nv[js]; V = ps.static_xy + js * kHullV * 2; }
+      if (nv > 0 && gjk_collision(nv, V, B)) hit = true;
+    }
+    const bool collides = __ballot(hit) != 0ull;
+    AS_TICK(1);
+    if (collides) continue;
+    const double dist = sqrt((pe[0] - gx) * (pe[0] - gx) + (pe[1] - gy) * (pe[1] - gy));
+    const double dfi = sqrt((pe[0] - init[0]) * (pe[0] - init[0]) + (pe[1] - init[1]) * (pe[1] - init[1]));
+    const double dtc = goal_occupied ? dist * dist : dfi;
+    const double dti = dtc * (double)index;
+    if (dti < smallest) { smallest = dti; closest = cur; }               // (:1683-1690)
+    if (dist < fc.goal_size) { status = NEP_FE_GOAL_REACHED; break; }
+    expand(cur, pe, pg, index);
+  }
+
+  if (lane == 0) {
+    int best = status == NEP_FE_GOAL_REACHED ? cur : closest;            // use_not_reaching_soln
+    if (best < 0) status = NEP_FE_NO_SOLUTION;
+    nep_guess* g = guess_out + slot;
+    for (int e = 0; e < 3 * NEP_MAX_POL * 4; e++) (&g->coeff[0][0][0])[e] = 0.0;
+    g->t_start = st->t_start; g->n_alpha = 0;
+    int K = 0, depth = 0; double cost = 0.0, dtg = 0.0;
+    if (best >= 0) {
+      const AsNode* b = pool + best;
+      depth = b->index; K = depth < D ? depth : D; cost = b->cost;
+      dtg = sqrt((b->end[0] - gx) * (b->end[0] - gx) + (b->end[1] - gy) * (b->end[1] - gy));
+      // recoverPwpOut (:521-553): the nodes of the path with index <= num_pol (a node's index is its place on its path)
+      int k = best;
+      for (int it = 0; it < cap && k >= 0; it++) {
+        const AsNode* q = pool + k;
+        const int d = q->index;
+        if (d >= 1 && d <= D) for (int c = 0; c < 4; c++) { g->coeff[0][d - 1][c] = q->cx[c]; g->coeff[1][d - 1][c] = q->cy[c]; }
+        k = q->prev;
+      }
+      int Kg = K;
+      if (fc.pad_hold && K < D) {   // hold the end point for the rest of the horizon (as frontend_kernel does)
+        for (int d = K + 1; d <= D; d++) { g->coeff[0][d - 1][3] = b->end[0]; g->coeff[1][d - 1][3] = b->end[1]; }
+        Kg = D;
+      }
+      fe_initial_z(st->pos[2], st->vel[2], st->accel[2], st->goal[2], sp.T_span, D, sp.v_max, sp.a_max, g->coeff[2]);   // coeffs_z_ (:540)
+      for (int d = Kg + 1; d <= D; d++) for (int c = 0; c < 4; c++) g->coeff[2][d - 1][c] = 0.0;
+      K = Kg;
+    }
+    g->K = K;
+    if (capped && ps.flags) atomicOr(ps.flags, NEP_FLAG_FE_ASTAR_POOL);
+    if (res_out) {
+      nep_fe_result* o = res_out + slot;
+      o->status = status; o->K = K; o->depth = depth; o->n_children = pops; o->n_feasible = used; o->n_collision_free = 0;
+      o->goal_occupied = goal_occupied ? 1 : 0; o->_pad = capped ? kAsPadPool : 0;
+      o->cost = cost; o->dist_to_goal = dtg; o->n_entangled = 0; o->ent_overflow = 0;
+    }
+#ifdef NEP_PROFILE_PHASES
+    AS_TICK(5);
+    if (ps.dbg) { for (int k = 0; k < 6; k++) ps.dbg[(long)slot * 32 + k] = tph[k]; ps.dbg[(long)slot * 32 + 8] = pops; ps.dbg[(long)slot * 32 + 9] = used; }
+#endif
+  }
+#undef AS_TICK
+}
+
+void launch_frontend_astar(int n_slots, const SceneParams& sp, const ProblemSet& ps_in, const nep_fe_cfg& fc, const FeAstarArgs& aa, const nep_fe_start* starts,
+                           nep_guess* guess_out, nep_fe_result* res_out, hipStream_t st, int* active_buf) {
+  if (n_slots <= 0) return;
+  ProblemSet ps = ps_in;
+  ps.fe_order = nullptr; ps.fe_count = nullptr;
+  if (ps.active && active_buf) {      // an active set: the searches run over the list of active slots; the others get what the beam's launch gives them
+    launch_active_list(n_slots, sp, ps.active, nullptr, active_buf, nullptr, st);
+    ps.fe_order = active_buf; ps.fe_count = active_buf + n_slots;
+    hipLaunchKernelGGL(skipped_fe_kernel, dim3((n_slots + 63) / 64), dim3(64), 0, st, sp, ps.active, n_slots, starts, guess_out, res_out);
+  }
+  hipLaunchKernelGGL(frontend_astar_kernel, dim3(n_slots), dim3(64), 0, st, sp, ps, fc, aa, starts, guess_out, res_out);
+}

@@ -3087,6 +3087,9 @@ void launch_frontend(int n_slots, const SceneParams& sp, const ProblemSet& ps_in
   else hipLaunchKernelGGL((frontend_kernel<false, NEP_FE_WAVES>), dim3(n_slots), dim3(256), lds, st, sp, ps, fc, starts, guess_out, res_out, none);
 }
 
+// the reference's best-first search over the same lattice (nep_batch_frontend_astar)
+#include "fe_astar.h"
+
 // Neptune::SamplePointsOfIntervals (neptune.cpp:500-565) for every committed trajectory of every scene:
 // sampled[scene][j][interval][0..ns][2] on the round's grid, present[scene][j] = the trajectory exists (trajs_ holds it)
 __global__ void ent_sample_kernel(const nep_traj_rec* __restrict__ recs, int n_scenes, int N, const double* __restrict__ ts0, long ts_scene_stride,

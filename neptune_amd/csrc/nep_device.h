@@ -125,6 +125,7 @@ struct ProblemSet {
 __device__ __forceinline__ bool slot_active(const SceneParams& sp, const int* active, int slot) {
   return active == nullptr || active[(long)(slot / sp.n_local) * sp.num_agents + sp.first_local + slot % sp.n_local] != 0;
 }
+constexpr int NEP_FLAG_FE_ASTAR_POOL = 256;   // nep_batch_frontend_astar: a search ran into a node pool smaller than the reference's 20 000 (nep_batch_set_fe_astar's max_nodes): it stopped creating nodes there
 constexpr int NEP_FLAG_MISSION = 128;       // nep_batch_fleet_mission: a draw found no goal among max_attempts candidates (the slot kept its goal; NEP_FLEET_FLAG_GOAL)
 constexpr int NEP_FLAG_FLEET = 64;           // nep_batch_fleet_commit: an accepted slot's plan or composed trajectory would have outgrown its storage (the slot kept both; NEP_FLEET_CAP)
 constexpr int NEP_FLAG_ENT_TRACK = 32;      // nep_batch_track_ent: a tracked state outgrew the fixed record (list, bend points or a step's crossings; the step was dropped) or was handed in malformed
@@ -236,6 +237,16 @@ size_t frontend_ent_xpool_words(const SceneParams& sp, const nep_fe_cfg& fc, int
 void launch_frontend(int n_slots, const SceneParams& sp, const ProblemSet& ps, const nep_fe_cfg& fc, const nep_fe_start* starts,
                      nep_guess* guess_out, nep_fe_result* res_out, const FeEntArgs* ea, hipStream_t st, int* order_buf = nullptr, bool have_history = false,
                      int* active_buf = nullptr);      // (active_buf: [slots + 1] for the active list when ps.active is set)
+// the best-first front end (fe_astar.h, nep_batch_set_fe_astar): budget, lattice order and the per-slot pools (device pointers)
+struct FeAstarArgs {
+  int max_pops, pool, tab_cap;   // pops per search; nodes per slot; entries of a slot's voxel table (a power of two >= 2 * pool)
+  const int* order;              // [num_samples^2] the lattice order (all_combinations_), or null: 0, 1, 2, ...
+  unsigned char* nodes;          // [slots][pool] nodes of NEP_FE_ASTAR_NODE_BYTES
+  int* heap;                     // [slots][pool] the open list's heap (its first entries live in LDS)
+  unsigned long long* tab_key; int* tab_val;      // [slots][tab_cap] voxel -> first node
+};
+void launch_frontend_astar(int n_slots, const SceneParams& sp, const ProblemSet& ps, const nep_fe_cfg& fc, const FeAstarArgs& aa, const nep_fe_start* starts,
+                           nep_guess* guess_out, nep_fe_result* res_out, hipStream_t st, int* active_buf = nullptr);
 void launch_ent_sample(const nep_traj_rec* recs, int n_scenes, int N, const double* ts0, long ts_scene_stride, int num_pol, int ns, double T_span,
                        double* sampled, int* present, hipStream_t st, int* zero_this = nullptr);
 // nep_batch_audit (audit_kernels.hip): the minima of one (scene, run of ticks, agent), ticks as indices of the call

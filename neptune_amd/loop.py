@@ -60,7 +60,19 @@ def stamp_bends(d_new, d_rec):
         vn[:, lo:hi].copy_(vr[:, lo:hi])
 
 
-def plan_round(be, fe, d_rec, d_start, d_guess, d_res, d_final, d_acc, tethers=False, d_case=None, d_ent=None, ent_samples=3):
+def check_search(search, max_pops, tethers):
+    """the front end's strategy: "beam" (the default) or "astar", the reference's best-first search with a budget of max_pops pops
+    per search (BatchBackend.set_fe_astar / frontend_astar), which has no entangle check"""
+    if search not in ("beam", "astar"):
+        raise ValueError("search must be 'beam' or 'astar'")
+    if search == "astar" and tethers:
+        raise ValueError("search='astar' has no entangle check: it cannot fly tethers=True")
+    if search == "astar" and int(max_pops) < 1:
+        raise ValueError("max_pops must be at least 1")
+    return search == "astar"
+
+
+def plan_round(be, fe, d_rec, d_start, d_guess, d_res, d_final, d_acc, tethers=False, d_case=None, d_ent=None, ent_samples=3, astar=False):
     """the plan half of a round: front end -> lines + QP -> safety pass, from the records d_rec and the starts d_start into d_final
     and d_acc.  With d_case the entangle check is on (d_ent: every tether's state at A): the QP gets the entangle rows and the safety
     pass re-checks.  Tethered rounds stamp the published bend points into the commit records before the safety pass."""
@@ -70,7 +82,7 @@ def plan_round(be, fe, d_rec, d_start, d_guess, d_res, d_final, d_acc, tethers=F
         stamp_bends(be.d_commit, d_rec)
         be.safety_commit_ent(d_rec, be.d_commit, d_guess, d_final, d_acc, d_ent_init=d_ent, ent_samples=ent_samples)
     else:
-        be.frontend(fe, d_rec, d_start, d_guess, d_res)
+        (be.frontend_astar if astar else be.frontend)(fe, d_rec, d_start, d_guess, d_res)      # (astar: the handle's set_fe_astar was called)
         be.replan(None, d_guess)
         if tethers:
             stamp_bends(be.d_commit, d_rec)
@@ -104,10 +116,11 @@ class _Audited:
 
 class FleetLoop(_Audited):
     def __init__(self, par, statics, starts, goals, beam_width=32, delta_t_states=6, replan_every=5, device=None, skip_arrived=False, audit=False,
-                 tethers=False, check=True, ent_samples=3):
+                 tethers=False, check=True, ent_samples=3, search="beam", max_pops=300):
         import torch
         self.torch = torch
         self.tethers, self.check, self.ent_samples = tethers, check, ent_samples
+        self.astar = check_search(search, max_pops, tethers)
         if tethers:
             import dataclasses
             par = dataclasses.replace(par, enable_entangle=True)
@@ -117,6 +130,8 @@ class FleetLoop(_Audited):
         self.be = BatchBackend(par, statics, n_scenes=1, device=device)
         self.be.set_safety_check_prev(True)    # nobody commits a trajectory that crosses what somebody else may keep flying
         self.be.set_line_cull(4.0)             # presolve: far separating lines are verified, not solved for (same optimum)
+        if self.astar:
+            self.be.set_fe_astar(max_pops)     # (allocates the searches' pools)
         self.fe = scene.frontend_cfg(par, beam_width=beam_width, pad_hold=1, entangle=tethers and check, ent_samples=ent_samples)
         if tethers:
             # the one-scene host form of DeviceFleetLoop(tethers=True): entangle_state_ of every agent at its tracked position is kept
@@ -229,7 +244,7 @@ class FleetLoop(_Audited):
         if self.tethers and self.check:
             d_ent_a = be.to_device(self.ent_a)
             d_case = torch.zeros(N * abi.NEP_MAX_POL * N, dtype=torch.int32, device=be.device)
-        plan_round(be, self.fe, d_com, d_start, d_guess, d_fres, d_final, d_acc, self.tethers, d_case, d_ent_a, self.ent_samples)
+        plan_round(be, self.fe, d_com, d_start, d_guess, d_fres, d_final, d_acc, self.tethers, d_case, d_ent_a, self.ent_samples, self.astar)
         sol = be.solutions(); states = be.states(); fres = d_fres.cpu().numpy().view(abi.FE_RESULT_DTYPE)
         acc = d_acc.cpu().numpy()
         self.stats["rounds"] += 1
@@ -350,6 +365,8 @@ class DeviceFleetLoop(_Audited):
     smaller plan ring than a splice can need (tests of the capacity path).
     run() downloads the slots' arrival flags (4 bytes per slot) after every round to know when to stop; nothing else leaves the
     device before report().  trace=True additionally downloads outcome, K and the two statuses per round (FleetLoop.trace).
+    search="astar" plans with the reference's best-first search, max_pops pops per search, in place of the beam
+    (BatchBackend.frontend_astar; not with tethers=True: ValueError).
 
     tethers=True flies tethered agents: the handle is created with enable_entangle and carries every tether's
     entangle state at the tracked position, and the round becomes
@@ -382,12 +399,14 @@ class DeviceFleetLoop(_Audited):
 
     def __init__(self, scenes, beam_width=32, delta_t_states=6, replan_every=5, periods=None, phases=None, audit=False, graph=True,
                  goals=None, device=None, ring_cap=0, trace=False, tethers=False, check=True, ent_samples=3, missions=None, ent_cap=None,
-                 ent_lists0=None, recorder=None):
+                 ent_lists0=None, recorder=None, search="beam", max_pops=300):
         import torch
         self.torch = torch
         self.scenes = scenes
+        self.astar = check_search(search, max_pops, tethers)
         self._opts = dict(beam_width=beam_width, delta_t_states=delta_t_states, replan_every=replan_every, audit=audit, ring_cap=ring_cap,
-                          tethers=tethers, check=check, ent_samples=ent_samples, ent_cap=ent_cap, missions=missions, goals=goals)
+                          tethers=tethers, check=check, ent_samples=ent_samples, ent_cap=ent_cap, missions=missions, goals=goals,
+                          search=search, max_pops=max_pops)
         S = self.S = len(scenes)
         p = self.p = scenes[0]["par"]
         self.tethers, self.check, self.ent_samples = tethers, check, ent_samples
@@ -400,6 +419,8 @@ class DeviceFleetLoop(_Audited):
         upload_statics(be, scenes, tethers)
         be.set_safety_check_prev(True)
         be.set_line_cull(4.0)
+        if self.astar:
+            be.set_fe_astar(max_pops)      # (allocates the searches' pools: here, before any capture)
         self.fe = scene.frontend_cfg(p, beam_width=beam_width, pad_hold=1, entangle=tethers and check, ent_samples=ent_samples)
         self.goals = np.stack([np.asarray(scene.reachable_goals(sc) if goals is None else goals[s], dtype=np.float64).reshape(N, 3)
                                for s, sc in enumerate(scenes)])
@@ -483,7 +504,7 @@ class DeviceFleetLoop(_Audited):
             if self.after_select is not None:
                 self.after_select(self)
         ent = (self.d_case, self.d_ent_a) if self.tethers and self.check else (None, None)
-        plan_round(be, self.fe, self.d_rec, self.d_start, self.d_guess, self.d_res, self.d_final, self.d_acc, self.tethers, *ent, self.ent_samples)
+        plan_round(be, self.fe, self.d_rec, self.d_start, self.d_guess, self.d_res, self.d_final, self.d_acc, self.tethers, *ent, self.ent_samples, self.astar)
         be.fleet_commit(self.d_res, self.d_acc, self.d_outcome)
         if self.after_commit is not None:
             self.after_commit(self)
@@ -574,6 +595,7 @@ class DeviceFleetLoop(_Audited):
         o["ent_cap"] = self.ent_cap
         o["missions"] = dataclasses.asdict(self.missions) if self.missions is not None else None
         o["masked"] = bool(self.masked)
+        o["search"], o["max_pops"] = self._opts["search"], int(self._opts["max_pops"])
         o["N"], o["n_statics"] = int(self.N), len(self.scenes[0]["statics"])
         return o
 
@@ -642,7 +664,11 @@ class DeviceFleetLoop(_Audited):
             raise ValueError("checkpoint %s was flown with %d agents and %d statics per scene" % (path, opts["N"], opts["n_statics"]))
         if opts["masked"] != ("periods" in kw or "phases" in kw):
             raise ValueError("checkpoint %s was flown %s periods / phases" % (path, "with" if opts["masked"] else "without"))
+        for k, dflt in (("search", "beam"), ("max_pops", 300)):      # (a file from before the option has the beam)
+            if k in kw and kw[k] != opts.get(k, dflt) and (k == "search" or opts.get("search", "beam") == "astar"):
+                raise ValueError("checkpoint %s was flown with %s=%r, not %r" % (path, k, opts.get(k, dflt), kw[k]))
         o = {k: opts[k] for k in cls._MUST_MATCH}
+        o["search"], o["max_pops"] = opts.get("search", "beam"), opts.get("max_pops", 300)
         o["missions"] = mission.MissionSpec(**opts["missions"]) if opts["missions"] is not None else None
         o.update({k: v for k, v in kw.items() if k not in o})
         lp = cls(scenes, **o)

@@ -2,9 +2,10 @@
 """Closed-loop flight of a fleet on the device path (neptune_amd/loop.py): every agent flies from its
 start next to its base to a random goal, replanning in bulk-synchronous rounds, the way the reference's
 benchmark driver logs a run (scripts/benchmark_mtlp.py:215-223: elapsed time, distance, success).
-  python scripts/closed_loop.py [--agents 16 --obstacles 8 --seed 0 --beam 32 --skip-arrived --audit --tethers [--no-check]]
+  python scripts/closed_loop.py [--agents 16 --obstacles 8 --seed 0 --beam 32 --skip-arrived --audit --tethers [--no-check] --search astar --max-pops 300]
 --tethers: tethered agents, the one-scene host form of DeviceFleetLoop(tethers=True) (entangle states kept on the host with
-nep_ent_track_step per control tick, nep_ent_predict_a per round)."""
+nep_ent_track_step per control tick, nep_ent_predict_a per round).  --search astar: the reference's best-first search, --max-pops
+pops per search, in place of the beam (not with --tethers)."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from neptune_amd import scene
@@ -17,11 +18,13 @@ ap.add_argument("--skip-arrived", action="store_true", help="arrived agents leav
 ap.add_argument("--audit", action="store_true", help="flight audit on the device (nep_batch_audit) next to the host's distance log")
 ap.add_argument("--tethers", action="store_true", help="tethered agents: entangle-aware front end and safety pass, tether states tracked per control tick")
 ap.add_argument("--no-check", action="store_true", help="with --tethers: plain front end and safety pass, the tracking stays on")
+ap.add_argument("--search", choices=("beam", "astar"), default="beam", help="front end: the beam (default) or the reference's best-first search (nep_batch_frontend_astar)")
+ap.add_argument("--max-pops", type=int, default=300, help="with --search astar: pops per search")
 a = ap.parse_args()
 sc = scene.make_scene(a.agents, a.obstacles, seed=a.seed)
 t0 = time.perf_counter()
 loop = FleetLoop(sc["par"], sc["statics"], sc["starts"], scene.reachable_goals(sc), beam_width=a.beam, skip_arrived=a.skip_arrived, audit=a.audit, tethers=a.tethers,
-                 check=not a.no_check)
+                 check=not a.no_check, search=a.search, max_pops=a.max_pops)
 if a.audit:
     loop.trace = []
 st = loop.run(a.max_rounds)

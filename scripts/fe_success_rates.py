@@ -5,7 +5,11 @@ oracle's restatement of the reference's best-first search (orc_frontend_astar: K
 outcomes are tabulated next to the device's (beam WITH the entangle check).  A search the reference's own A* cannot start either
 (no collision-free first primitive from point A) is a property of the scenario, not of the beam.
 
-  python scripts/fe_success_rates.py [scenes=4] [rounds=6] [host_scenes=2]   ->  stdout (kept under profiles/)
+Next to them the device's own best-first search (nep_batch_frontend_astar, entangle check off) runs EVERY search of every scene in one
+launch per budget — what the host loop cannot do at scale — and is tabulated against the device beam without the check: outcomes, K
+and the progress towards the goal ((|A - goal| - dist_to_goal) / |A - goal| of the returned node).
+
+  python scripts/fe_success_rates.py [scenes=4] [rounds=6] [host_scenes=2] [agents=256] [obstacles=100] [pops=100,300,1000]   ->  stdout (kept under profiles/)
 """
 import dataclasses
 import os
@@ -25,8 +29,10 @@ def main():
     S = int(sys.argv[1]) if len(sys.argv) > 1 else 4
     rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 6
     SH = int(sys.argv[3]) if len(sys.argv) > 3 else 2
-    N = 256
-    made = scene.make_scenes(N, 100, range(S), workers=min(S, 32))
+    N = int(sys.argv[4]) if len(sys.argv) > 4 else 256
+    n_obst = int(sys.argv[5]) if len(sys.argv) > 5 else 100
+    budgets = [int(x) for x in (sys.argv[6] if len(sys.argv) > 6 else "100,300,1000").split(",")]
+    made = scene.make_scenes(N, n_obst, range(S), workers=min(S, 16))
     p = dataclasses.replace(made[0]["par"], enable_entangle=True)
     be = BatchBackend(p, made[0]["statics"], n_scenes=S)
     for s in range(S):
@@ -62,6 +68,9 @@ def main():
     lost32 = (res["status"] >= 2)
     print("device beam of width 64 WITH the entangle check, same inputs: %s; of the %d searches the width-32 beam ended without a plan (died out / no solution), width 64 finds a plan for %d"
           % ({NAMES[k]: int((res64["status"] == k).sum()) for k in NAMES}, int(lost32.sum()), int((lost32 & (res64["status"] < 2)).sum())))
+    device_astar(be, p, cfg_plain, d_c, d_s, starts, S, N, budgets)
+    if SH <= 0:
+        return
     oracle.lib()
     jobs = [(s, a) for s in range(min(SH, S)) for a in range(N)]
 
@@ -71,7 +80,7 @@ def main():
         g1, r1 = oracle.frontend_astar(p, cfg_plain, a + 1, starts[s, a], hx, hn, made[s]["statics"], max_pops=20000)
         g2, r2 = oracle.frontend_beam(p, cfg_plain, a + 1, starts[s, a], hx, hn, made[s]["statics"])
         return r1["status"], int(g1["K"]), r2["status"], int(g2["K"])
-    with ThreadPoolExecutor(min(128, os.cpu_count() or 1)) as ex:
+    with ThreadPoolExecutor(min(16, os.cpu_count() or 1)) as ex:
         out = np.array(list(ex.map(one, jobs)))
     dev = res["status"].reshape(S, N)[:min(SH, S)].reshape(-1); devK = res["K"].reshape(S, N)[:min(SH, S)].reshape(-1)
     n = len(jobs)
@@ -83,6 +92,30 @@ def main():
     print("  searches with no solution on the device: %d; of these the reference's A* has no solution either: %d (no collision-free first primitive from point A: "
           "the scenario's, not the beam's); found by the A* but not by the device beam: %d" % (int((dev == 3).sum()), both_none, int(((dev == 3) & (out[:, 0] != 3)).sum())))
     print("  plans the device returns (K > 0): %d; the A* returns: %d; A* plans shorter than num_pol: %d" % (int((devK > 0).sum()), int((out[:, 1] > 0).sum()), int(((out[:, 1] > 0) & (out[:, 1] < p.num_pol)).sum())))
+
+
+def device_astar(be, p, cfg_plain, d_c, d_s, starts, S, N, budgets):
+    """the device beam (width 32) and the device A* at every budget, entangle check off, all S * N searches per launch"""
+    d_g = torch.zeros(S * N * abi.GUESS_DTYPE.itemsize, dtype=torch.uint8, device=be.device)
+    d_r = torch.zeros(S * N * abi.FE_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=be.device)
+    d0 = np.hypot(*(starts["pos"][..., :2] - starts["goal"][..., :2]).reshape(-1, 2).T)
+
+    def row(name, res):
+        far = d0 > 1.0      # (a search that starts at its goal has no progress to make)
+        prog = np.where(res["K"] > 0, (d0 - res["dist_to_goal"]) / np.maximum(d0, 1.0), 0.0)[far]
+        print("  %-34s %s; plans (K > 0) %d, mean K %.2f, plans shorter than num_pol %d; progress towards the goal of the %d searches that start more than 1 m from it: mean %.3f median %.3f"
+              % (name, {NAMES[k]: int((res["status"] == k).sum()) for k in NAMES}, int((res["K"] > 0).sum()), float(res["K"].mean()),
+                 int(((res["K"] > 0) & (res["K"] < p.num_pol)).sum()), int(far.sum()), float(prog.mean()), float(np.median(prog))), flush=True)
+    print("\ndevice searches WITHOUT the entangle check, last round's records, all %d searches per launch:" % (S * N))
+    be.frontend(cfg_plain, d_c, d_s, d_g, d_r); torch.cuda.synchronize()
+    row("beam, width 32", d_r.cpu().numpy().view(abi.FE_RESULT_DTYPE).copy())
+    for pops in budgets:
+        be.set_fe_astar(pops)
+        be.frontend_astar(cfg_plain, d_c, d_s, d_g, d_r); be.check()
+        res = d_r.cpu().numpy().view(abi.FE_RESULT_DTYPE).copy()
+        row("A*, %d pops (0: on the budget)" % pops, res)
+        print("  %-34s pops mean %.0f max %d; nodes mean %.0f max %d; returned depth max %d" % ("", res["n_children"].mean(), res["n_children"].max(),
+              res["n_feasible"].mean(), res["n_feasible"].max(), res["depth"].max()), flush=True)
 
 
 if __name__ == "__main__":

@@ -37,6 +37,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=400, help="at most; the flight stops when every agent of every scene has arrived")
     ap.add_argument("--beam", type=int, default=32)
     ap.add_argument("--stagger", type=int, default=0, metavar="P")
+    ap.add_argument("--search", choices=("beam", "astar"), default="beam", help="front end: the beam (default) or the reference's best-first search (nep_batch_frontend_astar; not with --tethers)")
+    ap.add_argument("--max-pops", type=int, default=300, help="with --search astar: pops per search")
     ap.add_argument("--audit", action="store_true", help="flight audit of every round, inside the graph")
     ap.add_argument("--eager", action="store_true", help="no graph capture")
     ap.add_argument("--tethers", action="store_true", help="tethered agents: entangle states tracked per control tick, predicted at A, checked by the front end and the safety pass")
@@ -59,7 +61,7 @@ def main():
     from neptune_amd.loop import DeviceFleetLoop, FleetLoop
     seeds = [a.seed0 + k for k in range(a.scenes)]
     scenes = scene.make_scenes(a.agents, a.obstacles, seeds, workers=min(len(seeds), len(os.sched_getaffinity(0)), 16))
-    kw = dict(beam_width=a.beam, audit=a.audit, graph=not a.eager)
+    kw = dict(beam_width=a.beam, audit=a.audit, graph=not a.eager, search=a.search, max_pops=a.max_pops)
     if a.tethers:
         kw.update(tethers=True, check=not a.no_check)
         if a.ent_cap:
@@ -160,7 +162,7 @@ def main():
     if a.host:
         sc = scenes[0]
         _, dev1, n1 = fly([sc], a.rounds)
-        ref = FleetLoop(sc["par"], sc["statics"], sc["starts"], scene.reachable_goals(sc), beam_width=a.beam, audit=a.audit, tethers=a.tethers, check=not a.no_check)
+        ref = FleetLoop(sc["par"], sc["statics"], sc["starts"], scene.reachable_goals(sc), beam_width=a.beam, audit=a.audit, tethers=a.tethers, check=not a.no_check, search=a.search, max_pops=a.max_pops)
         ref.round(); ref.round()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
