@@ -24,11 +24,12 @@ __global__ __launch_bounds__(1024) void audit_chunk_kernel(AuditArgs aa) {
   const int N = aa.N, S = aa.S, vs = aa.vstride;
   const int scene = blockIdx.x / aa.n_chunks, chunk = blockIdx.x - scene * aa.n_chunks;
   const int a = threadIdx.x;
-  double* pxy = (double*)au_lds;                  // [S][vs][2] polygon vertices
-  double* pinv = pxy + (size_t)S * vs * 2;        // [S][vs] 1 / |edge|^2
-  double* ag = pinv + (size_t)S * vs;             // [N][4] x, y, hx, hy
-  int* pnv = (int*)(ag + (size_t)N * 4);          // [S] vertex counts (clamped to vs)
-  int* apres = pnv + S;                           // [N]
+  const AuditLayout L = audit_layout(N, S, vs);      // (lds_layout.h)
+  double* pxy = lds_at<double>(au_lds, L.pxy);       // [S][vs][2] polygon vertices
+  double* pinv = lds_at<double>(au_lds, L.pinv);     // [S][vs] 1 / |edge|^2
+  double* ag = lds_at<double>(au_lds, L.ag);         // [N][4] x, y, hx, hy
+  int* pnv = lds_at<int>(au_lds, L.pnv);             // [S] vertex counts (clamped to vs)
+  int* apres = lds_at<int>(au_lds, L.apres);         // [N]
   const long sbase = (long)scene * aa.static_stride;
   for (int j = a; j < S; j += blockDim.x) { const int c = aa.static_nv[sbase + j]; pnv[j] = c < 0 ? 0 : (c > vs ? vs : c); }
   for (int e = a; e < S * vs; e += blockDim.x) {
@@ -111,14 +112,10 @@ __global__ void audit_merge_kernel(AuditArgs aa) {
 
 }  // namespace
 
-size_t audit_lds_bytes(int N, int S, int vstride) {
-  return ((size_t)S * vstride * 3 + (size_t)N * 4) * sizeof(double) + ((size_t)S + N) * sizeof(int);
-}
-
 void launch_audit(const AuditArgs& aa, hipStream_t st) {
   if (aa.n_scenes <= 0 || aa.N <= 0 || aa.n_ticks <= 0) return;
   const unsigned threads = (unsigned)((aa.N + 63) / 64 * 64);
-  hipLaunchKernelGGL(audit_chunk_kernel, dim3((unsigned)(aa.n_scenes * aa.n_chunks)), dim3(threads), audit_lds_bytes(aa.N, aa.S, aa.vstride), st, aa);
+  hipLaunchKernelGGL(audit_chunk_kernel, dim3((unsigned)(aa.n_scenes * aa.n_chunks)), dim3(threads), (size_t)audit_layout(aa.N, aa.S, aa.vstride).bytes, st, aa);
   const long total = (long)aa.n_scenes * aa.N;
   hipLaunchKernelGGL(audit_merge_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, aa);
 }

@@ -1371,7 +1371,8 @@ int nep_batch_set_static_reps(nep_batch_t* h, int32_t scene, const double* rep, 
 // not propagated twice) and the packed per-(agent, interval) records of the entangle check
 static int fe_ent_scratch(nep_batch* h, const nep_fe_cfg& cfg, FeEntArgs& ea) {
   Engine& E = h->eng;
-  const size_t cap = frontend_children_cap(cfg, h->cfg.num_pol);
+  const FeLayout fl = fe_layout(E.sp.num_agents, E.sp.n_static, cfg.beam_width, cfg.num_samples, E.sp.num_pol, true);      // (lds_layout.h)
+  const size_t cap = (size_t)fl.z.cap;      // children per depth of one search (beam_width x lattice)
   if (int e = E.d_fe_saved.ensure((size_t)h->slots * cap)) return e;
   if (int e = E.d_fe_arc.ensure((size_t)h->slots * cap)) return e;
   ea.saved = E.d_fe_saved.p; ea.saved_arc = E.d_fe_arc.p;
@@ -1379,7 +1380,7 @@ static int fe_ent_scratch(nep_batch* h, const nep_fe_cfg& cfg, FeEntArgs& ea) {
   if (int e = E.d_fe_stvox.ensure((size_t)h->slots * cap)) return e;
   ea.st_f = E.d_fe_stf.p; ea.st_vox = E.d_fe_stvox.p;
   {   // where a round's lists of new crossings go when the LDS pool is full (cross_round): one block of kEntAddCap words per (child, step)
-    const size_t xw = frontend_ent_xpool_words(E.sp, cfg, ea.ns);
+    const size_t xw = (size_t)fe_xpool_words(fl, ea.ns);
     if (int e = E.d_fe_xpool.ensure((size_t)h->slots * xw)) return e;
     ea.xpool = E.d_fe_xpool.p; ea.xpool_stride = (int)xw;
   }
@@ -1552,7 +1553,7 @@ int nep_batch_audit(nep_batch_t* h, const nep_traj_rec* d_records, const nep_fe_
   const int N = h->cfg.num_agents, S = h->cfg.n_scenes;
   if (N > 1024) return fail(NEP_E_CAP, "the flight audit takes up to 1024 agents per scene");
   const int vs = E.sp.n_static > 0 ? std::max(E.static_nv_max, 1) : 1;
-  if (audit_lds_bytes(N, E.sp.n_static, vs) > 64 * 1024) return fail(NEP_E_CAP, "the flight audit's agents and static polygons do not fit into 64 KB of LDS");
+  if (audit_layout(N, E.sp.n_static, vs).bytes > 64 * 1024) return fail(NEP_E_CAP, "the flight audit's agents and static polygons do not fit into 64 KB of LDS");
   if (int e = E.d_audit_part.ensure((size_t)S * nep_audit_impl::kAuditMaxChunks * N)) return e;      // (before the n_ticks == 0 return: the first call allocates)
   if (n_ticks == 0) return 0;
   const ProblemSet ps = round_set(h);
@@ -1823,7 +1824,7 @@ int mission_keep_ensure(nep_batch_t* h) {
 }
 // the kernel's dynamic LDS, sized once per handle for the largest keep-out set a scene can hold: a captured graph keeps the size
 // it was captured with, whatever is uploaded later
-size_t mission_lds_need(nep_batch_t* h) { return mission_lds_bytes(h->cfg.num_agents, NEP_MISSION_MAX_VERT, NEP_MISSION_MAX_POLY); }
+size_t mission_lds_need(nep_batch_t* h) { return (size_t)mission_layout(h->cfg.num_agents, NEP_MISSION_MAX_VERT, NEP_MISSION_MAX_POLY).bytes; }
 void fleet_mission_args(nep_batch_t* h, FleetMissionArgs& ma) {
   nep_batch::Fleet& F = h->fleet;
   ma.cfg = F.mis_cfg; ma.lds_bytes = F.mis_lds;

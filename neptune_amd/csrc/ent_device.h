@@ -39,7 +39,6 @@ struct EntCtx {
   long long* prof = nullptr;      // (NEP_PROFILE_PHASES builds: seven per-search accumulators, see scripts/fe_ent_phases.py)
 };
 struct Ev2 { double x, y; };
-constexpr int kEntAddCap = 32;
 // The crossings one sampled step adds, in the reference's order (at most kEntAddCap; more: flagged).  An entry is one word —
 // id | case << 16 | nb << 24 (nb: the crossed agent's bend-point count, known where the crossing is found; the merge needs it) —
 // and the first four entries are plain members that stay in registers (a step adds two or three crossings).  The tail is a
@@ -808,7 +807,6 @@ __device__ bool ent_lists_ok(const nep_ent_lists& L, long slot) {
   for (int k = 0; k < nb; k++) if (b[k] < 0 || b[k] >= na) return false;
   return true;
 }
-constexpr int kEntLdsBytes = ((NEP_FE_ENT_CAP * 3 + NEP_MAX_BEND + 3) & ~3) | 4;      // per thread; an odd number of dwords, so that the threads' lists fall into different banks
 // (false: the record is a big record's marker, or holds more than the view takes — the caller goes to the big form)
 __device__ __forceinline__ bool ent_lds_load(EntLds& L, const nep_fe_ent_state* __restrict__ src, int N) {
   L.n_alpha = src->n_alpha; L.n_bend = src->n_bend;
@@ -883,8 +881,7 @@ __device__ void ent_copy(nep_fe_ent_state* dst, const nep_fe_ent_state* src) {
 // the same from / into a big record (the big-record instantiation keeps lists of up to kEntBigLdsCap entries in LDS: a list in a
 // big record's global memory makes every step of the surgery a round trip of its own — a search that runs on big records took
 // 3.4 ms against 0.8 for one that does not)
-constexpr int kEntBigLdsCap = 120, kEntBigLdsBend = 16;
-constexpr int kEntBigLdsBytes = ((kEntBigLdsCap * 3 + kEntBigLdsBend + 3) & ~3) | 4;      // per thread; an odd number of dwords
+// (kEntBigLdsCap, kEntBigLdsBend, kEntBigLdsBytes: lds_layout.h)
 __device__ __forceinline__ bool ent_lds_load_big(EntLds& L, const EntBig& Q, int N) {
   L.n_alpha = Q.n_alpha; L.n_bend = Q.n_bend;
   if ((L.n_alpha > L.cap) | (L.n_bend > L.bend_cap)) return false;

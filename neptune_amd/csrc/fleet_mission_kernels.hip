@@ -57,13 +57,14 @@ __global__ __launch_bounds__(64) void fleet_mission_kernel(FleetMissionArgs ma, 
   const int n_poly = ma.kn[scene];
   const int* g_off = ma.koff + (long)scene * (NEP_MISSION_MAX_POLY + 1);
   const int n_vert = n_poly > 0 ? g_off[n_poly] : 0;
-  // the carve: end positions [N][3], goals drawn in this call [N][3] (before that: the leg lengths), keep-out vertices, what to do
-  // per agent [N], polygon offsets
-  double* s_end = ms_lds;
-  double* s_new = s_end + 3 * N;
-  double* s_kxy = s_new + 3 * N;
-  int* s_got = (int*)(s_kxy + 2 * n_vert);
-  int* s_off = s_got + N;
+  // the carve (lds_layout.h): end positions [N][3], goals drawn in this call [N][3] (before that: the leg lengths), keep-out vertices,
+  // what to do per agent [N], polygon offsets
+  const MissionLayout L = mission_layout(N, n_vert, n_poly);
+  double* s_end = lds_at<double>(ms_lds, L.s_end);
+  double* s_new = lds_at<double>(ms_lds, L.s_new);
+  double* s_kxy = lds_at<double>(ms_lds, L.s_kxy);
+  int* s_got = lds_at<int>(ms_lds, L.s_got);
+  int* s_off = lds_at<int>(ms_lds, L.s_off);
   for (int i = lane; i < 2 * n_vert; i += 64) s_kxy[i] = ma.kxy[(long)scene * NEP_MISSION_MAX_VERT * 2 + i];
   for (int i = lane; i <= n_poly; i += 64) s_off[i] = g_off[i];
   const long base = (long)scene * N;
@@ -177,9 +178,6 @@ __global__ void fleet_mission_seed_kernel(FleetMissionArgs ma, FleetArgs fa) {
 
 }  // namespace
 
-size_t mission_lds_bytes(int N, int n_vert, int n_poly) {
-  return (size_t)N * 6 * sizeof(double) + (size_t)n_vert * 2 * sizeof(double) + (size_t)N * sizeof(int) + (size_t)(n_poly + 1) * sizeof(int);
-}
 void launch_fleet_mission_seed(const FleetMissionArgs& ma, const FleetArgs& fa, hipStream_t st) {
   const long slots = (long)fa.n_scenes * fa.N;
   hipLaunchKernelGGL(fleet_mission_seed_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, ma, fa);

@@ -661,10 +661,7 @@ __device__ bool separator_impl(int nA, const double2* __restrict__ A, int kind, 
 // waves per SIMD: 11 % faster than three).  A polygon that does not fit what is left of the pool is read where it lies
 // (global memory / L2); the computed point sets (base squares, entangle segments) fall back to a private array.  The packed
 // offsets are not bank-conflict-free as the 13-pair stride was; the LDS pipe has the slack (the kernel is bound by VALU issue).
-#ifndef NEP_SEP_LDS
-#define NEP_SEP_LDS (10 * 1024)
-#endif
-constexpr int kSepLdsTarget = NEP_SEP_LDS;
+// (kSepLdsTarget and the wave's layout: sep_layout, lds_layout.h)
 // Candidate c of segment seg, in the reference's loop order (solver_gurobi_poly.cpp:477-495 agents,
 // :521-553 bases, :556-593 statics, :620-637 entangle): does the reference call the separator for
 // it, and (stage == true) what is point set A.
@@ -928,9 +925,10 @@ __device__ bool cand_eval(const SepCtx& cx, int seg, int c, const double* bx, co
 template <int RULE>
 __device__ __forceinline__ void separator_body(const SceneParams& sp, const ProblemSet& ps, int pool_pairs, int slot, int seg, bool presolve) {
   extern __shared__ __attribute__((aligned(16))) double sdyn[];
-  double2* sA = (double2*)sdyn;                      // [pool_pairs] (x,y) pairs: the batch's point sets A, packed
-  double* sBx = sdyn + 2 * pool_pairs; double* sBy = sBx + 4;
-  unsigned short* sAtt = (unsigned short*)(sBy + 4);
+  const SepLayout L = sep_carve(pool_pairs, sep_total(sp.n_hull, sp.num_agents, sp.n_static, sp.ent_enabled != 0));      // (lds_layout.h; pool_pairs: launch_separator's, from sep_layout)
+  double2* sA = lds_at<double2>(sdyn, L.sA);          // [pool_pairs] (x,y) pairs: the batch's point sets A, packed
+  double* sBx = lds_at<double>(sdyn, L.sBx); double* sBy = lds_at<double>(sdyn, L.sBy);
+  unsigned short* sAtt = lds_at<unsigned short>(sdyn, L.sAtt);
   const int lane = threadIdx.x;
   const nep_guess* g = ps.guess + slot;
   const int K = g->K;
@@ -1001,7 +999,7 @@ __device__ __forceinline__ void separator_body(const SceneParams& sp, const Prob
   // handed out densely, one per lane — a few rounds instead of one per 64 (j, k) slots (32 of a config-5 segment's 42 rounds,
   // and still 0.6 of the kernel's 1.0 ms when every lane with a case walked its own eight k).  Pair order = (j, k) order.
   if (n_plain < total) {
-    unsigned short* sAct = sAtt + (total + 8);
+    unsigned short* sAct = lds_at<unsigned short>(sdyn, L.sAct);
     int n_act = 0;
     for (int j0 = 0; j0 < cx.N; j0 += 64) {
       const int j = j0 + lane;
@@ -1638,23 +1636,11 @@ __global__ __launch_bounds__(64, NEP_SEP_WAVES) void separator_redo_kernel(Scene
   }
 }
 
-size_t separator_lds_bytes(const SceneParams& sp) {
-  const int total = sp.n_hull + sp.num_agents + sp.n_static + (sp.ent_enabled ? sp.num_agents * kBend : 0);
-  const size_t tail = 8 * sizeof(double) + (((size_t)(total + 8 + (sp.ent_enabled ? sp.num_agents : 0)) * sizeof(unsigned short) + 15) & ~(size_t)15);   // (+ the agents with an active entangle case)
-  // the pool takes what is left of 10 KB (sixteen waves per CU); with very long candidate lists (config 5 with the entangle rows)
-  // it keeps at least 64 x 8 pairs and the wave gets more LDS
-  size_t pool = tail + 64 * 8 * 16 <= (size_t)kSepLdsTarget ? (size_t)kSepLdsTarget - tail : (size_t)64 * 8 * 16;
-  pool &= ~(size_t)15;
-  return pool + tail;
-}
-static int separator_pool_pairs(const SceneParams& sp) {
-  const int total = sp.n_hull + sp.num_agents + sp.n_static + (sp.ent_enabled ? sp.num_agents * kBend : 0);
-  const size_t tail = 8 * sizeof(double) + (((size_t)(total + 8 + (sp.ent_enabled ? sp.num_agents : 0)) * sizeof(unsigned short) + 15) & ~(size_t)15);
-  return (int)((separator_lds_bytes(sp) - tail) / 16);
-}
+static SepLayout separator_layout_of(const SceneParams& sp) { return sep_layout(sp.n_hull, sp.num_agents, sp.n_static, sp.ent_enabled != 0); }
 
 // pack: segments per wave of the packed kernel, 0: the unpacked kernel; cert: the wave runs the zero-iteration certificate (ps.pre_tables,
-// ps.pre_sched_n and ps.presolved are given) — both are the launch plan's (launch_plan.h)
+// ps.pre_sched_n and ps.presolved are given) — both are the launch plan's (launch_plan.h).  The unpacked kernel's LDS: lds_layout.h; the packed
+// kernel keeps its own carve and the formula below.
 void launch_separator(int n_slots, const SceneParams& sp, const ProblemSet& ps, int pack, bool cert, hipStream_t st) {
   if (n_slots <= 0) return;
   if (pack > 0) {
@@ -1674,27 +1660,29 @@ void launch_separator(int n_slots, const SceneParams& sp, const ProblemSet& ps, 
     hipLaunchKernelGGL(separator_packed_kernel, dim3(n_slots * groups), dim3(64), lds_p, st, sp, ps, pairs, pack);
     return;
   }
-  const size_t lds = separator_lds_bytes(sp);
+  const SepLayout L = separator_layout_of(sp);
+  const size_t lds = (size_t)L.bytes;
   static DynLdsAttr attr[2];
   if (sp.sep_rule == 1) {
     (void)attr[1].ensure((const void*)separator_kernel<1>, lds);
-    hipLaunchKernelGGL(separator_kernel<1>, dim3(n_slots * NEP_MAX_POL), dim3(64), lds, st, sp, ps, separator_pool_pairs(sp));
+    hipLaunchKernelGGL(separator_kernel<1>, dim3(n_slots * NEP_MAX_POL), dim3(64), lds, st, sp, ps, L.pool_pairs);
   } else {
     (void)attr[0].ensure((const void*)separator_kernel<0>, lds);
-    hipLaunchKernelGGL(separator_kernel<0>, dim3(n_slots * NEP_MAX_POL), dim3(64), lds, st, sp, ps, separator_pool_pairs(sp));
+    hipLaunchKernelGGL(separator_kernel<0>, dim3(n_slots * NEP_MAX_POL), dim3(64), lds, st, sp, ps, L.pool_pairs);
   }
 }
 void launch_separator_redo(int n_slots, const SceneParams& sp, const ProblemSet& ps, hipStream_t st) {
   if (n_slots <= 0 || !ps.redo_count || !ps.redo_list) return;
-  const size_t lds = separator_lds_bytes(sp);
+  const SepLayout L = separator_layout_of(sp);
+  const size_t lds = (size_t)L.bytes;
   static DynLdsAttr attr[2];
   const int grid = n_slots * NEP_MAX_POL < 1024 ? n_slots * NEP_MAX_POL : 1024;
   if (sp.sep_rule == 1) {
     (void)attr[1].ensure((const void*)separator_redo_kernel<1>, lds);
-    hipLaunchKernelGGL(separator_redo_kernel<1>, dim3(grid), dim3(64), lds, st, sp, ps, separator_pool_pairs(sp));
+    hipLaunchKernelGGL(separator_redo_kernel<1>, dim3(grid), dim3(64), lds, st, sp, ps, L.pool_pairs);
   } else {
     (void)attr[0].ensure((const void*)separator_redo_kernel<0>, lds);
-    hipLaunchKernelGGL(separator_redo_kernel<0>, dim3(grid), dim3(64), lds, st, sp, ps, separator_pool_pairs(sp));
+    hipLaunchKernelGGL(separator_redo_kernel<0>, dim3(grid), dim3(64), lds, st, sp, ps, L.pool_pairs);
   }
 }
 
@@ -1883,14 +1871,15 @@ __global__ __launch_bounds__(256) void safety_resolve_kernel(const nep_traj_rec*
                                                              const unsigned char* __restrict__ conflict, const unsigned char* __restrict__ conflict_prev,
                                                              const int* __restrict__ entangles, nep_traj_rec* __restrict__ final_out, int* __restrict__ accept_out,
                                                              const int* __restrict__ active) {
-  extern __shared__ int sAcc[];   // [N] accept flags, [N] forced-bad flags, [N][W] symmetric conflict rows (32-bit words), [W] accepted ids
+  extern __shared__ int s_res[];   // ResolveLayout (lds_layout.h): [N] accept flags, [N] forced-bad flags, [N][W] symmetric conflict rows (32-bit words), [W] accepted ids
   // (kResolveParts workgroups per scene: each works out the accept flags — a few thousand bytes — and writes its share of the final
   // records: the copy, 120 KB per 64-agent scene, is what takes time, and one workgroup per scene left half of the chip idle)
   const int tid = threadIdx.x, scene = blockIdx.x / kResolveParts, part = blockIdx.x % kResolveParts;
-  const int W = (N + 31) >> 5;
-  int* sBad = sAcc + N;
-  unsigned* sRow = (unsigned*)(sBad + N);
-  unsigned* sBits = sRow + N * W;      // [W] accepted ids so far, when they do not fit eight registers (N > 256)
+  const ResolveLayout L = resolve_layout(N);
+  const int W = L.W;
+  int* sAcc = lds_at<int>(s_res, L.sAcc); int* sBad = lds_at<int>(s_res, L.sBad);
+  unsigned* sRow = lds_at<unsigned>(s_res, L.sRow);
+  unsigned* sBits = lds_at<unsigned>(s_res, L.sBits);      // [W] accepted ids so far, when they do not fit eight registers (N > 256)
   const unsigned char* Cm = conflict + (long)scene * N * N;
   const unsigned char* Cp = conflict_prev ? conflict_prev + (long)scene * N * N : nullptr;
   for (int e = tid; e < N * W + W; e += blockDim.x) sRow[e] = 0u;
@@ -1966,9 +1955,9 @@ void launch_safety(const nep_traj_rec* prev, const nep_traj_rec* fresh, int n_sc
   }
   hulls_of(fresh);
   hipLaunchKernelGGL(safety_conflict_kernel, dim3(n_scenes * ((N + 3) / 4)), dim3(256), 0, st, fresh, fresh, N, sp.num_pol, sp.T_span, ps.hull_xy, ps.hull_nv, conflict);
-  // (2 N + (N + 1) ceil(N / 32)) ints of dynamic LDS: quadratic in N — above the 64 KB default from N ~ 690 on, so the limit is
-  // raised explicitly (160 KB per CU: N up to ~1 100; beyond that the launch fails and HIPCHK(hipGetLastError()) reports it)
-  const size_t resolve_lds = (size_t)(2 * N + (N + 1) * ((N + 31) / 32)) * sizeof(int);
+  // (resolve_layout: quadratic in N — above the 64 KB default from N ~ 690 on, so the limit is raised explicitly (160 KB per CU:
+  // N up to ~1 100; beyond that the launch fails and HIPCHK(hipGetLastError()) reports it)
+  const size_t resolve_lds = (size_t)resolve_layout(N).bytes;
   static DynLdsAttr resolve_attr;
   (void)resolve_attr.ensure((const void*)safety_resolve_kernel, resolve_lds);
   hipLaunchKernelGGL(safety_resolve_kernel, dim3(n_scenes * kResolveParts), dim3(256), resolve_lds, st, prev, fresh, N, conflict, conflict_prev, entangles, final_out, accept_out, active);
@@ -2137,19 +2126,8 @@ __device__ __forceinline__ void fe_child_again(const SceneParams& sp, const nep_
   }
 }
 
-// LDS arrays are sized for the configured beam width (not the maximum), so that narrower beams leave room for
-// more workgroups per CU: cap = beam_width * num_samples^2 candidates per depth, hash tables a power of two above
-// 1.25x (per-depth voxel table) / 2x (visited voxels, beam_width * num_pol keys) their load.
-struct FeSizes { int cap, dd, vis, mb; };
-__host__ __device__ inline FeSizes fe_sizes(int beam_width, int num_samples, int num_pol) {
-  FeSizes z; z.cap = beam_width * num_samples * num_samples; if (z.cap < 64) z.cap = 64;
-  z.dd = 64; while (z.dd * 4 < z.cap * 5) z.dd *= 2;
-  z.vis = 64; while (z.vis < 2 * beam_width * num_pol) z.vis *= 2;
-  z.mb = beam_width <= 32 ? 32 : NEP_FE_MAX_BEAM;      // stride of the per-rank arrays (the beam's width rounded up: a width-32 beam does not pay for 64 ranks of LDS)
-  return z;
-}
+// (the sizes of the search's LDS arrays, fe_sizes, and their layout, fe_layout: lds_layout.h)
 constexpr unsigned long long kFeEmpty = ~0ull;
-constexpr int kFeObsLds = 24;   // shortlisted obstacles whose vertices are staged in LDS (the rest are read from global memory)
 
 __device__ __forceinline__ unsigned fe_hash(long long vox) { return (unsigned)(((unsigned long long)vox * 0x9E3779B97F4A7C15ull) >> 40); }
 
@@ -2223,9 +2201,7 @@ __global__ __launch_bounds__(256) void ent_pack_kernel(SceneParams sp, ProblemSe
   for (int k = 0; k < 2 * (ns + 1); k++) o[kEntPkHead + k] = sm[k];
 }
 
-#ifndef NEP_FE_ENT_WGS
-#define NEP_FE_ENT_WGS 3      // (round 4: 3 = 168 registers, 48 spilled, 52 KB of LDS at config 5) // workgroups per CU of the entangle instantiation: 2 = working records in global memory, registers bounded to 256 (19.9 ms per 2 048 config-5 searches); 1 = working records in LDS, 139 KB (27.4 ms: the list surgery is latency-bound, a second workgroup hides more than LDS saves)
-#endif
+// (NEP_FE_ENT_WGS, the workgroups per CU of the entangle instantiation: lds_layout.h)
 // BIG (with ENT): the instantiation that re-runs, after the launch proper, the few searches in which a child's entangle state outgrew
 // the fixed record (ea.redo_list): such a child — pruned and listed by the plain instantiation — is carried in a big record here
 // (ent_device.h), bounded by the reference's own rule only.  A kernel of its own because the big-record pass compiled into the
@@ -2244,34 +2220,33 @@ __global__ __launch_bounds__(256, WGS) void frontend_kernel(SceneParams sp, Prob
   else { if (ps.fe_count && (int)blockIdx.x >= *ps.fe_count) return; }      // (an active set: fe_order is the list of active slots, active_list_kernel)
   const int slot = BIG ? ea.redo_list[blockIdx.x] : (ps.fe_order ? ps.fe_order[blockIdx.x] : (int)blockIdx.x), scene = slot / sp.n_local, own = sp.first_local + (slot % sp.n_local);
   const int N = sp.num_agents, S = sp.n_static, W = fc.beam_width, ns = fc.num_samples, NC = ns * ns, D = sp.num_pol;
-  const FeSizes fz = fe_sizes(W, ns, D);
-  const int kFeCap = fz.cap, kFeDd = fz.dd, kFeVis = fz.vis, MB = fz.mb;
-  // ---- LDS carve ----
-  double* s_f = fe_smem;                                   // [kFeCap] f of candidate id
-  double* b_end = s_f + kFeCap;                            // [2][64][6]
-  double* b_g = b_end + 2 * MB * 6;           // [2][64]
-  double* b_dist = b_g + 2 * MB;              // [64]
-  double* b_f = b_dist + MB;                  // [64]
-  double* p_box = b_f + MB;                   // [64][4] box of every parent's children
-  double* o_aabb = p_box + MB * 4;            // [N+S][4] boxes of the shortlisted obstacles, dense
-  double* o_V = o_aabb + 4 * (N + S);                      // [kFeObsLds][16][2] their vertices (GJK walks them several times)
+  // ---- LDS carve (lds_layout.h) ----
+  const FeLayout FL = fe_layout(N, S, W, ns, D, ENT);      // (BIG: the lists of its own lie behind all of this, at ea.big_lds_off — FeLayout::big_lds_off of launch_frontend's call)
+  const int kFeCap = FL.z.cap, kFeDd = FL.z.dd, kFeVis = FL.z.vis, MB = FL.z.mb;
+  double* s_f = lds_at<double>(fe_smem, FL.s_f);             // [kFeCap] f of candidate id
+  double* b_end = lds_at<double>(fe_smem, FL.b_end);         // [2][64][6]
+  double* b_g = lds_at<double>(fe_smem, FL.b_g);             // [2][64]
+  double* b_dist = lds_at<double>(fe_smem, FL.b_dist);       // [64]
+  double* b_f = lds_at<double>(fe_smem, FL.b_f);             // [64]
+  double* p_box = lds_at<double>(fe_smem, FL.p_box);         // [64][4] box of every parent's children
+  double* o_aabb = lds_at<double>(fe_smem, FL.o_aabb);       // [N+S][4] boxes of the shortlisted obstacles, dense
+  double* o_V = lds_at<double>(fe_smem, FL.o_V);             // [kFeObsLds][16][2] their vertices (GJK walks them several times)
   // [kFeCap] f of the voxel winners, dense: written by the compaction and read by the rank count, when the shortlist's boxes and
   // vertices are dead — it lives in their storage when they are big enough (6.4 KB of the 51 a search held: with the per-rank arrays
   // at the beam's width the carve drops below 40 KB, four workgroups per CU instead of three; with the entangle check, where the same
   // storage is lent to the crossing lists in between, below 53 KB at config 5: three instead of two)
-  const bool rf_alias = 4 * (N + S) + kFeObsLds * kHullV * 2 >= kFeCap;
-  double* r_f = rf_alias ? o_aabb : o_V + kFeObsLds * kHullV * 2;
-  double* s_lat = o_V + kFeObsLds * kHullV * 2 + (rf_alias ? 0 : kFeCap);   // [4][NEP_FE_MAX_SAMPLES] lattice tables
-  long long* s_vox = (long long*)(s_lat + 4 * NEP_FE_MAX_SAMPLES);   // [kFeCap]
-  unsigned long long* v_key = (unsigned long long*)(s_vox + kFeCap);   // [kFeVis] visited voxels
-  int* d_slot = (int*)(v_key + kFeVis);                    // [kFeDd] voxel -> best candidate of the depth
-  int* o_nv = d_slot + kFeDd;                              // [N+S] dense
-  int* o_id = o_nv + (N + S);                              // [N+S] dense: obstacle index (agent j or N + static)
-  int* s_i = o_id + (N + S);                               // [32] counters (+ the path's ranks with the entangle check on)
-  unsigned short* r_id = (unsigned short*)(s_i + 32);      // [kFeCap] ids of the voxel winners, dense
-  unsigned char* s_state = (unsigned char*)(r_id + kFeCap);   // [kFeCap] 0 dead, 1 alive, 2 lost its voxel
-  signed char* p_parent = (signed char*)(s_state + kFeCap);   // [NEP_MAX_POL + 1][64]
-  signed char* p_comb = p_parent + (NEP_MAX_POL + 1) * MB;
+  double* r_f = lds_at<double>(fe_smem, FL.r_f);
+  double* s_lat = lds_at<double>(fe_smem, FL.s_lat);         // [4][NEP_FE_MAX_SAMPLES] lattice tables
+  long long* s_vox = lds_at<long long>(fe_smem, FL.s_vox);   // [kFeCap]
+  unsigned long long* v_key = lds_at<unsigned long long>(fe_smem, FL.v_key);   // [kFeVis] visited voxels
+  int* d_slot = lds_at<int>(fe_smem, FL.d_slot);             // [kFeDd] voxel -> best candidate of the depth
+  int* o_nv = lds_at<int>(fe_smem, FL.o_nv);                 // [N+S] dense
+  int* o_id = lds_at<int>(fe_smem, FL.o_id);                 // [N+S] dense: obstacle index (agent j or N + static)
+  int* s_i = lds_at<int>(fe_smem, FL.s_i);                   // [32] counters (+ the path's ranks with the entangle check on)
+  unsigned short* r_id = lds_at<unsigned short>(fe_smem, FL.r_id);         // [kFeCap] ids of the voxel winners, dense
+  unsigned char* s_state = lds_at<unsigned char>(fe_smem, FL.s_state);     // [kFeCap] 0 dead, 1 alive, 2 lost its voxel
+  signed char* p_parent = lds_at<signed char>(fe_smem, FL.p_parent);       // [NEP_MAX_POL + 1][64]
+  signed char* p_comb = lds_at<signed char>(fe_smem, FL.p_comb);
 
   const nep_fe_start* st = starts + slot;
   const double gx = st->goal[0], gy = st->goal[1];
@@ -2279,15 +2254,15 @@ __global__ __launch_bounds__(256, WGS) void frontend_kernel(SceneParams sp, Prob
   EntCtx ec;
   nep_fe_ent_state* my_work = nullptr;
   unsigned char* ent_lists = nullptr;
-  unsigned char* b_valid = (unsigned char*)(p_comb + (NEP_MAX_POL + 1) * MB);   // [64] may a plan end at this rank
+  unsigned char* b_valid = lds_at<unsigned char>(fe_smem, FL.b_valid);   // [64] may a plan end at this rank
   auto ent_node = [&](int d, int r) -> nep_fe_ent_state* { return ea.nodes + (((long)slot * (D + 1) + d) * W + r); };
   // ENT: per parent of the depth at hand, who can matter to ANY of its children (bit sets over the agents / statics; filled next
   // to the shortlist from the parent's children box, see there)
   const int MW = (N + 31) >> 5, SW = (S + 31) >> 5;
-  unsigned* m_ent = (unsigned*)(b_valid + MB + ((4 - ((3 * kFeCap) & 3)) & 3));      // [64][MW] agents whose tether a child's step may cross (aligned: every array before r_id is a multiple of four bytes)
-  unsigned* m_base = m_ent + MB * MW;               // [64][MW] agents whose base square a child may be near
-  unsigned* m_stat = m_base + MB * MW;              // [64][SW] static representatives a child's step may cross
-  unsigned char* f_bits = (unsigned char*)(m_stat + MB * SW);      // [N] ENT: per agent, the sampled steps in which its moving tether segment sweeps over our base (EntCtx::f_bits)
+  unsigned* m_ent = lds_at<unsigned>(fe_smem, FL.m_ent);        // [64][MW] agents whose tether a child's step may cross
+  unsigned* m_base = lds_at<unsigned>(fe_smem, FL.m_base);      // [64][MW] agents whose base square a child may be near
+  unsigned* m_stat = lds_at<unsigned>(fe_smem, FL.m_stat);      // [64][SW] static representatives a child's step may cross
+  unsigned char* f_bits = lds_at<unsigned char>(fe_smem, FL.f_bits);      // [N] ENT: per agent, the sampled steps in which its moving tether segment sweeps over our base (EntCtx::f_bits)
   if constexpr (ENT) {
     ec.N = N; ec.S = S; ec.own = own; ec.num_pol = D; ec.ns = ea.ns; ec.T_span = sp.T_span; ec.cable = fc.cable_length;
     ec.pb = ps.pb; ec.srep = ea.srep + (long)scene * sp.static_stride * 4; ec.slong = ea.slong + (long)scene * sp.static_stride * 2;
@@ -2300,8 +2275,8 @@ __global__ __launch_bounds__(256, WGS) void frontend_kernel(SceneParams sp, Prob
 #endif
     // the crossing lists of the children being merged (phase two of the propagation pass) live where the shortlist's boxes and
     // vertices and the winners' f values are: dead between a depth's GJK pass and its compaction / the next depth's shortlist
-    ent_lists = (unsigned char*)o_aabb;      // [n_merge][kEntLdsBytes]
-    my_work = NEP_FE_ENT_WGS == 1 ? (nep_fe_ent_state*)(((size_t)(f_bits + N) + 3 + 8 * MW + 7) & ~(size_t)7) + tid : ea.work + ((long)slot * 256 + tid);      // (one working record per thread, in LDS: the list surgery is a chain of dependent loads)
+    ent_lists = lds_at<unsigned char>(fe_smem, FL.ent_lists);      // [n_merge][kEntLdsBytes]
+    my_work = FL.work >= 0 ? lds_rec<nep_fe_ent_state>(fe_smem, FL.work) + tid : ea.work + ((long)slot * 256 + tid);      // (one working record per thread, in LDS: the list surgery is a chain of dependent loads)
     if (tid == 0) {
       nep_fe_ent_state* root = ent_node(0, 0);
       if (ea.init) {
@@ -2493,9 +2468,9 @@ __global__ __launch_bounds__(256, WGS) void frontend_kernel(SceneParams sp, Prob
     // survivor per thread: the propagation is two orders of magnitude dearer than anything else a child costs and only a fifth of
     // the children reach it, so examined in place the threads that drew two or three survivors kept the others waiting (pass 1 was
     // 65 % of a config-5 search, its critical path three propagations per depth instead of one).
-    unsigned short* p_list = r_id;      // (the GJK work list has been consumed when the survivors are listed; the winners are compacted after the propagation)
-    const int n_lists_a = (int)((sizeof(double) * (4 * (size_t)(N + S) + kFeObsLds * kHullV * 2 + (rf_alias ? 0 : kFeCap))) / kEntLdsBytes);      // crossing lists the borrowed storage holds (o_aabb, o_V, r_f when it has storage of its own)
-    const int n_lists_b = (int)((sizeof(int) * (size_t)kFeDd) / kEntLdsBytes), n_lists_c = (int)((sizeof(double) * (size_t)kFeCap) / kEntLdsBytes);      // ... the voxel table; s_f, and s_vox as many again
+    unsigned short* p_list = lds_at<unsigned short>(fe_smem, FL.p_list);      // (r_id's storage: the GJK work list has been consumed when the survivors are listed; the winners are compacted after the propagation)
+    const int n_lists_a = FL.n_lists_a;      // crossing lists the borrowed storage holds (o_aabb, o_V, r_f when it has storage of its own)
+    const int n_lists_b = FL.n_lists_b, n_lists_c = FL.n_lists_c;      // ... the voxel table; s_f, and s_vox as many again
     auto settle_voxel = [&](int id, FeChild& ch, unsigned iz) {
       const long long vox = ENT ? (long long)(((unsigned long long)(unsigned short)ch.vx << 48) | ((unsigned long long)(unsigned short)ch.vy << 32) | iz)
                                 : (((long long)ch.vx << 32) | (unsigned int)ch.vy);
@@ -2534,8 +2509,8 @@ __global__ __launch_bounds__(256, WGS) void frontend_kernel(SceneParams sp, Prob
     };
     // (fast instantiation: the lists of new crossings of the round's children were made by cross_round, below — hdr[rank * ns + j - 1] in
     // s_f's storage, the words in s_vox's — and this pass is the list surgery alone, ent_propagate_pre)
-    unsigned* x_hdr = (unsigned*)s_f; unsigned* x_pool = (unsigned*)s_vox;
-    const int x_pool_cap = (int)(sizeof(long long) * (size_t)kFeCap / sizeof(unsigned)), x_hdr_cap = (int)(sizeof(double) * (size_t)kFeCap / sizeof(unsigned));
+    unsigned* x_hdr = lds_at<unsigned>(fe_smem, FL.x_hdr); unsigned* x_pool = lds_at<unsigned>(fe_smem, FL.x_pool);
+    const int x_pool_cap = FL.x_words, x_hdr_cap = FL.x_words;
     auto propagate = [&](int id, int rank_in_round) {      // ENT, part two (see above)
       const int pr_ = id / NC, cc = id % NC;
       FeChild ch;
@@ -2557,7 +2532,7 @@ __global__ __launch_bounds__(256, WGS) void frontend_kernel(SceneParams sp, Prob
         L.cap = ea.fast_cap; L.bend_cap = ea.fast_bend;
         if constexpr (BIG) {
           if (ea.big_lds_off) {      // lists of up to kEntBigLdsCap entries in LDS of their own (one workgroup per CU: there is room), their betas in global memory
-            const lds_bytes bb = (lds_bytes)(unsigned)(size_t)((unsigned char*)fe_smem + ea.big_lds_off + tid * kEntBigLdsBytes);
+            const lds_bytes bb = (lds_bytes)(unsigned)(size_t)(lds_at<unsigned char>(fe_smem, ea.big_lds_off) + tid * kEntBigLdsBytes);
             L.id = (ent_lds_short)bb; L.cs = (ent_lds_char)(bb + 2 * kEntBigLdsCap); L.bend = (ent_lds_char)(bb + 3 * kEntBigLdsCap);
             L.beta = ea.big_beta + ((long)blockIdx.x * 256 + tid) * kEntBigLdsCap;
             L.cap = ea.big.cap < kEntBigLdsCap ? ea.big.cap : kEntBigLdsCap; L.bend_cap = kEntBigLdsBend;
@@ -2712,10 +2687,10 @@ __global__ __launch_bounds__(256, WGS) void frontend_kernel(SceneParams sp, Prob
       //      own — see ent_cross_step, ent_device.h.  The packed records of the depth's candidate agents (the union of the parents'
       //      masks) are staged in the storage the crossing lists use AFTER this pass (o_aabb, o_V); one thread per (child, step) walks
       //      its parent's candidates in index order out of LDS and leaves the step's list in the pool. ----
-      const int x_stage_cap = (ea.packed && ea.pk_stride > 0) ? (int)((sizeof(double) * (4 * (size_t)(N + S) + kFeObsLds * kHullV * 2)) / (sizeof(double) * (size_t)ea.pk_stride)) : 0;
-      unsigned* x_U = (unsigned*)(((size_t)(f_bits + N) + 3) & ~(size_t)3);      // [MW] union of the parents' agent masks; [MW] popcounts before each word (storage of their own behind f_bits)
-      unsigned short* x_ids = (unsigned short*)o_id;           // [n_stage] the staged agents, ascending (the shortlist's ids are dead by now)
-      double* x_rec = o_aabb;                                  // [n_stage][pk_stride]
+      const int x_stage_cap = (ea.packed && ea.pk_stride > 0) ? FL.x_rec_bytes / (int)(sizeof(double) * (size_t)ea.pk_stride) : 0;
+      unsigned* x_U = lds_at<unsigned>(fe_smem, FL.x_U);        // [MW] union of the parents' agent masks; [MW] popcounts before each word (storage of their own behind f_bits)
+      unsigned short* x_ids = lds_at<unsigned short>(fe_smem, FL.x_ids);      // [n_stage] the staged agents, ascending (o_id's storage: the shortlist's ids are dead by now)
+      double* x_rec = lds_at<double>(fe_smem, FL.x_rec);        // [n_stage][pk_stride] (o_aabb's and o_V's storage)
       auto cross_round = [&](int b0, int nr, bool first) {
         if (first) {      // (once per depth: who is staged)
           if (tid < MW) { unsigned u = 0u; for (int q = 0; q < nb_prev; q++) u |= m_ent[q * MW + tid]; x_U[tid] = u; }
@@ -3006,29 +2981,6 @@ void launch_gjk_explicit(int n_prob, const int* a_off, const double* a_xy, const
   hipLaunchKernelGGL(gjk_explicit_kernel, dim3((n_prob + 63) / 64), dim3(64), 0, st, n_prob, a_off, a_xy, b_xy, hit);
 }
 
-size_t frontend_children_cap(const nep_fe_cfg& fc, int num_pol) { return (size_t)fe_sizes(fc.beam_width, fc.num_samples, num_pol).cap; }
-// survivors per round of the entangle front end's propagation pass (fast instantiation: the crossing lists that fit the borrowed LDS,
-// as the kernel counts them) x sampled steps x kEntAddCap words: the global fallback of cross_round's LDS pool
-size_t frontend_ent_xpool_words(const SceneParams& sp, const nep_fe_cfg& fc, int ent_ns) {
-  const size_t NS = (size_t)sp.num_agents + sp.n_static;
-  const FeSizes z = fe_sizes(fc.beam_width, fc.num_samples, sp.num_pol);
-  const bool rf_alias = 4 * NS + kFeObsLds * kHullV * 2 >= (size_t)z.cap;
-  size_t n = (sizeof(double) * (4 * NS + kFeObsLds * kHullV * 2 + (rf_alias ? 0 : (size_t)z.cap))) / kEntLdsBytes + (sizeof(int) * (size_t)z.dd) / kEntLdsBytes;
-  if (n > 256) n = 256;
-  return n * (size_t)(ent_ns > 0 ? ent_ns : 1) * kEntAddCap;
-}
-size_t frontend_lds_bytes(const SceneParams& sp, const nep_fe_cfg& fc, bool ent) {
-  const size_t NS = (size_t)sp.num_agents + sp.n_static;
-  const FeSizes z = fe_sizes(fc.beam_width, fc.num_samples, sp.num_pol);
-  const size_t MB = (size_t)z.mb;
-  const bool rf_alias = 4 * NS + kFeObsLds * kHullV * 2 >= (size_t)z.cap;      // (as in the kernel's carve)
-  size_t b = sizeof(double) * ((size_t)z.cap * (rf_alias ? 1 : 2) + 2 * MB * 6 + 2 * MB + 2 * MB + 4 * MB + 4 * NS + kFeObsLds * kHullV * 2 + 4 * NEP_FE_MAX_SAMPLES)
-           + sizeof(long long) * ((size_t)z.cap + z.vis) + sizeof(int) * (z.dd + 2 * NS + 32)
-           + sizeof(unsigned short) * z.cap + z.cap + 2 * (NEP_MAX_POL + 1) * MB + MB;
-  if (ent) b = ((b + 3) & ~(size_t)3) + sizeof(unsigned) * MB * (2 * (size_t)((sp.num_agents + 31) >> 5) + (size_t)((sp.n_static + 31) >> 5)) + (((size_t)sp.num_agents + 3) & ~(size_t)3) + sizeof(unsigned) * 2 * (size_t)((sp.num_agents + 31) >> 5) + (NEP_FE_ENT_WGS == 1 ? 256 * sizeof(nep_fe_ent_state) + 8 : 0);      // (f_bits, then cross_round's union mask and its prefix counts)
-  return (b + 15) & ~(size_t)15;
-}
-
 // The outputs of the inactive slots of a front-end launch (nep_batch_set_active): result NEP_FE_SKIPPED with every other field zero, the
 // guess K = 0 with the start's t_start (what a masked replan that follows reads of it) and nothing else of it written.
 __global__ __launch_bounds__(64) void skipped_fe_kernel(SceneParams sp, const int* __restrict__ active, int n_slots, const nep_fe_start* __restrict__ starts,
@@ -3058,7 +3010,7 @@ void launch_frontend(int n_slots, const SceneParams& sp, const ProblemSet& ps_in
     hipLaunchKernelGGL(skipped_fe_kernel, dim3((n_slots + 63) / 64), dim3(64), 0, st, sp, ps.active, n_slots, starts, guess_out, res_out);
   }
   const bool ent = ea != nullptr;
-  const size_t lds = frontend_lds_bytes(sp, fc, ent);
+  const size_t lds = (size_t)fe_layout(sp.num_agents, sp.n_static, fc.beam_width, fc.num_samples, sp.num_pol, ent).bytes;      // (lds_layout.h)
   // a search whose LDS leaves room for four workgroups on a CU (160 KB / 4) runs the instantiation bounded to 128 registers
   // (11 spilled); larger ones — more obstacles, a wider beam — the one bounded for three
   const bool four = !ent && lds <= (size_t)40 * 1024 && !g_debug.fe_three;      // (A/B, nep_debug_set_global_option "fe_three": keep the three-workgroup instantiation)
@@ -3077,8 +3029,9 @@ void launch_frontend(int n_slots, const SceneParams& sp, const ProblemSet& ps_in
     if (ea->redo_list && ea->big.base && ea->redo_cap > 0) {      // the searches listed by that launch, again, with big records (nearly always none: the workgroups return at once)
       static DynLdsAttr attr_big;
       FeEntArgs eb = *ea;
-      size_t lds_b = lds;
-      if (eb.big_beta && lds + 256 * (size_t)kEntBigLdsBytes <= (size_t)160 * 1024) { eb.big_lds_off = (int)lds; lds_b = lds + 256 * (size_t)kEntBigLdsBytes; } else eb.big_lds_off = 0;
+      const FeLayout lb = fe_layout(sp.num_agents, sp.n_static, fc.beam_width, fc.num_samples, sp.num_pol, true, eb.big_beta != nullptr);      // (its lists in LDS when it has their betas' memory and the launch holds them)
+      eb.big_lds_off = lb.big_lds_off;
+      const size_t lds_b = (size_t)lb.bytes;
       (void)attr_big.ensure((const void*)frontend_kernel<true, 1, true>, lds_b);
       hipLaunchKernelGGL((frontend_kernel<true, 1, true>), dim3(ea->redo_cap < n_slots ? ea->redo_cap : n_slots), dim3(256), lds_b, st, sp, ps, fc, starts, guess_out, res_out, eb);
     }
@@ -3141,8 +3094,8 @@ __global__ __launch_bounds__(64) void ent_check_kernel(SceneParams sp, ProblemSe
   // interval (ent_agent_may_cross against the box of the samples), then lane 0 walks the reference's test over the rest
   extern __shared__ __attribute__((aligned(16))) unsigned m_ec[];
   const int N = sp.num_agents, S = sp.n_static, lane = threadIdx.x;
-  unsigned* m_agent = m_ec; unsigned* m_static = m_ec + ((N + 63) >> 6) * 2;
-  const int ec_lds_words = 2 * (((N + 63) >> 6) + ((S + 63) >> 6) + 1);      // (the masks: launch_ent_check sizes the same; an even number of words, so that the record behind them is 8-byte aligned)
+  const EntCheckLayout L = ent_check_layout(N, S);      // (lds_layout.h)
+  unsigned* m_agent = lds_at<unsigned>(m_ec, L.m_agent); unsigned* m_static = lds_at<unsigned>(m_ec, L.m_static);
   const long idx = blockIdx.x;
   const int scene = (int)(idx / N), a = (int)(idx % N);
   const nep_traj_rec* r = fresh + idx;
@@ -3180,7 +3133,7 @@ __global__ __launch_bounds__(64) void ent_check_kernel(SceneParams sp, ProblemSe
     ec.m_agent = m_agent; ec.m_static = m_static;
     // (the working record in LDS: lane 0's list surgery is a chain of dependent reads and writes of this record — in global memory
     // every one of them was a round trip)
-    nep_fe_ent_state* wk = (nep_fe_ent_state*)(m_ec + ec_lds_words);
+    nep_fe_ent_state* wk = lds_rec<nep_fe_ent_state>(m_ec, L.work);
     if (ea.init) ent_copy(wk, ea.init + idx); else { long* z = (long*)wk; for (int i = 0; i < (int)(sizeof(nep_fe_ent_state) / 8); i++) z[i] = 0; }
     double arc = 0.0;
     unsigned add_tail[kEntAddCap - EntAdd::reg];
@@ -3199,7 +3152,7 @@ __global__ __launch_bounds__(64) void ent_check_kernel(SceneParams sp, ProblemSe
 void launch_ent_check(const SceneParams& sp, const ProblemSet& ps, const FeEntArgs& ea, const nep_traj_rec* fresh, int n_scenes, double cable, int* entangles, hipStream_t st) {
   const long total = (long)n_scenes * sp.num_agents;
   if (total <= 0) return;
-  const size_t lds = sizeof(unsigned) * 2 * (size_t)(((sp.num_agents + 63) >> 6) + ((sp.n_static + 63) >> 6) + 1) + sizeof(nep_fe_ent_state);
+  const size_t lds = (size_t)ent_check_layout(sp.num_agents, sp.n_static).bytes;
   if (ea.packed && ea.ns <= 8) {      // the packed records of the NEW trajectories (the re-check reads interval 0 only; the kernel packs them all: 10 us)
     const long np_ = (long)n_scenes * sp.num_agents * sp.num_pol;
     hipLaunchKernelGGL(ent_pack_kernel, dim3((unsigned)((np_ + 255) / 256)), dim3(256), 0, st, sp, ps, ea, n_scenes);

@@ -6,6 +6,7 @@
 
 #include "nep_tables.h"
 #include "launch_plan.h"
+#include "lds_layout.h"
 #include "../../include/neptune_frontend.h"
 #include "../../include/neptune_fleet.h"
 #include "../../include/neptune_backend_debug.h"
@@ -215,7 +216,7 @@ struct FeEntArgs {
   const nep_fe_ent_state* init;  // [slots] entangle state at point A, or null (empty)
   nep_fe_ent_state* nodes;       // [slots][num_pol+1][beam_width] states of the installed nodes
   nep_fe_ent_state* work;        // [scenes * N] one working record per thread of ent_check_kernel
-  nep_fe_ent_state* saved;       // [slots][children cap] the state every surviving child of the depth at hand arrived with (frontend_children_cap)
+  nep_fe_ent_state* saved;       // [slots][children cap] the state every surviving child of the depth at hand arrived with (fe_sizes' cap)
   double* saved_arc;             // [slots][children cap] and its sampled arc length
   double* st_f; long long* st_vox;      // [slots][children cap] f and voxel key of the children that survive the propagation pass: parked here while the LDS arrays that hold them (s_f, s_vox) are lent to the crossing lists
   int* case_out;                 // [slots][NEP_MAX_POL][N] (out) or null
@@ -224,14 +225,12 @@ struct FeEntArgs {
   int pk_stride;
   EntBigPool big;                // front end: where states beyond the fixed record go (base == null: such children are pruned and flagged)
   EntBigPool big_check;          // the same for the safety pass's re-check (records of three times the bound; its counter is zeroed by ent_sample_kernel)
-  int big_lds_off;               // big-record instantiation: byte offset, in the dynamic LDS, of its per-thread lists (kEntBigLdsBytes each), or 0: none (the launch's LDS would not hold them)
+  int big_lds_off;               // big-record instantiation: byte offset, in the dynamic LDS, of its per-thread lists (kEntBigLdsBytes each), or 0: none (the launch's LDS would not hold them) — FeLayout::big_lds_off
   double* big_beta;              // [redo_cap][256][kEntBigLdsCap] betas of those lists
   int* redo_list; int* redo_count; int redo_cap;      // front end: searches in which a child outgrew the fixed record, listed by frontend_kernel<true, W> for frontend_kernel<true, 2, true> (beyond redo_cap: they stay flagged)
   unsigned* xpool; int xpool_stride;      // front end (fast instantiation): per slot, room for the lists of new crossings of a round's (child, step) pairs that do not fit the LDS pool ([slots][xpool_stride] words: kEntAddCap per pair), see cross_round
   int fast_cap, fast_add, fast_bend;      // front end: what the fixed record's path accepts (<= NEP_FE_ENT_CAP, 32, NEP_MAX_BEND; nep_batch_set_fe_ent_fast_caps — the tests shrink them to drive ordinary scenes through the big records)
 };
-size_t frontend_children_cap(const nep_fe_cfg& fc, int num_pol);
-size_t frontend_ent_xpool_words(const SceneParams& sp, const nep_fe_cfg& fc, int ent_ns);      // words per slot of FeEntArgs::xpool      // children per depth of one search (beam_width x lattice)
 // (order_buf: [slots] scratch for the launch order, used when the previous launch left its keys — have_history — and the launch is
 // more than one wave of workgroups; null: slot order)
 void launch_frontend(int n_slots, const SceneParams& sp, const ProblemSet& ps, const nep_fe_cfg& fc, const nep_fe_start* starts,
@@ -261,7 +260,6 @@ struct AuditArgs {
   AuditPart* part;               // [scenes][n_chunks][N] scratch
   nep_audit* out;                // [scenes][N] accumulated into
 };
-size_t audit_lds_bytes(int N, int S, int vstride);
 void launch_audit(const AuditArgs& aa, hipStream_t st);
 // nep_batch_fleet_* (fleet_kernels.hip, include/neptune_fleet.h): the committed plans of every slot.  All device pointers.
 struct FleetArgs {
@@ -295,7 +293,7 @@ void launch_fleet_tick(const FleetArgs& fa, hipStream_t st);
 // flags are FleetArgs'; everything else is the handle's mission state.  All device pointers.
 struct FleetMissionArgs {
   nep_mission_cfg cfg;
-  size_t lds_bytes;              // mission_lds_bytes of the handle's largest scene
+  size_t lds_bytes;              // mission_layout's bytes for the handle's agents and the largest keep-out set
   double* t_issue; double* length; int* completed;      // [slots]
   int* counts;                   // [slots][4]: issued, reached, timed out, no goal
   double* sums;                  // [slots][2]: leg time, leg length
@@ -306,7 +304,6 @@ struct FleetMissionArgs {
   const int* koff;               // [scenes][NEP_MISSION_MAX_POLY + 1]
   const double* kxy;             // [scenes][NEP_MISSION_MAX_VERT][2]
 };
-size_t mission_lds_bytes(int N, int n_vert, int n_poly);
 void launch_fleet_mission_seed(const FleetMissionArgs& ma, const FleetArgs& fa, hipStream_t st);
 void launch_fleet_mission(const FleetMissionArgs& ma, const FleetArgs& fa, hipStream_t st);
 // the fleet recorder (fleet_recorder_kernels.hip): nep_batch_fleet_snapshot / _snapshot_ring / _restore.  Section i of a scene block
