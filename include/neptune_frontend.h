@@ -36,7 +36,8 @@
  *   in-place update of an open node on every second such event, the "nearest the start" fallback node —
  *   with the two things that make the reference irreproducible turned into parameters (the lattice
  *   order, and a budget of pops in place of the wall clock).  Bit-identical to oracle/'s
- *   orc_frontend_astar.  Entangle check off only: an entangle-aware A* has no oracle yet.
+ *   orc_frontend_astar.  With the entangle check on it is nep_batch_frontend_astar_ent (below): the same search with a tether
+ *   state per node, bit-identical to its Python restatement, tests/astar_ent_ref.py.
  */
 #ifndef NEPTUNE_FRONTEND_H_
 #define NEPTUNE_FRONTEND_H_
@@ -117,15 +118,17 @@ typedef struct nep_fe_result {
   int32_t n_collision_free;       /* ... and the collision tests                                   */
   int32_t goal_occupied;          /* setUp's goal_occupied_ (:210-226)                             */
   int32_t _pad;                   /* entangle check on: bit 3 = the pool of big records ran out (ent_overflow); bits 8
-                                     and up = children of this search whose state went into a big record; nep_batch_frontend_astar:
-                                     bit 4 = the search ran into a node pool smaller than the reference's; else 0    */
+                                     and up = children of this search whose state went into a big record; nep_batch_frontend_astar and
+                                     nep_batch_frontend_astar_ent: bit 4 = the search ran into a node pool smaller than the
+                                     reference's; else 0                                                              */
   double cost;                    /* g + bias*h of the returned node                               */
   double dist_to_goal;
   int32_t n_entangled;            /* children pruned by entanglesWithOtherAgents (entangle check on)        */
   int32_t ent_overflow;           /* 1: a child needed a big record and the handle's pool had none left (pruned), or
                                      more than 256 searches of one launch needed big records (the ones beyond keep
                                      the fixed record's limits: _pad bits 0-2 say which) — deviations from the
-                                     reference's rule; 0 in every test and bench leg                                */
+                                     reference's rule; 0 in every test and bench leg.  nep_batch_frontend_astar_ent: 1 = a
+                                     child's state outgrew the fixed record and was dropped (it has no big records)  */
 } nep_fe_result;
 
 /* Front end of every slot of the batch handle, asynchronous on `stream`.
@@ -174,6 +177,36 @@ int nep_batch_frontend(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_traj_rec
 int nep_batch_set_fe_astar(nep_batch_t* h, int32_t max_pops, int32_t max_nodes, const int32_t* order, int32_t n_order);
 int nep_batch_frontend_astar(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_traj_rec* d_committed, const nep_fe_start* d_start,
                              nep_guess* d_guess, nep_fe_result* d_result, void* stream);
+
+/* ---- The reference's best-first search with enable_entangle_check -------------------------------------------------------------
+ * nep_batch_frontend_astar with what "enable_entangle_check on" (below) adds to a search node, as the reference's run does:
+ *   child        the parent's entangle state (the root: d_ent_init[slot], NULL = empty) through entanglesWithOtherAgents; true drops
+ *                the child (n_entangled).  g = parent g + sampled arc length, h = distance to the goal + 0.3 per crossing + 1.0 per
+ *                bend point
+ *   voxel table  the key is (ix, iy, getIz(state)), for the root expansion's inserts too; an open node updated in place keeps its
+ *                own entangle state (kinodynamic_search.cpp:1204 is commented out)
+ *   pop          after the hulls and statics, the other agents' 0.7 m base squares; the closest-so-far rule and the goal test both
+ *                ask for a valid end point (every active case count <= 1): an invalid node at the goal is expanded like any other
+ *   result       as nep_batch_frontend_astar, with n_entangled; d_case_out [slots][NEP_MAX_POL][N] (may be NULL) as
+ *                nep_batch_frontend_ent: row i from the state at the START of segment i of the returned path, rows at and beyond K
+ *                zero; with pad_hold the held segments keep the returned node's state
+ *   capacity     a node's state is the fixed record: a child whose list would outgrow NEP_FE_ENT_CAP entries, whose sampled step
+ *                adds more than 32 crossings or whose bend points would exceed NEP_MAX_BEND is DROPPED, not counted in n_entangled,
+ *                and the search says so: nep_fe_result.ent_overflow = 1 and NEP_E_CAP from nep_batch_check (a flag of its own, next
+ *                to the pool's bit 4 of _pad).  Where num_agents + n_static <= NEP_FE_ENT_CAP the reference's own prune binds first.
+ *                No big records here.  A malformed state at A (counts beyond the record, a bend index off the list) is flagged the
+ *                same way and the search starts from the empty state.
+ * Budget, order and node pool come from nep_batch_set_fe_astar (NEP_E_STATE before it).  Unsharded handle created with
+ * enable_entangle (else NEP_E_STATE); cfg->enable_entangle != 0 (else NEP_E_ARG); cfg->num_samples^2 == n_order when an order is
+ * set (else NEP_E_ARG); with static obstacles nep_batch_set_static_reps first.  Active sets and several scenes per launch as
+ * nep_batch_frontend_astar (an inactive slot's case rows are not written, as by nep_batch_frontend_ent).
+ * The FIRST call (and the first after a nep_batch_set_fe_astar that enlarges the pools) allocates, so it must be made eagerly, which
+ * is nep_batch_frontend_ent's contract; later calls allocate nothing and can be captured.  Device memory per slot, beside
+ * nep_batch_set_fe_astar's: max_nodes * NEP_FE_ASTAR_ENT_NODE_BYTES bytes of node states and 4 bytes per entry of the voxel table —
+ * 9.1 MB more at 20 000 nodes (13.2 MB in all), 1.2 MB more at the default of max_pops = 100.                                   */
+#define NEP_FE_ASTAR_ENT_NODE_BYTES 456
+int nep_batch_frontend_astar_ent(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_traj_rec* d_committed, const nep_fe_start* d_start, const nep_fe_ent_state* d_ent_init,
+                                 nep_guess* d_guess, nep_fe_result* d_result, int32_t* d_case_out, void* stream);
 
 /* The same against all-gathered hull blocks (multi-GPU rounds, include/neptune_backend.h:
  * nep_batch_hulls -> all-gather -> nep_batch_frontend_hulls -> nep_batch_replan_hulls).            */

@@ -348,6 +348,15 @@ class BatchBackend:
                                            d_result.data_ptr() if d_result is not None else None,
                                            d_case_out.data_ptr() if d_case_out is not None else None, st.cuda_stream))
 
+    def frontend_astar_ent(self, fe_cfg, d_committed, d_start, d_guess, d_result=None, d_case_out=None, d_ent_init=None, stream=None):
+        """frontend_ent() with the reference's best-first search in place of the beam (set_fe_astar first; fe_cfg.enable_entangle set;
+        one wave per slot).  Its first call allocates the nodes' states: make it before any capture."""
+        st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        check(lib().nep_batch_frontend_astar_ent(self._h, C.byref(fe_cfg), d_committed.data_ptr(), d_start.data_ptr(),
+                                                 d_ent_init.data_ptr() if d_ent_init is not None else None, d_guess.data_ptr(),
+                                                 d_result.data_ptr() if d_result is not None else None,
+                                                 d_case_out.data_ptr() if d_case_out is not None else None, st.cuda_stream))
+
     def frontend_ent_hulls(self, fe_cfg, d_blocks, d_start, d_guess, d_result=None, d_case_out=None, d_ent_init=None, stream=None):
         """frontend_ent against all-gathered hull blocks (sharded handle created with enable_entangle): nep_batch_frontend_ent_hulls"""
         st = stream if stream is not None else self.torch.cuda.current_stream(self.device)

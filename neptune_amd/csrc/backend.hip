@@ -161,6 +161,7 @@ struct Engine {
   const int* active = nullptr;       // the active set (nep_batch_set_active): device [scenes][N], or null
   // the best-first front end (nep_batch_set_fe_astar): per-slot node pools, heaps and voxel tables; the budget and the lattice order
   DevBuf<unsigned char> d_as_nodes; DevBuf<int> d_as_heap, d_as_val, d_as_order; DevBuf<unsigned long long> d_as_key;
+  DevBuf<unsigned> d_as_iz; DevBuf<unsigned char> d_as_states;      // nep_batch_frontend_astar_ent: the voxel key's third word, the nodes' entangle states
   bool as_ready = false; int as_max_pops = 0, as_pool = 0, as_tab = 0, as_n_order = 0;
   DevBuf<int> d_act, d_fe_act;       // [slots + 1] compacted active slots + count (active_list_kernel): the QP launches', the front end's
   ListBuf d_track_lsave;      // nep_batch_track_ent_lists: the same scratch in the list form, of the largest cap seen
@@ -1453,6 +1454,38 @@ int nep_batch_frontend_ent_hulls(nep_batch_t* h, const nep_fe_cfg* cfg, const vo
   return run_frontend(h, ps, *cfg, d_start, d_guess, d_result, &ea, stream);
 }
 
+// the reference's best-first search with the entangle check (fe_astar_ent.h): nep_batch_frontend_ent's inputs, nep_batch_set_fe_astar's
+// budget, order and pools, plus a state per node and the voxel key's third word (allocated here, at the first call: eager)
+int nep_batch_frontend_astar_ent(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_traj_rec* d_committed, const nep_fe_start* d_start,
+                                 const nep_fe_ent_state* d_ent_init, nep_guess* d_guess, nep_fe_result* d_result, int32_t* d_case_out, void* stream) {
+  if (!h || !cfg || !d_committed || !d_start || !d_guess) return fail(NEP_E_ARG, "null argument");
+  Engine& E = h->eng;
+  if (!h->cfg.enable_entangle) return fail(NEP_E_STATE, "nep_batch_frontend_astar_ent needs a handle created with enable_entangle");
+  if (h->cfg.n_local != h->cfg.num_agents) return fail(NEP_E_STATE, "nep_batch_frontend_astar_ent runs on an unsharded handle (n_local == num_agents)");
+  if (!cfg->enable_entangle) return fail(NEP_E_ARG, "nep_batch_frontend_astar_ent: enable_entangle must be set in the front-end configuration (without the check: nep_batch_frontend_astar)");
+  if (!E.as_ready) return fail(NEP_E_STATE, "nep_batch_frontend_astar_ent: call nep_batch_set_fe_astar first (it allocates the searches' pools)");
+  if (!(cfg->num_samples >= 2 && cfg->num_samples <= NEP_FE_MAX_SAMPLES && cfg->voxel_size > 0.0 && cfg->j_max > 0.0)) return fail(NEP_E_ARG, "bad front-end configuration");
+  if (E.as_n_order && cfg->num_samples * cfg->num_samples != E.as_n_order) return fail(NEP_E_ARG, "nep_batch_frontend_astar_ent: num_samples^2 differs from the n_order of nep_batch_set_fe_astar");
+  const ProblemSet ps = round_set(h);
+  h->fe_committed = d_committed;
+  launch_hulls_ts(d_committed, h->cfg.n_scenes, h->cfg.num_agents, &d_start->t_start, (long)sizeof(nep_fe_start), E.sp, ps, (hipStream_t)stream, grouped_hulls(E.sp, h->cfg.n_scenes, h->cfg.num_agents));
+  FeEntArgs ea{};
+  if (int e = ent_prepare(h, cfg->ent_samples, 0, d_committed, &d_start->t_start, (long)sizeof(nep_fe_start) * E.sp.n_local, ea, (hipStream_t)stream)) return e;
+  ea.init = d_ent_init; ea.case_out = d_case_out;
+  ea.pk_stride = 2 + 2 * kBend + 2 * (ea.ns + 1);
+  if (int e = E.d_fe_packed.ensure((size_t)h->cfg.n_scenes * h->cfg.num_agents * h->cfg.num_pol * ea.pk_stride)) return e;
+  ea.packed = E.d_fe_packed.p;
+  if (int e = E.d_as_iz.ensure((size_t)h->slots * E.as_tab)) return e;
+  if (int e = E.d_as_states.ensure((size_t)h->slots * E.as_pool * NEP_FE_ASTAR_ENT_NODE_BYTES)) return e;
+  FeAstarArgs aa{};
+  aa.max_pops = E.as_max_pops; aa.pool = E.as_pool; aa.tab_cap = E.as_tab; aa.order = E.as_n_order ? E.d_as_order.p : nullptr;
+  aa.nodes = E.d_as_nodes.p; aa.heap = E.d_as_heap.p; aa.tab_key = E.d_as_key.p; aa.tab_val = E.d_as_val.p;
+  const FeAstarEntArgs xa{E.d_as_iz.p, E.d_as_states.p};
+  launch_frontend_astar_ent(h->slots, E.sp, ps, *cfg, aa, xa, ea, d_start, d_guess, d_result, (hipStream_t)stream, E.d_fe_act.p);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 int nep_batch_safety_commit_ent(nep_batch_t* h, const nep_traj_rec* d_prev, const nep_traj_rec* d_new, const nep_guess* d_guess,
                                 const nep_fe_ent_state* d_ent_init, int32_t ent_samples, double cable_length, nep_traj_rec* d_final,
                                 int32_t* d_accept, void* stream) {
@@ -2416,6 +2449,7 @@ int nep_batch_check(nep_batch_t* h, void* stream) {
   if (flags & NEP_FLAG_FLEET) return fail(NEP_E_CAP, "nep_batch_fleet_commit: an accepted plan or composed trajectory would have outgrown the ring (ring_cap states), NEP_TRAJ_MAX_SEG intervals, or A was already flown (the slot kept its plan: outcome NEP_FLEET_CAP, flags in nep_batch_fleet_state)");
   if (flags & NEP_FLAG_MISSION) return fail(NEP_E_CAP, "nep_batch_fleet_mission: a draw found no goal among max_attempts candidates (the slot kept its goal: NEP_FLEET_FLAG_GOAL in nep_batch_fleet_state's flags, no_goal in nep_batch_fleet_mission_state's counts)");
   if (flags & NEP_FLAG_FE_ASTAR_POOL) return fail(NEP_E_CAP, "nep_batch_frontend_astar: a search ran into its node pool (it stopped creating nodes there: bit 4 of nep_fe_result._pad): nep_batch_set_fe_astar's max_nodes");
+  if (flags & NEP_FLAG_FE_ASTAR_ENT_REC) return fail(NEP_E_CAP, "nep_batch_frontend_astar_ent: a child's entangle state outgrew the fixed record — NEP_FE_ENT_CAP crossings, 32 new crossings in one sampled step or NEP_MAX_BEND bend points — and was dropped (nep_fe_result.ent_overflow), or a state at A was malformed");
   if (flags & NEP_FLAG_ENT_BETA) return fail(NEP_E_ARG, "an entangle state passed to the front end has a non-zero beta for an agent crossing (the reference's calculateBetaForCase makes it 0.0)");
   if (flags & NEP_FLAG_HULL_OVERFLOW) return fail(NEP_E_CAP, "an interval overlaps more than NEP_HULL_MAX_CP/4 committed segments (or its hull has more than NEP_HULL_MAX_V vertices)");
   return 0;

@@ -3042,6 +3042,8 @@ void launch_frontend(int n_slots, const SceneParams& sp, const ProblemSet& ps_in
 
 // the reference's best-first search over the same lattice (nep_batch_frontend_astar)
 #include "fe_astar.h"
+// ... and with the entangle check (nep_batch_frontend_astar_ent)
+#include "fe_astar_ent.h"
 
 // Neptune::SamplePointsOfIntervals (neptune.cpp:500-565) for every committed trajectory of every scene:
 // sampled[scene][j][interval][0..ns][2] on the round's grid, present[scene][j] = the trajectory exists (trajs_ holds it)

@@ -126,6 +126,7 @@ struct ProblemSet {
 __device__ __forceinline__ bool slot_active(const SceneParams& sp, const int* active, int slot) {
   return active == nullptr || active[(long)(slot / sp.n_local) * sp.num_agents + sp.first_local + slot % sp.n_local] != 0;
 }
+constexpr int NEP_FLAG_FE_ASTAR_ENT_REC = 512;   // nep_batch_frontend_astar_ent: a child's entangle state outgrew the fixed record (list, a step's crossings or bend points; the child was dropped: nep_fe_result.ent_overflow), or a state at A was malformed
 constexpr int NEP_FLAG_FE_ASTAR_POOL = 256;   // nep_batch_frontend_astar: a search ran into a node pool smaller than the reference's 20 000 (nep_batch_set_fe_astar's max_nodes): it stopped creating nodes there
 constexpr int NEP_FLAG_MISSION = 128;       // nep_batch_fleet_mission: a draw found no goal among max_attempts candidates (the slot kept its goal; NEP_FLEET_FLAG_GOAL)
 constexpr int NEP_FLAG_FLEET = 64;           // nep_batch_fleet_commit: an accepted slot's plan or composed trajectory would have outgrown its storage (the slot kept both; NEP_FLEET_CAP)
@@ -246,6 +247,13 @@ struct FeAstarArgs {
 };
 void launch_frontend_astar(int n_slots, const SceneParams& sp, const ProblemSet& ps, const nep_fe_cfg& fc, const FeAstarArgs& aa, const nep_fe_start* starts,
                            nep_guess* guess_out, nep_fe_result* res_out, hipStream_t st, int* active_buf = nullptr);
+// the same search with the entangle check (fe_astar_ent.h, nep_batch_frontend_astar_ent): what it needs beyond FeAstarArgs and FeEntArgs
+struct FeAstarEntArgs {
+  unsigned* tab_iz;              // [slots][tab_cap] the third word of a voxel's key: getIz of the node's state
+  unsigned char* states;         // [slots][pool] a node's entangle state, NEP_FE_ASTAR_ENT_NODE_BYTES each, beside the node pool
+};
+void launch_frontend_astar_ent(int n_slots, const SceneParams& sp, const ProblemSet& ps, const nep_fe_cfg& fc, const FeAstarArgs& aa, const FeAstarEntArgs& xa,
+                               const FeEntArgs& ea, const nep_fe_start* starts, nep_guess* guess_out, nep_fe_result* res_out, hipStream_t st, int* active_buf = nullptr);
 void launch_ent_sample(const nep_traj_rec* recs, int n_scenes, int N, const double* ts0, long ts_scene_stride, int num_pol, int ns, double T_span,
                        double* sampled, int* present, hipStream_t st, int* zero_this = nullptr);
 // nep_batch_audit (audit_kernels.hip): the minima of one (scene, run of ticks, agent), ticks as indices of the call

@@ -61,23 +61,27 @@ def stamp_bends(d_new, d_rec):
 
 
 def check_search(search, max_pops, tethers):
-    """the front end's strategy: "beam" (the default) or "astar", the reference's best-first search with a budget of max_pops pops
-    per search (BatchBackend.set_fe_astar / frontend_astar), which has no entangle check"""
-    if search not in ("beam", "astar"):
-        raise ValueError("search must be 'beam' or 'astar'")
+    """the front end's strategy: "beam" (the default), "astar", the reference's best-first search with a budget of max_pops pops
+    per search (BatchBackend.set_fe_astar / frontend_astar), which has no entangle check, or "astar_ent", the same search with the
+    check (frontend_astar_ent), which flies tethers=True only.  -> does the handle need set_fe_astar"""
+    if search not in ("beam", "astar", "astar_ent"):
+        raise ValueError("search must be 'beam', 'astar' or 'astar_ent'")
     if search == "astar" and tethers:
-        raise ValueError("search='astar' has no entangle check: it cannot fly tethers=True")
-    if search == "astar" and int(max_pops) < 1:
+        raise ValueError("search='astar' has no entangle check: it cannot fly tethers=True (search='astar_ent' does)")
+    if search == "astar_ent" and not tethers:
+        raise ValueError("search='astar_ent' is the best-first search with the entangle check: it needs tethers=True (without: search='astar')")
+    if search != "beam" and int(max_pops) < 1:
         raise ValueError("max_pops must be at least 1")
-    return search == "astar"
+    return search != "beam"
 
 
 def plan_round(be, fe, d_rec, d_start, d_guess, d_res, d_final, d_acc, tethers=False, d_case=None, d_ent=None, ent_samples=3, astar=False):
     """the plan half of a round: front end -> lines + QP -> safety pass, from the records d_rec and the starts d_start into d_final
     and d_acc.  With d_case the entangle check is on (d_ent: every tether's state at A): the QP gets the entangle rows and the safety
-    pass re-checks.  Tethered rounds stamp the published bend points into the commit records before the safety pass."""
+    pass re-checks.  Tethered rounds stamp the published bend points into the commit records before the safety pass.  astar: the
+    best-first search in place of the beam (check_search) — with d_case that is search="astar_ent", frontend_astar_ent."""
     if d_case is not None:
-        be.frontend_ent(fe, d_rec, d_start, d_guess, d_res, d_case, d_ent_init=d_ent)
+        (be.frontend_astar_ent if astar else be.frontend_ent)(fe, d_rec, d_start, d_guess, d_res, d_case, d_ent_init=d_ent)
         be.replan(None, d_guess, d_ent=d_case)
         stamp_bends(be.d_commit, d_rec)
         be.safety_commit_ent(d_rec, be.d_commit, d_guess, d_final, d_acc, d_ent_init=d_ent, ent_samples=ent_samples)
@@ -366,7 +370,8 @@ class DeviceFleetLoop(_Audited):
     run() downloads the slots' arrival flags (4 bytes per slot) after every round to know when to stop; nothing else leaves the
     device before report().  trace=True additionally downloads outcome, K and the two statuses per round (FleetLoop.trace).
     search="astar" plans with the reference's best-first search, max_pops pops per search, in place of the beam
-    (BatchBackend.frontend_astar; not with tethers=True: ValueError).
+    (BatchBackend.frontend_astar; not with tethers=True: ValueError); search="astar_ent" is that search with the entangle check
+    (BatchBackend.frontend_astar_ent) in place of frontend_ent in the tethered round below (only with tethers=True).
 
     tethers=True flies tethered agents: the handle is created with enable_entangle and carries every tether's
     entangle state at the tracked position, and the round becomes
@@ -665,7 +670,7 @@ class DeviceFleetLoop(_Audited):
         if opts["masked"] != ("periods" in kw or "phases" in kw):
             raise ValueError("checkpoint %s was flown %s periods / phases" % (path, "with" if opts["masked"] else "without"))
         for k, dflt in (("search", "beam"), ("max_pops", 300)):      # (a file from before the option has the beam)
-            if k in kw and kw[k] != opts.get(k, dflt) and (k == "search" or opts.get("search", "beam") == "astar"):
+            if k in kw and kw[k] != opts.get(k, dflt) and (k == "search" or opts.get("search", "beam") != "beam"):
                 raise ValueError("checkpoint %s was flown with %s=%r, not %r" % (path, k, opts.get(k, dflt), kw[k]))
         o = {k: opts[k] for k in cls._MUST_MATCH}
         o["search"], o["max_pops"] = opts.get("search", "beam"), opts.get("max_pops", 300)

@@ -18,8 +18,8 @@ ap.add_argument("--skip-arrived", action="store_true", help="arrived agents leav
 ap.add_argument("--audit", action="store_true", help="flight audit on the device (nep_batch_audit) next to the host's distance log")
 ap.add_argument("--tethers", action="store_true", help="tethered agents: entangle-aware front end and safety pass, tether states tracked per control tick")
 ap.add_argument("--no-check", action="store_true", help="with --tethers: plain front end and safety pass, the tracking stays on")
-ap.add_argument("--search", choices=("beam", "astar"), default="beam", help="front end: the beam (default) or the reference's best-first search (nep_batch_frontend_astar)")
-ap.add_argument("--max-pops", type=int, default=300, help="with --search astar: pops per search")
+ap.add_argument("--search", choices=("beam", "astar", "astar_ent"), default="beam", help="front end: the beam (default), the reference's best-first search (nep_batch_frontend_astar; not with --tethers) or that search with the entangle check (astar_ent: nep_batch_frontend_astar_ent; only with --tethers)")
+ap.add_argument("--max-pops", type=int, default=300, help="with --search astar / astar_ent: pops per search")
 a = ap.parse_args()
 sc = scene.make_scene(a.agents, a.obstacles, seed=a.seed)
 t0 = time.perf_counter()

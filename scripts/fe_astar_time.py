@@ -2,9 +2,12 @@
 N agents + M obstacles at several pop budgets, next to the beam front end (width 32) on the same inputs and to the oracle's
 orc_frontend_astar on 16 host threads for a sample of the same slots.  Per launch: hipEvent time of a captured graph replayed (hulls +
 search), after a warm-up.  With a PROFILE=1 library (NEP_BACKEND_LIB) and NEP_QP_PROFILE set, the wave's cycles per phase as well.
-   python scripts/fe_astar_time.py [scenes=128] [agents=64] [obstacles=20] [pops=100,300,1000] [host_sample=256]"""
+--ent: frontend_astar_ent_kernel (the same search with the entangle check) next to the plain A* and to the beam with
+the check, on the same scenes with config-5 style tethers (scene.synthetic_entangle), and tests/astar_ent_ref.py on host processes for a
+sample of the slots (its pop counts must equal the device's).
+   python scripts/fe_astar_time.py [--ent] [scenes=128] [agents=64] [obstacles=20] [pops=100,300,1000] [host_sample=256]"""
 import os, sys, time
-from concurrent.futures import ThreadPoolExecutor
+from concurrent.futures import ProcessPoolExecutor, ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 import numpy as np, torch
 from neptune_amd import scene, abi
@@ -31,7 +34,94 @@ def replay_ms(fn, reps=5):
     return float(np.median(ms)), ms
 
 
+def _ref_pops(job):
+    """tests/astar_ent_ref.py on one slot (a host process): pops, status"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import astar_ent_ref, helpers
+    sc, a, cfg_t, start, hulls, pops = job
+    cfg = abi.nep_fe_cfg(*cfg_t)
+    ent = helpers.ent_inputs(sc, a, t0=float(start["t_start"]))
+    _, r, _, _ = astar_ent_ref.astar(sc["par"], cfg, a + 1, start, hulls, sc["statics"], pops, ent=ent)
+    return r["n_children"], r["status"], r["n_entangled"]
+
+
+def main_ent(argv):
+    import dataclasses
+    S = int(argv[0]) if len(argv) > 0 else 128
+    N = int(argv[1]) if len(argv) > 1 else 64
+    M = int(argv[2]) if len(argv) > 2 else 20
+    budgets = [int(x) for x in (argv[3] if len(argv) > 3 else "100,300").split(",")]
+    n_host = int(argv[4]) if len(argv) > 4 else 64
+    made = scene.make_scenes(N, M, range(S), workers=min(S, 16))
+    for s, m in enumerate(made):
+        m["par"] = dataclasses.replace(m["par"], enable_entangle=True)
+        scene.synthetic_entangle(m, seed=900 + s)
+    p = made[0]["par"]
+    be = BatchBackend(p, made[0]["statics"], n_scenes=S)
+    for s in range(S):
+        be.set_scene_statics(s, made[s]["statics"])
+        reps, long_ = scene.static_reps(made[s]["statics"]); be.set_static_reps(reps, long_, scene=s)
+    com = np.stack([m["committed"] for m in made]); starts = np.stack([scene.frontend_starts(m) for m in made])
+    d_c = be.to_device(com); d_s = be.to_device(starts)
+    n = S * N
+    d_g = torch.zeros(n * abi.GUESS_DTYPE.itemsize, dtype=torch.uint8, device=be.device)
+    d_r = torch.zeros(n * abi.FE_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=be.device)
+    d_case = torch.zeros(n * abi.NEP_MAX_POL * N, dtype=torch.int32, device=be.device)
+    cfg = scene.frontend_cfg(p, beam_width=32); cfg_e = scene.frontend_cfg(p, beam_width=32, entangle=True)
+    print("%d searches (%d scenes of %d agents + %d obstacles), tethers with 2-4 bend points" % (n, S, N, M))
+    ms_b, all_ms = replay_ms(lambda: be.frontend(cfg, d_c, d_s, d_g, d_r))
+    print("beam, width 32, check off: %.3f ms per launch (replays: %s)" % (ms_b, " ".join("%.3f" % x for x in all_ms)), flush=True)
+    ms_be, all_ms = replay_ms(lambda: be.frontend_ent(cfg_e, d_c, d_s, d_g, d_r, d_case))
+    print("beam, width 32, check on:  %.3f ms per launch (replays: %s): %.1f x" % (ms_be, " ".join("%.3f" % x for x in all_ms), ms_be / ms_b), flush=True)
+    profile = os.environ.get("NEP_QP_PROFILE") is not None
+    sample = np.linspace(0, n - 1, min(n_host, n)).astype(int)
+    hulls = {}
+    for pops in budgets:
+        be.set_fe_astar(pops)
+        ms_p, all_p = replay_ms(lambda: be.frontend_astar(cfg, d_c, d_s, d_g, d_r))
+        be.check()
+        res_p = d_r.cpu().numpy().view(abi.FE_RESULT_DTYPE).copy()
+        ms, all_ms = replay_ms(lambda: be.frontend_astar_ent(cfg_e, d_c, d_s, d_g, d_r, d_case))
+        flagged = None
+        try:
+            be.check()
+        except Exception as e:      # (a fixed-record overflow is reported, not fatal here)
+            flagged = str(e)
+        res = d_r.cpu().numpy().view(abi.FE_RESULT_DTYPE).copy()
+        for nm, m_, am, r_, conc in (("A*, check off", ms_p, all_p, res_p, 256 * 12), ("A*, check on ", ms, all_ms, res, 256 * 4)):      # (waves a 256-CU chip holds: three per SIMD, one per SIMD)
+            tot = int(r_["n_children"].sum()); mx = int(r_["n_children"].max())
+            print("%s, %d pops: %.3f ms per launch (replays: %s); pops per search mean %.1f max %d, nodes mean %.1f max %d; %.2f us per pop of the longest search (launch / max pops), %.2f us per pop per wave (launch x concurrent waves / all pops: see DESIGN section 31), %.0f searches per second"
+                  % (nm, pops, m_, " ".join("%.3f" % x for x in am), tot / n, mx, r_["n_feasible"].mean(), int(r_["n_feasible"].max()), 1e3 * m_ / max(mx, 1),
+                     1e3 * m_ * min(n, conc) / max(tot, 1), n / (m_ * 1e-3)), flush=True)
+        print("   check on / check off: %.1f x per launch; statuses on %s off %s; children dropped by the check %d; searches with ent_overflow %d%s"
+              % (ms / ms_p, {k: int((res["status"] == k).sum()) for k in range(4)}, {k: int((res_p["status"] == k).sum()) for k in range(4)},
+                 int(res["n_entangled"].sum()), int((res["ent_overflow"] != 0).sum()), " (%s)" % flagged if flagged else ""), flush=True)
+        if profile:
+            rows = np.array([be.debug_phase_cycles(2 * int(s_)) for s_ in np.linspace(0, n - 1, min(64, n)).astype(int)], dtype=np.float64)
+            names = ("pop", "GJK + bases", "fe_child", "entangle propagation", "lookup + group", "commit", "state copy", "setup + result")
+            tot_c = rows[:, :8].sum(axis=1).mean()
+            print("   cycles per search (mean of %d slots): %s; per pop %.0f" % (len(rows), ", ".join("%s %.0f (%.0f %%)" % (nm, rows[:, k].mean(), 100 * rows[:, k].mean() / max(tot_c, 1)) for k, nm in enumerate(names)),
+                                                                                 rows[:, :7].sum() / max(rows[:, 8].sum(), 1)), flush=True)
+        if n_host > 0:
+            for i in sample:
+                s_ = int(i) // N
+                if s_ not in hulls:
+                    hulls[s_] = be.debug_hulls(s_)
+            cfg_t = tuple(getattr(cfg_e, f) for f, _ in abi.nep_fe_cfg._fields_)
+            jobs = [(made[int(i) // N], int(i) % N, cfg_t, starts[int(i) // N, int(i) % N], hulls[int(i) // N], pops) for i in sample]
+            t0 = time.perf_counter()
+            with ProcessPoolExecutor(16) as ex:
+                out = np.array(list(ex.map(_ref_pops, jobs)))
+            dt = time.perf_counter() - t0
+            same = int(((out[:, 0] == res["n_children"][sample]) & (out[:, 1] == res["status"][sample]) & (out[:, 2] == res["n_entangled"][sample])).sum())
+            print("   tests/astar_ent_ref.py, 16 host processes, %d of the slots: %.1f s; pops, status and n_entangled equal to the device's in %d of %d"
+                  % (len(sample), dt, same, len(sample)), flush=True)
+    be.close()
+
+
 def main():
+    if "--ent" in sys.argv:
+        return main_ent([x for x in sys.argv[1:] if x != "--ent"])
     S = int(sys.argv[1]) if len(sys.argv) > 1 else 128
     N = int(sys.argv[2]) if len(sys.argv) > 2 else 64
     M = int(sys.argv[3]) if len(sys.argv) > 3 else 20

@@ -9,6 +9,10 @@ Next to them the device's own best-first search (nep_batch_frontend_astar, entan
 launch per budget — what the host loop cannot do at scale — and is tabulated against the device beam without the check: outcomes, K
 and the progress towards the goal ((|A - goal| - dist_to_goal) / |A - goal| of the returned node).
 
+Last, the attribution the entangle-aware comparator allows: the device's best-first search WITH the check
+(nep_batch_frontend_astar_ent) at every budget against the device beam with the check on the same inputs, and whether the searches
+without a first primitive are the same set for every strategy.
+
   python scripts/fe_success_rates.py [scenes=4] [rounds=6] [host_scenes=2] [agents=256] [obstacles=100] [pops=100,300,1000]   ->  stdout (kept under profiles/)
 """
 import dataclasses
@@ -68,7 +72,12 @@ def main():
     lost32 = (res["status"] >= 2)
     print("device beam of width 64 WITH the entangle check, same inputs: %s; of the %d searches the width-32 beam ended without a plan (died out / no solution), width 64 finds a plan for %d"
           % ({NAMES[k]: int((res64["status"] == k).sum()) for k in NAMES}, int(lost32.sum()), int((lost32 & (res64["status"] < 2)).sum())))
+    try:
+        be.check()      # (a sticky capacity flag of the rounds above is reported here, once, and not charged to the searches below)
+    except Exception as e:
+        print("after the rounds: %s" % e)
     device_astar(be, p, cfg_plain, d_c, d_s, starts, S, N, budgets)
+    device_astar_ent(be, p, cfg, d_c, d_s, res, S, N, budgets)
     if SH <= 0:
         return
     oracle.lib()
@@ -116,6 +125,36 @@ def device_astar(be, p, cfg_plain, d_c, d_s, starts, S, N, budgets):
         row("A*, %d pops (0: on the budget)" % pops, res)
         print("  %-34s pops mean %.0f max %d; nodes mean %.0f max %d; returned depth max %d" % ("", res["n_children"].mean(), res["n_children"].max(),
               res["n_feasible"].mean(), res["n_feasible"].max(), res["depth"].max()), flush=True)
+
+
+def device_astar_ent(be, p, cfg, d_c, d_s, res_beam, S, N, budgets):
+    """the attribution: the reference's best-first search WITH the entangle check (nep_batch_frontend_astar_ent) at every budget against
+    the device beam with the check (res_beam), same records, same points A — are the searches without a first primitive the same set?"""
+    d_g = torch.zeros(S * N * abi.GUESS_DTYPE.itemsize, dtype=torch.uint8, device=be.device)
+    d_r = torch.zeros(S * N * abi.FE_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=be.device)
+    none_beam = res_beam["status"] == 3
+    print("\ndevice searches WITH the entangle check, last round's records, all %d searches per launch:" % (S * N))
+    print("  %-34s %s; plans (K > 0) %d" % ("beam, width 32", {NAMES[k]: int((res_beam["status"] == k).sum()) for k in NAMES}, int((res_beam["K"] > 0).sum())))
+    sets = [("beam 32", none_beam)]
+    for pops in budgets:
+        be.set_fe_astar(pops)
+        be.frontend_astar_ent(cfg, d_c, d_s, d_g, d_r)
+        flagged = ""
+        try:
+            be.check()
+        except Exception as e:
+            flagged = " [%s]" % e
+        res = d_r.cpu().numpy().view(abi.FE_RESULT_DTYPE).copy()
+        none = res["status"] == 3
+        sets.append(("A* %d" % pops, none))
+        print("  %-34s %s; plans (K > 0) %d, mean K %.2f; children dropped by the check %d; ent_overflow in %d searches%s"
+              % ("A*, %d pops (0: on the budget)" % pops, {NAMES[k]: int((res["status"] == k).sum()) for k in NAMES}, int((res["K"] > 0).sum()), float(res["K"].mean()),
+                 int(res["n_entangled"].sum()), int((res["ent_overflow"] != 0).sum()), flagged), flush=True)
+        print("  %-34s without a first primitive: beam %d, A* %d, both %d, beam only %d, A* only %d; of the A*-only ones, with the whole budget spent (no valid end point found) %d, with an empty open list %d"
+              % ("", int(none_beam.sum()), int(none.sum()), int((none_beam & none).sum()), int((none_beam & ~none).sum()), int((~none_beam & none).sum()),
+                 int((~none_beam & none & (res["n_children"] >= pops)).sum()), int((~none_beam & none & (res["n_children"] < pops)).sum())), flush=True)
+    same = all((m == sets[0][1]).all() for _, m in sets[1:])
+    print("  the searches without a first primitive are %s for every strategy (%s)" % ("the SAME set" if same else "NOT the same set", ", ".join("%s: %d" % (nm, int(m.sum())) for nm, m in sets)))
 
 
 if __name__ == "__main__":

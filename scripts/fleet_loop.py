@@ -37,8 +37,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=400, help="at most; the flight stops when every agent of every scene has arrived")
     ap.add_argument("--beam", type=int, default=32)
     ap.add_argument("--stagger", type=int, default=0, metavar="P")
-    ap.add_argument("--search", choices=("beam", "astar"), default="beam", help="front end: the beam (default) or the reference's best-first search (nep_batch_frontend_astar; not with --tethers)")
-    ap.add_argument("--max-pops", type=int, default=300, help="with --search astar: pops per search")
+    ap.add_argument("--search", choices=("beam", "astar", "astar_ent"), default="beam", help="front end: the beam (default), the reference's best-first search (nep_batch_frontend_astar; not with --tethers) or that search with the entangle check (astar_ent: nep_batch_frontend_astar_ent; only with --tethers)")
+    ap.add_argument("--max-pops", type=int, default=300, help="with --search astar / astar_ent: pops per search")
     ap.add_argument("--audit", action="store_true", help="flight audit of every round, inside the graph")
     ap.add_argument("--eager", action="store_true", help="no graph capture")
     ap.add_argument("--tethers", action="store_true", help="tethered agents: entangle states tracked per control tick, predicted at A, checked by the front end and the safety pass")

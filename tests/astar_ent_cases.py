@@ -1,0 +1,93 @@
+"""The scene set-ups the entangle-aware best-first search is tested on, and tests/astar_ent_ref.py's outcome for them (computed once
+per set-up, never changed) — shared by the CPU test of the ref and the GPU tests of the kernel."""
+import functools
+
+import numpy as np
+
+import astar_ent_ref as ref
+import helpers
+from neptune_amd import abi, scene
+
+
+def third_agent_inits(N, seed):
+    """the initial states of test_entangle_front_end_matches_the_oracle_bit_for_bit: every third search starts with one crossing"""
+    rng = np.random.default_rng(seed)
+    inits = np.zeros(N, dtype=abi.FE_ENT_STATE_DTYPE)
+    for a in range(0, N, 3):
+        j = int((a + 1 + rng.integers(0, N - 1)) % N)
+        if j != a:
+            inits[a]["n_alpha"] = 1; inits[a]["id"][0] = j + 1; inits[a]["cs"][0] = int(rng.integers(0, 3))
+    return inits
+
+
+def doubly_crossed_inits(N):
+    """every second agent starts with two crossings (cases 1 and 2) of its neighbour: an invalid end point until one is undone"""
+    inits = np.zeros(N, dtype=abi.FE_ENT_STATE_DTYPE)
+    for a in range(0, N, 2):
+        j = (a + 1) % N
+        inits[a]["n_alpha"] = 2; inits[a]["id"][0] = j + 1; inits[a]["id"][1] = j + 1; inits[a]["cs"][0] = 1; inits[a]["cs"][1] = 2
+    return inits
+
+
+@functools.lru_cache(maxsize=None)
+def setup(name):
+    """-> (scene, initial states [N], pop budget)"""
+    if name == "bends":
+        sc = scene.tether_crossing_scene(16, 8, 66)
+        scene.synthetic_entangle(sc, seed=966, frac=0.1, nb_range=(2, 5))
+        return sc, third_agent_inits(16, 66), 150
+    if name == "many_bends":
+        sc = scene.tether_crossing_scene(12, 4, 68)
+        scene.synthetic_entangle(sc, seed=968, frac=0.1, nb_range=(5, 9))
+        return sc, third_agent_inits(12, 68), 150
+    if name == "doubly":
+        return scene.tether_crossing_scene(8, 6, 60), doubly_crossed_inits(8), 300
+    if name == "plain":
+        return scene.tether_crossing_scene(8, 6, 60), third_agent_inits(8, 60), 150
+    if name.startswith("multi"):      # three scenes of one launch: the statics of the first, clocks 0.35 s apart
+        k = int(name[5:])
+        sc = dict(scene.tether_crossing_scene(8, 6, (60, 56, 62)[k]))
+        sc["statics"] = setup("multi0")[0]["statics"] if k else sc["statics"]
+        sc["guesses"] = sc["guesses"].copy(); sc["committed"] = sc["committed"].copy()
+        sc["guesses"]["t_start"] += 0.35 * k
+        sc["committed"]["pwp"]["times"] += 0.35 * k
+        return sc, third_agent_inits(8, 70 + k), 60
+    if name.startswith("bundle"):     # helpers.bundle_scene: agent 7 flies through a bundle of n - 1 tethers
+        n = int(name[6:])
+        sc = helpers.bundle_scene(n, 7, (0.004, 0.03), P=(-6.0, -0.5), Q=(6.0, 0.5))
+        return sc, np.zeros(n, dtype=abi.FE_ENT_STATE_DTYPE), 150
+    raise KeyError(name)
+
+
+def starts_of(name):
+    sc = setup(name)[0]
+    starts = scene.frontend_starts(sc)
+    if name.startswith("bundle"):     # (as test_a_bundle_of_tethers_needs_big_records_at_the_default_limits: from P towards Q at 1.5 m/s)
+        P, Q = sc["bundle"]
+        d = (Q - P) / np.linalg.norm(Q - P)
+        starts[7]["pos"][:2] = P; starts[7]["vel"][:2] = 1.5 * d; starts[7]["accel"][:2] = 0.0; starts[7]["goal"][:2] = Q
+    return starts
+
+
+def fe_cfg(p, num_samples=5, pad_hold=0):
+    return scene.frontend_cfg(p, num_samples=num_samples, pad_hold=pad_hold, entangle=True)
+
+
+_WANT = {}
+
+
+def want(oracle, name, max_pops=None, order=None, num_samples=5, max_nodes=ref.MAX_NODES, agents=None, pad_hold=0):
+    """{agent: (guess, result dict, case block, counters)} of the ref with the check on, for the agents of set-up `name`"""
+    key = (name, max_pops, None if order is None else tuple(int(x) for x in order), num_samples, max_nodes, pad_hold)
+    sc, inits, pops = setup(name)
+    p = sc["par"]
+    have = _WANT.setdefault(key, {})
+    starts = starts_of(name)
+    fe = fe_cfg(p, num_samples, pad_hold)
+    for a in (range(p.num_agents) if agents is None else agents):
+        if a in have:
+            continue
+        hulls = oracle.hulls_of_scene(p, a + 1, sc["committed"], float(starts[a]["t_start"]), sc["statics"])
+        ent = helpers.ent_inputs(sc, a, t0=float(starts[a]["t_start"]), init=inits[a])
+        have[a] = ref.astar(p, fe, a + 1, starts[a], hulls, sc["statics"], pops if max_pops is None else max_pops, order=order, max_nodes=max_nodes, ent=ent)
+    return have
