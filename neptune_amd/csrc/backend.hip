@@ -1244,21 +1244,38 @@ int nep_batch_set_fe_astar(nep_batch_t* h, int32_t max_pops, int32_t max_nodes, 
   return 0;
 }
 
-int nep_batch_frontend_astar(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_traj_rec* d_committed, const nep_fe_start* d_start,
-                             nep_guess* d_guess, nep_fe_result* d_result, void* stream) {
+// what both best-first entry points ask of their arguments, the handle and nep_batch_set_fe_astar's state, in the order each of them
+// asked it (who: the entry point, for the error texts; ent: the one with the entangle check)
+static int fe_astar_check(const nep_batch_t* h, const nep_fe_cfg* cfg, const void* d_committed, const void* d_start, const void* d_guess, const std::string& who, bool ent) {
   if (!h || !cfg || !d_committed || !d_start || !d_guess) return fail(NEP_E_ARG, "null argument");
-  Engine& E = h->eng;
-  if (!E.as_ready) return fail(NEP_E_STATE, "nep_batch_frontend_astar: call nep_batch_set_fe_astar first (it allocates the searches' pools)");
-  if (cfg->enable_entangle) return fail(NEP_E_ARG, "nep_batch_frontend_astar: the best-first search has no entangle check (enable_entangle must be 0)");
+  const Engine& E = h->eng;
+  if (ent) {
+    if (!h->cfg.enable_entangle) return fail(NEP_E_STATE, who + " needs a handle created with enable_entangle");
+    if (h->cfg.n_local != h->cfg.num_agents) return fail(NEP_E_STATE, who + " runs on an unsharded handle (n_local == num_agents)");
+    if (!cfg->enable_entangle) return fail(NEP_E_ARG, who + ": enable_entangle must be set in the front-end configuration (without the check: nep_batch_frontend_astar)");
+  }
+  if (!E.as_ready) return fail(NEP_E_STATE, who + ": call nep_batch_set_fe_astar first (it allocates the searches' pools)");
+  if (!ent && cfg->enable_entangle) return fail(NEP_E_ARG, who + ": the best-first search has no entangle check (enable_entangle must be 0)");
   if (!(cfg->num_samples >= 2 && cfg->num_samples <= NEP_FE_MAX_SAMPLES && cfg->voxel_size > 0.0 && cfg->j_max > 0.0)) return fail(NEP_E_ARG, "bad front-end configuration");
-  if (E.as_n_order && cfg->num_samples * cfg->num_samples != E.as_n_order) return fail(NEP_E_ARG, "nep_batch_frontend_astar: num_samples^2 differs from the n_order of nep_batch_set_fe_astar");
-  const ProblemSet ps = round_set(h);
-  h->fe_committed = d_committed;
-  launch_hulls_ts(d_committed, h->cfg.n_scenes, h->cfg.num_agents, &d_start->t_start, (long)sizeof(nep_fe_start), E.sp, ps, (hipStream_t)stream, grouped_hulls(E.sp, h->cfg.n_scenes, h->cfg.num_agents));
+  if (E.as_n_order && cfg->num_samples * cfg->num_samples != E.as_n_order) return fail(NEP_E_ARG, who + ": num_samples^2 differs from the n_order of nep_batch_set_fe_astar");
+  return 0;
+}
+// budget, order and pools as nep_batch_set_fe_astar left them
+static FeAstarArgs fe_astar_args(const Engine& E) {
   FeAstarArgs aa{};
   aa.max_pops = E.as_max_pops; aa.pool = E.as_pool; aa.tab_cap = E.as_tab; aa.order = E.as_n_order ? E.d_as_order.p : nullptr;
   aa.nodes = E.d_as_nodes.p; aa.heap = E.d_as_heap.p; aa.tab_key = E.d_as_key.p; aa.tab_val = E.d_as_val.p;
-  launch_frontend_astar(h->slots, E.sp, ps, *cfg, aa, d_start, d_guess, d_result, (hipStream_t)stream, E.d_fe_act.p);
+  return aa;
+}
+
+int nep_batch_frontend_astar(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_traj_rec* d_committed, const nep_fe_start* d_start,
+                             nep_guess* d_guess, nep_fe_result* d_result, void* stream) {
+  if (int e = fe_astar_check(h, cfg, d_committed, d_start, d_guess, "nep_batch_frontend_astar", false)) return e;
+  Engine& E = h->eng;
+  const ProblemSet ps = round_set(h);
+  h->fe_committed = d_committed;
+  launch_hulls_ts(d_committed, h->cfg.n_scenes, h->cfg.num_agents, &d_start->t_start, (long)sizeof(nep_fe_start), E.sp, ps, (hipStream_t)stream, grouped_hulls(E.sp, h->cfg.n_scenes, h->cfg.num_agents));
+  launch_frontend_astar(h->slots, E.sp, ps, *cfg, fe_astar_args(E), nullptr, nullptr, d_start, d_guess, d_result, (hipStream_t)stream, E.d_fe_act.p);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1454,18 +1471,12 @@ int nep_batch_frontend_ent_hulls(nep_batch_t* h, const nep_fe_cfg* cfg, const vo
   return run_frontend(h, ps, *cfg, d_start, d_guess, d_result, &ea, stream);
 }
 
-// the reference's best-first search with the entangle check (fe_astar_ent.h): nep_batch_frontend_ent's inputs, nep_batch_set_fe_astar's
+// the reference's best-first search with the entangle check (fe_astar.h): nep_batch_frontend_ent's inputs, nep_batch_set_fe_astar's
 // budget, order and pools, plus a state per node and the voxel key's third word (allocated here, at the first call: eager)
 int nep_batch_frontend_astar_ent(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_traj_rec* d_committed, const nep_fe_start* d_start,
                                  const nep_fe_ent_state* d_ent_init, nep_guess* d_guess, nep_fe_result* d_result, int32_t* d_case_out, void* stream) {
-  if (!h || !cfg || !d_committed || !d_start || !d_guess) return fail(NEP_E_ARG, "null argument");
+  if (int e = fe_astar_check(h, cfg, d_committed, d_start, d_guess, "nep_batch_frontend_astar_ent", true)) return e;
   Engine& E = h->eng;
-  if (!h->cfg.enable_entangle) return fail(NEP_E_STATE, "nep_batch_frontend_astar_ent needs a handle created with enable_entangle");
-  if (h->cfg.n_local != h->cfg.num_agents) return fail(NEP_E_STATE, "nep_batch_frontend_astar_ent runs on an unsharded handle (n_local == num_agents)");
-  if (!cfg->enable_entangle) return fail(NEP_E_ARG, "nep_batch_frontend_astar_ent: enable_entangle must be set in the front-end configuration (without the check: nep_batch_frontend_astar)");
-  if (!E.as_ready) return fail(NEP_E_STATE, "nep_batch_frontend_astar_ent: call nep_batch_set_fe_astar first (it allocates the searches' pools)");
-  if (!(cfg->num_samples >= 2 && cfg->num_samples <= NEP_FE_MAX_SAMPLES && cfg->voxel_size > 0.0 && cfg->j_max > 0.0)) return fail(NEP_E_ARG, "bad front-end configuration");
-  if (E.as_n_order && cfg->num_samples * cfg->num_samples != E.as_n_order) return fail(NEP_E_ARG, "nep_batch_frontend_astar_ent: num_samples^2 differs from the n_order of nep_batch_set_fe_astar");
   const ProblemSet ps = round_set(h);
   h->fe_committed = d_committed;
   launch_hulls_ts(d_committed, h->cfg.n_scenes, h->cfg.num_agents, &d_start->t_start, (long)sizeof(nep_fe_start), E.sp, ps, (hipStream_t)stream, grouped_hulls(E.sp, h->cfg.n_scenes, h->cfg.num_agents));
@@ -1477,11 +1488,8 @@ int nep_batch_frontend_astar_ent(nep_batch_t* h, const nep_fe_cfg* cfg, const ne
   ea.packed = E.d_fe_packed.p;
   if (int e = E.d_as_iz.ensure((size_t)h->slots * E.as_tab)) return e;
   if (int e = E.d_as_states.ensure((size_t)h->slots * E.as_pool * NEP_FE_ASTAR_ENT_NODE_BYTES)) return e;
-  FeAstarArgs aa{};
-  aa.max_pops = E.as_max_pops; aa.pool = E.as_pool; aa.tab_cap = E.as_tab; aa.order = E.as_n_order ? E.d_as_order.p : nullptr;
-  aa.nodes = E.d_as_nodes.p; aa.heap = E.d_as_heap.p; aa.tab_key = E.d_as_key.p; aa.tab_val = E.d_as_val.p;
   const FeAstarEntArgs xa{E.d_as_iz.p, E.d_as_states.p};
-  launch_frontend_astar_ent(h->slots, E.sp, ps, *cfg, aa, xa, ea, d_start, d_guess, d_result, (hipStream_t)stream, E.d_fe_act.p);
+  launch_frontend_astar(h->slots, E.sp, ps, *cfg, fe_astar_args(E), &xa, &ea, d_start, d_guess, d_result, (hipStream_t)stream, E.d_fe_act.p);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -3040,10 +3040,8 @@ void launch_frontend(int n_slots, const SceneParams& sp, const ProblemSet& ps_in
   else hipLaunchKernelGGL((frontend_kernel<false, NEP_FE_WAVES>), dim3(n_slots), dim3(256), lds, st, sp, ps, fc, starts, guess_out, res_out, none);
 }
 
-// the reference's best-first search over the same lattice (nep_batch_frontend_astar)
+// the reference's best-first search over the same lattice, without and with the entangle check (nep_batch_frontend_astar, nep_batch_frontend_astar_ent)
 #include "fe_astar.h"
-// ... and with the entangle check (nep_batch_frontend_astar_ent)
-#include "fe_astar_ent.h"
 
 // Neptune::SamplePointsOfIntervals (neptune.cpp:500-565) for every committed trajectory of every scene:
 // sampled[scene][j][interval][0..ns][2] on the round's grid, present[scene][j] = the trajectory exists (trajs_ holds it)

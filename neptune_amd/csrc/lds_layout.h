@@ -254,25 +254,27 @@ NEP_LDS_HD MissionLayout mission_layout(int N, int n_vert, int n_poly) {
   return L;
 }
 
-// ---- 7. frontend_astar_ent_kernel (fe_astar_ent.h) ------------------------------------------------------------------------------------
+// ---- 7. frontend_astar_kernel<true> (fe_astar.h) --------------------------------------------------------------------------------------
 // One wave per search, a fixed shape: 24.3 KB, six searches per CU by LDS (the kernel's registers admit no more than that either).
 // The working records are what the carve is for: a child's list surgery is a chain of dependent reads and writes of its record, which
-// in global memory are round trips (ent_check_kernel); the first entries of the heap as in frontend_astar_kernel.
-constexpr int kAsEntNC = NEP_FE_MAX_SAMPLES * NEP_FE_MAX_SAMPLES, kAsEntHeapLds = 2048;      // (= kAsNC, kAsHeapLds of fe_astar.h: asserted there)
+// in global memory are round trips (ent_check_kernel).  frontend_astar_kernel<false> has no records and keeps static arrays of the
+// same two sizes.
+constexpr int kAsNC = NEP_FE_MAX_SAMPLES * NEP_FE_MAX_SAMPLES;      // the children of an expansion, one lane each
+constexpr int kAsHeapLds = 2048;                                    // heap entries kept in LDS (levels 0-10 of the heap: every sift starts or ends there)
 struct AstarEntLayout {
-  int work;                   // [kAsEntNC + 1] nep_fe_ent_state: every lane's child state; the last one is the expansion's parent, staged once
-  int ch;                     // [kAsEntNC][17] double: a child of the expansion at hand (end state, cx, cy, g, h, cost)
-  int hcost;                  // [kAsEntNC] double: per voxel group, the holder's cost
+  int work;                   // [kAsNC + 1] nep_fe_ent_state: every lane's child state; the last one is the expansion's parent, staged once
+  int ch;                     // [kAsNC][17] double: a child of the expansion at hand (end state, cx, cy, g, h, cost)
+  int hcost;                  // [kAsNC] double: per voxel group, the holder's cost
   int lat;                    // [4][NEP_FE_MAX_SAMPLES] double: lattice tables
-  int heap;                   // [kAsEntHeapLds] int
-  int ints;                   // [10][kAsEntNC] int: vx, vy, iz, f, pos, hst, hidx, new, grp, valid
+  int heap;                   // [kAsHeapLds] int
+  int ints;                   // [10][kAsNC] int: vx, vy, iz, f, pos, hst, hidx, new, grp, valid
   int path;                   // [NEP_MAX_POL + 2] int: the returned path's nodes by index; [NEP_MAX_POL + 1]: the rows to fill
   int bytes;
 };
 NEP_LDS_HD AstarEntLayout astar_ent_layout() {
   AstarEntLayout L;
-  L.work = 0; L.ch = (kAsEntNC + 1) * (int)sizeof(nep_fe_ent_state); L.hcost = L.ch + kAsEntNC * 17 * 8; L.lat = L.hcost + kAsEntNC * 8;
-  L.heap = L.lat + 4 * NEP_FE_MAX_SAMPLES * 8; L.ints = L.heap + kAsEntHeapLds * 4; L.path = L.ints + 10 * kAsEntNC * 4;
+  L.work = 0; L.ch = (kAsNC + 1) * (int)sizeof(nep_fe_ent_state); L.hcost = L.ch + kAsNC * 17 * 8; L.lat = L.hcost + kAsNC * 8;
+  L.heap = L.lat + 4 * NEP_FE_MAX_SAMPLES * 8; L.ints = L.heap + kAsHeapLds * 4; L.path = L.ints + 10 * kAsNC * 4;
   L.bytes = lds_up(L.path + (NEP_MAX_POL + 2) * 4, 16);
   return L;
 }

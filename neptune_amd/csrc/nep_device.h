@@ -245,15 +245,14 @@ struct FeAstarArgs {
   int* heap;                     // [slots][pool] the open list's heap (its first entries live in LDS)
   unsigned long long* tab_key; int* tab_val;      // [slots][tab_cap] voxel -> first node
 };
-void launch_frontend_astar(int n_slots, const SceneParams& sp, const ProblemSet& ps, const nep_fe_cfg& fc, const FeAstarArgs& aa, const nep_fe_start* starts,
-                           nep_guess* guess_out, nep_fe_result* res_out, hipStream_t st, int* active_buf = nullptr);
-// the same search with the entangle check (fe_astar_ent.h, nep_batch_frontend_astar_ent): what it needs beyond FeAstarArgs and FeEntArgs
+// the same search with the entangle check (nep_batch_frontend_astar_ent): what it needs beyond FeAstarArgs and FeEntArgs
 struct FeAstarEntArgs {
   unsigned* tab_iz;              // [slots][tab_cap] the third word of a voxel's key: getIz of the node's state
   unsigned char* states;         // [slots][pool] a node's entangle state, NEP_FE_ASTAR_ENT_NODE_BYTES each, beside the node pool
 };
-void launch_frontend_astar_ent(int n_slots, const SceneParams& sp, const ProblemSet& ps, const nep_fe_cfg& fc, const FeAstarArgs& aa, const FeAstarEntArgs& xa,
-                               const FeEntArgs& ea, const nep_fe_start* starts, nep_guess* guess_out, nep_fe_result* res_out, hipStream_t st, int* active_buf = nullptr);
+// (xa and ea null: the plain search; both set: the search with the entangle check)
+void launch_frontend_astar(int n_slots, const SceneParams& sp, const ProblemSet& ps, const nep_fe_cfg& fc, const FeAstarArgs& aa, const FeAstarEntArgs* xa, const FeEntArgs* ea,
+                           const nep_fe_start* starts, nep_guess* guess_out, nep_fe_result* res_out, hipStream_t st, int* active_buf = nullptr);
 void launch_ent_sample(const nep_traj_rec* recs, int n_scenes, int N, const double* ts0, long ts_scene_stride, int num_pol, int ns, double T_span,
                        double* sampled, int* present, hipStream_t st, int* zero_this = nullptr);
 // nep_batch_audit (audit_kernels.hip): the minima of one (scene, run of ticks, agent), ticks as indices of the call

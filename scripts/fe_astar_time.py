@@ -1,8 +1,9 @@
-"""Development aid: device time of frontend_astar_kernel (the reference's best-first search, one wave per search) on S seeded scenes of
+"""Development aid: device time of frontend_astar_kernel<false> (the reference's best-first search, one wave per search) on S seeded scenes of
 N agents + M obstacles at several pop budgets, next to the beam front end (width 32) on the same inputs and to the oracle's
 orc_frontend_astar on 16 host threads for a sample of the same slots.  Per launch: hipEvent time of a captured graph replayed (hulls +
-search), after a warm-up.  With a PROFILE=1 library (NEP_BACKEND_LIB) and NEP_QP_PROFILE set, the wave's cycles per phase as well.
---ent: frontend_astar_ent_kernel (the same search with the entangle check) next to the plain A* and to the beam with
+search), after a warm-up.  With a PROFILE=1 library (NEP_BACKEND_LIB) and NEP_QP_PROFILE set, the wave's cycles per phase as well (one
+phase numbering for both instantiations, PHASES; without the check "entangle propagation" and "state copy" stay zero).
+--ent: frontend_astar_kernel<true> (the same search with the entangle check) next to the plain A* and to the beam with
 the check, on the same scenes with config-5 style tethers (scene.synthetic_entangle), and tests/astar_ent_ref.py on host processes for a
 sample of the slots (its pop counts must equal the device's).
    python scripts/fe_astar_time.py [--ent] [scenes=128] [agents=64] [obstacles=20] [pops=100,300,1000] [host_sample=256]"""
@@ -32,6 +33,16 @@ def replay_ms(fn, reps=5):
         ms.append(e0.elapsed_time(e1))
     del g
     return float(np.median(ms)), ms
+
+
+PHASES = ("pop", "GJK + bases", "fe_child", "entangle propagation", "lookup + group", "commit", "state copy", "setup + result")      # AS_TICK's numbering (fe_astar.h)
+
+
+def print_phases(rows):
+    """rows: debug_phase_cycles of a sample of slots ([8]: pops)"""
+    tot_c = rows[:, :8].sum(axis=1).mean()
+    print("   cycles per search (mean of %d slots): %s; per pop %.0f" % (len(rows), ", ".join("%s %.0f (%.0f %%)" % (nm, rows[:, k].mean(), 100 * rows[:, k].mean() / max(tot_c, 1)) for k, nm in enumerate(PHASES)),
+                                                                         rows[:, :7].sum() / max(rows[:, 8].sum(), 1)), flush=True)
 
 
 def _ref_pops(job):
@@ -98,10 +109,7 @@ def main_ent(argv):
                  int(res["n_entangled"].sum()), int((res["ent_overflow"] != 0).sum()), " (%s)" % flagged if flagged else ""), flush=True)
         if profile:
             rows = np.array([be.debug_phase_cycles(2 * int(s_)) for s_ in np.linspace(0, n - 1, min(64, n)).astype(int)], dtype=np.float64)
-            names = ("pop", "GJK + bases", "fe_child", "entangle propagation", "lookup + group", "commit", "state copy", "setup + result")
-            tot_c = rows[:, :8].sum(axis=1).mean()
-            print("   cycles per search (mean of %d slots): %s; per pop %.0f" % (len(rows), ", ".join("%s %.0f (%.0f %%)" % (nm, rows[:, k].mean(), 100 * rows[:, k].mean() / max(tot_c, 1)) for k, nm in enumerate(names)),
-                                                                                 rows[:, :7].sum() / max(rows[:, 8].sum(), 1)), flush=True)
+            print_phases(rows)
         if n_host > 0:
             for i in sample:
                 s_ = int(i) // N
@@ -157,10 +165,7 @@ def main():
               % (pops, ms, " ".join("%.3f" % x for x in all_ms), tot / n, mx, res["n_feasible"].mean(), int(res["n_feasible"].max()), 1e3 * ms / max(mx, 1), n / (ms * 1e-3), tot / ms * 1e-3), flush=True)
         if profile:
             rows = np.array([be.debug_phase_cycles(2 * int(s_)) for s_ in sample[:64]], dtype=np.float64)
-            names = ("pop", "GJK", "fe_child + lookup", "commit + push", "setup", "result")
-            tot_c = rows[:, :6].sum(axis=1).mean()
-            print("   cycles per search (mean of %d slots): %s; per pop %.0f" % (len(rows), ", ".join("%s %.0f (%.0f %%)" % (nm, rows[:, k].mean(), 100 * rows[:, k].mean() / max(tot_c, 1)) for k, nm in enumerate(names)),
-                                                                                 rows[:, :4].sum() / max(rows[:, 8].sum(), 1)), flush=True)
+            print_phases(rows)
         # the oracle on 16 host threads, a sample of the same slots
         for i in sample:
             s_ = int(i) // N

@@ -204,6 +204,45 @@ def test_three_scenes_and_an_active_set(be, oracle):
     bb.close()
 
 
+def test_both_searches_share_one_handle(be, oracle):
+    """The two searches are one kernel template behind one launcher and share a handle's node pool, heap and voxel table (the check adds
+    the key's third word): check off, check on, check off again on one handle, stale bytes in the outputs before each launch.  Each
+    launch equals its own reference, and the two references differ, so that a mix-up cannot pass."""
+    sc, inits, _ = cases.setup("plain"); p = sc["par"]; N = p.num_agents
+    starts = cases.starts_of("plain")
+    fe_off = scene.frontend_cfg(p)
+    off = {}
+    for a in range(N):
+        hx, hn = oracle.hulls_of_scene(p, a + 1, sc["committed"], float(starts[a]["t_start"]), sc["statics"])
+        off[a] = oracle.frontend_astar(p, fe_off, a + 1, starts[a], hx, hn, sc["statics"], max_pops=40)
+    on = cases.want(oracle, "plain", max_pops=40)
+    assert [off[a][1]["status"] for a in range(N)] == [1, 0, 0, 3, 1, 3, 1, 0] and _col(on, "status") == [0, 0, 0, 3, 0, 3, 0, 0]
+    assert sum(np.asarray(off[a][0]).tobytes() != np.asarray(on[a][0]).tobytes() for a in range(N)) >= 4
+    assert on[6][1]["n_entangled"] == 290 and all(off[a][1]["n_entangled"] == 0 for a in range(N))
+    bb = _handle(be, sc)
+    bb.set_fe_astar(40)
+    d_com = bb.to_device(np.ascontiguousarray(sc["committed"])); d_start = bb.to_device(np.ascontiguousarray(starts))
+
+    def check_off(where):
+        d_g, d_r, _ = _buffers(bb, N, N)
+        bb.frontend_astar(fe_off, d_com, d_start, d_g, d_r)
+        bb.torch.cuda.synchronize()
+        got_g, got_r = d_g.cpu().numpy().view(abi.GUESS_DTYPE), d_r.cpu().numpy().view(abi.FE_RESULT_DTYPE)
+        for a in range(N):
+            g, r = off[a]
+            for f in abi.FE_RESULT_DTYPE.names:
+                assert got_r[a][f].item() == r[f], (where, a, f, got_r[a][f].item(), r[f])
+            assert got_g[a].tobytes() == np.asarray(g).tobytes(), (where, a, "guess bytes")
+
+    check_off("check off, first")
+    got = _run(bb, cases.fe_cfg(p), sc["committed"], starts, inits, N, N)
+    for a in range(N):
+        _same(got, a, on[a], ("check on, between", "agent", a))
+    check_off("check off, after the check")
+    bb.check()
+    bb.close()
+
+
 def test_capture(be, oracle):
     """Test 7: after one eager call the call allocates nothing: captured and replayed twice it writes the eager call's bytes."""
     sc, inits, pops = cases.setup("plain"); p = sc["par"]
