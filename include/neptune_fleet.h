@@ -5,8 +5,8 @@
  * trip per agent and round.  Here the same state lives in the batched handle (include/neptune_backend.h: nep_batch_t), per
  * (scene, agent) slot, and three asynchronous calls move it — so a faithful round
  *
- *   nep_batch_fleet_select -> nep_batch_frontend -> nep_batch_replan -> nep_batch_safety_commit -> nep_batch_fleet_commit
- *     [-> nep_batch_audit] [-> nep_batch_fleet_mission] -> nep_batch_fleet_tick
+ *   nep_batch_fleet_select [-> nep_batch_fleet_moveback] -> nep_batch_frontend -> nep_batch_replan -> nep_batch_safety_commit ->
+ *     nep_batch_fleet_commit [-> nep_batch_audit] [-> nep_batch_fleet_mission] -> nep_batch_fleet_tick
  *
  * is a fixed launch sequence on fixed buffers: one HIP graph for all scenes, no host synchronisation in it.  The arithmetic is the
  * host library's own (neptune_amd/csrc/plan_common.h is compiled into both), so the plans, tracked states and trajectories on the
@@ -19,7 +19,8 @@
  *   last selection   k_index_end of the last nep_batch_fleet_select (what the splice erases)
  *   tracked state    12 doubles: the goal the perfect tracker took last (Neptune::getNextGoal)
  *   trajectory       the composed committed trajectory (pwp_prev_) and whether the agent has committed one yet
- *   bookkeeping      sticky `done` (arrived; a mission's new goal clears it), the last round's outcome, sticky NEP_FLEET_FLAG_* bits
+ *   bookkeeping      sticky `done` (arrived; a mission's new goal clears it), the last round's outcome, the NEP_FLEET_FLAG_* bits
+ *                    (sticky, but for NEP_FLEET_FLAG_WAY_BACK)
  * State of a scene: the clock t_now, a round counter, and counters of every outcome.
  *
  * What differs from the reference:
@@ -40,8 +41,9 @@
  * NEP_MAX_BEND points each), the NEP_ENT_TRACK_* flags of the last tracked round and their sticky OR; per scene, counter [7] =
  * slots ever flagged NEP_ENT_TRACK_ENTANGLED.  The round becomes
  *
- *   nep_batch_fleet_select -> nep_batch_fleet_predict_ent -> nep_batch_frontend_ent -> nep_batch_replan (entangle rows) ->
- *     nep_batch_safety_commit_ent -> nep_batch_fleet_commit [-> nep_batch_audit] -> nep_batch_fleet_track_ent -> nep_batch_fleet_tick
+ *   nep_batch_fleet_select [-> nep_batch_fleet_moveback] -> nep_batch_fleet_predict_ent -> nep_batch_frontend_ent ->
+ *     nep_batch_replan (entangle rows) -> nep_batch_safety_commit_ent -> nep_batch_fleet_commit [-> nep_batch_audit] ->
+ *     nep_batch_fleet_track_ent -> nep_batch_fleet_tick
  *
  * with the state at A (Neptune::PredictAlphasBetas, neptune.cpp:976-1008) made on the device and the state at the tracked
  * position moved once per control tick flown (NeptuneRos::odomCB -> updateEntStateStaticObs, neptune_ros.cpp:781-850).  Both equal,
@@ -72,6 +74,8 @@ extern "C" {
 #define NEP_FLEET_FLAG_SEG 1            /* sticky per slot: a composition needed more than NEP_TRAJ_MAX_SEG intervals        */
 #define NEP_FLEET_FLAG_RING 2           /* a splice needed more than ring_cap states (or n_states > max_states)              */
 #define NEP_FLEET_FLAG_SPLICE 4         /* a splice with size - 1 - k_index_end < 0 ("Already published the point A")        */
+/* (8: NEP_FLEET_FLAG_GOAL, with the missions.)  Bits 1, 2, 4, 8 are sticky and say that something overflowed.  Bit 16 is neither: */
+#define NEP_FLEET_FLAG_WAY_BACK 16      /* NOT sticky, no error: the slot is on its way back to its base (nep_batch_fleet_moveback) */
 
 /* nep_abi_sizeof(18).  The first eight fields are nep_plan_cfg's (runtime_opt and factor_alpha are carried for symmetry: the
  * front end's run-time budget and nep_plan_update_delta have no device form).                                               */
@@ -191,7 +195,8 @@ int nep_batch_fleet_ent_lists(nep_batch_t* h, nep_ent_lists* host_out, int32_t* 
  *   NEP_MISSION_FLEET_RUNS   scripts/benchmark_mtlp.py:167-281: the whole scene.  A run ends when every agent is `completed`
  *                            (within arrive_radius of its goal; the flag is re-evaluated at every tick, in both directions) —
  *                            a success — or after timeout — a failure; then every agent gets a new goal, in agent order.
- * The round becomes  ... fleet_commit -> [audit] -> [fleet_track_ent] -> nep_batch_fleet_mission -> fleet_tick.
+ * The round becomes  fleet_select -> [fleet_moveback] -> ... fleet_commit -> [audit] -> [fleet_track_ent] -> nep_batch_fleet_mission
+ * -> fleet_tick.
  *
  * The call looks at the round_ticks ticks about to be flown by nep_batch_fleet_track_ent's rule: p_0 the tracked state, p_q =
  * ring[(head + min(q - 1, size - 1)) mod cap], the end state s_end = the 12 doubles of p_round_ticks, the end clock t_end = t_now
@@ -229,7 +234,7 @@ int nep_batch_fleet_ent_lists(nep_batch_t* h, nep_ent_lists* host_out, int32_t* 
  *   no gate          benchmark_mtlp waits for the MTLP comparator's acknowledgement before the next run; there is no comparator here.
  *   one rule set     both modes share the five tests (autoCMD has 1-3, benchmark_mtlp 2, 4, 5); a test is off at parameter 0.
  *   quota            max_goals ends a campaign (the reference's scripts are stopped from outside or after 100 runs).
- *   use_moveback_, the single-agent A* benchmark branch of replanCB: not built.
+ *   use_moveback_    is nep_batch_fleet_moveback, below.  The single-agent A* benchmark branch of replanCB: not built.
  * Limits: the kernel stages a scene's end positions, new goals and keep-outs in 64 KB of LDS, sized once at
  * nep_batch_fleet_mission_init for 52 B per agent and a full keep-out set (NEP_MISSION_MAX_POLY polygons, NEP_MISSION_MAX_VERT
  * vertices in all per scene), so that keep-outs uploaded later fit a round captured earlier: up to 1 097 agents; beyond: NEP_E_CAP. */
@@ -321,6 +326,52 @@ int nep_batch_fleet_mission_log(nep_batch_t* h, nep_mission_leg* log_out, int32_
  * (neptune_amd/csrc/mission_common.h) and the device equals a chain of these calls byte for byte.  NEP_E_ARG on a bad
  * configuration or null pointers.                                                                                               */
 int nep_mission_step(const nep_mission_cfg* cfg, nep_mission_scene* sc);
+
+/* ---- move-back: a new goal is approached by way of the agent's own base ---------------------------------------------------------
+ * The reference's use_moveback_strategy (neptune_mtlp_benchmark.yaml: true; neptune_ros.cpp:1626-1636, :1291-1305): an agent that
+ * receives a new terminal goal does not head for it.  It first plans towards (pb.x, pb.y, the goal's z), a point at its own base,
+ * which unwinds its tether, and gets the real goal once it is within a radius of the base (yaml: 6.33 - (N - 4) * 0.33 m) or after
+ * 10 s.  One slot, in this order (moveback_common.h is the one statement, shared by the kernel and the host form):
+ *
+ *   t_iss = the slot's t_issue (missions), else nep_fleet_cfg.t0;   f = the slot's NEP_FLEET_FLAG_* word
+ *   if (t_iss == t_now)  f |= NEP_FLEET_FLAG_WAY_BACK
+ *   if (f & NEP_FLEET_FLAG_WAY_BACK) { d = sqrt(dx*dx + dy*dy) of the tracked (x, y) less pb[agent];
+ *                                      if (d < radius || t_now - t_iss > timeout)  f &= ~NEP_FLEET_FLAG_WAY_BACK }      (both strict)
+ *   the word = f;   if (f & NEP_FLEET_FLAG_WAY_BACK)  d_start[slot].goal = (pb.x, pb.y, d_start[slot].goal[2])
+ *
+ * t_iss == t_now is exact: nep_batch_fleet_mission issues a goal with t_issue = t_end, round_ticks repeated additions of dc to the
+ * clock, the very additions nep_batch_fleet_tick then makes, and nep_batch_fleet_mission_init starts t_issue at the scenes' clocks.
+ * So a goal issued at the end of round r is seen by the call of round r + 1 and by no other, the first goal by the first round, and
+ * a goal issued again (the no-goal path resets t_issue) starts a move-back again, as a re-published goal does in the reference.
+ * The only state is the bit, in the slot's flag word (nep_batch_fleet_state's flags, section SFLAGS of a snapshot; T_ISSUE and T_NOW
+ * are sections too: a snapshot carries a move-back in progress, and its layout, sizes and version are what they were).  The slot's
+ * goal stays the real one: the mission's leg tests, nep_batch_fleet_tick's arrival test and the log do not change; only the goal the
+ * search is given does.  A handle that never makes the call is what it was, byte for byte.
+ *
+ * What differs from the reference:
+ *   when it runs     the release test runs once per round, on the tracked state at the select; the reference runs it at every
+ *                    control tick (pubCB).
+ *   timer            the simulated clock: 10 000 ms of wall clock become timeout = 10.0 s.
+ *   radius           a parameter (neptune_amd.mission.MoveBack.reference(N) gives the yaml's formula).  It is <= 0 from N = 24 up,
+ *                    and then only the timer releases.
+ *   the own base     the back end treats the agent's own base square as an obstacle (solver_gurobi_poly.cpp:521-553), so an agent
+ *                    approaches its base and does not reach it — the reference's behaviour too.
+ *   move_when_goal_occupied, the yaml's other switch: not built.
+ *
+ * nep_batch_fleet_moveback   between nep_batch_fleet_select and the front end (tethered rounds: before or after
+ *                    nep_batch_fleet_predict_ent, which does not read the goal).  One thread per slot, every slot whatever the
+ *                    active mask.  Reads the handle's tracked states, bases, clocks and flag words, and the mission state's t_issue
+ *                    when nep_batch_fleet_mission_init has run; writes the flag words and d_start[slot].goal, nothing else.
+ *                    Asynchronous, allocates nothing, capturable.  NEP_E_STATE before nep_batch_fleet_init and on sharded handles;
+ *                    NEP_E_ARG for a null pointer, a timeout that is negative or not finite, a radius that is not finite.
+ * nep_moveback_step  host form for n slots of one scene (moveback_host.cpp; no HIP call): state [n][12], pb [n][2], t_issue [n] or
+ *                    NULL (every goal was issued at t_first), flags [n] and start [n] updated in place.  The device equals a chain
+ *                    of these calls byte for byte.  NEP_E_ARG as above.                                                           */
+/* nep_abi_sizeof(27): 16 bytes */
+typedef struct nep_moveback_cfg { double radius, timeout; } nep_moveback_cfg;
+int nep_batch_fleet_moveback(nep_batch_t* h, const nep_moveback_cfg* cfg, nep_fe_start* d_start, void* stream);
+int nep_moveback_step(const nep_moveback_cfg* cfg, int32_t n, const double* state, const double* pb, const double* t_issue,
+                      double t_first, double t_now, int32_t* flags, nep_fe_start* start);
 
 /* ---- recorder: snapshot, restore and replay ------------------------------------------------------------------------------------
  * A snapshot is the complete fleet state of a handle as one blob: whatever decides what the fleet calls do next.  A handle restored

@@ -53,6 +53,7 @@ FLEET_EXPORTS = ["nep_batch_fleet_init", "nep_batch_fleet_select", "nep_batch_fl
                  "nep_batch_fleet_plans", "nep_batch_fleet_state", "nep_batch_fleet_counters", "nep_batch_fleet_init_ent", "nep_batch_fleet_predict_ent",
                  "nep_batch_fleet_track_ent", "nep_batch_fleet_ent_state", "nep_batch_fleet_init_ent_lists", "nep_batch_fleet_ent_lists", "nep_batch_fleet_mission_keepout", "nep_batch_fleet_mission_init",
                  "nep_batch_fleet_mission", "nep_batch_fleet_mission_state", "nep_batch_fleet_mission_log", "nep_mission_step",
+                 "nep_batch_fleet_moveback", "nep_moveback_step",
                  "nep_batch_fleet_snapshot", "nep_batch_fleet_snapshot_ring", "nep_batch_fleet_restore", "nep_fleet_snapshot_describe"]
 # ... and the two of its recorder section that return a byte count (int64_t)
 FLEET_SIZE_EXPORTS = ["nep_batch_fleet_snapshot_bytes", "nep_batch_fleet_snapshot_ring_bytes"]
@@ -223,6 +224,8 @@ def lib():
     L.nep_batch_fleet_mission_state.argtypes = [vp, pd, pd, pd, pi, pi, pd, pi, pd]
     L.nep_batch_fleet_mission_log.argtypes = [vp, vp, pi]
     L.nep_mission_step.argtypes = [C.POINTER(abi.nep_mission_cfg), C.POINTER(abi.nep_mission_scene)]
+    L.nep_batch_fleet_moveback.argtypes = [vp, C.POINTER(abi.nep_moveback_cfg), vp, vp]
+    L.nep_moveback_step.argtypes = [C.POINTER(abi.nep_moveback_cfg), i, vp, vp, vp, d, d, vp, vp]
     L.nep_batch_fleet_snapshot_bytes.argtypes = [vp]; L.nep_batch_fleet_snapshot_bytes.restype = C.c_int64
     L.nep_batch_fleet_snapshot.argtypes = [vp, vp, vp]
     L.nep_batch_fleet_snapshot_ring_bytes.argtypes = [vp, i]; L.nep_batch_fleet_snapshot_ring_bytes.restype = C.c_int64
@@ -238,7 +241,7 @@ def lib():
     L.nep_abi_sizeof.argtypes = [i]; L.nep_abi_sizeof.restype = i
     for which, struct in ((1, abi.nep_traj_rec), (5, abi.nep_guess), (6, abi.nep_solution), (11, abi.nep_fe_cfg), (12, abi.nep_fe_start),
                           (13, abi.nep_fe_result), (14, abi.nep_fe_ent_state), (17, abi.nep_audit), (18, abi.nep_fleet_cfg),
-                          (20, abi.nep_mission_cfg), (21, abi.nep_mission_leg), (23, abi.nep_ent_lists), (25, abi.nep_fleet_snapshot_hdr)):
+                          (20, abi.nep_mission_cfg), (21, abi.nep_mission_leg), (23, abi.nep_ent_lists), (25, abi.nep_fleet_snapshot_hdr), (27, abi.nep_moveback_cfg)):
         if L.nep_abi_sizeof(which) != C.sizeof(struct):
             raise BackendError("%s: sizeof(%s) is %d in the library, %d in neptune_amd/abi.py — rebuild the library from this tree's headers"
                                % (LIB_PATH, struct.__name__, L.nep_abi_sizeof(which), C.sizeof(struct)))

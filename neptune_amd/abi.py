@@ -219,6 +219,8 @@ NEP_FLEET_N_COUNTERS = 8
 FLEET_OUTCOMES = ("skipped", "fe_no_solution", "qp_failed", "rejected_by_safety", "accepted", "cap")
 NEP_FLEET_FLAG_SEG, NEP_FLEET_FLAG_RING, NEP_FLEET_FLAG_SPLICE = 1, 2, 4
 NEP_FLEET_FLAG_GOAL = 8
+NEP_FLEET_FLAG_WAY_BACK = 16      # not sticky, no error: the slot is on its way back to its base (nep_batch_fleet_moveback)
+NEP_FLEET_FLAG_ERRORS = NEP_FLEET_FLAG_SEG | NEP_FLEET_FLAG_RING | NEP_FLEET_FLAG_SPLICE | NEP_FLEET_FLAG_GOAL      # the sticky bits: something overflowed
 
 
 # ---- missions (include/neptune_fleet.h) ----
@@ -251,6 +253,11 @@ class nep_mission_scene(C.Structure):
                 ("goal", C.c_void_p), ("done", C.c_void_p), ("flags", C.c_void_p), ("t_issue", C.c_void_p), ("length", C.c_void_p),
                 ("completed", C.c_void_p), ("counts", C.c_void_p), ("sums", C.c_void_p), ("scene_i", C.c_void_p), ("t_run", C.c_void_p),
                 ("log", C.c_void_p), ("log_n", C.c_void_p)]
+
+
+class nep_moveback_cfg(C.Structure):
+    """include/neptune_fleet.h: the move-back rule's two parameters (nep_batch_fleet_moveback, nep_moveback_step)."""
+    _fields_ = [("radius", C.c_double), ("timeout", C.c_double)]
 
 
 # ---- the recorder (include/neptune_fleet.h) ----

@@ -530,6 +530,12 @@ class BatchBackend:
         st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
         check(lib().nep_batch_fleet_mission(self._h, st.cuda_stream))
 
+    def fleet_moveback(self, cfg, d_start, stream=None):
+        """the move-back rule of the round (nep_batch_fleet_moveback), after fleet_select: cfg abi.nep_moveback_cfg; the slots on
+        their way back get their base as d_start's goal"""
+        st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        check(lib().nep_batch_fleet_moveback(self._h, C.byref(cfg), d_start.data_ptr(), st.cuda_stream))
+
     def fleet_mission_state(self):
         """the mission state (blocking) -> dict: goal [slots][3], t_issue / length / completed [slots], counts [slots][4] (abi.MISSION_COUNTS),
         sums [slots][2] (leg time, leg length), scene [n_scenes][4] (run, runs succeeded, runs failed, finished), t_run [n_scenes]"""

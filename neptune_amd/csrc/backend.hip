@@ -19,6 +19,7 @@
 #include "qp_outputs.h"
 #include "audit_common.h"
 #include "mission_common.h"
+#include "moveback_common.h"
 #include "recorder_common.h"
 #include "../../include/neptune_plan.h"
 #include "../../include/neptune_entangle.h"
@@ -1949,6 +1950,19 @@ int nep_batch_fleet_mission(nep_batch_t* h, void* stream) {
   return 0;
 }
 
+// ---- the move-back rule (include/neptune_fleet.h; kernel: fleet_moveback_kernels.hip; host form: moveback_host.cpp) ----
+int nep_batch_fleet_moveback(nep_batch_t* h, const nep_moveback_cfg* cfg, nep_fe_start* d_start, void* stream) {
+  if (int e = fleet_guard(h, true)) return e;
+  if (!cfg || !d_start) return fail(NEP_E_ARG, "null argument");
+  if (!nep_moveback_impl::moveback_cfg_ok(*cfg)) return fail(NEP_E_ARG, "bad move-back configuration (radius finite, timeout finite and >= 0)");
+  FleetArgs fa{};
+  fleet_args(h, fa);
+  fa.start = d_start;
+  launch_fleet_moveback(*cfg, fa, h->fleet.mis_ready ? h->fleet.mis_t_issue.p : nullptr, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 int nep_batch_fleet_mission_state(nep_batch_t* h, double* goal_out, double* t_issue_out, double* length_out, int32_t* completed_out,
                                   int32_t* counts_out, double* sums_out, int32_t* scene_out, double* t_run_out) {
   if (int e = fleet_guard(h, true)) return e;
@@ -2562,6 +2576,7 @@ int nep_abi_sizeof(int32_t which) {
     case 21: return (int)sizeof(nep_mission_leg);
     case 23: return (int)sizeof(nep_ent_lists);      // (22 stays unassigned: tests/test_fleet_mission_cpu.py pins it to -1)
     case 25: return (int)sizeof(nep_fleet_snapshot_hdr);      // (24 stays unassigned: tests/test_ent_lists_cpu.py pins it to -1)
+    case 27: return (int)sizeof(nep_moveback_cfg);      // (26 stays unassigned: tests/test_fleet_recorder_cpu.py pins it to -1)
     default: return -1;
   }
 }

@@ -313,6 +313,9 @@ struct FleetMissionArgs {
 };
 void launch_fleet_mission_seed(const FleetMissionArgs& ma, const FleetArgs& fa, hipStream_t st);
 void launch_fleet_mission(const FleetMissionArgs& ma, const FleetArgs& fa, hipStream_t st);
+// the move-back rule (fleet_moveback_kernels.hip): nep_batch_fleet_moveback.  State, bases, clocks and the slots' flags are FleetArgs',
+// fa.start the round's start records; t_issue is the mission state's [slots], or null (every goal was issued at fa.cfg.t0)
+void launch_fleet_moveback(const nep_moveback_cfg& c, const FleetArgs& fa, const double* t_issue, hipStream_t st);
 // the fleet recorder (fleet_recorder_kernels.hip): nep_batch_fleet_snapshot / _snapshot_ring / _restore.  Section i of a scene block
 // (recorder_common.h) is the scene's part — `bytes` bytes — of the handle's array `p`, at `off` in the block.  All device pointers.
 struct RecorderSection { char* p; long off; unsigned bytes; unsigned pad_; };

@@ -120,10 +120,14 @@ class _Audited:
 
 class FleetLoop(_Audited):
     def __init__(self, par, statics, starts, goals, beam_width=32, delta_t_states=6, replan_every=5, device=None, skip_arrived=False, audit=False,
-                 tethers=False, check=True, ent_samples=3, search="beam", max_pops=300):
+                 tethers=False, check=True, ent_samples=3, search="beam", max_pops=300, moveback=None):
         import torch
+        from . import mission
         self.torch = torch
         self.tethers, self.check, self.ent_samples = tethers, check, ent_samples
+        # moveback: the reference's move-back strategy for the loop's one (first) goal — nep_moveback_step after every selection
+        self.moveback_cfg = mission.check_moveback(moveback)
+        self.sflags = np.zeros(par.num_agents, dtype=np.int32)      # NEP_FLEET_FLAG_WAY_BACK per agent
         self.astar = check_search(search, max_pops, tethers)
         if tethers:
             import dataclasses
@@ -230,6 +234,10 @@ class FleetLoop(_Audited):
             starts[a]["pos"] = A[0:3]; starts[a]["vel"] = A[3:6]; starts[a]["accel"] = A[6:9]
             starts[a]["goal"] = self.goals[a]
             starts[a]["t_start"] = t_start      # one clock per round; an agent whose plan is shorter rests at its end
+        if self.moveback_cfg is not None:       # the agents on their way back search towards their base (the goal was issued at t = 0)
+            from . import mission
+            mission.moveback_step(self.moveback_cfg, self.state, p.pb, None, 0.0, t_now, self.sflags, starts)
+        self.last_starts = starts
         rec = self._records(t_now)
         if self.skip_arrived:
             self._d_active.copy_(torch.from_numpy((~self.done).astype(np.int32)).reshape(1, N))
@@ -357,7 +365,7 @@ class DeviceFleetLoop(_Audited):
     """FleetLoop's rounds for S scenes at once with nothing on the host (include/neptune_fleet.h): the plan deques, point A, the
     splice, the composition and the control ticks of every (scene, agent) live in the batched handle, and a round
 
-        fleet_select -> frontend -> replan -> safety_commit -> fleet_commit -> [audit] -> fleet_tick
+        fleet_select -> [fleet_moveback] -> frontend -> replan -> safety_commit -> fleet_commit -> [audit] -> fleet_tick
 
     is one captured graph (graph=True: captured after the first eager round, replayed afterwards).  `scenes` are make_scene
     dicts with the same agent and obstacle counts, each with its own statics; `goals` ([S][N][3], default: every scene's
@@ -376,8 +384,8 @@ class DeviceFleetLoop(_Audited):
     tethers=True flies tethered agents: the handle is created with enable_entangle and carries every tether's
     entangle state at the tracked position, and the round becomes
 
-        fleet_select -> fleet_predict_ent -> frontend_ent -> replan (entangle rows) -> safety_commit_ent -> fleet_commit -> [audit]
-          -> fleet_track_ent -> fleet_tick
+        fleet_select -> [fleet_moveback] -> fleet_predict_ent -> frontend_ent -> replan (entangle rows) -> safety_commit_ent
+          -> fleet_commit -> [audit] -> fleet_track_ent -> fleet_tick
 
     with the state at A (d_ent_a) predicted on the device and the commit records stamped with the published bend points before the
     safety pass (stamp_bends).  check=False keeps the plain front end and safety pass and leaves the tracking on: what the
@@ -397,21 +405,32 @@ class DeviceFleetLoop(_Audited):
     recorder=R keeps the complete fleet state before each of the last R rounds in a device ring: fleet_snapshot_ring
     is the first call of the round, inside the graph, and entry r mod R holds the state before round r.  rewind(scene, round)
     then gives a one-scene eager loop with tracing on, restored to the state before that round; save_checkpoint(path) and
-    resume(path, scenes) carry a flight over the end of the process.  With recorder=None nothing is allocated or launched."""
+    resume(path, scenes) carry a flight over the end of the process.  With recorder=None nothing is allocated or launched.
+
+    moveback=mission.MoveBack(radius, timeout) flies the reference's use_moveback_strategy: fleet_moveback goes
+    after fleet_select, and a slot with a new goal — the first one, or one a mission issued at the end of the last round — searches
+    towards its own base until it is within `radius` of it or `timeout` seconds have passed.  The slot's goal, the arrival test and
+    the missions' leg tests stay on the real goal.  report() adds `way_back`, the slots on their way back now, per scene; rewind
+    twins, checkpoints and resume carry the option, and a snapshot carries a move-back in progress.  With moveback=None nothing
+    is launched."""
 
     # the options a restored flight must share with the flight the snapshot was taken from
-    _MUST_MATCH = ("beam_width", "delta_t_states", "replan_every", "audit", "ring_cap", "tethers", "check", "ent_samples", "ent_cap")
+    _MUST_MATCH = ("beam_width", "delta_t_states", "replan_every", "audit", "ring_cap", "tethers", "check", "ent_samples", "ent_cap", "moveback")
 
     def __init__(self, scenes, beam_width=32, delta_t_states=6, replan_every=5, periods=None, phases=None, audit=False, graph=True,
                  goals=None, device=None, ring_cap=0, trace=False, tethers=False, check=True, ent_samples=3, missions=None, ent_cap=None,
-                 ent_lists0=None, recorder=None, search="beam", max_pops=300):
+                 ent_lists0=None, recorder=None, search="beam", max_pops=300, moveback=None):
         import torch
+        from . import mission as mission_mod
         self.torch = torch
         self.scenes = scenes
+        if isinstance(moveback, dict):      # (a checkpoint's options carry it as plain data)
+            moveback = mission_mod.MoveBack(**moveback)
+        self.moveback, self.moveback_cfg = moveback, mission_mod.check_moveback(moveback)
         self.astar = check_search(search, max_pops, tethers)
         self._opts = dict(beam_width=beam_width, delta_t_states=delta_t_states, replan_every=replan_every, audit=audit, ring_cap=ring_cap,
                           tethers=tethers, check=check, ent_samples=ent_samples, ent_cap=ent_cap, missions=missions, goals=goals,
-                          search=search, max_pops=max_pops)
+                          search=search, max_pops=max_pops, moveback=moveback)
         S = self.S = len(scenes)
         p = self.p = scenes[0]["par"]
         self.tethers, self.check, self.ent_samples = tethers, check, ent_samples
@@ -502,6 +521,8 @@ class DeviceFleetLoop(_Audited):
         if self.d_ring is not None:      # the state before this round -> entry round mod R
             be.fleet_snapshot_ring(self.d_ring, self.recorder)
         be.fleet_select(self.d_start, self.d_rec, self.d_active, self.d_clock if self.d_audit is not None else None)
+        if self.moveback_cfg is not None:      # the slots on their way back search towards their base
+            be.fleet_moveback(self.moveback_cfg, self.d_start)
         if self.tethers:
             if self.d_hold is not None:
                 self.d_hold.fill_(1)
@@ -557,6 +578,7 @@ class DeviceFleetLoop(_Audited):
         cnt, t_now, rnd = be.fleet_counters()
         st = be.fleet_state(pwp=False)
         state = st["state"].reshape(self.S, self.N, 12); done = st["done"].reshape(self.S, self.N)
+        flags = st["flags"].reshape(self.S, self.N)
         summ = audit_mod.summarize(self.audit_records(), self.S) if self.d_audit is not None else None
         ever = be.fleet_ent_state(states=False)["ever"].reshape(self.S, self.N) if self.tethers else None
         lists = held = None
@@ -576,6 +598,8 @@ class DeviceFleetLoop(_Audited):
                      qp_relaxed=int(c[6]), rejected_by_safety=int(c[3]), cap=int(c[5]), skipped=int(c[0]),
                      solves=int(c[1] + c[2] + c[3] + c[4] + c[5] + (0 if self.masked else c[0])), sim_time=float(t_now[s]), reached=int(done[s].sum()),
                      dist_to_goal_mean=float(np.hypot(*(state[s, :, :2] - goals_now[s, :, :2]).T).mean()))
+            if self.moveback_cfg is not None:      # the slots on their way back to their base now (the bit is no error and not sticky)
+                d["way_back"] = int(((flags[s] & abi.NEP_FLEET_FLAG_WAY_BACK) != 0).sum())
             if lists is not None:      # slot-rounds held at point A and the longest list now
                 d["held"] = int(held[s].sum()); d["max_list"] = int(lists.n_alpha.reshape(self.S, self.N)[s].max())
                 d["bend_full"] = int((lists.n_bend.reshape(self.S, self.N)[s] >= abi.NEP_MAX_BEND - 1).sum())      # (tethers at the bend-point limit)
@@ -599,6 +623,7 @@ class DeviceFleetLoop(_Audited):
         o = {k: self._opts[k] for k in self._MUST_MATCH}
         o["ent_cap"] = self.ent_cap
         o["missions"] = dataclasses.asdict(self.missions) if self.missions is not None else None
+        o["moveback"] = dataclasses.asdict(self.moveback) if self.moveback is not None else None
         o["masked"] = bool(self.masked)
         o["search"], o["max_pops"] = self._opts["search"], int(self._opts["max_pops"])
         o["N"], o["n_statics"] = int(self.N), len(self.scenes[0]["statics"])
@@ -660,6 +685,9 @@ class DeviceFleetLoop(_Audited):
         with np.load(path, allow_pickle=False) as z:
             blob, rounds, opts = z["blob"], int(z["rounds"]), json.loads(str(z["options"]))
             aud = z["audit"] if "audit" in z.files else None
+        opts.setdefault("moveback", None)      # (a file from before the option flew without it)
+        if isinstance(kw.get("moveback"), mission.MoveBack):
+            kw = dict(kw, moveback=__import__("dataclasses").asdict(kw["moveback"]))
         for k in cls._MUST_MATCH:
             if k in kw and kw[k] != opts[k] and not (k == "ent_cap" and kw[k] == "auto"):
                 raise ValueError("checkpoint %s was flown with %s=%r, not %r" % (path, k, opts[k], kw[k]))

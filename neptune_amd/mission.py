@@ -54,6 +54,50 @@ def mission_cfg(spec, par):
     return c
 
 
+@dataclasses.dataclass
+class MoveBack:
+    """The reference's use_moveback_strategy (neptune_ros.cpp:1626-1636, 1291-1305; include/neptune_fleet.h:
+    nep_batch_fleet_moveback): an agent with a new goal first plans towards its own base and gets the goal once it is within
+    `radius` of the base or `timeout` seconds have passed.  radius <= 0: only the timer releases."""
+    radius: float
+    timeout: float = 10.0
+
+    def __post_init__(self):
+        import math
+        self.radius, self.timeout = float(self.radius), float(self.timeout)
+        if not math.isfinite(self.radius) or not math.isfinite(self.timeout) or self.timeout < 0.0:
+            raise ValueError("MoveBack: radius must be finite, timeout finite and >= 0")
+
+    @classmethod
+    def reference(cls, num_agents, timeout=10.0):
+        """neptune_mtlp_benchmark.yaml's radius for a fleet of num_agents: 6.33 - (N - 4) * 0.33 (<= 0 from N = 24 up)"""
+        return cls(6.33 - (num_agents - 4) * 0.33, timeout)
+
+    def cfg(self):
+        return abi.nep_moveback_cfg(self.radius, self.timeout)
+
+
+def check_moveback(moveback):
+    """None or a MoveBack, else TypeError -> its abi.nep_moveback_cfg or None"""
+    if moveback is None:
+        return None
+    if not isinstance(moveback, MoveBack):
+        raise TypeError("moveback must be None or a neptune_amd.mission.MoveBack")
+    return moveback.cfg()
+
+
+def moveback_step(cfg, state, pb, t_issue, t_first, t_now, flags, start):
+    """nep_moveback_step, the host form of one scene: state [n][12] float64, pb [n][2], t_issue [n] or None, flags [n] int32 and
+    start [n] FE_START_DTYPE updated in place"""
+    n = len(flags)
+    state = np.ascontiguousarray(state, dtype=np.float64); pb = np.ascontiguousarray(pb, dtype=np.float64)
+    ti = None if t_issue is None else np.ascontiguousarray(t_issue, dtype=np.float64)
+    assert state.size == 12 * n and pb.size == 2 * n and (ti is None or ti.size == n) and len(start) == n
+    assert flags.dtype == np.int32 and flags.flags.c_contiguous and start.dtype == abi.FE_START_DTYPE and start.flags.c_contiguous
+    check(lib().nep_moveback_step(C.byref(cfg), n, state.ctypes.data, pb.ctypes.data, None if ti is None else ti.ctypes.data, float(t_first),
+                                  float(t_now), flags.ctypes.data, start.ctypes.data))
+
+
 def uses_keepouts(spec):
     return (spec.mode == "agent") if spec.keepouts is None else bool(spec.keepouts)
 

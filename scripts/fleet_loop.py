@@ -16,6 +16,9 @@ one round eagerly with tracing on and prints every agent's outcome, K and status
 the summary names the --rewind argument of the round in which the worst box clearance was flown.  --save PATH writes a checkpoint
 when the flight stops (at --rounds); --resume PATH continues one, up to --rounds rounds of the whole flight.
 
+--moveback [RADIUS|ref] [--moveback-timeout S]: fleet_moveback joins the round after fleet_select: an agent with a
+new goal plans towards its own base first, as the reference's use_moveback_strategy does.
+
 --stagger P: every agent replans every P-th round, agent a in the rounds with (round - a) mod P == 0, and a round flies one control
 tick (FleetLoop's cadence at P = 5 with the agents' timers spread over the ticks).  --host flies scene 0 with FleetLoop as well and
 prints its wall time per round next to the device loop's (one scene each)."""
@@ -48,6 +51,8 @@ def main():
     ap.add_argument("--fe-big-records", type=int, default=0, metavar="R", help="with --tethers: records in the front end's pool of big entangle-state records (nep_batch_set_fe_ent_big_records; 0: the default, 4 per slot)")
     ap.add_argument("--missions", choices=("agent", "runs"), help="a campaign (DESIGN section 23): per-agent successive goals (NeptuneRos::autoCMD) or fleet-wide runs (benchmark_mtlp.py), drawn on the device inside the graph; the flight stops when every scene's campaign is over")
     ap.add_argument("--goals", type=int, default=2, metavar="G", help="with --missions: legs per agent / runs per scene")
+    ap.add_argument("--moveback", nargs="?", const="ref", metavar="RADIUS|ref", help="the reference's move-back strategy (DESIGN section 32): an agent with a new goal first plans towards its own base, until it is within RADIUS m of it (ref, the default: 6.33 - (agents - 4) * 0.33) or --moveback-timeout has passed")
+    ap.add_argument("--moveback-timeout", type=float, default=10.0, metavar="S", help="with --moveback: seconds of simulated time after which the goal is released anyway")
     ap.add_argument("--record", type=int, default=0, metavar="R", help="flight recorder: the state before each of the last R rounds in a device ring, inside the graph")
     ap.add_argument("--rewind", metavar="SCENE:ROUND", help="fly ROUND + 1 rounds recorded (default --record 8), then that scene alone from the state before ROUND: one eager round, traced")
     ap.add_argument("--save", metavar="PATH", help="write a checkpoint (.npz) when the flight stops")
@@ -69,6 +74,11 @@ def main():
     if a.missions:
         from neptune_amd import mission
         kw.update(missions=mission.MissionSpec(a.missions, goals=a.goals, seed=a.seed0 + 1))
+    mb = None
+    if a.moveback:
+        from neptune_amd import mission
+        mb = mission.MoveBack.reference(a.agents, a.moveback_timeout) if a.moveback == "ref" else mission.MoveBack(float(a.moveback), a.moveback_timeout)
+        kw.update(moveback=mb)
     if a.stagger > 0:
         kw.update(replan_every=1, periods=a.stagger, phases=np.tile(np.arange(a.agents) % a.stagger, (a.scenes, 1)))
 
@@ -140,6 +150,8 @@ def main():
         if a.ent_cap:
             tot.update(held=int(sum(r["held"] for r in rep)), max_list=int(max(r["max_list"] for r in rep)), bend_full=int(sum(r["bend_full"] for r in rep)))
     print("total over %d scenes x %d agents, %d rounds: %s" % (a.scenes, a.agents, n, json.dumps(tot)))
+    if a.moveback:
+        print("move-back (radius %.2f m, timeout %.1f s): %d slots on their way back at the end" % (mb.radius, mb.timeout, sum(r["way_back"] for r in rep)))
     if a.missions:
         ms = [r["mission"] for r in rep]
         ended = sum(m["legs_reached"] + m["legs_timed_out"] for m in ms)
@@ -162,7 +174,7 @@ def main():
     if a.host:
         sc = scenes[0]
         _, dev1, n1 = fly([sc], a.rounds)
-        ref = FleetLoop(sc["par"], sc["statics"], sc["starts"], scene.reachable_goals(sc), beam_width=a.beam, audit=a.audit, tethers=a.tethers, check=not a.no_check, search=a.search, max_pops=a.max_pops)
+        ref = FleetLoop(sc["par"], sc["statics"], sc["starts"], scene.reachable_goals(sc), beam_width=a.beam, audit=a.audit, tethers=a.tethers, check=not a.no_check, search=a.search, max_pops=a.max_pops, moveback=mb)
         ref.round(); ref.round()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
