@@ -5,8 +5,8 @@
  * trip per agent and round.  Here the same state lives in the batched handle (include/neptune_backend.h: nep_batch_t), per
  * (scene, agent) slot, and three asynchronous calls move it — so a faithful round
  *
- *   nep_batch_fleet_select [-> nep_batch_fleet_moveback] -> nep_batch_frontend -> nep_batch_replan -> nep_batch_safety_commit ->
- *     nep_batch_fleet_commit [-> nep_batch_audit] [-> nep_batch_fleet_mission] -> nep_batch_fleet_tick
+ *   nep_batch_fleet_select [-> nep_batch_fleet_moveback] -> nep_batch_frontend [-> nep_batch_goal_gate] -> nep_batch_replan ->
+ *     nep_batch_safety_commit -> nep_batch_fleet_commit [-> nep_batch_audit] [-> nep_batch_fleet_mission] -> nep_batch_fleet_tick
  *
  * is a fixed launch sequence on fixed buffers: one HIP graph for all scenes, no host synchronisation in it.  The arithmetic is the
  * host library's own (neptune_amd/csrc/plan_common.h is compiled into both), so the plans, tracked states and trajectories on the
@@ -356,7 +356,8 @@ int nep_mission_step(const nep_mission_cfg* cfg, nep_mission_scene* sc);
  *                    and then only the timer releases.
  *   the own base     the back end treats the agent's own base square as an obstacle (solver_gurobi_poly.cpp:521-553), so an agent
  *                    approaches its base and does not reach it — the reference's behaviour too.
- *   move_when_goal_occupied, the yaml's other switch: not built.
+ *   move_when_goal_occupied, the yaml's other switch, is nep_batch_goal_gate (include/neptune_frontend.h), behind the front end: a
+ *                    slot on its way back is tested at its base, the goal its search got.
  *
  * nep_batch_fleet_moveback   between nep_batch_fleet_select and the front end (tethered rounds: before or after
  *                    nep_batch_fleet_predict_ent, which does not read the goal).  One thread per slot, every slot whatever the

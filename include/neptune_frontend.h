@@ -120,7 +120,7 @@ typedef struct nep_fe_result {
   int32_t _pad;                   /* entangle check on: bit 3 = the pool of big records ran out (ent_overflow); bits 8
                                      and up = children of this search whose state went into a big record; nep_batch_frontend_astar and
                                      nep_batch_frontend_astar_ent: bit 4 = the search ran into a node pool smaller than the
-                                     reference's; else 0                                                              */
+                                     reference's; nep_batch_goal_gate: bits 5 and 6 (NEP_FE_PAD_GATED, NEP_FE_PAD_GOAL_TAKEN); else 0 */
   double cost;                    /* g + bias*h of the returned node                               */
   double dist_to_goal;
   int32_t n_entangled;            /* children pruned by entanglesWithOtherAgents (entangle check on)        */
@@ -207,6 +207,41 @@ int nep_batch_frontend_astar(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_tr
 #define NEP_FE_ASTAR_ENT_NODE_BYTES 456
 int nep_batch_frontend_astar_ent(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_traj_rec* d_committed, const nep_fe_start* d_start, const nep_fe_ent_state* d_ent_init,
                                  nep_guess* d_guess, nep_fe_result* d_result, int32_t* d_case_out, void* stream);
+
+/* ---- move_when_goal_occupied: a plan that does not reach its goal is flown only when somebody is on the goal --------------------
+ * The reference's benchmark yaml sets move_when_goal_occupied next to use_not_reaching_soln.  Neptune::replanFull (neptune.cpp:1480-1500):
+ * a search that did not reach the goal (search_result != 1) has returned its closest-so-far node; that node is flown only if
+ * gjk::collision finds the square goal +- drone_radius on the LAST interval hull of some entry of hulls2d (the other agents' committed
+ * trajectories; the statics are not in it).  Otherwise replanFull returns false and the vehicle keeps its committed plan.
+ *
+ * nep_batch_goal_gate   goes between ANY front-end call and nep_batch_replan and reads only d_result[slot].status, so it serves the
+ *   beam and both best-first searches alike.  One wave per slot (goal_gate.h).  A slot whose status is NEP_FE_GOAL_REACHED,
+ *   NEP_FE_NO_SOLUTION or NEP_FE_SKIPPED is not touched.  A slot with NEP_FE_DEPTH_REACHED or NEP_FE_EMPTY is examined:
+ *     the goal      d_start[slot].goal, the goal the search got (a slot on its way back, nep_batch_fleet_moveback, is tested at its
+ *                   base, as setTerminalGoal(near_base) makes the reference do)
+ *     the box       (gx+r, gy+r), (gx+r, gy-r), (gx-r, gy+r), (gx-r, gy-r), r = half_side: the column order of neptune.cpp:1485-1488
+ *     occupied      some agent j != own has hull_nv > 0 and gjk_collision true on its hull of interval num_pol - 1: the obstacle set
+ *                   and indexing of the searches' own goal_occupied_ test.  The hulls are the ones the preceding front-end call left
+ *                   in the handle's scratch; the gate builds none.
+ *     occupied      _pad |= NEP_FE_PAD_GOAL_TAKEN; nothing else is written.
+ *     free          the slot becomes what a search without a first primitive leaves: d_guess[slot] K = 0, n_alpha = 0, every
+ *                   coefficient 0.0, t_start kept; d_result[slot] status = NEP_FE_NO_SOLUTION, K = 0, _pad |= NEP_FE_PAD_GATED, every
+ *                   other field kept (the search that was turned down stays visible); with d_case the slot's NEP_MAX_POL x N case
+ *                   rows are zeroed.  The replan, the safety pass and nep_batch_fleet_commit (NEP_FLEET_FE_NO_SOLUTION) know these bytes.
+ *   d_count         [n_scenes][4] or NULL: {examined, let through, turned down, 0} per scene, ADDED to with integer atomics; the
+ *                   caller owns and zeroes it.  A second call on the same buffers examines the let-through slots again (and counts
+ *                   them again); the slots it turned down are NEP_FE_NO_SOLUTION now.
+ *   What differs from the reference: the test runs once per bulk-synchronous round, against the hulls every agent's search saw;
+ *   nep_fe_result.goal_occupied stays setUp's other box (kinodynamic_search.cpp:210-226, half side 0.5 hard-coded).
+ *   Asynchronous on `stream`, allocates nothing, capturable.  NEP_E_ARG: a null h, d_start, d_guess or d_result, a half_side that
+ *   is not finite or <= 0.  NEP_E_STATE: no nep_batch_frontend / _ent / _astar / _astar_ent call has been made on the handle, or the
+ *   last front-end call was a _hulls one (no hulls in the scratch); a sharded handle (n_local != num_agents).  The _hulls / sharded
+ *   form and a host form are not built.                                                                                          */
+#define NEP_FE_PAD_GATED      32   /* nep_fe_result._pad bit 5: turned down by nep_batch_goal_gate */
+#define NEP_FE_PAD_GOAL_TAKEN 64   /* bit 6: examined by the gate, goal occupied, let through      */
+int nep_batch_goal_gate(nep_batch_t* h, double half_side, const nep_fe_start* d_start, nep_guess* d_guess,
+                        nep_fe_result* d_result, int32_t* d_case /* [slots][NEP_MAX_POL][N] or NULL */,
+                        int32_t* d_count /* [n_scenes][4], accumulating, or NULL */, void* stream);
 
 /* The same against all-gathered hull blocks (multi-GPU rounds, include/neptune_backend.h:
  * nep_batch_hulls -> all-gather -> nep_batch_frontend_hulls -> nep_batch_replan_hulls).            */

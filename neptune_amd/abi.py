@@ -17,6 +17,8 @@ NEP_STATE_DOUBLES = 12
 NEP_OK, NEP_RELAXED, NEP_FAILED = 0, 1, 2
 NEP_SKIPPED = 3          # nep_stats.status of a slot outside the active set (nep_batch_set_active)
 NEP_FE_SKIPPED = 4       # nep_fe_result.status of a slot outside the active set
+NEP_FE_PAD_GATED, NEP_FE_PAD_GOAL_TAKEN = 32, 64      # nep_fe_result._pad bits 5 and 6: turned down / let through by nep_batch_goal_gate
+GOAL_GATE_COUNTS = ("examined", "goal_taken", "gated", "unused")      # nep_batch_goal_gate's d_count [n_scenes][4]
 
 
 class nep_pwp(C.Structure):

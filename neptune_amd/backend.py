@@ -332,6 +332,16 @@ class BatchBackend:
         check(lib().nep_batch_frontend_astar(self._h, C.byref(fe_cfg), d_committed.data_ptr(), d_start.data_ptr(), d_guess.data_ptr(),
                                              d_result.data_ptr() if d_result is not None else None, st.cuda_stream))
 
+    def goal_gate(self, d_start, d_guess, d_result, half_side=None, d_case=None, d_count=None, stream=None):
+        """the reference's move_when_goal_occupied gate (nep_batch_goal_gate), between any front-end call and replan: a slot whose
+        search did not reach its goal keeps its plan only when another agent's last interval hull lies on the square goal +-
+        half_side (None: the handle's drone_radius); otherwise it becomes a NO_SOLUTION slot (guess and, with d_case, case rows
+        zeroed).  d_count: int32 [n_scenes][4] (abi.GOAL_GATE_COUNTS), added to"""
+        st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        check(lib().nep_batch_goal_gate(self._h, float(self.par.drone_radius if half_side is None else half_side), d_start.data_ptr(), d_guess.data_ptr(),
+                                        d_result.data_ptr(), d_case.data_ptr() if d_case is not None else None,
+                                        d_count.data_ptr() if d_count is not None else None, st.cuda_stream))
+
     # ---- entangle check on (include/neptune_frontend.h) ------------------------------------------------------------
     def set_static_reps(self, reps, longest, scene=-1):
         """staticObsRep_ [S][2][2] and staticObsLongestDist_ [S][2] (nep_batch_set_static_reps)"""

@@ -1281,6 +1281,19 @@ int nep_batch_frontend_astar(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_tr
   return 0;
 }
 
+// ---- the reference's move_when_goal_occupied gate (goal_gate.h): between any front-end call and nep_batch_replan ----
+int nep_batch_goal_gate(nep_batch_t* h, double half_side, const nep_fe_start* d_start, nep_guess* d_guess, nep_fe_result* d_result,
+                        int32_t* d_case, int32_t* d_count, void* stream) {
+  if (!h || !d_start || !d_guess || !d_result) return fail(NEP_E_ARG, "null argument");
+  if (!std::isfinite(half_side) || !(half_side > 0.0)) return fail(NEP_E_ARG, "nep_batch_goal_gate: half_side must be finite and positive");
+  if (h->cfg.n_local != h->cfg.num_agents) return fail(NEP_E_STATE, "nep_batch_goal_gate runs on an unsharded handle (n_local == num_agents)");
+  if (h->eng.sp.n_hull != h->cfg.num_agents) return fail(NEP_E_STATE, "nep_batch_goal_gate needs the batched (all-agent) hull layout");
+  if (!h->fe_committed) return fail(NEP_E_STATE, "nep_batch_goal_gate: no front-end call has left this round's hulls in the handle's scratch");
+  launch_goal_gate(h->slots, h->eng.sp, round_set(h), half_side, d_start, d_guess, d_result, d_case, d_count, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 int nep_batch_set_active(nep_batch_t* h, const int32_t* d_active) {
   if (!h) return fail(NEP_E_ARG, "null handle");
   Engine& E = h->eng;

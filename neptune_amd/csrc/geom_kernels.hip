@@ -3043,6 +3043,9 @@ void launch_frontend(int n_slots, const SceneParams& sp, const ProblemSet& ps_in
 // the reference's best-first search over the same lattice, without and with the entangle check (nep_batch_frontend_astar, nep_batch_frontend_astar_ent)
 #include "fe_astar.h"
 
+// the reference's move_when_goal_occupied gate behind any of the front ends above (nep_batch_goal_gate)
+#include "goal_gate.h"
+
 // Neptune::SamplePointsOfIntervals (neptune.cpp:500-565) for every committed trajectory of every scene:
 // sampled[scene][j][interval][0..ns][2] on the round's grid, present[scene][j] = the trajectory exists (trajs_ holds it)
 __global__ void ent_sample_kernel(const nep_traj_rec* __restrict__ recs, int n_scenes, int N, const double* __restrict__ ts0, long ts_scene_stride,

@@ -253,6 +253,10 @@ struct FeAstarEntArgs {
 // (xa and ea null: the plain search; both set: the search with the entangle check)
 void launch_frontend_astar(int n_slots, const SceneParams& sp, const ProblemSet& ps, const nep_fe_cfg& fc, const FeAstarArgs& aa, const FeAstarEntArgs* xa, const FeEntArgs* ea,
                            const nep_fe_start* starts, nep_guess* guess_out, nep_fe_result* res_out, hipStream_t st, int* active_buf = nullptr);
+// nep_batch_goal_gate (goal_gate.h): one wave per slot behind a front end; the hulls are the ones ps points at.  case_out
+// [slots][NEP_MAX_POL][N] and count [n_scenes][4] may be null
+void launch_goal_gate(int n_slots, const SceneParams& sp, const ProblemSet& ps, double half_side, const nep_fe_start* starts, nep_guess* guess,
+                      nep_fe_result* res, int* case_out, int* count, hipStream_t st);
 void launch_ent_sample(const nep_traj_rec* recs, int n_scenes, int N, const double* ts0, long ts_scene_stride, int num_pol, int ns, double T_span,
                        double* sampled, int* present, hipStream_t st, int* zero_this = nullptr);
 // nep_batch_audit (audit_kernels.hip): the minima of one (scene, run of ticks, agent), ticks as indices of the call

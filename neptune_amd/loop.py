@@ -75,18 +75,40 @@ def check_search(search, max_pops, tethers):
     return search != "beam"
 
 
-def plan_round(be, fe, d_rec, d_start, d_guess, d_res, d_final, d_acc, tethers=False, d_case=None, d_ent=None, ent_samples=3, astar=False):
+def check_goal_gate(goal_gate, search, drone_radius):
+    """the reference's move_when_goal_occupied gate (BatchBackend.goal_gate): False / None (off), True (the box
+    goal +- drone_radius, the reference's) or a half side in metres -> the half side, or None.  Not with the beam, whose ordinary
+    outcome for a far goal is DEPTH_REACHED: the gate would ground the fleet."""
+    if goal_gate is None or goal_gate is False:
+        return None
+    if not isinstance(goal_gate, (bool, int, float, np.integer, np.floating)):
+        raise ValueError("goal_gate must be False, True or a half side in metres")
+    r = float(drone_radius if goal_gate is True else goal_gate)
+    if not (np.isfinite(r) and r > 0.0):
+        raise ValueError("goal_gate: the half side must be finite and positive, not %r" % (r,))
+    if search == "beam":
+        raise ValueError("goal_gate needs search='astar' or 'astar_ent': the beam's ordinary outcome for a far goal is DEPTH_REACHED, "
+                         "and the gate would ground the fleet")
+    return r
+
+
+def plan_round(be, fe, d_rec, d_start, d_guess, d_res, d_final, d_acc, tethers=False, d_case=None, d_ent=None, ent_samples=3, astar=False, gate=None):
     """the plan half of a round: front end -> lines + QP -> safety pass, from the records d_rec and the starts d_start into d_final
     and d_acc.  With d_case the entangle check is on (d_ent: every tether's state at A): the QP gets the entangle rows and the safety
     pass re-checks.  Tethered rounds stamp the published bend points into the commit records before the safety pass.  astar: the
-    best-first search in place of the beam (check_search) — with d_case that is search="astar_ent", frontend_astar_ent."""
+    best-first search in place of the beam (check_search) — with d_case that is search="astar_ent", frontend_astar_ent.
+    gate: (half side, d_count or None) — the move_when_goal_occupied gate right behind the front end (check_goal_gate)."""
     if d_case is not None:
         (be.frontend_astar_ent if astar else be.frontend_ent)(fe, d_rec, d_start, d_guess, d_res, d_case, d_ent_init=d_ent)
+        if gate is not None:
+            be.goal_gate(d_start, d_guess, d_res, gate[0], d_case=d_case, d_count=gate[1])
         be.replan(None, d_guess, d_ent=d_case)
         stamp_bends(be.d_commit, d_rec)
         be.safety_commit_ent(d_rec, be.d_commit, d_guess, d_final, d_acc, d_ent_init=d_ent, ent_samples=ent_samples)
     else:
         (be.frontend_astar if astar else be.frontend)(fe, d_rec, d_start, d_guess, d_res)      # (astar: the handle's set_fe_astar was called)
+        if gate is not None:
+            be.goal_gate(d_start, d_guess, d_res, gate[0], d_count=gate[1])
         be.replan(None, d_guess)
         if tethers:
             stamp_bends(be.d_commit, d_rec)
@@ -120,11 +142,14 @@ class _Audited:
 
 class FleetLoop(_Audited):
     def __init__(self, par, statics, starts, goals, beam_width=32, delta_t_states=6, replan_every=5, device=None, skip_arrived=False, audit=False,
-                 tethers=False, check=True, ent_samples=3, search="beam", max_pops=300, moveback=None):
+                 tethers=False, check=True, ent_samples=3, search="beam", max_pops=300, moveback=None, goal_gate=False):
         import torch
         from . import mission
         self.torch = torch
         self.tethers, self.check, self.ent_samples = tethers, check, ent_samples
+        # goal_gate: the reference's move_when_goal_occupied — a plan that does not reach the goal is flown only
+        # when somebody else is on the goal; a gated replan counts as fe_no_solution (stats: gate_examined, goal_taken, gated)
+        self.goal_gate = check_goal_gate(goal_gate, search, par.drone_radius)
         # moveback: the reference's move-back strategy for the loop's one (first) goal — nep_moveback_step after every selection
         self.moveback_cfg = mission.check_moveback(moveback)
         self.sflags = np.zeros(par.num_agents, dtype=np.int32)      # NEP_FLEET_FLAG_WAY_BACK per agent
@@ -175,6 +200,10 @@ class FleetLoop(_Audited):
         self.trace = None                      # set to a list to record (t, agent, outcome, K) of every replan
         self.stats = dict(rounds=0, replans=0, accepted=0, fe_no_solution=0, qp_failed=0, qp_relaxed=0, rejected_by_safety=0,
                           min_pair_dist=np.inf, min_static_dist=np.inf, solves=0)
+        self._d_gate_count = None
+        if self.goal_gate is not None:
+            self._d_gate_count = torch.zeros((1, 4), dtype=torch.int32, device=self.be.device)
+            self.stats.update(gate_examined=0, goal_taken=0, gated=0)
         self._static_pts = [np.asarray(s, dtype=np.float64) for s in scene_raw(statics, par)]
         # audit: every round also audits, on the device, the records it uploads anyway over the replan_every ticks about to be flown
         # (nep_batch_audit; those ticks lie before the round's point A, so the uploaded records describe them); _tick keeps its host log
@@ -256,8 +285,13 @@ class FleetLoop(_Audited):
         if self.tethers and self.check:
             d_ent_a = be.to_device(self.ent_a)
             d_case = torch.zeros(N * abi.NEP_MAX_POL * N, dtype=torch.int32, device=be.device)
-        plan_round(be, self.fe, d_com, d_start, d_guess, d_fres, d_final, d_acc, self.tethers, d_case, d_ent_a, self.ent_samples, self.astar)
+        plan_round(be, self.fe, d_com, d_start, d_guess, d_fres, d_final, d_acc, self.tethers, d_case, d_ent_a, self.ent_samples, self.astar,
+                   gate=(self.goal_gate, self._d_gate_count) if self.goal_gate is not None else None)
         sol = be.solutions(); states = be.states(); fres = d_fres.cpu().numpy().view(abi.FE_RESULT_DTYPE)
+        self.last_fres = fres
+        if self._d_gate_count is not None:
+            gc = self._d_gate_count.cpu().numpy()[0]
+            self.stats.update(gate_examined=int(gc[0]), goal_taken=int(gc[1]), gated=int(gc[2]))
         acc = d_acc.cpu().numpy()
         self.stats["rounds"] += 1
         for a in range(N):
@@ -412,25 +446,34 @@ class DeviceFleetLoop(_Audited):
     towards its own base until it is within `radius` of it or `timeout` seconds have passed.  The slot's goal, the arrival test and
     the missions' leg tests stay on the real goal.  report() adds `way_back`, the slots on their way back now, per scene; rewind
     twins, checkpoints and resume carry the option, and a snapshot carries a move-back in progress.  With moveback=None nothing
-    is launched."""
+    is launched.
+
+    goal_gate=True (or a half side in metres) flies the reference's move_when_goal_occupied: BatchBackend.goal_gate
+    goes right behind the front end, and a slot whose search did not reach its goal keeps its closest-so-far plan only when another
+    agent's committed trajectory ends on the square goal +- drone_radius (the goal the search got: a slot on its way back is tested
+    at its base); otherwise the slot is turned down and keeps flying its committed plan.  Not with search="beam" (ValueError).
+    report() adds gate_examined, goal_taken and gated per scene, and fe_no_solution now INCLUDES the gated replans (they reach
+    fleet_commit as NEP_FE_NO_SOLUTION).  The gate keeps no state: snapshots are what they were; the counts belong to the loop
+    (d_gate_count) and travel in a checkpoint; rewind twins and resume carry the option (a file from before it resumes without)."""
 
     # the options a restored flight must share with the flight the snapshot was taken from
-    _MUST_MATCH = ("beam_width", "delta_t_states", "replan_every", "audit", "ring_cap", "tethers", "check", "ent_samples", "ent_cap", "moveback")
+    _MUST_MATCH = ("beam_width", "delta_t_states", "replan_every", "audit", "ring_cap", "tethers", "check", "ent_samples", "ent_cap", "moveback", "goal_gate")
 
     def __init__(self, scenes, beam_width=32, delta_t_states=6, replan_every=5, periods=None, phases=None, audit=False, graph=True,
                  goals=None, device=None, ring_cap=0, trace=False, tethers=False, check=True, ent_samples=3, missions=None, ent_cap=None,
-                 ent_lists0=None, recorder=None, search="beam", max_pops=300, moveback=None):
+                 ent_lists0=None, recorder=None, search="beam", max_pops=300, moveback=None, goal_gate=False):
         import torch
         from . import mission as mission_mod
         self.torch = torch
         self.scenes = scenes
+        self.goal_gate = check_goal_gate(goal_gate, search, scenes[0]["par"].drone_radius)      # the half side, or None
         if isinstance(moveback, dict):      # (a checkpoint's options carry it as plain data)
             moveback = mission_mod.MoveBack(**moveback)
         self.moveback, self.moveback_cfg = moveback, mission_mod.check_moveback(moveback)
         self.astar = check_search(search, max_pops, tethers)
         self._opts = dict(beam_width=beam_width, delta_t_states=delta_t_states, replan_every=replan_every, audit=audit, ring_cap=ring_cap,
                           tethers=tethers, check=check, ent_samples=ent_samples, ent_cap=ent_cap, missions=missions, goals=goals,
-                          search=search, max_pops=max_pops, moveback=moveback)
+                          search=search, max_pops=max_pops, moveback=moveback, goal_gate=self.goal_gate)
         S = self.S = len(scenes)
         p = self.p = scenes[0]["par"]
         self.tethers, self.check, self.ent_samples = tethers, check, ent_samples
@@ -495,6 +538,7 @@ class DeviceFleetLoop(_Audited):
             self.d_flags_a = torch.zeros(n, dtype=torch.int32, device=dev)
             self.d_flags = torch.zeros(n, dtype=torch.int32, device=dev)
             self.d_case = torch.zeros(n * abi.NEP_MAX_POL * N, dtype=torch.int32, device=dev)
+        self.d_gate_count = torch.zeros((S, 4), dtype=torch.int32, device=dev) if self.goal_gate is not None else None      # abi.GOAL_GATE_COUNTS
         self.missions = missions
         if missions is not None:
             from . import mission
@@ -530,7 +574,8 @@ class DeviceFleetLoop(_Audited):
             if self.after_select is not None:
                 self.after_select(self)
         ent = (self.d_case, self.d_ent_a) if self.tethers and self.check else (None, None)
-        plan_round(be, self.fe, self.d_rec, self.d_start, self.d_guess, self.d_res, self.d_final, self.d_acc, self.tethers, *ent, self.ent_samples, self.astar)
+        plan_round(be, self.fe, self.d_rec, self.d_start, self.d_guess, self.d_res, self.d_final, self.d_acc, self.tethers, *ent, self.ent_samples, self.astar,
+                   gate=(self.goal_gate, self.d_gate_count) if self.goal_gate is not None else None)
         be.fleet_commit(self.d_res, self.d_acc, self.d_outcome)
         if self.after_commit is not None:
             self.after_commit(self)
@@ -568,7 +613,8 @@ class DeviceFleetLoop(_Audited):
 
     def report(self):
         """per scene FleetLoop.stats' keys (min_pair_dist / min_static_dist come from the audit when it is on), plus `cap` and the
-        audit's summary"""
+        audit's summary.  With goal_gate: gate_examined, goal_taken (let through) and gated (turned down) — slot-rounds; fe_no_solution
+        includes the gated ones"""
         be = self.be
         try:
             be.check()
@@ -585,6 +631,7 @@ class DeviceFleetLoop(_Audited):
         if self.ent_cap is not None:
             lists, held = be.fleet_ent_lists(self.ent_cap)
             held = held.reshape(self.S, self.N)
+        gate = self.d_gate_count.cpu().numpy() if self.d_gate_count is not None else None
         msum, goals_now = None, self.goals
         if self.missions is not None:
             from . import mission
@@ -600,6 +647,8 @@ class DeviceFleetLoop(_Audited):
                      dist_to_goal_mean=float(np.hypot(*(state[s, :, :2] - goals_now[s, :, :2]).T).mean()))
             if self.moveback_cfg is not None:      # the slots on their way back to their base now (the bit is no error and not sticky)
                 d["way_back"] = int(((flags[s] & abi.NEP_FLEET_FLAG_WAY_BACK) != 0).sum())
+            if gate is not None:       # slot-rounds the gate examined, let through (somebody on the goal) and turned down
+                d["gate_examined"], d["goal_taken"], d["gated"] = int(gate[s, 0]), int(gate[s, 1]), int(gate[s, 2])
             if lists is not None:      # slot-rounds held at point A and the longest list now
                 d["held"] = int(held[s].sum()); d["max_list"] = int(lists.n_alpha.reshape(self.S, self.N)[s].max())
                 d["bend_full"] = int((lists.n_bend.reshape(self.S, self.N)[s] >= abi.NEP_MAX_BEND - 1).sum())      # (tethers at the bend-point limit)
@@ -672,6 +721,8 @@ class DeviceFleetLoop(_Audited):
         data = dict(blob=blob.cpu().numpy(), rounds=np.int64(self.rounds), options=np.array(json.dumps(self._options())))
         if self.d_audit is not None:
             data["audit"] = self.d_audit.cpu().numpy()
+        if self.d_gate_count is not None:
+            data["gate_count"] = self.d_gate_count.cpu().numpy()
         with open(path, "wb") as f:
             np.savez(f, **data)
 
@@ -685,7 +736,11 @@ class DeviceFleetLoop(_Audited):
         with np.load(path, allow_pickle=False) as z:
             blob, rounds, opts = z["blob"], int(z["rounds"]), json.loads(str(z["options"]))
             aud = z["audit"] if "audit" in z.files else None
+            gcnt = z["gate_count"] if "gate_count" in z.files else None
         opts.setdefault("moveback", None)      # (a file from before the option flew without it)
+        opts.setdefault("goal_gate", None)     # (likewise)
+        if "goal_gate" in kw:                  # (False, True or a half side -> what the file holds: the half side, or None)
+            kw = dict(kw, goal_gate=check_goal_gate(kw["goal_gate"], opts.get("search", "beam") if kw["goal_gate"] else "astar", scenes[0]["par"].drone_radius))
         if isinstance(kw.get("moveback"), mission.MoveBack):
             kw = dict(kw, moveback=__import__("dataclasses").asdict(kw["moveback"]))
         for k in cls._MUST_MATCH:
@@ -709,6 +764,8 @@ class DeviceFleetLoop(_Audited):
             lp.be.fleet_restore(blob)      # (refuses another scene count, another configuration, another state)
             if aud is not None:
                 lp.d_audit.copy_(lp.torch.from_numpy(aud))
+            if gcnt is not None and lp.d_gate_count is not None:
+                lp.d_gate_count.copy_(lp.torch.from_numpy(gcnt))
         except Exception:
             lp.close()
             raise

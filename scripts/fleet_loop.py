@@ -19,6 +19,10 @@ when the flight stops (at --rounds); --resume PATH continues one, up to --rounds
 --moveback [RADIUS|ref] [--moveback-timeout S]: fleet_moveback joins the round after fleet_select: an agent with a
 new goal plans towards its own base first, as the reference's use_moveback_strategy does.
 
+--goal-gate [HALF_SIDE]: goal_gate joins the round right behind the front end: a plan that does not reach its goal
+is flown only when another agent's committed trajectory ends on the square goal +- HALF_SIDE (default: the drone radius), as the
+reference's move_when_goal_occupied does.  Only with --search astar / astar_ent.
+
 --stagger P: every agent replans every P-th round, agent a in the rounds with (round - a) mod P == 0, and a round flies one control
 tick (FleetLoop's cadence at P = 5 with the agents' timers spread over the ticks).  --host flies scene 0 with FleetLoop as well and
 prints its wall time per round next to the device loop's (one scene each)."""
@@ -53,6 +57,7 @@ def main():
     ap.add_argument("--goals", type=int, default=2, metavar="G", help="with --missions: legs per agent / runs per scene")
     ap.add_argument("--moveback", nargs="?", const="ref", metavar="RADIUS|ref", help="the reference's move-back strategy (DESIGN section 32): an agent with a new goal first plans towards its own base, until it is within RADIUS m of it (ref, the default: 6.33 - (agents - 4) * 0.33) or --moveback-timeout has passed")
     ap.add_argument("--moveback-timeout", type=float, default=10.0, metavar="S", help="with --moveback: seconds of simulated time after which the goal is released anyway")
+    ap.add_argument("--goal-gate", nargs="?", const="radius", metavar="HALF_SIDE", help="the reference's move_when_goal_occupied gate (DESIGN section 33): a search that did not reach its goal is flown only when somebody else is on the goal's square of this half side (default: the drone radius); not with --search beam")
     ap.add_argument("--record", type=int, default=0, metavar="R", help="flight recorder: the state before each of the last R rounds in a device ring, inside the graph")
     ap.add_argument("--rewind", metavar="SCENE:ROUND", help="fly ROUND + 1 rounds recorded (default --record 8), then that scene alone from the state before ROUND: one eager round, traced")
     ap.add_argument("--save", metavar="PATH", help="write a checkpoint (.npz) when the flight stops")
@@ -79,6 +84,10 @@ def main():
         from neptune_amd import mission
         mb = mission.MoveBack.reference(a.agents, a.moveback_timeout) if a.moveback == "ref" else mission.MoveBack(float(a.moveback), a.moveback_timeout)
         kw.update(moveback=mb)
+    gg = False
+    if a.goal_gate:
+        gg = True if a.goal_gate == "radius" else float(a.goal_gate)
+        kw.update(goal_gate=gg)
     if a.stagger > 0:
         kw.update(replan_every=1, periods=a.stagger, phases=np.tile(np.arange(a.agents) % a.stagger, (a.scenes, 1)))
 
@@ -152,6 +161,9 @@ def main():
     print("total over %d scenes x %d agents, %d rounds: %s" % (a.scenes, a.agents, n, json.dumps(tot)))
     if a.moveback:
         print("move-back (radius %.2f m, timeout %.1f s): %d slots on their way back at the end" % (mb.radius, mb.timeout, sum(r["way_back"] for r in rep)))
+    if a.goal_gate:
+        print("goal gate (half side %s): %d slot-rounds examined, %d let through (goal taken), %d turned down (counted in fe_no_solution)"
+              % ("drone radius" if gg is True else "%.2f m" % gg, sum(r["gate_examined"] for r in rep), sum(r["goal_taken"] for r in rep), sum(r["gated"] for r in rep)))
     if a.missions:
         ms = [r["mission"] for r in rep]
         ended = sum(m["legs_reached"] + m["legs_timed_out"] for m in ms)
@@ -174,7 +186,7 @@ def main():
     if a.host:
         sc = scenes[0]
         _, dev1, n1 = fly([sc], a.rounds)
-        ref = FleetLoop(sc["par"], sc["statics"], sc["starts"], scene.reachable_goals(sc), beam_width=a.beam, audit=a.audit, tethers=a.tethers, check=not a.no_check, search=a.search, max_pops=a.max_pops, moveback=mb)
+        ref = FleetLoop(sc["par"], sc["statics"], sc["starts"], scene.reachable_goals(sc), beam_width=a.beam, audit=a.audit, tethers=a.tethers, check=not a.no_check, search=a.search, max_pops=a.max_pops, moveback=mb, goal_gate=gg)
         ref.round(); ref.round()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
