@@ -44,6 +44,8 @@ extern "C" {
 #define NEP_RELAXED 1       /* first failed, relaxed re-solve succeeded   -> optimize()==true  */
 #define NEP_FAILED 2        /* both failed: output == initial guess       -> optimize()==false */
 #define NEP_SKIPPED 3       /* batched handle: slot not in the active set this round — not solved (nep_batch_set_active) */
+#define NEP_GUESS 4         /* batched handle: both solves failed and nep_batch_guess_fallback published the front end's guess —
+                               what the reference flies after optimize()==false (neptune.cpp:1519-1527).  No other call writes it */
 
 /* error codes (< 0) */
 #define NEP_E_ARG (-1)
@@ -106,7 +108,7 @@ typedef struct nep_ent_view {
 } nep_ent_view;
 
 typedef struct nep_stats {
-  int32_t status;                 /* NEP_OK / NEP_RELAXED / NEP_FAILED */
+  int32_t status;                 /* NEP_OK / NEP_RELAXED / NEP_FAILED (batched: NEP_SKIPPED, NEP_GUESS) */
   int32_t iters;                  /* interior-point iterations of the accepted solve            */
   int32_t iters_first;            /* iterations spent in the first (failed or accepted) solve   */
   int32_t n_lines;                /* separating lines that produced constraint rows             */
@@ -280,8 +282,11 @@ int nep_batch_set_scene_statics(nep_batch_t* h, int32_t scene, int32_t n_static,
  *   d_commit    : device or NULL, [n_scenes][n_local] nep_traj_rec: the new trajectory as the
  *                 record the agent would publish (neptune_ros.cpp:434-480)         (out)
  * A replan that fails (status NEP_FAILED: both solves infeasible, or a guess with K < 1 or K > num_pol — a
- * front-end miss — which is never solved) publishes nothing, as in the reference (neptune_ros.cpp:651-663): its
- * d_commit slot receives the agent's PREVIOUS record (from d_committed, or from the records nep_batch_frontend
+ * front-end miss — which is never solved) publishes nothing.  That is this library's default, not the reference's: there a
+ * failed optimize() leaves pwp_out_ = pwp_init_ (solver_gurobi_poly.cpp:856-859) and replanFull goes on to publish the guess
+ * (neptune.cpp:1519-1527: the early return is commented out) — nep_batch_guess_fallback below is that rule; only a replanFull
+ * that returned false (a front-end miss, a failed safety check) keeps the committed plan (neptune_ros.cpp:651-663).  The
+ * d_commit slot of a failed replan receives the agent's PREVIOUS record (from d_committed, or from the records nep_batch_frontend
  * built this round's hulls from); when neither is known (nep_batch_replan_hulls) the slot is left exactly as the
  * caller passed it, so hand in the buffer that still holds the previous round's records.  d_solution of such a
  * slot: status NEP_FAILED, coefficients = the guess (all zero and K = 0 for an unusable guess).
@@ -291,6 +296,45 @@ int nep_batch_set_scene_statics(nep_batch_t* h, int32_t scene, int32_t n_static,
 int nep_batch_replan(nep_batch_t* h, const nep_traj_rec* d_committed, const nep_guess* d_guess,
                      const void* d_ent, nep_solution* d_solution, double* d_states,
                      nep_traj_rec* d_commit, void* stream);
+/* The reference's degrade-to-initial-guess rule for the batched path, optional and stateless.  When both solves fail,
+ * PolySolverGurobi::optimize leaves pwp_out_ = pwp_init_ and returns false (solver_gurobi_poly.cpp:856-859); Neptune::replanFull does
+ * not look at opt_success_ (neptune.cpp:1519-1527, the early return is commented out): generatePwpOut samples the guess,
+ * safetyCheckAfterReplan judges it (:1644) and it is spliced, composed and published (:1661-1699) — a vehicle whose QP fails
+ * flies the path its search found.  A NEP_FAILED slot of nep_batch_replan already holds all of that but the record: d_solution
+ * carries the guess (coefficients, knot times, K, n_states) and d_states its samples.
+ *
+ * nep_batch_guess_fallback   goes after nep_batch_replan / _replan_solve / _replan_hulls on the same stream, with the buffers that
+ *   call got, and before the safety pass (tethered rounds: before the bend points are stamped into d_commit).  One wave per slot.
+ *   A slot is examined iff d_solution[slot].stats.status == NEP_FAILED (an inactive slot is NEP_SKIPPED: the mask is not read).
+ *     1 <= K <= num_pol (K = d_solution[slot].K, which the replan set to 0 for an unusable guess): PUBLISHED.  d_commit[slot]
+ *                   receives the record the replan's own writer gives a solved slot, for the guess: id, is_agent, n_bend = 1, valid,
+ *                   bbox = 2 drone_radius, pos = the guess's start, bend[0] = the agent's base, pwp.n_seg = K, every knot time
+ *                   (copied from d_solution[slot].times, so equal bit for bit) and every coefficient (zero beyond K); bend[1..]
+ *                   and pwp._pad keep what the replan left, exactly as in a solved slot.  stats.status becomes NEP_GUESS; no other
+ *                   byte of d_solution and no byte of d_states changes.  nep_batch_safety_commit / _ent then judge the record like
+ *                   any other, and nep_batch_fleet_commit goes by d_accept (NEP_FLEET_ACCEPTED: the guess's states are spliced, its
+ *                   trajectory composed; NEP_FLEET_REJECTED otherwise), as for a solved slot.
+ *     K == 0        a front-end miss, a slot nep_batch_goal_gate turned down, a guess with K > num_pol: left exactly as it is.
+ *   d_count         [n_scenes][4] or NULL: {examined, published, 0, 0} per scene, ADDED to with integer atomics; the caller owns and
+ *                   zeroes it.  A second call on the same buffers writes nothing to the published slots (they are NEP_GUESS now) and
+ *                   counts only the unpublishable ones again.
+ *   A replan that failed because a line bucket overflowed (NEP_FLAG_LINES, nep_batch_set_line_capacity) is published like any
+ *   other: the guess does not depend on the lines, and nep_batch_check still reports the capacity.  Sharded handles work (the kernel
+ *   reads no hulls; id and bend[0] are the global agent's); after nep_batch_replan_hulls it overwrites the slot the caller handed in.
+ *   What differs from the reference: once per bulk-synchronous round, every published guess judged by the safety pass's id-ordered
+ *   rule against the others' NEW records.  The per-agent handle needs no such call and there is no host form: nep_backend_optimize
+ *   already degrades to the guess (generate_pwp_out after NEP_FAILED returns it).
+ *   Asynchronous on `stream`, allocates nothing, capturable.  NEP_E_ARG: a null h, d_guess, d_solution or d_commit.  NEP_E_STATE: no
+ *   replan has been made on the handle.
+ * nep_batch_guess_fallback_tally   after nep_batch_fleet_commit (include/neptune_fleet.h), one wave per scene: d_count[scene][2] +=
+ *   the slots with status NEP_GUESS whose d_outcome is NEP_FLEET_ACCEPTED (flown), d_count[scene][3] += those with any other outcome
+ *   (turned down by the safety pass, arrived, capacity).  Called every round it keeps published == flown + not flown.  NEP_E_ARG:
+ *   a null argument.                                                                                                            */
+int nep_batch_guess_fallback(nep_batch_t* h, const nep_guess* d_guess, nep_solution* d_solution,
+                             nep_traj_rec* d_commit, int32_t* d_count /* [n_scenes][4] or NULL */, void* stream);
+int nep_batch_guess_fallback_tally(nep_batch_t* h, const nep_solution* d_solution, const int32_t* d_outcome /* [n_scenes][n_local] */,
+                                   int32_t* d_count /* [n_scenes][4] */, void* stream);
+
 /* The same round as two enqueues, so that a host with several scene groups in flight (one handle per group) can put the
  * halves on different streams: nep_batch_replan_lines = interval hulls + separating-line LPs into the handle's scratch
  * (the chip-filling, VALU-bound half), nep_batch_replan_solve = the QPs on those lines + sampled states + commit records (a few

@@ -5,8 +5,9 @@
  * trip per agent and round.  Here the same state lives in the batched handle (include/neptune_backend.h: nep_batch_t), per
  * (scene, agent) slot, and three asynchronous calls move it — so a faithful round
  *
- *   nep_batch_fleet_select [-> nep_batch_fleet_moveback] -> nep_batch_frontend [-> nep_batch_goal_gate] -> nep_batch_replan ->
- *     nep_batch_safety_commit -> nep_batch_fleet_commit [-> nep_batch_audit] [-> nep_batch_fleet_mission] -> nep_batch_fleet_tick
+ *   nep_batch_fleet_select [-> nep_batch_fleet_moveback] -> nep_batch_frontend [-> nep_batch_goal_gate] -> nep_batch_replan
+ *     [-> nep_batch_guess_fallback] -> nep_batch_safety_commit -> nep_batch_fleet_commit [-> nep_batch_guess_fallback_tally]
+ *     [-> nep_batch_audit] [-> nep_batch_fleet_mission] -> nep_batch_fleet_tick
  *
  * is a fixed launch sequence on fixed buffers: one HIP graph for all scenes, no host synchronisation in it.  The arithmetic is the
  * host library's own (neptune_amd/csrc/plan_common.h is compiled into both), so the plans, tracked states and trajectories on the
@@ -65,7 +66,8 @@ extern "C" {
 /* outcome of a slot's round (nep_batch_fleet_commit), in the order the rules are tried */
 #define NEP_FLEET_SKIPPED 0             /* outside the active set, or arrived: the agent keeps its plan                      */
 #define NEP_FLEET_FE_NO_SOLUTION 1      /* nep_fe_result.status == NEP_FE_NO_SOLUTION or the solution's K == 0              */
-#define NEP_FLEET_QP_FAILED 2           /* nep_stats.status == NEP_FAILED                                                    */
+#define NEP_FLEET_QP_FAILED 2           /* nep_stats.status == NEP_FAILED (after nep_batch_guess_fallback, include/neptune_backend.h,
+                                           a failed replan with a usable guess is NEP_GUESS and goes by d_accept like a solved one) */
 #define NEP_FLEET_REJECTED 3            /* turned down by nep_batch_safety_commit                                           */
 #define NEP_FLEET_ACCEPTED 4            /* plan spliced, trajectory composed                                                 */
 #define NEP_FLEET_CAP 5                 /* accepted, but the plan or the trajectory would outgrow its storage: nothing changed */

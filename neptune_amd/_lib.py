@@ -16,7 +16,7 @@ EXPORTS = [
     "nep_backend_set_hulls", "nep_backend_set_hulls_no_inflation", "nep_backend_set_ent_state_vector",
     "nep_backend_optimize", "nep_backend_generate_pwp_out", "nep_backend_get_stats", "nep_inflate_static",
     "nep_separator_batch", "nep_separator_batch_rule", "nep_gjk_batch", "nep_hulls_batch", "nep_batch_create",
-    "nep_batch_destroy", "nep_batch_set_scene_statics", "nep_batch_replan", "nep_batch_replan_lines", "nep_batch_replan_solve", "nep_batch_hull_block_bytes",
+    "nep_batch_destroy", "nep_batch_set_scene_statics", "nep_batch_replan", "nep_batch_replan_lines", "nep_batch_replan_solve", "nep_batch_guess_fallback", "nep_batch_guess_fallback_tally", "nep_batch_hull_block_bytes",
     "nep_batch_set_ent_samples", "nep_batch_hulls", "nep_batch_replan_hulls", "nep_comm_unique_id",
     "nep_comm_create", "nep_comm_destroy", "nep_comm_nranks", "nep_batch_exchange_hulls",
     "nep_batch_exchange_records", "nep_batch_exchange_slots", "nep_comm_reserve", "nep_batch_ent_bytes",
@@ -195,6 +195,8 @@ def lib():
     L.nep_batch_frontend_astar.argtypes = [vp, C.POINTER(abi.nep_fe_cfg), vp, vp, vp, vp, vp]
     L.nep_batch_frontend_astar_ent.argtypes = [vp, C.POINTER(abi.nep_fe_cfg), vp, vp, vp, vp, vp, vp, vp]
     L.nep_batch_goal_gate.argtypes = [vp, d, vp, vp, vp, vp, vp, vp]
+    L.nep_batch_guess_fallback.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.nep_batch_guess_fallback_tally.argtypes = [vp, vp, vp, vp, vp]
     L.nep_batch_set_static_reps.argtypes = [vp, i, pd, pd]
     L.nep_batch_frontend_ent.argtypes = [vp, C.POINTER(abi.nep_fe_cfg), vp, vp, vp, vp, vp, vp, vp]
     L.nep_batch_safety_commit_ent.argtypes = [vp, vp, vp, vp, vp, i, d, vp, vp, vp]

@@ -16,9 +16,12 @@ NEP_STATE_DOUBLES = 12
 
 NEP_OK, NEP_RELAXED, NEP_FAILED = 0, 1, 2
 NEP_SKIPPED = 3          # nep_stats.status of a slot outside the active set (nep_batch_set_active)
+NEP_GUESS = 4            # nep_stats.status: both solves failed and nep_batch_guess_fallback published the front end's guess
 NEP_FE_SKIPPED = 4       # nep_fe_result.status of a slot outside the active set
 NEP_FE_PAD_GATED, NEP_FE_PAD_GOAL_TAKEN = 32, 64      # nep_fe_result._pad bits 5 and 6: turned down / let through by nep_batch_goal_gate
 GOAL_GATE_COUNTS = ("examined", "goal_taken", "gated", "unused")      # nep_batch_goal_gate's d_count [n_scenes][4]
+# nep_batch_guess_fallback's ([0], [1]) and nep_batch_guess_fallback_tally's ([2], [3]) d_count [n_scenes][4]
+GUESS_FALLBACK_COUNTS = ("qp_failed_seen", "guess_published", "guess_flown", "guess_not_flown")
 
 
 class nep_pwp(C.Structure):

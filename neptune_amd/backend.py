@@ -273,6 +273,22 @@ class BatchBackend:
                                      self.d_solution.data_ptr(), self.d_states.data_ptr(),
                                      self.d_commit.data_ptr() if want_commit else None, st.cuda_stream))
 
+    def guess_fallback(self, d_guess, d_count=None, stream=None):
+        """the reference's degrade-to-initial-guess rule (nep_batch_guess_fallback), right behind replan / replan_solve / replan_hulls
+        on this handle's d_solution and d_commit: a NEP_FAILED slot with a usable guess (1 <= K <= num_pol) gets the guess's record
+        in d_commit and status NEP_GUESS, so the safety pass judges it and fleet_commit flies it when accepted — what
+        Neptune::replanFull does after a failed optimize (neptune.cpp:1519-1527).  d_count: int32 [n_scenes][4]
+        (abi.GUESS_FALLBACK_COUNTS), [0] and [1] added to"""
+        st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        check(lib().nep_batch_guess_fallback(self._h, d_guess.data_ptr(), self.d_solution.data_ptr(), self.d_commit.data_ptr(),
+                                             d_count.data_ptr() if d_count is not None else None, st.cuda_stream))
+
+    def guess_fallback_tally(self, d_outcome, d_count, stream=None):
+        """after fleet_commit (nep_batch_guess_fallback_tally): d_count[scene][2] += the NEP_GUESS slots fleet_commit accepted,
+        [3] += the others"""
+        st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        check(lib().nep_batch_guess_fallback_tally(self._h, self.d_solution.data_ptr(), d_outcome.data_ptr(), d_count.data_ptr(), st.cuda_stream))
+
     def replan_lines(self, d_committed, d_guess, d_ent=None, stream=None):
         """first half of replan(): interval hulls + separating lines into the handle's scratch (nep_batch_replan_lines)"""
         st = stream if stream is not None else self.torch.cuda.current_stream(self.device)

@@ -1011,6 +1011,7 @@ struct nep_batch {
   int slots = 0;
   const nep_traj_rec* fe_committed = nullptr;   // the records nep_batch_frontend built this round's hulls from
   int ent_ns = 3;                               // num_sample_per_interval the hull blocks reserve room for (nep_batch_set_ent_samples; yaml: 3)
+  bool replanned = false;                       // a replan with a QP half has been enqueued (nep_batch_guess_fallback needs one before it)
   // nep_batch_fleet_* (include/neptune_fleet.h): the committed plans of every slot, allocated by nep_batch_fleet_init
   struct Fleet {
     bool ready = false, timers = false; int cap = 0; nep_fleet_cfg cfg{};
@@ -1050,6 +1051,7 @@ int replan_phases(nep_batch* h, int phases, const nep_traj_rec* d_committed, con
   // d_committed == NULL (nep_batch_replan alone): the interval hulls of this round are already in the handle's scratch, made by
   // nep_batch_frontend, whose records are this round's previous ones
   ProblemSet ps = round_set(h, d_guess, d_solution, d_states, d_commit, d_committed ? d_committed : h->fe_committed, d_ent);
+  if (phases & 2) h->replanned = true;
   return h->eng.run(d_committed, h->cfg.num_agents, ps, (hipStream_t)stream, phases);
 }
 }  // namespace
@@ -1188,6 +1190,7 @@ int nep_batch_replan_hulls(nep_batch_t* h, const void* d_blocks, int32_t n_block
   if (!h || !d_blocks || !d_guess || !d_solution) return fail(NEP_E_ARG, "null argument");
   ProblemSet ps = round_set(h, d_guess, d_solution, d_states, d_commit, nullptr, d_ent);
   if (int e = use_blocks(ps, h, d_blocks, n_blocks)) return e;
+  h->replanned = true;
   return h->eng.run(nullptr, 0, ps, (hipStream_t)stream);
 }
 
@@ -1290,6 +1293,22 @@ int nep_batch_goal_gate(nep_batch_t* h, double half_side, const nep_fe_start* d_
   if (h->eng.sp.n_hull != h->cfg.num_agents) return fail(NEP_E_STATE, "nep_batch_goal_gate needs the batched (all-agent) hull layout");
   if (!h->fe_committed) return fail(NEP_E_STATE, "nep_batch_goal_gate: no front-end call has left this round's hulls in the handle's scratch");
   launch_goal_gate(h->slots, h->eng.sp, round_set(h), half_side, d_start, d_guess, d_result, d_case, d_count, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ---- the reference's degrade-to-initial-guess rule (guess_fallback_kernels.hip): behind nep_batch_replan / _solve / _hulls; the tally
+// behind nep_batch_fleet_commit ----
+int nep_batch_guess_fallback(nep_batch_t* h, const nep_guess* d_guess, nep_solution* d_solution, nep_traj_rec* d_commit, int32_t* d_count, void* stream) {
+  if (!h || !d_guess || !d_solution || !d_commit) return fail(NEP_E_ARG, "null argument");
+  if (!h->replanned) return fail(NEP_E_STATE, "nep_batch_guess_fallback: no replan has been made on the handle");
+  launch_guess_fallback(h->slots, h->eng.sp, h->eng.d_pb.p, d_guess, d_solution, d_commit, d_count, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+int nep_batch_guess_fallback_tally(nep_batch_t* h, const nep_solution* d_solution, const int32_t* d_outcome, int32_t* d_count, void* stream) {
+  if (!h || !d_solution || !d_outcome || !d_count) return fail(NEP_E_ARG, "null argument");
+  launch_guess_fallback_tally(h->cfg.n_scenes, h->cfg.n_local, d_solution, d_outcome, d_count, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -257,6 +257,12 @@ void launch_frontend_astar(int n_slots, const SceneParams& sp, const ProblemSet&
 // [slots][NEP_MAX_POL][N] and count [n_scenes][4] may be null
 void launch_goal_gate(int n_slots, const SceneParams& sp, const ProblemSet& ps, double half_side, const nep_fe_start* starts, nep_guess* guess,
                       nep_fe_result* res, int* case_out, int* count, hipStream_t st);
+// nep_batch_guess_fallback / _tally (guess_fallback_kernels.hip): one wave per slot behind the replan — a NEP_FAILED slot with a usable
+// guess gets the guess's record in `commit` and status NEP_GUESS; one wave per scene after nep_batch_fleet_commit.  count [n_scenes][4]
+// (null allowed in the first)
+void launch_guess_fallback(int n_slots, const SceneParams& sp, const double* pb, const nep_guess* guess, nep_solution* sol, nep_traj_rec* commit,
+                           int* count, hipStream_t st);
+void launch_guess_fallback_tally(int n_scenes, int n_local, const nep_solution* sol, const int* outcome, int* count, hipStream_t st);
 void launch_ent_sample(const nep_traj_rec* recs, int n_scenes, int N, const double* ts0, long ts_scene_stride, int num_pol, int ns, double T_span,
                        double* sampled, int* present, hipStream_t st, int* zero_this = nullptr);
 // nep_batch_audit (audit_kernels.hip): the minima of one (scene, run of ticks, agent), ticks as indices of the call

@@ -92,17 +92,30 @@ def check_goal_gate(goal_gate, search, drone_radius):
     return r
 
 
-def plan_round(be, fe, d_rec, d_start, d_guess, d_res, d_final, d_acc, tethers=False, d_case=None, d_ent=None, ent_samples=3, astar=False, gate=None):
+def check_fly_guess(fly_guess):
+    """the reference's degrade-to-initial-guess rule (BatchBackend.guess_fallback): a boolean, nothing else (a
+    count, a string or None is a mistake worth hearing about before a flight) -> bool"""
+    if not isinstance(fly_guess, (bool, np.bool_)):
+        raise ValueError("fly_guess must be True or False, not %r" % (fly_guess,))
+    return bool(fly_guess)
+
+
+def plan_round(be, fe, d_rec, d_start, d_guess, d_res, d_final, d_acc, tethers=False, d_case=None, d_ent=None, ent_samples=3, astar=False, gate=None,
+               fallback=None):
     """the plan half of a round: front end -> lines + QP -> safety pass, from the records d_rec and the starts d_start into d_final
     and d_acc.  With d_case the entangle check is on (d_ent: every tether's state at A): the QP gets the entangle rows and the safety
     pass re-checks.  Tethered rounds stamp the published bend points into the commit records before the safety pass.  astar: the
     best-first search in place of the beam (check_search) — with d_case that is search="astar_ent", frontend_astar_ent.
-    gate: (half side, d_count or None) — the move_when_goal_occupied gate right behind the front end (check_goal_gate)."""
+    gate: (half side, d_count or None) — the move_when_goal_occupied gate right behind the front end (check_goal_gate).
+    fallback: a d_count (int32 [n_scenes][4], abi.GUESS_FALLBACK_COUNTS) — the degrade-to-initial-guess rule right behind the replan
+    (BatchBackend.guess_fallback, before the bend points are stamped); None: a failed replan publishes nothing."""
     if d_case is not None:
         (be.frontend_astar_ent if astar else be.frontend_ent)(fe, d_rec, d_start, d_guess, d_res, d_case, d_ent_init=d_ent)
         if gate is not None:
             be.goal_gate(d_start, d_guess, d_res, gate[0], d_case=d_case, d_count=gate[1])
         be.replan(None, d_guess, d_ent=d_case)
+        if fallback is not None:
+            be.guess_fallback(d_guess, fallback)
         stamp_bends(be.d_commit, d_rec)
         be.safety_commit_ent(d_rec, be.d_commit, d_guess, d_final, d_acc, d_ent_init=d_ent, ent_samples=ent_samples)
     else:
@@ -110,6 +123,8 @@ def plan_round(be, fe, d_rec, d_start, d_guess, d_res, d_final, d_acc, tethers=F
         if gate is not None:
             be.goal_gate(d_start, d_guess, d_res, gate[0], d_count=gate[1])
         be.replan(None, d_guess)
+        if fallback is not None:
+            be.guess_fallback(d_guess, fallback)
         if tethers:
             stamp_bends(be.d_commit, d_rec)
         be.safety_commit(d_rec, be.d_commit, d_guess, d_final, d_acc)
@@ -142,11 +157,16 @@ class _Audited:
 
 class FleetLoop(_Audited):
     def __init__(self, par, statics, starts, goals, beam_width=32, delta_t_states=6, replan_every=5, device=None, skip_arrived=False, audit=False,
-                 tethers=False, check=True, ent_samples=3, search="beam", max_pops=300, moveback=None, goal_gate=False):
+                 tethers=False, check=True, ent_samples=3, search="beam", max_pops=300, moveback=None, goal_gate=False, fly_guess=False):
         import torch
         from . import mission
         self.torch = torch
         self.tethers, self.check, self.ent_samples = tethers, check, ent_samples
+        # fly_guess: the reference's rule for a replan whose two QP solves failed (True is the reference) — the
+        # front end's guess is judged by the safety pass and flown when accepted (BatchBackend.guess_fallback; Neptune::replanFull
+        # does not look at opt_success_, neptune.cpp:1519-1527).  False, the default, is this library's own rule: such an agent keeps
+        # its committed plan.  stats then gets abi.GUESS_FALLBACK_COUNTS, and qp_failed counts only the failures with nothing to publish
+        self.fly_guess = check_fly_guess(fly_guess)
         # goal_gate: the reference's move_when_goal_occupied — a plan that does not reach the goal is flown only
         # when somebody else is on the goal; a gated replan counts as fe_no_solution (stats: gate_examined, goal_taken, gated)
         self.goal_gate = check_goal_gate(goal_gate, search, par.drone_radius)
@@ -204,6 +224,10 @@ class FleetLoop(_Audited):
         if self.goal_gate is not None:
             self._d_gate_count = torch.zeros((1, 4), dtype=torch.int32, device=self.be.device)
             self.stats.update(gate_examined=0, goal_taken=0, gated=0)
+        self._d_guess_count = None
+        if self.fly_guess:
+            self._d_guess_count = torch.zeros((1, 4), dtype=torch.int32, device=self.be.device)
+            self.stats.update({k: 0 for k in abi.GUESS_FALLBACK_COUNTS})
         self._static_pts = [np.asarray(s, dtype=np.float64) for s in scene_raw(statics, par)]
         # audit: every round also audits, on the device, the records it uploads anyway over the replan_every ticks about to be flown
         # (nep_batch_audit; those ticks lie before the round's point A, so the uploaded records describe them); _tick keeps its host log
@@ -286,16 +310,21 @@ class FleetLoop(_Audited):
             d_ent_a = be.to_device(self.ent_a)
             d_case = torch.zeros(N * abi.NEP_MAX_POL * N, dtype=torch.int32, device=be.device)
         plan_round(be, self.fe, d_com, d_start, d_guess, d_fres, d_final, d_acc, self.tethers, d_case, d_ent_a, self.ent_samples, self.astar,
-                   gate=(self.goal_gate, self._d_gate_count) if self.goal_gate is not None else None)
+                   gate=(self.goal_gate, self._d_gate_count) if self.goal_gate is not None else None, fallback=self._d_guess_count)
         sol = be.solutions(); states = be.states(); fres = d_fres.cpu().numpy().view(abi.FE_RESULT_DTYPE)
         self.last_fres = fres
         if self._d_gate_count is not None:
             gc = self._d_gate_count.cpu().numpy()[0]
             self.stats.update(gate_examined=int(gc[0]), goal_taken=int(gc[1]), gated=int(gc[2]))
+        if self._d_guess_count is not None:
+            fc = self._d_guess_count.cpu().numpy()[0]
+            self.stats.update(qp_failed_seen=int(fc[0]), guess_published=int(fc[1]))
         acc = d_acc.cpu().numpy()
         self.stats["rounds"] += 1
         for a in range(N):
             if self.done[a]:
+                if int(sol[a]["stats"]["status"]) == abi.NEP_GUESS:      # (an arrived agent's results are dropped, a published guess included)
+                    self.stats["guess_not_flown"] += 1
                 if self.skip_arrived and self.trace is not None:
                     self.trace.append((t_now, a, "skipped", int(sol[a]["K"]), int(fres[a]["status"]), int(sol[a]["stats"]["status"])))
                 continue
@@ -307,8 +336,13 @@ class FleetLoop(_Audited):
             if self.trace is not None:
                 self.trace.append((t_now, a, outcome, K, int(fres[a]["status"]), status))
             self.stats[outcome] += 1
+            if status == abi.NEP_GUESS:         # (fly_guess: a failed QP's guess went through the safety pass like a solution)
+                self.stats["guess_flown" if outcome == "accepted" else "guess_not_flown"] += 1
             if outcome != "accepted":
-                continue                        # replanFull() false: the agent keeps its plan (neptune.cpp:1519-1545, neptune_ros.cpp:651-663)
+                # the agent keeps its plan.  For fe_no_solution and rejected_by_safety that is the reference's replanFull() == false
+                # (neptune_ros.cpp:651-663); for qp_failed it is this library's default and NOT the reference, which flies the
+                # guess after a failed optimize (neptune.cpp:1519-1527: the early return is commented out) — fly_guess=True
+                continue
             self.stats["qp_relaxed"] += status == abi.NEP_RELAXED
             ns = int(sol[a]["n_states"])
             self.plans[a].splice(int(k_end[a]), states[a, :ns])
@@ -399,7 +433,7 @@ class DeviceFleetLoop(_Audited):
     """FleetLoop's rounds for S scenes at once with nothing on the host (include/neptune_fleet.h): the plan deques, point A, the
     splice, the composition and the control ticks of every (scene, agent) live in the batched handle, and a round
 
-        fleet_select -> [fleet_moveback] -> frontend -> replan -> safety_commit -> fleet_commit -> [audit] -> fleet_tick
+        fleet_select -> [fleet_moveback] -> frontend -> replan [-> guess_fallback] -> safety_commit -> fleet_commit -> [audit] -> fleet_tick
 
     is one captured graph (graph=True: captured after the first eager round, replayed afterwards).  `scenes` are make_scene
     dicts with the same agent and obstacle counts, each with its own statics; `goals` ([S][N][3], default: every scene's
@@ -454,18 +488,28 @@ class DeviceFleetLoop(_Audited):
     at its base); otherwise the slot is turned down and keeps flying its committed plan.  Not with search="beam" (ValueError).
     report() adds gate_examined, goal_taken and gated per scene, and fe_no_solution now INCLUDES the gated replans (they reach
     fleet_commit as NEP_FE_NO_SOLUTION).  The gate keeps no state: snapshots are what they were; the counts belong to the loop
-    (d_gate_count) and travel in a checkpoint; rewind twins and resume carry the option (a file from before it resumes without)."""
+    (d_gate_count) and travel in a checkpoint; rewind twins and resume carry the option (a file from before it resumes without).
+
+    fly_guess=True flies the reference's rule for a replan whose two QP solves failed — True is the reference,
+    False, the default, this library's own rule (such a slot keeps its committed plan).  BatchBackend.guess_fallback goes right
+    behind the replan: a NEP_FAILED slot with a usable guess gets the guess's record and status NEP_GUESS, the safety pass judges
+    it and fleet_commit splices the guess's states and composes its trajectory when it is accepted; guess_fallback_tally goes behind
+    fleet_commit.  report() adds qp_failed_seen, guess_published, guess_flown and guess_not_flown per scene (slot-rounds), and
+    qp_failed then counts only the failures that had nothing to publish.  The rule keeps no state: snapshots are what they were; the
+    counts belong to the loop (d_guess_count) and travel in a checkpoint; rewind twins and resume carry the option (a file from
+    before it resumes without)."""
 
     # the options a restored flight must share with the flight the snapshot was taken from
-    _MUST_MATCH = ("beam_width", "delta_t_states", "replan_every", "audit", "ring_cap", "tethers", "check", "ent_samples", "ent_cap", "moveback", "goal_gate")
+    _MUST_MATCH = ("beam_width", "delta_t_states", "replan_every", "audit", "ring_cap", "tethers", "check", "ent_samples", "ent_cap", "moveback", "goal_gate", "fly_guess")
 
     def __init__(self, scenes, beam_width=32, delta_t_states=6, replan_every=5, periods=None, phases=None, audit=False, graph=True,
                  goals=None, device=None, ring_cap=0, trace=False, tethers=False, check=True, ent_samples=3, missions=None, ent_cap=None,
-                 ent_lists0=None, recorder=None, search="beam", max_pops=300, moveback=None, goal_gate=False):
+                 ent_lists0=None, recorder=None, search="beam", max_pops=300, moveback=None, goal_gate=False, fly_guess=False):
         import torch
         from . import mission as mission_mod
         self.torch = torch
         self.scenes = scenes
+        self.fly_guess = check_fly_guess(fly_guess)
         self.goal_gate = check_goal_gate(goal_gate, search, scenes[0]["par"].drone_radius)      # the half side, or None
         if isinstance(moveback, dict):      # (a checkpoint's options carry it as plain data)
             moveback = mission_mod.MoveBack(**moveback)
@@ -473,7 +517,7 @@ class DeviceFleetLoop(_Audited):
         self.astar = check_search(search, max_pops, tethers)
         self._opts = dict(beam_width=beam_width, delta_t_states=delta_t_states, replan_every=replan_every, audit=audit, ring_cap=ring_cap,
                           tethers=tethers, check=check, ent_samples=ent_samples, ent_cap=ent_cap, missions=missions, goals=goals,
-                          search=search, max_pops=max_pops, moveback=moveback, goal_gate=self.goal_gate)
+                          search=search, max_pops=max_pops, moveback=moveback, goal_gate=self.goal_gate, fly_guess=self.fly_guess)
         S = self.S = len(scenes)
         p = self.p = scenes[0]["par"]
         self.tethers, self.check, self.ent_samples = tethers, check, ent_samples
@@ -539,6 +583,7 @@ class DeviceFleetLoop(_Audited):
             self.d_flags = torch.zeros(n, dtype=torch.int32, device=dev)
             self.d_case = torch.zeros(n * abi.NEP_MAX_POL * N, dtype=torch.int32, device=dev)
         self.d_gate_count = torch.zeros((S, 4), dtype=torch.int32, device=dev) if self.goal_gate is not None else None      # abi.GOAL_GATE_COUNTS
+        self.d_guess_count = torch.zeros((S, 4), dtype=torch.int32, device=dev) if self.fly_guess else None      # abi.GUESS_FALLBACK_COUNTS
         self.missions = missions
         if missions is not None:
             from . import mission
@@ -575,8 +620,10 @@ class DeviceFleetLoop(_Audited):
                 self.after_select(self)
         ent = (self.d_case, self.d_ent_a) if self.tethers and self.check else (None, None)
         plan_round(be, self.fe, self.d_rec, self.d_start, self.d_guess, self.d_res, self.d_final, self.d_acc, self.tethers, *ent, self.ent_samples, self.astar,
-                   gate=(self.goal_gate, self.d_gate_count) if self.goal_gate is not None else None)
+                   gate=(self.goal_gate, self.d_gate_count) if self.goal_gate is not None else None, fallback=self.d_guess_count)
         be.fleet_commit(self.d_res, self.d_acc, self.d_outcome)
+        if self.d_guess_count is not None:
+            be.guess_fallback_tally(self.d_outcome, self.d_guess_count)
         if self.after_commit is not None:
             self.after_commit(self)
         if self.d_audit is not None:
@@ -614,7 +661,8 @@ class DeviceFleetLoop(_Audited):
     def report(self):
         """per scene FleetLoop.stats' keys (min_pair_dist / min_static_dist come from the audit when it is on), plus `cap` and the
         audit's summary.  With goal_gate: gate_examined, goal_taken (let through) and gated (turned down) — slot-rounds; fe_no_solution
-        includes the gated ones"""
+        includes the gated ones.  With fly_guess: abi.GUESS_FALLBACK_COUNTS — slot-rounds whose QP failed, whose guess was published,
+        flown (accepted) and not flown; qp_failed is then what had nothing to publish"""
         be = self.be
         try:
             be.check()
@@ -632,6 +680,7 @@ class DeviceFleetLoop(_Audited):
             lists, held = be.fleet_ent_lists(self.ent_cap)
             held = held.reshape(self.S, self.N)
         gate = self.d_gate_count.cpu().numpy() if self.d_gate_count is not None else None
+        gcount = self.d_guess_count.cpu().numpy() if self.d_guess_count is not None else None
         msum, goals_now = None, self.goals
         if self.missions is not None:
             from . import mission
@@ -649,6 +698,8 @@ class DeviceFleetLoop(_Audited):
                 d["way_back"] = int(((flags[s] & abi.NEP_FLEET_FLAG_WAY_BACK) != 0).sum())
             if gate is not None:       # slot-rounds the gate examined, let through (somebody on the goal) and turned down
                 d["gate_examined"], d["goal_taken"], d["gated"] = int(gate[s, 0]), int(gate[s, 1]), int(gate[s, 2])
+            if gcount is not None:     # slot-rounds whose QP failed, whose guess was published, flown and not flown
+                d.update({k: int(gcount[s, i]) for i, k in enumerate(abi.GUESS_FALLBACK_COUNTS)})
             if lists is not None:      # slot-rounds held at point A and the longest list now
                 d["held"] = int(held[s].sum()); d["max_list"] = int(lists.n_alpha.reshape(self.S, self.N)[s].max())
                 d["bend_full"] = int((lists.n_bend.reshape(self.S, self.N)[s] >= abi.NEP_MAX_BEND - 1).sum())      # (tethers at the bend-point limit)
@@ -723,6 +774,8 @@ class DeviceFleetLoop(_Audited):
             data["audit"] = self.d_audit.cpu().numpy()
         if self.d_gate_count is not None:
             data["gate_count"] = self.d_gate_count.cpu().numpy()
+        if self.d_guess_count is not None:
+            data["guess_count"] = self.d_guess_count.cpu().numpy()
         with open(path, "wb") as f:
             np.savez(f, **data)
 
@@ -737,8 +790,12 @@ class DeviceFleetLoop(_Audited):
             blob, rounds, opts = z["blob"], int(z["rounds"]), json.loads(str(z["options"]))
             aud = z["audit"] if "audit" in z.files else None
             gcnt = z["gate_count"] if "gate_count" in z.files else None
+            fcnt = z["guess_count"] if "guess_count" in z.files else None
         opts.setdefault("moveback", None)      # (a file from before the option flew without it)
         opts.setdefault("goal_gate", None)     # (likewise)
+        opts.setdefault("fly_guess", False)    # (likewise)
+        if "fly_guess" in kw:
+            kw = dict(kw, fly_guess=check_fly_guess(kw["fly_guess"]))
         if "goal_gate" in kw:                  # (False, True or a half side -> what the file holds: the half side, or None)
             kw = dict(kw, goal_gate=check_goal_gate(kw["goal_gate"], opts.get("search", "beam") if kw["goal_gate"] else "astar", scenes[0]["par"].drone_radius))
         if isinstance(kw.get("moveback"), mission.MoveBack):
@@ -766,6 +823,8 @@ class DeviceFleetLoop(_Audited):
                 lp.d_audit.copy_(lp.torch.from_numpy(aud))
             if gcnt is not None and lp.d_gate_count is not None:
                 lp.d_gate_count.copy_(lp.torch.from_numpy(gcnt))
+            if fcnt is not None and lp.d_guess_count is not None:
+                lp.d_guess_count.copy_(lp.torch.from_numpy(fcnt))
         except Exception:
             lp.close()
             raise

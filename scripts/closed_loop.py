@@ -7,7 +7,9 @@ benchmark driver logs a run (scripts/benchmark_mtlp.py:215-223: elapsed time, di
 nep_ent_track_step per control tick, nep_ent_predict_a per round).  --search astar: the reference's best-first search, --max-pops
 pops per search, in place of the beam (not with --tethers).  --moveback [RADIUS|ref] [--moveback-timeout S]: every agent first plans
 towards its own base (the reference's use_moveback_strategy).  --goal-gate [HALF_SIDE]: a plan that does not reach its
-goal is flown only when somebody else is on the goal (the reference's move_when_goal_occupied; not with the beam)."""
+goal is flown only when somebody else is on the goal (the reference's move_when_goal_occupied; not with the beam).
+--fly-guess: a replan whose two QP solves failed flies the front end's guess when the safety pass accepts it (the reference's rule,
+DESIGN section 34; off by default: such an agent keeps its committed plan)."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from neptune_amd import scene
@@ -25,6 +27,7 @@ ap.add_argument("--max-pops", type=int, default=300, help="with --search astar /
 ap.add_argument("--moveback", nargs="?", const="ref", metavar="RADIUS|ref", help="the reference's move-back strategy (DESIGN section 32): an agent with a new goal first plans towards its own base, until it is within RADIUS m of it (ref, the default: 6.33 - (agents - 4) * 0.33) or --moveback-timeout has passed")
 ap.add_argument("--moveback-timeout", type=float, default=10.0, metavar="S", help="with --moveback: seconds of simulated time after which the goal is released anyway")
 ap.add_argument("--goal-gate", nargs="?", const="radius", metavar="HALF_SIDE", help="the reference's move_when_goal_occupied gate (DESIGN section 33): a search that did not reach its goal is flown only when somebody else is on the goal's square of this half side (default: the drone radius); not with --search beam")
+ap.add_argument("--fly-guess", action="store_true", help="the reference's rule for a replan whose two QP solves failed (DESIGN section 34): the front end's guess is judged by the safety pass and flown when accepted; off (the default): the agent keeps its committed plan")
 a = ap.parse_args()
 gg = False if not a.goal_gate else True if a.goal_gate == "radius" else float(a.goal_gate)
 mb = None
@@ -34,7 +37,7 @@ if a.moveback:
 sc = scene.make_scene(a.agents, a.obstacles, seed=a.seed)
 t0 = time.perf_counter()
 loop = FleetLoop(sc["par"], sc["statics"], sc["starts"], scene.reachable_goals(sc), beam_width=a.beam, skip_arrived=a.skip_arrived, audit=a.audit, tethers=a.tethers,
-                 check=not a.no_check, search=a.search, max_pops=a.max_pops, moveback=mb, goal_gate=gg)
+                 check=not a.no_check, search=a.search, max_pops=a.max_pops, moveback=mb, goal_gate=gg, fly_guess=a.fly_guess)
 if a.audit:
     loop.trace = []
 st = loop.run(a.max_rounds)

@@ -23,6 +23,13 @@ new goal plans towards its own base first, as the reference's use_moveback_strat
 is flown only when another agent's committed trajectory ends on the square goal +- HALF_SIDE (default: the drone radius), as the
 reference's move_when_goal_occupied does.  Only with --search astar / astar_ent.
 
+--fly-guess: guess_fallback joins the round right behind the replan and guess_fallback_tally behind fleet_commit:
+a replan whose two QP solves failed publishes the front end's guess, which the safety pass judges and fleet_commit flies when it is
+accepted, as the reference's replanFull does.  Off by default: such a slot keeps its committed plan.
+
+--cross: every agent's goal is its start mirrored through the middle of the world, so the whole fleet crosses the middle at once —
+where failed QPs are common.
+
 --stagger P: every agent replans every P-th round, agent a in the rounds with (round - a) mod P == 0, and a round flies one control
 tick (FleetLoop's cadence at P = 5 with the agents' timers spread over the ticks).  --host flies scene 0 with FleetLoop as well and
 prints its wall time per round next to the device loop's (one scene each)."""
@@ -58,6 +65,8 @@ def main():
     ap.add_argument("--moveback", nargs="?", const="ref", metavar="RADIUS|ref", help="the reference's move-back strategy (DESIGN section 32): an agent with a new goal first plans towards its own base, until it is within RADIUS m of it (ref, the default: 6.33 - (agents - 4) * 0.33) or --moveback-timeout has passed")
     ap.add_argument("--moveback-timeout", type=float, default=10.0, metavar="S", help="with --moveback: seconds of simulated time after which the goal is released anyway")
     ap.add_argument("--goal-gate", nargs="?", const="radius", metavar="HALF_SIDE", help="the reference's move_when_goal_occupied gate (DESIGN section 33): a search that did not reach its goal is flown only when somebody else is on the goal's square of this half side (default: the drone radius); not with --search beam")
+    ap.add_argument("--fly-guess", action="store_true", help="the reference's rule for a replan whose two QP solves failed (DESIGN section 34): the front end's guess is judged by the safety pass and flown when accepted; off (the default): the slot keeps its committed plan")
+    ap.add_argument("--cross", action="store_true", help="every agent's goal is its start mirrored through the middle of the world (scene.crossing_scene's goals): the whole fleet crosses the middle at once; not with --missions")
     ap.add_argument("--record", type=int, default=0, metavar="R", help="flight recorder: the state before each of the last R rounds in a device ring, inside the graph")
     ap.add_argument("--rewind", metavar="SCENE:ROUND", help="fly ROUND + 1 rounds recorded (default --record 8), then that scene alone from the state before ROUND: one eager round, traced")
     ap.add_argument("--save", metavar="PATH", help="write a checkpoint (.npz) when the flight stops")
@@ -88,6 +97,12 @@ def main():
     if a.goal_gate:
         gg = True if a.goal_gate == "radius" else float(a.goal_gate)
         kw.update(goal_gate=gg)
+    if a.fly_guess:
+        kw.update(fly_guess=True)
+    if a.cross:
+        if a.missions:
+            ap.error("--cross sets every agent's one goal: not with --missions")
+        kw.update(goals=[np.array([[-s[0], -s[1], sc["par"].goal_height] for s in sc["starts"]], dtype=np.float64) for sc in scenes])
     if a.stagger > 0:
         kw.update(replan_every=1, periods=a.stagger, phases=np.tile(np.arange(a.agents) % a.stagger, (a.scenes, 1)))
 
@@ -164,6 +179,9 @@ def main():
     if a.goal_gate:
         print("goal gate (half side %s): %d slot-rounds examined, %d let through (goal taken), %d turned down (counted in fe_no_solution)"
               % ("drone radius" if gg is True else "%.2f m" % gg, sum(r["gate_examined"] for r in rep), sum(r["goal_taken"] for r in rep), sum(r["gated"] for r in rep)))
+    if a.fly_guess:
+        print("fly guess: %d slot-rounds with both QP solves failed, %d guesses published, %d flown, %d not flown (turned down by the safety pass, arrived)"
+              % tuple(sum(r[k] for r in rep) for k in ("qp_failed_seen", "guess_published", "guess_flown", "guess_not_flown")))
     if a.missions:
         ms = [r["mission"] for r in rep]
         ended = sum(m["legs_reached"] + m["legs_timed_out"] for m in ms)
@@ -186,7 +204,7 @@ def main():
     if a.host:
         sc = scenes[0]
         _, dev1, n1 = fly([sc], a.rounds)
-        ref = FleetLoop(sc["par"], sc["statics"], sc["starts"], scene.reachable_goals(sc), beam_width=a.beam, audit=a.audit, tethers=a.tethers, check=not a.no_check, search=a.search, max_pops=a.max_pops, moveback=mb, goal_gate=gg)
+        ref = FleetLoop(sc["par"], sc["statics"], sc["starts"], kw["goals"][0] if a.cross else scene.reachable_goals(sc), beam_width=a.beam, audit=a.audit, tethers=a.tethers, check=not a.no_check, search=a.search, max_pops=a.max_pops, moveback=mb, goal_gate=gg, fly_guess=a.fly_guess)
         ref.round(); ref.round()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
