@@ -7,7 +7,7 @@
  *
  *   nep_batch_fleet_select [-> nep_batch_fleet_moveback] -> nep_batch_frontend [-> nep_batch_goal_gate] -> nep_batch_replan
  *     [-> nep_batch_guess_fallback] -> nep_batch_safety_commit -> nep_batch_fleet_commit [-> nep_batch_guess_fallback_tally]
- *     [-> nep_batch_audit] [-> nep_batch_fleet_mission] -> nep_batch_fleet_tick
+ *     [-> nep_batch_audit] [-> nep_batch_fleet_mission] [-> nep_batch_fleet_effort] -> nep_batch_fleet_tick
  *
  * is a fixed launch sequence on fixed buffers: one HIP graph for all scenes, no host synchronisation in it.  The arithmetic is the
  * host library's own (neptune_amd/csrc/plan_common.h is compiled into both), so the plans, tracked states and trajectories on the
@@ -237,11 +237,14 @@ int nep_batch_fleet_ent_lists(nep_batch_t* h, nep_ent_lists* host_out, int32_t* 
  *   one rule set     both modes share the five tests (autoCMD has 1-3, benchmark_mtlp 2, 4, 5); a test is off at parameter 0.
  *   quota            max_goals ends a campaign (the reference's scripts are stopped from outside or after 100 runs).
  *   use_moveback_    is nep_batch_fleet_moveback, below.  The single-agent A* benchmark branch of replanCB: not built.
+ *   given goals      auto_commands_together.py's fixed lists are nep_batch_fleet_mission_script with mode
+ *                    NEP_MISSION_FLEET_TOGETHER, and benchmark_multi_direct.py's mean jerk is nep_batch_fleet_effort, both below.
  * Limits: the kernel stages a scene's end positions, new goals and keep-outs in 64 KB of LDS, sized once at
  * nep_batch_fleet_mission_init for 52 B per agent and a full keep-out set (NEP_MISSION_MAX_POLY polygons, NEP_MISSION_MAX_VERT
  * vertices in all per scene), so that keep-outs uploaded later fit a round captured earlier: up to 1 097 agents; beyond: NEP_E_CAP. */
 #define NEP_MISSION_PER_AGENT 1
 #define NEP_MISSION_FLEET_RUNS 2
+#define NEP_MISSION_FLEET_TOGETHER 3    /* scripts/auto_commands_together.py: see "scripted goals" below                      */
 #define NEP_MISSION_REACHED 1           /* nep_mission_leg.outcome (mode FLEET_RUNS: the run succeeded)                      */
 #define NEP_MISSION_TIMED_OUT 2         /* (mode FLEET_RUNS: the run failed)                                                 */
 #define NEP_MISSION_NO_GOAL 3           /* no candidate of max_attempts passed: the slot keeps its goal                      */
@@ -251,13 +254,14 @@ int nep_batch_fleet_ent_lists(nep_batch_t* h, nep_ent_lists* host_out, int32_t* 
 
 /* nep_abi_sizeof(20) */
 typedef struct nep_mission_cfg {
-  int32_t mode;                   /* NEP_MISSION_PER_AGENT or NEP_MISSION_FLEET_RUNS                                         */
+  int32_t mode;                   /* NEP_MISSION_PER_AGENT, NEP_MISSION_FLEET_RUNS or NEP_MISSION_FLEET_TOGETHER             */
   int32_t max_goals;              /* legs per slot (runs per scene) that may end, >= 1                                       */
   int32_t max_attempts;           /* candidates per draw: a multiple of 64, 64 .. 4096                                       */
   int32_t log_cap;                /* records kept per slot (per scene in mode FLEET_RUNS), >= 0                              */
   uint64_t seed;
   double lo[2], hi[2];            /* the box goals are drawn in (the caller shrinks the world)                               */
-  double goal_z, arrive_radius, min_interval, timeout, rest_v, rest_a;      /* (min_interval, rest_*: mode PER_AGENT only)  */
+  double goal_z, arrive_radius, min_interval, timeout, rest_v, rest_a;      /* (min_interval, rest_*: mode PER_AGENT only;
+                                                                               timeout = +infinity: none)                   */
   double min_dist_self, tether_max, close_pos, close_goal;                  /* the tests 1, 2, 4, 5; 0: off                 */
 } nep_mission_cfg;
 
@@ -328,6 +332,79 @@ int nep_batch_fleet_mission_log(nep_batch_t* h, nep_mission_leg* log_out, int32_
  * (neptune_amd/csrc/mission_common.h) and the device equals a chain of these calls byte for byte.  NEP_E_ARG on a bad
  * configuration or null pointers.                                                                                               */
 int nep_mission_step(const nep_mission_cfg* cfg, nep_mission_scene* sc);
+
+/* ---- scripted goals and the position-exchange driver ---------------------------------------------------------------------------
+ * nep_batch_fleet_mission_script hands the controller a table of goals per slot: host data, goals [slots][n_goals][3] (slot =
+ * scene * num_agents + agent), in the style of nep_batch_fleet_mission_keepout.  Wherever the controller would draw a goal for a
+ * slot and a script is set, the goal is row (i - 1) mod n_goals of the slot's table, i being the slot's `issued` count at that
+ * moment — the goal index the generator hashes; leg 0 is the goal given to nep_batch_fleet_init — with all three coordinates
+ * (cfg.goal_z is not used).  No candidate is generated and none of the five tests is applied: the leg record's attempts is 0 (mode
+ * FLEET_RUNS / FLEET_TOGETHER: the run's), the goal counts as found, and the no-goal path cannot be taken.  Triggers, quotas, logs,
+ * t_issue, done and the move-back rule are what they are without a script.  The row follows from `issued`, which a snapshot
+ * carries: the snapshot's layout, sizes and version do not change, and the table itself — like the keep-outs — is not in it.
+ *
+ * The table and its length live in the handle's device buffers and are read by the kernel when it runs.  Capacity: the n_goals of
+ * the first upload with n_goals > 0 fixes the rows per slot for the handle's life; a later table of at most that many rows
+ * replaces it in place (also between replays of a captured round, which then honours it), a longer one is NEP_E_CAP and changes
+ * nothing.  n_goals = 0 switches the script off (and allocates nothing).  A non-finite coordinate is NEP_E_ARG.  The table
+ * survives nep_batch_fleet_init and nep_batch_fleet_mission_init.  Synchronises; not capturable; nep_batch_fleet_mission itself
+ * never allocates.  A round captured BEFORE the first upload with n_goals > 0 was recorded without the table's address: it keeps
+ * drawing whatever is uploaded later.  Upload first, then capture.  Unsharded handles only (NEP_E_STATE).
+ *
+ * NEP_MISSION_FLEET_TOGETHER is scripts/auto_commands_together.py:154-182, the driver of the position exchange: like mode
+ * FLEET_RUNS, except that `completed` is STICKY within a run — set at a tick where dx*dx < r*r && dy*dy < r*r (x-y only, r =
+ * arrive_radius; the script's `< 0.5` on the squares is r = sqrt(0.5)) and cleared only by the next run — and that the leg grows
+ * while completed is 0 before the tick's test, as in mode FLEET_RUNS.  The run is over when every slot is completed, or after
+ * `timeout` (a failure; the script has no timeout: give +infinity).  Modes PER_AGENT and FLEET_RUNS take a script too, and mode
+ * FLEET_TOGETHER without one draws.
+ *
+ * What differs from the reference (auto_commands_together.py):
+ *   when it runs     the script compares every odometry message of every agent on wall-clock callbacks; here every flown tick is
+ *                    tested, once per round, and the next goals are issued at the round's end.
+ *   who advances     the script publishes the next list when its `completed` list is all true, then sleeps; here that is the run's
+ *                    end, with a leg record (time, mean distance) the script does not keep.
+ *   how long         the script alternates goals1 / goals0 while currentrun < 3; here max_goals runs (the first on the goals
+ *                    given to nep_batch_fleet_init) over a table of any length, taken in a circle.
+ *
+ * nep_mission_step_script   the host form with a script: script [n_agents][n_goals][3], the scene's rows.  n_goals = 0 (script
+ *                    may be NULL) is nep_mission_step for modes PER_AGENT and FLEET_RUNS, byte for byte.  nep_mission_step keeps
+ *                    its contract — those two modes, anything else NEP_E_ARG —; mode FLEET_TOGETHER goes through this call.       */
+int nep_batch_fleet_mission_script(nep_batch_t* h, int32_t n_goals, const double* goals);
+int nep_mission_step_script(const nep_mission_cfg* cfg, nep_mission_scene* sc, int32_t n_goals, const double* script);
+
+/* ---- effort: what the flown ticks cost, and whether they keep the limits ------------------------------------------------------------
+ * scripts/benchmark_multi_direct.py judges a journey by its mean jerk (cmdCB: jerkSum += |j| * 0.05 per command, until completion).
+ * nep_batch_fleet_effort accumulates that per slot over the ticks about to be flown, with the largest |component| of velocity,
+ * acceleration and jerk and counts of the ticks that break a limit — the trajectories flown include guesses the QP never optimised
+ * (nep_batch_guess_fallback), and nep_batch_audit judges positions only.
+ *
+ * The call goes where nep_batch_fleet_mission goes: after nep_batch_fleet_commit, before nep_batch_fleet_tick.  It walks the ticks
+ * q = 1..round_ticks by the rule of nep_batch_fleet_mission and nep_batch_fleet_track_ent: s_q = ring[(head + min(q - 1, size - 1))
+ * mod cap], 12 doubles (position, velocity, acceleration, jerk).  A tick is COUNTED when it pops a fresh state (q - 1 <= size - 1)
+ * and the slot's done flag is clear: a repeated last state and an arrived agent add nothing.  Per counted tick, in tick order:
+ *   n_ticks += 1;   jerk_sum = jerk_sum + sqrt((jx*jx + jy*jy) + jz*jz) * dc;   max_v[i] = max(max_v[i], |v_i|), likewise max_a, max_j;
+ *   n_v_viol += 1 when |v_i| > v_max + slack for some i; n_a_viol with a_max; n_j_viol with j_max.
+ * v_max and a_max are the handle's (nep_batch_cfg: one value for every axis); the handle keeps no j_max — it is a parameter of
+ * the front end's configuration (nep_fe_cfg.j_max) — so the caller gives it.  slack is absolute and >= 0, the limits finite and
+ * > 0, else NEP_E_ARG.  d_effort [slots] is the caller's, accumulated into (zero it first); chained calls equal one long call bit
+ * for bit.  One thread per slot, no LDS, no atomics; reads the fleet state and writes d_effort only.  Asynchronous, capturable,
+ * allocates nothing.  NEP_E_STATE without fleet state and on sharded handles.
+ *
+ * What differs from the reference (benchmark_multi_direct.py): the sum runs over the flown ticks at dc, not over command messages
+ * at an assumed 0.05 s; it stops at the sticky arrival of nep_batch_fleet_tick (a mission's new goal starts it again), where the
+ * script stops at its own completion test on agent 0's callbacks; the maxima and the violation counts are not in the script.
+ *
+ * nep_effort_step    host form for one slot (effort_host.cpp; no HIP call): ring [cap][12] with head and size, as the handle holds
+ *                    them.  Shares effort_common.h with the kernel; the device equals a chain of these calls byte for byte.       */
+/* nep_abi_sizeof(29): 96 bytes; 28 stays unassigned: tests/test_fleet_moveback_cpu.py pins it to -1 */
+typedef struct nep_fleet_effort {
+  double jerk_sum;                     /* sum over counted ticks of |jerk|_2 (3-D) * dc, added in tick order                  */
+  double max_v[3], max_a[3], max_j[3]; /* largest |component| at a counted tick                                               */
+  int32_t n_ticks, n_v_viol, n_a_viol, n_j_viol;
+} nep_fleet_effort;
+int nep_batch_fleet_effort(nep_batch_t* h, double j_max, double slack, nep_fleet_effort* d_effort, void* stream);
+int nep_effort_step(double v_max, double a_max, double j_max, double dc, int32_t round_ticks, const double* ring, int32_t head,
+                    int32_t size, int32_t cap, int32_t done, double slack, nep_fleet_effort* out);
 
 /* ---- move-back: a new goal is approached by way of the agent's own base ---------------------------------------------------------
  * The reference's use_moveback_strategy (neptune_mtlp_benchmark.yaml: true; neptune_ros.cpp:1626-1636, :1291-1305): an agent that

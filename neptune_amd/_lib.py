@@ -54,6 +54,7 @@ FLEET_EXPORTS = ["nep_batch_fleet_init", "nep_batch_fleet_select", "nep_batch_fl
                  "nep_batch_fleet_track_ent", "nep_batch_fleet_ent_state", "nep_batch_fleet_init_ent_lists", "nep_batch_fleet_ent_lists", "nep_batch_fleet_mission_keepout", "nep_batch_fleet_mission_init",
                  "nep_batch_fleet_mission", "nep_batch_fleet_mission_state", "nep_batch_fleet_mission_log", "nep_mission_step",
                  "nep_batch_fleet_moveback", "nep_moveback_step",
+                 "nep_batch_fleet_mission_script", "nep_mission_step_script", "nep_batch_fleet_effort", "nep_effort_step",
                  "nep_batch_fleet_snapshot", "nep_batch_fleet_snapshot_ring", "nep_batch_fleet_restore", "nep_fleet_snapshot_describe"]
 # ... and the two of its recorder section that return a byte count (int64_t)
 FLEET_SIZE_EXPORTS = ["nep_batch_fleet_snapshot_bytes", "nep_batch_fleet_snapshot_ring_bytes"]
@@ -229,6 +230,10 @@ def lib():
     L.nep_mission_step.argtypes = [C.POINTER(abi.nep_mission_cfg), C.POINTER(abi.nep_mission_scene)]
     L.nep_batch_fleet_moveback.argtypes = [vp, C.POINTER(abi.nep_moveback_cfg), vp, vp]
     L.nep_moveback_step.argtypes = [C.POINTER(abi.nep_moveback_cfg), i, vp, vp, vp, d, d, vp, vp]
+    L.nep_batch_fleet_mission_script.argtypes = [vp, i, vp]
+    L.nep_mission_step_script.argtypes = [C.POINTER(abi.nep_mission_cfg), C.POINTER(abi.nep_mission_scene), i, vp]
+    L.nep_batch_fleet_effort.argtypes = [vp, d, d, vp, vp]
+    L.nep_effort_step.argtypes = [d, d, d, d, i, vp, i, i, i, i, d, vp]
     L.nep_batch_fleet_snapshot_bytes.argtypes = [vp]; L.nep_batch_fleet_snapshot_bytes.restype = C.c_int64
     L.nep_batch_fleet_snapshot.argtypes = [vp, vp, vp]
     L.nep_batch_fleet_snapshot_ring_bytes.argtypes = [vp, i]; L.nep_batch_fleet_snapshot_ring_bytes.restype = C.c_int64
@@ -244,7 +249,8 @@ def lib():
     L.nep_abi_sizeof.argtypes = [i]; L.nep_abi_sizeof.restype = i
     for which, struct in ((1, abi.nep_traj_rec), (5, abi.nep_guess), (6, abi.nep_solution), (11, abi.nep_fe_cfg), (12, abi.nep_fe_start),
                           (13, abi.nep_fe_result), (14, abi.nep_fe_ent_state), (17, abi.nep_audit), (18, abi.nep_fleet_cfg),
-                          (20, abi.nep_mission_cfg), (21, abi.nep_mission_leg), (23, abi.nep_ent_lists), (25, abi.nep_fleet_snapshot_hdr), (27, abi.nep_moveback_cfg)):
+                          (20, abi.nep_mission_cfg), (21, abi.nep_mission_leg), (23, abi.nep_ent_lists), (25, abi.nep_fleet_snapshot_hdr), (27, abi.nep_moveback_cfg),
+                          (29, abi.nep_fleet_effort)):
         if L.nep_abi_sizeof(which) != C.sizeof(struct):
             raise BackendError("%s: sizeof(%s) is %d in the library, %d in neptune_amd/abi.py — rebuild the library from this tree's headers"
                                % (LIB_PATH, struct.__name__, L.nep_abi_sizeof(which), C.sizeof(struct)))

@@ -229,7 +229,7 @@ NEP_FLEET_FLAG_ERRORS = NEP_FLEET_FLAG_SEG | NEP_FLEET_FLAG_RING | NEP_FLEET_FLA
 
 
 # ---- missions (include/neptune_fleet.h) ----
-NEP_MISSION_PER_AGENT, NEP_MISSION_FLEET_RUNS = 1, 2
+NEP_MISSION_PER_AGENT, NEP_MISSION_FLEET_RUNS, NEP_MISSION_FLEET_TOGETHER = 1, 2, 3
 NEP_MISSION_REACHED, NEP_MISSION_TIMED_OUT, NEP_MISSION_NO_GOAL = 1, 2, 3
 NEP_MISSION_MAX_POLY, NEP_MISSION_MAX_VERT = 64, 512
 MISSION_COUNTS = ("issued", "reached", "timed_out", "no_goal")
@@ -263,6 +263,12 @@ class nep_mission_scene(C.Structure):
 class nep_moveback_cfg(C.Structure):
     """include/neptune_fleet.h: the move-back rule's two parameters (nep_batch_fleet_moveback, nep_moveback_step)."""
     _fields_ = [("radius", C.c_double), ("timeout", C.c_double)]
+
+
+class nep_fleet_effort(C.Structure):
+    """include/neptune_fleet.h: a slot's effort record (nep_batch_fleet_effort, nep_effort_step)."""
+    _fields_ = [("jerk_sum", C.c_double), ("max_v", C.c_double * 3), ("max_a", C.c_double * 3), ("max_j", C.c_double * 3),
+                ("n_ticks", C.c_int32), ("n_v_viol", C.c_int32), ("n_a_viol", C.c_int32), ("n_j_viol", C.c_int32)]
 
 
 # ---- the recorder (include/neptune_fleet.h) ----
@@ -301,6 +307,7 @@ FE_ENT_STATE_DTYPE = np.dtype(nep_fe_ent_state)
 AUDIT_DTYPE = np.dtype(nep_audit)
 PWP_DTYPE = np.dtype(nep_pwp)
 MISSION_LEG_DTYPE = np.dtype(nep_mission_leg)
+EFFORT_DTYPE = np.dtype(nep_fleet_effort)
 
 
 def dptr(a):

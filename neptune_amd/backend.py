@@ -556,6 +556,27 @@ class BatchBackend:
         st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
         check(lib().nep_batch_fleet_mission(self._h, st.cuda_stream))
 
+    def fleet_mission_script(self, goals):
+        """the scripted goals of every slot (nep_batch_fleet_mission_script): goals [slots][G][3] host data, or None / G = 0: off.
+        The first upload fixes the capacity; a longer table later is NEP_E_CAP"""
+        if goals is None:
+            check(lib().nep_batch_fleet_mission_script(self._h, 0, None))
+            return
+        g = np.ascontiguousarray(goals, dtype=np.float64)
+        if g.ndim != 3 or g.shape[0] != self.slots or g.shape[2] != 3:
+            raise ValueError("scripted goals are [slots][G][3]")
+        check(lib().nep_batch_fleet_mission_script(self._h, g.shape[1], g.ctypes.data))
+
+    def new_effort(self):
+        """a zeroed [slots] abi.EFFORT_DTYPE buffer on the device (uint8 tensor) for fleet_effort"""
+        return self.torch.zeros(self.slots * abi.EFFORT_DTYPE.itemsize, dtype=self.torch.uint8, device=self.device)
+
+    def fleet_effort(self, j_max, slack, d_effort, stream=None):
+        """the effort record of the ticks about to be flown (nep_batch_fleet_effort), accumulated into d_effort; where fleet_mission
+        goes: after fleet_commit, before fleet_tick"""
+        st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        check(lib().nep_batch_fleet_effort(self._h, float(j_max), float(slack), d_effort.data_ptr(), st.cuda_stream))
+
     def fleet_moveback(self, cfg, d_start, stream=None):
         """the move-back rule of the round (nep_batch_fleet_moveback), after fleet_select: cfg abi.nep_moveback_cfg; the slots on
         their way back get their base as d_start's goal"""
@@ -581,7 +602,7 @@ class BatchBackend:
 
     def fleet_mission_log(self, ordered=True):
         """the mission log (blocking) -> (records, n): n [owners] records ever written, records a list per owner (slot, or scene in mode
-        FLEET_RUNS) of the last min(n, log_cap) MISSION_LEG_DTYPE records, oldest first (ordered=False: the [owners][log_cap] array as stored)"""
+        FLEET_RUNS / FLEET_TOGETHER) of the last min(n, log_cap) MISSION_LEG_DTYPE records, oldest first (ordered=False: the [owners][log_cap] array as stored)"""
         cfg = self.mission_cfg
         owners = self.slots if cfg.mode == abi.NEP_MISSION_PER_AGENT else self.n_scenes
         cap = int(cfg.log_cap)

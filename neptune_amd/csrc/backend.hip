@@ -19,6 +19,7 @@
 #include "qp_outputs.h"
 #include "audit_common.h"
 #include "mission_common.h"
+#include "effort_common.h"
 #include "moveback_common.h"
 #include "recorder_common.h"
 #include "../../include/neptune_plan.h"
@@ -1028,6 +1029,9 @@ struct nep_batch {
     bool mis_ready = false; nep_mission_cfg mis_cfg{}; size_t mis_lds = 0;
     DevBuf<double> mis_t_issue, mis_length, mis_sums, mis_t_run; DevBuf<int> mis_completed, mis_counts, mis_scene, mis_log_n; DevBuf<nep_mission_leg> mis_log;
     DevBuf<int> keep_n, keep_off; DevBuf<double> keep_xy;
+    // the scripted goals (nep_batch_fleet_mission_script): [slots][*script_n][3] and the rows per slot now; script_cap rows per slot
+    // were allocated by the first upload (0: none yet) and no init drops them
+    int script_cap = 0; DevBuf<double> script; DevBuf<int> script_n;
     DevBuf<char> rec_stage;      // nep_batch_fleet_restore: the blob (or the one block of it) on its way in
     std::vector<hipStream_t> seen;      // the streams nep_batch_fleet_select and the snapshot calls were given (restore refuses while one captures)
     void saw(void* stream) { hipStream_t st = (hipStream_t)stream; if (!st) return; for (hipStream_t q : seen) if (q == st) return; if (seen.size() < 16) seen.push_back(st); }      // (the null stream cannot capture)
@@ -1905,6 +1909,7 @@ void fleet_mission_args(nep_batch_t* h, FleetMissionArgs& ma) {
   ma.t_issue = F.mis_t_issue.p; ma.length = F.mis_length.p; ma.completed = F.mis_completed.p; ma.counts = F.mis_counts.p; ma.sums = F.mis_sums.p;
   ma.scene_i = F.mis_scene.p; ma.t_run = F.mis_t_run.p; ma.log = F.mis_log.p; ma.log_n = F.mis_log_n.p;
   ma.kn = F.keep_n.p; ma.koff = F.keep_off.p; ma.kxy = F.keep_xy.p;
+  ma.script = F.script_cap > 0 ? F.script.p : nullptr; ma.script_n = F.script_cap > 0 ? F.script_n.p : nullptr;
 }
 constexpr size_t kMissionLds = 64 * 1024;
 }  // namespace
@@ -1934,10 +1939,31 @@ int nep_batch_fleet_mission_keepout(nep_batch_t* h, int32_t scene, int32_t n_pol
   return 0;
 }
 
+int nep_batch_fleet_mission_script(nep_batch_t* h, int32_t n_goals, const double* goals) {
+  if (int e = fleet_guard(h, false)) return e;
+  if (n_goals < 0 || (n_goals > 0 && !goals)) return fail(NEP_E_ARG, "bad arguments (n_goals >= 0, a table when n_goals > 0)");
+  nep_batch::Fleet& F = h->fleet;
+  const size_t slots = (size_t)h->slots;
+  if (n_goals > (1 << 20)) return fail(NEP_E_CAP, "more than 2^20 scripted goals per slot");
+  for (size_t i = 0; i < slots * (size_t)n_goals * 3; i++)
+    if (!(goals[i] - goals[i] == 0.0)) return fail(NEP_E_ARG, "a scripted goal is not finite");
+  if (F.script_cap > 0 && n_goals > F.script_cap) return fail(NEP_E_CAP, "the script is longer than the handle's capacity (the n_goals of the first upload)");
+  if (F.script_cap == 0 && n_goals == 0) return 0;      // nothing uploaded yet, nothing to switch off
+  HIPCHK(hipDeviceSynchronize());     // the previous table may still be read by kernels in flight
+  if (F.script_cap == 0) {
+    if (int e = F.script.ensure(slots * (size_t)n_goals * 3)) return e;
+    if (int e = F.script_n.ensure(1)) return e;
+    F.script_cap = n_goals;
+  }
+  if (n_goals > 0) HIPCHK(hipMemcpy(F.script.p, goals, slots * (size_t)n_goals * 3 * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(F.script_n.p, &n_goals, sizeof(int), hipMemcpyHostToDevice));
+  return 0;
+}
+
 int nep_batch_fleet_mission_init(nep_batch_t* h, const nep_mission_cfg* cfg, void* stream) {
   if (int e = fleet_guard(h, true)) return e;
   if (!cfg) return fail(NEP_E_ARG, "null argument");
-  if (!nep_mission_impl::mission_cfg_ok(*cfg)) return fail(NEP_E_ARG, "bad mission configuration (mode, max_goals >= 1, max_attempts a multiple of 64 in 64..4096, log_cap >= 0, lo < hi, arrive_radius and timeout > 0, nothing negative)");
+  if (!nep_mission_impl::mission_cfg_ok(*cfg)) return fail(NEP_E_ARG, "bad mission configuration (mode 1..3, max_goals >= 1, max_attempts a multiple of 64 in 64..4096, log_cap >= 0, lo < hi, arrive_radius and timeout > 0, nothing negative)");
   nep_batch::Fleet& F = h->fleet;
   if (cfg->mode == NEP_MISSION_PER_AGENT && !(cfg->min_dist_self > F.cfg.goal_radius)) return fail(NEP_E_ARG, "mode NEP_MISSION_PER_AGENT needs min_dist_self > the fleet's goal_radius: a fresh goal must not count as reached");
   hipStream_t st = (hipStream_t)stream;
@@ -1978,6 +2004,19 @@ int nep_batch_fleet_mission(nep_batch_t* h, void* stream) {
   FleetMissionArgs ma{};
   fleet_mission_args(h, ma);
   launch_fleet_mission(ma, fa, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ---- the effort record (include/neptune_fleet.h; kernel: fleet_effort_kernels.hip; host form: effort_host.cpp) ----
+int nep_batch_fleet_effort(nep_batch_t* h, double j_max, double slack, nep_fleet_effort* d_effort, void* stream) {
+  if (int e = fleet_guard(h, true)) return e;
+  if (!d_effort) return fail(NEP_E_ARG, "null argument");
+  FleetArgs fa{};
+  fleet_args(h, fa);
+  const nep_effort_impl::EffortLimits l{h->eng.sp.v_max, h->eng.sp.a_max, j_max, slack};
+  if (!nep_effort_impl::effort_args_ok(l, fa.cfg.dc, fa.cfg.round_ticks)) return fail(NEP_E_ARG, "bad effort arguments (v_max, a_max and j_max finite and > 0, slack finite and >= 0)");
+  launch_fleet_effort(fa, l.v_max, l.a_max, l.j_max, l.slack, d_effort, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -2609,6 +2648,7 @@ int nep_abi_sizeof(int32_t which) {
     case 23: return (int)sizeof(nep_ent_lists);      // (22 stays unassigned: tests/test_fleet_mission_cpu.py pins it to -1)
     case 25: return (int)sizeof(nep_fleet_snapshot_hdr);      // (24 stays unassigned: tests/test_ent_lists_cpu.py pins it to -1)
     case 27: return (int)sizeof(nep_moveback_cfg);      // (26 stays unassigned: tests/test_fleet_recorder_cpu.py pins it to -1)
+    case 29: return (int)sizeof(nep_fleet_effort);      // (28 stays unassigned: tests/test_fleet_moveback_cpu.py pins it to -1)
     default: return -1;
   }
 }

@@ -5,12 +5,14 @@
 //
 // Layout: one wave (one 64-thread workgroup) per scene.  Lanes stride over the agents for the walk over the round's ticks and the
 // triggers, and leave in LDS every agent's end position and what the call has to do for it.  The agents that need a goal are then
-// taken in agent order (mode PER_AGENT: the set bits of a ballot per 64 agents; mode FLEET_RUNS: everyone), and a draw is
+// taken in agent order (mode PER_AGENT: the set bits of a ballot per 64 agents; the run modes: everyone), and a draw is
 // cooperative: lane l evaluates candidate k = 64 b + l against all five tests, the winner is the lowest set bit of the ballot, and
 // batches b go on until one is found or max_attempts is reached — a serial rejection loop's result, whatever the scheduling.  The
 // slot's owner lane (agent mod 64) writes the record, the totals and the goal with plain stores; the only atomic is the sticky
 // global flag on the no-goal path.  Every branch around a barrier or a ballot depends on kernel arguments, on values all lanes
 // load from the same address, or on a ballot's result.
+// With a script (nep_batch_fleet_mission_script) the draw is replaced by a read of the slot's table: the length comes from device memory
+// — one address, uniform — so a table replaced between replays of a captured round is the one that is read.
 #include <hip/hip_runtime.h>
 
 #define NEP_MISSION_FN __device__ inline
@@ -47,6 +49,14 @@ __device__ inline int mission_draw(const nep_mission_cfg& c, int lane, uint64_t 
   return -1;
 }
 
+// A scripted goal of `slot` (nep_batch_fleet_mission_script): row (issued - 1) mod n_goals of its table; every lane reads the same
+// three doubles.  Returns k = 0: found.
+__device__ inline int mission_scripted(const FleetMissionArgs& ma, long slot, int n_goals, double& gx, double& gy, double& gz) {
+  const double* g = ma.script + (slot * n_goals + mission_script_row(ma.counts[slot * 4 + kIssued], n_goals)) * 3;
+  gx = g[0]; gy = g[1]; gz = g[2];
+  return 0;
+}
+
 __global__ __launch_bounds__(64) void fleet_mission_kernel(FleetMissionArgs ma, FleetArgs fa) {
   extern __shared__ __attribute__((aligned(16))) double ms_lds[];
   const int scene = blockIdx.x, lane = threadIdx.x;
@@ -72,6 +82,7 @@ __global__ __launch_bounds__(64) void fleet_mission_kernel(FleetMissionArgs ma, 
   const long gbase = (long)origin * N;
   const double t_end = mission_t_end(fa.t_now[scene], fa.cfg.dc, T);
   const bool per_agent = c.mode == NEP_MISSION_PER_AGENT;
+  const int n_script = ma.script ? ma.script_n[0] : 0;      // (one address for every lane: uniform; 0: the goals are drawn)
   // ---- the ticks and the triggers: lanes stride over the agents ----------------------------------------------------------------
   bool all_completed = true;
   for (int a0 = 0; a0 < N; a0 += 64) {
@@ -118,15 +129,16 @@ __global__ __launch_bounds__(64) void fleet_mission_kernel(FleetMissionArgs ma, 
         const long slot = base + a;
         const int outcome = s_got[a];
         const bool draws = mission_agent_draws(c, ma.counts + slot * 4);
-        double gx = 0.0, gy = 0.0;
+        double gx = 0.0, gy = 0.0, gz = c.goal_z;
         int k = -1;
-        if (draws) k = mission_draw(c, lane, mission_h1(c.seed, (uint64_t)(gbase + a), (uint64_t)ma.counts[slot * 4 + kIssued]), a, N, s_end, pb, n_poly, s_off, s_kxy, s_new, s_got, gx, gy);
+        if (draws && n_script > 0) k = mission_scripted(ma, slot, n_script, gx, gy, gz);
+        else if (draws) k = mission_draw(c, lane, mission_h1(c.seed, (uint64_t)(gbase + a), (uint64_t)ma.counts[slot * 4 + kIssued]), a, N, s_end, pb, n_poly, s_off, s_kxy, s_new, s_got, gx, gy);
         __syncthreads();      // (every lane has read the slot's counts and the LDS lists before the owner changes them)
         if (lane == (a & 63)) {
-          const bool none = mission_end_leg(c, mission_slot(ma, fa, slot), ma.log + slot * c.log_cap, ma.log_n + slot, (int)(gbase + a), outcome, t_end, draws, k, gx, gy);
+          const bool none = mission_end_leg(c, mission_slot(ma, fa, slot), ma.log + slot * c.log_cap, ma.log_n + slot, (int)(gbase + a), outcome, t_end, draws, n_script > 0, k, gx, gy, gz);
           if (none) atomicOr(fa.gflags, NEP_FLAG_MISSION);
           s_got[a] = draws && k >= 0 ? kGotNew : kNoNew;
-          if (draws && k >= 0) { s_new[3 * a] = gx; s_new[3 * a + 1] = gy; s_new[3 * a + 2] = c.goal_z; }
+          if (draws && k >= 0) { s_new[3 * a] = gx; s_new[3 * a + 1] = gy; s_new[3 * a + 2] = gz; }
         }
         __syncthreads();
       }
@@ -135,7 +147,7 @@ __global__ __launch_bounds__(64) void fleet_mission_kernel(FleetMissionArgs ma, 
     if (fin && lane == 0) scene_i[kFinished] = 1;
     return;
   }
-  // ---- benchmark_mtlp: the scene's run ------------------------------------------------------------------------------------------
+  // ---- benchmark_mtlp, auto_commands_together: the scene's run ------------------------------------------------------------------------------------------
   const double el = t_end - ma.t_run[scene];
   if (!mission_run_over(c, all_completed, el)) return;
   double sum = 0.0;
@@ -145,17 +157,16 @@ __global__ __launch_bounds__(64) void fleet_mission_kernel(FleetMissionArgs ma, 
   int attempts = 0;
   for (int a = 0; a < N; a++) {
     const long slot = base + a;
-    double gx = 0.0, gy = 0.0;
+    double gx = 0.0, gy = 0.0, gz = c.goal_z;
     int k = -1;
-    if (draws) {
-      k = mission_draw(c, lane, mission_h1(c.seed, (uint64_t)(gbase + a), (uint64_t)ma.counts[slot * 4 + kIssued]), a, N, s_end, pb, n_poly, s_off, s_kxy, s_new, s_got, gx, gy);
-      attempts += k >= 0 ? k + 1 : c.max_attempts;
-    }
+    if (draws && n_script > 0) k = mission_scripted(ma, slot, n_script, gx, gy, gz);
+    else if (draws) k = mission_draw(c, lane, mission_h1(c.seed, (uint64_t)(gbase + a), (uint64_t)ma.counts[slot * 4 + kIssued]), a, N, s_end, pb, n_poly, s_off, s_kxy, s_new, s_got, gx, gy);
+    attempts += mission_attempts(c, draws, n_script > 0, k);
     __syncthreads();
     if (lane == (a & 63)) {
-      const bool none = mission_end_run_slot(c, mission_slot(ma, fa, slot), el, t_end, draws, k, gx, gy);
+      const bool none = mission_end_run_slot(c, mission_slot(ma, fa, slot), el, t_end, draws, k, gx, gy, gz);
       if (none) atomicOr(fa.gflags, NEP_FLAG_MISSION);
-      if (draws && k >= 0) { s_got[a] = kGotNew; s_new[3 * a] = gx; s_new[3 * a + 1] = gy; s_new[3 * a + 2] = c.goal_z; }
+      if (draws && k >= 0) { s_got[a] = kGotNew; s_new[3 * a] = gx; s_new[3 * a + 1] = gy; s_new[3 * a + 2] = gz; }
     }
     __syncthreads();
   }

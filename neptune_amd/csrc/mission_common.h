@@ -48,15 +48,32 @@ NEP_MISSION_FN double mission_t_end(double t_now, double dc, int round_ticks) {
   return t;
 }
 
-// one tick of one slot: the leg grows while the agent is not arrived; mode FLEET_RUNS re-evaluates `completed` (both directions)
+// mode FLEET_TOGETHER's test (auto_commands_together.py:160-164): inside the square of half side arrive_radius around the goal, x-y only
+NEP_MISSION_FN bool mission_in_box(const nep_mission_cfg& c, const double* p, const double* goal) {
+  const double dx = p[0] - goal[0], dy = p[1] - goal[1], rr = c.arrive_radius * c.arrive_radius;
+  return dx * dx < rr && dy * dy < rr;
+}
+
+// one tick of one slot: the leg grows while the agent is not arrived; mode FLEET_RUNS re-evaluates `completed` (both directions),
+// mode FLEET_TOGETHER only sets it
 NEP_MISSION_FN void mission_tick(const nep_mission_cfg& c, const double* p_prev, const double* p, const double* goal, double& length, int& completed) {
   const double d = mission_dist3(p, goal), step = mission_dist3(p, p_prev);
   if (c.mode == NEP_MISSION_PER_AGENT) {
     if (d > c.arrive_radius) length = length + step;
-  } else {
+  } else if (c.mode == NEP_MISSION_FLEET_RUNS) {
     if (!completed) length = length + step;
     completed = d < c.arrive_radius ? 1 : 0;
+  } else {
+    if (!completed) length = length + step;
+    if (mission_in_box(c, p, goal)) completed = 1;
   }
+}
+
+// scripted goals: the row of a slot's table for the goal it is issued now (`issued` before the increment: the generator's goal index)
+NEP_MISSION_FN int mission_script_row(int issued, int n_goals) { return (issued - 1) % n_goals; }
+// the candidates a draw has examined, as a leg record states them: none without a draw and for a scripted goal
+NEP_MISSION_FN int mission_attempts(const nep_mission_cfg& c, bool draws, bool scripted, int k_win) {
+  return !draws || scripted ? 0 : (k_win >= 0 ? k_win + 1 : c.max_attempts);
 }
 
 // autoCMD's trigger on the end state (neptune_ros.cpp:1055-1066): 0 nothing, else NEP_MISSION_REACHED / NEP_MISSION_TIMED_OUT
@@ -102,7 +119,7 @@ NEP_MISSION_FN bool mission_accept(const nep_mission_cfg& c, double x, double y,
 }
 
 NEP_MISSION_FN bool mission_cfg_ok(const nep_mission_cfg& c) {
-  if (c.mode != NEP_MISSION_PER_AGENT && c.mode != NEP_MISSION_FLEET_RUNS) return false;
+  if (c.mode != NEP_MISSION_PER_AGENT && c.mode != NEP_MISSION_FLEET_RUNS && c.mode != NEP_MISSION_FLEET_TOGETHER) return false;
   if (c.max_goals < 1 || c.log_cap < 0 || c.max_attempts < 64 || c.max_attempts > 4096 || c.max_attempts % 64 != 0) return false;
   if (!(c.hi[0] > c.lo[0]) || !(c.hi[1] > c.lo[1]) || !(c.arrive_radius > 0.0) || !(c.timeout > 0.0)) return false;
   if (!(c.min_interval >= 0.0) || !(c.rest_v >= 0.0) || !(c.rest_a >= 0.0)) return false;
@@ -129,44 +146,45 @@ NEP_MISSION_FN bool mission_quota_used(const nep_mission_cfg& c, const int* coun
 // mode PER_AGENT: does the leg that ends now leave room for another one (is a goal drawn)?
 NEP_MISSION_FN bool mission_agent_draws(const nep_mission_cfg& c, const int* counts) { return counts[kReached] + counts[kTimedOut] + 1 < c.max_goals; }
 
-// the new leg of a slot: the goal drawn (k_win >= 0) or, without one, the goal it has; returns true on the no-goal path
-NEP_MISSION_FN bool mission_issue(const nep_mission_cfg& c, const MissionSlot& s, double t_end, int k_win, double gx, double gy) {
+// the new leg of a slot: the goal drawn or scripted (k_win >= 0; gz: cfg.goal_z, or the table's) or, without one, the goal it has;
+// returns true on the no-goal path
+NEP_MISSION_FN bool mission_issue(const nep_mission_cfg& c, const MissionSlot& s, double t_end, int k_win, double gx, double gy, double gz) {
   const bool none = k_win < 0;
   if (none) { s.counts[kNoGoal] = s.counts[kNoGoal] + 1; *s.flags = *s.flags | NEP_FLEET_FLAG_GOAL; }
-  else { s.goal[0] = gx; s.goal[1] = gy; s.goal[2] = c.goal_z; }
+  else { s.goal[0] = gx; s.goal[1] = gy; s.goal[2] = gz; }
   s.counts[kIssued] = s.counts[kIssued] + 1;
   *s.t_issue = t_end; *s.length = 0.0; *s.completed = 0; *s.done = 0;
   return none;
 }
 
-// mode PER_AGENT: the leg of a slot ends with `outcome`; `draws`, k_win, (gx, gy): the draw that followed.  Returns true on the
-// no-goal path (the caller raises the handle's flag).
+// mode PER_AGENT: the leg of a slot ends with `outcome`; `draws`, k_win, (gx, gy, gz): the draw that followed, or (scripted, k_win = 0)
+// the table's row.  Returns true on the no-goal path (the caller raises the handle's flag).
 NEP_MISSION_FN bool mission_end_leg(const nep_mission_cfg& c, const MissionSlot& s, nep_mission_leg* log, int* log_n, int gslot, int outcome,
-                                    double t_end, bool draws, int k_win, double gx, double gy) {
+                                    double t_end, bool draws, bool scripted, int k_win, double gx, double gy, double gz) {
   const double el = t_end - *s.t_issue;
   const int index = s.counts[kIssued] - 1;
   const int which = outcome == NEP_MISSION_REACHED ? kReached : kTimedOut;
   s.counts[which] = s.counts[which] + 1;
   s.sums[0] = s.sums[0] + el; s.sums[1] = s.sums[1] + *s.length;
-  const int attempts = !draws ? 0 : (k_win >= 0 ? k_win + 1 : c.max_attempts);
+  const int attempts = mission_attempts(c, draws, scripted, k_win);
   mission_log(c, log, log_n, gslot, index, outcome, attempts, *s.t_issue, t_end, *s.length, s.goal[0], s.goal[1], s.goal[2]);
   if (!draws) return false;
   if (k_win < 0) mission_log(c, log, log_n, gslot, index + 1, NEP_MISSION_NO_GOAL, c.max_attempts, t_end, t_end, 0.0, s.goal[0], s.goal[1], s.goal[2]);
-  return mission_issue(c, s, t_end, k_win, gx, gy);
+  return mission_issue(c, s, t_end, k_win, gx, gy, gz);
 }
 
-// mode FLEET_RUNS: a slot at the end of a run that took `el`
-NEP_MISSION_FN bool mission_end_run_slot(const nep_mission_cfg& c, const MissionSlot& s, double el, double t_end, bool draws, int k_win, double gx, double gy) {
+// modes FLEET_RUNS and FLEET_TOGETHER: a slot at the end of a run that took `el`
+NEP_MISSION_FN bool mission_end_run_slot(const nep_mission_cfg& c, const MissionSlot& s, double el, double t_end, bool draws, int k_win, double gx, double gy, double gz) {
   const int which = *s.completed ? kReached : kTimedOut;
   s.counts[which] = s.counts[which] + 1;
   s.sums[0] = s.sums[0] + el; s.sums[1] = s.sums[1] + *s.length;
   if (!draws) return false;
-  return mission_issue(c, s, t_end, k_win, gx, gy);
+  return mission_issue(c, s, t_end, k_win, gx, gy, gz);
 }
-// mode FLEET_RUNS: is the run over (all_completed: every slot's flag after the call's ticks)?
+// modes FLEET_RUNS and FLEET_TOGETHER: is the run over (all_completed: every slot's flag after the call's ticks)?
 NEP_MISSION_FN bool mission_run_over(const nep_mission_cfg& c, bool all_completed, double el) { return all_completed || el > c.timeout; }
 NEP_MISSION_FN bool mission_run_draws(const nep_mission_cfg& c, const int* scene_i) { return scene_i[kRun] + 1 < c.max_goals; }
-// mode FLEET_RUNS: the scene's record and counters (length_sum: the slots' leg lengths summed in agent order)
+// modes FLEET_RUNS and FLEET_TOGETHER: the scene's record and counters (length_sum: the slots' leg lengths summed in agent order)
 NEP_MISSION_FN void mission_end_run(const nep_mission_cfg& c, int* scene_i, double* t_run, nep_mission_leg* log, int* log_n, int scene, bool success,
                                     double t_end, double length_sum, int N, int attempts) {
   mission_log(c, log, log_n, scene, scene_i[kRun], success ? NEP_MISSION_REACHED : NEP_MISSION_TIMED_OUT, attempts, *t_run, t_end,

@@ -320,12 +320,16 @@ struct FleetMissionArgs {
   const int* kn;                 // [scenes] keep-out polygons of the scene
   const int* koff;               // [scenes][NEP_MISSION_MAX_POLY + 1]
   const double* kxy;             // [scenes][NEP_MISSION_MAX_VERT][2]
+  const double* script;          // [slots][*script_n][3] the scripted goals (nep_batch_fleet_mission_script), or null: never uploaded
+  const int* script_n;           // [1] rows per slot now (0: off); read when the kernel runs, so a replaced table reaches a captured round
 };
 void launch_fleet_mission_seed(const FleetMissionArgs& ma, const FleetArgs& fa, hipStream_t st);
 void launch_fleet_mission(const FleetMissionArgs& ma, const FleetArgs& fa, hipStream_t st);
 // the move-back rule (fleet_moveback_kernels.hip): nep_batch_fleet_moveback.  State, bases, clocks and the slots' flags are FleetArgs',
 // fa.start the round's start records; t_issue is the mission state's [slots], or null (every goal was issued at fa.cfg.t0)
 void launch_fleet_moveback(const nep_moveback_cfg& c, const FleetArgs& fa, const double* t_issue, hipStream_t st);
+// the effort record (fleet_effort_kernels.hip): nep_batch_fleet_effort.  Rings, heads, sizes and done flags are FleetArgs'; out [slots]
+void launch_fleet_effort(const FleetArgs& fa, double v_max, double a_max, double j_max, double slack, nep_fleet_effort* out, hipStream_t st);
 // the fleet recorder (fleet_recorder_kernels.hip): nep_batch_fleet_snapshot / _snapshot_ring / _restore.  Section i of a scene block
 // (recorder_common.h) is the scene's part — `bytes` bytes — of the handle's array `p`, at `off` in the block.  All device pointers.
 struct RecorderSection { char* p; long off; unsigned bytes; unsigned pad_; };

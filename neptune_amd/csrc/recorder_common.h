@@ -56,7 +56,7 @@ inline bool fields_ok(const nep_fleet_snapshot_hdr& h) {
   return h.n_scenes >= 1 && h.N >= 1 && h.N <= (1 << 20) && h.ring_cap >= 1 && h.ring_cap <= (1 << 20) && h.num_pol >= 1 && h.num_pol <= NEP_MAX_POL && h.max_states >= 1 &&
          h.tether_form >= 0 && h.tether_form <= 2 && (h.tether_form == 0 ? h.tether_cap == 0 : h.tether_form == 1 ? h.tether_cap == NEP_FE_ENT_CAP
                                                                                                   : h.tether_cap > NEP_FE_ENT_CAP && h.tether_cap <= NEP_ENT_LISTS_MAX_CAP) &&
-         (h.mission_mode == 0 ? h.log_cap == 0 : (h.mission_mode == NEP_MISSION_PER_AGENT || h.mission_mode == NEP_MISSION_FLEET_RUNS) && h.log_cap >= 0 && h.log_cap <= (1 << 20)) &&
+         (h.mission_mode == 0 ? h.log_cap == 0 : (h.mission_mode >= NEP_MISSION_PER_AGENT && h.mission_mode <= NEP_MISSION_FLEET_TOGETHER) && h.log_cap >= 0 && h.log_cap <= (1 << 20)) &&
          (h.timers == 0 || h.timers == 1);
 }
 

@@ -469,6 +469,14 @@ class DeviceFleetLoop(_Audited):
     the next goals on the device, inside the graph.  run() then stops when every scene's campaign is finished (it downloads the
     scenes' flags instead of the slots' arrival flags), and report() adds `mission` per scene: legs or runs reached / timed out /
     without a goal, mean leg time and length, the success rate.  Without missions nothing of this is allocated or launched.
+    MissionSpec(mode="together", script=mission.exchange_script(N)) flies the position exchange: the goals of
+    every new leg come from the table (uploaded per scene before the capture; rewind twins and resume upload the origin scenes'
+    rows), a run ends when every agent has been inside its goal's square once; report() adds `longest_leg_time` from the log.
+
+    effort=True | slack adds fleet_effort behind fleet_mission: per slot the jerk integral, the largest velocity,
+    acceleration and jerk component and the ticks that break v_max / a_max / j_max by more than the slack (True: 1e-6) over every
+    tick flown before arrival.  The records belong to the loop (d_effort) and travel in a checkpoint; report() adds jerk_sum_mean,
+    max_v, max_a, max_j, v_viol, a_viol, j_viol per scene.  With effort=False nothing of it is allocated or launched.
 
     recorder=R keeps the complete fleet state before each of the last R rounds in a device ring: fleet_snapshot_ring
     is the first call of the round, inside the graph, and entry r mod R holds the state before round r.  rewind(scene, round)
@@ -500,15 +508,18 @@ class DeviceFleetLoop(_Audited):
     before it resumes without)."""
 
     # the options a restored flight must share with the flight the snapshot was taken from
-    _MUST_MATCH = ("beam_width", "delta_t_states", "replan_every", "audit", "ring_cap", "tethers", "check", "ent_samples", "ent_cap", "moveback", "goal_gate", "fly_guess")
+    _MUST_MATCH = ("beam_width", "delta_t_states", "replan_every", "audit", "ring_cap", "tethers", "check", "ent_samples", "ent_cap", "moveback", "goal_gate", "fly_guess",
+                   "script", "effort")
 
     def __init__(self, scenes, beam_width=32, delta_t_states=6, replan_every=5, periods=None, phases=None, audit=False, graph=True,
                  goals=None, device=None, ring_cap=0, trace=False, tethers=False, check=True, ent_samples=3, missions=None, ent_cap=None,
-                 ent_lists0=None, recorder=None, search="beam", max_pops=300, moveback=None, goal_gate=False, fly_guess=False):
+                 ent_lists0=None, recorder=None, search="beam", max_pops=300, moveback=None, goal_gate=False, fly_guess=False, effort=False):
         import torch
         from . import mission as mission_mod
         self.torch = torch
         self.scenes = scenes
+        self.effort = mission_mod.effort_slack(effort)      # the slack, or None
+        self.script = mission_mod.script_rows(missions, len(scenes), scenes[0]["par"].num_agents)      # [S][N][G][3], or None
         self.fly_guess = check_fly_guess(fly_guess)
         self.goal_gate = check_goal_gate(goal_gate, search, scenes[0]["par"].drone_radius)      # the half side, or None
         if isinstance(moveback, dict):      # (a checkpoint's options carry it as plain data)
@@ -517,7 +528,8 @@ class DeviceFleetLoop(_Audited):
         self.astar = check_search(search, max_pops, tethers)
         self._opts = dict(beam_width=beam_width, delta_t_states=delta_t_states, replan_every=replan_every, audit=audit, ring_cap=ring_cap,
                           tethers=tethers, check=check, ent_samples=ent_samples, ent_cap=ent_cap, missions=missions, goals=goals,
-                          search=search, max_pops=max_pops, moveback=moveback, goal_gate=self.goal_gate, fly_guess=self.fly_guess)
+                          search=search, max_pops=max_pops, moveback=moveback, goal_gate=self.goal_gate, fly_guess=self.fly_guess,
+                          script=mission_mod.spec_plain(missions)[1], effort=self.effort)
         S = self.S = len(scenes)
         p = self.p = scenes[0]["par"]
         self.tethers, self.check, self.ent_samples = tethers, check, ent_samples
@@ -591,7 +603,10 @@ class DeviceFleetLoop(_Audited):
             if mission.uses_keepouts(missions):
                 for s, sc in enumerate(scenes):
                     be.fleet_mission_keepout(s, scene.keepout_polygons(sc))
+            if self.script is not None:      # (before any capture: the first upload allocates and fixes the capacity)
+                be.fleet_mission_script(self.script.reshape(S * N, -1, 3))
             be.fleet_mission_init(self.mission_cfg)
+        self.d_effort = be.new_effort() if self.effort is not None else None      # [slots] abi.EFFORT_DTYPE: the loop's, like d_gate_count
         self.recorder, self.d_ring = None, None
         if recorder is not None:      # (allocated here, outside any capture, for the state the handle has now: tethers and missions included)
             self.recorder = int(recorder)
@@ -634,6 +649,8 @@ class DeviceFleetLoop(_Audited):
             be.fleet_mission()
             if self.after_mission is not None:
                 self.after_mission(self)
+        if self.d_effort is not None:
+            be.fleet_effort(self.p.j_max, self.effort, self.d_effort)
         be.fleet_tick()
 
     def round(self):
@@ -681,12 +698,17 @@ class DeviceFleetLoop(_Audited):
             held = held.reshape(self.S, self.N)
         gate = self.d_gate_count.cpu().numpy() if self.d_gate_count is not None else None
         gcount = self.d_guess_count.cpu().numpy() if self.d_guess_count is not None else None
-        msum, goals_now = None, self.goals
+        msum, goals_now, longest = None, self.goals, None
+        from . import mission
         if self.missions is not None:
-            from . import mission
             ms = be.fleet_mission_state()
             msum = mission.summarize(ms, None, self.N, self.mission_cfg.mode)
             goals_now = ms["goal"].reshape(self.S, self.N, 3)      # (dist_to_goal_mean below: to the goals the agents have now)
+            recs, _ = be.fleet_mission_log()      # the longest leg (run) the log still holds, per scene: benchmark_multi_direct's longest time
+            per = len(recs) // self.S
+            longest = [max([float(r["t_end"] - r["t_issue"]) for o in range(s * per, (s + 1) * per) for r in recs[o] if r["outcome"] != abi.NEP_MISSION_NO_GOAL],
+                           default=None) for s in range(self.S)]
+        esum = mission.summarize_effort(self.effort_records(), self.N) if self.d_effort is not None else None
         out = []
         for s in range(self.S):
             c = cnt[s]
@@ -709,6 +731,9 @@ class DeviceFleetLoop(_Audited):
                 d["track_cap"] = int(((ever[s] & abi.NEP_ENT_TRACK_CAP) != 0).sum())
             if msum is not None:
                 d["mission"] = msum[s]
+                d["longest_leg_time"] = longest[s]
+            if esum is not None:
+                d.update(esum[s])
             if summ is not None:
                 d["audit"] = summ[s]
                 d["min_pair_dist"] = summ[s]["min_center_dist"]["value"] if summ[s]["min_center_dist"] else np.inf
@@ -716,13 +741,18 @@ class DeviceFleetLoop(_Audited):
             out.append(d)
         return out
 
+    def effort_records(self):
+        """[S*N] abi.EFFORT_DTYPE: every slot's effort record as it stands (blocking); effort= must be on"""
+        return self.d_effort.cpu().numpy().view(abi.EFFORT_DTYPE).copy()
+
     # ---- the recorder (DESIGN section 26) ---------------------------------------------------------------------------------------
     def _options(self):
         """the options a snapshot's flight and the flight restored from it must share, as plain data"""
         import dataclasses
         o = {k: self._opts[k] for k in self._MUST_MATCH}
         o["ent_cap"] = self.ent_cap
-        o["missions"] = dataclasses.asdict(self.missions) if self.missions is not None else None
+        from . import mission
+        o["missions"] = mission.spec_plain(self.missions)[0]      # (the script travels as o["script"])
         o["moveback"] = dataclasses.asdict(self.moveback) if self.moveback is not None else None
         o["masked"] = bool(self.masked)
         o["search"], o["max_pops"] = self._opts["search"], int(self._opts["max_pops"])
@@ -737,6 +767,10 @@ class DeviceFleetLoop(_Audited):
             o["goals"] = [o["goals"][s] for s in rows]
         if self.masked:
             o.update(periods=self.periods[rows], phases=self.phases[rows])
+        if self.script is not None:      # the origin scenes' rows, as the keep-outs are the origin scenes'
+            import dataclasses
+            o["missions"] = dataclasses.replace(o["missions"], script=self.script[rows])
+        del o["script"]
         o.update(kw)
         return DeviceFleetLoop(scenes, device=self.be.device, **o)
 
@@ -776,6 +810,8 @@ class DeviceFleetLoop(_Audited):
             data["gate_count"] = self.d_gate_count.cpu().numpy()
         if self.d_guess_count is not None:
             data["guess_count"] = self.d_guess_count.cpu().numpy()
+        if self.d_effort is not None:
+            data["effort"] = self.d_effort.cpu().numpy()
         with open(path, "wb") as f:
             np.savez(f, **data)
 
@@ -791,6 +827,11 @@ class DeviceFleetLoop(_Audited):
             aud = z["audit"] if "audit" in z.files else None
             gcnt = z["gate_count"] if "gate_count" in z.files else None
             fcnt = z["guess_count"] if "guess_count" in z.files else None
+            eff = z["effort"] if "effort" in z.files else None
+        opts.setdefault("script", None)        # (a file from before the options flew without them)
+        opts.setdefault("effort", None)
+        if "effort" in kw:
+            kw = dict(kw, effort=mission.effort_slack(kw["effort"]))
         opts.setdefault("moveback", None)      # (a file from before the option flew without it)
         opts.setdefault("goal_gate", None)     # (likewise)
         opts.setdefault("fly_guess", False)    # (likewise)
@@ -803,7 +844,7 @@ class DeviceFleetLoop(_Audited):
         for k in cls._MUST_MATCH:
             if k in kw and kw[k] != opts[k] and not (k == "ent_cap" and kw[k] == "auto"):
                 raise ValueError("checkpoint %s was flown with %s=%r, not %r" % (path, k, opts[k], kw[k]))
-        if "missions" in kw and (None if kw["missions"] is None else __import__("dataclasses").asdict(kw["missions"])) != opts["missions"]:
+        if "missions" in kw and (mission.spec_plain(kw["missions"])[0] != opts["missions"] or mission.spec_plain(kw["missions"])[1] != opts["script"]):
             raise ValueError("checkpoint %s was flown with other missions" % path)
         if scenes[0]["par"].num_agents != opts["N"] or len(scenes[0]["statics"]) != opts["n_statics"]:
             raise ValueError("checkpoint %s was flown with %d agents and %d statics per scene" % (path, opts["N"], opts["n_statics"]))
@@ -814,7 +855,8 @@ class DeviceFleetLoop(_Audited):
                 raise ValueError("checkpoint %s was flown with %s=%r, not %r" % (path, k, opts.get(k, dflt), kw[k]))
         o = {k: opts[k] for k in cls._MUST_MATCH}
         o["search"], o["max_pops"] = opts.get("search", "beam"), opts.get("max_pops", 300)
-        o["missions"] = mission.MissionSpec(**opts["missions"]) if opts["missions"] is not None else None
+        o["missions"] = mission.MissionSpec(**opts["missions"], script=opts["script"]) if opts["missions"] is not None else None
+        del o["script"]
         o.update({k: v for k, v in kw.items() if k not in o})
         lp = cls(scenes, **o)
         try:
@@ -825,6 +867,8 @@ class DeviceFleetLoop(_Audited):
                 lp.d_gate_count.copy_(lp.torch.from_numpy(gcnt))
             if fcnt is not None and lp.d_guess_count is not None:
                 lp.d_guess_count.copy_(lp.torch.from_numpy(fcnt))
+            if eff is not None and lp.d_effort is not None:
+                lp.d_effort.copy_(lp.torch.from_numpy(eff))
         except Exception:
             lp.close()
             raise

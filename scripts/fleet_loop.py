@@ -60,7 +60,9 @@ def main():
     ap.add_argument("--no-proof", action="store_true", help="with --tethers: debug option fleet_ent_proof 0 (every other agent walked at every tick)")
     ap.add_argument("--ent-cap", metavar="K", help="with --tethers: the tracked states in the list form of K entries per slot (DESIGN section 24) instead of the 40-entry record; 'auto' = 2 (agents + obstacles)")
     ap.add_argument("--fe-big-records", type=int, default=0, metavar="R", help="with --tethers: records in the front end's pool of big entangle-state records (nep_batch_set_fe_ent_big_records; 0: the default, 4 per slot)")
-    ap.add_argument("--missions", choices=("agent", "runs"), help="a campaign (DESIGN section 23): per-agent successive goals (NeptuneRos::autoCMD) or fleet-wide runs (benchmark_mtlp.py), drawn on the device inside the graph; the flight stops when every scene's campaign is over")
+    ap.add_argument("--missions", choices=("agent", "runs", "together"), help="a campaign (DESIGN section 23): per-agent successive goals (NeptuneRos::autoCMD), fleet-wide runs (benchmark_mtlp.py) or the position-exchange driver's runs (auto_commands_together.py, DESIGN section 35), drawn on the device inside the graph or taken from --script; the flight stops when every scene's campaign is over")
+    ap.add_argument("--script", metavar="exchange[:RADIUS]|PATH.npy", help="with --missions: the goals of every new leg from a table instead of the generator (DESIGN section 35). exchange: auto_commands_together.py's two lists on a circle of RADIUS m (default 10), antipodes in turn, and the first leg onto the circle; PATH.npy: an array [agents][G][3] or [scenes][agents][G][3]")
+    ap.add_argument("--effort", nargs="?", const="1e-6", metavar="SLACK", help="the effort record of every flown tick (DESIGN section 35): mean jerk integral, largest velocity / acceleration / jerk component, ticks beyond v_max / a_max / j_max by more than SLACK (default 1e-6)")
     ap.add_argument("--goals", type=int, default=2, metavar="G", help="with --missions: legs per agent / runs per scene")
     ap.add_argument("--moveback", nargs="?", const="ref", metavar="RADIUS|ref", help="the reference's move-back strategy (DESIGN section 32): an agent with a new goal first plans towards its own base, until it is within RADIUS m of it (ref, the default: 6.33 - (agents - 4) * 0.33) or --moveback-timeout has passed")
     ap.add_argument("--moveback-timeout", type=float, default=10.0, metavar="S", help="with --moveback: seconds of simulated time after which the goal is released anyway")
@@ -87,7 +89,18 @@ def main():
             kw.update(ent_cap="auto" if a.ent_cap == "auto" else int(a.ent_cap))
     if a.missions:
         from neptune_amd import mission
-        kw.update(missions=mission.MissionSpec(a.missions, goals=a.goals, seed=a.seed0 + 1))
+        script = None
+        if a.script:
+            if a.script.split(":")[0] == "exchange":
+                script = mission.exchange_script(a.agents, float(a.script.split(":")[1]) if ":" in a.script else 10.0, scenes[0]["par"].goal_height)
+                kw.update(goals=[script[:, -1] for _ in scenes])      # the first leg: onto the circle, where the driver's vehicles start
+            else:
+                script = np.load(a.script, allow_pickle=False)
+        kw.update(missions=mission.MissionSpec(a.missions, goals=a.goals, seed=a.seed0 + 1, script=script))
+    elif a.script:
+        ap.error("--script gives the goals of a campaign: only with --missions")
+    if a.effort:
+        kw.update(effort=float(a.effort))
     mb = None
     if a.moveback:
         from neptune_amd import mission
@@ -188,6 +201,17 @@ def main():
         print("missions (%s, %d goals): legs issued %d, reached %d, timed out %d, no goal %d; share reached %s; scenes finished %d of %d"
               % (a.missions, a.goals, sum(m["legs_issued"] for m in ms), sum(m["legs_reached"] for m in ms), sum(m["legs_timed_out"] for m in ms),
                  sum(m["no_goal"] for m in ms), "%.3f" % (sum(m["legs_reached"] for m in ms) / ended) if ended else "-", sum(m["finished"] for m in ms), len(ms)))
+        if a.missions != "agent":
+            lt = [r["longest_leg_time"] for r in rep if r["longest_leg_time"] is not None]
+            print("runs: %d ok, %d failed; longest run %s s; mean leg time %s s, mean leg length %s m"
+                  % (sum(m["runs_succeeded"] for m in ms), sum(m["runs_failed"] for m in ms), "%.2f" % max(lt) if lt else "-",
+                     "%.2f" % np.mean([m["mean_leg_time"] for m in ms if m["mean_leg_time"] is not None]) if ended else "-",
+                     "%.2f" % np.mean([m["mean_leg_length"] for m in ms if m["mean_leg_length"] is not None]) if ended else "-"))
+    if a.effort:
+        p0 = scenes[0]["par"]
+        print("effort (slack %g): mean jerk integral per agent %.3f; max |v| %.9f of %.3f, max |a| %.9f of %.3f, max |j| %.9f of %.3f; ticks beyond the limits: v %d, a %d, j %d of %d"
+              % (float(a.effort), np.mean([r["jerk_sum_mean"] for r in rep]), max(r["max_v"] for r in rep), p0.v_max, max(r["max_a"] for r in rep), p0.a_max,
+                 max(r["max_j"] for r in rep), p0.j_max, sum(r["v_viol"] for r in rep), sum(r["a_viol"] for r in rep), sum(r["j_viol"] for r in rep), sum(r["effort_ticks"] for r in rep)))
     print("wall time per round (rounds 3..%d, %s, %s downloaded every round): %.3f ms = %.1f rounds/s, %.0f scene-rounds/s"
           % (n, "eager" if a.eager else "one graph", "the scenes' finished flags" if a.missions else "arrival flags", per_round * 1e3, 1.0 / per_round, a.scenes / per_round))
     if a.audit:
