@@ -1150,18 +1150,10 @@ int use_blocks(ProblemSet& ps, const nep_batch* h, const void* d_blocks, int n_b
   return 0;
 }
 
-bool fe_cfg_ok(const nep_fe_cfg* cfg) {
-  return cfg->num_samples >= 2 && cfg->num_samples <= NEP_FE_MAX_SAMPLES && cfg->beam_width >= 1 && cfg->beam_width <= NEP_FE_MAX_BEAM &&
+// (beam: with the beam's width, which the best-first search does not read)
+bool fe_cfg_ok(const nep_fe_cfg* cfg, bool beam = true) {
+  return cfg->num_samples >= 2 && cfg->num_samples <= NEP_FE_MAX_SAMPLES && (!beam || (cfg->beam_width >= 1 && cfg->beam_width <= NEP_FE_MAX_BEAM)) &&
          cfg->voxel_size > 0.0 && cfg->j_max > 0.0;
-}
-// the searches of every slot against the hulls ps points at (ea: the entangle-aware front end's arguments, or null)
-int run_frontend(nep_batch* h, const ProblemSet& ps, const nep_fe_cfg& cfg, const nep_fe_start* d_start, nep_guess* d_guess, nep_fe_result* d_result,
-                 const FeEntArgs* ea, void* stream) {
-  Engine& E = h->eng;
-  launch_frontend(h->slots, E.sp, ps, cfg, d_start, d_guess, d_result, ea, (hipStream_t)stream, E.lpt ? E.d_fe_order.p : nullptr, E.fe_history, E.d_fe_act.p);
-  E.fe_history = true;
-  HIPCHK(hipGetLastError());
-  return 0;
 }
 }  // namespace
 
@@ -1198,28 +1190,6 @@ int nep_batch_replan_hulls(nep_batch_t* h, const void* d_blocks, int32_t n_block
   return h->eng.run(nullptr, 0, ps, (hipStream_t)stream);
 }
 
-// hulls -> front-end beam search; the guesses land where nep_batch_replan reads them
-int nep_batch_frontend(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_traj_rec* d_committed, const nep_fe_start* d_start,
-                       nep_guess* d_guess, nep_fe_result* d_result, void* stream) {
-  if (!h || !cfg || !d_committed || !d_start || !d_guess) return fail(NEP_E_ARG, "null argument");
-  if (!fe_cfg_ok(cfg)) return fail(NEP_E_ARG, "bad front-end configuration");
-  const ProblemSet ps = round_set(h);
-  h->fe_committed = d_committed;
-  launch_hulls_ts(d_committed, h->cfg.n_scenes, h->cfg.num_agents, &d_start->t_start, (long)sizeof(nep_fe_start), h->eng.sp, ps, (hipStream_t)stream, grouped_hulls(h->eng.sp, h->cfg.n_scenes, h->cfg.num_agents));
-  return run_frontend(h, ps, *cfg, d_start, d_guess, d_result, nullptr, stream);
-}
-
-// the same against all-gathered hull blocks (multi-GPU rounds: nep_batch_hulls -> all-gather -> this -> nep_batch_replan_hulls)
-int nep_batch_frontend_hulls(nep_batch_t* h, const nep_fe_cfg* cfg, const void* d_blocks, int32_t n_blocks, const nep_fe_start* d_start,
-                             nep_guess* d_guess, nep_fe_result* d_result, void* stream) {
-  if (!h || !cfg || !d_blocks || !d_start || !d_guess) return fail(NEP_E_ARG, "null argument");
-  ProblemSet ps = round_set(h);
-  if (int e = use_blocks(ps, h, d_blocks, n_blocks)) return e;
-  if (!fe_cfg_ok(cfg)) return fail(NEP_E_ARG, "bad front-end configuration");
-  h->fe_committed = nullptr;
-  return run_frontend(h, ps, *cfg, d_start, d_guess, d_result, nullptr, stream);
-}
-
 // ---- the reference's best-first search (fe_astar.h) ----
 int nep_batch_set_fe_astar(nep_batch_t* h, int32_t max_pops, int32_t max_nodes, const int32_t* order, int32_t n_order) {
   if (!h) return fail(NEP_E_ARG, "null handle");
@@ -1252,40 +1222,12 @@ int nep_batch_set_fe_astar(nep_batch_t* h, int32_t max_pops, int32_t max_nodes, 
   return 0;
 }
 
-// what both best-first entry points ask of their arguments, the handle and nep_batch_set_fe_astar's state, in the order each of them
-// asked it (who: the entry point, for the error texts; ent: the one with the entangle check)
-static int fe_astar_check(const nep_batch_t* h, const nep_fe_cfg* cfg, const void* d_committed, const void* d_start, const void* d_guess, const std::string& who, bool ent) {
-  if (!h || !cfg || !d_committed || !d_start || !d_guess) return fail(NEP_E_ARG, "null argument");
-  const Engine& E = h->eng;
-  if (ent) {
-    if (!h->cfg.enable_entangle) return fail(NEP_E_STATE, who + " needs a handle created with enable_entangle");
-    if (h->cfg.n_local != h->cfg.num_agents) return fail(NEP_E_STATE, who + " runs on an unsharded handle (n_local == num_agents)");
-    if (!cfg->enable_entangle) return fail(NEP_E_ARG, who + ": enable_entangle must be set in the front-end configuration (without the check: nep_batch_frontend_astar)");
-  }
-  if (!E.as_ready) return fail(NEP_E_STATE, who + ": call nep_batch_set_fe_astar first (it allocates the searches' pools)");
-  if (!ent && cfg->enable_entangle) return fail(NEP_E_ARG, who + ": the best-first search has no entangle check (enable_entangle must be 0)");
-  if (!(cfg->num_samples >= 2 && cfg->num_samples <= NEP_FE_MAX_SAMPLES && cfg->voxel_size > 0.0 && cfg->j_max > 0.0)) return fail(NEP_E_ARG, "bad front-end configuration");
-  if (E.as_n_order && cfg->num_samples * cfg->num_samples != E.as_n_order) return fail(NEP_E_ARG, who + ": num_samples^2 differs from the n_order of nep_batch_set_fe_astar");
-  return 0;
-}
 // budget, order and pools as nep_batch_set_fe_astar left them
 static FeAstarArgs fe_astar_args(const Engine& E) {
   FeAstarArgs aa{};
   aa.max_pops = E.as_max_pops; aa.pool = E.as_pool; aa.tab_cap = E.as_tab; aa.order = E.as_n_order ? E.d_as_order.p : nullptr;
   aa.nodes = E.d_as_nodes.p; aa.heap = E.d_as_heap.p; aa.tab_key = E.d_as_key.p; aa.tab_val = E.d_as_val.p;
   return aa;
-}
-
-int nep_batch_frontend_astar(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_traj_rec* d_committed, const nep_fe_start* d_start,
-                             nep_guess* d_guess, nep_fe_result* d_result, void* stream) {
-  if (int e = fe_astar_check(h, cfg, d_committed, d_start, d_guess, "nep_batch_frontend_astar", false)) return e;
-  Engine& E = h->eng;
-  const ProblemSet ps = round_set(h);
-  h->fe_committed = d_committed;
-  launch_hulls_ts(d_committed, h->cfg.n_scenes, h->cfg.num_agents, &d_start->t_start, (long)sizeof(nep_fe_start), E.sp, ps, (hipStream_t)stream, grouped_hulls(E.sp, h->cfg.n_scenes, h->cfg.num_agents));
-  launch_frontend_astar(h->slots, E.sp, ps, *cfg, fe_astar_args(E), nullptr, nullptr, d_start, d_guess, d_result, (hipStream_t)stream, E.d_fe_act.p);
-  HIPCHK(hipGetLastError());
-  return 0;
 }
 
 // ---- the reference's move_when_goal_occupied gate (goal_gate.h): between any front-end call and nep_batch_replan ----
@@ -1375,15 +1317,24 @@ int ent_ready(nep_batch* h, const char* no_reps = "entangle check with static ob
   if (!E.d_srep.p) { if (int e = E.d_srep.ensure(4)) return e; if (int e = E.d_slong.ensure(2)) return e; }
   return 0;
 }
+// what the entangle check reads besides the trajectories' samples, and the threads' working records (beam_width > 0: the beam's node states too)
+int ent_common(nep_batch* h, int ns, int beam_width, FeEntArgs& ea) {
+  Engine& E = h->eng;
+  if (int e = E.d_fe_work.ensure((size_t)std::max(h->slots * 256, h->cfg.n_scenes * h->cfg.num_agents))) return e;
+  if (beam_width > 0) { if (int e = E.d_fe_nodes.ensure((size_t)h->slots * (h->cfg.num_pol + 1) * beam_width)) return e; }
+  ea.srep = E.d_srep.p; ea.slong = E.d_slong.p; ea.nodes = E.d_fe_nodes.p; ea.work = E.d_fe_work.p; ea.ns = ns;
+  ea.fast_cap = E.fe_fast_cap; ea.fast_add = E.fe_fast_add; ea.fast_bend = E.fe_fast_bend;
+  return 0;
+}
+// ... with the samples and presence flags of the records' trajectories (ent_sample_kernel, which zeroes the re-check's pool on its way)
 int ent_prepare(nep_batch* h, int ns, int beam_width, const nep_traj_rec* d_recs, const double* ts0, long ts_scene_stride, FeEntArgs& ea, hipStream_t st) {
   Engine& E = h->eng;
   const int N = h->cfg.num_agents, S = h->cfg.n_scenes, np = h->cfg.num_pol;
   if (ns < 1 || ns > 8) return fail(NEP_E_ARG, "ent_samples out of range");
   if (int e = ent_ready(h)) return e;
+  if (int e = ent_common(h, ns, beam_width, ea)) return e;
   if (int e = E.d_sampled.ensure((size_t)S * N * np * (ns + 1) * 2)) return e;
   if (int e = E.d_present.ensure((size_t)S * N)) return e;
-  if (int e = E.d_fe_work.ensure((size_t)std::max(h->slots * 256, S * N))) return e;
-  if (beam_width > 0) { if (int e = E.d_fe_nodes.ensure((size_t)h->slots * (np + 1) * beam_width)) return e; }
   {   // the re-check's big records (three times the search's bound: entangleCheckGivenPwp); a sixteenth of the search's pool, at least 256
     const long n_rec = std::max(256L, (E.fe_big_records > 0 ? E.fe_big_records : std::max(4096L, 4L * h->slots)) / 16);
     const size_t rec = (size_t)ent_big_rec_bytes(N, E.sp.n_static, 3);
@@ -1392,9 +1343,14 @@ int ent_prepare(nep_batch* h, int ns, int beam_width, const nep_traj_rec* d_recs
     ea.big_check = EntBigPool{E.d_fe_big_check.p, E.d_fe_big_check_count.p, (int)n_rec, (int)rec, ent_big_cap(N, E.sp.n_static, 3), ent_big_add_lim(N, E.sp.n_static, 3)};
   }
   launch_ent_sample(d_recs, S, N, ts0, ts_scene_stride, np, ns, E.sp.T_span, E.d_sampled.p, E.d_present.p, st, E.d_fe_big_check_count.p);
-  ea.sampled = E.d_sampled.p; ea.present = E.d_present.p; ea.srep = E.d_srep.p; ea.slong = E.d_slong.p;
-  ea.nodes = E.d_fe_nodes.p; ea.work = E.d_fe_work.p; ea.ns = ns; ea.init = nullptr; ea.case_out = nullptr; ea.saved = nullptr; ea.saved_arc = nullptr;
-  ea.fast_cap = E.fe_fast_cap; ea.fast_add = E.fe_fast_add; ea.fast_bend = E.fe_fast_bend;
+  ea.sampled = E.d_sampled.p; ea.present = E.d_present.p;
+  return 0;
+}
+// the packed per-(agent, interval) records of the entangle check (ent_pack_kernel fills them), for ea.ns samples per interval
+int ent_packed(nep_batch* h, FeEntArgs& ea) {
+  ea.pk_stride = 2 + 2 * kBend + 2 * (ea.ns + 1);      // (kEntPkHead + the samples: an even number of doubles)
+  if (int e = h->eng.d_fe_packed.ensure((size_t)h->cfg.n_scenes * h->cfg.num_agents * h->cfg.num_pol * ea.pk_stride)) return e;
+  ea.packed = h->eng.d_fe_packed.p;
   return 0;
 }
 }  // namespace
@@ -1439,21 +1395,18 @@ static int fe_ent_scratch(nep_batch* h, const nep_fe_cfg& cfg, FeEntArgs& ea) {
     if (int e = E.d_fe_xpool.ensure((size_t)h->slots * xw)) return e;
     ea.xpool = E.d_fe_xpool.p; ea.xpool_stride = (int)xw;
   }
-  ea.pk_stride = 2 + 2 * kBend + 2 * (ea.ns + 1);      // (kEntPkHead + the samples: an even number of doubles)
-  if (int e = E.d_fe_packed.ensure((size_t)h->cfg.n_scenes * h->cfg.num_agents * h->cfg.num_pol * ea.pk_stride)) return e;
-  ea.packed = E.d_fe_packed.p;
+  if (int e = ent_packed(h, ea)) return e;
   // the pool of big records: states beyond the fixed record's capacities (rare: a handful of children in a few of 8 192 config-5
   // searches), sized by the reference's own bound on a list (num_agents + statics)
   const int N = h->cfg.num_agents, S = E.sp.n_static;
   const long n_rec = E.fe_big_records > 0 ? E.fe_big_records : std::max(4096L, 4L * h->slots);
   const size_t rec = (size_t)ent_big_rec_bytes(N, S);
   if (int e = E.d_fe_big.ensure(rec * (size_t)n_rec)) return e;
-  if (int e = E.d_fe_big_count.ensure(2 + 256)) return e;      // [0] records claimed, [1] searches listed for the big-record instantiation, [2..] the list
-  ea.redo_count = E.d_fe_big_count.p + 1; ea.redo_list = E.d_fe_big_count.p + 2; ea.redo_cap = 256;
+  if (int e = E.d_fe_big_count.ensure(2 + kFeRedoCap)) return e;      // [0] records claimed, [1] searches listed for the big-record instantiation, [2..] the list
+  ea.redo_count = E.d_fe_big_count.p + 1; ea.redo_list = E.d_fe_big_count.p + 2; ea.redo_cap = kFeRedoCap;
   if (int e = E.d_fe_big_beta.ensure((size_t)ea.redo_cap * 256 * 120)) return e;      // (kEntBigLdsCap betas per thread of the big-record instantiation: 63 MB)
   ea.big_beta = E.d_fe_big_beta.p;
   ea.big = EntBigPool{E.d_fe_big.p, E.d_fe_big_count.p, (int)n_rec, (int)rec, ent_big_cap(N, S), ent_big_add_lim(N, S)};
-  ea.fast_cap = E.fe_fast_cap; ea.fast_add = E.fe_fast_add; ea.fast_bend = E.fe_fast_bend;
   return 0;
 }
 int nep_batch_set_fe_ent_big_records(nep_batch_t* h, int64_t records) {
@@ -1467,68 +1420,114 @@ int nep_batch_set_fe_ent_fast_caps(nep_batch_t* h, int32_t list_cap, int32_t add
   return 0;
 }
 
+// ---- the six front-end entry points: one call, told which search, whether the entangle check is on and where its hulls come from ----
+namespace {
+constexpr bool kBeam = false, kBestFirst = true, kPlain = false, kEnt = true, kRecords = false, kBlocks = true;
+struct FeCall {
+  const char* who; bool best_first, ent, blocks;      // the entry point (for the error texts); kBeam | kBestFirst; kPlain | kEnt (the check); kRecords | kBlocks (where the hulls come from)
+  const nep_fe_cfg* cfg;
+  const nep_traj_rec* d_committed; const void* d_blocks; int n_blocks;      // the records (!blocks) or the gathered blocks
+  const nep_fe_start* d_start; const nep_fe_ent_state* d_ent_init; nep_guess* d_guess; nep_fe_result* d_result; int32_t* d_case_out; void* stream;
+};
+// what the entry point asks of its configuration, the handle and the setters' state, in the order it always asked
+int fe_call_checks(nep_batch* h, const FeCall& c) {
+  const Engine& E = h->eng; const nep_fe_cfg* cfg = c.cfg; const std::string who = c.who;
+  const bool unsharded = h->cfg.n_local == h->cfg.num_agents;
+  if (!c.best_first) {
+    if (!fe_cfg_ok(cfg)) return fail(NEP_E_ARG, "bad front-end configuration");
+    if (!c.ent) return 0;
+    if (!cfg->enable_entangle || !h->cfg.enable_entangle) return fail(NEP_E_STATE, who + " needs enable_entangle in the front-end configuration and in the handle");
+    if (!c.blocks) return unsharded ? 0 : fail(NEP_E_STATE, "the entangle-aware front end runs on an unsharded handle (n_local == num_agents)");
+    if (cfg->ent_samples != h->ent_ns) return fail(NEP_E_ARG, "ent_samples differs from what the hull blocks were made with (nep_batch_set_ent_samples)");
+    return ent_ready(h);      // (ahead of everything the call changes, as this entry point always had it)
+  }
+  if (c.ent) {
+    if (!h->cfg.enable_entangle) return fail(NEP_E_STATE, who + " needs a handle created with enable_entangle");
+    if (!unsharded) return fail(NEP_E_STATE, who + " runs on an unsharded handle (n_local == num_agents)");
+    if (!cfg->enable_entangle) return fail(NEP_E_ARG, who + ": enable_entangle must be set in the front-end configuration (without the check: nep_batch_frontend_astar)");
+  }
+  if (!E.as_ready) return fail(NEP_E_STATE, who + ": call nep_batch_set_fe_astar first (it allocates the searches' pools)");
+  if (!c.ent && cfg->enable_entangle) return fail(NEP_E_ARG, who + ": the best-first search has no entangle check (enable_entangle must be 0)");
+  if (!fe_cfg_ok(cfg, false)) return fail(NEP_E_ARG, "bad front-end configuration");
+  if (E.as_n_order && cfg->num_samples * cfg->num_samples != E.as_n_order) return fail(NEP_E_ARG, who + ": num_samples^2 differs from the n_order of nep_batch_set_fe_astar");
+  return 0;
+}
+// hulls (from the records) -> the searches of every slot; the guesses land where nep_batch_replan reads them.  The
+// launches are plan_frontend's (launch_plan.h); every buffer is sized here, at the call (an entry point's first call allocates: eager)
+int frontend_call(nep_batch* h, const FeCall& c) {
+  if (!h || !c.cfg || !(c.blocks ? c.d_blocks : (const void*)c.d_committed) || !c.d_start || !c.d_guess) return fail(NEP_E_ARG, "null argument");
+  Engine& E = h->eng;
+  hipStream_t st = (hipStream_t)c.stream;
+  ProblemSet ps = round_set(h);
+  if (c.blocks) { if (int e = use_blocks(ps, h, c.d_blocks, c.n_blocks)) return e; }      // (the _hulls calls: ahead of the configuration's checks)
+  if (int e = fe_call_checks(h, c)) return e;
+  // the facts, the plan (launch_plan.h), and the plan followed: hulls, the entangle check's arguments and scratch, the searches
+  FrontendFacts f;
+  f.num_agents = E.sp.num_agents; f.n_static = E.sp.n_static; f.num_pol = E.sp.num_pol; f.hull_mode = E.sp.hull_mode;
+  f.slots = h->slots; f.n_scenes = h->cfg.n_scenes; f.best_first = c.best_first; f.ent = c.ent;
+  f.beam_width = c.cfg->beam_width; f.num_samples = c.cfg->num_samples; f.have_recs = !c.blocks; f.active = ps.active && E.d_fe_act.p;
+  f.lpt = E.lpt && E.d_fe_order.p; f.order_key_ok = ps.fe_order_key != nullptr; f.fe_history = E.fe_history;
+  f.big_beta = c.ent && !c.best_first;      // (fe_ent_scratch below sizes the betas' memory or fails the call)
+  f.fe_three = g_debug.fe_three; f.fe_xcd = g_debug.fe_xcd;      // (A/B, nep_debug_set_global_option)
+  const FrontendPlan plan = plan_frontend(f);
+  h->fe_committed = c.blocks ? nullptr : c.d_committed;
+  if (plan.hulls) launch_hulls_ts(c.d_committed, h->cfg.n_scenes, h->cfg.num_agents, &c.d_start->t_start, (long)sizeof(nep_fe_start), E.sp, ps, st, plan.grouped_hulls);
+  // the entangle check's arguments: the trajectories' samples and presence flags are made here from the records, or lie in the blocks
+  FeEntArgs ea{}; FeAstarEntArgs xa{};
+  if (c.ent) {
+    const int beam_width = c.best_first ? 0 : c.cfg->beam_width;
+    if (plan.ent_sample) { if (int e = ent_prepare(h, c.cfg->ent_samples, beam_width, c.d_committed, &c.d_start->t_start, (long)sizeof(nep_fe_start) * E.sp.n_local, ea, st)) return e; }
+    else {
+      const HullBlock b = block_of(h);
+      if (int e = ent_common(h, h->ent_ns, beam_width, ea)) return e;
+      ea.sampled = (const double*)((const char*)c.d_blocks + b.samp); ea.present = (const int*)((const char*)c.d_blocks + b.present);
+    }
+    ea.init = c.d_ent_init; ea.case_out = c.d_case_out;
+    // the searches' scratch: the beam's; the best-first search's packed records, voxel keys' third words and node states
+    if (!c.best_first) { if (int e = fe_ent_scratch(h, *c.cfg, ea)) return e; }
+    else {
+      if (int e = ent_packed(h, ea)) return e;
+      if (int e = E.d_as_iz.ensure((size_t)h->slots * E.as_tab)) return e;
+      if (int e = E.d_as_states.ensure((size_t)h->slots * E.as_pool * NEP_FE_ASTAR_ENT_NODE_BYTES)) return e;
+      xa = FeAstarEntArgs{E.d_as_iz.p, E.d_as_states.p};
+    }
+  }
+  launch_frontend(plan, h->slots, h->cfg.n_scenes, E.sp, ps, *c.cfg, c.best_first ? fe_astar_args(E) : FeAstarArgs{}, xa, ea, c.d_start, c.d_guess, c.d_result, st, E.d_fe_order.p, E.d_fe_act.p);
+  E.fe_history = plan.have_history;
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+}  // namespace
+
+int nep_batch_frontend(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_traj_rec* d_committed, const nep_fe_start* d_start,
+                       nep_guess* d_guess, nep_fe_result* d_result, void* stream) {
+  return frontend_call(h, FeCall{"nep_batch_frontend", kBeam, kPlain, kRecords, cfg, d_committed, nullptr, 0, d_start, nullptr, d_guess, d_result, nullptr, stream});
+}
+// the same against all-gathered hull blocks (multi-GPU rounds: nep_batch_hulls -> all-gather -> this -> nep_batch_replan_hulls)
+int nep_batch_frontend_hulls(nep_batch_t* h, const nep_fe_cfg* cfg, const void* d_blocks, int32_t n_blocks, const nep_fe_start* d_start,
+                             nep_guess* d_guess, nep_fe_result* d_result, void* stream) {
+  return frontend_call(h, FeCall{"nep_batch_frontend_hulls", kBeam, kPlain, kBlocks, cfg, nullptr, d_blocks, n_blocks, d_start, nullptr, d_guess, d_result, nullptr, stream});
+}
+// the front end with per-node entangle states: guesses and the dense case block of nep_batch_replan
 int nep_batch_frontend_ent(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_traj_rec* d_committed, const nep_fe_start* d_start,
                            const nep_fe_ent_state* d_ent_init, nep_guess* d_guess, nep_fe_result* d_result, int32_t* d_case_out, void* stream) {
-  if (!h || !cfg || !d_committed || !d_start || !d_guess) return fail(NEP_E_ARG, "null argument");
-  if (!fe_cfg_ok(cfg)) return fail(NEP_E_ARG, "bad front-end configuration");
-  if (!cfg->enable_entangle || !h->cfg.enable_entangle) return fail(NEP_E_STATE, "nep_batch_frontend_ent needs enable_entangle in the front-end configuration and in the handle");
-  if (h->cfg.n_local != h->cfg.num_agents) return fail(NEP_E_STATE, "the entangle-aware front end runs on an unsharded handle (n_local == num_agents)");
-  Engine& E = h->eng;
-  const ProblemSet ps = round_set(h);
-  h->fe_committed = d_committed;
-  launch_hulls_ts(d_committed, h->cfg.n_scenes, h->cfg.num_agents, &d_start->t_start, (long)sizeof(nep_fe_start), E.sp, ps, (hipStream_t)stream, grouped_hulls(E.sp, h->cfg.n_scenes, h->cfg.num_agents));
-  FeEntArgs ea{};
-  if (int e = ent_prepare(h, cfg->ent_samples, cfg->beam_width, d_committed, &d_start->t_start, (long)sizeof(nep_fe_start) * E.sp.n_local, ea, (hipStream_t)stream)) return e;
-  ea.init = d_ent_init; ea.case_out = d_case_out;
-  if (int e = fe_ent_scratch(h, *cfg, ea)) return e;
-  return run_frontend(h, ps, *cfg, d_start, d_guess, d_result, &ea, stream);
+  return frontend_call(h, FeCall{"nep_batch_frontend_ent", kBeam, kEnt, kRecords, cfg, d_committed, nullptr, 0, d_start, d_ent_init, d_guess, d_result, d_case_out, stream});
 }
-
 // the same against all-gathered hull blocks (which carry the samples and the presence flags of every agent's trajectory when the
 // handle was created with enable_entangle: nep_batch_hulls): the entangle-aware front end of a sharded handle
 int nep_batch_frontend_ent_hulls(nep_batch_t* h, const nep_fe_cfg* cfg, const void* d_blocks, int32_t n_blocks, const nep_fe_start* d_start,
                                  const nep_fe_ent_state* d_ent_init, nep_guess* d_guess, nep_fe_result* d_result, int32_t* d_case_out, void* stream) {
-  if (!h || !cfg || !d_blocks || !d_start || !d_guess) return fail(NEP_E_ARG, "null argument");
-  ProblemSet ps = round_set(h);
-  if (int e = use_blocks(ps, h, d_blocks, n_blocks)) return e;
-  if (!fe_cfg_ok(cfg)) return fail(NEP_E_ARG, "bad front-end configuration");
-  if (!cfg->enable_entangle || !h->cfg.enable_entangle) return fail(NEP_E_STATE, "nep_batch_frontend_ent_hulls needs enable_entangle in the front-end configuration and in the handle");
-  if (cfg->ent_samples != h->ent_ns) return fail(NEP_E_ARG, "ent_samples differs from what the hull blocks were made with (nep_batch_set_ent_samples)");
-  if (int e = ent_ready(h)) return e;
-  Engine& E = h->eng;
-  const HullBlock b = block_of(h);
-  h->fe_committed = nullptr;
-  if (int e = E.d_fe_work.ensure((size_t)std::max(h->slots * 256, h->cfg.n_scenes * h->cfg.num_agents))) return e;
-  if (int e = E.d_fe_nodes.ensure((size_t)h->slots * (h->cfg.num_pol + 1) * cfg->beam_width)) return e;
-  FeEntArgs ea{};
-  ea.sampled = (const double*)((const char*)d_blocks + b.samp); ea.present = (const int*)((const char*)d_blocks + b.present);
-  ea.srep = E.d_srep.p; ea.slong = E.d_slong.p; ea.nodes = E.d_fe_nodes.p; ea.work = E.d_fe_work.p; ea.ns = h->ent_ns;
-  ea.init = d_ent_init; ea.case_out = d_case_out;
-  if (int e = fe_ent_scratch(h, *cfg, ea)) return e;
-  return run_frontend(h, ps, *cfg, d_start, d_guess, d_result, &ea, stream);
+  return frontend_call(h, FeCall{"nep_batch_frontend_ent_hulls", kBeam, kEnt, kBlocks, cfg, nullptr, d_blocks, n_blocks, d_start, d_ent_init, d_guess, d_result, d_case_out, stream});
 }
-
-// the reference's best-first search with the entangle check (fe_astar.h): nep_batch_frontend_ent's inputs, nep_batch_set_fe_astar's
-// budget, order and pools, plus a state per node and the voxel key's third word (allocated here, at the first call: eager)
+// the reference's best-first search (fe_astar.h) in place of the beam: nep_batch_set_fe_astar's budget, order and pools
+int nep_batch_frontend_astar(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_traj_rec* d_committed, const nep_fe_start* d_start,
+                             nep_guess* d_guess, nep_fe_result* d_result, void* stream) {
+  return frontend_call(h, FeCall{"nep_batch_frontend_astar", kBestFirst, kPlain, kRecords, cfg, d_committed, nullptr, 0, d_start, nullptr, d_guess, d_result, nullptr, stream});
+}
+// ... with the entangle check: nep_batch_frontend_ent's inputs, plus a state per node and the voxel key's third word
 int nep_batch_frontend_astar_ent(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_traj_rec* d_committed, const nep_fe_start* d_start,
                                  const nep_fe_ent_state* d_ent_init, nep_guess* d_guess, nep_fe_result* d_result, int32_t* d_case_out, void* stream) {
-  if (int e = fe_astar_check(h, cfg, d_committed, d_start, d_guess, "nep_batch_frontend_astar_ent", true)) return e;
-  Engine& E = h->eng;
-  const ProblemSet ps = round_set(h);
-  h->fe_committed = d_committed;
-  launch_hulls_ts(d_committed, h->cfg.n_scenes, h->cfg.num_agents, &d_start->t_start, (long)sizeof(nep_fe_start), E.sp, ps, (hipStream_t)stream, grouped_hulls(E.sp, h->cfg.n_scenes, h->cfg.num_agents));
-  FeEntArgs ea{};
-  if (int e = ent_prepare(h, cfg->ent_samples, 0, d_committed, &d_start->t_start, (long)sizeof(nep_fe_start) * E.sp.n_local, ea, (hipStream_t)stream)) return e;
-  ea.init = d_ent_init; ea.case_out = d_case_out;
-  ea.pk_stride = 2 + 2 * kBend + 2 * (ea.ns + 1);
-  if (int e = E.d_fe_packed.ensure((size_t)h->cfg.n_scenes * h->cfg.num_agents * h->cfg.num_pol * ea.pk_stride)) return e;
-  ea.packed = E.d_fe_packed.p;
-  if (int e = E.d_as_iz.ensure((size_t)h->slots * E.as_tab)) return e;
-  if (int e = E.d_as_states.ensure((size_t)h->slots * E.as_pool * NEP_FE_ASTAR_ENT_NODE_BYTES)) return e;
-  const FeAstarEntArgs xa{E.d_as_iz.p, E.d_as_states.p};
-  launch_frontend_astar(h->slots, E.sp, ps, *cfg, fe_astar_args(E), &xa, &ea, d_start, d_guess, d_result, (hipStream_t)stream, E.d_fe_act.p);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return frontend_call(h, FeCall{"nep_batch_frontend_astar_ent", kBestFirst, kEnt, kRecords, cfg, d_committed, nullptr, 0, d_start, d_ent_init, d_guess, d_result, d_case_out, stream});
 }
 
 int nep_batch_safety_commit_ent(nep_batch_t* h, const nep_traj_rec* d_prev, const nep_traj_rec* d_new, const nep_guess* d_guess,
@@ -1546,9 +1545,7 @@ int nep_batch_safety_commit_ent(nep_batch_t* h, const nep_traj_rec* d_prev, cons
   FeEntArgs ea{};
   if (int e = ent_prepare(h, ent_samples, 0, d_new, &d_guess->t_start, (long)sizeof(nep_guess) * E.sp.n_local, ea, (hipStream_t)stream)) return e;
   ea.init = d_ent_init;
-  ea.pk_stride = 2 + 2 * kBend + 2 * (ea.ns + 1);
-  if (int e = E.d_fe_packed.ensure((size_t)h->cfg.n_scenes * N * h->cfg.num_pol * ea.pk_stride)) return e;
-  ea.packed = E.d_fe_packed.p;
+  if (int e = ent_packed(h, ea)) return e;
   launch_hulls(d_new, h->cfg.n_scenes, N, d_guess, E.sp, ps, (hipStream_t)stream, grouped_hulls(E.sp, h->cfg.n_scenes, N));     // (with the bend points: ent_enabled)
   launch_ent_check(E.sp, ps, ea, d_new, h->cfg.n_scenes, cable_length, E.d_entangles.p, (hipStream_t)stream);
   return safety_end(h, ps, d_prev, d_new, E.d_entangles.p, d_final, d_accept, (hipStream_t)stream);

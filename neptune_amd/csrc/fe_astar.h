@@ -1,6 +1,6 @@
 // fe_astar.h — the reference's best-first search as a device kernel, without and with enable_entangle_check.
 // Included by geom_kernels.hip, inside namespace nep, below the beam front end: it uses that file's fe_child, fe_lattice_fill,
-// fe_pos_cps, gjk_collision, hull_ref, fe_initial_z, ent_pack_kernel and skipped_fe_kernel, ent_device.h's ent_propagate, ent_iz,
+// fe_pos_cps, gjk_collision, hull_ref and fe_initial_z (its launch is launch_frontend's, behind this header), ent_device.h's ent_propagate, ent_iz,
 // ent_valid_endpoint and ent_copy, lds_layout.h's kAsNC, kAsHeapLds and astar_ent_layout, and that object's -ffp-contract=off.
 //
 // KinodynamicSearch::run (kinodynamic_search.cpp:1629-1827) as oracle/neptune_oracle.c restates it (orc_frontend_astar, entangle
@@ -454,26 +454,4 @@ __global__ __launch_bounds__(64) void frontend_astar_kernel(SceneParams sp, Prob
   if (lane == 0 && ps.dbg) { for (int k = 0; k < 8; k++) ps.dbg[(long)slot * 32 + k] = tph[k]; ps.dbg[(long)slot * 32 + 8] = pops; ps.dbg[(long)slot * 32 + 9] = used; }
 #endif
 #undef AS_TICK
-}
-
-// xa and ea null: the plain search; both set: the search with the entangle check
-void launch_frontend_astar(int n_slots, const SceneParams& sp, const ProblemSet& ps_in, const nep_fe_cfg& fc, const FeAstarArgs& aa, const FeAstarEntArgs* xa, const FeEntArgs* ea,
-                           const nep_fe_start* starts, nep_guess* guess_out, nep_fe_result* res_out, hipStream_t st, int* active_buf) {
-  if (n_slots <= 0) return;
-  ProblemSet ps = ps_in;
-  ps.fe_order = nullptr; ps.fe_count = nullptr;
-  if (ps.active && active_buf) {      // an active set: the searches run over the list of active slots; the others get what the beam's launch gives them
-    launch_active_list(n_slots, sp, ps.active, nullptr, active_buf, nullptr, st);
-    ps.fe_order = active_buf; ps.fe_count = active_buf + n_slots;
-    hipLaunchKernelGGL(skipped_fe_kernel, dim3((n_slots + 63) / 64), dim3(64), 0, st, sp, ps.active, n_slots, starts, guess_out, res_out);
-  }
-  if (!xa || !ea) {
-    hipLaunchKernelGGL(frontend_astar_kernel<false>, dim3(n_slots), dim3(64), 0, st, sp, ps, fc, aa, FeAstarEntArgs{}, FeEntArgs{}, starts, guess_out, res_out);
-    return;
-  }
-  // one record per (scene, agent, interval) of what the entangle check reads (ent_pack_kernel)
-  const int n_scenes = n_slots / (sp.n_local > 0 ? sp.n_local : 1);
-  const long np_ = (long)n_scenes * sp.num_agents * sp.num_pol;
-  hipLaunchKernelGGL(ent_pack_kernel, dim3((unsigned)((np_ + 255) / 256)), dim3(256), 0, st, sp, ps, *ea, n_scenes);
-  hipLaunchKernelGGL(frontend_astar_kernel<true>, dim3(n_slots), dim3(64), (size_t)astar_ent_layout().bytes, st, sp, ps, fc, aa, *xa, *ea, starts, guess_out, res_out);
 }

@@ -2990,58 +2990,52 @@ __global__ __launch_bounds__(64) void skipped_fe_kernel(SceneParams sp, const in
   guess_out[slot].K = 0; guess_out[slot].t_start = starts[slot].t_start;
   if (res_out) { nep_fe_result r{}; r.status = NEP_FE_SKIPPED; res_out[slot] = r; }
 }
-void launch_frontend(int n_slots, const SceneParams& sp, const ProblemSet& ps_in, const nep_fe_cfg& fc, const nep_fe_start* starts,
-                     nep_guess* guess_out, nep_fe_result* res_out, const FeEntArgs* ea, hipStream_t st, int* order_buf, bool have_history,
-                     int* active_buf) {
-  if (n_slots <= 0) return;
-  ProblemSet ps = ps_in;
-  ps.fe_order = nullptr;
-  const int xcd_mode = g_debug.fe_xcd;      // (A/B, nep_debug_set_global_option "fe_xcd": 0 = the launch order without the XCD placement)
-  if (order_buf && more_than_one_wave(n_slots) && n_slots % 8 == 0 && xcd_mode) {      // a few whole scenes per XCD, the longest expected searches first within each (order_xcd_kernel)
-    launch_order_xcd(n_slots, (ps.fe_order_key && have_history) ? ps.fe_order_key : nullptr, order_buf, st);
-    ps.fe_order = order_buf;
-  } else if (ps.fe_order_key && order_buf && have_history && more_than_one_wave(n_slots)) {
-    launch_qp_order(n_slots, ps.fe_order_key, order_buf, st);
-    ps.fe_order = order_buf;
-  }
-  if (ps.active && active_buf) {      // an active set: the searches run over the list of active slots, in the launch order made above
-    launch_active_list(n_slots, sp, ps.active, ps.fe_order, active_buf, nullptr, st);
-    ps.fe_order = active_buf; ps.fe_count = active_buf + n_slots;
-    hipLaunchKernelGGL(skipped_fe_kernel, dim3((n_slots + 63) / 64), dim3(64), 0, st, sp, ps.active, n_slots, starts, guess_out, res_out);
-  }
-  const bool ent = ea != nullptr;
-  const size_t lds = (size_t)fe_layout(sp.num_agents, sp.n_static, fc.beam_width, fc.num_samples, sp.num_pol, ent).bytes;      // (lds_layout.h)
-  // a search whose LDS leaves room for four workgroups on a CU (160 KB / 4) runs the instantiation bounded to 128 registers
-  // (11 spilled); larger ones — more obstacles, a wider beam — the one bounded for three
-  const bool four = !ent && lds <= (size_t)40 * 1024 && !g_debug.fe_three;      // (A/B, nep_debug_set_global_option "fe_three": keep the three-workgroup instantiation)
-  static DynLdsAttr attr[3];
-  const void* fn = ent ? (const void*)frontend_kernel<true, NEP_FE_ENT_WGS> : four ? (const void*)frontend_kernel<false, 4> : (const void*)frontend_kernel<false, NEP_FE_WAVES>;
-  (void)attr[ent ? 0 : four ? 1 : 2].ensure(fn, lds);
-  FeEntArgs none{};
-  launch_boxes(n_slots / (sp.n_local > 0 ? sp.n_local : 1), sp, ps, st);
-  if (ent && ea->packed) {
-    const int n_scenes = n_slots / (sp.n_local > 0 ? sp.n_local : 1);
-    const long np_ = (long)n_scenes * sp.num_agents * sp.num_pol;
-    hipLaunchKernelGGL(ent_pack_kernel, dim3((unsigned)((np_ + 255) / 256)), dim3(256), 0, st, sp, ps, *ea, n_scenes);
-  }
-  if (ent) {
-    hipLaunchKernelGGL((frontend_kernel<true, NEP_FE_ENT_WGS>), dim3(n_slots), dim3(256), lds, st, sp, ps, fc, starts, guess_out, res_out, *ea);
-    if (ea->redo_list && ea->big.base && ea->redo_cap > 0) {      // the searches listed by that launch, again, with big records (nearly always none: the workgroups return at once)
-      static DynLdsAttr attr_big;
-      FeEntArgs eb = *ea;
-      const FeLayout lb = fe_layout(sp.num_agents, sp.n_static, fc.beam_width, fc.num_samples, sp.num_pol, true, eb.big_beta != nullptr);      // (its lists in LDS when it has their betas' memory and the launch holds them)
-      eb.big_lds_off = lb.big_lds_off;
-      const size_t lds_b = (size_t)lb.bytes;
-      (void)attr_big.ensure((const void*)frontend_kernel<true, 1, true>, lds_b);
-      hipLaunchKernelGGL((frontend_kernel<true, 1, true>), dim3(ea->redo_cap < n_slots ? ea->redo_cap : n_slots), dim3(256), lds_b, st, sp, ps, fc, starts, guess_out, res_out, eb);
-    }
-  }
-  else if (four) hipLaunchKernelGGL((frontend_kernel<false, 4>), dim3(n_slots), dim3(256), lds, st, sp, ps, fc, starts, guess_out, res_out, none);
-  else hipLaunchKernelGGL((frontend_kernel<false, NEP_FE_WAVES>), dim3(n_slots), dim3(256), lds, st, sp, ps, fc, starts, guess_out, res_out, none);
-}
 
 // the reference's best-first search over the same lattice, without and with the entangle check (nep_batch_frontend_astar, nep_batch_frontend_astar_ent)
 #include "fe_astar.h"
+
+// One front-end call behind its hull launch, as plan_frontend decided it (launch_plan.h: every condition and its reason): the plan is
+// followed in order, and the searches' ProblemSet is derived from the caller's and the plan.  aa, xa: the best-first kernels' arguments;
+// ea: the entangle check's (each read by the plan's kernel only).  order_buf [slots], active_buf [slots + 1]: the handle's scratch
+void launch_frontend(const FrontendPlan& plan, int n_slots, int n_scenes, const SceneParams& sp, const ProblemSet& ps_in, const nep_fe_cfg& fc,
+                     const FeAstarArgs& aa, const FeAstarEntArgs& xa, const FeEntArgs& ea, const nep_fe_start* starts, nep_guess* guess_out,
+                     nep_fe_result* res_out, hipStream_t st, int* order_buf, int* active_buf) {
+  if (n_slots <= 0) return;
+  if (plan.order == kFeOrderXcd || plan.order == kFeOrderXcdKeyed) launch_order_xcd(n_slots, plan.order == kFeOrderXcdKeyed ? ps_in.fe_order_key : nullptr, order_buf, st);
+  if (plan.order == kFeOrderKeyed) launch_qp_order(n_slots, ps_in.fe_order_key, order_buf, st);
+  const int* order = plan.order != kFeOrderNone ? order_buf : nullptr;
+  if (plan.active_list) {
+    launch_active_list(n_slots, sp, ps_in.active, order, active_buf, nullptr, st);
+    hipLaunchKernelGGL(skipped_fe_kernel, dim3((n_slots + 63) / 64), dim3(64), 0, st, sp, ps_in.active, n_slots, starts, guess_out, res_out);
+  }
+  // the searches' set: workgroup -> slot (the active list, the launch order, or slot order)
+  ProblemSet ps = ps_in;
+  ps.fe_order = plan.active_list ? active_buf : order;
+  ps.fe_count = plan.active_list ? active_buf + n_slots : nullptr;
+  if (plan.boxes) launch_boxes(n_scenes, sp, ps, st);
+  if (plan.ent_pack) {
+    const long np_ = (long)n_scenes * sp.num_agents * sp.num_pol;
+    hipLaunchKernelGGL(ent_pack_kernel, dim3((unsigned)((np_ + 255) / 256)), dim3(256), 0, st, sp, ps, ea, n_scenes);
+  }
+  const size_t lds = (size_t)plan.lds_bytes;
+  // the beam's instantiations by the plan's kernel, then the big-record one (the best-first kernels stay below the default bound)
+  static DynLdsAttr attr[4];
+  static const void* const fn[4] = {(const void*)frontend_kernel<true, NEP_FE_ENT_WGS>, (const void*)frontend_kernel<false, 4>, (const void*)frontend_kernel<false, NEP_FE_WAVES>,
+                                    (const void*)frontend_kernel<true, 1, true>};
+  if (plan.kernel <= kFeBeamThree) (void)attr[plan.kernel].ensure(fn[plan.kernel], lds);
+  const dim3 grid(n_slots);
+  if (plan.kernel == kFeBeamEnt) hipLaunchKernelGGL((frontend_kernel<true, NEP_FE_ENT_WGS>), grid, dim3(256), lds, st, sp, ps, fc, starts, guess_out, res_out, ea);
+  if (plan.kernel == kFeBeamFour) hipLaunchKernelGGL((frontend_kernel<false, 4>), grid, dim3(256), lds, st, sp, ps, fc, starts, guess_out, res_out, FeEntArgs{});
+  if (plan.kernel == kFeBeamThree) hipLaunchKernelGGL((frontend_kernel<false, NEP_FE_WAVES>), grid, dim3(256), lds, st, sp, ps, fc, starts, guess_out, res_out, FeEntArgs{});
+  if (plan.kernel == kFeBestFirst) hipLaunchKernelGGL(frontend_astar_kernel<false>, grid, dim3(64), 0, st, sp, ps, fc, aa, FeAstarEntArgs{}, FeEntArgs{}, starts, guess_out, res_out);
+  if (plan.kernel == kFeBestFirstEnt) hipLaunchKernelGGL(frontend_astar_kernel<true>, grid, dim3(64), lds, st, sp, ps, fc, aa, xa, ea, starts, guess_out, res_out);
+  if (plan.big_redo) {
+    FeEntArgs eb = ea;
+    eb.big_lds_off = plan.big_lds_off;
+    (void)attr[3].ensure(fn[3], (size_t)plan.big_lds_bytes);
+    hipLaunchKernelGGL((frontend_kernel<true, 1, true>), dim3(plan.big_grid), dim3(256), (size_t)plan.big_lds_bytes, st, sp, ps, fc, starts, guess_out, res_out, eb);
+  }
+}
 
 // the reference's move_when_goal_occupied gate behind any of the front ends above (nep_batch_goal_gate)
 #include "goal_gate.h"

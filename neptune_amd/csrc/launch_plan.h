@@ -1,12 +1,14 @@
-// launch_plan.h — the launch topology of one replan (Engine::run, backend.hip), decided once: the caller copies the facts out of its
-// handle and its call (ReplanFacts), plan_replan says what will be launched (ReplanPlan), the launch code follows the plan and the debug
-// calls read it back (path_bits).  Every rule of the sequence is stated here and nowhere else.  Plain C++, no HIP: tests/cpp/launch_plan_check.cpp
-// runs the rules without a GPU.  plan_replan allocates nothing and loops over nothing (the per-agent handle calls it on every optimize()).
+// launch_plan.h — the launch topology of one replan (Engine::run, backend.hip) and of one front-end call (frontend_call), decided once:
+// the caller copies the facts out of its handle and its call (ReplanFacts, FrontendFacts), plan_replan / plan_frontend say what will be
+// launched (ReplanPlan, FrontendPlan), the launch code follows the plan and the debug calls read it back (path_bits).  Every rule of the
+// sequences is stated here and nowhere else.  Plain C++, no HIP: tests/cpp/launch_plan_check.cpp and fe_launch_plan_check.cpp run the rules
+// without a GPU.  plan_replan allocates nothing and loops over nothing (the per-agent handle calls it on every optimize()).
 #ifndef NEP_LAUNCH_PLAN_H_
 #define NEP_LAUNCH_PLAN_H_
 
 #include "../../include/neptune_backend.h"
 #include "../../include/neptune_backend_debug.h"
+#include "lds_layout.h"
 
 namespace nep {
 
@@ -130,6 +132,78 @@ inline ReplanPlan plan_replan(const ReplanFacts& f) {
   p.redo_pass = p.qp && p.skip && !f.no_redo;
   p.polish_pass = p.qp && p.polish_armed;      // (the slots the QP kernel listed: nearly always none — workgroups beyond the count return at once)
   p.have_history = p.qp ? p.keyed : f.have_history;
+  return p;
+}
+
+// --- the front end (frontend_call, backend.hip -> launch_frontend, geom_kernels.hip) ------------------------------------------------
+// The same for the six nep_batch_frontend* entry points: one call's facts, what it launches, in launch order.  fe_layout (lds_layout.h)
+// is the only loop behind plan_frontend, as it was behind the launchers.
+
+struct FrontendFacts {
+  // the scene parameters
+  int num_agents = 0, n_static = 0, num_pol = 0, hull_mode = 0;
+  // the call: its searches and their kind, where its hulls come from (records: the call makes them; else gathered blocks), an active set
+  // in force (nep_batch_set_active, which also sized the list's buffer)
+  int slots = 0, n_scenes = 0;
+  bool best_first = false, ent = false;
+  int beam_width = 0, num_samples = 0;
+  bool have_recs = false, active = false;
+  // the handle's switches and state: nep_batch_set_launch_order (with the order's buffer in place), the keys' buffer holds one entry per
+  // slot (Engine::fill's condition for ps.fe_order_key), a beam call has left its searches' times in the keys, the big-record
+  // instantiation's betas have their global memory (the entangle-aware beam's scratch: sized at the call, or the call fails)
+  bool lpt = true, order_key_ok = false, fe_history = false, big_beta = false;
+  // process-wide A/B switches (nep_debug_set_global_option): keep the three-workgroup instantiation; 0 = no XCD placement
+  bool fe_three = false; int fe_xcd = 1;
+};
+
+enum FeOrder { kFeOrderNone = 0, kFeOrderXcd = 1, kFeOrderXcdKeyed = 2, kFeOrderKeyed = 3 };      // slot order; order_xcd_kernel without and with keys; order_kernel
+// frontend_kernel<true, NEP_FE_ENT_WGS>, <false, 4>, <false, NEP_FE_WAVES>; frontend_astar_kernel<false>, <true>
+enum FeKernel { kFeBeamEnt = 0, kFeBeamFour = 1, kFeBeamThree = 2, kFeBestFirst = 3, kFeBestFirstEnt = 4 };
+constexpr int kFeRedoCap = 256;      // searches one call can hand to the big-record instantiation (beyond it they stay flagged)
+
+struct FrontendPlan {
+  bool hulls = false, grouped_hulls = false;         // the hull launch, and whether it is the eight-hulls-per-wave kernel
+  bool ent_sample = false;                           // ent_sample_kernel: the committed trajectories' samples and presence flags
+  FeOrder order = kFeOrderNone;
+  bool active_list = false;                          // active_list_kernel, and skipped_fe_kernel for the outputs of the inactive slots
+  bool boxes = false, ent_pack = false;              // fe_box_kernel, ent_pack_kernel
+  FeKernel kernel = kFeBeamFour; int lds_bytes = 0;  // the searches, one workgroup per slot, and their dynamic LDS
+  bool big_redo = false; int big_grid = 0, big_lds_bytes = 0, big_lds_off = 0;      // frontend_kernel<true, 1, true> over the searches the launch above listed
+  bool have_history = false;                         // what the call leaves behind for the next one
+};
+
+inline FrontendPlan plan_frontend(const FrontendFacts& f) {
+  FrontendPlan p;
+  const bool any = f.slots > 0, beam = !f.best_first;      // (no slot: the launchers launch nothing)
+  p.hulls = f.have_recs;
+  p.grouped_hulls = p.hulls && eight_hulls_per_wave(f.num_pol, f.hull_mode, f.n_scenes, f.num_agents);
+  p.ent_sample = f.ent && f.have_recs;      // (gathered blocks carry the samples: nep_batch_hulls made them)
+  // The launch order of the beam's workgroups (the best-first searches run in slot order).  A few whole scenes per XCD, the longest
+  // expected searches first within each (order_xcd_kernel; it deals the slots out in eights: slots % 8 == 0), with the keys when the
+  // previous beam call left them, the placement alone when not; launches it cannot take get the keyed order (order_kernel), which
+  // needs the keys.  Neither below two waves of workgroups.
+  const bool orderable = any && beam && f.lpt && more_than_one_wave(f.slots), keys = f.order_key_ok && f.fe_history;
+  p.order = !orderable ? kFeOrderNone : (f.slots % 8 == 0 && f.fe_xcd) ? (keys ? kFeOrderXcdKeyed : kFeOrderXcd) : keys ? kFeOrderKeyed : kFeOrderNone;
+  // an active set: the searches run over the list of active slots, in the launch order made above; the others get skipped_fe_kernel's outputs
+  p.active_list = any && f.active;
+  p.boxes = any && beam;      // (the beam's obstacle shortlist reads them; the best-first search tests every obstacle as the reference does)
+  // one record per (scene, agent, interval) of what the entangle check reads.  A constant of the entangle-aware calls: every one of them
+  // sizes the records' buffer before it launches (ent_packed, backend.hip)
+  p.ent_pack = any && f.ent;
+  p.lds_bytes = f.best_first ? (f.ent ? astar_ent_layout().bytes : 0) : fe_layout(f.num_agents, f.n_static, f.beam_width, f.num_samples, f.num_pol, f.ent).bytes;
+  // a beam whose LDS leaves room for four workgroups on a CU (160 KB / 4) runs the instantiation bounded to 128 registers (11 spilled);
+  // larger ones — more obstacles, a wider beam — the one bounded for three
+  const bool four = p.lds_bytes <= 40 * 1024 && !f.fe_three;
+  p.kernel = f.best_first ? (f.ent ? kFeBestFirstEnt : kFeBestFirst) : f.ent ? kFeBeamEnt : four ? kFeBeamFour : kFeBeamThree;
+  // the searches in which a child outgrew the fixed record, again, with big records (nearly always none: the workgroups return at once).
+  // A constant of the entangle-aware beam: its scratch (fe_ent_scratch) always holds the list, the pool and kFeRedoCap > 0.  Its lists
+  // live in LDS when they have their betas' memory and the launch holds them (fe_layout's big)
+  p.big_redo = any && beam && f.ent;
+  if (p.big_redo) {
+    const FeLayout lb = fe_layout(f.num_agents, f.n_static, f.beam_width, f.num_samples, f.num_pol, true, f.big_beta);
+    p.big_grid = kFeRedoCap < f.slots ? kFeRedoCap : f.slots; p.big_lds_bytes = lb.bytes; p.big_lds_off = lb.big_lds_off;
+  }
+  p.have_history = beam ? true : f.fe_history;      // (a beam call's searches write the keys; a best-first call leaves the handle's state alone)
   return p;
 }
 

@@ -19,7 +19,7 @@ constexpr int kBend = NEP_MAX_BEND;      // 8
 
 // Process-wide A/B knobs of the launchers (nep_debug_set_global_option, include/neptune_backend_debug.h): scheduling and placement
 // only — results do not depend on them — and never read from the environment (the library behaves the same under any environment).
-struct DebugGlobals { bool fe_three = false; int fe_xcd = 1; int polish_grid = 256; };
+struct DebugGlobals { bool fe_three = false; int fe_xcd = 1; int polish_grid = 256; };      // (fe_three, fe_xcd: read where a front-end call's facts are filled, backend.hip)
 extern DebugGlobals g_debug;
 
 // Scene-level constants (setMaxValues, ctor arguments; solver_gurobi_poly.cpp:25-175)
@@ -232,11 +232,6 @@ struct FeEntArgs {
   unsigned* xpool; int xpool_stride;      // front end (fast instantiation): per slot, room for the lists of new crossings of a round's (child, step) pairs that do not fit the LDS pool ([slots][xpool_stride] words: kEntAddCap per pair), see cross_round
   int fast_cap, fast_add, fast_bend;      // front end: what the fixed record's path accepts (<= NEP_FE_ENT_CAP, 32, NEP_MAX_BEND; nep_batch_set_fe_ent_fast_caps — the tests shrink them to drive ordinary scenes through the big records)
 };
-// (order_buf: [slots] scratch for the launch order, used when the previous launch left its keys — have_history — and the launch is
-// more than one wave of workgroups; null: slot order)
-void launch_frontend(int n_slots, const SceneParams& sp, const ProblemSet& ps, const nep_fe_cfg& fc, const nep_fe_start* starts,
-                     nep_guess* guess_out, nep_fe_result* res_out, const FeEntArgs* ea, hipStream_t st, int* order_buf = nullptr, bool have_history = false,
-                     int* active_buf = nullptr);      // (active_buf: [slots + 1] for the active list when ps.active is set)
 // the best-first front end (fe_astar.h, nep_batch_set_fe_astar): budget, lattice order and the per-slot pools (device pointers)
 struct FeAstarArgs {
   int max_pops, pool, tab_cap;   // pops per search; nodes per slot; entries of a slot's voxel table (a power of two >= 2 * pool)
@@ -250,9 +245,10 @@ struct FeAstarEntArgs {
   unsigned* tab_iz;              // [slots][tab_cap] the third word of a voxel's key: getIz of the node's state
   unsigned char* states;         // [slots][pool] a node's entangle state, NEP_FE_ASTAR_ENT_NODE_BYTES each, beside the node pool
 };
-// (xa and ea null: the plain search; both set: the search with the entangle check)
-void launch_frontend_astar(int n_slots, const SceneParams& sp, const ProblemSet& ps, const nep_fe_cfg& fc, const FeAstarArgs& aa, const FeAstarEntArgs* xa, const FeEntArgs* ea,
-                           const nep_fe_start* starts, nep_guess* guess_out, nep_fe_result* res_out, hipStream_t st, int* active_buf = nullptr);
+// one front-end call behind its hull launch, as its plan says (launch_plan.h: plan_frontend); order_buf [slots], active_buf [slots + 1]
+void launch_frontend(const FrontendPlan& plan, int n_slots, int n_scenes, const SceneParams& sp, const ProblemSet& ps, const nep_fe_cfg& fc,
+                     const FeAstarArgs& aa, const FeAstarEntArgs& xa, const FeEntArgs& ea, const nep_fe_start* starts, nep_guess* guess_out,
+                     nep_fe_result* res_out, hipStream_t st, int* order_buf, int* active_buf);
 // nep_batch_goal_gate (goal_gate.h): one wave per slot behind a front end; the hulls are the ones ps points at.  case_out
 // [slots][NEP_MAX_POL][N] and count [n_scenes][4] may be null
 void launch_goal_gate(int n_slots, const SceneParams& sp, const ProblemSet& ps, double half_side, const nep_fe_start* starts, nep_guess* guess,

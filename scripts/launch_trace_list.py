@@ -6,8 +6,17 @@ of the same program launched the same kernels when their outputs are equal.
 
     rocprofv3 --kernel-trace --output-format csv -d DIR -o kt -- python scripts/launch_paths.py --per-agent
     python scripts/launch_trace_list.py DIR/<host>/kt_kernel_trace.csv > launches.txt
+
+With --calls CASES.json (what scripts/fe_launch_paths.py --out wrote under the same trace) the trace is cut into that table's calls:
+the script launched a delimiter — nep::gjk_explicit_kernel over 64 n work-items, n = 1, 2, ... — in front of every call and behind
+it.  Every delimiter must be there once and in order; they are dropped, and so is whatever ran between two calls (a handle's set-up)
+and every kernel that is not the library's.  The output gives the distinct launches as above and one line of ids per call;
+--fixture OUT writes the table with those lines added.
+
+    python scripts/launch_trace_list.py --calls CASES.json DIR/<host>/kt_kernel_trace.csv --fixture tests/golden/fe_launch_paths.json
 """
 import csv
+import json
 import sys
 
 
@@ -52,5 +61,59 @@ def write(seq, out=sys.stdout):
         out.write(" ".join(words[i:i + 24]) + "\n")
 
 
+DELIMITER = "nep::gjk_explicit_kernel"
+
+
+def by_call(seq):
+    """the library's launches between delimiter 2c + 1 and 2c + 2, for c = 0, 1, ... -> [[launch]]"""
+    calls, n, cur = [], 0, None
+    for line in seq:
+        name, grid = [w.strip() for w in line.split("|")[:2]]
+        if name == DELIMITER:
+            n += 1
+            if int(grid.split("x")[0]) != 64 * n:
+                raise SystemExit("delimiter %d missing or out of order: %s" % (n, line))
+            if n % 2:
+                cur = []
+            else:
+                calls.append(cur); cur = None
+        elif cur is not None and "nep::" in name:
+            cur.append(line)
+    if cur is not None:
+        raise SystemExit("the trace ends inside a call")
+    return calls
+
+
+def main(argv):
+    if "--calls" not in argv:
+        write(launches(argv[0]))
+        return
+    argv = list(argv)
+    fixture = argv.pop(argv.index("--fixture") + 1) if "--fixture" in argv else None
+    table = argv.pop(argv.index("--calls") + 1)
+    trace = [a for a in argv if not a.startswith("--")][0]
+    with open(table) as f:
+        doc = json.load(f)
+    calls = by_call(launches(trace))
+    if len(calls) != sum(len(c["calls"]) for c in doc["cases"]):
+        raise SystemExit("%d calls in the trace, %d in the table" % (len(calls), sum(len(c["calls"]) for c in doc["cases"])))
+    ids, it = {}, iter(calls)
+    for c in doc["cases"]:
+        for call in c["calls"]:
+            call["launches"] = " ".join("k%d" % ids.setdefault(line, len(ids)) for line in next(it))
+    doc["launch_ids"] = {"k%d" % k: line for line, k in ids.items()}
+    for k, line in doc["launch_ids"].items():
+        sys.stdout.write("%s = %s\n" % (k, line))
+    sys.stdout.write("\n")
+    for c in doc["cases"]:
+        for r, call in enumerate(c["calls"]):
+            sys.stdout.write("%s %d x %d, call %d: %s\n" % (c["name"], c["scenes"], c["agents"], r, call["launches"]))
+    if fixture:
+        sys.path.insert(0, __import__("os").path.dirname(__import__("os").path.abspath(__file__)))
+        from fe_launch_paths import write_fixture
+        with open(fixture, "w") as f:
+            write_fixture(doc, f)
+
+
 if __name__ == "__main__":
-    write(launches(sys.argv[1]))
+    main(sys.argv[1:])
