@@ -208,6 +208,26 @@ int nep_batch_frontend_astar(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_tr
 int nep_batch_frontend_astar_ent(nep_batch_t* h, const nep_fe_cfg* cfg, const nep_traj_rec* d_committed, const nep_fe_start* d_start, const nep_fe_ent_state* d_ent_init,
                                  nep_guess* d_guess, nep_fe_result* d_result, int32_t* d_case_out, void* stream);
 
+/* ---- ... on four waves per search -------------------------------------------------------------------------------------------------
+ * nep_batch_frontend_astar_ent runs one wave per search by default.  Its latency is one search's, nine tenths of it the children's
+ * entangle propagation, and a launch of a few dozen searches leaves the GPU empty.  nep_batch_set_fe_astar_team(h, 4) makes the
+ * calls that follow run a workgroup of four waves per search, which finds the children's new crossings in a dense pass over (child,
+ * sampled step, chunk of obstacles) and leaves the list surgery to the children's lanes.  Measured on an MI355X (DESIGN.md section
+ * 37): 3.0 to 3.3 times shorter launches up to 512 searches, 1.7 times from 1 024 to 4 096 (a CU holds two such workgroups).
+ *   results     bit-identical to the one-wave form: every byte of every output
+ *   scope       nep_batch_frontend_astar_ent only.  nep_batch_frontend_astar (check off) keeps its one wave whatever the setting
+ *   setter      waves 1 (the default) or 4, anything else NEP_E_ARG.  Eager, allocates nothing, legal before or after
+ *               nep_batch_set_fe_astar in any order; a later nep_batch_set_fe_astar leaves it alone
+ *   graphs      a captured graph keeps the form it was captured with; the setter does not reach into it.  As for the entry point
+ *               itself, the first call of a form on a process is made eagerly
+ *   storage     pools, budget, order, voxel table, active sets, several scenes per launch, the eager first call and the NEP_E_*
+ *               conditions are nep_batch_frontend_astar_ent's: both forms read and write the same per-slot memory, so calls with
+ *               waves 1 and 4 may alternate on one handle
+ *   reader      nep_batch_fe_astar_team: the waves per search of the last nep_batch_frontend_astar_ent call on this handle, 0
+ *               when there has been none (no other call changes it)                                                               */
+int nep_batch_set_fe_astar_team(nep_batch_t* h, int32_t waves);   /* 1 (default) or 4; anything else NEP_E_ARG */
+int nep_batch_fe_astar_team(nep_batch_t* h);
+
 /* ---- move_when_goal_occupied: a plan that does not reach its goal is flown only when somebody is on the goal --------------------
  * The reference's benchmark yaml sets move_when_goal_occupied next to use_not_reaching_soln.  Neptune::replanFull (neptune.cpp:1480-1500):
  * a search that did not reach the goal (search_result != 1) has returned its closest-so-far node; that node is flown only if

@@ -47,7 +47,7 @@ PLAN_EXPORTS = [
 ]
 # every symbol include/neptune_entangle.h declares (host-only)
 # include/neptune_frontend.h
-FE_EXPORTS = ["nep_batch_frontend", "nep_batch_frontend_hulls", "nep_batch_set_fe_astar", "nep_batch_frontend_astar", "nep_batch_frontend_astar_ent", "nep_batch_goal_gate", "nep_batch_set_static_reps", "nep_batch_set_fe_ent_big_records", "nep_batch_frontend_ent", "nep_batch_frontend_ent_hulls", "nep_batch_safety_commit_ent", "nep_batch_track_ent", "nep_batch_track_ent_lists", "nep_batch_ent_lists_at_a", "nep_batch_next_starts", "nep_batch_audit", "nep_audit_records", "nep_audit_init"]
+FE_EXPORTS = ["nep_batch_frontend", "nep_batch_frontend_hulls", "nep_batch_set_fe_astar", "nep_batch_frontend_astar", "nep_batch_frontend_astar_ent", "nep_batch_set_fe_astar_team", "nep_batch_fe_astar_team", "nep_batch_goal_gate", "nep_batch_set_static_reps", "nep_batch_set_fe_ent_big_records", "nep_batch_frontend_ent", "nep_batch_frontend_ent_hulls", "nep_batch_safety_commit_ent", "nep_batch_track_ent", "nep_batch_track_ent_lists", "nep_batch_ent_lists_at_a", "nep_batch_next_starts", "nep_batch_audit", "nep_audit_records", "nep_audit_init"]
 # include/neptune_fleet.h
 FLEET_EXPORTS = ["nep_batch_fleet_init", "nep_batch_fleet_select", "nep_batch_fleet_commit", "nep_batch_fleet_tick", "nep_batch_fleet_ring_cap",
                  "nep_batch_fleet_plans", "nep_batch_fleet_state", "nep_batch_fleet_counters", "nep_batch_fleet_init_ent", "nep_batch_fleet_predict_ent",
@@ -195,6 +195,8 @@ def lib():
     L.nep_batch_set_fe_astar.argtypes = [vp, i, i, pi, i]
     L.nep_batch_frontend_astar.argtypes = [vp, C.POINTER(abi.nep_fe_cfg), vp, vp, vp, vp, vp]
     L.nep_batch_frontend_astar_ent.argtypes = [vp, C.POINTER(abi.nep_fe_cfg), vp, vp, vp, vp, vp, vp, vp]
+    L.nep_batch_set_fe_astar_team.argtypes = [vp, i]
+    L.nep_batch_fe_astar_team.argtypes = [vp]
     L.nep_batch_goal_gate.argtypes = [vp, d, vp, vp, vp, vp, vp, vp]
     L.nep_batch_guess_fallback.argtypes = [vp, vp, vp, vp, vp, vp]
     L.nep_batch_guess_fallback_tally.argtypes = [vp, vp, vp, vp, vp]

@@ -144,6 +144,7 @@ class nep_fe_cfg(C.Structure):
 
 
 NEP_FE_ENT_CAP = 40
+NEP_FE_ASTAR_TEAMS = (1, 4)      # nep_batch_set_fe_astar_team: waves per search of nep_batch_frontend_astar_ent (anything else NEP_E_ARG)
 
 
 class nep_fe_ent_state(C.Structure):

@@ -165,6 +165,7 @@ struct Engine {
   DevBuf<unsigned char> d_as_nodes; DevBuf<int> d_as_heap, d_as_val, d_as_order; DevBuf<unsigned long long> d_as_key;
   DevBuf<unsigned> d_as_iz; DevBuf<unsigned char> d_as_states;      // nep_batch_frontend_astar_ent: the voxel key's third word, the nodes' entangle states
   bool as_ready = false; int as_max_pops = 0, as_pool = 0, as_tab = 0, as_n_order = 0;
+  int as_team = 1, as_team_last = 0;      // nep_batch_set_fe_astar_team: waves per search of nep_batch_frontend_astar_ent; what its last call launched (0: none yet)
   DevBuf<int> d_act, d_fe_act;       // [slots + 1] compacted active slots + count (active_list_kernel): the QP launches', the front end's
   ListBuf d_track_lsave;      // nep_batch_track_ent_lists: the same scratch in the list form, of the largest cap seen
   DevBuf<nep_fe_ent_state> d_track_save; DevBuf<int> d_track_flags; DevBuf<double> d_track_pos;      // nep_batch_track_ent: per-slot scratch, flags when the caller passes none, the positions of the largest call
@@ -1222,6 +1223,19 @@ int nep_batch_set_fe_astar(nep_batch_t* h, int32_t max_pops, int32_t max_nodes, 
   return 0;
 }
 
+// waves per search of nep_batch_frontend_astar_ent (fe_astar.h: frontend_astar_kernel<true>, frontend_astar_team_kernel): a number kept
+// on the handle, nothing else — the two forms share every buffer
+int nep_batch_set_fe_astar_team(nep_batch_t* h, int32_t waves) {
+  if (!h) return fail(NEP_E_ARG, "null handle");
+  if (waves != 1 && waves != kAsTeamWaves) return fail(NEP_E_ARG, "nep_batch_set_fe_astar_team: waves must be 1 or 4");
+  h->eng.as_team = waves;
+  return 0;
+}
+int nep_batch_fe_astar_team(nep_batch_t* h) {
+  if (!h) return fail(NEP_E_ARG, "null handle");
+  return h->eng.as_team_last;
+}
+
 // budget, order and pools as nep_batch_set_fe_astar left them
 static FeAstarArgs fe_astar_args(const Engine& E) {
   FeAstarArgs aa{};
@@ -1469,6 +1483,7 @@ int frontend_call(nep_batch* h, const FeCall& c) {
   f.lpt = E.lpt && E.d_fe_order.p; f.order_key_ok = ps.fe_order_key != nullptr; f.fe_history = E.fe_history;
   f.big_beta = c.ent && !c.best_first;      // (fe_ent_scratch below sizes the betas' memory or fails the call)
   f.fe_three = g_debug.fe_three; f.fe_xcd = g_debug.fe_xcd;      // (A/B, nep_debug_set_global_option)
+  f.team = E.as_team;
   const FrontendPlan plan = plan_frontend(f);
   h->fe_committed = c.blocks ? nullptr : c.d_committed;
   if (plan.hulls) launch_hulls_ts(c.d_committed, h->cfg.n_scenes, h->cfg.num_agents, &c.d_start->t_start, (long)sizeof(nep_fe_start), E.sp, ps, st, plan.grouped_hulls);
@@ -1494,6 +1509,7 @@ int frontend_call(nep_batch* h, const FeCall& c) {
   }
   launch_frontend(plan, h->slots, h->cfg.n_scenes, E.sp, ps, *c.cfg, c.best_first ? fe_astar_args(E) : FeAstarArgs{}, xa, ea, c.d_start, c.d_guess, c.d_result, st, E.d_fe_order.p, E.d_fe_act.p);
   E.fe_history = plan.have_history;
+  if (plan.kernel == kFeBestFirstEnt) E.as_team_last = plan.team;      // (nep_batch_fe_astar_team; every other call leaves it alone)
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -3028,7 +3028,12 @@ void launch_frontend(const FrontendPlan& plan, int n_slots, int n_scenes, const 
   if (plan.kernel == kFeBeamFour) hipLaunchKernelGGL((frontend_kernel<false, 4>), grid, dim3(256), lds, st, sp, ps, fc, starts, guess_out, res_out, FeEntArgs{});
   if (plan.kernel == kFeBeamThree) hipLaunchKernelGGL((frontend_kernel<false, NEP_FE_WAVES>), grid, dim3(256), lds, st, sp, ps, fc, starts, guess_out, res_out, FeEntArgs{});
   if (plan.kernel == kFeBestFirst) hipLaunchKernelGGL(frontend_astar_kernel<false>, grid, dim3(64), 0, st, sp, ps, fc, aa, FeAstarEntArgs{}, FeEntArgs{}, starts, guess_out, res_out);
-  if (plan.kernel == kFeBestFirstEnt) hipLaunchKernelGGL(frontend_astar_kernel<true>, grid, dim3(64), lds, st, sp, ps, fc, aa, xa, ea, starts, guess_out, res_out);
+  if (plan.kernel == kFeBestFirstEnt && plan.team == 1) hipLaunchKernelGGL(frontend_astar_kernel<true>, grid, dim3(64), lds, st, sp, ps, fc, aa, xa, ea, starts, guess_out, res_out);
+  if (plan.kernel == kFeBestFirstEnt && plan.team != 1) {      // four waves per search (79 KB of LDS: above the default bound)
+    static DynLdsAttr team_attr;
+    (void)team_attr.ensure((const void*)frontend_astar_team_kernel, (size_t)plan.team_lds_bytes);
+    hipLaunchKernelGGL(frontend_astar_team_kernel, grid, dim3(64 * plan.team), (size_t)plan.team_lds_bytes, st, sp, ps, fc, aa, xa, ea, starts, guess_out, res_out);
+  }
   if (plan.big_redo) {
     FeEntArgs eb = ea;
     eb.big_lds_off = plan.big_lds_off;

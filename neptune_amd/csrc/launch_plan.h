@@ -154,10 +154,13 @@ struct FrontendFacts {
   bool lpt = true, order_key_ok = false, fe_history = false, big_beta = false;
   // process-wide A/B switches (nep_debug_set_global_option): keep the three-workgroup instantiation; 0 = no XCD placement
   bool fe_three = false; int fe_xcd = 1;
+  // nep_batch_set_fe_astar_team: waves per search of the best-first search with the entangle check, 1 or 4 (read for that search alone)
+  int team = 1;
 };
 
 enum FeOrder { kFeOrderNone = 0, kFeOrderXcd = 1, kFeOrderXcdKeyed = 2, kFeOrderKeyed = 3 };      // slot order; order_xcd_kernel without and with keys; order_kernel
-// frontend_kernel<true, NEP_FE_ENT_WGS>, <false, 4>, <false, NEP_FE_WAVES>; frontend_astar_kernel<false>, <true>
+// frontend_kernel<true, NEP_FE_ENT_WGS>, <false, 4>, <false, NEP_FE_WAVES>; frontend_astar_kernel<false>, <true> (kFeBestFirstEnt with
+// FrontendPlan::team == 4: frontend_astar_team_kernel, the same search on four waves)
 enum FeKernel { kFeBeamEnt = 0, kFeBeamFour = 1, kFeBeamThree = 2, kFeBestFirst = 3, kFeBestFirstEnt = 4 };
 constexpr int kFeRedoCap = 256;      // searches one call can hand to the big-record instantiation (beyond it they stay flagged)
 
@@ -168,6 +171,7 @@ struct FrontendPlan {
   bool active_list = false;                          // active_list_kernel, and skipped_fe_kernel for the outputs of the inactive slots
   bool boxes = false, ent_pack = false;              // fe_box_kernel, ent_pack_kernel
   FeKernel kernel = kFeBeamFour; int lds_bytes = 0;  // the searches, one workgroup per slot, and their dynamic LDS
+  int team = 1, team_lds_bytes = 0;                  // waves per search (the workgroup is 64 * team threads: kFeBestFirstEnt alone has a form with four); that form's LDS, 0 with team == 1
   bool big_redo = false; int big_grid = 0, big_lds_bytes = 0, big_lds_off = 0;      // frontend_kernel<true, 1, true> over the searches the launch above listed
   bool have_history = false;                         // what the call leaves behind for the next one
 };
@@ -195,6 +199,9 @@ inline FrontendPlan plan_frontend(const FrontendFacts& f) {
   // larger ones — more obstacles, a wider beam — the one bounded for three
   const bool four = p.lds_bytes <= 40 * 1024 && !f.fe_three;
   p.kernel = f.best_first ? (f.ent ? kFeBestFirstEnt : kFeBestFirst) : f.ent ? kFeBeamEnt : four ? kFeBeamFour : kFeBeamThree;
+  // four waves per search: the handle's choice, for the best-first search with the check only (every other call keeps its form whatever the setting)
+  p.team = p.kernel == kFeBestFirstEnt && f.team == kAsTeamWaves ? kAsTeamWaves : 1;
+  p.team_lds_bytes = p.team == kAsTeamWaves ? astar_ent_team_layout().bytes : 0;
   // the searches in which a child outgrew the fixed record, again, with big records (nearly always none: the workgroups return at once).
   // A constant of the entangle-aware beam: its scratch (fe_ent_scratch) always holds the list, the pool and kFeRedoCap > 0.  Its lists
   // live in LDS when they have their betas' memory and the launch holds them (fe_layout's big)

@@ -279,5 +279,40 @@ NEP_LDS_HD AstarEntLayout astar_ent_layout() {
   return L;
 }
 
+// ---- 8. frontend_astar_team_kernel (fe_astar.h) ---------------------------------------------------------------------------------------
+// Four waves per search (nep_batch_set_fe_astar_team): the one-wave carve as it is, at the same offsets (`one`), and behind it what
+// the dense crossing pass leaves for the surgery — a header word and kEntAddCap list words per (child, sampled step), the format of
+// ent_cross_step / ent_propagate_pre — plus what the four waves hand each other.  A fixed shape, 79.2 KB: two workgroups per CU by LDS, as by registers (207).
+constexpr int kAsTeamWaves = 4, kAsTeamThreads = 64 * kAsTeamWaves;
+constexpr int kAsTeamSteps = 8;       // sampled steps of a child: nep_fe_cfg.ent_samples <= 8
+constexpr int kAsTeamChunks = 8;      // contiguous chunks of the obstacle index range one (child, step) is split into, at most
+constexpr int kAsTeamCtl = 16;        // control words (fe_astar.h: kTc*)
+struct AstarEntTeamLayout {
+  AstarEntLayout one;         // [0, one.bytes): astar_ent_layout(), offsets unchanged
+  int x_hdr;                  // [kAsNC][kAsTeamSteps] unsigned: offset | n << 16 | overflow << 24 of a (child, step)'s list
+  int x_pool;                 // [kAsNC * kAsTeamSteps][kEntAddCap] unsigned: the lists, one fixed block per (child with "have", step)
+  int x_stage;                // [kAsTeamThreads][kEntAddCap - 4] unsigned: the tail of the list a work item is making (EntAdd::rest)
+  int x_cn;                   // [kAsTeamThreads] unsigned: a work item's n | peak << 8 | overflow << 16
+  int have;                   // [kAsNC] int: the children with "have", dense, in lattice order
+  int ctl;                    // [kAsTeamCtl] int: loop control and verdicts
+  int bytes;
+};
+NEP_LDS_HD AstarEntTeamLayout astar_ent_team_layout() {
+  AstarEntTeamLayout L;
+  L.one = astar_ent_layout();
+  L.x_hdr = L.one.bytes;
+  L.x_pool = L.x_hdr + kAsNC * kAsTeamSteps * 4;
+  L.x_stage = L.x_pool + kAsNC * kAsTeamSteps * kEntAddCap * 4;
+  L.x_cn = L.x_stage + kAsTeamThreads * (kEntAddCap - 4) * 4;
+  L.have = L.x_cn + kAsTeamThreads * 4;
+  L.ctl = L.have + kAsNC * 4;
+  L.bytes = lds_up(L.ctl + kAsTeamCtl * 4, 16);
+  return L;
+}
+static_assert(kAsNC * kAsTeamSteps <= kAsTeamThreads, "one work item per (child, step) at least: the dense pass is one round");
+static_assert(kAsNC * kAsTeamSteps * kEntAddCap <= 0xffff, "a list's offset is 16 bits of its header word");
+static_assert(kEntAddCap <= 0xff, "a work item's n and peak are 8 bits each");
+static_assert(kAsNC <= 64, "the children are wave 0's lanes");
+
 }  // namespace nep
 #endif

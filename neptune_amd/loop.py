@@ -75,6 +75,16 @@ def check_search(search, max_pops, tethers):
     return search != "beam"
 
 
+def check_team(team, search):
+    """waves per search of search="astar_ent" (BatchBackend.set_fe_astar_team): 1 (the default) or 4.  A launch choice like graph=:
+    the flight does not depend on it.  ValueError for another value, or for 4 with a search that has no such form"""
+    if isinstance(team, bool) or not isinstance(team, (int, np.integer)) or int(team) not in abi.NEP_FE_ASTAR_TEAMS:
+        raise ValueError("team must be 1 or 4, not %r" % (team,))
+    if int(team) != 1 and search != "astar_ent":
+        raise ValueError("team=4 is a form of search='astar_ent' only (search=%r keeps one wave per search)" % (search,))
+    return int(team)
+
+
 def check_goal_gate(goal_gate, search, drone_radius):
     """the reference's move_when_goal_occupied gate (BatchBackend.goal_gate): False / None (off), True (the box
     goal +- drone_radius, the reference's) or a half side in metres -> the half side, or None.  Not with the beam, whose ordinary
@@ -157,9 +167,10 @@ class _Audited:
 
 class FleetLoop(_Audited):
     def __init__(self, par, statics, starts, goals, beam_width=32, delta_t_states=6, replan_every=5, device=None, skip_arrived=False, audit=False,
-                 tethers=False, check=True, ent_samples=3, search="beam", max_pops=300, moveback=None, goal_gate=False, fly_guess=False):
+                 tethers=False, check=True, ent_samples=3, search="beam", max_pops=300, moveback=None, goal_gate=False, fly_guess=False, team=1):
         import torch
         from . import mission
+        self.team = check_team(team, search)      # (waves per search of search="astar_ent": same flight either way)
         self.torch = torch
         self.tethers, self.check, self.ent_samples = tethers, check, ent_samples
         # fly_guess: the reference's rule for a replan whose two QP solves failed (True is the reference) — the
@@ -185,6 +196,7 @@ class FleetLoop(_Audited):
         self.be.set_line_cull(4.0)             # presolve: far separating lines are verified, not solved for (same optimum)
         if self.astar:
             self.be.set_fe_astar(max_pops)     # (allocates the searches' pools)
+            self.be.set_fe_astar_team(self.team)
         self.fe = scene.frontend_cfg(par, beam_width=beam_width, pad_hold=1, entangle=tethers and check, ent_samples=ent_samples)
         if tethers:
             # the one-scene host form of DeviceFleetLoop(tethers=True): entangle_state_ of every agent at its tracked position is kept
@@ -513,9 +525,10 @@ class DeviceFleetLoop(_Audited):
 
     def __init__(self, scenes, beam_width=32, delta_t_states=6, replan_every=5, periods=None, phases=None, audit=False, graph=True,
                  goals=None, device=None, ring_cap=0, trace=False, tethers=False, check=True, ent_samples=3, missions=None, ent_cap=None,
-                 ent_lists0=None, recorder=None, search="beam", max_pops=300, moveback=None, goal_gate=False, fly_guess=False, effort=False):
+                 ent_lists0=None, recorder=None, search="beam", max_pops=300, moveback=None, goal_gate=False, fly_guess=False, effort=False, team=1):
         import torch
         from . import mission as mission_mod
+        self.team = check_team(team, search)      # (waves per search of search="astar_ent"; not among the options a checkpoint carries: the flight does not depend on it)
         self.torch = torch
         self.scenes = scenes
         self.effort = mission_mod.effort_slack(effort)      # the slack, or None
@@ -529,7 +542,7 @@ class DeviceFleetLoop(_Audited):
         self._opts = dict(beam_width=beam_width, delta_t_states=delta_t_states, replan_every=replan_every, audit=audit, ring_cap=ring_cap,
                           tethers=tethers, check=check, ent_samples=ent_samples, ent_cap=ent_cap, missions=missions, goals=goals,
                           search=search, max_pops=max_pops, moveback=moveback, goal_gate=self.goal_gate, fly_guess=self.fly_guess,
-                          script=mission_mod.spec_plain(missions)[1], effort=self.effort)
+                          script=mission_mod.spec_plain(missions)[1], effort=self.effort, team=self.team)
         S = self.S = len(scenes)
         p = self.p = scenes[0]["par"]
         self.tethers, self.check, self.ent_samples = tethers, check, ent_samples
@@ -544,6 +557,7 @@ class DeviceFleetLoop(_Audited):
         be.set_line_cull(4.0)
         if self.astar:
             be.set_fe_astar(max_pops)      # (allocates the searches' pools: here, before any capture)
+            be.set_fe_astar_team(self.team)
         self.fe = scene.frontend_cfg(p, beam_width=beam_width, pad_hold=1, entangle=tethers and check, ent_samples=ent_samples)
         self.goals = np.stack([np.asarray(scene.reachable_goals(sc) if goals is None else goals[s], dtype=np.float64).reshape(N, 3)
                                for s, sc in enumerate(scenes)])

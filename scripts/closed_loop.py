@@ -2,7 +2,7 @@
 """Closed-loop flight of a fleet on the device path (neptune_amd/loop.py): every agent flies from its
 start next to its base to a random goal, replanning in bulk-synchronous rounds, the way the reference's
 benchmark driver logs a run (scripts/benchmark_mtlp.py:215-223: elapsed time, distance, success).
-  python scripts/closed_loop.py [--agents 16 --obstacles 8 --seed 0 --beam 32 --skip-arrived --audit --tethers [--no-check] --search astar --max-pops 300]
+  python scripts/closed_loop.py [--agents 16 --obstacles 8 --seed 0 --beam 32 --skip-arrived --audit --tethers [--no-check] --search astar --max-pops 300 --team 4]
 --tethers: tethered agents, the one-scene host form of DeviceFleetLoop(tethers=True) (entangle states kept on the host with
 nep_ent_track_step per control tick, nep_ent_predict_a per round).  --search astar: the reference's best-first search, --max-pops
 pops per search, in place of the beam (not with --tethers).  --moveback [RADIUS|ref] [--moveback-timeout S]: every agent first plans
@@ -24,6 +24,7 @@ ap.add_argument("--tethers", action="store_true", help="tethered agents: entangl
 ap.add_argument("--no-check", action="store_true", help="with --tethers: plain front end and safety pass, the tracking stays on")
 ap.add_argument("--search", choices=("beam", "astar", "astar_ent"), default="beam", help="front end: the beam (default), the reference's best-first search (nep_batch_frontend_astar; not with --tethers) or that search with the entangle check (astar_ent: nep_batch_frontend_astar_ent; only with --tethers)")
 ap.add_argument("--max-pops", type=int, default=300, help="with --search astar / astar_ent: pops per search")
+ap.add_argument("--team", type=int, choices=(1, 4), default=1, help="with --search astar_ent: waves per search (4: a workgroup of four waves per search; the flight is the same)")
 ap.add_argument("--moveback", nargs="?", const="ref", metavar="RADIUS|ref", help="the reference's move-back strategy (DESIGN section 32): an agent with a new goal first plans towards its own base, until it is within RADIUS m of it (ref, the default: 6.33 - (agents - 4) * 0.33) or --moveback-timeout has passed")
 ap.add_argument("--moveback-timeout", type=float, default=10.0, metavar="S", help="with --moveback: seconds of simulated time after which the goal is released anyway")
 ap.add_argument("--goal-gate", nargs="?", const="radius", metavar="HALF_SIDE", help="the reference's move_when_goal_occupied gate (DESIGN section 33): a search that did not reach its goal is flown only when somebody else is on the goal's square of this half side (default: the drone radius); not with --search beam")
@@ -37,7 +38,7 @@ if a.moveback:
 sc = scene.make_scene(a.agents, a.obstacles, seed=a.seed)
 t0 = time.perf_counter()
 loop = FleetLoop(sc["par"], sc["statics"], sc["starts"], scene.reachable_goals(sc), beam_width=a.beam, skip_arrived=a.skip_arrived, audit=a.audit, tethers=a.tethers,
-                 check=not a.no_check, search=a.search, max_pops=a.max_pops, moveback=mb, goal_gate=gg, fly_guess=a.fly_guess)
+                 check=not a.no_check, search=a.search, max_pops=a.max_pops, moveback=mb, goal_gate=gg, fly_guess=a.fly_guess, team=a.team)
 if a.audit:
     loop.trace = []
 st = loop.run(a.max_rounds)

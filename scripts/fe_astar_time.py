@@ -6,7 +6,11 @@ phase numbering for both instantiations, PHASES; without the check "entangle pro
 --ent: frontend_astar_kernel<true> (the same search with the entangle check) next to the plain A* and to the beam with
 the check, on the same scenes with config-5 style tethers (scene.synthetic_entangle), and tests/astar_ent_ref.py on host processes for a
 sample of the slots (its pop counts must equal the device's).
-   python scripts/fe_astar_time.py [--ent] [scenes=128] [agents=64] [obstacles=20] [pops=100,300,1000] [host_sample=256]"""
+--ent --team: frontend_astar_kernel<true> (one wave per search) next to frontend_astar_team_kernel (four waves per search)
+on the same inputs in one run: one captured graph per form, replayed in alternation; per size (searches = scenes x agents) and budget the
+time per launch of both, their spread, the us per pop of the longest search and whether every output byte is equal.
+   python scripts/fe_astar_time.py [--ent] [scenes=128] [agents=64] [obstacles=20] [pops=100,300,1000] [host_sample=256]
+   python scripts/fe_astar_time.py --ent --team [searches=64,256,1024] [agents=64] [obstacles=20] [pops=100,300] [rounds=7]"""
 import os, sys, time
 from concurrent.futures import ProcessPoolExecutor, ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
@@ -127,7 +131,89 @@ def main_ent(argv):
     be.close()
 
 
+PHASES_TEAM = ("pop", "GJK + bases", "fe_child", "dense crossing pass", "surgery + lookup + group", "commit", "state copy", "setup + result")      # frontend_astar_team_kernel's AS_TICK
+
+
+def capture(fn):
+    """fn() captured after two eager calls -> the graph"""
+    for _ in range(2):
+        fn()
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream(); s.wait_stream(torch.cuda.current_stream())
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(s):
+        g.capture_begin(); fn(); g.capture_end()
+    torch.cuda.current_stream().wait_stream(s)
+    g.replay(); torch.cuda.synchronize()
+    return g
+
+
+def timed(g):
+    e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+    e0.record(); g.replay(); e1.record(); torch.cuda.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def main_team(argv):
+    import dataclasses
+    sizes = [int(x) for x in (argv[0] if len(argv) > 0 else "64,256,1024").split(",")]
+    N = int(argv[1]) if len(argv) > 1 else 64
+    M = int(argv[2]) if len(argv) > 2 else 20
+    budgets = [int(x) for x in (argv[3] if len(argv) > 3 else "100,300").split(",")]
+    rounds = int(argv[4]) if len(argv) > 4 else 7
+    S_max = max(1, max(sizes) // N)
+    made = scene.make_scenes(N, M, range(S_max), workers=min(S_max, 16))
+    for s, m in enumerate(made):
+        m["par"] = dataclasses.replace(m["par"], enable_entangle=True)
+        scene.synthetic_entangle(m, seed=900 + s)
+    p = made[0]["par"]
+    profile = os.environ.get("NEP_QP_PROFILE") is not None
+    cfg_e = scene.frontend_cfg(p, beam_width=32, entangle=True)
+    print("one wave per search against four (hulls + search, a captured graph each, replayed in alternation, %d rounds); %d agents + %d obstacles, tethers with 2-4 bend points" % (rounds, N, M))
+    for size in sizes:
+        S = max(1, size // N); n = S * N
+        be = BatchBackend(p, made[0]["statics"], n_scenes=S)
+        for s in range(S):
+            be.set_scene_statics(s, made[s]["statics"])
+            reps, long_ = scene.static_reps(made[s]["statics"]); be.set_static_reps(reps, long_, scene=s)
+        d_c = be.to_device(np.stack([m["committed"] for m in made[:S]])); d_s = be.to_device(np.stack([scene.frontend_starts(m) for m in made[:S]]))
+        out = {t: (torch.zeros(n * abi.GUESS_DTYPE.itemsize, dtype=torch.uint8, device=be.device), torch.zeros(n * abi.FE_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=be.device),
+                   torch.zeros(n * abi.NEP_MAX_POL * N, dtype=torch.int32, device=be.device)) for t in (1, 4)}
+        for pops in budgets:
+            be.set_fe_astar(pops)
+            graphs = {}
+            for t in (1, 4):
+                be.set_fe_astar_team(t)
+                graphs[t] = capture(lambda: be.frontend_astar_ent(cfg_e, d_c, d_s, *out[t]))
+                assert be.fe_astar_team() == t
+            ms = {1: [], 4: []}
+            for _ in range(rounds):
+                for t in (1, 4):
+                    ms[t].append(timed(graphs[t]))
+            try:
+                be.check()
+            except Exception:      # (a fixed-record overflow is reported by both forms alike)
+                pass
+            same = all(bool((a == b).all()) for a, b in zip(out[1], out[4]))
+            res = out[4][1].cpu().numpy().view(abi.FE_RESULT_DTYPE)
+            mx = int(res["n_children"].max())
+            m1, m4 = float(np.median(ms[1])), float(np.median(ms[4]))
+            print("%5d searches, %4d pops: one wave %.3f ms (min %.3f max %.3f), four waves %.3f ms (min %.3f max %.3f): %.2f x; us per pop of the longest search (%d pops) %.1f against %.1f; outputs %s"
+                  % (n, pops, m1, min(ms[1]), max(ms[1]), m4, min(ms[4]), max(ms[4]), m1 / m4, mx, 1e3 * m1 / max(mx, 1), 1e3 * m4 / max(mx, 1), "equal byte for byte" if same else "DIFFER"), flush=True)
+            if profile:
+                for t, names in ((1, PHASES), (4, PHASES_TEAM)):
+                    graphs[t].replay(); torch.cuda.synchronize()
+                    rows = np.array([be.debug_phase_cycles(2 * int(s_)) for s_ in np.linspace(0, n - 1, min(64, n)).astype(int)], dtype=np.float64)
+                    tot_c = rows[:, :8].sum(axis=1).mean()
+                    print("   %d wave(s), cycles per search (mean of %d slots): %s; per pop %.0f" % (t, len(rows), ", ".join("%s %.0f (%.0f %%)" % (nm, rows[:, k].mean(), 100 * rows[:, k].mean() / max(tot_c, 1)) for k, nm in enumerate(names)),
+                                                                                                  rows[:, :7].sum() / max(rows[:, 8].sum(), 1)), flush=True)
+            del graphs
+        be.close()
+
+
 def main():
+    if "--ent" in sys.argv and "--team" in sys.argv:
+        return main_team([x for x in sys.argv[1:] if x not in ("--ent", "--team")])
     if "--ent" in sys.argv:
         return main_ent([x for x in sys.argv[1:] if x != "--ent"])
     S = int(sys.argv[1]) if len(sys.argv) > 1 else 128

@@ -53,6 +53,7 @@ def main():
     ap.add_argument("--stagger", type=int, default=0, metavar="P")
     ap.add_argument("--search", choices=("beam", "astar", "astar_ent"), default="beam", help="front end: the beam (default), the reference's best-first search (nep_batch_frontend_astar; not with --tethers) or that search with the entangle check (astar_ent: nep_batch_frontend_astar_ent; only with --tethers)")
     ap.add_argument("--max-pops", type=int, default=300, help="with --search astar / astar_ent: pops per search")
+    ap.add_argument("--team", type=int, choices=(1, 4), default=1, help="with --search astar_ent: waves per search (4: a workgroup of four waves per search, for fleets of few agents; the flight is the same)")
     ap.add_argument("--audit", action="store_true", help="flight audit of every round, inside the graph")
     ap.add_argument("--eager", action="store_true", help="no graph capture")
     ap.add_argument("--tethers", action="store_true", help="tethered agents: entangle states tracked per control tick, predicted at A, checked by the front end and the safety pass")
@@ -82,7 +83,7 @@ def main():
     from neptune_amd.loop import DeviceFleetLoop, FleetLoop
     seeds = [a.seed0 + k for k in range(a.scenes)]
     scenes = scene.make_scenes(a.agents, a.obstacles, seeds, workers=min(len(seeds), len(os.sched_getaffinity(0)), 16))
-    kw = dict(beam_width=a.beam, audit=a.audit, graph=not a.eager, search=a.search, max_pops=a.max_pops)
+    kw = dict(beam_width=a.beam, audit=a.audit, graph=not a.eager, search=a.search, max_pops=a.max_pops, team=a.team)
     if a.tethers:
         kw.update(tethers=True, check=not a.no_check)
         if a.ent_cap:
@@ -228,7 +229,7 @@ def main():
     if a.host:
         sc = scenes[0]
         _, dev1, n1 = fly([sc], a.rounds)
-        ref = FleetLoop(sc["par"], sc["statics"], sc["starts"], kw["goals"][0] if a.cross else scene.reachable_goals(sc), beam_width=a.beam, audit=a.audit, tethers=a.tethers, check=not a.no_check, search=a.search, max_pops=a.max_pops, moveback=mb, goal_gate=gg, fly_guess=a.fly_guess)
+        ref = FleetLoop(sc["par"], sc["statics"], sc["starts"], kw["goals"][0] if a.cross else scene.reachable_goals(sc), beam_width=a.beam, audit=a.audit, tethers=a.tethers, check=not a.no_check, search=a.search, max_pops=a.max_pops, moveback=mb, goal_gate=gg, fly_guess=a.fly_guess, team=a.team)
         ref.round(); ref.round()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
