@@ -568,6 +568,13 @@ int read_lines(Engine& E, size_t slot, int n_seg, int32_t cap, int32_t* seg, dou
   if (E.sp.cull_radius > 0.0) HIPCHK(hipMemcpy(far.data(), E.d_line_far.p + slot * NEP_MAX_POL, far.size() * sizeof(int), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(buf.data(), E.d_line_nd.p + slot * NEP_MAX_POL * E.sp.lines_cap * 3, buf.size() * sizeof(double), hipMemcpyDeviceToHost));
   for (int& c : cnt) c = line_count(c);      // (an overflowed bucket's count is stored as -1 - n)
+  // (a slot no separator has written yet — inactive under an active set since the handle was made — holds whatever the allocation
+  // held: the counts are kept inside the bucket, so that this reader never leaves its copy of it)
+  const int lc = E.sp.lines_cap > 0 ? E.sp.lines_cap : 0;
+  for (int s = 0; s < NEP_MAX_POL; s++) {
+    cnt[s] = cnt[s] < 0 ? 0 : cnt[s] > lc ? lc : cnt[s];
+    far[s] = far[s] < 0 ? 0 : far[s] > lc - cnt[s] ? lc - cnt[s] : far[s];
+  }
   int n = 0;
   for (int s = 0; s < n_seg && s < NEP_MAX_POL; s++)
     for (int c = 0; c < cnt[s] + far[s]; c++) {

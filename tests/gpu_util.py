@@ -152,6 +152,51 @@ def _check_scene(be, oracle, sc, n_scenes=1, first_local=0, n_local=None, hull_k
     return worst
 
 
+def check_replanned_handle(oracle, bb, guesses, committed, refs, mask=None):
+    """_check_scene's per-slot rules for ONE handle that the caller prepared (options, scenes' statics, separator pack ...) and
+    replanned: guesses, committed [n_scenes][N] as the replan got them, refs [n_scenes][N] the oracle's result per (scene, agent) —
+    None where the guess has K = 0: such a slot reports NEP_FAILED with an empty solution, no line, no LP and no row —, mask
+    [n_scenes][N] the active set in force (0: the slot is NEP_SKIPPED) or None.  The solve path is the handle's: with line_cull() == 0
+    the lines bit for bit in the reference's call order and n_rows equal; otherwise every held line one of the oracle's in the same
+    segment, bit for bit, and n_rows <= the oracle's.  Both: n_lines, n_lp, n_lp_failed, status, coefficients <= COEF_TOL, cost <=
+    COST_RTOL, check_slot_outputs.  -> the worst coefficient error"""
+    p = bb.par
+    full = bb.line_cull() == 0.0
+    nl = bb.n_local
+    sol = bb.solutions(); states = bb.states(); com = bb.commits()
+    worst = 0.0
+    for s in range(bb.n_scenes):
+        for a in range(nl):
+            own = bb.first_local + a; slot = s * nl + a
+            g = guesses[s][own]; r = refs[s][own]; st = sol[slot]["stats"]; tag = (s, own)
+            skipped = mask is not None and not mask[s][own]
+            seg, nd = (None, None) if skipped else bb.debug_lines(slot)      # (no separator ran for an inactive slot: its buckets are not a result)
+            if skipped:
+                assert int(st["status"]) == abi.NEP_SKIPPED, tag
+            elif r is None:
+                assert int(g["K"]) == 0 and int(st["status"]) == abi.NEP_FAILED and int(sol[slot]["K"]) == 0 and len(seg) == 0, tag
+                assert (int(st["n_lines"]), int(st["n_lp"]), int(st["n_lp_failed"]), int(st["n_rows"])) == (0, 0, 0, 0), tag
+            else:
+                K = int(sol[slot]["K"])
+                assert K == int(g["K"]), tag
+                if full:
+                    np.testing.assert_array_equal(seg, r["line_seg"], err_msg=str(tag))
+                    np.testing.assert_array_equal(nd, r["line_nd"], err_msg=str(tag))
+                    assert int(st["n_rows"]) == r["n_rows"], tag
+                else:
+                    want = {(int(s_), l.tobytes()) for s_, l in zip(r["line_seg"], r["line_nd"])}
+                    assert all((int(s_), np.ascontiguousarray(l).tobytes()) in want for s_, l in zip(seg, nd)), tag
+                    assert int(st["n_rows"]) <= r["n_rows"], tag
+                assert int(st["status"]) == r["status"] and int(st["n_lines"]) == r["n_lines"], (tag, int(st["status"]), r["status"], int(st["n_lines"]), r["n_lines"])
+                assert int(st["n_lp"]) == r["n_lp"] and int(st["n_lp_failed"]) == r["n_lp_failed"], tag
+                err = np.abs(np.array(sol[slot]["coeff"])[:, :K, :] - r["coeff"]).max(); worst = max(worst, err)
+                assert err <= COEF_TOL, (tag, err)
+                if r["status"] != abi.NEP_FAILED:
+                    assert abs(float(st["objective"]) - r["objective"]) <= COST_RTOL * (1 + abs(r["objective"])), tag
+            check_slot_outputs(oracle, p, own, g, sol[slot], states[slot], com[slot], prev=committed[s][own])
+    return worst
+
+
 def check_frontend_beam(be, oracle, sc, W, near=(0.9, 0.3)):
     """The front-end kernel against the deterministic beam rule of the oracle: results and guesses (lattice primitives) identical,
     the same with pad_hold on goals `near` the starts (short searches), then the back end on the device-made guesses against the

@@ -347,7 +347,7 @@ def test_sharded_hull_blocks_equal_the_single_rank_replan(be, world, entangle):
 def test_packed_separator_gives_the_unpacked_kernels_lines(be, n_agents, n_static, seed, ent, radius):
     """separator_packed_kernel (the spatial presolve's separator: several segments of a slot per wave, LPs solved 64 to a batch
     across the segments) against separator_kernel<0> on the same launch: every line bucket (near lines in call order, parked lines
-    from the end), every count and every solution byte for byte — with 1, 3 and 8 segments per wave (the host picks by launch
+    from the end), every count and every solution byte for byte — with 1, 2, 3, 4 and 8 segments per wave (the host picks by launch
     size; nep_batch_debug_set_separator_pack forces one), with a candidate list far shorter than a wave (5 agents) and with entangle candidates."""
     import dataclasses, os
     sc = scene.make_scene(n_agents, n_static, seed=seed)
@@ -367,7 +367,7 @@ def test_packed_separator_gives_the_unpacked_kernels_lines(be, n_agents, n_stati
         return sol, lines, bb.redo_count()
     ref_sol, ref_lines, ref_redo = run(-1)
     assert int(ref_sol["stats"]["n_lines"].sum()) > 0
-    for pack in (1, 3, 8):
+    for pack in (1, 2, 3, 4, 8):
         sol, lines, redo = run(pack)
         assert sol.tobytes() == ref_sol.tobytes(), pack
         assert redo == ref_redo
