@@ -87,7 +87,10 @@ int nep_batch_debug_launch_order(nep_batch_t* h, int32_t* order, int32_t cap, in
  *                  and more; nep_batch_replan, no active set) that wave runs the certificate itself and qp_presolve_kernel is not
  *                  launched | 0: always the kernel of its own.  Same bytes either way (tests/test_gpu_presolve_fused.py)
  * Process-wide (launcher choices, results do not depend on them): "fe_three" (keep the three-workgroup front-end instantiation),
- * "fe_xcd" (0: no XCD placement of the searches), "polish_grid" (workgroups of the polish pass, default 256).
+ * "fe_xcd" (0: no XCD placement of the searches), "polish_grid" (workgroups of the polish pass, default 256), "polish_impl" (1, the
+ * default: the polish pass's batched form | 0: its first form, the one the default is compared with), "parked_bound" (1, the default: a
+ * slot the polish pass certified reads its parked lines back only when a control point left the certificate's movement bound | 0:
+ * always).  Same bytes either way (tests/test_gpu_polish_forms.py); read when a replan is enqueued, so a captured graph keeps its form.
  * Unknown names are refused (NEP_E_ARG).                                                                                      */
 int nep_batch_debug_set_option(nep_batch_t* h, const char* name, int32_t value);
 int nep_backend_debug_set_option(nep_backend_t* h, const char* name, int32_t value);
@@ -157,7 +160,8 @@ int nep_batch_set_fe_ent_fast_caps(nep_batch_t* h, int32_t list_cap, int32_t add
 int nep_batch_debug_polish_count(nep_batch_t* h, int32_t* listed, int32_t* certified);
 /* ... and per slot: flags [slots] (host) — 0 = not listed; bit 0 / bit 1: the first / the relaxed problem's solve was left for the pass; bit 8: the
  * pass certified an optimum and wrote the slot's status, objective and trajectory (nep_stats.iters / iters_first stay the interior point's;
- * nep_stats.solve_us includes the pass's device time).                                                                                  */
+ * nep_stats.solve_us includes the pass's device time); bit 9: the pass read a certified point's parked lines back (under "parked_bound" only
+ * when a control point left the movement bound); bit 10: it dropped a certified point that failed the presolve's verification.          */
 int nep_batch_debug_polish_flags(nep_batch_t* h, int32_t* flags, int32_t cap);
 
 /* Test hook of the library's ownership of memory: the bytes of device memory and of page-locked host memory that the handles and

@@ -840,7 +840,8 @@ class BatchBackend:
 
     def polish_flags(self):
         """per slot of the last replan: 0 not listed for the polish pass; bit 0 / 1 the first / relaxed solve was left for it; bit 8 (256) the pass
-        certified an optimum and wrote the result (nep_batch_debug_polish_flags)"""
+        certified an optimum and wrote the result; bit 9 (512) it read a certified point's parked lines back; bit 10 (1024) it dropped a
+        certified point that failed the presolve's verification (nep_batch_debug_polish_flags)"""
         out = np.zeros(self.n_scenes * self.n_local, dtype=np.int32)
         check(lib().nep_batch_debug_polish_flags(self._h, abi.iptr(out), len(out)))
         return out

@@ -2421,6 +2421,8 @@ int nep_debug_set_global_option(const char* name, int32_t value) {
   if (n == "fe_three") g_debug.fe_three = value != 0;
   else if (n == "fe_xcd") g_debug.fe_xcd = value;
   else if (n == "polish_grid") { if (value < 1) return fail(NEP_E_ARG, "polish_grid >= 1"); g_debug.polish_grid = value; }
+  else if (n == "polish_impl") { if (value < 0 || value > 1) return fail(NEP_E_ARG, "polish_impl: 0 the first form of the polish pass, 1 the batched one"); g_debug.polish_impl = value; }
+  else if (n == "parked_bound") g_debug.parked_bound = value != 0;      // 0: a certified slot always reads its parked lines back (same verdicts)
   else return fail(NEP_E_ARG, "unknown global debug option: " + n);
   return 0;
 }
@@ -2510,7 +2512,9 @@ int nep_batch_debug_polish_count(nep_batch_t* h, int32_t* listed, int32_t* certi
   return 0;
 }
 // Test hook: per slot of the last replan, 0 = not listed for the polish pass, else the flag word — bit m: the solve of mode m (0 first
-// problem, 1 relaxed) was left for the pass; bit 8: the pass certified an optimum and wrote the slot's result.
+// problem, 1 relaxed) was left for the pass; bit 8: the pass certified an optimum and wrote the slot's result; bit 9: it read a
+// certified point's parked lines back (with "parked_bound": only when a control point left the movement bound); bit 10: it dropped a
+// certified point that failed the presolve's verification.
 int nep_batch_debug_polish_flags(nep_batch_t* h, int32_t* flags, int32_t cap) {
   if (!h || !flags || cap < h->slots) return fail(NEP_E_ARG, "bad arguments");
   for (int i = 0; i < h->slots; i++) flags[i] = 0;
