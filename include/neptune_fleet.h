@@ -236,7 +236,7 @@ int nep_batch_fleet_ent_lists(nep_batch_t* h, nep_ent_lists* host_out, int32_t* 
  *   no gate          benchmark_mtlp waits for the MTLP comparator's acknowledgement before the next run; there is no comparator here.
  *   one rule set     both modes share the five tests (autoCMD has 1-3, benchmark_mtlp 2, 4, 5); a test is off at parameter 0.
  *   quota            max_goals ends a campaign (the reference's scripts are stopped from outside or after 100 runs).
- *   use_moveback_    is nep_batch_fleet_moveback, below.  The single-agent A* benchmark branch of replanCB: not built.
+ *   use_moveback_    is nep_batch_fleet_moveback, below.  The single-agent A* benchmark branch of replanCB: include/neptune_hastar.h.
  *   given goals      auto_commands_together.py's fixed lists are nep_batch_fleet_mission_script with mode
  *                    NEP_MISSION_FLEET_TOGETHER, and benchmark_multi_direct.py's mean jerk is nep_batch_fleet_effort, both below.
  * Limits: the kernel stages a scene's end positions, new goals and keep-outs in 64 KB of LDS, sized once at

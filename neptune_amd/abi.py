@@ -292,6 +292,32 @@ class nep_fleet_snapshot_info(C.Structure):
     _fields_ = [("hdr", nep_fleet_snapshot_hdr), ("offset", C.c_int64 * NEP_SNAPSHOT_N_SECTIONS), ("bytes", C.c_int64 * NEP_SNAPSHOT_N_SECTIONS)]
 
 
+NEP_HASTAR_FLAG_HSIG, NEP_HASTAR_FLAG_CONT, NEP_HASTAR_FLAG_PATH, NEP_HASTAR_FLAG_POOL, NEP_HASTAR_FLAG_STATE = 1, 2, 4, 8, 16
+NEP_HASTAR_MAX_REP = 256
+NEP_HASTAR_POOL_PER_NODE = 8
+
+
+class nep_hastar_cfg(C.Structure):
+    """include/neptune_hastar.h: the homotopic grid A* of the single-agent benchmark (AstarPathFinder::init and this build's caps)."""
+    _fields_ = [("resolution", C.c_double), ("x_min", C.c_double), ("x_max", C.c_double), ("y_min", C.c_double), ("y_max", C.c_double),
+                ("z_min", C.c_double), ("z_max", C.c_double), ("cable_length", C.c_double), ("bias", C.c_double),
+                ("max_pops", C.c_int32), ("max_nodes", C.c_int32), ("hsig_cap", C.c_int32), ("cont_cap", C.c_int32), ("path_cap", C.c_int32)]
+
+
+class nep_hastar_result(C.Structure):
+    """include/neptune_hastar.h: one search's outcome and counters."""
+    _fields_ = [("status", C.c_int32), ("n_path", C.c_int32), ("nodes_used", C.c_int32), ("pops", C.c_int32), ("n_updates", C.c_int32),
+                ("n_length_checks", C.c_int32), ("n_cable_pruned", C.c_int32), ("flags", C.c_int32),
+                ("g_cells", C.c_double), ("length_m", C.c_double)]
+
+
+class nep_hastar_state(C.Structure):
+    """include/neptune_hastar.h: eu::ent_state_orig of many searches as a struct of arrays (host struct, host or device arrays)."""
+    _fields_ = [("hsig_cap", C.c_int32), ("cont_cap", C.c_int32), ("n_hsig", C.c_void_p), ("hsig_id", C.c_void_p), ("hsig_sign", C.c_void_p),
+                ("n_cont", C.c_void_p), ("cont", C.c_void_p)]
+
+
+HASTAR_RESULT_DTYPE = np.dtype(nep_hastar_result)
 SNAPSHOT_STAMP_DTYPE = np.dtype([("used", np.int32), ("round", np.int32), ("origin", np.int32), ("_pad", np.int32)])
 
 

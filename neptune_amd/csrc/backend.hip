@@ -24,6 +24,7 @@
 #include "recorder_common.h"
 #include "../../include/neptune_plan.h"
 #include "../../include/neptune_entangle.h"
+#include "../../include/neptune_hastar.h"
 
 using namespace nep;
 
@@ -2673,6 +2674,9 @@ int nep_abi_sizeof(int32_t which) {
     case 25: return (int)sizeof(nep_fleet_snapshot_hdr);      // (24 stays unassigned: tests/test_ent_lists_cpu.py pins it to -1)
     case 27: return (int)sizeof(nep_moveback_cfg);      // (26 stays unassigned: tests/test_fleet_recorder_cpu.py pins it to -1)
     case 29: return (int)sizeof(nep_fleet_effort);      // (28 stays unassigned: tests/test_fleet_moveback_cpu.py pins it to -1)
+    case 31: return (int)sizeof(nep_hastar_cfg);      // (30 stays unassigned: a test pins it to -1)
+    case 32: return (int)sizeof(nep_hastar_result);
+    case 33: return (int)sizeof(nep_hastar_state);
     default: return -1;
   }
 }
