@@ -61,6 +61,9 @@ FLEET_SIZE_EXPORTS = ["nep_batch_fleet_snapshot_bytes", "nep_batch_fleet_snapsho
 # every symbol include/neptune_hastar.h declares (nep_abi_sizeof and nep_last_error are neptune_backend.h's)
 HASTAR_EXPORTS = ["nep_hastar_create", "nep_hastar_destroy", "nep_hastar_set_inflated", "nep_hastar_set_uninflated", "nep_hastar_set_reps",
                   "nep_hastar_inflate", "nep_hastar_gjk", "nep_hastar_search_bytes", "nep_hastar_search", "nep_hastar_search_host", "nep_hastar_check"]
+# every symbol include/neptune_mtlp.h declares
+MTLP_EXPORTS = ["nep_mtlp_create", "nep_mtlp_destroy", "nep_mtlp_search_bytes", "nep_mtlp_solve", "nep_mtlp_solve_host", "nep_mtlp_check",
+                "nep_mtlp_circle_bases", "nep_mtlp_predicates_host", "nep_mtlp_predicates_device"]
 ENT_EXPORTS = ["nep_ent_sample_points", "nep_ent_propagate_segment", "nep_ent_propagate_guess", "nep_ent_case_ids", "nep_ent_track_step", "nep_ent_predict_a"]
 
 
@@ -261,13 +264,23 @@ def lib():
     L.nep_hastar_search.argtypes = [vp, i, vp, vp, vp, phs, vp, vp, phs, vp]
     L.nep_hastar_search_host.argtypes = [vp, i, vp, vp, vp, phs, vp, vp, phs]
     L.nep_hastar_check.argtypes = [vp, vp]
+    L.nep_mtlp_create.argtypes = [C.POINTER(abi.nep_mtlp_cfg)]; L.nep_mtlp_create.restype = vp
+    L.nep_mtlp_destroy.argtypes = [vp]; L.nep_mtlp_destroy.restype = None
+    L.nep_mtlp_search_bytes.argtypes = [vp]; L.nep_mtlp_search_bytes.restype = C.c_int64
+    L.nep_mtlp_solve.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp]
+    L.nep_mtlp_solve_host.argtypes = [vp, i, vp, vp, vp, vp, vp, vp]
+    L.nep_mtlp_check.argtypes = [vp, vp]
+    L.nep_mtlp_circle_bases.argtypes = [i, pd]
+    L.nep_mtlp_predicates_host.argtypes = [i, i, vp, vp, vp]
+    L.nep_mtlp_predicates_device.argtypes = [i, i, vp, vp, vp, vp]
     # the records this mirror builds with ctypes must have the library's layout (a library compiled from other headers would read
     # them at another stride): fail loudly at load, not as wrong numbers later
     L.nep_abi_sizeof.argtypes = [i]; L.nep_abi_sizeof.restype = i
     for which, struct in ((1, abi.nep_traj_rec), (5, abi.nep_guess), (6, abi.nep_solution), (11, abi.nep_fe_cfg), (12, abi.nep_fe_start),
                           (13, abi.nep_fe_result), (14, abi.nep_fe_ent_state), (17, abi.nep_audit), (18, abi.nep_fleet_cfg),
                           (20, abi.nep_mission_cfg), (21, abi.nep_mission_leg), (23, abi.nep_ent_lists), (25, abi.nep_fleet_snapshot_hdr), (27, abi.nep_moveback_cfg),
-                          (29, abi.nep_fleet_effort), (31, abi.nep_hastar_cfg), (32, abi.nep_hastar_result), (33, abi.nep_hastar_state)):
+                          (29, abi.nep_fleet_effort), (31, abi.nep_hastar_cfg), (32, abi.nep_hastar_result), (33, abi.nep_hastar_state),
+                          (35, abi.nep_mtlp_cfg), (36, abi.nep_mtlp_result)):
         if L.nep_abi_sizeof(which) != C.sizeof(struct):
             raise BackendError("%s: sizeof(%s) is %d in the library, %d in neptune_amd/abi.py — rebuild the library from this tree's headers"
                                % (LIB_PATH, struct.__name__, L.nep_abi_sizeof(which), C.sizeof(struct)))

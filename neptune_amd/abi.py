@@ -318,6 +318,25 @@ class nep_hastar_state(C.Structure):
 
 
 HASTAR_RESULT_DTYPE = np.dtype(nep_hastar_result)
+
+NEP_MTLP_FLAG_PATH, NEP_MTLP_FLAG_STATE, NEP_MTLP_FLAG_DEGEN = 1, 2, 4
+NEP_MTLP_MAX_ROBOTS = 64
+
+
+class nep_mtlp_cfg(C.Structure):
+    """include/neptune_mtlp.h: the MTLP comparator's set-up (mtlp::mtlp and this build's budgets)."""
+    _fields_ = [("resolution", C.c_double), ("x_min", C.c_double), ("x_max", C.c_double), ("y_min", C.c_double), ("y_max", C.c_double),
+                ("z_min", C.c_double), ("z_max", C.c_double), ("radius", C.c_double), ("bias", C.c_double),
+                ("n_robots", C.c_int32), ("max_nodes", C.c_int32), ("max_pops", C.c_int32), ("path_cap", C.c_int32)]
+
+
+class nep_mtlp_result(C.Structure):
+    """include/neptune_mtlp.h: one robot's search: outcome and counters."""
+    _fields_ = [("status", C.c_int32), ("n_path", C.c_int32), ("nodes_used", C.c_int32), ("pops", C.c_int32), ("n_updates", C.c_int32),
+                ("flags", C.c_int32), ("n_degenerate", C.c_int64), ("n_ball_only", C.c_int64), ("g_cells", C.c_double)]
+
+
+MTLP_RESULT_DTYPE = np.dtype(nep_mtlp_result)
 SNAPSHOT_STAMP_DTYPE = np.dtype([("used", np.int32), ("round", np.int32), ("origin", np.int32), ("_pad", np.int32)])
 
 

@@ -25,6 +25,7 @@
 #include "../../include/neptune_plan.h"
 #include "../../include/neptune_entangle.h"
 #include "../../include/neptune_hastar.h"
+#include "../../include/neptune_mtlp.h"
 
 using namespace nep;
 
@@ -2677,6 +2678,8 @@ int nep_abi_sizeof(int32_t which) {
     case 31: return (int)sizeof(nep_hastar_cfg);      // (30 stays unassigned: a test pins it to -1)
     case 32: return (int)sizeof(nep_hastar_result);
     case 33: return (int)sizeof(nep_hastar_state);
+    case 35: return (int)sizeof(nep_mtlp_cfg);      // (34 stays unassigned: tests/test_mtlp_cpu.py pins it to -1)
+    case 36: return (int)sizeof(nep_mtlp_result);
     default: return -1;
   }
 }
