@@ -69,25 +69,31 @@ def starts_of(name):
     return starts
 
 
-def fe_cfg(p, num_samples=5, pad_hold=0):
-    return scene.frontend_cfg(p, num_samples=num_samples, pad_hold=pad_hold, entangle=True)
+def fe_cfg(p, num_samples=5, pad_hold=0, ent_samples=3, setting=()):
+    """setting: (field, value) pairs written over scene.frontend_cfg's result (tests/fe_cfg_cases.py names them), ent_samples among them"""
+    fe = scene.frontend_cfg(p, num_samples=num_samples, pad_hold=pad_hold, entangle=True, ent_samples=ent_samples)
+    for k, v in setting:
+        setattr(fe, k, v)
+    return fe
 
 
 _WANT = {}
 
 
-def want(oracle, name, max_pops=None, order=None, num_samples=5, max_nodes=ref.MAX_NODES, agents=None, pad_hold=0):
-    """{agent: (guess, result dict, case block, counters)} of the ref with the check on, for the agents of set-up `name`"""
-    key = (name, max_pops, None if order is None else tuple(int(x) for x in order), num_samples, max_nodes, pad_hold)
+def want(oracle, name, max_pops=None, order=None, num_samples=5, max_nodes=ref.MAX_NODES, agents=None, pad_hold=0, ent_samples=3, setting=()):
+    """{agent: (guess, result dict, case block, counters)} of the ref with the check on, for the agents of set-up `name`, at fe_cfg's
+    configuration: the trajectories are sampled at its ent_samples, and the whole setting is part of the cache key"""
     sc, inits, pops = setup(name)
     p = sc["par"]
+    fe = fe_cfg(p, num_samples, pad_hold, ent_samples, setting)
+    key = (name, max_pops, None if order is None else tuple(int(x) for x in order), num_samples, max_nodes, pad_hold, int(fe.ent_samples),
+           tuple(sorted((str(k), v) for k, v in setting)))
     have = _WANT.setdefault(key, {})
     starts = starts_of(name)
-    fe = fe_cfg(p, num_samples, pad_hold)
     for a in (range(p.num_agents) if agents is None else agents):
         if a in have:
             continue
         hulls = oracle.hulls_of_scene(p, a + 1, sc["committed"], float(starts[a]["t_start"]), sc["statics"])
-        ent = helpers.ent_inputs(sc, a, t0=float(starts[a]["t_start"]), init=inits[a])
+        ent = helpers.ent_inputs(sc, a, num_samples=int(fe.ent_samples), t0=float(starts[a]["t_start"]), init=inits[a])
         have[a] = ref.astar(p, fe, a + 1, starts[a], hulls, sc["statics"], pops if max_pops is None else max_pops, order=order, max_nodes=max_nodes, ent=ent)
     return have

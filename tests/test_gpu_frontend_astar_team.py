@@ -131,11 +131,15 @@ def test_budgets_order_and_lattice(be, oracle, case):
 
 
 @pytest.mark.parametrize("ent_samples", [1, 8])
-def test_one_and_eight_sampled_steps(be, ent_samples):
-    """ent_samples 1 and 8 (the ref is pinned at 3): 25 and 200 (child, step) pairs, against the one-wave kernel."""
+def test_one_and_eight_sampled_steps(be, oracle, ent_samples):
+    """ent_samples 1 and 8: 25 and 200 (child, step) pairs, against the one-wave kernel — and against the ref, which samples the
+    trajectories at the same count (tests/test_fe_cfg_cases_cpu.py pins it away from the default configuration)."""
     bb, got = _device(be, "plain", max_pops=40, ent_samples=ent_samples)
     r = got[1]
     assert len({int(x) for x in r["status"]}) >= 2 and int(r["n_children"].max()) == 40 and int(r["n_entangled"].sum()) > 0, r
+    want = cases.want(oracle, "plain", max_pops=40, ent_samples=ent_samples)
+    for a in range(8):
+        _same(got, a, want[a], ("ent_samples", ent_samples, "agent", a))
     bb.check()
     bb.close()
 

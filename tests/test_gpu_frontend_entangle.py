@@ -201,40 +201,59 @@ def test_config5_style_device_made_guesses_and_cases(be):
     bb.close()
 
 
-@pytest.mark.parametrize("fast_add", [32, 0])
-def test_safety_pass_entangle_recheck(be, oracle, fast_add):
+@pytest.mark.parametrize("fast_add,ent_samples,made", [pytest.param(32, 3, False, id="32"), pytest.param(0, 3, False, id="0")] +
+                         [pytest.param(32, k, True, id="32-ent%d" % k) for k in (1, 2, 3, 5, 8)] + [pytest.param(0, 8, True, id="0-ent8")])
+def test_safety_pass_entangle_recheck(be, oracle, fast_add, ent_samples, made):
     """nep_batch_safety_commit_ent: the flags equal the oracle's entangleCheckGivenPwp on every new trajectory (against
     everybody's NEW trajectories), and a flagged agent keeps its previous record.  fast_add = 0: every interval with a
-    crossing goes through the re-check's big records (what a step of more than 32 new crossings does)."""
-    sc = scene.tether_crossing_scene(8, 6, 60)
-    p = sc["par"]; N = 8
+    crossing goes through the re-check's big records (what a step of more than 32 new crossings does).
+    made = False: the back end's own new trajectories of (8, 6, 60), at three samples — their first intervals cross no tether,
+    so every verdict there is "free".  made = True, ent_samples 1, 2, 3, 5 and 8 (ent_check_kernel builds its own trajectory's
+    sampled steps from the count, and everybody's samples are made at it): fe_cfg_cases.recheck_inputs on (16, 8, 66), new
+    trajectories that do cross a tether in their first interval — one flag per new trajectory against the oracle on inputs
+    sampled at the same count, both verdicts at every count (tests/test_fe_cfg_cases_cpu.py shows them)."""
+    import fe_cfg_cases as fc
+    sc = scene.tether_crossing_scene(*fc.RECHECK_SCENE) if made else scene.tether_crossing_scene(8, 6, 60)
+    p = sc["par"]; N = p.num_agents
     bb = be.BatchBackend(p, sc["statics"])
     bb.set_fe_ent_fast_caps(40, fast_add, 8)
     reps, longest = scene.static_reps(sc["statics"])
     bb.set_static_reps(reps, longest)
     T = bb.torch
     d_prev = bb.to_device(sc["committed"]); d_guess = bb.to_device(sc["guesses"])
-    bb.replan(d_prev, d_guess)
-    fresh = bb.commits()
-    # entangle states at the start that make some re-checks fire: a crossing with a neighbour already on the list
-    inits = np.zeros(N, dtype=abi.FE_ENT_STATE_DTYPE)
-    for a in range(N):
-        j = (a + 3) % N
-        inits[a]["n_alpha"] = 1; inits[a]["id"][0] = j + 1; inits[a]["cs"][0] = 1
+    if made:
+        fresh, inits = fc.recheck_inputs(sc)
+        d_new = bb.to_device(fresh)
+    else:
+        bb.replan(d_prev, d_guess)
+        fresh = bb.commits()
+        d_new = bb.d_commit
+        # entangle states at the start: a crossing with a neighbour already on the list
+        inits = np.zeros(N, dtype=abi.FE_ENT_STATE_DTYPE)
+        for a in range(N):
+            j = (a + 3) % N
+            inits[a]["n_alpha"] = 1; inits[a]["id"][0] = j + 1; inits[a]["cs"][0] = 1
     d_final = T.zeros_like(bb.d_commit); d_acc = T.zeros(N, dtype=T.int32, device=bb.device)
-    bb.safety_commit_ent(d_prev, bb.d_commit, d_guess, d_final, d_acc, d_ent_init=bb.to_device(inits))
+    bb.safety_commit_ent(d_prev, d_new, d_guess, d_final, d_acc, d_ent_init=bb.to_device(inits), ent_samples=ent_samples)
     T.cuda.synchronize()
     acc = d_acc.cpu().numpy(); fin = d_final.cpu().numpy().view(abi.TRAJ_REC_DTYPE)
     conflict = bb.debug_conflicts(0)
     want = []
     for a in range(N):
-        ent = helpers.ent_inputs(sc, a, recs=fresh, t0=float(sc["guesses"][a]["t_start"]), init=inits[a])
+        ent = helpers.ent_inputs(sc, a, num_samples=ent_samples, recs=fresh, t0=float(sc["guesses"][a]["t_start"]), init=inits[a])
         want.append(oracle.entangle_check_pwp(p, a + 1, p.tether_length, np.array(fresh[a]["pwp"]["coeff"])[0, 0], np.array(fresh[a]["pwp"]["coeff"])[1, 0], ent))
+    print("ent_samples %d: the oracle's verdicts %r" % (ent_samples, [int(w) for w in want]))
+    if made:
+        assert [int(w) for w in want] == fc.RECHECK_VERDICTS[ent_samples] and 0 < sum(want) < N, (ent_samples, want)
     accept = []
     for a in range(N):
         bad = want[a] or any(accept[j] and (conflict[a, j] or conflict[j, a]) for j in range(a))
         accept.append(0 if bad else 1)
     np.testing.assert_array_equal(acc, accept)
+    if made:
+        assert any(want[a] and not any(accept[j] and (conflict[a, j] or conflict[j, a]) for j in range(a)) for a in range(N))      # (a rejection that is the re-check's alone)
     for a in range(N):
         assert fin[a].tobytes() == (fresh[a] if accept[a] else sc["committed"][a]).tobytes()
+    if made:
+        bb.check()
     bb.close()
