@@ -144,6 +144,55 @@ int nep_ent_track_step(const nep_ent_cfg* cfg, const nep_ent_track_inputs* in, n
 int nep_ent_predict_a(const nep_ent_cfg* cfg, const double* pik, const double* pik1, const int32_t* present, const int32_t* bend_off,
                       const double* bend_xy, const nep_ent_state* in, const double pk[2], const double pk1[2], nep_ent_state* out);
 
+/* ---- The tether audit: taut length, slack and winding of every flown tick --------------------------------
+ * eu::getTetherLength of *state with the vehicle at pk1: base -> the anchors of the bend indices, + 2 x static_longest per static
+ * anchor, -> pk1, summed in that order — the very expression nep_ent_track_step compares with cfg->cable_length.  What the
+ * reference prints from pubCB every 100 ms (neptune_ros.cpp:1264-1267).  cfg: num_agents, id, pb and the statics are read.
+ * Returns NEP_OK, or NEP_E_ARG (a null argument, a malformed state, a bend index that names nobody).                        */
+int nep_ent_tether_length(const nep_ent_cfg* cfg, const nep_ent_state* state, const double pk1[2], double* len);
+
+/* One record per (scene, agent); nep_abi_sizeof(37): 120 bytes.  One tracked move is one tick.  Calls accumulate into it; the
+ * ticks of a whole flight are numbered from 1 (`tick_*` fields and `entangled_partner`, `wind_partner`: 0 = never / nobody).
+ * The length of a tick is taken on the state after its move with the vehicle at that tick's position; on a dropped move
+ * (NEP_ENT_TRACK_CAP) on the state that was kept — it lies behind the tether, n_dropped says so — and the other flag counters
+ * stand still.  A maximum is replaced only by a strictly larger value: ties go to the earlier tick and, within a tick, to the
+ * lower agent id.  Initial values (nep_tether_audit_init): max_len -inf, every time 0.0, everything else 0.                  */
+typedef struct nep_tether_audit {
+  double max_len;                 /* the largest taut length after a tracked move                                       */
+  double t_max_len;               /* ... the time of that tick                                                          */
+  double sum_len;                 /* running sum over the audited ticks, added in tick order (mean = sum_len / n_ticks)  */
+  double last_len;                /* the length at the last audited tick                                                */
+  double t_first_too_long;
+  double t_first_entangled;
+  double t_max_wind;
+  int32_t tick_max_len;           /* the value of n_ticks after counting that tick                                      */
+  int32_t n_ticks;                /* ticks audited                                                                      */
+  int32_t n_too_long;             /* ticks whose move returned NEP_ENT_TRACK_TOO_LONG                                   */
+  int32_t n_entangled;            /* ... NEP_ENT_TRACK_ENTANGLED                                                        */
+  int32_t n_two_cases;            /* ... NEP_ENT_TRACK_TWO_CASES                                                        */
+  int32_t n_abort;                /* ... NEP_ENT_TRACK_ABORT                                                            */
+  int32_t n_dropped;              /* ticks whose move was dropped (NEP_ENT_TRACK_CAP)                                   */
+  int32_t tick_first_too_long;
+  int32_t tick_first_entangled;
+  int32_t entangled_partner;      /* 1-based id of the lowest agent i with active_cases[i] > 2 at that tick              */
+  int32_t max_alpha;              /* the largest n_alpha / n_bend the state held after a tick                           */
+  int32_t max_bend;
+  int32_t max_wind;               /* the largest active_cases[i] over the agents i, as the ENTANGLED rule reads it        */
+  int32_t wind_partner;           /* ... 1-based id of the lowest such i                                                */
+  int32_t tick_max_wind;
+  int32_t crossings_added;        /* sum over ticks of the new crossings the moves produced (the step list before the merge;
+                                     a move with more than NEP_ENT_TRACK_ADD_CAP counts NEP_ENT_TRACK_ADD_CAP)            */
+} nep_tether_audit;
+
+/* out[0..n) = the initial values.  NEP_E_ARG for a null pointer or n < 0.                                                    */
+int nep_tether_audit_init(nep_tether_audit* out, int64_t n);
+
+/* nep_ent_track_step plus one tick accumulated into *a, `t` the tick's time (t0 + (double)q * dt for tick q = 1.. of a stretch):
+ * the same return value, the same *state.  A call that returns NEP_E_ARG audits nothing.  nep_batch_set_tether_audit
+ * (include/neptune_frontend.h) is the device form; the two are equal byte for byte.                                         */
+int nep_ent_track_step_audit(const nep_ent_cfg* cfg, const nep_ent_track_inputs* in, nep_ent_state* state, const double pk[2],
+                             const double pk1[2], double t, nep_tether_audit* a);
+
 #ifdef __cplusplus
 }
 #endif

@@ -157,7 +157,11 @@ int nep_batch_fleet_predict_ent(nep_batch_t* h, const nep_fe_start* d_start, con
  * them.  The others' bend lists are d_records' (published this round); at the first tick only, the list an agent published a round
  * ago counts as the previous check's (an empty one: as the current one).  Every slot is tracked — active or not, arrived or not.
  * The flags are ORed over the ticks into d_flags ([slots], may be NULL) and into the sticky word; a CAP (that tick's move is
- * dropped) raises NEP_FLAG_ENT_TRACK.  Asynchronous, capturable.                                                              */
+ * dropped) raises NEP_FLAG_ENT_TRACK.  Asynchronous, capturable.
+ * With a buffer registered by nep_batch_set_tether_audit (include/neptune_frontend.h) every tick is also one tick of the slot's
+ * nep_tether_audit (include/neptune_entangle.h) — taut length, windings, list and bend counts, flag and drop counts — at
+ * t_now + q * dc, t_now the scene's clock as nep_batch_fleet_counters reports it before the round's nep_batch_fleet_tick; states,
+ * flags and records are those of the call without it.  nep_batch_fleet_predict_ent never audits: it flies nothing.           */
 int nep_batch_fleet_track_ent(nep_batch_t* h, const nep_traj_rec* d_records, int32_t* d_flags, void* stream);
 
 /* Blocking reader (host memory, each may be NULL): the states at the tracked positions, the last tracked round's flags, the sticky
@@ -183,7 +187,9 @@ int nep_batch_fleet_ent_state(nep_batch_t* h, nep_fe_ent_state* states_out, int3
  * nep_batch_fleet_ent_lists   blocking reader: host_out's arrays (host_out->cap == the handle's, else NEP_E_ARG; may be NULL) and
  *                         held_rounds_out ([slots], may be NULL).  NEP_E_STATE on a handle that is not on the list form.
  * nep_batch_fleet_ent_state on such a handle fills states_out for the slots that fit a fixed record; a slot that does not gets
- * n_alpha = -1 and zeros.                                                                                                        */
+ * n_alpha = -1 and zeros.
+ * The tether audit (nep_batch_set_tether_audit) runs on the list form as on the fixed record: nep_batch_fleet_track_ent folds every
+ * tick into the registered buffer, and max_alpha is the headroom against the handle's capacity.                                  */
 int nep_batch_fleet_init_ent_lists(nep_batch_t* h, double cable_length, const nep_ent_lists* host_lists, void* stream);
 int nep_batch_fleet_ent_lists(nep_batch_t* h, nep_ent_lists* host_out, int32_t* held_rounds_out);
 

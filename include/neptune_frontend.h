@@ -352,7 +352,9 @@ int nep_batch_safety_commit_ent(nep_batch_t* h, const nep_traj_rec* d_prev, cons
  * A tracked slot's state comes back with id / cs / beta beyond n_alpha and bend beyond n_bend ZEROED (the bytes of a state
  * depend on the state alone, as with nep_batch_fleet_track_ent, whose kernel this call runs); earlier versions left there
  * what the list surgery had left.  Nothing reads those entries.  The debug option fleet_ent_proof applies (same states).
- * (The faithful fleet loop tracks per control tick instead: nep_batch_fleet_track_ent, include/neptune_fleet.h.)              */
+ * (The faithful fleet loop tracks per control tick instead: nep_batch_fleet_track_ent, include/neptune_fleet.h.)
+ * With a buffer registered by nep_batch_set_tether_audit (below) every sampled step of a tracked slot is also one tick of the
+ * slot's nep_tether_audit, at t_start + q * dt, q = 1..n_intervals * ent_samples; the call's other outputs do not change.       */
 int nep_batch_track_ent(nep_batch_t* h, const nep_traj_rec* d_prev, nep_traj_rec* d_records, const nep_guess* d_guess,
                         int32_t n_intervals, int32_t ent_samples, double cable_length, nep_fe_ent_state* d_ent,
                         int32_t* d_flags, void* stream);
@@ -386,10 +388,26 @@ typedef struct nep_ent_lists {
  * would outgrow d_lists->cap crossings, NEP_MAX_BEND - 1 bend points or NEP_ENT_TRACK_ADD_CAP new crossings is dropped:
  * NEP_ENT_TRACK_CAP in d_flags, NEP_E_CAP from nep_batch_check.  A slot whose counts or bend indices are out of range on the way
  * in keeps its state and gets NEP_ENT_TRACK_CAP, like a malformed fixed record.  Bit-identical to chaining nep_ent_track_step
- * with state->cap = d_lists->cap.  The working list of a slot sits in LDS: 11 bytes per entry (45 KB at the largest cap).   */
+ * with state->cap = d_lists->cap.  The working list of a slot sits in LDS: 11 bytes per entry (45 KB at the largest cap).
+ * The tether audit (nep_batch_set_tether_audit, below) counts its steps like nep_batch_track_ent's; max_alpha is then the
+ * headroom against d_lists->cap.                                                                                            */
 int nep_batch_track_ent_lists(nep_batch_t* h, const nep_traj_rec* d_prev, nep_traj_rec* d_records, const nep_guess* d_guess,
                               int32_t n_intervals, int32_t ent_samples, double cable_length, const nep_ent_lists* d_lists,
                               int32_t* d_flags, void* stream);
+
+/* The tether audit (include/neptune_entangle.h: nep_tether_audit).  Registers d_audit, a [n_scenes][N] device
+ * buffer holding nep_tether_audit_init's values or an earlier flight's records; d_audit == NULL switches the audit off again.
+ * While a buffer is registered, nep_batch_track_ent, nep_batch_track_ent_lists and nep_batch_fleet_track_ent (fixed records and
+ * the list form, include/neptune_fleet.h) accumulate one tick per tracked move into it, inside the launch that tracks: tick
+ * q = 1.. of a call lies at t0 + (double)q * dt, t0 the scene's t_start as the call reads it from d_guess (between rounds) or the
+ * scene's fleet clock (nep_batch_fleet_counters' t_now), and dt the value given here — 0: the call's own step, T_span / ent_samples
+ * or the fleet's dc.  A slot the tracking skips (no trajectory, a malformed state or list) audits nothing, and the predictions
+ * (nep_batch_fleet_predict_ent, nep_batch_ent_lists_at_a) never audit: they fly nothing.  Equal byte for byte to chaining
+ * nep_ent_track_step_audit on the host.  States, flags, bend points and records are those of a call without the audit, and
+ * without a registered buffer the step kernels that run are the plain ones.  Synchronises nothing; call it outside a capture (a
+ * captured graph keeps the buffer it was captured with).  NEP_E_ARG: dt < 0 or NaN; NEP_E_STATE: a sharded handle.              */
+struct nep_tether_audit;
+int nep_batch_set_tether_audit(nep_batch_t* h, struct nep_tether_audit* d_audit, double dt);
 
 /* The state at A the front end and the safety re-check take, from the list form, for a loop that tracks between rounds (the
  * fleet's nep_batch_fleet_predict_ent has the same rule, include/neptune_fleet.h): d_ent_a[slot] receives the slot's list as a

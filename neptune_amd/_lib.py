@@ -47,7 +47,7 @@ PLAN_EXPORTS = [
 ]
 # every symbol include/neptune_entangle.h declares (host-only)
 # include/neptune_frontend.h
-FE_EXPORTS = ["nep_batch_frontend", "nep_batch_frontend_hulls", "nep_batch_set_fe_astar", "nep_batch_frontend_astar", "nep_batch_frontend_astar_ent", "nep_batch_set_fe_astar_team", "nep_batch_fe_astar_team", "nep_batch_goal_gate", "nep_batch_set_static_reps", "nep_batch_set_fe_ent_big_records", "nep_batch_frontend_ent", "nep_batch_frontend_ent_hulls", "nep_batch_safety_commit_ent", "nep_batch_track_ent", "nep_batch_track_ent_lists", "nep_batch_ent_lists_at_a", "nep_batch_next_starts", "nep_batch_audit", "nep_audit_records", "nep_audit_init"]
+FE_EXPORTS = ["nep_batch_frontend", "nep_batch_frontend_hulls", "nep_batch_set_fe_astar", "nep_batch_frontend_astar", "nep_batch_frontend_astar_ent", "nep_batch_set_fe_astar_team", "nep_batch_fe_astar_team", "nep_batch_goal_gate", "nep_batch_set_static_reps", "nep_batch_set_fe_ent_big_records", "nep_batch_frontend_ent", "nep_batch_frontend_ent_hulls", "nep_batch_safety_commit_ent", "nep_batch_track_ent", "nep_batch_track_ent_lists", "nep_batch_ent_lists_at_a", "nep_batch_next_starts", "nep_batch_audit", "nep_audit_records", "nep_audit_init", "nep_batch_set_tether_audit"]
 # include/neptune_fleet.h
 FLEET_EXPORTS = ["nep_batch_fleet_init", "nep_batch_fleet_select", "nep_batch_fleet_commit", "nep_batch_fleet_tick", "nep_batch_fleet_ring_cap",
                  "nep_batch_fleet_plans", "nep_batch_fleet_state", "nep_batch_fleet_counters", "nep_batch_fleet_init_ent", "nep_batch_fleet_predict_ent",
@@ -64,7 +64,8 @@ HASTAR_EXPORTS = ["nep_hastar_create", "nep_hastar_destroy", "nep_hastar_set_inf
 # every symbol include/neptune_mtlp.h declares
 MTLP_EXPORTS = ["nep_mtlp_create", "nep_mtlp_destroy", "nep_mtlp_search_bytes", "nep_mtlp_solve", "nep_mtlp_solve_host", "nep_mtlp_check",
                 "nep_mtlp_circle_bases", "nep_mtlp_predicates_host", "nep_mtlp_predicates_device"]
-ENT_EXPORTS = ["nep_ent_sample_points", "nep_ent_propagate_segment", "nep_ent_propagate_guess", "nep_ent_case_ids", "nep_ent_track_step", "nep_ent_predict_a"]
+ENT_EXPORTS = ["nep_ent_sample_points", "nep_ent_propagate_segment", "nep_ent_propagate_guess", "nep_ent_case_ids", "nep_ent_track_step", "nep_ent_predict_a",
+               "nep_ent_tether_length", "nep_tether_audit_init", "nep_ent_track_step_audit"]
 
 
 class BackendError(RuntimeError):
@@ -196,6 +197,10 @@ def lib():
     L.nep_ent_case_ids.argtypes = [i, i, pi, pi, pi, i, pi]
     L.nep_ent_track_step.argtypes = [pcfg, C.POINTER(abi.nep_ent_track_inputs), pst, pd, pd]
     L.nep_ent_predict_a.argtypes = [pcfg, pd, pd, pi, pi, pd, pst, pd, pd, pst]
+    L.nep_ent_tether_length.argtypes = [pcfg, pst, pd, pd]
+    L.nep_tether_audit_init.argtypes = [vp, C.c_int64]
+    L.nep_ent_track_step_audit.argtypes = [pcfg, C.POINTER(abi.nep_ent_track_inputs), pst, pd, pd, d, vp]
+    L.nep_batch_set_tether_audit.argtypes = [vp, vp, d]
     L.nep_batch_frontend.argtypes = [vp, C.POINTER(abi.nep_fe_cfg), vp, vp, vp, vp, vp]
     L.nep_batch_frontend_hulls.argtypes = [vp, C.POINTER(abi.nep_fe_cfg), vp, i, vp, vp, vp, vp]
     L.nep_batch_set_fe_astar.argtypes = [vp, i, i, pi, i]
@@ -280,7 +285,7 @@ def lib():
                           (13, abi.nep_fe_result), (14, abi.nep_fe_ent_state), (17, abi.nep_audit), (18, abi.nep_fleet_cfg),
                           (20, abi.nep_mission_cfg), (21, abi.nep_mission_leg), (23, abi.nep_ent_lists), (25, abi.nep_fleet_snapshot_hdr), (27, abi.nep_moveback_cfg),
                           (29, abi.nep_fleet_effort), (31, abi.nep_hastar_cfg), (32, abi.nep_hastar_result), (33, abi.nep_hastar_state),
-                          (35, abi.nep_mtlp_cfg), (36, abi.nep_mtlp_result)):
+                          (35, abi.nep_mtlp_cfg), (36, abi.nep_mtlp_result), (37, abi.nep_tether_audit)):
         if L.nep_abi_sizeof(which) != C.sizeof(struct):
             raise BackendError("%s: sizeof(%s) is %d in the library, %d in neptune_amd/abi.py — rebuild the library from this tree's headers"
                                % (LIB_PATH, struct.__name__, L.nep_abi_sizeof(which), C.sizeof(struct)))

@@ -211,6 +211,16 @@ class nep_audit(C.Structure):
                 ("n_ticks", C.c_int32), ("n_pair_viol", C.c_int32), ("n_static_viol", C.c_int32)]
 
 
+class nep_tether_audit(C.Structure):
+    """include/neptune_entangle.h: the tether audit of one (scene, agent); the tracking calls accumulate one tick per move into it."""
+    _fields_ = [("max_len", C.c_double), ("t_max_len", C.c_double), ("sum_len", C.c_double), ("last_len", C.c_double),
+                ("t_first_too_long", C.c_double), ("t_first_entangled", C.c_double), ("t_max_wind", C.c_double),
+                ("tick_max_len", C.c_int32), ("n_ticks", C.c_int32), ("n_too_long", C.c_int32), ("n_entangled", C.c_int32),
+                ("n_two_cases", C.c_int32), ("n_abort", C.c_int32), ("n_dropped", C.c_int32), ("tick_first_too_long", C.c_int32),
+                ("tick_first_entangled", C.c_int32), ("entangled_partner", C.c_int32), ("max_alpha", C.c_int32), ("max_bend", C.c_int32),
+                ("max_wind", C.c_int32), ("wind_partner", C.c_int32), ("tick_max_wind", C.c_int32), ("crossings_added", C.c_int32)]
+
+
 class nep_fleet_cfg(C.Structure):
     """include/neptune_fleet.h: nep_plan_cfg's fields plus what a bulk-synchronous round needs (nep_batch_fleet_init)."""
     _fields_ = [("dc", C.c_double), ("T_span", C.c_double), ("lower_bound_runtime", C.c_double),
@@ -351,6 +361,7 @@ FE_START_DTYPE = np.dtype(nep_fe_start)
 FE_RESULT_DTYPE = np.dtype(nep_fe_result)
 FE_ENT_STATE_DTYPE = np.dtype(nep_fe_ent_state)
 AUDIT_DTYPE = np.dtype(nep_audit)
+TETHER_AUDIT_DTYPE = np.dtype(nep_tether_audit)
 PWP_DTYPE = np.dtype(nep_pwp)
 MISSION_LEG_DTYPE = np.dtype(nep_mission_leg)
 EFFORT_DTYPE = np.dtype(nep_fleet_effort)

@@ -1,7 +1,11 @@
 """Flight audit (include/neptune_frontend.h: nep_audit): per-agent clearances of what the fleets fly, at the control ticks.
 
 `audit_records` is the host form through ctypes (nep_audit_records, no HIP call behind it); the device form is
-BatchBackend.audit and equals it bit for bit.  `summarize` turns the per-agent records into one line of facts per scene."""
+BatchBackend.audit and equals it bit for bit.  `summarize` turns the per-agent records into one line of facts per scene.
+
+Tether audit (include/neptune_entangle.h: nep_tether_audit): taut length, slack and winding of every tracked move.
+`tether_audit_records` is the host form (a chain of nep_ent_track_step_audit); the device form is BatchBackend.set_tether_audit and
+equals it byte for byte.  `summarize_tethers` gives the facts per scene, `format_tether_summary` the lines the scripts print."""
 import ctypes as C
 
 import numpy as np
@@ -77,4 +81,88 @@ def format_summary(summary):
     lines.append("audit ticks %d  pair violations %d (agent-ticks, in %d scenes)  static violations %d (in %d scenes)  of %d scenes"
                  % (max(sc["n_ticks"] for sc in summary), sum(sc["n_pair_viol"] for sc in summary), sum(sc["n_pair_viol"] > 0 for sc in summary),
                     sum(sc["n_static_viol"] for sc in summary), sum(sc["n_static_viol"] > 0 for sc in summary), len(summary)))
+    return lines
+
+
+# ---- the tether audit ---------------------------------------------------------------------------------------------------------
+def new_tether_audit(n):
+    """n records with the initial values: max_len -inf, every partner, tick and time 0, the rest 0 (nep_tether_audit_init)"""
+    out = np.zeros(n, dtype=abi.TETHER_AUDIT_DTYPE)
+    check(lib().nep_tether_audit_init(out.ctypes.data_as(C.c_void_p), n))
+    return out
+
+
+def tether_audit_records(chk, state, moves, t0, dt, out=None):
+    """One agent's tether over a stretch of tracked moves, on the host: chk its entangle.EntangleCheck, state its entangle.State
+    (updated in place), moves a sequence of track_step's arguments (pk, pk1, pik, pik1, present, bendpts, bendpts_prev); move
+    q = 1.. is the tick at t0 + q * dt.  Accumulates into `out` ([1] TETHER_AUDIT_DTYPE, made fresh when None);
+    -> (out, the moves' NEP_ENT_TRACK_* bits)."""
+    if out is None:
+        out = new_tether_audit(1)
+    flags = []
+    for q, m in enumerate(moves, 1):
+        flags.append(chk.track_step(state, *m, audit=out, t=t0 + float(q) * dt))
+    return out, flags
+
+
+def summarize_tethers(records, cable_length, n_scenes=1):
+    """records: [n_scenes*N] TETHER_AUDIT_DTYPE (or the bytes of it) -> one dict per scene: the smallest slack cable_length - max_len
+    with agent (1-based id) and time, the mean length, the largest list and bend counts, the largest wind with the pair
+    (agent, partner; 1-based) and time, and the ticks too long / entangled / dropped (agent-ticks)"""
+    a = np.asarray(records)
+    if a.dtype != abi.TETHER_AUDIT_DTYPE:
+        a = a.view(abi.TETHER_AUDIT_DTYPE)
+    a = a.reshape(n_scenes, -1)
+    out = []
+    for s in range(n_scenes):
+        r = a[s]
+        seen = r["n_ticks"] > 0
+        d = dict(min_slack=None, mean_len=None, max_alpha=int(r["max_alpha"].max()) if len(r) else 0, max_bend=int(r["max_bend"].max()) if len(r) else 0,
+                 max_wind=None, n_ticks=int(r["n_ticks"].max()) if len(r) else 0, n_too_long=int(r["n_too_long"].sum()),
+                 n_entangled=int(r["n_entangled"].sum()), n_two_cases=int(r["n_two_cases"].sum()), n_abort=int(r["n_abort"].sum()),
+                 n_dropped=int(r["n_dropped"].sum()), crossings_added=int(r["crossings_added"].sum()))
+        if seen.any():
+            i = int(np.argmax(np.where(seen, r["max_len"], -np.inf)))
+            d["min_slack"] = dict(value=float(cable_length - r["max_len"][i]), agent=i + 1, t=float(r["t_max_len"][i]), tick=int(r["tick_max_len"][i]))
+            d["mean_len"] = float(r["sum_len"][seen].sum() / r["n_ticks"][seen].sum())
+            w = int(np.argmax(r["max_wind"]))
+            if r["max_wind"][w] > 0:
+                d["max_wind"] = dict(value=int(r["max_wind"][w]), agent=w + 1, partner=int(r["wind_partner"][w]), t=float(r["t_max_wind"][w]),
+                                     tick=int(r["tick_max_wind"][w]))
+        out.append(d)
+    return out
+
+
+def format_tether_summary(summary, cap=None):
+    """the lines scripts/fleet_loop.py, scripts/tether_loop.py and scripts/closed_loop.py print: the scene with the least slack, the
+    scene with the largest wind, the largest counts (next to `cap`, the list capacity in force, when given) and the tick counts"""
+    lines = []
+    best = None
+    for s, sc in enumerate(summary):
+        m = sc["min_slack"]
+        if m is not None and (best is None or m["value"] < best[1]["value"]):
+            best = (s, m)
+    if best is None:
+        lines.append("tether min_slack        none")
+    else:
+        s, m = best
+        lines.append("tether min_slack        %+.9f m  scene %d  agent %d  t %.3f s (tick %d)" % (m["value"], s, m["agent"], m["t"], m["tick"]))
+    means = [sc["mean_len"] for sc in summary if sc["mean_len"] is not None]
+    if means:
+        lines.append("tether mean_len         %.6f m (mean over %d scenes)" % (float(np.mean(means)), len(means)))
+    wind = None
+    for s, sc in enumerate(summary):
+        m = sc["max_wind"]
+        if m is not None and (wind is None or m["value"] > wind[1]["value"]):
+            wind = (s, m)
+    if wind is None:
+        lines.append("tether max_wind         0")
+    else:
+        s, m = wind
+        lines.append("tether max_wind         %d  scene %d  agent %d round agent %d  t %.3f s (tick %d)" % (m["value"], s, m["agent"], m["partner"], m["t"], m["tick"]))
+    lines.append("tether max_alpha %d%s  max_bend %d (of %d)" % (max(sc["max_alpha"] for sc in summary), " (cap %d)" % cap if cap is not None else "",
+                                                                 max(sc["max_bend"] for sc in summary), abi.NEP_MAX_BEND - 1))
+    lines.append("tether ticks %d  too long %d  entangled %d  dropped %d (agent-ticks)  crossings added %d  of %d scenes"
+                 % (max(sc["n_ticks"] for sc in summary), sum(sc["n_too_long"] for sc in summary), sum(sc["n_entangled"] for sc in summary),
+                    sum(sc["n_dropped"] for sc in summary), sum(sc["crossings_added"] for sc in summary), len(summary)))
     return lines

@@ -449,6 +449,18 @@ class BatchBackend:
         st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
         check(lib().nep_batch_audit(self._h, d_records.data_ptr(), d_start.data_ptr(), float(tick), int(n_ticks), d_audit.data_ptr(), st.cuda_stream))
 
+    def new_tether_audit(self):
+        """device buffer of n_scenes*N tether-audit records with the initial values (TETHER_AUDIT_DTYPE bytes; nep_tether_audit_init)"""
+        from . import audit
+        return self.to_device(audit.new_tether_audit(self.n_scenes * self.par.num_agents))
+
+    def set_tether_audit(self, d_audit, dt=0.0):
+        """registers d_audit ([n_scenes*N] TETHER_AUDIT_DTYPE bytes; None: off) with the tracking calls, which then accumulate one tick
+        per tracked move into it; dt the time between two ticks, 0 = each call's own step (nep_batch_set_tether_audit).  The caller
+        keeps the buffer alive while it is registered"""
+        check(lib().nep_batch_set_tether_audit(self._h, d_audit.data_ptr() if d_audit is not None else None, float(dt)))
+        self._tether_audit = d_audit
+
     # ---- the committed plans on the device (include/neptune_fleet.h) ---------------------------------------------
     def fleet_init(self, cfg, d_state0, d_goal, d_period=None, d_phase=None, stream=None):
         """allocates / re-seeds the fleet state (nep_batch_fleet_init): cfg abi.nep_fleet_cfg, d_state0 [slots][12] and d_goal [slots][3]

@@ -1023,6 +1023,8 @@ struct nep_batch {
   const nep_traj_rec* fe_committed = nullptr;   // the records nep_batch_frontend built this round's hulls from
   int ent_ns = 3;                               // num_sample_per_interval the hull blocks reserve room for (nep_batch_set_ent_samples; yaml: 3)
   bool replanned = false;                       // a replan with a QP half has been enqueued (nep_batch_guess_fallback needs one before it)
+  // nep_batch_set_tether_audit: the caller's [slots] records the tracking calls accumulate into (null: off) and the tick's length
+  nep_tether_audit* tether_audit = nullptr; double tether_audit_dt = 0.0;
   // nep_batch_fleet_* (include/neptune_fleet.h): the committed plans of every slot, allocated by nep_batch_fleet_init
   struct Fleet {
     bool ready = false, timers = false; int cap = 0; nep_fleet_cfg cfg{};
@@ -1612,6 +1614,10 @@ int track_ent_round(nep_batch_t* h, const nep_traj_rec* d_prev, nep_traj_rec* d_
   ea.prev_n = (const char*)&d_prev->n_bend; ea.prev_xy = (const char*)&d_prev->bend[0][0]; ea.prev_n_stride = ea.prev_xy_stride = (long)sizeof(nep_traj_rec);
   ea.in = d_ent; ea.out = d_ent; ea.save = E.d_track_save.p; ea.flags = d_flags ? d_flags : E.d_track_flags.p; ea.gflags = ps.flags;
   if (lists) { ea.lists = *lists; ea.lsave = E.d_track_lsave.view(); ea.lsave.cap = lists->cap; }      // (the scratch is indexed at the call's cap)
+  if (h->tether_audit) {      // one tick per sampled step, from the scene's t_start (the first agent's, as the sampling reads it)
+    ea.audit = h->tether_audit; ea.audit_t0 = (const char*)&d_guess->t_start; ea.audit_t0_stride = (long)sizeof(nep_guess) * N;
+    ea.audit_dt = h->tether_audit_dt > 0.0 ? h->tether_audit_dt : E.sp.T_span / ent_samples;
+  }
   launch_tether_steps(ea, FleetArgs{}, (hipStream_t)stream);
   launch_tether_publish(ea, false, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
@@ -1629,6 +1635,13 @@ int nep_batch_track_ent_lists(nep_batch_t* h, const nep_traj_rec* d_prev, nep_tr
                               int32_t ent_samples, double cable_length, const nep_ent_lists* d_lists, int32_t* d_flags, void* stream) {
   if (!d_lists) return fail(NEP_E_ARG, "null argument");
   return track_ent_round(h, d_prev, d_records, d_guess, n_intervals, ent_samples, cable_length, nullptr, d_lists, d_flags, stream);
+}
+
+int nep_batch_set_tether_audit(nep_batch_t* h, nep_tether_audit* d_audit, double dt) {
+  if (!h || !(dt >= 0.0)) return fail(NEP_E_ARG, "bad arguments");
+  if (h->cfg.n_local != h->cfg.num_agents) return fail(NEP_E_STATE, "tether tracking runs on an unsharded handle (n_local == num_agents)");
+  h->tether_audit = d_audit; h->tether_audit_dt = d_audit ? dt : 0.0;
+  return 0;
 }
 
 int nep_batch_ent_lists_at_a(nep_batch_t* h, const nep_ent_lists* d_lists, nep_fe_ent_state* d_ent_a, int32_t* d_flags_a, const int32_t* d_mask_in,
@@ -1851,6 +1864,10 @@ int nep_batch_fleet_track_ent(nep_batch_t* h, const nep_traj_rec* d_records, int
   fleet_ent_args(h, ea);
   ea.n_steps = h->fleet.cfg.round_ticks; ea.start = nullptr; ea.recs = d_records; ea.out = h->fleet.ent.p;
   ea.flags = d_flags ? d_flags : h->fleet.ent_flags.p;
+  if (h->tether_audit) {      // one tick per control tick, from the scene's fleet clock
+    ea.audit = h->tether_audit; ea.audit_t0 = (const char*)h->fleet.t_now.p; ea.audit_t0_stride = (long)sizeof(double);
+    ea.audit_dt = h->tether_audit_dt > 0.0 ? h->tether_audit_dt : h->fleet.cfg.dc;
+  }
   launch_tether_steps(ea, fa, (hipStream_t)stream);
   if (d_flags) HIPCHK(hipMemcpyAsync(h->fleet.ent_flags.p, d_flags, (size_t)h->slots * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   HIPCHK(hipGetLastError());
@@ -2680,6 +2697,7 @@ int nep_abi_sizeof(int32_t which) {
     case 33: return (int)sizeof(nep_hastar_state);
     case 35: return (int)sizeof(nep_mtlp_cfg);      // (34 stays unassigned: tests/test_mtlp_cpu.py pins it to -1)
     case 36: return (int)sizeof(nep_mtlp_result);
+    case 37: return (int)sizeof(nep_tether_audit);
     default: return -1;
   }
 }

@@ -14,6 +14,10 @@
 
 #include "nep_device.h"
 #include "../../include/neptune_entangle.h"
+#ifndef NEP_TETHER_AUDIT_FN
+#define NEP_TETHER_AUDIT_FN __device__ __forceinline__
+#endif
+#include "tether_audit_common.h"
 
 namespace nep {
 
@@ -511,13 +515,21 @@ __device__ bool ent_state_ok(const nep_fe_ent_state* st) {
 // the caller collected for the move, `abort` what ent_cross_agent_changed returned for them.  save() runs before a move that can
 // outgrow the record and restore() when it did; such a move is dropped, as is one with more new crossings than `add` takes.
 // -> the move's NEP_ENT_TRACK_* bits.
-template <class ST, class SAVE, class RESTORE>
-__device__ __forceinline__ int ent_track_move(EntAdd& add, ST* W, SAVE save, RESTORE restore, Ev2 pk, Ev2 pk1, Ev2 pb_self, const EntCtx& c, double cable, bool abort) {
-  if (add.overflow) return NEP_ENT_TRACK_CAP;
+// AUDIT: *tk also receives the tick as the tether audit sees it (tether_audit_common.h; tk->t is the caller's) — the length the move
+// compared with the cable, handed out instead of computed again, and on a dropped move the length and windings of the state kept.
+template <bool AUDIT, class ST, class SAVE, class RESTORE>
+__device__ __forceinline__ int ent_track_move_any(EntAdd& add, ST* W, SAVE save, RESTORE restore, Ev2 pk, Ev2 pk1, Ev2 pb_self, const EntCtx& c, double cable, bool abort,
+                                                  nep_tether_audit_impl::TetherTick* tk) {
+  if constexpr (AUDIT) { tk->n_add = add.n; tk->wind = 0; tk->wind_partner = 0; tk->ent_partner = 0; }
+  auto dropped = [&]() {      // (AUDIT only) the tick of a dropped move: the state that was kept
+    for (int e = 0; e < W->n_alpha; e++) { const int id_ = W->id[e]; if (id_ <= c.N) nep_tether_audit_impl::tether_wind(*tk, id_, ent_count(W->id, W->n_alpha, id_)); }
+    tk->flags = NEP_ENT_TRACK_CAP; tk->n_alpha = W->n_alpha; tk->n_bend = W->n_bend; tk->len = ent_tether(W, pb_self, pk1, c);
+  };
+  if (add.overflow) { if constexpr (AUDIT) dropped(); return NEP_ENT_TRACK_CAP; }
   if (add.n > 0 || W->n_bend >= NEP_MAX_BEND - 1) save();
   bool over = add.n > 0 && ent_merge(add, W, pk, pb_self, c);
   if (!over) { over = ent_update_bends(W, pk1, pb_self, c); over |= W->n_bend > NEP_MAX_BEND - 1; }
-  if (over) { restore(); return NEP_ENT_TRACK_CAP; }
+  if (over) { restore(); if constexpr (AUDIT) dropped(); return NEP_ENT_TRACK_CAP; }
   int fl = abort ? NEP_ENT_TRACK_ABORT : 0;
   for (int e = 0; e < W->n_alpha; e++) {      // active_cases of the agents: entries per id
     const int id_ = W->id[e];
@@ -525,9 +537,16 @@ __device__ __forceinline__ int ent_track_move(EntAdd& add, ST* W, SAVE save, RES
     const int k = ent_count(W->id, W->n_alpha, id_);
     if (k > 2) fl |= NEP_ENT_TRACK_ENTANGLED;
     if (k >= 2) fl |= NEP_ENT_TRACK_TWO_CASES;
+    if constexpr (AUDIT) nep_tether_audit_impl::tether_wind(*tk, id_, k);
   }
-  if (ent_tether(W, pb_self, pk1, c) > cable) fl |= NEP_ENT_TRACK_TOO_LONG;
+  const double len = ent_tether(W, pb_self, pk1, c);
+  if (len > cable) fl |= NEP_ENT_TRACK_TOO_LONG;
+  if constexpr (AUDIT) { tk->flags = fl; tk->n_alpha = W->n_alpha; tk->n_bend = W->n_bend; tk->len = len; }
   return fl;
+}
+template <class ST, class SAVE, class RESTORE>
+__device__ __forceinline__ int ent_track_move(EntAdd& add, ST* W, SAVE save, RESTORE restore, Ev2 pk, Ev2 pk1, Ev2 pb_self, const EntCtx& c, double cable, bool abort) {
+  return ent_track_move_any<false>(add, W, save, restore, pk, pk1, pb_self, c, cable, abort, nullptr);
 }
 // the bend point a record publishes for list entry (id, cs): its anchor, or (0, 0) for an entry that names nobody (c: N, S, pb, srep)
 __device__ __forceinline__ Ev2 ent_publish_point(int id, int cs, const EntCtx& c) {

@@ -12,8 +12,11 @@
 #include <vector>
 
 #include "../../include/neptune_entangle.h"
+#include "tether_audit_common.h"
 
 namespace {
+
+using nep_tether_audit_impl::TetherTick;
 
 struct V2 { double x, y; };
 struct A2 { int id, cs; };                       // (agent or static id, case)
@@ -303,8 +306,17 @@ bool crossings_agent_changed(CappedAdd& add, const V2& pk, const V2& pk1, const 
   return abort;
 }
 
-// NeptuneRos::updateEntStateStaticObs (neptune_ros.cpp:800-850) for the move pk -> pk1, without early exit
-int track_step(const Ctx& cx, const nep_ent_track_inputs* in, State& st, const V2& pk, const V2& pk1, int cap) {
+// what the tether audit reads of the state a move left (tk->t and tk->n_add are the caller's)
+void measure_tick(const Ctx& cx, const State& st, int flags, double len, TetherTick* tk) {
+  tk->flags = flags; tk->len = len;
+  tk->n_alpha = (int)st.alphas.size(); tk->n_bend = (int)st.bend.size();
+  tk->wind = 0; tk->wind_partner = 0; tk->ent_partner = 0;
+  for (int i = 0; i < cx.N; i++) nep_tether_audit_impl::tether_wind(*tk, i + 1, st.active[i]);
+}
+
+// NeptuneRos::updateEntStateStaticObs (neptune_ros.cpp:800-850) for the move pk -> pk1, without early exit.  tk (may be null): the
+// tick as the tether audit sees it.
+int track_step(const Ctx& cx, const nep_ent_track_inputs* in, State& st, const V2& pk, const V2& pk1, int cap, TetherTick* tk = nullptr) {
   const nep_ent_cfg& c = *cx.c;
   const V2 pb_self = cx.pb(c.id - 1);
   CappedAdd add;
@@ -321,17 +333,24 @@ int track_step(const Ctx& cx, const nep_ent_track_inputs* in, State& st, const V
     abort |= crossings_agent_changed(add, pk, pk1, pik, pik1, pb_self, b.data(), nb, q.data(), nq, i + 1);
   }
   crossings_static(add, pk, pk1, cx);
-  if (add.overflow) return NEP_ENT_TRACK_CAP;
+  if (tk) tk->n_add = (int)add.size();
+  if (add.overflow) { if (tk) measure_tick(cx, st, NEP_ENT_TRACK_CAP, tether_length(st, pb_self, pk1, cx), tk); return NEP_ENT_TRACK_CAP; }
   State before = st;
   merge_crossings(add.v, st, pk, pb_self, cx);
   update_bend_points(st, pk1, pb_self, cx);
-  if ((int)st.alphas.size() > cap || (int)st.bend.size() > NEP_MAX_BEND - 1) { st = before; return NEP_ENT_TRACK_CAP; }
+  if ((int)st.alphas.size() > cap || (int)st.bend.size() > NEP_MAX_BEND - 1) {
+    st = before;
+    if (tk) measure_tick(cx, st, NEP_ENT_TRACK_CAP, tether_length(st, pb_self, pk1, cx), tk);      // (the state that was kept)
+    return NEP_ENT_TRACK_CAP;
+  }
   int flags = abort ? NEP_ENT_TRACK_ABORT : 0;
   for (int i = 0; i < cx.N; i++) {
     if (st.active[i] > 2) flags |= NEP_ENT_TRACK_ENTANGLED;
     if (st.active[i] >= 2) flags |= NEP_ENT_TRACK_TWO_CASES;
   }
-  if (tether_length(st, pb_self, pk1, cx) > c.cable_length) flags |= NEP_ENT_TRACK_TOO_LONG;
+  const double len = tether_length(st, pb_self, pk1, cx);
+  if (len > c.cable_length) flags |= NEP_ENT_TRACK_TOO_LONG;
+  if (tk) measure_tick(cx, st, flags, len, tk);
   return flags;
 }
 
@@ -477,7 +496,10 @@ int nep_ent_propagate_guess(const nep_ent_cfg* cfg, const nep_ent_inputs* in, co
   return NEP_OK;
 }
 
-int nep_ent_track_step(const nep_ent_cfg* cfg, const nep_ent_track_inputs* in, nep_ent_state* state, const double pk[2], const double pk1[2]) {
+namespace {
+// nep_ent_track_step, and nep_ent_track_step_audit where a != null
+int track_step_any(const nep_ent_cfg* cfg, const nep_ent_track_inputs* in, nep_ent_state* state, const double pk[2], const double pk1[2], double t,
+                   nep_tether_audit* a) {
   if (!cfg || !in || !cfg->pb || cfg->num_agents < 1 || cfg->id < 1 || cfg->id > cfg->num_agents || !pk || !pk1) return NEP_E_ARG;
   if (cfg->n_static < 0 || (cfg->n_static && (!cfg->static_rep || !cfg->static_longest))) return NEP_E_ARG;
   if (!in->pik || !in->pik1 || !in->present || !in->bend_off || !in->bend_off_prev) return NEP_E_ARG;
@@ -486,9 +508,47 @@ int nep_ent_track_step(const nep_ent_cfg* cfg, const nep_ent_track_inputs* in, n
   if (!load_state(state, st) || state->n_active < cfg->num_agents + cfg->n_static) return NEP_E_ARG;
   const nep_ent_inputs cur{nullptr, in->present, in->bend_off, in->bend_xy};
   Ctx cx{cfg, &cur, cfg->num_agents, cfg->n_static};
-  const int flags = track_step(cx, in, st, V2{pk[0], pk[1]}, V2{pk1[0], pk1[1]}, state->cap);
+  TetherTick tk{};
+  tk.t = t;
+  const int flags = track_step(cx, in, st, V2{pk[0], pk[1]}, V2{pk1[0], pk1[1]}, state->cap, a ? &tk : nullptr);
   if (int e = store_state(st, state)) return e;
+  if (a) nep_tether_audit_impl::tether_audit_tick(a, tk);
   return flags;
+}
+}  // namespace
+
+int nep_ent_track_step(const nep_ent_cfg* cfg, const nep_ent_track_inputs* in, nep_ent_state* state, const double pk[2], const double pk1[2]) {
+  return track_step_any(cfg, in, state, pk, pk1, 0.0, nullptr);
+}
+
+int nep_ent_track_step_audit(const nep_ent_cfg* cfg, const nep_ent_track_inputs* in, nep_ent_state* state, const double pk[2], const double pk1[2],
+                             double t, nep_tether_audit* a) {
+  if (!a) return NEP_E_ARG;
+  return track_step_any(cfg, in, state, pk, pk1, t, a);
+}
+
+int nep_ent_tether_length(const nep_ent_cfg* cfg, const nep_ent_state* state, const double pk1[2], double* len) {
+  if (!cfg || !cfg->pb || cfg->num_agents < 1 || cfg->id < 1 || cfg->id > cfg->num_agents || !pk1 || !len) return NEP_E_ARG;
+  if (cfg->n_static < 0 || (cfg->n_static && (!cfg->static_rep || !cfg->static_longest))) return NEP_E_ARG;
+  State st;
+  if (!load_state(state, st)) return NEP_E_ARG;
+  for (int bi : st.bend) {      // every bend index names a list entry, and the entry an agent's base or a static's representative
+    if (bi < 0 || bi >= (int)st.alphas.size()) return NEP_E_ARG;
+    const A2 b = st.alphas[bi];
+    if (b.id < 1 || b.id > cfg->num_agents + cfg->n_static || (b.id > cfg->num_agents && b.cs != 0 && b.cs != 1)) return NEP_E_ARG;
+  }
+  Ctx cx{cfg, nullptr, cfg->num_agents, cfg->n_static};
+  *len = tether_length(st, cx.pb(cfg->id - 1), V2{pk1[0], pk1[1]}, cx);
+  return NEP_OK;
+}
+
+int nep_tether_audit_init(nep_tether_audit* out, int64_t n) {
+  if (!out || n < 0) return NEP_E_ARG;
+  for (int64_t i = 0; i < n; i++) {
+    std::memset(out + i, 0, sizeof(nep_tether_audit));
+    out[i].max_len = -INFINITY;
+  }
+  return NEP_OK;
 }
 
 int nep_ent_predict_a(const nep_ent_cfg* cfg, const double* pik, const double* pik1, const int32_t* present, const int32_t* bend_off,

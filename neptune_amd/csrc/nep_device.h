@@ -9,6 +9,7 @@
 #include "lds_layout.h"
 #include "../../include/neptune_frontend.h"
 #include "../../include/neptune_fleet.h"
+#include "../../include/neptune_entangle.h"
 #include "../../include/neptune_backend_debug.h"
 
 namespace nep {
@@ -378,6 +379,10 @@ struct TetherArgs {
   int* walked;                   // [slots] (other agent, step) pairs walked, accumulated (the fleet's tracking) or null
   int* counters;                 // [scenes][NEP_FLEET_N_COUNTERS]: [7] = slots ever flagged NEP_ENT_TRACK_ENTANGLED
   int* gflags;                   // sticky NEP_FLAG_ENT_TRACK
+  // the tether audit (nep_batch_set_tether_audit): null = off, the plain step kernels run.  Else [slots] records the tracking calls
+  // accumulate one tick per move into; tick q = 1..n_steps of a call lies at t0 + (double)q * audit_dt, t0 the scene's clock
+  // *(const double*)(audit_t0 + scene * audit_t0_stride).  A prediction never audits.
+  nep_tether_audit* audit; const char* audit_t0; long audit_t0_stride; double audit_dt;
 };
 bool fleet_ent_fits(int N, int S);
 void launch_tether_publish(const TetherArgs& ea, bool fleet, hipStream_t st);      // (fleet: nep_batch_fleet_select's contract, else nep_batch_track_ent's)

@@ -172,9 +172,10 @@ __global__ void ent_publish_kernel(TetherArgs ea) {
 // LISTS = false, the fixed record (ea.in / out / save), copied whole into LDS; LISTS = true, the list form (ea.lists, in place; scratch
 // ea.lsave), one slot's list of ea.lists.cap entries in dynamic LDS (EntListLds).  A prediction in the list form leaves the lists alone
 // and writes the fixed record at A the front end takes — or, where the result holds more than NEP_FE_ENT_CAP crossings, a zeroed one
-// with NEP_ENT_TRACK_HELD, and takes the slot out of the round's active mask.
+// with NEP_ENT_TRACK_HELD, and takes the slot out of the round's active mask.  AUDIT: lane 0 also folds every move into the slot's
+// nep_tether_audit (tether_audit_common.h, the host form's arithmetic); a slot that returns early audits nothing.
 extern __shared__ __attribute__((aligned(16))) unsigned char s_ent_list[];
-template <bool LISTS> __device__ __forceinline__ void tether_step(const TetherArgs& ea) {
+template <bool LISTS, bool AUDIT> __device__ __forceinline__ void tether_step(const TetherArgs& ea) {
   __shared__ __attribute__((aligned(16))) nep_fe_ent_state s_st;      // (LISTS: unused)
   __shared__ int s_cnt[2];                                            // (LISTS: the counts after the walk)
   __shared__ unsigned long long s_mask[kMaskWords], s_chg[kMaskWords];
@@ -318,6 +319,10 @@ template <bool LISTS> __device__ __forceinline__ void tether_step(const TetherAr
     unsigned add_tail[kEntAddCap - EntAdd::reg];
     int fl = 0, walked = 0;
     Ev2 pk = own(0);
+    // the tether audit: the slot's record and its scene's clock, read once before the walk, written once after it
+    nep_tether_audit A{};
+    double t0 = 0.0;
+    if constexpr (AUDIT) { A = ea.audit[slot]; t0 = *(const double*)(ea.audit_t0 + (long)scene * ea.audit_t0_stride); }
     for (int q = 1; q <= T; q++) {
       const bool first = q == 1;
       const Ev2 pk1 = own(q);
@@ -340,9 +345,16 @@ template <bool LISTS> __device__ __forceinline__ void tether_step(const TetherAr
         }
       }
       ent_cross_static(add, pk, pk1, ec);
+      if constexpr (AUDIT) {
+        nep_tether_audit_impl::TetherTick tk;
+        tk.t = t0 + (double)q * ea.audit_dt;
+        fl |= ent_track_move_any<true>(add, &W, save, restore, pk, pk1, pb_self, ec, ea.cable, abort, &tk);
+        nep_tether_audit_impl::tether_audit_tick(&A, tk);
+      } else
       fl |= ent_track_move(add, &W, save, restore, pk, pk1, pb_self, ec, ea.cable, abort);
       pk = pk1;
     }
+    if constexpr (AUDIT) ea.audit[slot] = A;
     if constexpr (LISTS) {
       for (int i = W.n_bend; i < NEP_MAX_BEND; i++) W.bend[i] = 0;
       s_cnt[0] = W.n_alpha; s_cnt[1] = W.n_bend;
@@ -385,8 +397,11 @@ template <bool LISTS> __device__ __forceinline__ void tether_step(const TetherAr
   for (int i = lane; i < (int)(sizeof(nep_fe_ent_state) / 4); i += 64) ((int*)dst)[i] = ((const int*)&s_st)[i];
   }
 }
-__global__ __launch_bounds__(64) void tether_step_kernel(TetherArgs ea) { tether_step<false>(ea); }
-__global__ __launch_bounds__(64) void tether_step_lists_kernel(TetherArgs ea) { tether_step<true>(ea); }
+__global__ __launch_bounds__(64) void tether_step_kernel(TetherArgs ea) { tether_step<false, false>(ea); }
+__global__ __launch_bounds__(64) void tether_step_lists_kernel(TetherArgs ea) { tether_step<true, false>(ea); }
+// the audited twins (ea.audit != null): the same moves, and one tick per move into the slot's nep_tether_audit
+__global__ __launch_bounds__(64) void tether_step_audit_kernel(TetherArgs ea) { tether_step<false, true>(ea); }
+__global__ __launch_bounds__(64) void tether_step_lists_audit_kernel(TetherArgs ea) { tether_step<true, true>(ea); }
 
 // The bulk-synchronous loop's state at A from the list form (nep_batch_ent_lists_at_a), one thread per slot: the fixed record where the
 // list fits it; where it holds more than NEP_FE_ENT_CAP crossings a zeroed record, NEP_ENT_TRACK_HELD, one more held round and a
@@ -439,8 +454,9 @@ void launch_tether_steps(const TetherArgs& ea, const FleetArgs& fa, hipStream_t 
   if (slots <= 0) return;
   const long total = slots * (ea.n_steps + 1);
   hipLaunchKernelGGL(tether_pos_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, ea, fa);
-  if (ea.lists.cap) hipLaunchKernelGGL(tether_step_lists_kernel, dim3((unsigned)slots), dim3(64), ent_list_lds_bytes(ea.lists.cap), st, ea);
-  else hipLaunchKernelGGL(tether_step_kernel, dim3((unsigned)slots), dim3(64), 0, st, ea);
+  const bool audit = ea.audit != nullptr && ea.start == nullptr;      // (a prediction flies nothing)
+  if (ea.lists.cap) hipLaunchKernelGGL(audit ? tether_step_lists_audit_kernel : tether_step_lists_kernel, dim3((unsigned)slots), dim3(64), ent_list_lds_bytes(ea.lists.cap), st, ea);
+  else hipLaunchKernelGGL(audit ? tether_step_audit_kernel : tether_step_kernel, dim3((unsigned)slots), dim3(64), 0, st, ea);
   if (ea.ever && ea.counters) hipLaunchKernelGGL(fleet_ent_count_kernel, dim3((unsigned)ea.n_scenes), dim3(64), 0, st, ea);
 }
 

@@ -107,10 +107,18 @@ class EntangleCheck:
         return dict(alpha_off=alpha_off, alphas=alphas[:alpha_off[K + 1]].copy(), active_cases=active, entangled_at=int(hit.value),
                     final=final, case_id=case_id)
 
-    def track_step(self, state, pk, pk1, pik, pik1, present, bendpts, bendpts_prev):
+    def tether_length(self, state, pk1):
+        """eu::getTetherLength of `state` with the vehicle at pk1 (nep_ent_tether_length): what track_step compares with the cable"""
+        p1 = np.ascontiguousarray(pk1, dtype=np.float64)
+        out = C.c_double(0.0)
+        _ck(lib().nep_ent_tether_length(C.byref(self.cfg), C.byref(state.c), abi.dptr(p1), C.byref(out)), "nep_ent_tether_length")
+        return out.value
+
+    def track_step(self, state, pk, pk1, pik, pik1, present, bendpts, bendpts_prev, audit=None, t=0.0):
         """One updateEntStateStaticObs of the agent's own tether for its move pk -> pk1 (nep_ent_track_step): pik / pik1 [N][2]
         the other agents at the previous check and now, bendpts / bendpts_prev lists per agent of (k,2) arrays now and at the
-        previous check.  Updates state in place; -> the NEP_ENT_TRACK_* bits."""
+        previous check.  Updates state in place; -> the NEP_ENT_TRACK_* bits.  audit: a one-record TETHER_AUDIT_DTYPE array (a view
+        into the caller's buffer) the move is accumulated into as the tick at time t (nep_ent_track_step_audit)."""
         def csr(lists):
             off = np.zeros(self.N + 1, dtype=np.int32)
             for j, b in enumerate(lists):
@@ -126,6 +134,10 @@ class EntangleCheck:
         pr = np.ascontiguousarray(present, dtype=np.int32).reshape(self.N)
         tin = abi.nep_ent_track_inputs(abi.dptr(a), abi.dptr(b), abi.iptr(pr), abi.iptr(off), abi.dptr(xy), abi.iptr(offp), abi.dptr(xyp))
         p0 = np.ascontiguousarray(pk, dtype=np.float64); p1 = np.ascontiguousarray(pk1, dtype=np.float64)
+        if audit is not None:
+            assert audit.dtype == abi.TETHER_AUDIT_DTYPE and audit.size == 1 and audit.flags["C_CONTIGUOUS"] and audit.flags["WRITEABLE"]
+            return _ck(lib().nep_ent_track_step_audit(C.byref(self.cfg), C.byref(tin), C.byref(state.c), abi.dptr(p0), abi.dptr(p1), float(t),
+                                                      audit.ctypes.data_as(C.c_void_p)), "nep_ent_track_step_audit")
         return _ck(lib().nep_ent_track_step(C.byref(self.cfg), C.byref(tin), C.byref(state.c), abi.dptr(p0), abi.dptr(p1)), "nep_ent_track_step")
 
     def predict_a(self, state, pk, pk1, pik, pik1, present, bendpts):

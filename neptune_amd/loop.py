@@ -164,12 +164,28 @@ class _Audited:
         """the flight audit so far: AUDIT_DTYPE, [N] (FleetLoop) or [S, N]"""
         return self.d_audit.cpu().numpy().view(abi.AUDIT_DTYPE).reshape(self._audit_shape)
 
+    def tether_audit_records(self):
+        """the tether audit so far: TETHER_AUDIT_DTYPE, [N] (FleetLoop) or [S, N]; tether_audit= must be on"""
+        if isinstance(self.d_tether_audit, np.ndarray):      # (FleetLoop: the host form)
+            return self.d_tether_audit.copy().reshape(self._audit_shape)
+        return self.d_tether_audit.cpu().numpy().view(abi.TETHER_AUDIT_DTYPE).reshape(self._audit_shape)
+
+
+def check_tether_audit(tether_audit, tethers):
+    if tether_audit and not tethers:
+        raise ValueError("tether_audit=True audits the tethers: it needs tethers=True")
+    return bool(tether_audit)
+
 
 class FleetLoop(_Audited):
     def __init__(self, par, statics, starts, goals, beam_width=32, delta_t_states=6, replan_every=5, device=None, skip_arrived=False, audit=False,
-                 tethers=False, check=True, ent_samples=3, search="beam", max_pops=300, moveback=None, goal_gate=False, fly_guess=False, team=1):
+                 tethers=False, check=True, ent_samples=3, search="beam", max_pops=300, moveback=None, goal_gate=False, fly_guess=False, team=1,
+                 tether_audit=False):
         import torch
         from . import mission
+        # tether_audit: every tracked control tick also goes into a nep_tether_audit per agent (nep_ent_track_step_audit in the chain
+        # below; DESIGN section 41) — the host form of DeviceFleetLoop(tether_audit=True).  stats then carries its summary
+        self.tether_audit = check_tether_audit(tether_audit, tethers)
         self.team = check_team(team, search)      # (waves per search of search="astar_ent": same flight either way)
         self.torch = torch
         self.tethers, self.check, self.ent_samples = tethers, check, ent_samples
@@ -245,6 +261,7 @@ class FleetLoop(_Audited):
         # (nep_batch_audit; those ticks lie before the round's point A, so the uploaded records describe them); _tick keeps its host log
         self.d_audit = self.be.new_audit() if audit else None
         self._audit_shape = (N,)
+        self.d_tether_audit = audit_mod.new_tether_audit(N) if self.tether_audit else None      # (host memory: the chain runs here)
 
     # ---- records every agent publishes (publishOwnTraj) ----
     def _records(self, t_from):
@@ -371,7 +388,7 @@ class FleetLoop(_Audited):
             before = self.state[:, :2].copy()
             self._tick()
             if self.tethers:                    # odomCB -> updateEntStateStaticObs, once per control tick
-                self._track_tick(before, self.state[:, :2].copy(), bends, q == 0)
+                self._track_tick(before, self.state[:, :2].copy(), bends, q == 0, t_now + float(q + 1) * self.dc)
         if self.tethers:
             self._bends_prev = bends
         # arrived (sticky): inside the goal radius and practically at rest; such an agent stops replanning and its
@@ -395,14 +412,15 @@ class FleetLoop(_Audited):
             self.ent_a[a] = ent_state_record(out); self.flags_a[a] = fl
         return bends
 
-    def _track_tick(self, before, after, bends, first):
+    def _track_tick(self, before, after, bends, first, t=0.0):
         N = self.N
         old = bends
         if first and self._bends_prev is not None:      # the previous check saw the lists published a round ago
             old = [self._bends_prev[j] if len(self._bends_prev[j]) else bends[j] for j in range(N)]
         present = np.ones(N, dtype=np.int32)
         for a in range(N):
-            fl = self._chk[a].track_step(self.ent[a], before[a], after[a], before, after, present, bends, old)
+            rec = self.d_tether_audit[a:a + 1] if self.d_tether_audit is not None else None
+            fl = self._chk[a].track_step(self.ent[a], before[a], after[a], before, after, present, bends, old, audit=rec, t=t)
             self.ent_flags[a] |= fl; self.ent_ever[a] |= fl
 
     def run(self, max_rounds=400):
@@ -418,6 +436,8 @@ class FleetLoop(_Audited):
         self.stats["dist_to_goal_mean"] = float(np.hypot(*(self.state[:, :2] - self.goals[:, :2]).T).mean())
         if self.d_audit is not None:
             self.stats["audit"] = audit_mod.summarize(self.audit_records())[0]
+        if self.d_tether_audit is not None:
+            self.stats["tether_audit"] = audit_mod.summarize_tethers(self.tether_audit_records(), self.p.tether_length)[0]
         return self.stats
 
     def close(self):
@@ -454,7 +474,9 @@ class DeviceFleetLoop(_Audited):
     written on the device by fleet_select into the buffer set_active got once; without them every agent is solved every round
     and the results of the arrived ones are dropped (FleetLoop's default).  audit=True audits the records published at the
     round's start over the replan_every ticks about to be flown, from t_now + dc: FleetLoop's placement and clock.  ring_cap: a
-    smaller plan ring than a splice can need (tests of the capacity path).
+    smaller plan ring than a splice can need (tests of the capacity path).  tether_audit=True (with tethers=True, else ValueError):
+    fleet_track_ent also folds every control tick it tracks into a nep_tether_audit per slot — taut length, slack, windings, list
+    and bend counts (tether_audit_records(), report()'s tether_audit; a checkpoint carries the buffer).
     run() downloads the slots' arrival flags (4 bytes per slot) after every round to know when to stop; nothing else leaves the
     device before report().  trace=True additionally downloads outcome, K and the two statuses per round (FleetLoop.trace).
     search="astar" plans with the reference's best-first search, max_pops pops per search, in place of the beam
@@ -521,13 +543,15 @@ class DeviceFleetLoop(_Audited):
 
     # the options a restored flight must share with the flight the snapshot was taken from
     _MUST_MATCH = ("beam_width", "delta_t_states", "replan_every", "audit", "ring_cap", "tethers", "check", "ent_samples", "ent_cap", "moveback", "goal_gate", "fly_guess",
-                   "script", "effort")
+                   "script", "effort", "tether_audit")
 
     def __init__(self, scenes, beam_width=32, delta_t_states=6, replan_every=5, periods=None, phases=None, audit=False, graph=True,
                  goals=None, device=None, ring_cap=0, trace=False, tethers=False, check=True, ent_samples=3, missions=None, ent_cap=None,
-                 ent_lists0=None, recorder=None, search="beam", max_pops=300, moveback=None, goal_gate=False, fly_guess=False, effort=False, team=1):
+                 ent_lists0=None, recorder=None, search="beam", max_pops=300, moveback=None, goal_gate=False, fly_guess=False, effort=False, team=1,
+                 tether_audit=False):
         import torch
         from . import mission as mission_mod
+        self.tether_audit = check_tether_audit(tether_audit, tethers)
         self.team = check_team(team, search)      # (waves per search of search="astar_ent"; not among the options a checkpoint carries: the flight does not depend on it)
         self.torch = torch
         self.scenes = scenes
@@ -542,7 +566,7 @@ class DeviceFleetLoop(_Audited):
         self._opts = dict(beam_width=beam_width, delta_t_states=delta_t_states, replan_every=replan_every, audit=audit, ring_cap=ring_cap,
                           tethers=tethers, check=check, ent_samples=ent_samples, ent_cap=ent_cap, missions=missions, goals=goals,
                           search=search, max_pops=max_pops, moveback=moveback, goal_gate=self.goal_gate, fly_guess=self.fly_guess,
-                          script=mission_mod.spec_plain(missions)[1], effort=self.effort, team=self.team)
+                          script=mission_mod.spec_plain(missions)[1], effort=self.effort, team=self.team, tether_audit=self.tether_audit)
         S = self.S = len(scenes)
         p = self.p = scenes[0]["par"]
         self.tethers, self.check, self.ent_samples = tethers, check, ent_samples
@@ -608,6 +632,12 @@ class DeviceFleetLoop(_Audited):
             self.d_flags_a = torch.zeros(n, dtype=torch.int32, device=dev)
             self.d_flags = torch.zeros(n, dtype=torch.int32, device=dev)
             self.d_case = torch.zeros(n * abi.NEP_MAX_POL * N, dtype=torch.int32, device=dev)
+        # tether_audit: fleet_track_ent also accumulates every control tick it tracks into a nep_tether_audit per slot, inside its
+        # launch (registered here, outside any capture)
+        self.d_tether_audit = None
+        if self.tether_audit:
+            self.d_tether_audit = be.new_tether_audit()
+            be.set_tether_audit(self.d_tether_audit, p.dc)
         self.d_gate_count = torch.zeros((S, 4), dtype=torch.int32, device=dev) if self.goal_gate is not None else None      # abi.GOAL_GATE_COUNTS
         self.d_guess_count = torch.zeros((S, 4), dtype=torch.int32, device=dev) if self.fly_guess else None      # abi.GUESS_FALLBACK_COUNTS
         self.missions = missions
@@ -723,6 +753,7 @@ class DeviceFleetLoop(_Audited):
             longest = [max([float(r["t_end"] - r["t_issue"]) for o in range(s * per, (s + 1) * per) for r in recs[o] if r["outcome"] != abi.NEP_MISSION_NO_GOAL],
                            default=None) for s in range(self.S)]
         esum = mission.summarize_effort(self.effort_records(), self.N) if self.d_effort is not None else None
+        tsum = audit_mod.summarize_tethers(self.tether_audit_records(), self.p.tether_length, self.S) if self.d_tether_audit is not None else None
         out = []
         for s in range(self.S):
             c = cnt[s]
@@ -748,6 +779,8 @@ class DeviceFleetLoop(_Audited):
                 d["longest_leg_time"] = longest[s]
             if esum is not None:
                 d.update(esum[s])
+            if tsum is not None:
+                d["tether_audit"] = tsum[s]
             if summ is not None:
                 d["audit"] = summ[s]
                 d["min_pair_dist"] = summ[s]["min_center_dist"]["value"] if summ[s]["min_center_dist"] else np.inf
@@ -826,6 +859,8 @@ class DeviceFleetLoop(_Audited):
             data["guess_count"] = self.d_guess_count.cpu().numpy()
         if self.d_effort is not None:
             data["effort"] = self.d_effort.cpu().numpy()
+        if self.d_tether_audit is not None:
+            data["tether_audit"] = self.d_tether_audit.cpu().numpy()
         with open(path, "wb") as f:
             np.savez(f, **data)
 
@@ -842,8 +877,10 @@ class DeviceFleetLoop(_Audited):
             gcnt = z["gate_count"] if "gate_count" in z.files else None
             fcnt = z["guess_count"] if "guess_count" in z.files else None
             eff = z["effort"] if "effort" in z.files else None
+            taud = z["tether_audit"] if "tether_audit" in z.files else None
         opts.setdefault("script", None)        # (a file from before the options flew without them)
         opts.setdefault("effort", None)
+        opts.setdefault("tether_audit", False)
         if "effort" in kw:
             kw = dict(kw, effort=mission.effort_slack(kw["effort"]))
         opts.setdefault("moveback", None)      # (a file from before the option flew without it)
@@ -883,6 +920,8 @@ class DeviceFleetLoop(_Audited):
                 lp.d_guess_count.copy_(lp.torch.from_numpy(fcnt))
             if eff is not None and lp.d_effort is not None:
                 lp.d_effort.copy_(lp.torch.from_numpy(eff))
+            if taud is not None and lp.d_tether_audit is not None:
+                lp.d_tether_audit.copy_(lp.torch.from_numpy(taud))
         except Exception:
             lp.close()
             raise
@@ -904,6 +943,8 @@ class TetherLoop(_Audited):
     writes the bend points of the next A into the flown records.  `active` ([S, N] int32 device tensor) is the handle's active set
     (nep_batch_set_active).  check=False flies the same rounds with the entangle check of
     the front end and of the safety pass off (plain nep_batch_frontend / nep_batch_safety_commit) and the tracking still on.
+    tether_audit=True makes the tracking fold every sampled step it tracks into a nep_tether_audit per slot (DESIGN section 41;
+    tether_audit_records(), report()'s tether_audit).
     audit=True adds the flight audit (nep_batch_audit) of the round's final records over the control ticks of the stretch the round
     flies, inside the graph, after the copy into d_rec and before next_starts; report() then carries its summary.
     ent_cap=K (or "auto": 2 (N + statics); ent_lists0: an abi.EntLists to start from) tracks the states in the list form of K entries
@@ -912,7 +953,7 @@ class TetherLoop(_Audited):
     handle's mask (`d_mask` = `active` and the fit; nep_batch_ent_lists_at_a), flying its record on.  report() adds held, max_list."""
 
     def __init__(self, scenes, beam_width=16, n_intervals=1, ent_samples=3, check=True, device=None, graph=True, active=None, audit=False,
-                 ent_cap=None, ent_lists0=None):
+                 ent_cap=None, ent_lists0=None, tether_audit=False):
         import dataclasses
         import torch
         from neptune_amd import dist as ndist
@@ -958,6 +999,12 @@ class TetherLoop(_Audited):
         if audit:
             self.d_audit = be.new_audit()
             be.audit(self.d_rec, self.d_start, p.dc, 0, self.d_audit)      # (the call that allocates: made here, outside any capture)
+        # tether_audit: track_ent / track_ent_lists also accumulate every sampled step they track into a nep_tether_audit per slot,
+        # the steps T_span / ent_samples apart from the round's t_start
+        self.d_tether_audit = None
+        if tether_audit:
+            self.d_tether_audit = be.new_tether_audit()
+            be.set_tether_audit(self.d_tether_audit, p.T_span / ent_samples)
 
     def _round_ops(self):
         be = self.be
@@ -1005,6 +1052,8 @@ class TetherLoop(_Audited):
             rep["max_list"] = [int(x) for x in self.lists.n_alpha.cpu().numpy().reshape(self.S, self.N).max(axis=1)]
         if self.d_audit is not None:
             rep["audit"] = audit_mod.summarize(self.audit_records(), self.S)
+        if self.d_tether_audit is not None:
+            rep["tether_audit"] = audit_mod.summarize_tethers(self.tether_audit_records(), self.p.tether_length, self.S)
         return rep
 
     def close(self):

@@ -5,7 +5,7 @@ fleet_select -> fleet_predict_ent -> entangle-aware front end -> lines + QP with
 re-check -> fleet_commit -> [audit] -> fleet_track_ent -> fleet_tick (--no-check: the plain front end and safety pass, tracking on).  Prints the per-scene report (FleetLoop's
 stats), the totals, the wall time per round and, with --audit, the worst clearances over all scenes.
 
-  python scripts/fleet_loop.py --agents 64 --obstacles 20 --scenes 128 --rounds 30 [--stagger 5] [--audit] [--host] [--tethers [--no-check]]
+  python scripts/fleet_loop.py --agents 64 --obstacles 20 --scenes 128 --rounds 30 [--stagger 5] [--audit] [--host] [--tethers [--no-check] [--tether-audit]]
 
 --missions {agent,runs} --goals G: fleet_mission joins the round before fleet_tick and flies a campaign of G goals per agent (runs per
 scene); the report gains the legs' accounts.
@@ -55,6 +55,7 @@ def main():
     ap.add_argument("--max-pops", type=int, default=300, help="with --search astar / astar_ent: pops per search")
     ap.add_argument("--team", type=int, choices=(1, 4), default=1, help="with --search astar_ent: waves per search (4: a workgroup of four waves per search, for fleets of few agents; the flight is the same)")
     ap.add_argument("--audit", action="store_true", help="flight audit of every round, inside the graph")
+    ap.add_argument("--tether-audit", action="store_true", help="with --tethers: the tether audit (DESIGN section 41) — taut length, slack, windings, list and bend counts of every tracked control tick, inside the tracking's launch")
     ap.add_argument("--eager", action="store_true", help="no graph capture")
     ap.add_argument("--tethers", action="store_true", help="tethered agents: entangle states tracked per control tick, predicted at A, checked by the front end and the safety pass")
     ap.add_argument("--no-check", action="store_true", help="with --tethers: plain front end and safety pass, the tracking stays on")
@@ -84,8 +85,10 @@ def main():
     seeds = [a.seed0 + k for k in range(a.scenes)]
     scenes = scene.make_scenes(a.agents, a.obstacles, seeds, workers=min(len(seeds), len(os.sched_getaffinity(0)), 16))
     kw = dict(beam_width=a.beam, audit=a.audit, graph=not a.eager, search=a.search, max_pops=a.max_pops, team=a.team)
+    if a.tether_audit and not a.tethers:
+        ap.error("--tether-audit audits the tethers: only with --tethers")
     if a.tethers:
-        kw.update(tethers=True, check=not a.no_check)
+        kw.update(tethers=True, check=not a.no_check, tether_audit=a.tether_audit)
         if a.ent_cap:
             kw.update(ent_cap="auto" if a.ent_cap == "auto" else int(a.ent_cap))
     if a.missions:
@@ -181,7 +184,7 @@ def main():
 
     rep, per_round, n = fly(scenes, a.rounds, a.resume)
     for s, r in enumerate(rep):
-        print("scene %d (seed %d): %s" % (s, seeds[s], json.dumps({k: v for k, v in r.items() if k != "audit"})))
+        print("scene %d (seed %d): %s" % (s, seeds[s], json.dumps({k: v for k, v in r.items() if k not in ("audit", "tether_audit")})))
     tot = {k: int(sum(r[k] for r in rep)) for k in ("replans", "accepted", "fe_no_solution", "qp_failed", "qp_relaxed", "rejected_by_safety", "cap", "skipped", "reached")}
     if a.tethers:
         tot.update({k: int(sum(r[k] for r in rep)) for k in ("ever_entangled", "too_long", "track_cap")})
@@ -215,6 +218,10 @@ def main():
                  max(r["max_j"] for r in rep), p0.j_max, sum(r["v_viol"] for r in rep), sum(r["a_viol"] for r in rep), sum(r["j_viol"] for r in rep), sum(r["effort_ticks"] for r in rep)))
     print("wall time per round (rounds 3..%d, %s, %s downloaded every round): %.3f ms = %.1f rounds/s, %.0f scene-rounds/s"
           % (n, "eager" if a.eager else "one graph", "the scenes' finished flags" if a.missions else "arrival flags", per_round * 1e3, 1.0 / per_round, a.scenes / per_round))
+    if a.tether_audit:      # (with --ent-cap: the largest list next to the capacity in force)
+        cap_now = None if not a.ent_cap else 2 * (a.agents + a.obstacles) if a.ent_cap == "auto" else int(a.ent_cap)
+        for line in audit.format_tether_summary([r["tether_audit"] for r in rep], cap=cap_now):
+            print(line)
     if a.audit:
         for line in audit.format_summary([r["audit"] for r in rep]):
             print(line)

@@ -7,7 +7,7 @@ With --audit every round also runs the flight audit (nep_batch_audit) inside the
 minimum and, for the smallest box clearance and static distance, the round it fell into and what the replans of the agent and of its
 partner came to in that round (front-end status, QP status, accepted by the safety pass).
 
-  python scripts/tether_loop.py --agents 16 --obstacles 8 --scenes 4 --rounds 40 --crossing [--audit]"""
+  python scripts/tether_loop.py --agents 16 --obstacles 8 --scenes 4 --rounds 40 --crossing [--audit] [--tether-audit]"""
 import argparse
 import json
 import os
@@ -29,6 +29,7 @@ def main():
     ap.add_argument("--crossing", action="store_true", help="scene.tether_crossing_scene: agents hover beyond each other's paths")
     ap.add_argument("--no-check", action="store_true", help="the front end and the safety pass without the entangle check")
     ap.add_argument("--ent-cap", metavar="K", help="the tracked states in the list form of K entries per slot (DESIGN section 24); 'auto' = 2 (agents + obstacles)")
+    ap.add_argument("--tether-audit", action="store_true", help="the tether audit (DESIGN section 41): taut length, slack, windings, list and bend counts of every tracked step, inside the tracking's launch")
     ap.add_argument("--audit", action="store_true", help="flight audit of every round, inside the graph (reads each round's replan outcomes back)")
     a = ap.parse_args()
     import numpy as np
@@ -38,7 +39,7 @@ def main():
     seeds = [a.seed + k for k in range(a.scenes)]
     scenes = [scene.tether_crossing_scene(a.agents, a.obstacles, s) for s in seeds] if a.crossing else \
         scene.make_scenes(a.agents, a.obstacles, seeds, workers=min(len(seeds), len(os.sched_getaffinity(0))))
-    lp = TetherLoop(scenes, beam_width=a.beam, n_intervals=a.intervals, check=not a.no_check, audit=a.audit,
+    lp = TetherLoop(scenes, beam_width=a.beam, n_intervals=a.intervals, check=not a.no_check, audit=a.audit, tether_audit=a.tether_audit,
                     ent_cap=None if not a.ent_cap else "auto" if a.ent_cap == "auto" else int(a.ent_cap))
     t_first = float(lp.d_start.cpu().numpy().view(abi.FE_START_DTYPE)["t_start"][0])
     outcomes = []                               # --audit: per round [S, N, 3] front-end status, QP status, accepted
@@ -65,9 +66,13 @@ def main():
     rep = run(a.rounds - 2)
     dt = (time.perf_counter() - t0) / max(a.rounds - 2, 1)
     summary = rep.pop("audit", None)
+    tethers = rep.pop("tether_audit", None)
     rep.update(agents=a.agents, obstacles=a.obstacles, scenes=a.scenes, crossing=a.crossing, check=not a.no_check,
                intervals=a.intervals, round_ms=dt * 1e3, note="round_ms includes one flag read-back per round")
     print(json.dumps(rep))
+    if tethers is not None:      # (with --ent-cap: the largest list next to the capacity in force)
+        for line in audit.format_tether_summary(tethers, cap=lp.ent_cap):
+            print(line)
     span = a.intervals * lp.p.T_span
     for name, summary in ([("rounds 0..%d (an initial record of the scene can still be flown)" % (split - 1), early[0]),
                            ("rounds %d..%d" % (split, a.rounds - 1), summary)] if early else [("all rounds", summary)] if summary is not None else []):
