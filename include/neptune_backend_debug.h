@@ -91,6 +91,9 @@ int nep_batch_debug_launch_order(nep_batch_t* h, int32_t* order, int32_t cap, in
  * default: the polish pass's batched form | 0: its first form, the one the default is compared with), "parked_bound" (1, the default: a
  * slot the polish pass certified reads its parked lines back only when a control point left the certificate's movement bound | 0:
  * always).  Same bytes either way (tests/test_gpu_polish_forms.py); read when a replan is enqueued, so a captured graph keeps its form.
+ * "hull_sort" (1, the default: the eight-hulls-per-wave kernel sorts an inflated hull's corners as stacked pairs where that gives
+ * the lexicographic sort, neptune_amd/csrc/hull_pair_sort.h | 0: always the full network over the 64 corners).  Same hulls either way
+ * (tests/test_gpu_hull_pair_sort.py); read when the hull launch is enqueued.
  * Unknown names are refused (NEP_E_ARG).                                                                                      */
 int nep_batch_debug_set_option(nep_batch_t* h, const char* name, int32_t value);
 int nep_backend_debug_set_option(nep_backend_t* h, const char* name, int32_t value);

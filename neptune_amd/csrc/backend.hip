@@ -2441,7 +2441,8 @@ int nep_debug_set_global_option(const char* name, int32_t value) {
   else if (n == "fe_xcd") g_debug.fe_xcd = value;
   else if (n == "polish_grid") { if (value < 1) return fail(NEP_E_ARG, "polish_grid >= 1"); g_debug.polish_grid = value; }
   else if (n == "polish_impl") { if (value < 0 || value > 1) return fail(NEP_E_ARG, "polish_impl: 0 the first form of the polish pass, 1 the batched one"); g_debug.polish_impl = value; }
-  else if (n == "parked_bound") g_debug.parked_bound = value != 0;      // 0: a certified slot always reads its parked lines back (same verdicts)
+  else if (n == "hull_sort") { if (value < 0 || value > 1) return fail(NEP_E_ARG, "hull_sort: 0 the full network over the corners, 1 stacked pairs"); g_debug.hull_sort = value; }      // (hull_group_kernel's sort of an inflated hull, read at launch; same hulls)
+  else if (n == "parked_bound") g_debug.parked_bound = value != 0;     // 0: a certified slot always reads its parked lines back (same verdicts)
   else return fail(NEP_E_ARG, "unknown global debug option: " + n);
   return 0;
 }

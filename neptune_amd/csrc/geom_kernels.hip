@@ -23,6 +23,7 @@
 #include "ent_device.h"
 #include "qp_presolve.h"
 #include "hull_chain.h"
+#include "hull_pair_sort.h"
 
 namespace nep {
 
@@ -269,20 +270,90 @@ __device__ __forceinline__ unsigned long long grp_or_low(unsigned long long v) {
   return ((unsigned long long)hi << 32) | lo;
 }
 
+// The group's n points, sorted lexicographically, into sxy: the full network over (x, y).
+template <int J>
+__device__ __forceinline__ void group_sort(int n, const double (&px)[J], const double (&py)[J], double* sxy, int sub) {
+  __syncthreads();
+  double kx[J], ky[J];
+#pragma unroll
+  for (int j = 0; j < J; j++) { const bool in = sub + 8 * j < n; kx[j] = in ? px[j] : NEP_INF; ky[j] = in ? py[j] : NEP_INF; }
+  grp_bitonic<J, 8 * J>(kx, ky, sub);
+#pragma unroll
+  for (int r = 0; r < J; r++) { const int e = sub * J + r; if (e < n) { sxy[2 * e] = kx[r]; sxy[2 * e + 1] = ky[r]; } }
+}
+
+// The same array for an INFLATED hull, from its 2 np0 stacked pairs (hull_pair_sort.h: the array, the rule, and why the arrays are
+// equal): a network over the pairs (X, y) — half the elements, the same comparison — and the pairs' two points stored run by run.
+// `ok`: what the rule says about this group before the network (pair_sort_allowed; true for a group without points).  Every lane of
+// the wave calls it; returns false when some group of the wave is not ok, has a key that is no number or a zero, or a run whose
+// points would not ascend: the caller then runs group_sort on the corners (sxy may have been written; group_sort starts with a barrier).
+struct PairLanes {
+  double (&kx)[kPairJ]; double (&ky)[kPairJ]; int sub;
+  template <int K_, int JJ> __device__ __forceinline__ void step() {
+    if constexpr (JJ < kPairJ) pair_step_local<kPairJ, K_, JJ>(kx, ky, sub);
+    else {
+      double ox[kPairJ], oy[kPairJ];
+#pragma unroll
+      for (int r = 0; r < kPairJ; r++) { ox[r] = grp_xor<JJ / kPairJ>(kx[r]); oy[r] = grp_xor<JJ / kPairJ>(ky[r]); }
+      pair_step_cross<kPairJ, K_, JJ>(kx, ky, sub, ox, oy);
+    }
+  }
+};
+__device__ __forceinline__ bool group_sort_pairs(int np0, const double* cpx, const double* cpy, double dx, double dy, bool ok, double* sxy, int sub) {
+  constexpr int J = kPairJ;
+  if (__ballot(!ok) != 0ull) return false;
+  double kx[J], ky[J];
+#pragma unroll
+  for (int r = 0; r < J; r++) {
+    const int pi = sub * J + r;
+    const bool in = pi < 2 * np0;
+    kx[r] = in ? pair_x(cpx[pi >> 1], dx, pi & 1) : NEP_INF;
+    ky[r] = in ? cpy[pi >> 1] : NEP_INF;
+  }
+  PairLanes lanes{kx, ky, sub};
+  pair_bitonic<J, 8 * J>(lanes);
+  // where runs begin: a pair against its predecessor — a register, or the last register of the lane before (row_shr:1; sub = 0 has
+  // none) — as four bits a lane, ORed over the group's eight lanes (two quad permutes, then lane ^ 4 by two row shifts, each
+  // written to its half of the eight alone)
+  const double before = __hiloint2double(__builtin_amdgcn_mov_dpp(__double2hiint(kx[J - 1]), 0x111, 0xf, 0xf, true),
+                                         __builtin_amdgcn_mov_dpp(__double2loint(kx[J - 1]), 0x111, 0xf, 0xf, true));
+  bool bad = false;
+  unsigned starts = (sub == 0 || kx[0] != before) ? 1u : 0u;
+#pragma unroll
+  for (int r = 0; r < J; r++) {
+    if (r) starts |= kx[r] != kx[r - 1] ? 1u << r : 0u;
+    bad |= sub * J + r < 2 * np0 && pair_key_bad(kx[r]);
+  }
+  if (__ballot(bad) != 0ull) return false;
+  starts <<= 4 * sub;
+  starts |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)starts, 0xB1, 0xf, 0xf, true);      // quad_perm [1,0,3,2]
+  starts |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)starts, 0x4E, 0xf, 0xf, true);      // quad_perm [2,3,0,1]
+  starts |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)starts, 0x104, 0xf, 0x5, false)     // row_shl:4 into lanes 0-3 of each eight
+          | (unsigned)__builtin_amdgcn_update_dpp(0, (int)starts, 0x114, 0xf, 0xa, false);    // row_shr:4 into lanes 4-7
+  __syncthreads();
+  int chk[J]; double yhi0[J];
+#pragma unroll
+  for (int r = 0; r < J; r++) {
+    const int e = sub * J + r;
+    chk[r] = -1; yhi0[r] = 0;
+    if (e < 2 * np0) {
+      int s, t;
+      pair_run_of(starts, e, s, t);
+      pair_store(sxy, e, s, t, kx[r], ky[r], dy);
+      if (e == s) { chk[r] = pair_run_check_at(s, t); yhi0[r] = pair_yhi(ky[r], dy); }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < J; r++) if (chk[r] >= 0) bad |= !pair_run_ok(sxy[chk[r]], yhi0[r]);
+  return __ballot(bad) == 0ull;
+}
+
+// sxy: the group's n points, sorted (group_sort or group_sort_pairs)
 // cmax: no coordinate of the n points is larger in magnitude (what the chains' skip rule takes its gap from: hull_chain.h)
 template <int J>
-__device__ __forceinline__ int group_hull(int n, const double (&px)[J], const double (&py)[J], double cmax, double* sxy, int g, int sub,
-                                          bool write, double* __restrict__ out_xy, int cap) {
+__device__ __forceinline__ int group_hull_sorted(int n, double cmax, double* sxy, int g, int sub, bool write, double* __restrict__ out_xy, int cap) {
   constexpr int kGrpPts = J;          // (points per lane in this instantiation: 8 for the inflated hull's <= 64 points, 2 for the <= 16 control points)
-  __syncthreads();
-  {
-    double kx[J], ky[J];
-#pragma unroll
-    for (int j = 0; j < J; j++) { const bool in = sub + 8 * j < n; kx[j] = in ? px[j] : NEP_INF; ky[j] = in ? py[j] : NEP_INF; }
-    grp_bitonic<J, 8 * J>(kx, ky, sub);
-#pragma unroll
-    for (int r = 0; r < J; r++) { const int e = sub * J + r; if (e < n) { sxy[2 * e] = kx[r]; sxy[2 * e + 1] = ky[r]; } }
-  }
   __syncthreads();
   // unique: sorted position p survives if it differs from its predecessor; new position = number of survivors before it
   // (and on its way the chains' skip flags, hull_chain.h: a kept point's predecessor in the de-duplicated array equals its predecessor
@@ -345,6 +416,12 @@ __device__ __forceinline__ int group_hull(int n, const double (&px)[J], const do
   }
   return k;
 }
+template <int J>
+__device__ __forceinline__ int group_hull(int n, const double (&px)[J], const double (&py)[J], double cmax, double* sxy, int g, int sub,
+                                          bool write, double* __restrict__ out_xy, int cap) {
+  group_sort<J>(n, px, py, sxy, sub);
+  return group_hull_sorted<J>(n, cmax, sxy, g, sub, write, out_xy, cap);
+}
 
 // One block (= one wave) per (scene, committed trajectory): interval i on lanes 8 i .. 8 i + 7 (num_pol <= 8).
 __global__ __launch_bounds__(64) void hull_group_kernel(const nep_traj_rec* __restrict__ recs, int n_rec_per_scene,
@@ -354,7 +431,8 @@ __global__ __launch_bounds__(64) void hull_group_kernel(const nep_traj_rec* __re
                                                         double* __restrict__ hull0_xy, int* __restrict__ hull0_nv,
                                                         double* __restrict__ bend_xy, int* __restrict__ bend_n, int* __restrict__ flags,
                                                         double* __restrict__ box_out, int box_per_scene, int* __restrict__ zero4,
-                                                        int n_traj, int ord_n, const int* __restrict__ ord_key, int* __restrict__ ord_out, int* __restrict__ ord_zero4) {
+                                                        int n_traj, int ord_n, const int* __restrict__ ord_key, int* __restrict__ ord_out, int* __restrict__ ord_zero4,
+                                                        int pair_sort) {      // ("hull_sort": 0 the full network always, 1 pairs)
   // LDS of a wave: the groups' sorted points (8 KB) and their control points (2 KB, read again after the hull by the uninflated hull
   // of the entangle rows).  The knot vector lives in the last group's point area — it is dead before the first point is stored — so
   // that the wave takes exactly 10 KB: sixteen waves per CU, and the 8 192 waves of a 128-scene launch are two full rounds (with the
@@ -452,20 +530,6 @@ __global__ __launch_bounds__(64) void hull_group_kernel(const nep_traj_rec* __re
   const double dx = r->bbox[0] / 2.0 + drone_radius, dy = r->bbox[1] / 2.0 + drone_radius;  // neptune.cpp:340
   const bool inflate = !(sqrt(dx * dx + dy * dy) < 1e-6);
   const int np = inflate ? 4 * np0 : np0;          // inflated points: 4 corners per control point (:442-445)
-  double px[kGrpPts], py[kGrpPts];
-#pragma unroll
-  for (int j = 0; j < kGrpPts; j++) {
-    const int p = sub + 8 * j;
-    px[j] = 0; py[j] = 0;
-    if (p < np) {
-      if (inflate) {
-        const int c = p >> 2, q = p & 3;
-        const double x = cpx[c], y = cpy[c];
-        px[j] = (q < 2) ? x + dx : x - dx;
-        py[j] = (q == 0 || q == 3) ? y + dy : y - dy;
-      } else { px[j] = cpx[p]; py[j] = cpy[p]; }
-    }
-  }
   // The box of the hull's vertices is the box of the points it is the hull of (an extreme point is a vertex), and x -> x +- dx is monotone
   // in floating point too: min over the corners (x - dx) = (min x) - dx.  So: extremes of the control points over the group's lanes
   // (two points a lane, three exchange steps), then the corner offsets — the same four doubles fe_box_kernel reads off the vertices
@@ -491,7 +555,32 @@ __global__ __launch_bounds__(64) void hull_group_kernel(const nep_traj_rec* __re
   double cm0 = fmax(fmax(fabs(x0), fabs(x1)), fmax(fabs(y0), fabs(y1)));
   cm0 = __hiloint2double(__builtin_amdgcn_update_dpp(__double2hiint(cm0), __double2hiint(cm0), 0x114, 0xf, 0xa, false),
                          __builtin_amdgcn_update_dpp(__double2loint(cm0), __double2loint(cm0), 0x114, 0xf, 0xa, false));      // row_shr:4, banks 1 and 3
-  int k = group_hull<kGrpPts>(np, px, py, inflate ? cm0 + fmax(fabs(dx), fabs(dy)) : cm0, s_sxy[g], g, sub, act, hull_xy + out * kHullV * 2, kHullV);
+  const double cmax = inflate ? cm0 + fmax(fabs(dx), fabs(dy)) : cm0;
+  // The sort.  An inflated hull's corners are stacked pairs: half as many elements to sort, where the rule of hull_pair_sort.h allows
+  // it for every hull of the wave; otherwise, and without inflation, the corners are built and go through the full network.
+  bool sorted = false;
+  if (inflate && pair_sort) {
+    const bool ok = np0 <= 0 || pair_sort_allowed(cmax, dy);
+    sorted = group_sort_pairs(np0, cpx, cpy, dx, dy, ok, s_sxy[g], sub);
+  }
+  if (!sorted) {
+    double px[kGrpPts], py[kGrpPts];
+#pragma unroll
+    for (int j = 0; j < kGrpPts; j++) {
+      const int p = sub + 8 * j;
+      px[j] = 0; py[j] = 0;
+      if (p < np) {
+        if (inflate) {
+          const int c = p >> 2, q = p & 3;
+          const double x = cpx[c], y = cpy[c];
+          px[j] = (q < 2) ? x + dx : x - dx;
+          py[j] = (q == 0 || q == 3) ? y + dy : y - dy;
+        } else { px[j] = cpx[p]; py[j] = cpy[p]; }
+      }
+    }
+    group_sort<kGrpPts>(np, px, py, s_sxy[g], sub);
+  }
+  int k = group_hull_sorted<kGrpPts>(np, cmax, s_sxy[g], g, sub, act, hull_xy + out * kHullV * 2, kHullV);
   if (k > kHullV) { k = kHullV; if (act && sub == 0 && flags) atomicOr(flags, NEP_FLAG_HULL_OVERFLOW); }
   if (act && sub == 0) hull_nv[out] = k;
   if (hull0_nv) {
@@ -519,7 +608,7 @@ void launch_hulls_ts(const nep_traj_rec* recs, int n_scenes, int n_rec, const do
                        sp.num_pol, sp.T_span, sp.drone_radius, ps.hull_xy, ps.hull_nv, need0 ? ps.hull0_xy : nullptr,
                        need0 ? ps.hull0_nv : nullptr, need0 ? ps.bend_xy : nullptr, need0 ? ps.bend_n : nullptr, ps.flags,
                        boxes ? ps.fe_box : nullptr, sp.num_agents + sp.n_static, boxes ? ps.redo_count : nullptr,
-                       n_scenes * n_rec, ord ? n_scenes * sp.n_local : 0, ord ? (const int*)ps.order_key : nullptr, ord ? (int*)ps.order : nullptr, ord ? ps.polish_count : nullptr);
+                       n_scenes * n_rec, ord ? n_scenes * sp.n_local : 0, ord ? (const int*)ps.order_key : nullptr, ord ? (int*)ps.order : nullptr, ord ? ps.polish_count : nullptr, g_debug.hull_sort);
     return;
   }
   hipLaunchKernelGGL(hull_kernel, dim3(blocks), dim3(64), 0, st, recs, n_rec, ts0, ts_slot_stride * sp.n_local,
@@ -1944,7 +2033,7 @@ void launch_safety(const nep_traj_rec* prev, const nep_traj_rec* fresh, int n_sc
     if (eight_hulls_per_wave(sp.num_pol, sp.hull_mode, n_scenes, N))
       hipLaunchKernelGGL(hull_group_kernel, dim3(n_scenes * N), dim3(64), 0, st, recs, N, &ps.guess->t_start, (long)sizeof(nep_guess) * sp.n_local, sp.num_pol, sp.T_span,
                          sp.drone_radius, ps.hull_xy, ps.hull_nv, (double*)nullptr, (int*)nullptr, (double*)nullptr, (int*)nullptr, ps.flags,
-                         (double*)nullptr, 0, (int*)nullptr, n_scenes * N, 0, (const int*)nullptr, (int*)nullptr, (int*)nullptr);
+                         (double*)nullptr, 0, (int*)nullptr, n_scenes * N, 0, (const int*)nullptr, (int*)nullptr, (int*)nullptr, g_debug.hull_sort);
     else
       hipLaunchKernelGGL(hull_kernel, dim3(n_scenes * N * sp.num_pol), dim3(64), 0, st, recs, N, &ps.guess->t_start, (long)sizeof(nep_guess) * sp.n_local, sp.num_pol, sp.T_span,
                          sp.drone_radius, ps.hull_xy, ps.hull_nv, (double*)nullptr, (int*)nullptr, (double*)nullptr, (int*)nullptr, ps.flags);

@@ -22,7 +22,7 @@ constexpr int kBend = NEP_MAX_BEND;      // 8
 // only — results do not depend on them — and never read from the environment (the library behaves the same under any environment).
 // One exception, a test hook's: bit 9 of a slot's polish flag word (nep_batch_debug_polish_flags: "the pass read the parked lines back")
 // says what polish_impl and parked_bound made the pass do, and so differs with them; every result of a replan is the same.
-struct DebugGlobals { bool fe_three = false; int fe_xcd = 1; int polish_grid = 256; int polish_impl = 1; int parked_bound = 1; };      // (fe_three, fe_xcd: read where a front-end call's facts are filled, backend.hip)
+struct DebugGlobals { bool fe_three = false; int fe_xcd = 1; int polish_grid = 256; int polish_impl = 1; int parked_bound = 1; int hull_sort = 1; };      // (fe_three, fe_xcd: read where a front-end call's facts are filled, backend.hip)
 extern DebugGlobals g_debug;
 
 // Scene-level constants (setMaxValues, ctor arguments; solver_gurobi_poly.cpp:25-175)
