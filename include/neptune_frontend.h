@@ -488,6 +488,51 @@ int nep_audit_records(const nep_traj_rec* recs, int32_t n, const int32_t* static
 int nep_batch_audit(nep_batch_t* h, const nep_traj_rec* d_records, const nep_fe_start* d_start, double tick, int32_t n_ticks,
                     nep_audit* d_audit, void* stream);
 
+/* ---- Span audit: the same three clearances between the ticks ----------------------------------------------
+ * nep_audit looks at the control ticks; the planner promises its box clearance for every t.  The span audit takes the minima of
+ * the centre distance, the box clearance and the signed static distance over the whole closed window
+ * [t_start, t_start + n_ticks * tick] of a call — exactly: the records are cubics, so the window is cut at the ticks and at every
+ * knot of the records involved, and on each piece the minima lie at its ends or at real roots of polynomials of degree <= 5.
+ * Those polynomials only find candidate TIMES; every value is taken by nep_audit's own expressions at the candidate time, so the
+ * ticks are among the candidates, evaluated identically: a call's span minimum is <= the minimum nep_audit finds over the same
+ * call's ticks, as doubles, and where the tick is the earliest time at which the value is attained, time and partner agree too.
+ *
+ * nep_span_audit          one entry per (scene, agent); calls ACCUMULATE into it.  Initial values (nep_span_audit_init): the
+ *                         minima and center_d2 +inf, partners and index -1, everything else 0.  nep_abi_sizeof(39) is its size.
+ *   min_center_dist, center_partner, t_center   as in nep_audit, over the window; the time is the candidate's
+ *   min_box_clear, box_partner, t_box           likewise
+ *   min_static_dist, static_index, t_static     likewise
+ *   center_d2             min_center_dist squared, carried from call to call
+ *   span                  seconds audited: the sum of the calls' window lengths
+ *   n_spans, n_pair_viol, n_static_viol         calls; calls whose box minimum was < 0; calls whose static minimum was < 0
+ *   gap_box, gap_static   the largest amount by which a call's span minimum lay below the minimum over that call's ticks: what
+ *                         the tick audit missed
+ * A minimum is the least (value, time, partner id or static index), in that order: ties go to the earlier time, then to the lower
+ * partner or index; across calls the earlier call keeps a tie.  Records are read by nep_audit's rules (present = valid &&
+ * is_agent && n_seg >= 1; at rest before the first knot and beyond the last; x-y only; the active mask does not apply).
+ *
+ * nep_span_audit_records  host form (no HIP call), the arguments of nep_audit_records; tick must be finite.
+ * nep_batch_audit_span    device form, byte-identical to the host form; the contract of nep_batch_audit: a scene's clock is the
+ *                         t_start of its first slot in d_start, n_ticks = 0 does nothing, the handle's static polygons are used,
+ *                         unsharded handles only (else NEP_E_STATE), asynchronous on `stream` and capturable: the FIRST call
+ *                         (n_ticks = 0 will do) sets the kernel's LDS size up, later ones nothing; no call allocates (a wave
+ *                         merges its lanes in registers, there is no scratch).  NEP_E_CAP when the scene's agents and polygons
+ *                         do not fit into 160 KB of LDS (about 700 agents with 100 four-edge polygons).                       */
+typedef struct nep_span_audit {
+  double min_center_dist, t_center;
+  double min_box_clear, t_box;
+  double min_static_dist, t_static;
+  double center_d2, span;
+  double gap_box, gap_static;
+  int32_t center_partner, box_partner, static_index;
+  int32_t n_spans, n_pair_viol, n_static_viol;
+} nep_span_audit;
+int nep_span_audit_init(nep_span_audit* out, int64_t n);
+int nep_span_audit_records(const nep_traj_rec* recs, int32_t n, const int32_t* static_off, const double* static_xy, int32_t n_static,
+                           double drone_radius, double t0, double tick, int32_t n_ticks, nep_span_audit* out);
+int nep_batch_audit_span(nep_batch_t* h, const nep_traj_rec* d_records, const nep_fe_start* d_start, double tick, int32_t n_ticks,
+                         nep_span_audit* d_span, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

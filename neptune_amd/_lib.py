@@ -47,7 +47,7 @@ PLAN_EXPORTS = [
 ]
 # every symbol include/neptune_entangle.h declares (host-only)
 # include/neptune_frontend.h
-FE_EXPORTS = ["nep_batch_frontend", "nep_batch_frontend_hulls", "nep_batch_set_fe_astar", "nep_batch_frontend_astar", "nep_batch_frontend_astar_ent", "nep_batch_set_fe_astar_team", "nep_batch_fe_astar_team", "nep_batch_goal_gate", "nep_batch_set_static_reps", "nep_batch_set_fe_ent_big_records", "nep_batch_frontend_ent", "nep_batch_frontend_ent_hulls", "nep_batch_safety_commit_ent", "nep_batch_track_ent", "nep_batch_track_ent_lists", "nep_batch_ent_lists_at_a", "nep_batch_next_starts", "nep_batch_audit", "nep_audit_records", "nep_audit_init", "nep_batch_set_tether_audit"]
+FE_EXPORTS = ["nep_batch_frontend", "nep_batch_frontend_hulls", "nep_batch_set_fe_astar", "nep_batch_frontend_astar", "nep_batch_frontend_astar_ent", "nep_batch_set_fe_astar_team", "nep_batch_fe_astar_team", "nep_batch_goal_gate", "nep_batch_set_static_reps", "nep_batch_set_fe_ent_big_records", "nep_batch_frontend_ent", "nep_batch_frontend_ent_hulls", "nep_batch_safety_commit_ent", "nep_batch_track_ent", "nep_batch_track_ent_lists", "nep_batch_ent_lists_at_a", "nep_batch_next_starts", "nep_batch_audit", "nep_audit_records", "nep_audit_init", "nep_batch_set_tether_audit", "nep_span_audit_init", "nep_span_audit_records", "nep_batch_audit_span"]
 # include/neptune_fleet.h
 FLEET_EXPORTS = ["nep_batch_fleet_init", "nep_batch_fleet_select", "nep_batch_fleet_commit", "nep_batch_fleet_tick", "nep_batch_fleet_ring_cap",
                  "nep_batch_fleet_plans", "nep_batch_fleet_state", "nep_batch_fleet_counters", "nep_batch_fleet_init_ent", "nep_batch_fleet_predict_ent",
@@ -221,6 +221,9 @@ def lib():
     L.nep_batch_audit.argtypes = [vp, vp, vp, d, i, vp, vp]
     L.nep_audit_records.argtypes = [vp, i, pi, pd, i, d, d, d, i, vp]
     L.nep_audit_init.argtypes = [vp, C.c_int64]
+    L.nep_batch_audit_span.argtypes = [vp, vp, vp, d, i, vp, vp]
+    L.nep_span_audit_records.argtypes = [vp, i, pi, pd, i, d, d, d, i, vp]
+    L.nep_span_audit_init.argtypes = [vp, C.c_int64]
     L.nep_batch_fleet_init.argtypes = [vp, C.POINTER(abi.nep_fleet_cfg), vp, vp, vp, vp, vp]
     L.nep_batch_fleet_select.argtypes = [vp, vp, vp, vp, vp, vp]
     L.nep_batch_fleet_commit.argtypes = [vp, vp, vp, vp, vp, vp, vp]
@@ -285,7 +288,7 @@ def lib():
                           (13, abi.nep_fe_result), (14, abi.nep_fe_ent_state), (17, abi.nep_audit), (18, abi.nep_fleet_cfg),
                           (20, abi.nep_mission_cfg), (21, abi.nep_mission_leg), (23, abi.nep_ent_lists), (25, abi.nep_fleet_snapshot_hdr), (27, abi.nep_moveback_cfg),
                           (29, abi.nep_fleet_effort), (31, abi.nep_hastar_cfg), (32, abi.nep_hastar_result), (33, abi.nep_hastar_state),
-                          (35, abi.nep_mtlp_cfg), (36, abi.nep_mtlp_result), (37, abi.nep_tether_audit)):
+                          (35, abi.nep_mtlp_cfg), (36, abi.nep_mtlp_result), (37, abi.nep_tether_audit), (39, abi.nep_span_audit)):
         if L.nep_abi_sizeof(which) != C.sizeof(struct):
             raise BackendError("%s: sizeof(%s) is %d in the library, %d in neptune_amd/abi.py — rebuild the library from this tree's headers"
                                % (LIB_PATH, struct.__name__, L.nep_abi_sizeof(which), C.sizeof(struct)))

@@ -211,6 +211,15 @@ class nep_audit(C.Structure):
                 ("n_ticks", C.c_int32), ("n_pair_viol", C.c_int32), ("n_static_viol", C.c_int32)]
 
 
+class nep_span_audit(C.Structure):
+    """include/neptune_frontend.h: the span audit of one (scene, agent): the flight audit's minima over whole windows; calls accumulate."""
+    _fields_ = [("min_center_dist", C.c_double), ("t_center", C.c_double), ("min_box_clear", C.c_double), ("t_box", C.c_double),
+                ("min_static_dist", C.c_double), ("t_static", C.c_double), ("center_d2", C.c_double), ("span", C.c_double),
+                ("gap_box", C.c_double), ("gap_static", C.c_double),
+                ("center_partner", C.c_int32), ("box_partner", C.c_int32), ("static_index", C.c_int32),
+                ("n_spans", C.c_int32), ("n_pair_viol", C.c_int32), ("n_static_viol", C.c_int32)]
+
+
 class nep_tether_audit(C.Structure):
     """include/neptune_entangle.h: the tether audit of one (scene, agent); the tracking calls accumulate one tick per move into it."""
     _fields_ = [("max_len", C.c_double), ("t_max_len", C.c_double), ("sum_len", C.c_double), ("last_len", C.c_double),
@@ -362,6 +371,7 @@ FE_RESULT_DTYPE = np.dtype(nep_fe_result)
 FE_ENT_STATE_DTYPE = np.dtype(nep_fe_ent_state)
 AUDIT_DTYPE = np.dtype(nep_audit)
 TETHER_AUDIT_DTYPE = np.dtype(nep_tether_audit)
+SPAN_AUDIT_DTYPE = np.dtype(nep_span_audit)
 PWP_DTYPE = np.dtype(nep_pwp)
 MISSION_LEG_DTYPE = np.dtype(nep_mission_leg)
 EFFORT_DTYPE = np.dtype(nep_fleet_effort)

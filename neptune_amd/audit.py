@@ -3,6 +3,10 @@
 `audit_records` is the host form through ctypes (nep_audit_records, no HIP call behind it); the device form is
 BatchBackend.audit and equals it bit for bit.  `summarize` turns the per-agent records into one line of facts per scene.
 
+Span audit (include/neptune_frontend.h: nep_span_audit): the same three minima over the whole flown window, not
+only at its ticks.  `span_audit_records` is the host form, BatchBackend.audit_span the device form, byte for byte the same;
+`summarize_span` and `format_span_summary` give the facts and the lines, among them how much the ticks missed.
+
 Tether audit (include/neptune_entangle.h: nep_tether_audit): taut length, slack and winding of every tracked move.
 `tether_audit_records` is the host form (a chain of nep_ent_track_step_audit); the device form is BatchBackend.set_tether_audit and
 equals it byte for byte.  `summarize_tethers` gives the facts per scene, `format_tether_summary` the lines the scripts print."""
@@ -80,6 +84,69 @@ def format_summary(summary):
             lines.append("audit %-16s %+.9f m  scene %d  agent %d  %s %d  t %.3f s" % (key, m["value"], s, m["agent"], whom, m["partner"], m["t"]))
     lines.append("audit ticks %d  pair violations %d (agent-ticks, in %d scenes)  static violations %d (in %d scenes)  of %d scenes"
                  % (max(sc["n_ticks"] for sc in summary), sum(sc["n_pair_viol"] for sc in summary), sum(sc["n_pair_viol"] > 0 for sc in summary),
+                    sum(sc["n_static_viol"] for sc in summary), sum(sc["n_static_viol"] > 0 for sc in summary), len(summary)))
+    return lines
+
+
+# ---- the span audit ---------------------------------------------------------------------------------------------------------------
+def new_span_audit(n):
+    """n records with the initial values: minima +inf, partners and index -1, the rest 0 (nep_span_audit_init)"""
+    out = np.zeros(n, dtype=abi.SPAN_AUDIT_DTYPE)
+    check(lib().nep_span_audit_init(out.ctypes.data_as(C.c_void_p), n))
+    return out
+
+
+def span_audit_records(recs, statics, drone_radius, t0, tick, n_ticks, out=None):
+    """One scene over the whole window [t0, t0 + n_ticks*tick], not only at its ticks (nep_span_audit_records):
+    the arguments of audit_records.  Accumulates into `out` ([n] SPAN_AUDIT_DTYPE, made fresh when None) and returns it."""
+    recs = np.ascontiguousarray(recs, dtype=abi.TRAJ_REC_DTYPE).reshape(-1)
+    n = len(recs)
+    if out is None:
+        out = new_span_audit(n)
+    assert out.dtype == abi.SPAN_AUDIT_DTYPE and out.shape == (n,) and out.flags["C_CONTIGUOUS"]
+    off, xy = scene.statics_csr(statics)
+    check(lib().nep_span_audit_records(recs.ctypes.data_as(C.c_void_p), n, abi.iptr(off), abi.dptr(xy), len(statics), float(drone_radius),
+                                       float(t0), float(tick), int(n_ticks), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def summarize_span(span, n_scenes=1):
+    """span: [n_scenes*N] SPAN_AUDIT_DTYPE (or the bytes of it) -> one dict per scene: the three minima as summarize gives them, the
+    violation counts (agent-calls), the seconds audited and the largest gaps to the tick audit (what the sampler missed)"""
+    a = np.asarray(span)
+    if a.dtype != abi.SPAN_AUDIT_DTYPE:
+        a = a.view(abi.SPAN_AUDIT_DTYPE)
+    a = a.reshape(n_scenes, -1)
+    out = []
+    for s in range(n_scenes):
+        r = a[s]
+        out.append(dict(min_center_dist=_worst(r, "min_center_dist", "center_partner", "t_center"),
+                        min_box_clear=_worst(r, "min_box_clear", "box_partner", "t_box"),
+                        min_static_dist=_worst(r, "min_static_dist", "static_index", "t_static"),
+                        n_pair_viol=int(r["n_pair_viol"].sum()), n_static_viol=int(r["n_static_viol"].sum()),
+                        n_spans=int(r["n_spans"].max()) if len(r) else 0, span=float(r["span"].max()) if len(r) else 0.0,
+                        gap_box=float(r["gap_box"].max()) if len(r) else 0.0, gap_static=float(r["gap_static"].max()) if len(r) else 0.0))
+    return out
+
+
+def format_span_summary(summary):
+    """the lines the scripts print next to the tick audit's: the worst scene of each minimum over the whole flight, then the gaps"""
+    lines = []
+    for key, whom in (("min_center_dist", "agent"), ("min_box_clear", "agent"), ("min_static_dist", "polygon")):
+        best = None
+        for s, sc in enumerate(summary):
+            m = sc[key]
+            if m is not None and (best is None or m["value"] < best[1]["value"]):
+                best = (s, m)
+        if best is None:
+            lines.append("span  %-16s none" % key)
+        else:
+            s, m = best
+            lines.append("span  %-16s %+.9f m  scene %d  agent %d  %s %d  t %.6f s" % (key, m["value"], s, m["agent"], whom, m["partner"], m["t"]))
+    lines.append("span  gaps to the ticks: box %.9f m  static %.9f m  over %.3f s in %d calls  pair violations %d (agent-calls, in %d scenes)  "
+                 "static violations %d (in %d scenes)  of %d scenes"
+                 % (max(sc["gap_box"] for sc in summary), max(sc["gap_static"] for sc in summary), max(sc["span"] for sc in summary),
+                    max(sc["n_spans"] for sc in summary), sum(sc["n_pair_viol"] for sc in summary), sum(sc["n_pair_viol"] > 0 for sc in summary),
                     sum(sc["n_static_viol"] for sc in summary), sum(sc["n_static_viol"] > 0 for sc in summary), len(summary)))
     return lines
 

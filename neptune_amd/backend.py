@@ -449,6 +449,16 @@ class BatchBackend:
         st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
         check(lib().nep_batch_audit(self._h, d_records.data_ptr(), d_start.data_ptr(), float(tick), int(n_ticks), d_audit.data_ptr(), st.cuda_stream))
 
+    def new_span_audit(self):
+        """device buffer of n_scenes*N span-audit records with the initial values (SPAN_AUDIT_DTYPE bytes; nep_span_audit_init)"""
+        from . import audit
+        return self.to_device(audit.new_span_audit(self.n_scenes * self.par.num_agents))
+
+    def audit_span(self, d_records, d_start, tick, n_ticks, d_span, stream=None):
+        """the span audit of d_records over the window [t_start, t_start + n_ticks*tick], accumulated into d_span (nep_batch_audit_span)"""
+        st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        check(lib().nep_batch_audit_span(self._h, d_records.data_ptr(), d_start.data_ptr(), float(tick), int(n_ticks), d_span.data_ptr(), st.cuda_stream))
+
     def new_tether_audit(self):
         """device buffer of n_scenes*N tether-audit records with the initial values (TETHER_AUDIT_DTYPE bytes; nep_tether_audit_init)"""
         from . import audit

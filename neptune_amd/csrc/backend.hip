@@ -1680,6 +1680,27 @@ int nep_batch_audit(nep_batch_t* h, const nep_traj_rec* d_records, const nep_fe_
   return 0;
 }
 
+int nep_batch_audit_span(nep_batch_t* h, const nep_traj_rec* d_records, const nep_fe_start* d_start, double tick, int32_t n_ticks,
+                         nep_span_audit* d_span, void* stream) {
+  if (!h || !d_records || !d_start || !d_span || n_ticks < 0 || !(tick >= 0.0 && tick < HUGE_VAL)) return fail(NEP_E_ARG, "bad arguments");
+  if (h->cfg.n_local != h->cfg.num_agents) return fail(NEP_E_STATE, "the span audit runs on an unsharded handle (n_local == num_agents)");
+  Engine& E = h->eng;
+  const int N = h->cfg.num_agents, S = h->cfg.n_scenes;
+  const int vs = E.sp.n_static > 0 ? std::max(E.static_nv_max, 1) : 1;
+  const long long lds = span_audit_lds_bytes(N, E.sp.n_static, vs);
+  if (lds > kLdsPerCu) return fail(NEP_E_CAP, "the span audit's agents and static polygons do not fit into 160 KB of LDS");
+  HIPCHK(prepare_audit_span(lds));      // (before the n_ticks == 0 return: what the first call has to set up; there is no scratch to allocate)
+  if (n_ticks == 0) return 0;
+  const ProblemSet ps = round_set(h);
+  SpanAuditArgs sa{};
+  sa.N = N; sa.S = E.sp.n_static; sa.n_scenes = S; sa.static_stride = E.sp.static_stride; sa.vstride = vs; sa.n_ticks = n_ticks;
+  sa.tick = tick; sa.drone_radius = E.sp.drone_radius;
+  sa.recs = d_records; sa.starts = d_start; sa.static_xy = ps.static_xy; sa.static_nv = ps.static_nv; sa.out = d_span;
+  launch_audit_span(sa, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // ---- the committed plans on the device (include/neptune_fleet.h; kernels: fleet_kernels.hip) ----
 namespace {
 // a null handle without a device is "no device" (nothing could have made a handle), with one it is a bad argument
@@ -2699,6 +2720,7 @@ int nep_abi_sizeof(int32_t which) {
     case 35: return (int)sizeof(nep_mtlp_cfg);      // (34 stays unassigned: tests/test_mtlp_cpu.py pins it to -1)
     case 36: return (int)sizeof(nep_mtlp_result);
     case 37: return (int)sizeof(nep_tether_audit);
+    case 39: return (int)sizeof(nep_span_audit);      // (38 stays unassigned: tests/test_tether_audit_cpu.py pins it to -1)
     default: return -1;
   }
 }

@@ -238,6 +238,30 @@ NEP_LDS_HD AuditLayout audit_layout(int N, int S, int vstride) {
   return L;
 }
 
+// ---- 5b. span_audit_kernel (audit_span_kernels.hip) -----------------------------------------------------------------------------------
+// (pieces: kSpanLdsPieces, piece_bytes: sizeof(SpanPiece), both audit_span_common.h's — this header knows neither)
+struct SpanAuditLayout {
+  long long pxy;              // [S][vstride][2] double: polygon vertices
+  long long pinv;             // [S][vstride] double: 1 / |edge|^2
+  long long pc;               // [N][pieces] SpanPiece: a record's pieces inside the window
+  long long ts;               // [N][pieces] double: where each begins
+  long long hxy;              // [N][2] double: inflated half-widths
+  long long box;              // [N][4] double: a box round the record's positions over the window (the pruning bound)
+  long long pnv;              // [S] int: vertex counts
+  long long npc;              // [N] int: pieces staged (-1: more than `pieces`, read the record)
+  long long apres;            // [N] int
+  long long bytes;
+};
+NEP_LDS_HD SpanAuditLayout span_audit_layout(int N, int S, int vstride, int pieces, int piece_bytes) {
+  SpanAuditLayout L;
+  const long long sv = (long long)S * vstride, np = (long long)N * pieces;
+  L.pxy = 0; L.pinv = sv * 2 * 8; L.pc = L.pinv + sv * 8; L.ts = L.pc + np * piece_bytes; L.hxy = L.ts + np * 8;
+  L.box = L.hxy + (long long)N * 2 * 8;
+  L.pnv = L.box + (long long)N * 4 * 8; L.npc = L.pnv + (long long)S * 4; L.apres = L.npc + (long long)N * 4;
+  L.bytes = L.apres + (long long)N * 4;
+  return L;
+}
+
 // ---- 6. fleet_mission_kernel --------------------------------------------------------------------------------------------------------
 // (the kernel carves with its scene's vertex and polygon counts, the launch is sized with NEP_MISSION_MAX_VERT and NEP_MISSION_MAX_POLY)
 struct MissionLayout {

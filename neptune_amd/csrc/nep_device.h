@@ -277,6 +277,19 @@ struct AuditArgs {
   nep_audit* out;                // [scenes][N] accumulated into
 };
 void launch_audit(const AuditArgs& aa, hipStream_t st);
+// nep_batch_audit_span (audit_span_kernels.hip): the span audit of every (scene, agent), one wave per agent
+struct SpanAuditArgs {
+  int N, S, n_scenes, static_stride, vstride, n_ticks;
+  double tick, drone_radius;
+  const nep_traj_rec* recs;      // [scenes][N]
+  const nep_fe_start* starts;    // [scenes][N]: a scene's clock is its first slot's t_start
+  const double* static_xy;       // [scenes or 1][S][kHullV][2]
+  const int* static_nv;          // [scenes or 1][S]
+  nep_span_audit* out;           // [scenes][N] accumulated into
+};
+long long span_audit_lds_bytes(int N, int S, int vstride);
+hipError_t prepare_audit_span(long long lds_bytes);
+void launch_audit_span(const SpanAuditArgs& sa, hipStream_t st);
 // nep_batch_fleet_* (fleet_kernels.hip, include/neptune_fleet.h): the committed plans of every slot.  All device pointers.
 struct FleetArgs {
   int N, n_scenes, cap, max_states;

@@ -164,11 +164,21 @@ class _Audited:
         """the flight audit so far: AUDIT_DTYPE, [N] (FleetLoop) or [S, N]"""
         return self.d_audit.cpu().numpy().view(abi.AUDIT_DTYPE).reshape(self._audit_shape)
 
+    def span_audit_records(self):
+        """the span audit so far: SPAN_AUDIT_DTYPE, [N] (FleetLoop) or [S, N]; span_audit= must be on"""
+        return self.d_span.cpu().numpy().view(abi.SPAN_AUDIT_DTYPE).reshape(self._audit_shape)
+
     def tether_audit_records(self):
         """the tether audit so far: TETHER_AUDIT_DTYPE, [N] (FleetLoop) or [S, N]; tether_audit= must be on"""
         if isinstance(self.d_tether_audit, np.ndarray):      # (FleetLoop: the host form)
             return self.d_tether_audit.copy().reshape(self._audit_shape)
         return self.d_tether_audit.cpu().numpy().view(abi.TETHER_AUDIT_DTYPE).reshape(self._audit_shape)
+
+
+def check_span_audit(span_audit, audit):
+    if span_audit and not audit:
+        raise ValueError("span_audit=True audits the stretch between the tick audit's ticks: it needs audit=True")
+    return bool(span_audit)
 
 
 def check_tether_audit(tether_audit, tethers):
@@ -180,9 +190,12 @@ def check_tether_audit(tether_audit, tethers):
 class FleetLoop(_Audited):
     def __init__(self, par, statics, starts, goals, beam_width=32, delta_t_states=6, replan_every=5, device=None, skip_arrived=False, audit=False,
                  tethers=False, check=True, ent_samples=3, search="beam", max_pops=300, moveback=None, goal_gate=False, fly_guess=False, team=1,
-                 tether_audit=False):
+                 tether_audit=False, span_audit=False):
         import torch
         from . import mission
+        # span_audit (with audit=True, else ValueError): right behind the tick audit the same records go through nep_batch_audit_span
+        # over the same window — the minima between the ticks too.  stats then carries its summary
+        self.span_audit = check_span_audit(span_audit, audit)
         # tether_audit: every tracked control tick also goes into a nep_tether_audit per agent (nep_ent_track_step_audit in the chain
         # below) — the host form of DeviceFleetLoop(tether_audit=True).  stats then carries its summary
         self.tether_audit = check_tether_audit(tether_audit, tethers)
@@ -260,6 +273,7 @@ class FleetLoop(_Audited):
         # audit: every round also audits, on the device, the records it uploads anyway over the replan_every ticks about to be flown
         # (nep_batch_audit; those ticks lie before the round's point A, so the uploaded records describe them); _tick keeps its host log
         self.d_audit = self.be.new_audit() if audit else None
+        self.d_span = self.be.new_span_audit() if self.span_audit else None
         self._audit_shape = (N,)
         self.d_tether_audit = audit_mod.new_tether_audit(N) if self.tether_audit else None      # (host memory: the chain runs here)
 
@@ -328,7 +342,10 @@ class FleetLoop(_Audited):
         if self.d_audit is not None:
             clock = np.zeros(N, dtype=abi.FE_START_DTYPE)
             clock["t_start"] = t_now + self.dc      # the first tick about to be flown
-            be.audit(d_com, be.to_device(clock), self.dc, self.replan_every, self.d_audit)
+            d_clock = be.to_device(clock)
+            be.audit(d_com, d_clock, self.dc, self.replan_every, self.d_audit)
+            if self.d_span is not None:
+                be.audit_span(d_com, d_clock, self.dc, self.replan_every, self.d_span)
         d_guess = torch.zeros(N * abi.GUESS_DTYPE.itemsize, dtype=torch.uint8, device=be.device)
         d_fres = torch.zeros(N * abi.FE_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=be.device)
         d_final = torch.empty_like(d_com); d_acc = torch.zeros(N, dtype=torch.int32, device=be.device)
@@ -436,6 +453,8 @@ class FleetLoop(_Audited):
         self.stats["dist_to_goal_mean"] = float(np.hypot(*(self.state[:, :2] - self.goals[:, :2]).T).mean())
         if self.d_audit is not None:
             self.stats["audit"] = audit_mod.summarize(self.audit_records())[0]
+        if self.d_span is not None:
+            self.stats["span_audit"] = audit_mod.summarize_span(self.span_audit_records())[0]
         if self.d_tether_audit is not None:
             self.stats["tether_audit"] = audit_mod.summarize_tethers(self.tether_audit_records(), self.p.tether_length)[0]
         return self.stats
@@ -543,15 +562,16 @@ class DeviceFleetLoop(_Audited):
 
     # the options a restored flight must share with the flight the snapshot was taken from
     _MUST_MATCH = ("beam_width", "delta_t_states", "replan_every", "audit", "ring_cap", "tethers", "check", "ent_samples", "ent_cap", "moveback", "goal_gate", "fly_guess",
-                   "script", "effort", "tether_audit")
+                   "script", "effort", "tether_audit", "span_audit")
 
     def __init__(self, scenes, beam_width=32, delta_t_states=6, replan_every=5, periods=None, phases=None, audit=False, graph=True,
                  goals=None, device=None, ring_cap=0, trace=False, tethers=False, check=True, ent_samples=3, missions=None, ent_cap=None,
                  ent_lists0=None, recorder=None, search="beam", max_pops=300, moveback=None, goal_gate=False, fly_guess=False, effort=False, team=1,
-                 tether_audit=False):
+                 tether_audit=False, span_audit=False):
         import torch
         from . import mission as mission_mod
         self.tether_audit = check_tether_audit(tether_audit, tethers)
+        self.span_audit = check_span_audit(span_audit, audit)
         self.team = check_team(team, search)      # (waves per search of search="astar_ent"; not among the options a checkpoint carries: the flight does not depend on it)
         self.torch = torch
         self.scenes = scenes
@@ -566,7 +586,8 @@ class DeviceFleetLoop(_Audited):
         self._opts = dict(beam_width=beam_width, delta_t_states=delta_t_states, replan_every=replan_every, audit=audit, ring_cap=ring_cap,
                           tethers=tethers, check=check, ent_samples=ent_samples, ent_cap=ent_cap, missions=missions, goals=goals,
                           search=search, max_pops=max_pops, moveback=moveback, goal_gate=self.goal_gate, fly_guess=self.fly_guess,
-                          script=mission_mod.spec_plain(missions)[1], effort=self.effort, team=self.team, tether_audit=self.tether_audit)
+                          script=mission_mod.spec_plain(missions)[1], effort=self.effort, team=self.team, tether_audit=self.tether_audit,
+                          span_audit=self.span_audit)
         S = self.S = len(scenes)
         p = self.p = scenes[0]["par"]
         self.tethers, self.check, self.ent_samples = tethers, check, ent_samples
@@ -616,6 +637,11 @@ class DeviceFleetLoop(_Audited):
         if audit:
             self.d_audit = be.new_audit()
             be.audit(self.d_rec, self.d_clock, p.dc, 0, self.d_audit)      # (the call that allocates: made here, outside any capture)
+        # span_audit: the tick audit's records and window through nep_batch_audit_span, right behind it in the round
+        self.d_span = None
+        if self.span_audit:
+            self.d_span = be.new_span_audit()
+            be.audit_span(self.d_rec, self.d_clock, p.dc, 0, self.d_span)      # (checks the capacities here, outside any capture)
         self.ent_cap = None
         self.d_hold = None
         if tethers and ent_cap is not None:
@@ -687,6 +713,8 @@ class DeviceFleetLoop(_Audited):
             self.after_commit(self)
         if self.d_audit is not None:
             be.audit(self.d_rec, self.d_clock, self.p.dc, self.replan_every, self.d_audit)
+            if self.d_span is not None:
+                be.audit_span(self.d_rec, self.d_clock, self.p.dc, self.replan_every, self.d_span)
         if self.tethers:
             be.fleet_track_ent(self.d_rec, self.d_flags)
         if self.missions is not None:
@@ -735,6 +763,7 @@ class DeviceFleetLoop(_Audited):
         state = st["state"].reshape(self.S, self.N, 12); done = st["done"].reshape(self.S, self.N)
         flags = st["flags"].reshape(self.S, self.N)
         summ = audit_mod.summarize(self.audit_records(), self.S) if self.d_audit is not None else None
+        ssum = audit_mod.summarize_span(self.span_audit_records(), self.S) if self.d_span is not None else None
         ever = be.fleet_ent_state(states=False)["ever"].reshape(self.S, self.N) if self.tethers else None
         lists = held = None
         if self.ent_cap is not None:
@@ -785,6 +814,8 @@ class DeviceFleetLoop(_Audited):
                 d["audit"] = summ[s]
                 d["min_pair_dist"] = summ[s]["min_center_dist"]["value"] if summ[s]["min_center_dist"] else np.inf
                 d["min_static_dist"] = summ[s]["min_static_dist"]["value"] if summ[s]["min_static_dist"] else np.inf
+            if ssum is not None:
+                d["span_audit"] = ssum[s]
             out.append(d)
         return out
 
@@ -853,6 +884,8 @@ class DeviceFleetLoop(_Audited):
         data = dict(blob=blob.cpu().numpy(), rounds=np.int64(self.rounds), options=np.array(json.dumps(self._options())))
         if self.d_audit is not None:
             data["audit"] = self.d_audit.cpu().numpy()
+        if self.d_span is not None:
+            data["span_audit"] = self.d_span.cpu().numpy()
         if self.d_gate_count is not None:
             data["gate_count"] = self.d_gate_count.cpu().numpy()
         if self.d_guess_count is not None:
@@ -878,9 +911,11 @@ class DeviceFleetLoop(_Audited):
             fcnt = z["guess_count"] if "guess_count" in z.files else None
             eff = z["effort"] if "effort" in z.files else None
             taud = z["tether_audit"] if "tether_audit" in z.files else None
+            saud = z["span_audit"] if "span_audit" in z.files else None
         opts.setdefault("script", None)        # (a file from before the options flew without them)
         opts.setdefault("effort", None)
         opts.setdefault("tether_audit", False)
+        opts.setdefault("span_audit", False)
         if "effort" in kw:
             kw = dict(kw, effort=mission.effort_slack(kw["effort"]))
         opts.setdefault("moveback", None)      # (a file from before the option flew without it)
@@ -922,6 +957,8 @@ class DeviceFleetLoop(_Audited):
                 lp.d_effort.copy_(lp.torch.from_numpy(eff))
             if taud is not None and lp.d_tether_audit is not None:
                 lp.d_tether_audit.copy_(lp.torch.from_numpy(taud))
+            if saud is not None and lp.d_span is not None:
+                lp.d_span.copy_(lp.torch.from_numpy(saud))
         except Exception:
             lp.close()
             raise
@@ -953,11 +990,12 @@ class TetherLoop(_Audited):
     handle's mask (`d_mask` = `active` and the fit; nep_batch_ent_lists_at_a), flying its record on.  report() adds held, max_list."""
 
     def __init__(self, scenes, beam_width=16, n_intervals=1, ent_samples=3, check=True, device=None, graph=True, active=None, audit=False,
-                 ent_cap=None, ent_lists0=None, tether_audit=False):
+                 ent_cap=None, ent_lists0=None, tether_audit=False, span_audit=False):
         import dataclasses
         import torch
         from neptune_amd import dist as ndist
         self.torch = torch
+        self.span_audit = check_span_audit(span_audit, audit)
         self.scenes = scenes
         S = self.S = len(scenes)
         p = self.p = dataclasses.replace(scenes[0]["par"], enable_entangle=True)
@@ -999,6 +1037,11 @@ class TetherLoop(_Audited):
         if audit:
             self.d_audit = be.new_audit()
             be.audit(self.d_rec, self.d_start, p.dc, 0, self.d_audit)      # (the call that allocates: made here, outside any capture)
+        # span_audit: the stretch the round flies, [t_start, t_start + n_intervals * T_span], between the ticks too
+        self.d_span = None
+        if self.span_audit:
+            self.d_span = be.new_span_audit()
+            be.audit_span(self.d_rec, self.d_start, p.dc, 0, self.d_span)      # (checks the capacities here, outside any capture)
         # tether_audit: track_ent / track_ent_lists also accumulate every sampled step they track into a nep_tether_audit per slot,
         # the steps T_span / ent_samples apart from the round's t_start
         self.d_tether_audit = None
@@ -1024,6 +1067,8 @@ class TetherLoop(_Audited):
         self.d_rec.copy_(self.d_final)
         if self.d_audit is not None:
             be.audit(self.d_rec, self.d_start, self.p.dc, self.audit_ticks, self.d_audit)
+            if self.d_span is not None:
+                be.audit_span(self.d_rec, self.d_start, self.p.dc, self.audit_ticks, self.d_span)
         be.next_starts(self.d_rec, self.n_intervals * self.p.T_span, self.d_start)
 
     def round(self):
@@ -1052,6 +1097,8 @@ class TetherLoop(_Audited):
             rep["max_list"] = [int(x) for x in self.lists.n_alpha.cpu().numpy().reshape(self.S, self.N).max(axis=1)]
         if self.d_audit is not None:
             rep["audit"] = audit_mod.summarize(self.audit_records(), self.S)
+        if self.d_span is not None:
+            rep["span_audit"] = audit_mod.summarize_span(self.span_audit_records(), self.S)
         if self.d_tether_audit is not None:
             rep["tether_audit"] = audit_mod.summarize_tethers(self.tether_audit_records(), self.p.tether_length, self.S)
         return rep

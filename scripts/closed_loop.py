@@ -2,7 +2,7 @@
 """Closed-loop flight of a fleet on the device path (neptune_amd/loop.py): every agent flies from its
 start next to its base to a random goal, replanning in bulk-synchronous rounds, the way the reference's
 benchmark driver logs a run (scripts/benchmark_mtlp.py:215-223: elapsed time, distance, success).
-  python scripts/closed_loop.py [--agents 16 --obstacles 8 --seed 0 --beam 32 --skip-arrived --audit --tethers [--no-check] [--tether-audit] --search astar --max-pops 300 --team 4]
+  python scripts/closed_loop.py [--agents 16 --obstacles 8 --seed 0 --beam 32 --skip-arrived --audit [--span-audit] --tethers [--no-check] [--tether-audit] --search astar --max-pops 300 --team 4]
 --tethers: tethered agents, the one-scene host form of DeviceFleetLoop(tethers=True) (entangle states kept on the host with
 nep_ent_track_step per control tick, nep_ent_predict_a per round).  --search astar: the reference's best-first search, --max-pops
 pops per search, in place of the beam (not with --tethers).  --moveback [RADIUS|ref] [--moveback-timeout S]: every agent first plans
@@ -20,6 +20,7 @@ ap.add_argument("--agents", type=int, default=16); ap.add_argument("--obstacles"
 ap.add_argument("--seed", type=int, default=0); ap.add_argument("--beam", type=int, default=32); ap.add_argument("--max-rounds", type=int, default=400)
 ap.add_argument("--skip-arrived", action="store_true", help="arrived agents leave the active set (nep_batch_set_active) instead of being solved and discarded")
 ap.add_argument("--audit", action="store_true", help="flight audit on the device (nep_batch_audit) next to the host's distance log")
+ap.add_argument("--span-audit", action="store_true", help="with --audit: the span audit (DESIGN section 43; nep_batch_audit_span) — the same minima over the whole flown stretch, between the ticks too, and how much the ticks missed")
 ap.add_argument("--tethers", action="store_true", help="tethered agents: entangle-aware front end and safety pass, tether states tracked per control tick")
 ap.add_argument("--tether-audit", action="store_true", help="with --tethers: the tether audit (DESIGN section 41; the host form, nep_ent_track_step_audit per control tick)")
 ap.add_argument("--no-check", action="store_true", help="with --tethers: plain front end and safety pass, the tracking stays on")
@@ -33,6 +34,8 @@ ap.add_argument("--fly-guess", action="store_true", help="the reference's rule f
 a = ap.parse_args()
 if a.tether_audit and not a.tethers:
     ap.error("--tether-audit audits the tethers: only with --tethers")
+if a.span_audit and not a.audit:
+    ap.error("--span-audit goes with the flight audit: only with --audit")
 gg = False if not a.goal_gate else True if a.goal_gate == "radius" else float(a.goal_gate)
 mb = None
 if a.moveback:
@@ -41,7 +44,7 @@ if a.moveback:
 sc = scene.make_scene(a.agents, a.obstacles, seed=a.seed)
 t0 = time.perf_counter()
 loop = FleetLoop(sc["par"], sc["statics"], sc["starts"], scene.reachable_goals(sc), beam_width=a.beam, skip_arrived=a.skip_arrived, audit=a.audit, tethers=a.tethers,
-                 check=not a.no_check, search=a.search, max_pops=a.max_pops, moveback=mb, goal_gate=gg, fly_guess=a.fly_guess, team=a.team, tether_audit=a.tether_audit)
+                 check=not a.no_check, search=a.search, max_pops=a.max_pops, moveback=mb, goal_gate=gg, fly_guess=a.fly_guess, team=a.team, tether_audit=a.tether_audit, span_audit=a.span_audit)
 if a.audit:
     loop.trace = []
 st = loop.run(a.max_rounds)
@@ -49,6 +52,7 @@ st["wall_s"] = time.perf_counter() - t0
 st["success"] = bool(st["reached"] == a.agents)
 summary = st.pop("audit", None)
 tethers = st.pop("tether_audit", None)
+span = st.pop("span_audit", None)
 print(json.dumps({k: (float(v) if hasattr(v, "dtype") else v) for k, v in st.items()}))
 if tethers is not None:
     from neptune_amd import audit
@@ -58,6 +62,9 @@ if summary is not None:
     from neptune_amd import audit
     for line in audit.format_summary([summary]):
         print(line)
+    if span is not None:
+        for line in audit.format_span_summary([span]):
+            print(line)
     # the replans of the round the smallest box clearance fell into, for the agent and its partner: (round start, agent, outcome, K, fe, qp)
     m = summary["min_box_clear"]
     if m is not None:

@@ -5,7 +5,7 @@ fleet_select -> fleet_predict_ent -> entangle-aware front end -> lines + QP with
 re-check -> fleet_commit -> [audit] -> fleet_track_ent -> fleet_tick (--no-check: the plain front end and safety pass, tracking on).  Prints the per-scene report (FleetLoop's
 stats), the totals, the wall time per round and, with --audit, the worst clearances over all scenes.
 
-  python scripts/fleet_loop.py --agents 64 --obstacles 20 --scenes 128 --rounds 30 [--stagger 5] [--audit] [--host] [--tethers [--no-check] [--tether-audit]]
+  python scripts/fleet_loop.py --agents 64 --obstacles 20 --scenes 128 --rounds 30 [--stagger 5] [--audit [--span-audit]] [--host] [--tethers [--no-check] [--tether-audit]]
 
 --missions {agent,runs} --goals G: fleet_mission joins the round before fleet_tick and flies a campaign of G goals per agent (runs per
 scene); the report gains the legs' accounts.
@@ -55,6 +55,7 @@ def main():
     ap.add_argument("--max-pops", type=int, default=300, help="with --search astar / astar_ent: pops per search")
     ap.add_argument("--team", type=int, choices=(1, 4), default=1, help="with --search astar_ent: waves per search (4: a workgroup of four waves per search, for fleets of few agents; the flight is the same)")
     ap.add_argument("--audit", action="store_true", help="flight audit of every round, inside the graph")
+    ap.add_argument("--span-audit", action="store_true", help="with --audit: the span audit (DESIGN section 43) right behind it in the round — the same minima over the whole flown stretch, between the ticks too, and how much the ticks missed")
     ap.add_argument("--tether-audit", action="store_true", help="with --tethers: the tether audit (DESIGN section 41) — taut length, slack, windings, list and bend counts of every tracked control tick, inside the tracking's launch")
     ap.add_argument("--eager", action="store_true", help="no graph capture")
     ap.add_argument("--tethers", action="store_true", help="tethered agents: entangle states tracked per control tick, predicted at A, checked by the front end and the safety pass")
@@ -84,7 +85,9 @@ def main():
     from neptune_amd.loop import DeviceFleetLoop, FleetLoop
     seeds = [a.seed0 + k for k in range(a.scenes)]
     scenes = scene.make_scenes(a.agents, a.obstacles, seeds, workers=min(len(seeds), len(os.sched_getaffinity(0)), 16))
-    kw = dict(beam_width=a.beam, audit=a.audit, graph=not a.eager, search=a.search, max_pops=a.max_pops, team=a.team)
+    if a.span_audit and not a.audit:
+        ap.error("--span-audit goes with the flight audit: only with --audit")
+    kw = dict(beam_width=a.beam, audit=a.audit, span_audit=a.span_audit, graph=not a.eager, search=a.search, max_pops=a.max_pops, team=a.team)
     if a.tether_audit and not a.tethers:
         ap.error("--tether-audit audits the tethers: only with --tethers")
     if a.tethers:
@@ -184,7 +187,7 @@ def main():
 
     rep, per_round, n = fly(scenes, a.rounds, a.resume)
     for s, r in enumerate(rep):
-        print("scene %d (seed %d): %s" % (s, seeds[s], json.dumps({k: v for k, v in r.items() if k not in ("audit", "tether_audit")})))
+        print("scene %d (seed %d): %s" % (s, seeds[s], json.dumps({k: v for k, v in r.items() if k not in ("audit", "tether_audit", "span_audit")})))
     tot = {k: int(sum(r[k] for r in rep)) for k in ("replans", "accepted", "fe_no_solution", "qp_failed", "qp_relaxed", "rejected_by_safety", "cap", "skipped", "reached")}
     if a.tethers:
         tot.update({k: int(sum(r[k] for r in rep)) for k in ("ever_entangled", "too_long", "track_cap")})
@@ -225,6 +228,9 @@ def main():
     if a.audit:
         for line in audit.format_summary([r["audit"] for r in rep]):
             print(line)
+        if a.span_audit:
+            for line in audit.format_span_summary([r["span_audit"] for r in rep]):
+                print(line)
         worst = min(r["audit"]["min_box_clear"]["value"] for r in rep if r["audit"]["min_box_clear"])
         print("scenes with min_box_clear < 0: %d of %d; worst %.9f m" % (sum(1 for r in rep if r["audit"]["min_box_clear"] and r["audit"]["min_box_clear"]["value"] < 0), len(rep), worst))
         # the round that flew the worst box clearance: the audit's ticks of round r are t0 + (r T + 1 .. r T + T) dc

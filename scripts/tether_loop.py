@@ -7,7 +7,7 @@ With --audit every round also runs the flight audit (nep_batch_audit) inside the
 minimum and, for the smallest box clearance and static distance, the round it fell into and what the replans of the agent and of its
 partner came to in that round (front-end status, QP status, accepted by the safety pass).
 
-  python scripts/tether_loop.py --agents 16 --obstacles 8 --scenes 4 --rounds 40 --crossing [--audit] [--tether-audit]"""
+  python scripts/tether_loop.py --agents 16 --obstacles 8 --scenes 4 --rounds 40 --crossing [--audit [--span-audit]] [--tether-audit]"""
 import argparse
 import json
 import os
@@ -31,7 +31,10 @@ def main():
     ap.add_argument("--ent-cap", metavar="K", help="the tracked states in the list form of K entries per slot (DESIGN section 24); 'auto' = 2 (agents + obstacles)")
     ap.add_argument("--tether-audit", action="store_true", help="the tether audit (DESIGN section 41): taut length, slack, windings, list and bend counts of every tracked step, inside the tracking's launch")
     ap.add_argument("--audit", action="store_true", help="flight audit of every round, inside the graph (reads each round's replan outcomes back)")
+    ap.add_argument("--span-audit", action="store_true", help="with --audit: the span audit (DESIGN section 43) right behind it in the graph — the same minima over the whole flown stretch, between the ticks too, and how much the ticks missed")
     a = ap.parse_args()
+    if a.span_audit and not a.audit:
+        ap.error("--span-audit goes with the flight audit: only with --audit")
     import numpy as np
     import torch
     from neptune_amd import abi, audit, scene
@@ -39,14 +42,14 @@ def main():
     seeds = [a.seed + k for k in range(a.scenes)]
     scenes = [scene.tether_crossing_scene(a.agents, a.obstacles, s) for s in seeds] if a.crossing else \
         scene.make_scenes(a.agents, a.obstacles, seeds, workers=min(len(seeds), len(os.sched_getaffinity(0))))
-    lp = TetherLoop(scenes, beam_width=a.beam, n_intervals=a.intervals, check=not a.no_check, audit=a.audit, tether_audit=a.tether_audit,
+    lp = TetherLoop(scenes, beam_width=a.beam, n_intervals=a.intervals, check=not a.no_check, audit=a.audit, tether_audit=a.tether_audit, span_audit=a.span_audit,
                     ent_cap=None if not a.ent_cap else "auto" if a.ent_cap == "auto" else int(a.ent_cap))
     t_first = float(lp.d_start.cpu().numpy().view(abi.FE_START_DTYPE)["t_start"][0])
     outcomes = []                               # --audit: per round [S, N, 3] front-end status, QP status, accepted
     # The scenes' initial records are part of the input, and an agent whose first replans fail keeps flying them: the audit of the
     # rounds that can still fly one (the first num_pol intervals) is reported apart from the audit of the rounds after them.
     split = -(-lp.p.num_pol // a.intervals)
-    early = []
+    early, early_span = [], []
 
     def run(n):
         if not a.audit:
@@ -59,6 +62,9 @@ def main():
             if lp.rounds == split and a.rounds > split:
                 early.append(audit.summarize(lp.audit_records(), S))
                 lp.d_audit.copy_(lp.be.new_audit())      # (in place: the captured graph keeps its buffer)
+                if a.span_audit:
+                    early_span.append(audit.summarize_span(lp.span_audit_records(), S))
+                    lp.d_span.copy_(lp.be.new_span_audit())
         torch.cuda.synchronize()
         return lp.report()
     run(2)                                      # eager round (allocations) + capture
@@ -67,6 +73,7 @@ def main():
     dt = (time.perf_counter() - t0) / max(a.rounds - 2, 1)
     summary = rep.pop("audit", None)
     tethers = rep.pop("tether_audit", None)
+    spans = rep.pop("span_audit", None)
     rep.update(agents=a.agents, obstacles=a.obstacles, scenes=a.scenes, crossing=a.crossing, check=not a.no_check,
                intervals=a.intervals, round_ms=dt * 1e3, note="round_ms includes one flag read-back per round")
     print(json.dumps(rep))
@@ -74,11 +81,14 @@ def main():
         for line in audit.format_tether_summary(tethers, cap=lp.ent_cap):
             print(line)
     span = a.intervals * lp.p.T_span
-    for name, summary in ([("rounds 0..%d (an initial record of the scene can still be flown)" % (split - 1), early[0]),
-                           ("rounds %d..%d" % (split, a.rounds - 1), summary)] if early else [("all rounds", summary)] if summary is not None else []):
+    for name, summary, between in ([("rounds 0..%d (an initial record of the scene can still be flown)" % (split - 1), early[0], early_span[0] if early_span else None),
+                                    ("rounds %d..%d" % (split, a.rounds - 1), summary, spans)] if early else [("all rounds", summary, spans)] if summary is not None else []):
         print("audit of", name)
         for line in audit.format_summary(summary):
             print(line)
+        if between is not None:
+            for line in audit.format_span_summary(between):
+                print(line)
         for key, is_pair in (("min_box_clear", True), ("min_static_dist", False)):
             cand = [(sc[key]["value"], s) for s, sc in enumerate(summary) if sc[key] is not None]
             if not cand:
