@@ -1,6 +1,6 @@
 // mtlp_host_check.cpp — the host form of the MTLP comparator (neptune_amd/csrc/mtlp_host.cpp, include/neptune_mtlp.h) as a
 // stand-alone executable for -fsanitize=address,undefined: the cases in which a capacity binds (the node pool, the budget of pops,
-// the path), the malformed inputs, and the exact arithmetic at the edges of the stated domain (coordinates of magnitude 1e5 and
+// the path), one robot alone and NEP_MTLP_MAX_ROBOTS robots (a full list of 63 cable lines), the malformed inputs, and the exact arithmetic at the edges of the stated domain (coordinates of magnitude 1e5 and
 // 2^20 that differ by 2^-60 in effect, the smallest multiples of 2^-60), with every output buffer allocated at its exact size, so
 // that a write past one is an error the sanitizer reports.  Built from mtlp_host.cpp alone:
 //   g++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -Iinclude tests/cpp/mtlp_host_check.cpp neptune_amd/csrc/mtlp_host.cpp
@@ -73,6 +73,50 @@ int main() {
     Out o(1, 2, 4);
     CHECK(nep_mtlp_solve_host(h, 1, bases, sg, o.graph.data(), o.status.data(), o.res.data(), o.path.data()) == 0);
     CHECK(o.res[0].status == 1 && o.res[0].n_path == 4 && (o.res[0].flags & NEP_MTLP_FLAG_PATH));
+    nep_mtlp_destroy(h);
+  }
+  {      // one robot: no cable line, an empty dense block; the goal lies below its cell's centre, so 2 pops spend the budget
+    const nep_mtlp_cfg c = make_cfg(1, 64, 2, 8, 0.25);
+    nep_mtlp_t* h = nep_mtlp_create(&c);
+    CHECK(h);
+    const double b1[3] = {0.5, 0.5, 0.0}, s1[6] = {1.0, 1.0, 0.5, 3.0, 3.0, 0.55};
+    Out o(1, 1, 8);
+    CHECK(nep_mtlp_solve_host(h, 1, b1, s1, o.graph.data(), o.status.data(), o.res.data(), o.path.data()) == 0);
+    CHECK(o.status[0] == 1 && o.graph[0] == 1);
+    CHECK(o.res[0].status == 0 && o.res[0].pops == 2 && o.res[0].nodes_used > 1 && o.res[0].nodes_used <= 64 && o.res[0].n_path == 0 && o.res[0].n_ball_only == 0);
+    for (int k = 0; k < 8 * 3; k++) CHECK(o.path[k] == 0.0);
+    nep_mtlp_destroy(h);
+  }
+  // ---- NEP_MTLP_MAX_ROBOTS robots on a 1/16 lattice, 2 pops each: 4 096 graph entries, and robot 0's list of cable lines is full —
+  // every later robot gives it one, 63 in all.  With a radius of 8 every one of them lies wholly inside the ball of every
+  // neighbour of robot 0's start: its n_ball_only counts 63 lines times 26 neighbours, and its list empties at the first pop
+  for (int variant = 0; variant < 2; variant++) {
+    const int n = NEP_MTLP_MAX_ROBOTS;
+    CHECK(n == 64);
+    const nep_mtlp_cfg c = make_cfg(n, 256, 2, 4, variant == 0 ? 0.25 : 8.0);
+    nep_mtlp_t* h = nep_mtlp_create(&c);
+    CHECK(h);
+    CHECK(nep_mtlp_search_bytes(h) >= (int64_t)((n - 1) * 6 * sizeof(double)));
+    std::vector<double> b((size_t)n * 3), s((size_t)n * 6);
+    uint32_t lcg = 12345u;
+    auto lat = [&lcg](int lo, int hi) { lcg = lcg * 1664525u + 1013904223u; return (double)(lo + (int)((lcg >> 8) % (uint32_t)(hi - lo + 1))) / 16.0; };
+    for (int i = 0; i < n; i++) {
+      b[3 * i] = lat(4, 60); b[3 * i + 1] = lat(4, 60); b[3 * i + 2] = 0.0;
+      s[6 * i] = lat(4, 60); s[6 * i + 1] = lat(4, 60); s[6 * i + 2] = lat(1, 15);
+      s[6 * i + 3] = lat(4, 60); s[6 * i + 4] = lat(4, 60); s[6 * i + 5] = 0.6875;
+    }
+    s[0] = 2.0; s[1] = 2.0; s[2] = 0.3125; s[5] = 0.9375;      // robot 0: cell (8, 8, 1), and no neighbour above the goal height
+    Out o(1, n, c.path_cap);
+    CHECK(nep_mtlp_solve_host(h, 1, b.data(), s.data(), o.graph.data(), o.status.data(), o.res.data(), o.path.data()) == 0);
+    CHECK(o.status[0] == 1);
+    for (int i = 0; i < n; i++) {
+      CHECK(o.graph[(size_t)i * n + i] == 1);
+      for (int j = 0; j < n; j++) CHECK(o.graph[(size_t)i * n + j] == 0 || o.graph[(size_t)i * n + j] == 1);
+      const nep_mtlp_result& r = o.res[i];
+      CHECK(r.status >= -1 && r.status <= 1 && r.pops >= 1 && r.pops <= 2 && r.nodes_used >= 1 && r.nodes_used <= 256 && r.n_path <= c.path_cap && !(r.flags & NEP_MTLP_FLAG_STATE));
+      for (int k = 3 * r.n_path; k < 3 * c.path_cap; k++) CHECK(o.path[(size_t)i * c.path_cap * 3 + k] == 0.0);
+    }
+    if (variant == 1) CHECK(o.res[0].n_ball_only == 63 * 26 && o.res[0].status == -1 && o.res[0].pops == 1 && o.res[0].nodes_used == 1);
     nep_mtlp_destroy(h);
   }
   // ---- malformed: configurations create refuses, runs outside the domain
